@@ -28,9 +28,6 @@ import subprocess
 import sys
 import time
 
-# before anything initialises HIP (torch included): one hardware queue per reactor-range stream
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-
 import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -40,6 +37,8 @@ DEFAULT_CHUNK = 50            # outer steps per work item (the library's default
 HBM_PEAK_GBS = 8000.0         # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 FP64_VECTOR_PEAK_TFLOPS = 78.6  # 256 CUs x 4 SIMDs x 16 fp64 FMA lanes/clk x 2 flop x 2.4 GHz
 PROFILE_DIR = os.path.join(ROOT, "profiles", "r3")
+DUMP_BUDGET_BYTES = 60 * 2**20  # --dump-outputs: array data per run, below 64 MB with the .npy headers
+DUMP_SAMPLE_SEED = 0x0D0D      # fixed: the same reactors are sampled on every run with the same arguments
 # BASELINE.md section 2 (survey container, 1 core of an 8-core Xeon @ 2.1 GHz): the reference cannot
 # travel to the GPU box, so its measured rate is carried as a labelled constant
 REFERENCE_PYTHON = {"value": 1.63e3, "unit": "reactor-zone-steps/s", "cores": 1,
@@ -80,6 +79,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--placement", choices=("adaptive", "identity"), default="adaptive",
                     help="adaptive (library default): reactors of similar solver cost share a wavefront, re-dealt from the "
                          "solver counters of the previous calls; identity: reactor r in slot r")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to a caller (the ensemble state "
+                         "of ReactorEnsemble.state, plus the sensor readings / register images when enabled) as "
+                         "DIR/<name>.npy in float32 / float64; above 64 MB a fixed, seeded sample of reactors "
+                         "(DIR/reactor_index.npy)")
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU rehearsal of the launcher / sharding / timing / gather logic (gloo, no HIP call, no "
                          "stepping): what tests/test_bench_launcher.py runs")
@@ -93,15 +97,20 @@ def _free_port() -> int:
         return s.getsockname()[1]
 
 
-def spawn_ranks(n_ranks: int, argv) -> int:
+def spawn_ranks(n_ranks: int, argv, dry_run: bool = False) -> int:
     """`python bench.py --gpus N` outside torch.distributed.run: start the N ranks as CHILD processes.
     Nothing in this process has touched HIP or torch.cuda yet (the parent must never re-exec after it has),
-    and it never does: it only waits for the children and passes rank 0's JSON line through."""
+    and it never does: it only waits for the children and passes rank 0's JSON line through.
+    A dry run hides the GPUs from the launcher and its ranks: torch.distributed.run asks for the device count,
+    which would start the HIP runtime (and open the GPU) in every one of those processes."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n_ranks}",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.abspath(__file__)] + list(argv)
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")   # dmabuf IPC for RCCL on this pool
     env.setdefault("OMP_NUM_THREADS", "1")
+    if dry_run:
+        env["PYTORCH_NVML_BASED_CUDA_CHECK"] = "1"   # device count from the visible-device list, without HIP
+        env["HIP_VISIBLE_DEVICES"] = ""
     proc = subprocess.run(cmd, env=env)
     return proc.returncode
 
@@ -191,6 +200,50 @@ def _profile_json(name: str):
     return None
 
 
+# --------------------------------------------------------------------------- --dump-outputs
+def timed_path_outputs(ens, sensors: bool, plant_io: bool):
+    """What a caller of the timed path receives after its last step: name -> (array, reactor axis), every array
+    float32 or float64 (integer and boolean fields widened losslessly)."""
+    s = ens.state
+    out = {k: (getattr(s, k), 0) for k in ("time", "pH", "chlorine", "temperature", "flow_rate", "H_concentration",
+                                           "density", "chlorine_decay_rate")}
+    out["status"] = (s.status.astype(np.float64), 0)
+    if sensors:
+        v, st, flt = ens.sensor_readings()
+        out["sensor_values"] = (v, 1)
+        out["sensor_status"] = (st.astype(np.float32), 1)
+        out["sensor_fault"] = (flt.astype(np.float32), 1)
+    if plant_io:
+        img, ok = ens.input_image()
+        out["plc_input_image"] = (img.astype(np.float32), 0)
+        out["plc_update_ok"] = (ok.astype(np.float32), 0)
+    return out
+
+
+def dump_rows(total: int, bytes_per_reactor: float, budget: int = DUMP_BUDGET_BYTES):
+    """None when every reactor's outputs fit the budget, else the sorted, seeded sample of reactor indices that does
+    (each sampled reactor also costs its float64 entry in reactor_index.npy)."""
+    if total * bytes_per_reactor <= budget:
+        return None
+    k = max(1, int(budget // (bytes_per_reactor + 8)))
+    return np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(total, size=k, replace=False))
+
+
+def write_outputs(directory: str, arrays, rows=None) -> int:
+    """DIR/<name>.npy for every array (and DIR/reactor_index.npy when ``rows`` samples the reactors); returns the
+    bytes of array data written."""
+    os.makedirs(directory, exist_ok=True)
+    if rows is not None:
+        arrays = dict(arrays, reactor_index=np.asarray(rows, dtype=np.float64))
+    nbytes = 0
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(directory, name + ".npy"), a)
+        nbytes += a.nbytes
+    return nbytes
+
+
 # --------------------------------------------------------------------------- one rank
 def run_rank(args) -> int:
     rank = int(os.environ.get("RANK", "0"))
@@ -259,12 +312,20 @@ def run_rank(args) -> int:
         ens.set_placement(args.placement == "adaptive")
     sched = ens.schedule() if ens is not None else {"mode": "dry-run", "streams": 0, "chunk": args.chunk, "workers": 0}
 
+    def rank_barrier():
+        # dist.barrier() looks for an accelerator first, which starts HIP; a dry run never does, so it meets on a
+        # CPU all_reduce instead
+        if dry:
+            dist.all_reduce(torch.zeros(1))
+        else:
+            dist.barrier()
+
     def barrier():
         if ens is not None:
             ens.synchronize()
             torch.cuda.synchronize()
         if use_dist:
-            dist.barrier()
+            rank_barrier()
 
     def run(k: int):
         if ens is not None and k > 0:
@@ -303,7 +364,7 @@ def run_rank(args) -> int:
     if use_dist:
         if not dry:
             torch.cuda.synchronize()
-        dist.barrier()
+        rank_barrier()
         g0 = time.perf_counter()
         final = wt.gather_state(local, world, force_collective=True, sizes=sizes)
         if not dry:
@@ -317,6 +378,26 @@ def run_rank(args) -> int:
         dist.all_reduce(flagged)
     checksum = float(final.sum())
     assert final.shape == (3, total, n), final.shape
+
+    # --dump-outputs, outside the timed region: every rank samples its own block by global reactor index, rank 0
+    # concatenates the blocks in rank (= reactor) order and writes them
+    if args.dump_outputs:
+        if ens is not None:
+            mine = timed_path_outputs(ens, args.sensors, args.plant_io)
+        else:             # dry run: nothing is stepped, the state is the initial one
+            mine = {k: (local[i].cpu().numpy(), 0) for i, k in enumerate(("pH", "chlorine", "temperature"))}
+        per_reactor = sum(a.nbytes for a, _ in mine.values()) / N
+        rows = dump_rows(total, per_reactor)
+        if rows is not None:
+            sel = rows[(rows >= lo) & (rows < hi)] - lo
+            mine = {k: (np.take(a, sel, axis=ax), ax) for k, (a, ax) in mine.items()}
+        blocks = [mine]
+        if use_dist:
+            blocks = [None] * world
+            dist.all_gather_object(blocks, mine)
+        if rank == 0:
+            arrays = {k: np.concatenate([b[k][0] for b in blocks], axis=ax) for k, (_, ax) in mine.items()}
+            write_outputs(args.dump_outputs, arrays, rows)
 
     if rank == 0:
         zone_steps = total * n * args.steps
@@ -413,7 +494,7 @@ def run_rank(args) -> int:
                 out["cpu_baseline"] = None
         print(json.dumps(out), flush=True)
     if use_dist:
-        dist.barrier()
+        rank_barrier()
         dist.destroy_process_group()
     if ens is not None:
         ens.close()
@@ -427,7 +508,7 @@ def main(argv=None) -> int:
         print("bench.py: --gpus must be >= 1", file=sys.stderr)
         return 2
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
-        return spawn_ranks(args.gpus, argv)
+        return spawn_ranks(args.gpus, argv, args.dry_run)
     return run_rank(args)
 
 

@@ -100,3 +100,34 @@ def test_eight_rank_rehearsal_of_the_baseline_configs(wt, sensors):
     cols, _ = wt.make_ensemble(100000)
     expect = 8 * float(cols["initial_pH"].sum() + cols["initial_chlorine"].sum() + cols["temperature"].sum())
     assert abs(o["state_checksum"] - expect) <= 1e-9 * abs(expect)     # the gathered block is the whole ensemble, in order
+
+
+def test_dump_outputs_two_ranks_in_reactor_order(wt, tmp_path):
+    """--dump-outputs writes the gathered outputs once, in reactor order, as float64 .npy files; the same arguments
+    write the same bytes again."""
+    for d in ("a", "b"):
+        p = _run(["--gpus", "2", "--total-reactors", "301", "--zones", "4", "--steps", "2", "--warmup", "0", "--dry-run",
+                  "--dump-outputs", str(tmp_path / d)])
+        assert p.returncode == 0, p.stderr[-2000:]
+    cols, _ = wt.make_ensemble(301)
+    for name, col in (("pH", "initial_pH"), ("chlorine", "initial_chlorine"), ("temperature", "temperature")):
+        a = np.load(tmp_path / "a" / f"{name}.npy")
+        assert a.dtype == np.float64 and a.shape == (301, 4)
+        assert np.array_equal(a, np.broadcast_to(cols[col][:, None], (301, 4)))
+        assert np.array_equal(a, np.load(tmp_path / "b" / f"{name}.npy"))
+    assert not (tmp_path / "a" / "reactor_index.npy").exists()
+
+
+def test_dump_sample_is_fixed_and_fits_the_budget(tmp_path):
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.dump_rows(10000, 200.0) is None
+    per = 3 * 20 * 8 + 4 * 8                               # 20 zones: three per-zone fields + four per-reactor ones
+    rows = bench.dump_rows(10**6, per)
+    assert rows is not None and np.array_equal(rows, bench.dump_rows(10**6, per))
+    assert np.all(np.diff(rows) > 0) and rows[0] >= 0 and rows[-1] < 10**6
+    assert len(rows) * (per + 8) <= bench.DUMP_BUDGET_BYTES < 64 * 2**20
+    arrays = {"x": np.zeros((len(rows[:10]), 3)), "s": np.zeros((7, 10), dtype=np.float32)}
+    n = bench.write_outputs(str(tmp_path), arrays, rows[:10])
+    assert n == 10 * 3 * 8 + 7 * 10 * 4 + 10 * 8
+    assert np.array_equal(np.load(tmp_path / "reactor_index.npy"), rows[:10].astype(np.float64))

@@ -47,7 +47,7 @@ def _worker(rank, world, port, q, n_total=N_TOTAL):
     full = wt.gather_state(local, world, sizes=sizes)
     if rank == 0:
         q.put(full.numpy())
-    dist.barrier()
+    dist.all_reduce(torch.zeros(1))       # barrier on the CPU: dist.barrier() would start HIP to look for a device
     dist.destroy_process_group()
 
 
