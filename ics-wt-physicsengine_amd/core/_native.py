@@ -77,6 +77,9 @@ def lib():
     L.wt_ensemble_set_state.argtypes = [vp, dp, dp, dp, dp]
     L.wt_ensemble_set_boundary.argtypes = [vp, dp]
     L.wt_ensemble_step.argtypes = [vp, C.c_double, C.c_int, C.c_int]
+    L.wt_ensemble_step_scheduled.argtypes = [vp, C.c_double, C.c_int, C.c_int, dp]
+    L.wt_ensemble_record.argtypes = [vp, C.c_int, C.c_int]
+    L.wt_ensemble_get_record.argtypes = [vp, dp, dp, dp, dp, dp, u32p, C.POINTER(C.c_int)]
     L.wt_ensemble_set_schedule.argtypes = [vp, C.c_int, C.c_int]
     ip = C.POINTER(C.c_int)
     L.wt_ensemble_get_schedule.argtypes = [vp, ip, ip, ip, ip]
@@ -134,7 +137,8 @@ def lib():
                  "wt_ensemble_export_state_device", "wt_ensemble_set_stream", "wt_ensemble_timer_start",
                  "wt_ensemble_diagnostics", "wt_ensemble_plc_enable", "wt_ensemble_plc_write_holding", "wt_ensemble_plc_read_inputs", "wt_ensemble_plc_device", "wt_ensemble_get_boundary",
                  "wt_ensemble_timer_stop", "wt_ensemble_zones", "wt_ph_solve", "wt_selftest_shuffles", "wt_ensemble_wave_diag", "wt_ensemble_set_schedule", "wt_ensemble_set_sync", "wt_ensemble_set_step_limit", "wt_ensemble_set_placement", "wt_ensemble_get_placement", "wt_ensemble_sensors_enable", "wt_ensemble_sensors_get",
-                 "wt_ensemble_sensors_history", "wt_ensemble_launch_timing", "wt_ensemble_launch_stats"):
+                 "wt_ensemble_sensors_history", "wt_ensemble_launch_timing", "wt_ensemble_launch_stats",
+                 "wt_ensemble_step_scheduled", "wt_ensemble_record", "wt_ensemble_get_record"):
         getattr(L, name).restype = C.c_int
     if L.wt_abi_version() != 1:
         raise ImportError("libwtphys.so ABI version mismatch; rebuild it")

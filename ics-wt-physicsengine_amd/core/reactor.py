@@ -150,6 +150,22 @@ class EnsembleState:
         return s
 
 
+@dataclass
+class Trajectory:
+    """Recorded states of N reactors (ReactorEnsemble.record / .trajectory): record i is what
+    ``ReactorEnsemble.state`` would have shown after outer step (i + 1) * every since recording started."""
+
+    time: np.ndarray          # (R, N)
+    pH: np.ndarray            # (R, N, n_zones)
+    chlorine: np.ndarray      # (R, N, n_zones)
+    temperature: np.ndarray   # (R, N, n_zones)
+    flow_rate: np.ndarray     # (R, N)
+    status: np.ndarray        # (R, N) uint32 status words (ST_* bits)
+
+    def __len__(self) -> int:
+        return self.time.shape[0]
+
+
 _CFG_FIELDS = [f.name for f in fields(ReactorConfiguration)]
 
 
@@ -180,6 +196,24 @@ def boundary_block(boundaries, n_reactors: int) -> np.ndarray:
             raise ValueError(f"expected {n_reactors} boundary conditions, got {len(seq)}")
         for i, name in enumerate(params.BOUNDARY_FIELDS):
             blk[i] = [getattr(b, name) for b in seq]
+    return blk
+
+
+def boundary_schedule_block(schedule, n_steps: int, n_reactors: int) -> np.ndarray:
+    """(K, NB, N) float64 block of a per-step boundary schedule: row k is the boundary of outer step k.  Takes an
+    array (K, NB, N) or a sequence of K items that :func:`boundary_block` accepts; K must equal ``n_steps``."""
+    NB = params.NB
+    if isinstance(schedule, np.ndarray):
+        blk = np.ascontiguousarray(schedule, dtype=np.float64)
+        if blk.ndim != 3 or blk.shape[1:] != (NB, n_reactors):
+            raise ValueError(f"boundary schedule must have shape (n_steps, {NB}, {n_reactors}), got {blk.shape}")
+    else:
+        rows = list(schedule)
+        blk = np.empty((len(rows), NB, n_reactors), dtype=np.float64)
+        for k, row in enumerate(rows):
+            blk[k] = boundary_block(row, n_reactors)
+    if blk.shape[0] != n_steps:
+        raise ValueError(f"boundary schedule has {blk.shape[0]} rows for n_steps = {n_steps}")
     return blk
 
 
@@ -268,8 +302,27 @@ class ReactorEnsemble:
         self._device_boundary_moved = False
 
     def step(self, dt: float, boundaries=None, n_steps: int = 1, fused: bool = True,
-             download: bool = True) -> Optional[EnsembleState]:
-        """Advance every reactor ``n_steps`` outer steps of length ``dt`` [s]."""
+             download: bool = True, boundary_schedule=None) -> Optional[EnsembleState]:
+        """Advance every reactor ``n_steps`` outer steps of length ``dt`` [s].
+
+        ``boundary_schedule``: one boundary per outer step, (n_steps, NB, N) or a sequence of n_steps items
+        :func:`boundary_block` accepts -- the same bits as ``set_boundary(S[k]); step(dt, n_steps=1)`` for every k, in
+        one fused call.  Afterwards the boundary is ``S[-1]``.  Not with ``boundaries``, not under plant I/O."""
+        if boundary_schedule is not None:
+            if boundaries is not None:
+                raise ValueError("give either boundaries or boundary_schedule, not both")
+            blk = boundary_schedule_block(boundary_schedule, int(n_steps), self.n_reactors)
+            try:
+                _native.check(_native.lib().wt_ensemble_step_scheduled(self._h, float(dt), int(n_steps), 1 if fused else 0,
+                                                                       _native.dptr(blk)))
+            except _native.WtError as e:
+                if e.code in (_native.WT_E_ARG, _native.WT_E_STATE):
+                    raise ValueError(e.message) from None
+                raise
+            if blk.shape[0] > 0:
+                self._boundary = blk[-1].copy()     # what the device's boundary block now holds
+                self._device_boundary_moved = False
+            return self.state if download else None
         if boundaries is not None:
             self.set_boundary(boundaries)
         if self._boundary is None:
@@ -283,6 +336,28 @@ class ReactorEnsemble:
         if getattr(self, "_plant_io", False):
             self._device_boundary_moved = True    # every PLC scan rewrites the device's boundary rows 0 / 4 / 6
         return self.state if download else None
+
+    def record(self, every: int = 1, capacity: int = 0) -> None:
+        """Record the state after every ``every``-th outer step of later :meth:`step` calls (scheduled or not), up to
+        ``capacity`` records; then recording stops.  ``capacity=0`` switches it off.  Calling it again restarts."""
+        try:
+            _native.check(_native.lib().wt_ensemble_record(self._h, int(every), int(capacity)))
+        except _native.WtError as e:
+            if e.code == _native.WT_E_ARG:
+                raise ValueError(e.message) from None
+            raise
+
+    def trajectory(self) -> Trajectory:
+        """The records taken since :meth:`record` (one synchronisation per call)."""
+        L = _native.lib()
+        nr = C.c_int(0)
+        _native.check(L.wt_ensemble_get_record(self._h, None, None, None, None, None, None, C.byref(nr)))
+        R, N, n = nr.value, self.n_reactors, self.n_zones
+        pH, Cl, T = np.empty((R, N, n)), np.empty((R, N, n)), np.empty((R, N, n))
+        t, flow, st = np.empty((R, N)), np.empty((R, N)), np.zeros((R, N), dtype=np.uint32)
+        _native.check(L.wt_ensemble_get_record(self._h, _native.dptr(pH), _native.dptr(Cl), _native.dptr(T), _native.dptr(t),
+                                               _native.dptr(flow), st.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(nr)))
+        return Trajectory(time=t, pH=pH, chlorine=Cl, temperature=T, flow_rate=flow, status=st)
 
     def set_schedule(self, n_streams: int = 0, chunk_steps: int = 50) -> None:
         """Advance the ensemble as ``n_streams`` contiguous reactor ranges on internal HIP

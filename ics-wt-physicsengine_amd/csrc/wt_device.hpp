@@ -291,7 +291,20 @@ struct StepArgs {
     wts::SuiteArgs sens; // fused sensor suite + plant I/O (sens.on == 0: none)
     KTab kt;             // fp64 constants of the RHS sections (scalar loads)
     RTab rt;             // ... of the solver sections
+    // Forcing and trajectory recording (wt_ensemble_step_scheduled / wt_ensemble_record), both handled in the cold
+    // end-of-outer-step section of run_item.  x_on == 0: neither (the section is one scalar load and a branch).
+    int x_on;
+    const double *sched;   // [call_steps][NB][N]: row gs is the boundary of outer step gs of the call; nullptr: bc
+    double *rec_pH, *rec_Cl, *rec_T;   // [rec_cap][N][n], nullptr: not recording in this call
+    double *rec_time, *rec_flow;       // [rec_cap][N]
+    uint32_t *rec_status;              // [rec_cap][N]
+    int rec_every, rec_cap;
+    int rec_phase, rec_slot0;  // outer steps taken since wt_ensemble_record before this call: % rec_every, / rec_every
 };
+static_assert(sizeof(StepArgs) <= 4096, "the kernel-argument segment holds at most 4 KiB");
+constexpr int NB = 10;     // rows of a boundary block (WT_NB)
+// kernels that record and reload the schedule inside a work item (n <= 32); the others take one outer step per launch
+__host__ __device__ constexpr bool x_in_item(int LV) { return LV <= 5; }
 enum { Q_AVAIL = 0, Q_HEAD = 1, Q_TAIL = 2, Q_ERROR = 3, Q_TRACE = 4, Q_DONE = 5, Q_WORDS = 16 };
 
 // ---------------------------------------------------------------- lane geometry and cross-lane moves
@@ -1881,7 +1894,9 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
         if (st & (ST_T_RANGE | ST_T_RANGE_POST)) frozen = true;
         y0[SPH] = a->pH[idx]; y0[SCL] = a->Cl[idx]; y0[STT] = a->T[idx];
         t_out = a->time[r];
-        RK k0; load_reactor(a->par, a->bc, a->N, r, n_zones, k0); mask_reactor_for_lane(L, k0);
+        // under a boundary schedule the item's first outer step integrates under its own row
+        const double *bc = a->sched ? a->sched + (int64_t)(a->first_step + step0) * NB * a->N : a->bc;
+        RK k0; load_reactor(a->par, bc, a->N, r, n_zones, k0); mask_reactor_for_lane(L, k0);
         park_reactor(ks, k0);
         if (sens_on && L.z == 0) hist0[seg] = a->sens.hist_value ? a->sens.hist_pos[r] : 0;
         if (L.z == 0) rix[seg] = (int)r;
@@ -2376,7 +2391,40 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
             }
             __syncthreads();                 // hand-off read; the next step's factors may overwrite it
         }
-        WT_STAMP(7);       // sensor suite, plant I/O
+        // The n > 32 kernel has no register to spare for this section (any fp64 store here costs it scratch): the host
+        // runs its forced / recorded calls one outer step per launch instead (x_in_item).
+        if constexpr (x_in_item(LV)) {
+          if (WT_RARE(fresh(pa)->x_on)) {
+            ArgPtr x = fresh(pa);            // ---- section: trajectory record, next row of the boundary schedule
+            const int gs = x->first_step + step0 + k;
+            if (x->rec_pH) {
+                // what wt_ensemble_get_snapshot would return now (a reactor that did not step keeps what memory holds);
+                // 32-bit arithmetic: the host folds the steps before this call into rec_phase / rec_slot0
+                const unsigned m = (unsigned)x->rec_phase + (unsigned)gs + 1u, every = (unsigned)x->rec_every;
+                const unsigned slot = (unsigned)x->rec_slot0 + m / every - 1u;
+                if (m % every == 0u && slot < (unsigned)x->rec_cap && present) {
+                    const int64_t row = (int64_t)slot * x->N;
+                    const int64_t o = row * n_zones + idx;
+                    x->rec_pH[o] = y0[SPH]; x->rec_Cl[o] = y0[SCL]; x->rec_T[o] = y0[STT];
+                    if (L.z == 0) {
+                        x->rec_time[row + r] = t_out;
+                        x->rec_flow[row + r] = steps_done > 0 ? flow_used : x->flow[r];
+                        x->rec_status[row + r] = st;
+                    }
+                }
+            }
+            if (x->sched && k + 1 < cnt) {
+                // the PLC scan's reload (above) with the next row: the next step integrates under its own boundary
+                if (present) {
+                    RK k1; load_reactor(x->par, x->sched + (int64_t)(gs + 1) * NB * x->N, x->N, r, n_zones, k1);
+                    mask_reactor_for_lane(L, k1);
+                    park_reactor(ks, k1);
+                }
+                f_valid = false;
+            }
+          }
+        }
+        WT_STAMP(7);       // sensor suite, plant I/O, forcing, recording
     }
 
     // ================= the item's results
@@ -2412,6 +2460,26 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
 #ifdef WT_STAMPS
         for (int i = 0; i < 8; ++i) atomicAdd(o + 8 + i, (unsigned long long)sec[i]);
 #endif
+    }
+}
+
+// One trajectory record from the state in memory, for the kernels that record at launch boundaries (x_in_item):
+// reactors [r0, r1), destination pointers already at the record's slot.
+struct RecordCopyArgs {
+    int64_t r0, r1; int n;
+    const double *pH, *Cl, *T, *time, *flow; const uint32_t *status;
+    double *rec_pH, *rec_Cl, *rec_T, *rec_time, *rec_flow; uint32_t *rec_status;
+};
+__global__ __launch_bounds__(256) void record_copy_kernel(const RecordCopyArgs a)
+{
+    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;   // grid: (r1 - r0) * n threads
+    if (j < (a.r1 - a.r0) * a.n) {
+        const int64_t i = a.r0 * a.n + j;
+        a.rec_pH[i] = a.pH[i]; a.rec_Cl[i] = a.Cl[i]; a.rec_T[i] = a.T[i];
+    }
+    if (j < a.r1 - a.r0) {
+        const int64_t r = a.r0 + j;
+        a.rec_time[r] = a.time[r]; a.rec_flow[r] = a.flow[r]; a.rec_status[r] = a.status[r];
     }
 }
 

@@ -100,9 +100,20 @@ struct wt_ensemble {
     bool time_launches = false;
     std::vector<hipEvent_t> lt_pool;   // start/stop pairs
     size_t lt_used = 0;
+    // boundary schedule of wt_ensemble_step_scheduled ([n_steps][WT_NB][N], grown on demand); call_sched is set
+    // only while such a call queues its launches
+    double *sched = nullptr; size_t sched_bytes = 0; const double *call_sched = nullptr;
+    // trajectory records of wt_ensemble_record: [rec_cap][N][n] / [rec_cap][N]; rec_steps = outer steps since then
+    double *rec_pH = nullptr, *rec_Cl = nullptr, *rec_T = nullptr, *rec_time = nullptr, *rec_flow = nullptr;
+    uint32_t *rec_status = nullptr;
+    int rec_every = 1, rec_cap = 0;
+    int64_t rec_steps = 0;
 };
 
 namespace {
+
+// recording is on and has free slots (afterwards the launches carry no record pointers at all)
+bool recording_open(const wt_ensemble *h) { return h->rec_pH && h->rec_steps / h->rec_every < h->rec_cap; }
 
 wt::StepArgs make_args(const wt_ensemble *h, double dt, int n_steps, int first_step, int call_steps, int scan_every)
 {
@@ -130,6 +141,14 @@ wt::StepArgs make_args(const wt_ensemble *h, double dt, int n_steps, int first_s
     s.hist_cap = h->s_hist_cap; s.hist_pos = h->s_hist_pos;
     s.pack.loop_time = h->p_loop_time; s.pack.ir = h->p_ir; s.pack.update_ok = h->p_update_ok;
     s.cmd.N = h->N; s.cmd.hr = h->p_hr; s.cmd.bc = h->bc;
+    a.sched = h->call_sched;
+    const bool rec = recording_open(h);
+    a.rec_pH = rec ? h->rec_pH : nullptr; a.rec_Cl = h->rec_Cl; a.rec_T = h->rec_T;
+    a.rec_time = h->rec_time; a.rec_flow = h->rec_flow; a.rec_status = h->rec_status;
+    a.rec_every = h->rec_every; a.rec_cap = h->rec_cap;
+    a.rec_phase = rec ? (int)(h->rec_steps % h->rec_every) : 0;
+    a.rec_slot0 = rec ? (int)(h->rec_steps / h->rec_every) : 0;
+    a.x_on = (a.sched || a.rec_pH) ? 1 : 0;
     return a;
 }
 
@@ -143,6 +162,13 @@ void release_sensor_buffers(wt_ensemble *h)
     free_and_null(h->s_out_status); free_and_null(h->s_out_fault);
     free_and_null(h->s_hist_status); free_and_null(h->s_hist_fault);
     h->s_hist_cap = 0; h->sensors_on = false;
+}
+
+void release_record_buffers(wt_ensemble *h)
+{
+    free_and_null(h->rec_pH); free_and_null(h->rec_Cl); free_and_null(h->rec_T);
+    free_and_null(h->rec_time); free_and_null(h->rec_flow); free_and_null(h->rec_status);
+    h->rec_cap = 0; h->rec_every = 1; h->rec_steps = 0;
 }
 
 void release_plc_buffers(wt_ensemble *h)
@@ -375,6 +401,8 @@ int wt_ensemble_destroy(wt_ensemble *h)
         if (h->sub_stream[s]) { (void)hipStreamSynchronize(h->sub_stream[s]); (void)hipStreamDestroy(h->sub_stream[s]); }
         if (h->sub_done[s]) (void)hipEventDestroy(h->sub_done[s]);
     }
+    release_record_buffers(h);
+    if (h->sched) (void)hipFree(h->sched);
     void *sp[] = {h->s_fs, h->s_full_scale, h->s_ring_t, h->s_ring_v, h->s_out_value, h->s_hist_value, h->s_ds, h->s_t_enable, h->s_is,
                   h->s_ring_head, h->s_ring_cnt, h->s_hist_pos, h->s_out_status, h->s_out_fault, h->s_hist_status,
                   h->s_hist_fault, h->p_ir, h->p_hr, h->p_loop_time, h->p_update_ok, h->diag_out};
@@ -430,16 +458,16 @@ int wt_ensemble_set_boundary(wt_ensemble *h, const double *bc)
     return WT_OK;
 }
 
-int wt_ensemble_step(wt_ensemble *h, double dt, int n_steps, int fused)
+} // extern "C"
+
+namespace {
+
+// Steps [first, first + n_steps) of a call of `total` outer steps (first > 0 only where a forced / recorded call runs
+// one outer step per launch, see run_steps): the launches of the schedule in force, queued on the handle's stream.
+int queue_steps(wt_ensemble *h, double dt, int n_steps, int fused, int first, int total)
 {
-    if (!h) return fail(WT_E_ARG, "NULL handle");
-    if (!h->have_state || !h->have_bc) return fail(WT_E_STATE, "set_state and set_boundary must precede step");
-    if (!(dt > 0)) return fail(WT_E_ARG, "`max_step` must be positive."); // scipy validate_max_step (reactor.py:480)
-    if (n_steps < 0) return fail(WT_E_ARG, "n_steps must be >= 0");
-    if (n_steps == 0) return WT_OK;
-    HIP_TRY(hipSetDevice(h->device));
     // chunk_steps: PLC scan interval; under the stream schedule also the launch length
-    const int chunk = fused ? (h->chunk_steps > 0 ? h->chunk_steps : n_steps) : 1;
+    const int chunk = fused ? (h->chunk_steps > 0 ? h->chunk_steps : total) : 1;
     if (h->wave_diag)
         HIP_TRY(hipMemsetAsync(h->wave_diag, 0, sizeof(int64_t) * wt::WT_DIAG_SLOTS * (size_t)h->n_groups, h->stream));
     // (the stream schedule feeds the cost history too; only the queue schedule re-deals)
@@ -468,7 +496,7 @@ int wt_ensemble_step(wt_ensemble *h, double dt, int n_steps, int fused)
             // every group has a worker of its own: nothing to hand over, so no queue -- one plain launch in which
             // workgroup g advances group g by the whole call (the drop-in's N = 1 lives here: one kernel per step())
             redeal();
-            const wt::StepArgs a = make_args(h, dt, n_steps, 0, n_steps, chunk);
+            const wt::StepArgs a = make_args(h, dt, n_steps, first, total, chunk);
             launch_step(h, a, (unsigned)h->n_groups, h->stream);
             if (h->placement == WT_PLACE_ADAPTIVE) h->cost_steps += n_steps;
             HIP_TRY(hipGetLastError());
@@ -477,7 +505,7 @@ int wt_ensemble_step(wt_ensemble *h, double dt, int n_steps, int fused)
         for (int64_t done = 0; done < n_steps; done += per_launch) {
             const int cnt = (int)((n_steps - done < per_launch) ? n_steps - done : per_launch);
             redeal();
-            wt::StepArgs a = make_args(h, dt, cnt, (int)done, n_steps, chunk);
+            wt::StepArgs a = make_args(h, dt, cnt, first + (int)done, total, chunk);
             a.q_ctrl = h->q_ctrl; a.q_slots = h->q_slots; a.q_next = h->q_next; a.q_cap = h->q_cap; a.item_steps = item;
             wt::QueueResetArgs qr{h->q_ctrl, h->q_slots, h->q_next, (int)h->n_groups, h->q_cap};
             hipLaunchKernelGGL(wt::queue_reset_kernel, dim3((unsigned)((h->q_cap + 255) / 256)), dim3(256), 0, h->stream, qr);
@@ -492,7 +520,7 @@ int wt_ensemble_step(wt_ensemble *h, double dt, int n_steps, int fused)
     const int S = h->n_sub;
     if (S <= 1) {
         for (int done = 0; done < n_steps; done += chunk) {
-            const wt::StepArgs a = make_args(h, dt, (n_steps - done < chunk) ? n_steps - done : chunk, done, n_steps, chunk);
+            const wt::StepArgs a = make_args(h, dt, (n_steps - done < chunk) ? n_steps - done : chunk, first + done, total, chunk);
             launch_step(h, a, (unsigned)h->n_groups, h->stream);
         }
         HIP_TRY(hipGetLastError());
@@ -509,7 +537,7 @@ int wt_ensemble_step(wt_ensemble *h, double dt, int n_steps, int fused)
     for (int s = 0; s < S; ++s) HIP_TRY(hipStreamWaitEvent(h->sub_stream[s], h->ev_fork, 0));
     const int64_t groups = h->n_groups;   // wavefront-sized groups of reactors
     for (int done = 0; done < n_steps; done += chunk) {
-        wt::StepArgs a = make_args(h, dt, (n_steps - done < chunk) ? n_steps - done : chunk, done, n_steps, chunk);
+        wt::StepArgs a = make_args(h, dt, (n_steps - done < chunk) ? n_steps - done : chunk, first + done, total, chunk);
         for (int s = 0; s < S; ++s) {
             const int64_t g0 = groups * s / S, g1 = groups * (s + 1) / S;
             a.r0 = g0 * h->R; a.r1 = (g1 * h->R < h->N) ? g1 * h->R : h->N;
@@ -522,6 +550,130 @@ int wt_ensemble_step(wt_ensemble *h, double dt, int n_steps, int fused)
         HIP_TRY(hipEventRecord(h->sub_done[s], h->sub_stream[s]));
         HIP_TRY(hipStreamWaitEvent(h->stream, h->sub_done[s], 0));
     }
+    return WT_OK;
+}
+
+// A step call: the launches, trajectory records where the kernel does not write them itself, the record count.
+int run_steps(wt_ensemble *h, double dt, int n_steps, int fused)
+{
+    const bool rec = recording_open(h);
+    int rc = WT_OK;
+    if ((h->call_sched || rec) && !wt::x_in_item(levels_for(h->n))) {
+        // the n > 32 kernel neither reloads the schedule nor records inside a work item: one outer step per launch
+        // (each starts from its own schedule row), a record copied from the state in memory after the steps that want one
+        for (int s = 0; s < n_steps && rc == WT_OK; ++s) {
+            rc = queue_steps(h, dt, 1, fused, s, n_steps);
+            const int64_t m = h->rec_steps + s + 1;
+            if (rc == WT_OK && rec && m % h->rec_every == 0 && m / h->rec_every <= h->rec_cap) {
+                const int64_t o = (m / h->rec_every - 1) * h->N;
+                const wt::RecordCopyArgs ca{0, h->N, h->n, h->pH, h->Cl, h->T, h->time, h->flow, h->status,
+                                            h->rec_pH + o * h->n, h->rec_Cl + o * h->n, h->rec_T + o * h->n,
+                                            h->rec_time + o, h->rec_flow + o, h->rec_status + o};
+                const int64_t cnt = h->N * h->n;
+                hipLaunchKernelGGL(wt::record_copy_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, h->stream, ca);
+                HIP_TRY(hipGetLastError());
+            }
+        }
+    } else {
+        rc = queue_steps(h, dt, n_steps, fused, 0, n_steps);
+    }
+    if (rc == WT_OK && h->rec_pH) h->rec_steps += n_steps;
+    return rc;
+}
+
+} // namespace
+
+extern "C" {
+
+int wt_ensemble_step(wt_ensemble *h, double dt, int n_steps, int fused)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    if (!h->have_state || !h->have_bc) return fail(WT_E_STATE, "set_state and set_boundary must precede step");
+    if (!(dt > 0)) return fail(WT_E_ARG, "`max_step` must be positive."); // scipy validate_max_step (reactor.py:480)
+    if (n_steps < 0) return fail(WT_E_ARG, "n_steps must be >= 0");
+    if (n_steps == 0) return WT_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    return run_steps(h, dt, n_steps, fused);
+}
+
+int wt_ensemble_step_scheduled(wt_ensemble *h, double dt, int n_steps, int fused, const double *bc_schedule)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    if (!bc_schedule) return fail(WT_E_ARG, "bc_schedule is NULL");
+    if (h->plc_on) return fail(WT_E_STATE, "a boundary schedule cannot be combined with plant I/O (the command path owns the boundary)");
+    if (!h->have_state) return fail(WT_E_STATE, "set_state must precede step");
+    if (!(dt > 0)) return fail(WT_E_ARG, "`max_step` must be positive."); // scipy validate_max_step (reactor.py:480)
+    if (n_steps < 0) return fail(WT_E_ARG, "n_steps must be >= 0");
+    if (n_steps == 0) return WT_OK;
+    int64_t row = 0, bytes = 0;
+    if (__builtin_mul_overflow((int64_t)WT_NB, h->N, &row) || __builtin_mul_overflow(row, (int64_t)n_steps, &bytes) ||
+        __builtin_mul_overflow(bytes, (int64_t)sizeof(double), &bytes))
+        return fail(WT_E_ARG, "boundary schedule size overflows int64");
+    HIP_TRY(hipSetDevice(h->device));
+    if ((size_t)bytes > h->sched_bytes) {    // grown here, never inside the launch path
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        free_and_null(h->sched); h->sched_bytes = 0;
+        HIP_TRY(hipMalloc((void **)&h->sched, (size_t)bytes));
+        h->sched_bytes = (size_t)bytes;
+    }
+    // ordered after the launches of an earlier call that still read the buffer; the caller's array is free on return
+    HIP_TRY(hipMemcpyAsync(h->sched, bc_schedule, (size_t)bytes, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->call_sched = h->sched;
+    const int rc = run_steps(h, dt, n_steps, fused);
+    h->call_sched = nullptr;
+    if (rc != WT_OK) return rc;
+    // the boundary block is the last row from now on (get_boundary, rhs, later plain step calls)
+    HIP_TRY(hipMemcpyAsync(h->bc, h->sched + (size_t)(n_steps - 1) * (size_t)row, sizeof(double) * (size_t)row,
+                           hipMemcpyDeviceToDevice, h->stream));
+    h->have_bc = true;
+    return WT_OK;
+}
+
+int wt_ensemble_record(wt_ensemble *h, int every, int capacity)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    if (every < 1) return fail(WT_E_ARG, "every must be >= 1");
+    if (capacity < 0) return fail(WT_E_ARG, "capacity must be >= 0 (0 = recording off)");
+    int64_t per = 0, zone = 0;
+    if (__builtin_mul_overflow((int64_t)capacity, h->N, &per) || __builtin_mul_overflow(per, (int64_t)h->n, &zone) ||
+        __builtin_mul_overflow(zone, (int64_t)sizeof(double), &zone) || __builtin_mul_overflow(per, (int64_t)sizeof(double), &per))
+        return fail(WT_E_ARG, "record size overflows int64");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still write the old records
+    release_record_buffers(h);
+    if (capacity == 0) return WT_OK;
+    hipError_t e = hipMalloc((void **)&h->rec_pH, (size_t)zone);
+    if (e == hipSuccess) e = hipMalloc((void **)&h->rec_Cl, (size_t)zone);
+    if (e == hipSuccess) e = hipMalloc((void **)&h->rec_T, (size_t)zone);
+    if (e == hipSuccess) e = hipMalloc((void **)&h->rec_time, (size_t)per);
+    if (e == hipSuccess) e = hipMalloc((void **)&h->rec_flow, (size_t)per);
+    if (e == hipSuccess) e = hipMalloc((void **)&h->rec_status, (size_t)per / 2);
+    if (e != hipSuccess) { release_record_buffers(h); return fail(WT_E_HIP, std::string("record: ") + hipGetErrorString(e)); }
+    h->rec_every = every; h->rec_cap = capacity; h->rec_steps = 0;
+    return WT_OK;
+}
+
+int wt_ensemble_get_record(wt_ensemble *h, double *pH, double *Cl, double *T, double *time, double *flow,
+                           uint32_t *status, int *n_records)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    if (!h->rec_pH) return fail(WT_E_STATE, "recording is off (wt_ensemble_record)");
+    HIP_TRY(hipSetDevice(h->device));
+    const int64_t done = h->rec_steps / h->rec_every;
+    const int64_t nr = done < h->rec_cap ? done : h->rec_cap;
+    const size_t per = (size_t)nr * (size_t)h->N, zone = per * (size_t)h->n;
+    if (n_records) *n_records = (int)nr;
+    if (nr > 0) {
+        if (pH) HIP_TRY(hipMemcpyAsync(pH, h->rec_pH, sizeof(double) * zone, hipMemcpyDeviceToHost, h->stream));
+        if (Cl) HIP_TRY(hipMemcpyAsync(Cl, h->rec_Cl, sizeof(double) * zone, hipMemcpyDeviceToHost, h->stream));
+        if (T) HIP_TRY(hipMemcpyAsync(T, h->rec_T, sizeof(double) * zone, hipMemcpyDeviceToHost, h->stream));
+        if (time) HIP_TRY(hipMemcpyAsync(time, h->rec_time, sizeof(double) * per, hipMemcpyDeviceToHost, h->stream));
+        if (flow) HIP_TRY(hipMemcpyAsync(flow, h->rec_flow, sizeof(double) * per, hipMemcpyDeviceToHost, h->stream));
+        if (status) HIP_TRY(hipMemcpyAsync(status, h->rec_status, sizeof(uint32_t) * per, hipMemcpyDeviceToHost, h->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (h->err_host[0] | h->err_host[1]) return fail(WT_E_HIP, k_incomplete);
     return WT_OK;
 }
 

@@ -101,8 +101,27 @@ int wt_ensemble_set_boundary(wt_ensemble *h, const double *bc);
  * before other work on the handle's stream.  The boundary is held constant unless plant I/O is on (then the
  * command path rewrites it at every PLC scan).  fused == 0 makes every outer step a PLC scan, as the reference's
  * loop does; otherwise a scan happens every chunk_steps outer steps and at the end of the call.  Results do not
- * depend on the schedule (tests assert bitwise equality). */
+ * depend on the schedule (tests assert bitwise equality).  A time series of boundaries goes through
+ * wt_ensemble_step_scheduled. */
 int wt_ensemble_step(wt_ensemble *h, double dt, int n_steps, int fused);
+/* IntegratedCSTR.step(dt, bc_schedule[k]) for k = 0 .. n_steps-1: row k (host [n_steps][WT_NB][N]) is the boundary of
+ * outer step k of this call (open-loop forcing: dosing pulses, inlet ramps, flow steps).  Same schedules, fused semantics
+ * and results as n_steps calls of wt_ensemble_set_boundary(row k) + wt_ensemble_step(h, dt, 1, fused), bit for bit.
+ * The rows are uploaded into a device buffer of the handle (grown on demand) and the call synchronises the stream before
+ * its launches.  Afterwards the handle's boundary block is row n_steps-1 (wt_ensemble_get_boundary, wt_ensemble_rhs and
+ * later wt_ensemble_step calls see it).  WT_E_STATE while plant I/O is on (the command path owns the boundary). */
+int wt_ensemble_step_scheduled(wt_ensemble *h, double dt, int n_steps, int fused, const double *bc_schedule);
+/* Trajectory recording.  From this call on, the state after every `every`-th outer step of later step calls (scheduled
+ * or not) goes into record i = (steps since this call) / every - 1, for i < capacity; after that, recording stops.
+ * A record holds what wt_ensemble_get_snapshot would have returned after that outer step: state, time, flow and the
+ * status word (a stopped reactor keeps its frozen state and time, its status shows why).  Records are indexed by
+ * reactor, whatever the placement.  capacity == 0 switches recording off and frees the buffers; calling it again
+ * restarts the count.  Synchronises the stream. */
+int wt_ensemble_record(wt_ensemble *h, int every, int capacity);
+/* records [n_records][N][n] (pH, Cl, T), [n_records][N] (time, flow, status); any pointer may be NULL; synchronises.
+ * n_records = min(capacity, steps since wt_ensemble_record / every).  WT_E_STATE when recording is off. */
+int wt_ensemble_get_record(wt_ensemble *h, double *pH, double *Cl, double *T, double *time, double *flow,
+                           uint32_t *status, int *n_records);
 /* Schedule.  n_streams == 0 (default), WT_SCHED_QUEUE: one kernel launch per call; worker wavefronts take
  * (wavefront-group, next few outer steps) work items from a device-side FIFO, so no wavefront ever waits for a
  * launch boundary and a scan per outer step costs no launch.  n_streams >= 1, WT_SCHED_STREAMS (the round-1
