@@ -1,0 +1,138 @@
+"""Per-reactor PI dosing programs that run on the device at every PLC scan (include/wtphys.h,
+``wt_ensemble_control_*``).
+
+They stand in for the master side of the reference's loop (``__main__.py:227-271``): what a Modbus master computes
+from the input image and writes into the holding registers between two scans.  Loop 0 doses chlorine (holding words
+2-3), loop 1 acid (words 0-1).  This module only builds and checks the parameter block and unpacks the state; the
+update itself runs in ``csrc/wt_ctl.hpp``.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Optional, Union
+
+import numpy as np
+
+LOOPS = ("chlorine", "acid")            # loop index order of the blocks
+NC, NCS = 9, 8                          # WT_NC, WT_NCS
+PARAM_ROWS = ("enable", "sensor", "direction", "setpoint", "kp", "ki", "bias", "out_min", "out_max")
+STATE_ROWS = ("integral", "output", "ise", "iae", "dose", "n_exec", "n_held", "n_sat")
+SENSOR_NAMES = ("pH_inlet", "pH_outlet", "chlorine_inlet", "chlorine_outlet", "flow_main", "temp_inlet", "temp_outlet")
+HOLDING_WORD = {"chlorine": 2, "acid": 0}    # first holding word of each loop's float32 output
+COMMAND_LIMIT = {"chlorine": 1.0, "acid": 2.0}   # validate_flow_rate's maxima (__main__.py:57-63, :236-242)
+
+Scalar = Union[float, int, np.ndarray]
+
+
+@dataclass
+class PILoop:
+    """One PI loop's parameters; every field takes a scalar or an (N,) array.  ``sensor`` is a name of
+    :data:`SENSOR_NAMES` or its index.  ``direction`` +1 (direct: output rises while the reading is below the
+    setpoint) or -1 (reverse).  ``ki`` is per second.  ``out_max=None`` is the actuator's command limit."""
+
+    sensor: Union[str, int, np.ndarray]
+    setpoint: Scalar
+    kp: Scalar = 0.0
+    ki: Scalar = 0.0
+    direction: Scalar = 1
+    bias: Scalar = 0.0
+    out_min: Scalar = 0.0
+    out_max: Optional[Scalar] = None
+    enable: Scalar = 1
+
+
+@dataclass
+class LoopState:
+    """State of one loop, (N,) float64 each (counts are whole numbers)."""
+
+    integral: np.ndarray
+    output: np.ndarray
+    ise: np.ndarray        # integral of e^2 dt over the executed scans
+    iae: np.ndarray        # integral of |e| dt
+    dose: np.ndarray       # integral of the output dt
+    n_exec: np.ndarray
+    n_held: np.ndarray     # scans without a valid reading (not finite, or a sensor fault)
+    n_sat: np.ndarray      # executed scans whose output was clamped
+
+
+@dataclass
+class ControlState:
+    """``ReactorEnsemble.control_state()``: one :class:`LoopState` per loop, indexed by reactor."""
+
+    chlorine: LoopState
+    acid: LoopState
+
+    @classmethod
+    def from_block(cls, block: np.ndarray) -> "ControlState":
+        """From a [WT_CTL_LOOPS][WT_NCS][N] block."""
+        return cls(*(LoopState(*(np.array(block[l, k]) for k in range(NCS))) for l in range(len(LOOPS))))
+
+    def block(self) -> np.ndarray:
+        """The (2, NCS, N) block again."""
+        return np.stack([np.stack([getattr(getattr(self, loop), k) for k in STATE_ROWS]) for loop in LOOPS])
+
+
+def sensor_index(sensor) -> np.ndarray:
+    """Sensor names or indices -> float64 indices (validity is checked by :func:`control_block`)."""
+    if isinstance(sensor, str):
+        if sensor not in SENSOR_NAMES:
+            raise ValueError(f"unknown sensor {sensor!r}: one of {SENSOR_NAMES}")
+        return np.float64(SENSOR_NAMES.index(sensor))
+    a = np.asarray(sensor)
+    if a.dtype.kind in "US":
+        bad = [s for s in a.ravel() if str(s) not in SENSOR_NAMES]
+        if bad:
+            raise ValueError(f"unknown sensor {bad[0]!r}: one of {SENSOR_NAMES}")
+        return np.vectorize(lambda s: float(SENSOR_NAMES.index(str(s))), otypes=[np.float64])(a)
+    return a.astype(np.float64)
+
+
+def _off_rows(n: int) -> np.ndarray:
+    rows = np.zeros((NC, n))
+    rows[PARAM_ROWS.index("direction")] = 1.0
+    return rows
+
+
+def loop_rows(loop: Optional[PILoop], name: str, n: int) -> np.ndarray:
+    """(NC, N) rows of one loop; ``None`` or ``False`` is a disabled loop."""
+    if loop is None or loop is False:
+        return _off_rows(n)
+    if not isinstance(loop, PILoop):
+        raise TypeError(f"{name}: expected a PILoop, got {type(loop).__name__}")
+    vals = {k: getattr(loop, k) for k in PARAM_ROWS}
+    if vals["out_max"] is None:
+        vals["out_max"] = COMMAND_LIMIT[name]
+    vals["sensor"] = sensor_index(vals["sensor"])
+    rows = np.empty((NC, n))
+    for i, k in enumerate(PARAM_ROWS):
+        try:
+            rows[i] = np.broadcast_to(np.asarray(vals[k], dtype=np.float64), (n,))
+        except ValueError:
+            raise ValueError(f"{name}.{k}: expected a scalar or ({n},) values, got shape {np.shape(vals[k])}") from None
+    return rows
+
+
+def validate_block(block: np.ndarray) -> None:
+    """The checks ``wt_ensemble_control_enable`` makes; ``ValueError`` names the first one that fails."""
+    if not np.all(np.isfinite(block)):
+        raise ValueError("control parameters must be finite")
+    p = {k: block[:, i] for i, k in enumerate(PARAM_ROWS)}
+    if not np.all((p["enable"] == 0) | (p["enable"] == 1)):
+        raise ValueError("enable must be 0 or 1")
+    s = p["sensor"]
+    if not np.all((s == np.floor(s)) & (s >= 0) & (s < len(SENSOR_NAMES))):
+        raise ValueError("sensor must be an integer in 0..6")
+    if not np.all(np.abs(p["direction"]) == 1):
+        raise ValueError("direction must be +1 or -1")
+    if not np.all((p["kp"] >= 0) & (p["ki"] >= 0)):
+        raise ValueError("kp and ki must be >= 0")
+    if not np.all(p["out_min"] <= p["out_max"]):
+        raise ValueError("out_min must not exceed out_max")
+
+
+def control_block(n_reactors: int, chlorine: Optional[PILoop] = None, acid: Optional[PILoop] = None) -> np.ndarray:
+    """The [WT_CTL_LOOPS][WT_NC][N] float64 parameter block of ``wt_ensemble_control_enable``, validated."""
+    n = int(n_reactors)
+    block = np.ascontiguousarray(np.stack([loop_rows(chlorine, "chlorine", n), loop_rows(acid, "acid", n)]))
+    validate_block(block)
+    return block

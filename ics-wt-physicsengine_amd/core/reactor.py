@@ -18,7 +18,7 @@ from typing import Dict, Iterable, List, Optional, Sequence, Union
 
 import numpy as np
 
-from . import _native, params
+from . import _native, control, params
 
 logger = logging.getLogger(__name__)
 
@@ -272,6 +272,7 @@ class ReactorEnsemble:
         self._boundary: Optional[np.ndarray] = None
         self._device_boundary_moved = False     # the command path (plant I/O) rewrites the device's boundary block
         self._plant_io = False
+        self._control_params: Optional[np.ndarray] = None   # the last block enable_control / retune_control sent
 
     # -- lifetime
     def close(self) -> None:
@@ -561,6 +562,49 @@ class ReactorEnsemble:
         out = np.empty((len(params.BOUNDARY_FIELDS), self.n_reactors), dtype=np.float64)
         _native.check(_native.lib().wt_ensemble_get_boundary(self._h, _native.dptr(out)))
         return out
+
+    # -- PI dosing programs at every PLC scan, on the device (wt_ctl.hpp)
+    def _control_call(self, fn, *args) -> None:
+        try:
+            _native.check(fn(self._h, *args))
+        except _native.WtError as e:
+            if e.code in (_native.WT_E_ARG, _native.WT_E_STATE):
+                raise ValueError(e.message) from None
+            raise
+
+    def enable_control(self, chlorine: Optional["control.PILoop"] = None, acid: Optional["control.PILoop"] = None) -> None:
+        """Run up to two PI loops per reactor at every PLC scan, inside the step call: ``chlorine`` writes the
+        chlorine_flow_rate holding register, ``acid`` the acid_flow_rate one; a loop left out stays off and its
+        register free for :meth:`write_commands`.  Each enabled loop starts with integral 0 and output
+        ``clip(bias, out_min, out_max)``.  The output acts from the next scan on, exactly as a host master writing
+        between two calls of one scan interval would.  Needs :meth:`enable_plant_io`."""
+        blk = control.control_block(self.n_reactors, chlorine, acid)
+        self._control_call(_native.lib().wt_ensemble_control_enable, _native.dptr(blk))
+        self._control_params = blk
+
+    def retune_control(self, chlorine=None, acid=None) -> None:
+        """New parameters for running loops: a :class:`PILoop` replaces a loop's parameters, ``None`` keeps them,
+        ``False`` switches the loop off.  Integral, output and metrics stay; a loop switched on starts as at enable."""
+        old = getattr(self, "_control_params", None)
+        if old is None:
+            raise ValueError("control is off (enable_control)")
+        rows = [old[i] if loop is None else control.loop_rows(loop, name, self.n_reactors)
+                for i, (name, loop) in enumerate(zip(control.LOOPS, (chlorine, acid)))]
+        blk = np.ascontiguousarray(np.stack(rows))
+        control.validate_block(blk)
+        self._control_call(_native.lib().wt_ensemble_control_retune, _native.dptr(blk))
+        self._control_params = blk
+
+    def disable_control(self) -> None:
+        """Stop the PI programs; the holding registers keep their last outputs."""
+        self._control_call(_native.lib().wt_ensemble_control_disable)
+        self._control_params = None
+
+    def control_state(self) -> "control.ControlState":
+        """Integral, output and metrics of both loops by reactor (one synchronisation)."""
+        blk = np.empty((len(control.LOOPS), control.NCS, self.n_reactors), dtype=np.float64)
+        self._control_call(_native.lib().wt_ensemble_control_get, _native.dptr(blk))
+        return control.ControlState.from_block(blk)
 
     # -- diagnostics (NEXT-4)
     DIAGNOSTIC_FIELDS = ("total_chlorine_mg", "total_H_mol", "total_OH_mol", "charge_balance_mol", "thermal_energy_kJ",

@@ -37,6 +37,7 @@
 #include <stdint.h>
 #include <type_traits>
 #include "wt_sensors.hpp"
+#include "wt_ctl.hpp"
 
 namespace wt {
 
@@ -300,6 +301,7 @@ struct StepArgs {
     uint32_t *rec_status;              // [rec_cap][N]
     int rec_every, rec_cap;
     int rec_phase, rec_slot0;  // outer steps taken since wt_ensemble_record before this call: % rec_every, / rec_every
+    wtc::CtlArgs ctl;    // per-reactor PI programs run at PLC scans (wt_ensemble_control_*; ctl.on == 0: none)
 };
 static_assert(sizeof(StepArgs) <= 4096, "the kernel-argument segment holds at most 4 KiB");
 constexpr int NB = 10;     // rows of a boundary block (WT_NB)
@@ -2379,6 +2381,13 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
                         io.cmd[0][lane] = c[0]; io.cmd[1][lane] = c[1]; io.cmd[2][lane] = c[2];
                     }
                     b->sens.pack.loop_time[rr] = lt + dt;                 // sim_time += dt (__main__.py:446)
+                }
+                // the PLC program, after the scan's command path: its commands act from the next scan on, like a host
+                // master's between two calls; t_now is the loop time just stored
+                if (scan && WT_RARE(fresh(pa)->ctl.on) && lane < R && io.stepped[lane]) {
+                    ArgPtr cp = fresh(pa);
+                    const int64_t rr = rix[lane];
+                    wtc::pi_execute(cp->ctl, rr, &io.val[0][lane], &io.fault[0][lane], wts::RMAX, cp->sens.pack.loop_time[rr]);
                 }
                 if (scan) {
                     __syncthreads();

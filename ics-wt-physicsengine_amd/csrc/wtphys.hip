@@ -108,6 +108,9 @@ struct wt_ensemble {
     uint32_t *rec_status = nullptr;
     int rec_every = 1, rec_cap = 0;
     int64_t rec_steps = 0;
+    // optional per-reactor PI programs (wt_ctl.hpp), indexed by reactor: parameter records and state
+    bool ctl_on = false;
+    double *c_par = nullptr, *c_st = nullptr;   // [N][wtc::PAR_DOUBLES], [N][wtc::ST_DOUBLES]
 };
 
 namespace {
@@ -149,6 +152,7 @@ wt::StepArgs make_args(const wt_ensemble *h, double dt, int n_steps, int first_s
     a.rec_phase = rec ? (int)(h->rec_steps % h->rec_every) : 0;
     a.rec_slot0 = rec ? (int)(h->rec_steps / h->rec_every) : 0;
     a.x_on = (a.sched || a.rec_pH) ? 1 : 0;
+    a.ctl.on = h->ctl_on ? 1 : 0; a.ctl.par = h->c_par; a.ctl.st = h->c_st; a.ctl.hr = h->p_hr;
     return a;
 }
 
@@ -169,6 +173,12 @@ void release_record_buffers(wt_ensemble *h)
     free_and_null(h->rec_pH); free_and_null(h->rec_Cl); free_and_null(h->rec_T);
     free_and_null(h->rec_time); free_and_null(h->rec_flow); free_and_null(h->rec_status);
     h->rec_cap = 0; h->rec_every = 1; h->rec_steps = 0;
+}
+
+void release_control_buffers(wt_ensemble *h)
+{
+    free_and_null(h->c_par); free_and_null(h->c_st);
+    h->ctl_on = false;
 }
 
 void release_plc_buffers(wt_ensemble *h)
@@ -402,6 +412,7 @@ int wt_ensemble_destroy(wt_ensemble *h)
         if (h->sub_done[s]) (void)hipEventDestroy(h->sub_done[s]);
     }
     release_record_buffers(h);
+    release_control_buffers(h);
     if (h->sched) (void)hipFree(h->sched);
     void *sp[] = {h->s_fs, h->s_full_scale, h->s_ring_t, h->s_ring_v, h->s_out_value, h->s_hist_value, h->s_ds, h->s_t_enable, h->s_is,
                   h->s_ring_head, h->s_ring_cnt, h->s_hist_pos, h->s_out_status, h->s_out_fault, h->s_hist_status,
@@ -846,6 +857,128 @@ int wt_ensemble_plc_device(wt_ensemble *h, void **input_image, void **holding_im
     if (!h->plc_on) return fail(WT_E_STATE, "plant I/O not enabled");
     if (input_image) *input_image = h->p_ir;
     if (holding_image) *holding_image = h->p_hr;
+    return WT_OK;
+}
+
+} // extern "C"
+
+namespace {
+
+static_assert(WT_CTL_LOOPS == wtc::LOOPS && WT_NC == wtc::NC && WT_NCS == wtc::NCS, "control blocks of the C ABI");
+
+// Host-side checks of a [WT_CTL_LOOPS][WT_NC][N] parameter block; nullptr when it is valid.
+const char *control_params_error(const double *p, int64_t N)
+{
+    for (int l = 0; l < wtc::LOOPS; ++l)
+        for (int64_t r = 0; r < N; ++r) {
+            double c[wtc::NC];
+            for (int k = 0; k < wtc::NC; ++k) {
+                c[k] = p[((int64_t)l * wtc::NC + k) * N + r];
+                if (!std::isfinite(c[k])) return "control parameters must be finite";
+            }
+            if (c[wtc::C_ENABLE] != 0.0 && c[wtc::C_ENABLE] != 1.0) return "enable must be 0 or 1";
+            const double sensor = c[wtc::C_SENSOR];
+            if (sensor != std::floor(sensor) || sensor < 0 || sensor >= WT_N_SENSORS) return "sensor must be an integer in 0..6";
+            if (c[wtc::C_DIRECTION] != 1.0 && c[wtc::C_DIRECTION] != -1.0) return "direction must be +1 or -1";
+            if (!(c[wtc::C_KP] >= 0) || !(c[wtc::C_KI] >= 0)) return "kp and ki must be >= 0";
+            if (!(c[wtc::C_OUT_MIN] <= c[wtc::C_OUT_MAX])) return "out_min must not exceed out_max";
+        }
+    return nullptr;
+}
+
+// Enable (retune == false) or retune the PI programs.  A loop starts -- integral 0, output and holding words the
+// float32 of the clamped bias, metrics 0 -- where enable switches it on; retune keeps the state of the other loops.
+int control_load(wt_ensemble *h, const double *params, bool retune)
+{
+    if (!params) return fail(WT_E_ARG, "params is NULL");
+    if (!h->plc_on) return fail(WT_E_STATE, "control writes the holding image: enable plant I/O first");
+    if (retune && !h->ctl_on) return fail(WT_E_STATE, "control is off (wt_ensemble_control_enable)");
+    if (const char *msg = control_params_error(params, h->N)) return fail(WT_E_ARG, msg);
+    HIP_TRY(hipSetDevice(h->device));
+    const int64_t N = h->N;
+    const size_t par_bytes = sizeof(double) * wtc::PAR_DOUBLES * (size_t)N, st_bytes = sizeof(double) * wtc::ST_DOUBLES * (size_t)N;
+    std::vector<double> par((size_t)N * wtc::PAR_DOUBLES), old((size_t)N * wtc::PAR_DOUBLES, 0.0);
+    std::vector<double> st((size_t)N * wtc::ST_DOUBLES, 0.0), lt((size_t)N);
+    std::vector<uint16_t> hr((size_t)N * wtp::HR_WORDS);
+    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still read or write the old records
+    if (!h->c_par) {
+        hipError_t e = hipMalloc((void **)&h->c_par, par_bytes);
+        if (e == hipSuccess) e = hipMalloc((void **)&h->c_st, st_bytes);
+        if (e != hipSuccess) { release_control_buffers(h); return fail(WT_E_HIP, std::string("control: ") + hipGetErrorString(e)); }
+    }
+    HIP_TRY(hipMemcpyAsync(hr.data(), h->p_hr, sizeof(uint16_t) * hr.size(), hipMemcpyDeviceToHost, h->stream));
+    if (retune) {
+        HIP_TRY(hipMemcpyAsync(st.data(), h->c_st, st_bytes, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipMemcpyAsync(old.data(), h->c_par, par_bytes, hipMemcpyDeviceToHost, h->stream));
+    } else {
+        HIP_TRY(hipMemcpyAsync(lt.data(), h->p_loop_time, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost, h->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    for (int64_t r = 0; r < N; ++r) {
+        double *s = st.data() + r * wtc::ST_DOUBLES;
+        if (!retune) s[wtc::T_PREV] = lt[(size_t)r];
+        for (int l = 0; l < wtc::LOOPS; ++l) {
+            double *c = par.data() + r * wtc::PAR_DOUBLES + l * wtc::NC;
+            for (int k = 0; k < wtc::NC; ++k) c[k] = params[((int64_t)l * wtc::NC + k) * N + r];
+            const bool was_on = retune && old[(size_t)(r * wtc::PAR_DOUBLES + l * wtc::NC + wtc::C_ENABLE)] == 1.0;
+            if (c[wtc::C_ENABLE] != 1.0 || was_on) continue;
+            const double y = std::fmin(std::fmax(c[wtc::C_BIAS], c[wtc::C_OUT_MIN]), c[wtc::C_OUT_MAX]);
+            double *q = s + l * wtc::NCS;
+            for (int k = 0; k < wtc::NCS; ++k) q[k] = 0.0;
+            q[wtc::CS_OUTPUT] = y;
+            const float f = (float)y;   // round to nearest even, as the device's store
+            uint32_t b; std::memcpy(&b, &f, sizeof b);
+            uint16_t *w = hr.data() + r * wtp::HR_WORDS + wtc::loop_word(l);
+            w[0] = (uint16_t)(b >> 16); w[1] = (uint16_t)(b & 0xffffu);
+        }
+    }
+    HIP_TRY(hipMemcpyAsync(h->c_par, par.data(), par_bytes, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->c_st, st.data(), st_bytes, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->p_hr, hr.data(), sizeof(uint16_t) * hr.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // the host vectors are freed on return
+    h->ctl_on = true;
+    return WT_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int wt_ensemble_control_enable(wt_ensemble *h, const double *params)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    return control_load(h, params, false);
+}
+
+int wt_ensemble_control_retune(wt_ensemble *h, const double *params)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    return control_load(h, params, true);
+}
+
+int wt_ensemble_control_get(wt_ensemble *h, double *state)
+{
+    if (!h || !state) return fail(WT_E_ARG, "NULL argument");
+    if (!h->ctl_on) return fail(WT_E_STATE, "control is off (wt_ensemble_control_enable)");
+    HIP_TRY(hipSetDevice(h->device));
+    const int64_t N = h->N;
+    std::vector<double> st((size_t)N * wtc::ST_DOUBLES);
+    HIP_TRY(hipMemcpyAsync(st.data(), h->c_st, sizeof(double) * st.size(), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (h->err_host[0] | h->err_host[1]) return fail(WT_E_HIP, k_incomplete);
+    for (int l = 0; l < wtc::LOOPS; ++l)
+        for (int k = 0; k < wtc::NCS; ++k)
+            for (int64_t r = 0; r < N; ++r)
+                state[((int64_t)l * wtc::NCS + k) * N + r] = st[(size_t)(r * wtc::ST_DOUBLES + l * wtc::NCS + k)];
+    return WT_OK;
+}
+
+int wt_ensemble_control_disable(wt_ensemble *h)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still use the records
+    release_control_buffers(h);
     return WT_OK;
 }
 

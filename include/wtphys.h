@@ -257,6 +257,44 @@ int wt_ensemble_plc_device(wt_ensemble *h, void **input_image, void **holding_im
 /* current boundary block [WT_NB][N] (after the command path acted on it) */
 int wt_ensemble_get_boundary(wt_ensemble *h, double *bc);
 
+/* ---- per-reactor PI dosing programs on the device (closed loop without a host round trip) ----
+ * The master side of the reference's loop (__main__.py:227-271) -- whatever a Modbus master computes from the input
+ * image and writes into the holding registers between two scans -- as a "virtual PLC program" per reactor; the
+ * reference has no controller of its own.  Up to two independent PI loops: loop 0 doses chlorine (holding words 2-3,
+ * chlorine_flow_rate), loop 1 acid (words 0-1, acid_flow_rate).  At every PLC scan, for a reactor that stepped, after
+ * that scan's update_modbus_inputs and read_modbus_commands, each enabled loop takes v = the scan's raw reading of its
+ * sensor and f = its fault code, t_now = the loop time the scan stores, h = t_now - t_prev (t_prev = t_now afterwards;
+ * one t_prev per reactor, set to the loop time at enable), and without fused multiply-adds:
+ *   hold when v is not finite or f != 0: n_held += 1, nothing else changes, nothing is written;
+ *   e = direction * (setpoint - (double)v);  Ic = integral + (ki * e) * h;  u = (bias + kp * e) + Ic;
+ *   if ((u > out_max && e > 0) || (u < out_min && e < 0)) { Ic = integral; u = (bias + kp * e) + Ic; }
+ *   y = fmin(fmax(u, out_min), out_max);  integral = Ic;  output = y;  holding words = float32(y) (high, low);
+ *   ise += (e * e) * h;  iae += fabs(e) * h;  dose += y * h;  n_exec += 1;  n_sat += (y != u).
+ * So the output acts from the next scan on, through the unchanged command path -- the same bits as a host master
+ * that reads the readings after every call of one scan interval and writes its commands before the next.
+ * params: host [WT_CTL_LOOPS][WT_NC][N]; all finite, enable 0 or 1, sensor an integer 0..6 (WT_N_SENSORS order),
+ * direction +1 (direct) or -1 (reverse), kp, ki >= 0 (ki per second), out_min <= out_max; otherwise WT_E_ARG.
+ * Needs plant I/O (WT_E_STATE).  enable: every enabled loop starts with integral 0, output and holding words the
+ * float32 of fmin(fmax(bias, out_min), out_max), metrics 0.  A disabled loop never touches its words.  retune: new
+ * parameters; state, metrics and t_prev stay, a loop it switches on starts as at enable.  All synchronise. */
+#define WT_CTL_LOOPS 2
+enum {
+    WT_C_ENABLE = 0, WT_C_SENSOR = 1, WT_C_DIRECTION = 2, WT_C_SETPOINT = 3, WT_C_KP = 4, WT_C_KI = 5, WT_C_BIAS = 6,
+    WT_C_OUT_MIN = 7, WT_C_OUT_MAX = 8,
+    WT_NC = 9
+};
+enum {
+    WT_CS_INTEGRAL = 0, WT_CS_OUTPUT = 1, WT_CS_ISE = 2, WT_CS_IAE = 3, WT_CS_DOSE = 4, WT_CS_N_EXEC = 5,
+    WT_CS_N_HELD = 6, WT_CS_N_SAT = 7,
+    WT_NCS = 8
+};
+int wt_ensemble_control_enable(wt_ensemble *h, const double *params /* [WT_CTL_LOOPS][WT_NC][N] */);
+int wt_ensemble_control_retune(wt_ensemble *h, const double *params /* [WT_CTL_LOOPS][WT_NC][N] */);
+/* controller state by reactor: host [WT_CTL_LOOPS][WT_NCS][N]; synchronises; WT_E_STATE while control is off */
+int wt_ensemble_control_get(wt_ensemble *h, double *state);
+/* control off, buffers freed; the holding words keep the last outputs (no effect while control is off) */
+int wt_ensemble_control_disable(wt_ensemble *h);
+
 /* ---- reactor diagnostics (SURVEY.md section 8(f) NEXT-4): reductions over the zones of every reactor ----
  * out: host [WT_N_DIAG][N] doubles, rows
  *   0 total_chlorine_mg, 1 total_H_mol, 2 total_OH_mol, 3 charge_balance_mol, 4 thermal_energy_kJ
