@@ -1,0 +1,128 @@
+"""Per-reactor injection programs that run on the device at every PLC scan (include/wtphys.h,
+``wt_ensemble_inject_*``): scripted sensor spoofing and command tampering on the cyber layer between the plant and
+its controller.
+
+A program has up to four slots.  A slot spoofs one sensor reading on its way into the input image and the PI
+programs, or tampers with one decoded actuator command on its way into the command path, while its window
+``start <= t < end`` holds.  This module builds and checks the parameter block and unpacks the state; the
+tampering itself runs in ``csrc/wt_inj.hpp``.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Union
+
+import numpy as np
+
+SLOTS, NI, NIS = 4, 6, 4                 # WT_INJ_SLOTS, WT_NI, WT_NIS
+PARAM_ROWS = ("mode", "target", "start", "end", "a", "b")
+STATE_ROWS = ("n_applied", "t_first", "t_last", "held")
+MODES = ("off", "bias", "gain", "constant", "ramp", "freeze", "dropout", "fault")
+SENSOR_NAMES = ("pH_inlet", "pH_outlet", "chlorine_inlet", "chlorine_outlet", "flow_main", "temp_inlet", "temp_outlet")
+COMMAND_NAMES = ("acid_flow_rate", "chlorine_flow_rate", "inlet_flow_rate")
+TARGETS = SENSOR_NAMES + COMMAND_NAMES   # index = target code (WT_INJ_CMD_ACID = 7 ...)
+FAULT = MODES.index("fault")
+
+Value = Union[float, int, str, np.ndarray]
+
+
+@dataclass
+class Injection:
+    """One slot.  ``target``: a name of :data:`TARGETS` or its index; ``mode``: a name of :data:`MODES` or its index.
+    Active at the scans whose loop time t has ``start <= t < end``.  BIAS x + a, GAIN x * a, CONSTANT a,
+    RAMP x + (a + b (t - start)), FREEZE the value at the first application, DROPOUT NaN, FAULT (sensors only) the
+    fault code ``a`` (1..6).  Every field takes a scalar or an (N,) array."""
+
+    target: Value
+    mode: Value
+    start: Value = 0.0
+    end: Value = np.inf
+    a: Value = 0.0
+    b: Value = 0.0
+
+
+@dataclass
+class InjectionState:
+    """``ReactorEnsemble.injection_state()``: (SLOTS, N) float64 each, indexed by slot and reactor."""
+
+    n_applied: np.ndarray
+    t_first: np.ndarray      # loop time of the first application (NaN: never applied)
+    t_last: np.ndarray
+    held: np.ndarray         # FREEZE: the value it replays (NaN otherwise)
+
+    @classmethod
+    def from_block(cls, block: np.ndarray) -> "InjectionState":
+        """From a [WT_INJ_SLOTS][WT_NIS][N] block."""
+        return cls(*(np.array(block[:, k]) for k in range(NIS)))
+
+    def block(self) -> np.ndarray:
+        """The (SLOTS, NIS, N) block again."""
+        return np.stack([getattr(self, k) for k in STATE_ROWS], axis=1)
+
+
+def _codes(value, names, what) -> np.ndarray:
+    """Names or indices -> float64 codes (validity is checked by :func:`validate_block`)."""
+    a = np.asarray(value)
+    if a.dtype.kind in "US":
+        bad = [s for s in a.ravel() if str(s) not in names]
+        if bad:
+            raise ValueError(f"unknown {what} {str(bad[0])!r}: one of {names}")
+        return np.vectorize(lambda s: float(names.index(str(s))), otypes=[np.float64])(a)
+    return a.astype(np.float64)
+
+
+def _off_rows(n: int) -> np.ndarray:
+    rows = np.zeros((NI, n))
+    rows[PARAM_ROWS.index("end")] = np.inf
+    return rows
+
+
+def slot_rows(inj: Injection, n: int, name: str = "injection") -> np.ndarray:
+    """(NI, N) rows of one slot."""
+    if not isinstance(inj, Injection):
+        raise TypeError(f"{name}: expected an Injection, got {type(inj).__name__}")
+    vals = {k: getattr(inj, k) for k in PARAM_ROWS}
+    vals["mode"] = _codes(vals["mode"], MODES, "mode")
+    vals["target"] = _codes(vals["target"], TARGETS, "target")
+    rows = np.empty((NI, n))
+    for i, k in enumerate(PARAM_ROWS):
+        try:
+            rows[i] = np.broadcast_to(np.asarray(vals[k], dtype=np.float64), (n,))
+        except ValueError:
+            raise ValueError(f"{name}.{k}: expected a scalar or ({n},) values, got shape {np.shape(vals[k])}") from None
+    return rows
+
+
+def validate_block(block: np.ndarray) -> None:
+    """The checks ``wt_ensemble_inject_set`` makes; ``ValueError`` names the first one that fails."""
+    p = {k: block[:, i] for i, k in enumerate(PARAM_ROWS)}
+    finite = np.isfinite(block)
+    finite[:, PARAM_ROWS.index("end")] |= p["end"] == np.inf
+    if not finite.all():
+        raise ValueError("injection parameters must be finite (end may be +inf)")
+    m, tg = p["mode"], p["target"]
+    if not np.all((m == np.floor(m)) & (m >= 0) & (m < len(MODES))):
+        raise ValueError("mode must be an integer in 0..7")
+    if not np.all((tg == np.floor(tg)) & (tg >= 0) & (tg < len(TARGETS))):
+        raise ValueError("target must be an integer in 0..9")
+    if not np.all(p["start"] <= p["end"]):
+        raise ValueError("start must not exceed end")
+    fault = m == FAULT
+    if np.any(fault & (tg >= len(SENSOR_NAMES))):
+        raise ValueError("a FAULT slot must target a sensor")
+    a = p["a"]
+    if np.any(fault & ~((a == np.floor(a)) & (a >= 1) & (a <= 6))):
+        raise ValueError("a FAULT slot's fault code (a) must be an integer in 1..6")
+
+
+def injection_block(n_reactors: int, *injections: Injection) -> np.ndarray:
+    """The [WT_INJ_SLOTS][WT_NI][N] float64 block of ``wt_ensemble_inject_set``, validated: slot k is the k-th
+    injection, the slots after the last are off."""
+    n = int(n_reactors)
+    if len(injections) > SLOTS:
+        raise ValueError(f"at most {SLOTS} injections per program, got {len(injections)}")
+    rows = [slot_rows(inj, n, f"injection {k}") for k, inj in enumerate(injections)]
+    rows += [_off_rows(n)] * (SLOTS - len(injections))
+    block = np.ascontiguousarray(np.stack(rows))
+    validate_block(block)
+    return block

@@ -18,7 +18,7 @@ from typing import Dict, Iterable, List, Optional, Sequence, Union
 
 import numpy as np
 
-from . import _native, control, params
+from . import _native, control, inject, params
 
 logger = logging.getLogger(__name__)
 
@@ -605,6 +605,27 @@ class ReactorEnsemble:
         blk = np.empty((len(control.LOOPS), control.NCS, self.n_reactors), dtype=np.float64)
         self._control_call(_native.lib().wt_ensemble_control_get, _native.dptr(blk))
         return control.ControlState.from_block(blk)
+
+    # -- injection programs at every PLC scan, on the device (wt_inj.hpp)
+    def set_injections(self, *injections: "inject.Injection") -> None:
+        """Run an injection program of up to four :class:`Injection` slots at every PLC scan, inside the step call:
+        sensor targets spoof the reading the input image and the PI programs see (the instrument itself is
+        untouched), command targets tamper with the decoded actuator command before it is validated (the holding
+        registers keep what the master wrote).  Replaces any program and resets the state.  Needs
+        :meth:`enable_plant_io` and at most 32 zones per reactor."""
+        blk = inject.injection_block(self.n_reactors, *injections)
+        self._control_call(_native.lib().wt_ensemble_inject_set, _native.dptr(blk))
+
+    def injection_state(self) -> "inject.InjectionState":
+        """Applications, first and last application time and the FREEZE value of every slot by reactor (one
+        synchronisation)."""
+        blk = np.empty((inject.SLOTS, inject.NIS, self.n_reactors), dtype=np.float64)
+        self._control_call(_native.lib().wt_ensemble_inject_get, _native.dptr(blk))
+        return inject.InjectionState.from_block(blk)
+
+    def clear_injections(self) -> None:
+        """Stop the injection program."""
+        self._control_call(_native.lib().wt_ensemble_inject_clear)
 
     # -- diagnostics (NEXT-4)
     DIAGNOSTIC_FIELDS = ("total_chlorine_mg", "total_H_mol", "total_OH_mol", "charge_balance_mol", "thermal_energy_kJ",

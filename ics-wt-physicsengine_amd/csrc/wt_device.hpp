@@ -38,6 +38,7 @@
 #include <type_traits>
 #include "wt_sensors.hpp"
 #include "wt_ctl.hpp"
+#include "wt_inj.hpp"
 
 namespace wt {
 
@@ -302,11 +303,16 @@ struct StepArgs {
     int rec_every, rec_cap;
     int rec_phase, rec_slot0;  // outer steps taken since wt_ensemble_record before this call: % rec_every, / rec_every
     wtc::CtlArgs ctl;    // per-reactor PI programs run at PLC scans (wt_ensemble_control_*; ctl.on == 0: none)
+    wti::InjArgs inj;    // per-reactor injection programs run at PLC scans (wt_ensemble_inject_*; inj.on == 0: none)
 };
 static_assert(sizeof(StepArgs) <= 4096, "the kernel-argument segment holds at most 4 KiB");
 constexpr int NB = 10;     // rows of a boundary block (WT_NB)
 // kernels that record and reload the schedule inside a work item (n <= 32); the others take one outer step per launch
 __host__ __device__ constexpr bool x_in_item(int LV) { return LV <= 5; }
+// kernels that carry the injection section (wt_inj.hpp).  The n > 32 kernel has no register for it: every variant
+// tried cost it 8 B of scratch and 4 VGPR spills, with or without a program, so it compiles the section out and
+// wt_ensemble_inject_set refuses ensembles of more than 32 zones.
+__host__ __device__ constexpr bool inj_in_item(int LV) { return LV <= 5; }
 enum { Q_AVAIL = 0, Q_HEAD = 1, Q_TAIL = 2, Q_ERROR = 3, Q_TRACE = 4, Q_DONE = 5, Q_WORDS = 16 };
 
 // ---------------------------------------------------------------- lane geometry and cross-lane moves
@@ -2375,9 +2381,14 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
                     const int64_t rr = rix[lane];
                     const double lt = b->sens.pack.loop_time[rr];
                     if (scan) {
+                        // an injection program (wave-uniform flag) tampers with this lane's copy of the readings and
+                        // with the decoded commands; t is the loop time this scan stores.  Not in the n > 32 kernel.
+                        const bool inj = inj_in_item(LV) && WT_RARE(fresh(pa)->inj.on);
+                        if (inj) wti::tamper_sensors(fresh(pa)->inj, rr, &io.val[0][lane], &io.fault[0][lane], wts::RMAX, lt + dt);
                         wtp::pack_inputs(b->sens.pack, rr, &io.val[0][lane], &io.fault[0][lane], wts::RMAX, lt);   // update_modbus_inputs
                         double c[3];
-                        wtp::apply_commands(b->sens.cmd, rr, c);         // read_modbus_commands + apply_boundary_conditions
+                        if (inj) wtp::apply_commands(b->sens.cmd, rr, c, wti::command_tamper(fresh(pa)->inj, rr, lt + dt));
+                        else wtp::apply_commands(b->sens.cmd, rr, c);    // read_modbus_commands + apply_boundary_conditions
                         io.cmd[0][lane] = c[0]; io.cmd[1][lane] = c[1]; io.cmd[2][lane] = c[2];
                     }
                     b->sens.pack.loop_time[rr] = lt + dt;                 // sim_time += dt (__main__.py:446)

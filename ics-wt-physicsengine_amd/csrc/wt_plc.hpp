@@ -1,7 +1,8 @@
 // wt_plc.hpp -- gfx950 device code of the plant I/O layer around the physics step (SURVEY.md
 // section 8(f) NEXT-2 driver loop, NEXT-3 Modbus register image), one virtual PLC slave per reactor.
 //
-//   pack_inputs            update_modbus_inputs  __main__.py:166-224  (NaN/inf -> 0.0, system_status, fault bits)
+//   pack_inputs            update_modbus_inputs  __main__.py:166-224  (NaN/inf -> 0.0, system_status, fault bits,
+//                          a value outside +-1e9 raises: slave.py:146-147)
 //                          ModbusEncoder.float32_to_registers  modbus/protocols.py:35-58 (high word, low word)
 //                          addresses  modbus/register_map.py:119-244, 364-401
 //   apply_commands         read_modbus_commands  __main__.py:227-252, validate_flow_rate :57-63,
@@ -45,7 +46,10 @@ template <class A> __device__ __forceinline__ void pack_inputs(const A &a, int64
     for (int i = 0; i < NSENS; ++i) {
         float v = value[i * stride];
         if (!(fabsf(v) <= 3.402823466e38f)) v = 0.0f;                           // safe_value: NaN, +-inf -> 0.0
-        const uint32_t b = __float_as_uint(v);                                  // |v| <= range of the sensor << 1e9
+        // ValueError, the rest of the image stays stale; a sensor's own reading stays in its range far below 1e9,
+        // a tampered one (wt_inj.hpp) need not
+        if (!(fabsf(v) <= 1e9f)) { a.update_ok[r] = 0; return; }
+        const uint32_t b = __float_as_uint(v);
         ir[SENSOR_REG[i]] = (uint16_t)(b >> 16); ir[SENSOR_REG[i] + 1] = (uint16_t)(b & 0xffffu);
         const bool f = fault[i * stride] != 0;
         any_fault |= f;
@@ -71,14 +75,19 @@ __device__ __forceinline__ double validate_flow_rate(float v, double max_value)
     return fmax(0.0, fmin((double)v, max_value));
 }
 
+struct NoTamper { __device__ __forceinline__ void operator()(float &, float &, float &) const {} };
+
 // read_modbus_commands validates, apply_boundary_conditions validates again (idempotent).  Writes the boundary
 // block and returns the three rows in force afterwards (cmd[0] inlet, cmd[1] acid, cmd[2] chlorine flow).
-template <class A> __device__ __forceinline__ void apply_commands(const A &a, int64_t r, double cmd[3])
+// tamper: what a man-in-the-middle does to the three decoded floats (acid, chlorine, inlet) before they are
+// validated (wti::CommandTamper); the holding image is not touched.
+template <class A, class T = NoTamper> __device__ __forceinline__ void apply_commands(const A &a, int64_t r, double cmd[3], const T &tamper = T())
 {
     const uint16_t *hr = a.hr + r * HR_WORDS;
-    const float acid = __uint_as_float(((uint32_t)hr[0] << 16) | hr[1]);
-    const float chlorine = __uint_as_float(((uint32_t)hr[2] << 16) | hr[3]);
-    const float inlet = __uint_as_float(((uint32_t)hr[4] << 16) | hr[5]);
+    float acid = __uint_as_float(((uint32_t)hr[0] << 16) | hr[1]);
+    float chlorine = __uint_as_float(((uint32_t)hr[2] << 16) | hr[3]);
+    float inlet = __uint_as_float(((uint32_t)hr[4] << 16) | hr[5]);
+    tamper(acid, chlorine, inlet);
     cmd[1] = validate_flow_rate(acid, 2.0);
     cmd[2] = validate_flow_rate(chlorine, 1.0);
     const double inlet_v = validate_flow_rate(inlet, 20.0);

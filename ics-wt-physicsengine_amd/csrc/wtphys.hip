@@ -111,6 +111,9 @@ struct wt_ensemble {
     // optional per-reactor PI programs (wt_ctl.hpp), indexed by reactor: parameter records and state
     bool ctl_on = false;
     double *c_par = nullptr, *c_st = nullptr;   // [N][wtc::PAR_DOUBLES], [N][wtc::ST_DOUBLES]
+    // optional per-reactor injection programs (wt_inj.hpp), indexed by reactor: slot records and slot state
+    bool inj_on = false;
+    double *i_par = nullptr, *i_st = nullptr;   // [N][wti::PAR_DOUBLES], [N][wti::ST_DOUBLES]
 };
 
 namespace {
@@ -153,6 +156,7 @@ wt::StepArgs make_args(const wt_ensemble *h, double dt, int n_steps, int first_s
     a.rec_slot0 = rec ? (int)(h->rec_steps / h->rec_every) : 0;
     a.x_on = (a.sched || a.rec_pH) ? 1 : 0;
     a.ctl.on = h->ctl_on ? 1 : 0; a.ctl.par = h->c_par; a.ctl.st = h->c_st; a.ctl.hr = h->p_hr;
+    a.inj.on = h->inj_on ? 1 : 0; a.inj.par = h->i_par; a.inj.st = h->i_st;
     return a;
 }
 
@@ -179,6 +183,12 @@ void release_control_buffers(wt_ensemble *h)
 {
     free_and_null(h->c_par); free_and_null(h->c_st);
     h->ctl_on = false;
+}
+
+void release_inject_buffers(wt_ensemble *h)
+{
+    free_and_null(h->i_par); free_and_null(h->i_st);
+    h->inj_on = false;
 }
 
 void release_plc_buffers(wt_ensemble *h)
@@ -413,6 +423,7 @@ int wt_ensemble_destroy(wt_ensemble *h)
     }
     release_record_buffers(h);
     release_control_buffers(h);
+    release_inject_buffers(h);
     if (h->sched) (void)hipFree(h->sched);
     void *sp[] = {h->s_fs, h->s_full_scale, h->s_ring_t, h->s_ring_v, h->s_out_value, h->s_hist_value, h->s_ds, h->s_t_enable, h->s_is,
                   h->s_ring_head, h->s_ring_cnt, h->s_hist_pos, h->s_out_status, h->s_out_fault, h->s_hist_status,
@@ -979,6 +990,97 @@ int wt_ensemble_control_disable(wt_ensemble *h)
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still use the records
     release_control_buffers(h);
+    return WT_OK;
+}
+
+} // extern "C"
+
+namespace {
+
+static_assert(WT_INJ_SLOTS == wti::SLOTS && WT_NI == wti::NI && WT_NIS == wti::NIS, "injection blocks of the C ABI");
+static_assert(WT_INJ_N_TARGETS == wti::N_TARGETS && WT_INJ_CMD_ACID == wti::CMD_ACID && WT_INJ_CMD_CHLORINE == wti::CMD_CHLORINE &&
+              WT_INJ_CMD_INLET == wti::CMD_INLET && WT_INJ_FAULT == wti::M_FAULT && WT_INJ_FAULT + 1 == wti::N_MODES,
+              "injection targets and modes of the C ABI");
+
+// Host-side checks of a [WT_INJ_SLOTS][WT_NI][N] program; nullptr when it is valid.
+const char *inject_params_error(const double *p, int64_t N)
+{
+    for (int s = 0; s < wti::SLOTS; ++s)
+        for (int64_t r = 0; r < N; ++r) {
+            double c[wti::NI];
+            for (int k = 0; k < wti::NI; ++k) c[k] = p[((int64_t)s * wti::NI + k) * N + r];
+            for (int k = 0; k < wti::NI; ++k)
+                if (!std::isfinite(c[k]) && !(k == wti::I_T_END && c[k] == INFINITY))
+                    return "injection parameters must be finite (t_end may be +inf)";
+            const double mode = c[wti::I_MODE], target = c[wti::I_TARGET];
+            if (mode != std::floor(mode) || mode < 0 || mode >= wti::N_MODES) return "mode must be an integer in 0..7";
+            if (target != std::floor(target) || target < 0 || target >= wti::N_TARGETS) return "target must be an integer in 0..9";
+            if (c[wti::I_T_START] > c[wti::I_T_END]) return "t_start must not exceed t_end";
+            if (mode == wti::M_FAULT) {
+                if (target >= wti::CMD_ACID) return "a FAULT slot must target a sensor";
+                const double a = c[wti::I_A];
+                if (a != std::floor(a) || a < 1 || a > 6) return "a FAULT slot's fault code (a) must be an integer in 1..6";
+            }
+        }
+    return nullptr;
+}
+
+} // namespace
+
+extern "C" {
+
+int wt_ensemble_inject_set(wt_ensemble *h, const double *params)
+{
+    if (!h || !params) return fail(WT_E_ARG, "NULL argument");
+    if (!h->plc_on) return fail(WT_E_STATE, "injection acts on the plant I/O images: enable plant I/O first");
+    if (!wt::inj_in_item(levels_for(h->n))) return fail(WT_E_STATE, "injection programs run in the kernels for up to 32 zones");
+    if (const char *msg = inject_params_error(params, h->N)) return fail(WT_E_ARG, msg);
+    HIP_TRY(hipSetDevice(h->device));
+    const int64_t N = h->N;
+    const size_t par_bytes = sizeof(double) * wti::PAR_DOUBLES * (size_t)N, st_bytes = sizeof(double) * wti::ST_DOUBLES * (size_t)N;
+    std::vector<double> par((size_t)N * wti::PAR_DOUBLES), st((size_t)N * wti::ST_DOUBLES);
+    for (int64_t r = 0; r < N; ++r)
+        for (int s = 0; s < wti::SLOTS; ++s) {
+            for (int k = 0; k < wti::NI; ++k) par[(size_t)(r * wti::PAR_DOUBLES + s * wti::NI + k)] = params[((int64_t)s * wti::NI + k) * N + r];
+            double *q = st.data() + r * wti::ST_DOUBLES + s * wti::NIS;
+            q[wti::IS_N_APPLIED] = 0.0; q[wti::IS_T_FIRST] = q[wti::IS_T_LAST] = q[wti::IS_HELD] = NAN;
+        }
+    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still read or write the old records
+    if (!h->i_par) {
+        hipError_t e = hipMalloc((void **)&h->i_par, par_bytes);
+        if (e == hipSuccess) e = hipMalloc((void **)&h->i_st, st_bytes);
+        if (e != hipSuccess) { release_inject_buffers(h); return fail(WT_E_HIP, std::string("inject: ") + hipGetErrorString(e)); }
+    }
+    HIP_TRY(hipMemcpyAsync(h->i_par, par.data(), par_bytes, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->i_st, st.data(), st_bytes, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // the host vectors are freed on return
+    h->inj_on = true;
+    return WT_OK;
+}
+
+int wt_ensemble_inject_get(wt_ensemble *h, double *state)
+{
+    if (!h || !state) return fail(WT_E_ARG, "NULL argument");
+    if (!h->inj_on) return fail(WT_E_STATE, "no injection program is set (wt_ensemble_inject_set)");
+    HIP_TRY(hipSetDevice(h->device));
+    const int64_t N = h->N;
+    std::vector<double> st((size_t)N * wti::ST_DOUBLES);
+    HIP_TRY(hipMemcpyAsync(st.data(), h->i_st, sizeof(double) * st.size(), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (h->err_host[0] | h->err_host[1]) return fail(WT_E_HIP, k_incomplete);
+    for (int s = 0; s < wti::SLOTS; ++s)
+        for (int k = 0; k < wti::NIS; ++k)
+            for (int64_t r = 0; r < N; ++r)
+                state[((int64_t)s * wti::NIS + k) * N + r] = st[(size_t)(r * wti::ST_DOUBLES + s * wti::NIS + k)];
+    return WT_OK;
+}
+
+int wt_ensemble_inject_clear(wt_ensemble *h)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still use the records
+    release_inject_buffers(h);
     return WT_OK;
 }
 

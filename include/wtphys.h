@@ -295,6 +295,43 @@ int wt_ensemble_control_get(wt_ensemble *h, double *state);
 /* control off, buffers freed; the holding words keep the last outputs (no effect while control is off) */
 int wt_ensemble_control_disable(wt_ensemble *h);
 
+/* ---- per-reactor injection programs: scripted sensor spoofing and command tampering at every PLC scan ----
+ * The cyber layer between the plant and its controller under attack or fault, in the spirit of the reference's
+ * roadmap item "fault injection framework (scripted scenarios)"; its sensors only fail at random.  Up to
+ * WT_INJ_SLOTS slots per reactor, each (mode, target, t_start, t_end, a, b).  Targets 0..6 are the sensors in
+ * WT_N_SENSORS order, WT_INJ_CMD_ACID / _CHLORINE / _INLET the decoded acid, chlorine and inlet flow commands.  At
+ * every PLC scan, for a reactor that stepped, with t = the loop time the scan stores (the PI programs' t_now), a slot
+ * is active when t_start <= t < t_end; active slots apply in ascending order, each to its target's current value
+ * (the previous slot's output).  One application takes x = (double) of the incoming float32 and, without fused
+ * multiply-adds, gives x' rounded once to float32 (round to nearest even):
+ *   1 BIAS x + a;  2 GAIN x * a;  3 CONSTANT a;  4 RAMP x + (a + b * (t - t_start));
+ *   5 FREEZE held, the incoming value at the slot's first application (a replay);  6 DROPOUT NaN;
+ *   7 FAULT (sensors only) the value unchanged, the fault code (int)a;  0 OFF: the slot is ignored.
+ * and n_applied += 1, t_first = t at the first application, t_last = t.
+ * Sensor targets act on the scan's copy of the readings before update_modbus_inputs: the input image and the PI
+ * programs see the tampered value; the instrument (its state, wt_ensemble_sensors_get, the history) does not.  The
+ * image follows update_input_register: a value outside +-1e9 raises there, which leaves the rest of the image stale
+ * and update_ok 0.  Command targets act on the float32 each holding word pair decodes to, before
+ * validate_flow_rate: the clamps, NaN -> 0 and the inlet's > 0.1 rule see the tampered value; the holding image
+ * keeps the words the master (or the PI program) wrote.
+ * params: host [WT_INJ_SLOTS][WT_NI][N]; mode an integer 0..7, target an integer 0..9, t_start finite, t_end finite
+ * or +inf and >= t_start, a and b finite, a FAULT slot targets a sensor and has a an integer 1..6 (a SensorFault code); otherwise
+ * WT_E_ARG.  Needs plant I/O and n <= 32 zones (WT_E_STATE: the n > 32 kernel has no registers for it).  set
+ * resets the state (counts 0, times and held NaN); all synchronise. */
+#define WT_INJ_SLOTS 4
+enum {
+    WT_INJ_OFF = 0, WT_INJ_BIAS = 1, WT_INJ_GAIN = 2, WT_INJ_CONSTANT = 3, WT_INJ_RAMP = 4, WT_INJ_FREEZE = 5,
+    WT_INJ_DROPOUT = 6, WT_INJ_FAULT = 7
+};
+enum { WT_INJ_CMD_ACID = 7, WT_INJ_CMD_CHLORINE = 8, WT_INJ_CMD_INLET = 9, WT_INJ_N_TARGETS = 10 };
+enum { WT_I_MODE = 0, WT_I_TARGET = 1, WT_I_T_START = 2, WT_I_T_END = 3, WT_I_A = 4, WT_I_B = 5, WT_NI = 6 };
+enum { WT_IS_N_APPLIED = 0, WT_IS_T_FIRST = 1, WT_IS_T_LAST = 2, WT_IS_HELD = 3, WT_NIS = 4 };
+int wt_ensemble_inject_set(wt_ensemble *h, const double *params /* [WT_INJ_SLOTS][WT_NI][N] */);
+/* slot state by reactor: host [WT_INJ_SLOTS][WT_NIS][N]; synchronises; WT_E_STATE while no program is set */
+int wt_ensemble_inject_get(wt_ensemble *h, double *state);
+/* program off, buffers freed (no effect while none is set) */
+int wt_ensemble_inject_clear(wt_ensemble *h);
+
 /* ---- reactor diagnostics (SURVEY.md section 8(f) NEXT-4): reductions over the zones of every reactor ----
  * out: host [WT_N_DIAG][N] doubles, rows
  *   0 total_chlorine_mg, 1 total_H_mol, 2 total_OH_mol, 3 charge_balance_mol, 4 thermal_energy_kJ

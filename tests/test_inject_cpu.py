@@ -1,0 +1,176 @@
+"""CPU checks of the per-reactor injection programs: the restatement (inject_ref.py) against worked answers, the block
+of ``injection_block`` with its validation, and the new C ABI symbols."""
+import ctypes
+import importlib
+import os
+import re
+
+import numpy as np
+import pytest
+
+from inject_ref import IS_HELD, IS_N_APPLIED, IS_T_FIRST, IS_T_LAST, InjectRef
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def inj():
+    return importlib.import_module("ics-wt-physicsengine_amd.core.inject")
+
+
+def _readings(v=1.5, sensor=3):
+    vals = np.zeros((7, 1), dtype=np.float32)
+    vals[sensor, 0] = v
+    return vals, np.zeros((7, 1), dtype=np.uint8)
+
+
+def _spoof(inj, *injections, v=1.5, sensor=3, t=10.0):
+    ref = InjectRef(inj.injection_block(1, *injections))
+    vals, f = ref.sensors(*_readings(v, sensor), [t])
+    return ref, vals[sensor, 0], f[sensor, 0]
+
+
+@pytest.mark.parametrize("mode, a, b, want", [
+    ("bias", -0.75, 0.0, np.float32(1.5) + -0.75),
+    ("gain", 0.1, 0.0, np.float64(np.float32(1.5)) * 0.1),
+    ("constant", 0.0, 0.0, 0.0),
+    ("ramp", 0.5, 0.01, 1.5 + (0.5 + 0.01 * (10.0 - 4.0))),
+    ("dropout", 0.0, 0.0, np.nan),
+])
+def test_modes_worked_answers(inj, mode, a, b, want):
+    ref, y, f = _spoof(inj, inj.Injection("chlorine_outlet", mode, start=4.0, a=a, b=b))
+    assert y.dtype == np.float32 and f == 0
+    assert np.array_equal(y, np.float32(want), equal_nan=True)
+    assert ref.st[0, IS_N_APPLIED, 0] == 1 and ref.st[0, IS_T_FIRST, 0] == 10.0 == ref.st[0, IS_T_LAST, 0]
+    assert np.isnan(ref.st[0, IS_HELD, 0])
+
+
+def test_rounding_is_once_to_float32(inj):
+    # 0.1f + 0.2 in fp64 is not (0.1f + (float)0.2) in float32
+    ref, y, _ = _spoof(inj, inj.Injection(3, 1, a=0.2), v=0.1)
+    assert y == np.float32(np.float64(np.float32(0.1)) + 0.2)
+
+
+def test_fault_keeps_the_value_and_sets_the_code(inj):
+    ref, y, f = _spoof(inj, inj.Injection("pH_inlet", "fault", a=4), v=7.25, sensor=0)
+    assert y == np.float32(7.25) and f == 4 and ref.st[0, IS_N_APPLIED, 0] == 1
+
+
+def test_window_edges(inj):
+    ref = InjectRef(inj.injection_block(1, inj.Injection("chlorine_outlet", "constant", start=20.0, end=40.0, a=9.0)))
+    got = [ref.sensors(*_readings(1.0), [t])[0][3, 0] for t in (10.0, 19.999, 20.0, 30.0, 39.999, 40.0, 50.0)]
+    assert got == [1.0, 1.0, 9.0, 9.0, 9.0, 1.0, 1.0]
+    assert ref.st[0, IS_N_APPLIED, 0] == 3 and ref.st[0, IS_T_FIRST, 0] == 20.0 and ref.st[0, IS_T_LAST, 0] == 39.999
+
+
+def test_stepped_mask_and_other_targets(inj):
+    blk = inj.injection_block(2, inj.Injection("flow_main", "constant", a=3.0))
+    ref = InjectRef(blk)
+    vals = np.ones((7, 2), dtype=np.float32)
+    v, _ = ref.sensors(vals, np.zeros((7, 2)), [5.0, 5.0], stepped=[True, False])
+    assert v[4, 0] == 3.0 and v[4, 1] == 1.0 and (v[[0, 1, 2, 3, 5, 6]] == 1.0).all()
+    assert list(ref.st[0, IS_N_APPLIED]) == [1, 0]
+    c = ref.commands(np.ones((3, 2), dtype=np.float32), [5.0, 5.0])     # a sensor slot leaves the commands alone
+    assert (c == 1.0).all()
+
+
+def test_slots_compose_in_ascending_order(inj):
+    ref, y, _ = _spoof(inj, inj.Injection(3, "gain", a=2.0), inj.Injection(3, "bias", a=1.0), v=1.5)
+    assert y == 4.0
+    ref, y, _ = _spoof(inj, inj.Injection(3, "bias", a=1.0), inj.Injection(3, "gain", a=2.0), v=1.5)
+    assert y == 5.0
+
+
+def test_freeze_replays_the_first_value(inj):
+    ref = InjectRef(inj.injection_block(1, inj.Injection(3, "bias", a=1.0), inj.Injection(3, "freeze", start=10.0)))
+    outs = [ref.sensors(*_readings(v), [t])[0][3, 0] for v, t in ((1.0, 0.0), (2.0, 10.0), (3.0, 20.0), (4.0, 30.0))]
+    assert outs == [2.0, 3.0, 3.0, 3.0]              # slot 1 captures slot 0's output at its first application
+    assert ref.st[1, IS_HELD, 0] == 3.0 and ref.st[1, IS_N_APPLIED, 0] == 3 and ref.st[0, IS_N_APPLIED, 0] == 4
+
+
+def test_command_slots(inj):
+    blk = inj.injection_block(1, inj.Injection("chlorine_flow_rate", "constant", a=50.0),
+                              inj.Injection("acid_flow_rate", "dropout"), inj.Injection(9, "gain", a=0.5))
+    c = InjectRef(blk).commands(np.array([[1.0], [0.3], [0.1]], dtype=np.float32), [1.0])
+    assert np.isnan(c[0, 0]) and c[1, 0] == 50.0 and c[2, 0] == np.float32(np.float64(np.float32(0.1)) * 0.5)
+
+
+def test_injection_block_packing_and_broadcasting(inj):
+    N = 4
+    blk = inj.injection_block(N, inj.Injection(np.array(["pH_inlet", "flow_main", "inlet_flow_rate", "temp_outlet"]),
+                                               np.array(["bias", "ramp", "gain", "freeze"]), start=np.arange(N) * 10.0,
+                                               a=0.5, b=np.full(N, 0.01)),
+                              inj.Injection(7, 6, end=100.0))
+    assert blk.shape == (4, 6, N) and blk.dtype == np.float64 and blk.flags["C_CONTIGUOUS"]
+    assert np.array_equal(blk[0, 0], [1, 4, 2, 5]) and np.array_equal(blk[0, 1], [0, 4, 9, 6])
+    assert np.array_equal(blk[0, :, 2], [2, 9, 20.0, np.inf, 0.5, 0.01])
+    assert np.array_equal(blk[1, :, 0], [6, 7, 0.0, 100.0, 0.0, 0.0])
+    off = blk[2:]
+    assert not off[:, 0].any() and np.all(off[:, 3] == np.inf)
+    assert np.array_equal(inj.injection_block(N), np.stack([off[0]] * 4))
+
+
+@pytest.mark.parametrize("kw, msg", [
+    (dict(target="pH_middle"), "unknown target"),
+    (dict(mode="replay"), "unknown mode"),
+    (dict(target=10), "target must be"),
+    (dict(target=2.5), "target must be"),
+    (dict(mode=8), "mode must be"),
+    (dict(mode=-1), "mode must be"),
+    (dict(start=50.0, end=40.0), "start must not exceed end"),
+    (dict(start=np.nan), "finite"),
+    (dict(start=-np.inf), "finite"),
+    (dict(end=-np.inf), "finite"),
+    (dict(end=np.nan), "finite"),
+    (dict(a=np.inf), "finite"),
+    (dict(b=np.nan), "finite"),
+    (dict(mode="fault", target="acid_flow_rate", a=1), "must target a sensor"),
+    (dict(mode="fault", a=0), "fault code"),
+    (dict(mode="fault", a=7), "fault code"),
+    (dict(mode="fault", a=2.5), "fault code"),
+])
+def test_injection_block_validation(inj, kw, msg):
+    args = dict(target="chlorine_outlet", mode="bias")
+    args.update(kw)
+    with pytest.raises(ValueError, match=msg):
+        inj.injection_block(3, inj.Injection(**args))
+
+
+def test_injection_block_count_and_shape_errors(inj):
+    with pytest.raises(ValueError, match="at most 4"):
+        inj.injection_block(3, *[inj.Injection(0, "bias")] * 5)
+    with pytest.raises(ValueError, match="start"):
+        inj.injection_block(3, inj.Injection(0, "bias", start=np.ones(4)))
+    with pytest.raises(TypeError):
+        inj.injection_block(3, {"target": 0})
+    inj.injection_block(3, inj.Injection(0, "fault", a=6), inj.Injection(0, "off", a=99.5))   # OFF slots: a is free
+
+
+def test_injection_state_block_round_trip(inj):
+    blk = np.arange(4 * 4 * 3, dtype=np.float64).reshape(4, 4, 3)
+    st = inj.InjectionState.from_block(blk)
+    assert np.array_equal(st.n_applied, blk[:, 0]) and np.array_equal(st.held, blk[:, 3])
+    assert np.array_equal(st.block(), blk)
+
+
+def test_inject_symbols_declared_and_exported():
+    header = open(os.path.join(ROOT, "include", "wtphys.h")).read()
+    names = ("wt_ensemble_inject_set", "wt_ensemble_inject_get", "wt_ensemble_inject_clear")
+    for name in names:
+        assert re.search(r"\bint " + name + r"\(", header), name
+    assert re.search(r"#define WT_INJ_SLOTS 4\b", header)
+    assert re.search(r"WT_NI = 6\b", header) and re.search(r"WT_NIS = 4\b", header)
+    assert re.search(r"WT_INJ_CMD_ACID = 7\b", header) and re.search(r"WT_INJ_CMD_INLET = 9\b", header)
+    assert re.search(r"WT_INJ_FAULT = 7\b", header)
+    assert re.search(r"#define WT_ABI_VERSION 1\b", header)
+    native = importlib.import_module("ics-wt-physicsengine_amd.core._native")
+    native.build()
+    assert "wt_inj.hpp" in native.BUILD_SOURCES
+    lib = ctypes.CDLL(native.LIB_PATH)
+    for name in names:
+        assert hasattr(lib, name), name
+    wt = importlib.import_module("ics-wt-physicsengine_amd")
+    for name in ("Injection", "InjectionState", "injection_block"):
+        assert name in wt.__all__ and hasattr(wt, name)
+    for name in ("set_injections", "injection_state", "clear_injections"):
+        assert callable(getattr(wt.ReactorEnsemble, name))
