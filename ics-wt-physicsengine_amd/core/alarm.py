@@ -1,0 +1,155 @@
+"""Per-reactor alarm and interlock programs that run on the device at every PLC scan (include/wtphys.h,
+``wt_ensemble_alarm_*``): the safety side of the control layer.
+
+A program has up to four slots.  A slot watches one sensor reading -- the scan's image copy, after any injection
+program, or the instrument's own field reading -- against a HIGH or LOW limit with deadband, on-delay and latch.  An
+active slot may trip the acid or chlorine dosing command to a fixed value from the next scan on.  This module builds
+and checks the parameter block and unpacks the state; the evaluation itself runs in ``csrc/wt_alm.hpp``.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Optional, Union
+
+import numpy as np
+
+SLOTS, NA, NAS, NAR = 4, 10, 8, 6        # WT_ALM_SLOTS, WT_NA, WT_NAS, WT_NAR
+PARAM_ROWS = ("kind", "sensor", "source", "setpoint", "deadband", "on_delay", "latch", "on_bad", "action", "trip_value")
+STATE_ROWS = ("active", "cond", "pending", "n_act", "t_first", "t_last", "time_active", "n_bad")
+REACTOR_ROWS = ("t_prev", "first_out", "ovr_acid", "ovr_chlorine", "n_ovr_acid", "n_ovr_chlorine")
+KINDS = ("off", "high", "low")
+SOURCES = ("image", "field")
+ON_BAD = ("hold", "alarm")
+ACTIONS = ("none", "trip_acid", "trip_chlorine")
+SENSOR_NAMES = ("pH_inlet", "pH_outlet", "chlorine_inlet", "chlorine_outlet", "flow_main", "temp_inlet", "temp_outlet")
+# alarm word bits (wt_ensemble_alarm_words)
+WORD_ACID, WORD_CHLORINE, WORD_FIRST_OUT_SHIFT = 1 << 8, 1 << 9, 12
+
+Value = Union[float, int, str, np.ndarray]
+
+
+@dataclass
+class Alarm:
+    """One slot.  ``sensor``: a name of :data:`SENSOR_NAMES` or its index; ``kind``: "high" or "low" (or "off");
+    ``source``: "image" (the scan's copy after any injection program) or "field" (the instrument's own reading);
+    ``on_bad``: "hold" (a NaN or faulted reading changes nothing but the count) or "alarm" (it counts as the
+    condition); ``action``: None, "trip_acid" or "trip_chlorine", with ``trip_value`` the command the trip forces.
+    A HIGH slot's condition is v > setpoint and clears at v < setpoint - deadband (LOW mirrored); it activates after
+    the condition held for ``on_delay`` seconds; a latched slot stays active until :meth:`reset_alarms`.  Every field
+    takes a scalar or an (N,) array."""
+
+    sensor: Value
+    kind: Value
+    setpoint: Value
+    deadband: Value = 0.0
+    on_delay: Value = 0.0
+    latch: Value = False
+    source: Value = "image"
+    on_bad: Value = "hold"
+    action: Optional[Value] = None
+    trip_value: Value = 0.0
+
+
+@dataclass
+class AlarmState:
+    """``ReactorEnsemble.alarm_state()``: slot fields (SLOTS, N), reactor fields (N,), float64."""
+
+    active: np.ndarray
+    cond: np.ndarray
+    pending: np.ndarray        # loop time the condition started to stand while inactive (NaN: none)
+    n_act: np.ndarray          # activations
+    t_first: np.ndarray        # loop time of the first activation (NaN: never)
+    t_last: np.ndarray         # last scan at which the slot was active
+    time_active: np.ndarray    # seconds active
+    n_bad: np.ndarray          # scans with a NaN or faulted reading
+    t_prev: np.ndarray
+    first_out: np.ndarray      # slot that activated first since the last clean state (-1: none)
+    ovr_acid: np.ndarray       # trip value in force for the next scan (NaN: none)
+    ovr_chlorine: np.ndarray
+    n_ovr_acid: np.ndarray     # scans whose command was overridden
+    n_ovr_chlorine: np.ndarray
+
+    @classmethod
+    def from_block(cls, slot_block: np.ndarray, reactor_block: np.ndarray) -> "AlarmState":
+        """From a [WT_ALM_SLOTS][WT_NAS][N] and a [WT_NAR][N] block."""
+        return cls(*(np.array(slot_block[:, k]) for k in range(NAS)), *(np.array(reactor_block[k]) for k in range(NAR)))
+
+    def block(self):
+        """The (SLOTS, NAS, N) and (NAR, N) blocks again."""
+        return (np.stack([getattr(self, k) for k in STATE_ROWS], axis=1),
+                np.stack([getattr(self, k) for k in REACTOR_ROWS]))
+
+
+def _codes(value, names, what) -> np.ndarray:
+    """Names or indices -> float64 codes (validity is checked by :func:`validate_block`)."""
+    a = np.asarray(value)
+    if a.dtype.kind in "US":
+        bad = [s for s in a.ravel() if str(s) not in names]
+        if bad:
+            raise ValueError(f"unknown {what} {str(bad[0])!r}: one of {names}")
+        return np.vectorize(lambda s: float(names.index(str(s))), otypes=[np.float64])(a)
+    return a.astype(np.float64)
+
+
+def slot_rows(alarm: Alarm, n: int, name: str = "alarm") -> np.ndarray:
+    """(NA, N) rows of one slot."""
+    if not isinstance(alarm, Alarm):
+        raise TypeError(f"{name}: expected an Alarm, got {type(alarm).__name__}")
+    vals = {k: getattr(alarm, k) for k in PARAM_ROWS}
+    vals["kind"] = _codes(vals["kind"], KINDS, "kind")
+    vals["sensor"] = _codes(vals["sensor"], SENSOR_NAMES, "sensor")
+    vals["source"] = _codes(vals["source"], SOURCES, "source")
+    vals["on_bad"] = _codes(vals["on_bad"], ON_BAD, "on_bad")
+    vals["action"] = _codes("none" if vals["action"] is None else vals["action"], ACTIONS, "action")
+    rows = np.empty((NA, n))
+    for i, k in enumerate(PARAM_ROWS):
+        try:
+            rows[i] = np.broadcast_to(np.asarray(vals[k], dtype=np.float64), (n,))
+        except ValueError:
+            raise ValueError(f"{name}.{k}: expected a scalar or ({n},) values, got shape {np.shape(vals[k])}") from None
+    return rows
+
+
+def validate_block(block: np.ndarray) -> None:
+    """The checks ``wt_ensemble_alarm_set`` makes, in its order; ``ValueError`` names the first one that fails."""
+    p = {k: block[:, i] for i, k in enumerate(PARAM_ROWS)}
+
+    def int_in(x, lo, hi):
+        return np.all((x == np.floor(x)) & (x >= lo) & (x <= hi))
+
+    if not np.isfinite(block).all():
+        raise ValueError("alarm parameters must be finite")
+    if not int_in(p["kind"], 0, 2):
+        raise ValueError("kind must be 0 (off), 1 (high) or 2 (low)")
+    if not int_in(p["sensor"], 0, len(SENSOR_NAMES) - 1):
+        raise ValueError("sensor must be an integer in 0..6")
+    if not int_in(p["source"], 0, 1):
+        raise ValueError("source must be 0 (image) or 1 (field)")
+    if np.any(p["deadband"] < 0):
+        raise ValueError("deadband must be >= 0")
+    if np.any(p["on_delay"] < 0):
+        raise ValueError("on_delay must be >= 0")
+    if not int_in(p["latch"], 0, 1):
+        raise ValueError("latch must be 0 or 1")
+    if not int_in(p["on_bad"], 0, 1):
+        raise ValueError("on_bad must be 0 (hold) or 1 (alarm)")
+    if not int_in(p["action"], 0, 2):
+        raise ValueError("action must be 0 (none), 1 (trip_acid) or 2 (trip_chlorine)")
+    tv = p["trip_value"]
+    if np.any((p["action"] == 1) & ~((tv >= 0) & (tv <= 2.0))):
+        raise ValueError("a trip_acid slot's trip_value must be in [0, 2]")
+    if np.any((p["action"] == 2) & ~((tv >= 0) & (tv <= 1.0))):
+        raise ValueError("a trip_chlorine slot's trip_value must be in [0, 1]")
+
+
+def alarm_block(n_reactors: int, *alarms: Alarm) -> np.ndarray:
+    """The [WT_ALM_SLOTS][WT_NA][N] float64 block of ``wt_ensemble_alarm_set``, validated: slot k is the k-th alarm,
+    the slots after the last are off."""
+    n = int(n_reactors)
+    if len(alarms) > SLOTS:
+        raise ValueError(f"at most {SLOTS} alarms per program, got {len(alarms)}")
+    rows = [slot_rows(a, n, f"alarm {k}") for k, a in enumerate(alarms)]
+    rows += [np.zeros((NA, n))] * (SLOTS - len(alarms))
+    block = np.ascontiguousarray(np.stack(rows))
+    validate_block(block)
+    return block

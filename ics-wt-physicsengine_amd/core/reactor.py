@@ -18,7 +18,7 @@ from typing import Dict, Iterable, List, Optional, Sequence, Union
 
 import numpy as np
 
-from . import _native, control, inject, params
+from . import _native, alarm, control, inject, params
 
 logger = logging.getLogger(__name__)
 
@@ -626,6 +626,50 @@ class ReactorEnsemble:
     def clear_injections(self) -> None:
         """Stop the injection program."""
         self._control_call(_native.lib().wt_ensemble_inject_clear)
+
+    # -- alarm and interlock programs at every PLC scan, on the device (wt_alm.hpp)
+    def set_alarms(self, *alarms: "alarm.Alarm") -> None:
+        """Run an alarm program of up to four :class:`Alarm` slots at every PLC scan, inside the step call, after the
+        PI programs: a HIGH or LOW limit on an image or field reading with deadband, on-delay and latch; an active
+        slot with a trip action forces the acid or chlorine command to its trip value from the next scan on (the
+        holding registers keep what the master wrote).  Replaces any program and resets the state.  Needs
+        :meth:`enable_plant_io` and at most 32 zones per reactor."""
+        blk = alarm.alarm_block(self.n_reactors, *alarms)
+        self._control_call(_native.lib().wt_ensemble_alarm_set, _native.dptr(blk))
+
+    def alarm_state(self) -> "alarm.AlarmState":
+        """Slot and reactor state of the alarm program (one synchronisation)."""
+        slots = np.empty((alarm.SLOTS, alarm.NAS, self.n_reactors), dtype=np.float64)
+        reactors = np.empty((alarm.NAR, self.n_reactors), dtype=np.float64)
+        self._control_call(_native.lib().wt_ensemble_alarm_get, _native.dptr(slots), _native.dptr(reactors))
+        return alarm.AlarmState.from_block(slots, reactors)
+
+    def alarm_words(self) -> np.ndarray:
+        """(N,) uint16 alarm words: bits 0-3 active slots, 4-7 their conditions, 8 acid trip, 9 chlorine trip,
+        12-14 first-out slot + 1."""
+        w = np.empty(self.n_reactors, dtype=np.uint16)
+        self._control_call(_native.lib().wt_ensemble_alarm_words, w.ctypes.data_as(C.POINTER(C.c_uint16)))
+        return w
+
+    def reset_alarms(self, reactors=None) -> None:
+        """Acknowledge latched alarms: in the given reactors (indices or an (N,) bool mask; None: all), every latched
+        slot whose condition has cleared becomes inactive; one whose condition still stands stays active."""
+        if reactors is None:
+            self._control_call(_native.lib().wt_ensemble_alarm_reset, None)
+            return
+        r = np.asarray(reactors)
+        mask = np.zeros(self.n_reactors, dtype=np.uint8)
+        if r.dtype == bool:
+            if r.shape != (self.n_reactors,):
+                raise ValueError(f"a reactor mask must have shape ({self.n_reactors},)")
+            mask[r] = 1
+        else:
+            mask[r.astype(np.int64)] = 1
+        self._control_call(_native.lib().wt_ensemble_alarm_reset, mask.ctypes.data_as(C.POINTER(C.c_uint8)))
+
+    def clear_alarms(self) -> None:
+        """Stop the alarm program (trips in force end with it)."""
+        self._control_call(_native.lib().wt_ensemble_alarm_clear)
 
     # -- diagnostics (NEXT-4)
     DIAGNOSTIC_FIELDS = ("total_chlorine_mg", "total_H_mol", "total_OH_mol", "charge_balance_mol", "thermal_energy_kJ",

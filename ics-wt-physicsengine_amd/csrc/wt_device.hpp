@@ -39,6 +39,7 @@
 #include "wt_sensors.hpp"
 #include "wt_ctl.hpp"
 #include "wt_inj.hpp"
+#include "wt_alm.hpp"
 
 namespace wt {
 
@@ -304,6 +305,7 @@ struct StepArgs {
     int rec_phase, rec_slot0;  // outer steps taken since wt_ensemble_record before this call: % rec_every, / rec_every
     wtc::CtlArgs ctl;    // per-reactor PI programs run at PLC scans (wt_ensemble_control_*; ctl.on == 0: none)
     wti::InjArgs inj;    // per-reactor injection programs run at PLC scans (wt_ensemble_inject_*; inj.on == 0: none)
+    wta::AlmArgs alm;    // per-reactor alarm and interlock programs run at PLC scans (wt_ensemble_alarm_*; alm.on == 0: none)
 };
 static_assert(sizeof(StepArgs) <= 4096, "the kernel-argument segment holds at most 4 KiB");
 constexpr int NB = 10;     // rows of a boundary block (WT_NB)
@@ -313,6 +315,9 @@ __host__ __device__ constexpr bool x_in_item(int LV) { return LV <= 5; }
 // tried cost it 8 B of scratch and 4 VGPR spills, with or without a program, so it compiles the section out and
 // wt_ensemble_inject_set refuses ensembles of more than 32 zones.
 __host__ __device__ constexpr bool inj_in_item(int LV) { return LV <= 5; }
+// kernels that carry the alarm section (wt_alm.hpp).  The n > 32 kernel compiles it out for the same reason, and
+// wt_ensemble_alarm_set refuses ensembles of more than 32 zones.
+__host__ __device__ constexpr bool alm_in_item(int LV) { return LV <= 5; }
 enum { Q_AVAIL = 0, Q_HEAD = 1, Q_TAIL = 2, Q_ERROR = 3, Q_TRACE = 4, Q_DONE = 5, Q_WORDS = 16 };
 
 // ---------------------------------------------------------------- lane geometry and cross-lane moves
@@ -2389,6 +2394,8 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
                         double c[3];
                         if (inj) wtp::apply_commands(b->sens.cmd, rr, c, wti::command_tamper(fresh(pa)->inj, rr, lt + dt));
                         else wtp::apply_commands(b->sens.cmd, rr, c);    // read_modbus_commands + apply_boundary_conditions
+                        // an alarm program's trips in force (from the previous scan) replace the validated commands
+                        if (alm_in_item(LV) && WT_RARE(fresh(pa)->alm.on)) wta::override_commands(fresh(pa)->alm, b->sens.cmd, rr, c);
                         io.cmd[0][lane] = c[0]; io.cmd[1][lane] = c[1]; io.cmd[2][lane] = c[2];
                     }
                     b->sens.pack.loop_time[rr] = lt + dt;                 // sim_time += dt (__main__.py:446)
@@ -2399,6 +2406,14 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
                     ArgPtr cp = fresh(pa);
                     const int64_t rr = rix[lane];
                     wtc::pi_execute(cp->ctl, rr, &io.val[0][lane], &io.fault[0][lane], wts::RMAX, cp->sens.pack.loop_time[rr]);
+                }
+                // the alarm program, after the PLC program: IMAGE slots read this lane's (possibly tampered) copy,
+                // FIELD slots what the sensor lanes stored before the barrier above; its trips act from the next scan on
+                if (alm_in_item(LV) && scan && WT_RARE(fresh(pa)->alm.on) && lane < R && io.stepped[lane]) {
+                    ArgPtr ap = fresh(pa);
+                    const int64_t rr = rix[lane];
+                    wta::evaluate(ap->alm, rr, ap->sens.N, &io.val[0][lane], &io.fault[0][lane], wts::RMAX, ap->sens.out_value,
+                                  ap->sens.out_fault, ap->sens.pack.loop_time[rr]);
                 }
                 if (scan) {
                     __syncthreads();

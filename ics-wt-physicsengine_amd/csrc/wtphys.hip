@@ -114,6 +114,10 @@ struct wt_ensemble {
     // optional per-reactor injection programs (wt_inj.hpp), indexed by reactor: slot records and slot state
     bool inj_on = false;
     double *i_par = nullptr, *i_st = nullptr;   // [N][wti::PAR_DOUBLES], [N][wti::ST_DOUBLES]
+    // optional per-reactor alarm and interlock programs (wt_alm.hpp), indexed by reactor
+    bool alm_on = false;
+    double *a_par = nullptr, *a_st = nullptr, *a_rst = nullptr;   // [N][wta::PAR_DOUBLES], [N][wta::ST_DOUBLES], [N][wta::RST_DOUBLES]
+    uint16_t *a_word = nullptr;                                   // [N]
 };
 
 namespace {
@@ -157,6 +161,7 @@ wt::StepArgs make_args(const wt_ensemble *h, double dt, int n_steps, int first_s
     a.x_on = (a.sched || a.rec_pH) ? 1 : 0;
     a.ctl.on = h->ctl_on ? 1 : 0; a.ctl.par = h->c_par; a.ctl.st = h->c_st; a.ctl.hr = h->p_hr;
     a.inj.on = h->inj_on ? 1 : 0; a.inj.par = h->i_par; a.inj.st = h->i_st;
+    a.alm.on = h->alm_on ? 1 : 0; a.alm.par = h->a_par; a.alm.st = h->a_st; a.alm.rst = h->a_rst; a.alm.word = h->a_word;
     return a;
 }
 
@@ -189,6 +194,12 @@ void release_inject_buffers(wt_ensemble *h)
 {
     free_and_null(h->i_par); free_and_null(h->i_st);
     h->inj_on = false;
+}
+
+void release_alarm_buffers(wt_ensemble *h)
+{
+    free_and_null(h->a_par); free_and_null(h->a_st); free_and_null(h->a_rst); free_and_null(h->a_word);
+    h->alm_on = false;
 }
 
 void release_plc_buffers(wt_ensemble *h)
@@ -424,6 +435,7 @@ int wt_ensemble_destroy(wt_ensemble *h)
     release_record_buffers(h);
     release_control_buffers(h);
     release_inject_buffers(h);
+    release_alarm_buffers(h);
     if (h->sched) (void)hipFree(h->sched);
     void *sp[] = {h->s_fs, h->s_full_scale, h->s_ring_t, h->s_ring_v, h->s_out_value, h->s_hist_value, h->s_ds, h->s_t_enable, h->s_is,
                   h->s_ring_head, h->s_ring_cnt, h->s_hist_pos, h->s_out_status, h->s_out_fault, h->s_hist_status,
@@ -1081,6 +1093,199 @@ int wt_ensemble_inject_clear(wt_ensemble *h)
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still use the records
     release_inject_buffers(h);
+    return WT_OK;
+}
+
+} // extern "C"
+
+namespace {
+
+static_assert(WT_ALM_SLOTS == wta::SLOTS && WT_NA == wta::NA && WT_NAS == wta::NAS && WT_NAR == wta::NAR, "alarm blocks of the C ABI");
+static_assert(WT_ALM_HIGH == wta::K_HIGH && WT_ALM_LOW == wta::K_LOW && WT_ALM_FIELD == wta::SRC_FIELD &&
+              WT_ALM_ALARM == wta::ON_BAD_ALARM && WT_ALM_TRIP_ACID == wta::ACT_TRIP_ACID &&
+              WT_ALM_TRIP_CHLORINE == wta::ACT_TRIP_CHLORINE && WT_ALM_TRIP_CHLORINE + 1 == wta::N_ACTIONS,
+              "alarm kinds, sources and actions of the C ABI");
+static_assert(WT_A_TRIP_VALUE == wta::A_TRIP_VALUE && WT_AS_N_BAD == wta::AS_N_BAD && WT_AR_N_OVR_CHLORINE == wta::AR_N_OVR_CHLORINE,
+              "alarm rows of the C ABI");
+
+// Host-side checks of a [WT_ALM_SLOTS][WT_NA][N] program; nullptr when it is valid.  core/alarm.py validate_block
+// makes the same checks in the same order.
+const char *alarm_params_error(const double *p, int64_t N)
+{
+    const auto is_int_in = [](double x, int lo, int hi) { return x == std::floor(x) && x >= lo && x <= hi; };
+    for (int s = 0; s < wta::SLOTS; ++s)
+        for (int64_t r = 0; r < N; ++r) {
+            double c[wta::NA];
+            for (int k = 0; k < wta::NA; ++k) c[k] = p[((int64_t)s * wta::NA + k) * N + r];
+            for (int k = 0; k < wta::NA; ++k)
+                if (!std::isfinite(c[k])) return "alarm parameters must be finite";
+            if (!is_int_in(c[wta::A_KIND], 0, 2)) return "kind must be 0 (off), 1 (high) or 2 (low)";
+            if (!is_int_in(c[wta::A_SENSOR], 0, WT_N_SENSORS - 1)) return "sensor must be an integer in 0..6";
+            if (!is_int_in(c[wta::A_SOURCE], 0, 1)) return "source must be 0 (image) or 1 (field)";
+            if (c[wta::A_DEADBAND] < 0) return "deadband must be >= 0";
+            if (c[wta::A_ON_DELAY] < 0) return "on_delay must be >= 0";
+            if (!is_int_in(c[wta::A_LATCH], 0, 1)) return "latch must be 0 or 1";
+            if (!is_int_in(c[wta::A_ON_BAD], 0, 1)) return "on_bad must be 0 (hold) or 1 (alarm)";
+            if (!is_int_in(c[wta::A_ACTION], 0, 2)) return "action must be 0 (none), 1 (trip_acid) or 2 (trip_chlorine)";
+            const double tv = c[wta::A_TRIP_VALUE];
+            if (c[wta::A_ACTION] == wta::ACT_TRIP_ACID && !(tv >= 0 && tv <= 2.0)) return "a trip_acid slot's trip_value must be in [0, 2]";
+            if (c[wta::A_ACTION] == wta::ACT_TRIP_CHLORINE && !(tv >= 0 && tv <= 1.0)) return "a trip_chlorine slot's trip_value must be in [0, 1]";
+        }
+    return nullptr;
+}
+
+// ovr_*, first_out and the word of reactor r from its slot records and state (after a reset)
+uint16_t alarm_settle(const double *par, const double *st, double *rst)
+{
+    double ovr[2] = {NAN, NAN};
+    unsigned word = 0;
+    bool any = false;
+    for (int s = 0; s < wta::SLOTS; ++s) {
+        const double *p = par + s * wta::NA, *q = st + s * wta::NAS;
+        if (q[wta::AS_ACTIVE] != 0.0) {
+            any = true;
+            word |= 1u << s;
+            const double act = p[wta::A_ACTION];
+            if (act == wta::ACT_TRIP_ACID && std::isnan(ovr[0])) ovr[0] = p[wta::A_TRIP_VALUE];
+            if (act == wta::ACT_TRIP_CHLORINE && std::isnan(ovr[1])) ovr[1] = p[wta::A_TRIP_VALUE];
+        }
+        if (q[wta::AS_COND] != 0.0) word |= 1u << (4 + s);
+    }
+    if (!any) rst[wta::AR_FIRST_OUT] = -1.0;
+    rst[wta::AR_OVR_ACID] = ovr[0]; rst[wta::AR_OVR_CHLORINE] = ovr[1];
+    if (!std::isnan(ovr[0])) word |= wta::W_ACID;
+    if (!std::isnan(ovr[1])) word |= wta::W_CHLORINE;
+    word |= (unsigned)((int)rst[wta::AR_FIRST_OUT] + 1) << wta::W_FIRST_OUT_SHIFT;
+    return (uint16_t)word;
+}
+
+const char *k_no_alarm = "no alarm program is set (wt_ensemble_alarm_set)";
+
+} // namespace
+
+extern "C" {
+
+int wt_ensemble_alarm_set(wt_ensemble *h, const double *params)
+{
+    if (!h || !params) return fail(WT_E_ARG, "NULL argument");
+    if (!h->plc_on) return fail(WT_E_STATE, "alarms act on the plant I/O scan: enable plant I/O first");
+    if (!wt::alm_in_item(levels_for(h->n))) return fail(WT_E_STATE, "alarm programs run in the kernels for up to 32 zones");
+    if (const char *msg = alarm_params_error(params, h->N)) return fail(WT_E_ARG, msg);
+    HIP_TRY(hipSetDevice(h->device));
+    const int64_t N = h->N;
+    const size_t par_bytes = sizeof(double) * wta::PAR_DOUBLES * (size_t)N, st_bytes = sizeof(double) * wta::ST_DOUBLES * (size_t)N;
+    const size_t rst_bytes = sizeof(double) * wta::RST_DOUBLES * (size_t)N, word_bytes = sizeof(uint16_t) * (size_t)N;
+    std::vector<double> par((size_t)N * wta::PAR_DOUBLES), st((size_t)N * wta::ST_DOUBLES, 0.0), rst((size_t)N * wta::RST_DOUBLES, 0.0);
+    std::vector<double> lt((size_t)N);
+    for (int64_t r = 0; r < N; ++r)
+        for (int s = 0; s < wta::SLOTS; ++s) {
+            for (int k = 0; k < wta::NA; ++k) par[(size_t)(r * wta::PAR_DOUBLES + s * wta::NA + k)] = params[((int64_t)s * wta::NA + k) * N + r];
+            double *q = st.data() + r * wta::ST_DOUBLES + s * wta::NAS;
+            q[wta::AS_PENDING] = q[wta::AS_T_FIRST] = q[wta::AS_T_LAST] = NAN;
+        }
+    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still read or write the old records
+    HIP_TRY(hipMemcpyAsync(lt.data(), h->p_loop_time, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    for (int64_t r = 0; r < N; ++r) {
+        double *q = rst.data() + r * wta::RST_DOUBLES;
+        q[wta::AR_T_PREV] = lt[(size_t)r]; q[wta::AR_FIRST_OUT] = -1.0; q[wta::AR_OVR_ACID] = q[wta::AR_OVR_CHLORINE] = NAN;
+    }
+    if (!h->a_par) {
+        hipError_t e = hipMalloc((void **)&h->a_par, par_bytes);
+        if (e == hipSuccess) e = hipMalloc((void **)&h->a_st, st_bytes);
+        if (e == hipSuccess) e = hipMalloc((void **)&h->a_rst, rst_bytes);
+        if (e == hipSuccess) e = hipMalloc((void **)&h->a_word, word_bytes);
+        if (e != hipSuccess) { release_alarm_buffers(h); return fail(WT_E_HIP, std::string("alarm: ") + hipGetErrorString(e)); }
+    }
+    HIP_TRY(hipMemcpyAsync(h->a_par, par.data(), par_bytes, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->a_st, st.data(), st_bytes, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->a_rst, rst.data(), rst_bytes, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemsetAsync(h->a_word, 0, word_bytes, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // the host vectors are freed on return
+    h->alm_on = true;
+    return WT_OK;
+}
+
+int wt_ensemble_alarm_get(wt_ensemble *h, double *slot_state, double *reactor_state)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    if (!h->alm_on) return fail(WT_E_STATE, k_no_alarm);
+    HIP_TRY(hipSetDevice(h->device));
+    const int64_t N = h->N;
+    std::vector<double> st((size_t)N * wta::ST_DOUBLES), rst((size_t)N * wta::RST_DOUBLES);
+    HIP_TRY(hipMemcpyAsync(st.data(), h->a_st, sizeof(double) * st.size(), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(rst.data(), h->a_rst, sizeof(double) * rst.size(), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (h->err_host[0] | h->err_host[1]) return fail(WT_E_HIP, k_incomplete);
+    if (slot_state)
+        for (int s = 0; s < wta::SLOTS; ++s)
+            for (int k = 0; k < wta::NAS; ++k)
+                for (int64_t r = 0; r < N; ++r)
+                    slot_state[((int64_t)s * wta::NAS + k) * N + r] = st[(size_t)(r * wta::ST_DOUBLES + s * wta::NAS + k)];
+    if (reactor_state)
+        for (int k = 0; k < wta::NAR; ++k)
+            for (int64_t r = 0; r < N; ++r) reactor_state[(int64_t)k * N + r] = rst[(size_t)(r * wta::RST_DOUBLES + k)];
+    return WT_OK;
+}
+
+int wt_ensemble_alarm_reset(wt_ensemble *h, const uint8_t *mask)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    if (!h->alm_on) return fail(WT_E_STATE, k_no_alarm);
+    HIP_TRY(hipSetDevice(h->device));
+    const int64_t N = h->N;
+    std::vector<double> par((size_t)N * wta::PAR_DOUBLES), st((size_t)N * wta::ST_DOUBLES), rst((size_t)N * wta::RST_DOUBLES);
+    std::vector<uint16_t> word((size_t)N);
+    HIP_TRY(hipMemcpyAsync(par.data(), h->a_par, sizeof(double) * par.size(), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(st.data(), h->a_st, sizeof(double) * st.size(), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(rst.data(), h->a_rst, sizeof(double) * rst.size(), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(word.data(), h->a_word, sizeof(uint16_t) * word.size(), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (h->err_host[0] | h->err_host[1]) return fail(WT_E_HIP, k_incomplete);
+    for (int64_t r = 0; r < N; ++r) {
+        if (mask && !mask[r]) continue;
+        const double *p = par.data() + r * wta::PAR_DOUBLES;
+        double *q = st.data() + r * wta::ST_DOUBLES;
+        for (int s = 0; s < wta::SLOTS; ++s) {
+            double *qs = q + s * wta::NAS;
+            if (p[s * wta::NA + wta::A_LATCH] == 1.0 && qs[wta::AS_ACTIVE] == 1.0 && qs[wta::AS_COND] == 0.0) {
+                qs[wta::AS_ACTIVE] = 0.0; qs[wta::AS_PENDING] = NAN;
+            }
+        }
+        word[(size_t)r] = alarm_settle(p, q, rst.data() + r * wta::RST_DOUBLES);
+    }
+    HIP_TRY(hipMemcpyAsync(h->a_st, st.data(), sizeof(double) * st.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->a_rst, rst.data(), sizeof(double) * rst.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->a_word, word.data(), sizeof(uint16_t) * word.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    return WT_OK;
+}
+
+int wt_ensemble_alarm_words(wt_ensemble *h, uint16_t *words)
+{
+    if (!h || !words) return fail(WT_E_ARG, "NULL argument");
+    if (!h->alm_on) return fail(WT_E_STATE, k_no_alarm);
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipMemcpyAsync(words, h->a_word, sizeof(uint16_t) * (size_t)h->N, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (h->err_host[0] | h->err_host[1]) return fail(WT_E_HIP, k_incomplete);
+    return WT_OK;
+}
+
+int wt_ensemble_alarm_device(wt_ensemble *h, void **word)
+{
+    if (!h || !word) return fail(WT_E_ARG, "NULL argument");
+    if (!h->alm_on) return fail(WT_E_STATE, k_no_alarm);
+    *word = h->a_word;
+    return WT_OK;
+}
+
+int wt_ensemble_alarm_clear(wt_ensemble *h)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still use the records
+    release_alarm_buffers(h);
     return WT_OK;
 }
 

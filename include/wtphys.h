@@ -332,6 +332,72 @@ int wt_ensemble_inject_get(wt_ensemble *h, double *state);
 /* program off, buffers freed (no effect while none is set) */
 int wt_ensemble_inject_clear(wt_ensemble *h);
 
+/* ---- per-reactor alarm and interlock programs: limits on a reading and trips of the dosing pumps at every PLC scan ----
+ * The safety side of the reference's control layer ("alarm logic and interlocks"), which it lists as missing.  Up to
+ * WT_ALM_SLOTS slots per reactor.  Parameters [WT_ALM_SLOTS][WT_NA][N]: kind (0 OFF, 1 HIGH, 2 LOW), sensor (0..6,
+ * WT_N_SENSORS order), source (0 IMAGE: the scan's copy of the readings after any injection program, what the input
+ * image and the PI programs see; 1 FIELD: the instrument's own reading and fault code of this scan, what
+ * wt_ensemble_sensors_get returns, an independent transmitter the man in the middle does not reach), setpoint,
+ * deadband >= 0, on_delay >= 0 (seconds), latch (0 or 1), on_bad (0 HOLD, 1 ALARM), action (0 NONE, 1 TRIP_ACID,
+ * 2 TRIP_CHLORINE), trip_value ([0, 2] for acid, [0, 1] for chlorine); all finite, otherwise WT_E_ARG.
+ * Slot state [WT_ALM_SLOTS][WT_NAS][N]: active, cond, pending, n_act, t_first, t_last, time_active, n_bad.  Reactor
+ * state [WT_NAR][N]: t_prev, first_out, ovr_acid, ovr_chlorine, n_ovr_acid, n_ovr_chlorine.  set resets both: all 0,
+ * except pending, t_first, t_last, ovr_* NaN, first_out -1 and t_prev the reactor's loop time.
+ * At every PLC scan of a reactor that stepped, after its PI program, with t = the loop time the scan stores and
+ * without fused multiply-adds:
+ *   h = t - t_prev; t_prev = t;
+ *   for each slot s = 0..3 with kind != OFF, in ascending order:
+ *     if active: time_active += h;
+ *     v, f = float32 reading and fault code of sensor from source;  bad = !isfinite(v) || f != 0;
+ *     if bad: n_bad += 1, and under HOLD nothing else changes for this slot;
+ *     c = bad ? 1 : HIGH: active ? !((double)v < setpoint - deadband) : (double)v > setpoint
+ *                   LOW:  active ? !((double)v > setpoint + deadband) : (double)v < setpoint;   cond = c;
+ *     if !active: if c { if pending is NaN: pending = t;  if t - pending >= on_delay: active = 1, pending = NaN,
+ *                        n_act += 1, t_first = t if NaN, first_out = s if -1 }  else pending = NaN;
+ *     else if !c && latch == 0: active = 0;
+ *     if active: t_last = t;
+ *   ovr_acid = trip_value of the lowest active slot with action TRIP_ACID, else NaN; ovr_chlorine likewise.
+ *   word = active bits 0-3 | cond bits 4-7 | (ovr_acid set) << 8 | (ovr_chlorine set) << 9 | (first_out + 1) << 12.
+ * Interlock, from the next scan on: right after read_modbus_commands decoded and validated the holding words (and any
+ * command tamper acted), ovr_acid not NaN gives acid command = validate_flow_rate((float)ovr_acid, 2.0), boundary
+ * row 4 = that value, n_ovr_acid += 1; chlorine likewise (limit 1.0, row 6).  The inlet is never overridden and the
+ * holding image keeps the master's words: a host master that writes float32(trip_value) gets the same commands.
+ * Reactors that did not step at a scan get neither.  Needs plant I/O and n <= 32 zones (WT_E_STATE); all synchronise. */
+#define WT_ALM_SLOTS 4
+enum { WT_ALM_OFF = 0, WT_ALM_HIGH = 1, WT_ALM_LOW = 2 };
+enum { WT_ALM_IMAGE = 0, WT_ALM_FIELD = 1 };
+enum { WT_ALM_HOLD = 0, WT_ALM_ALARM = 1 };
+enum { WT_ALM_NONE = 0, WT_ALM_TRIP_ACID = 1, WT_ALM_TRIP_CHLORINE = 2 };
+enum {
+    WT_A_KIND = 0, WT_A_SENSOR = 1, WT_A_SOURCE = 2, WT_A_SETPOINT = 3, WT_A_DEADBAND = 4, WT_A_ON_DELAY = 5,
+    WT_A_LATCH = 6, WT_A_ON_BAD = 7, WT_A_ACTION = 8, WT_A_TRIP_VALUE = 9,
+    WT_NA = 10
+};
+enum {
+    WT_AS_ACTIVE = 0, WT_AS_COND = 1, WT_AS_PENDING = 2, WT_AS_N_ACT = 3, WT_AS_T_FIRST = 4, WT_AS_T_LAST = 5,
+    WT_AS_TIME_ACTIVE = 6, WT_AS_N_BAD = 7,
+    WT_NAS = 8
+};
+enum {
+    WT_AR_T_PREV = 0, WT_AR_FIRST_OUT = 1, WT_AR_OVR_ACID = 2, WT_AR_OVR_CHLORINE = 3, WT_AR_N_OVR_ACID = 4,
+    WT_AR_N_OVR_CHLORINE = 5,
+    WT_NAR = 6
+};
+int wt_ensemble_alarm_set(wt_ensemble *h, const double *params /* [WT_ALM_SLOTS][WT_NA][N] */);
+/* host [WT_ALM_SLOTS][WT_NAS][N] slot state and [WT_NAR][N] reactor state (either may be NULL); WT_E_STATE while no
+ * program is set */
+int wt_ensemble_alarm_get(wt_ensemble *h, double *slot_state, double *reactor_state);
+/* for each reactor with mask[r] != 0 (mask NULL: all), every latched slot that is active and whose cond is 0 becomes
+ * inactive (pending NaN); then ovr_* follow the remaining active slots, first_out returns to -1 when none is active,
+ * and the word is rewritten.  A slot whose condition still stands stays active. */
+int wt_ensemble_alarm_reset(wt_ensemble *h, const uint8_t *mask /* [N] or NULL */);
+/* the alarm words, host uint16 [N] */
+int wt_ensemble_alarm_words(wt_ensemble *h, uint16_t *words);
+/* device pointer of the alarm words [N] for co-resident servers (synchronise first) */
+int wt_ensemble_alarm_device(wt_ensemble *h, void **word);
+/* program off, buffers freed (no effect while none is set) */
+int wt_ensemble_alarm_clear(wt_ensemble *h);
+
 /* ---- reactor diagnostics (SURVEY.md section 8(f) NEXT-4): reductions over the zones of every reactor ----
  * out: host [WT_N_DIAG][N] doubles, rows
  *   0 total_chlorine_mg, 1 total_H_mol, 2 total_OH_mol, 3 charge_balance_mol, 4 thermal_energy_kJ
