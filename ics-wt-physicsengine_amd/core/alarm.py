@@ -13,6 +13,8 @@ from typing import Optional, Union
 
 import numpy as np
 
+from ._program import SENSOR_NAMES, codes, field_rows, slot_block
+
 SLOTS, NA, NAS, NAR = 4, 10, 8, 6        # WT_ALM_SLOTS, WT_NA, WT_NAS, WT_NAR
 PARAM_ROWS = ("kind", "sensor", "source", "setpoint", "deadband", "on_delay", "latch", "on_bad", "action", "trip_value")
 STATE_ROWS = ("active", "cond", "pending", "n_act", "t_first", "t_last", "time_active", "n_bad")
@@ -21,7 +23,6 @@ KINDS = ("off", "high", "low")
 SOURCES = ("image", "field")
 ON_BAD = ("hold", "alarm")
 ACTIONS = ("none", "trip_acid", "trip_chlorine")
-SENSOR_NAMES = ("pH_inlet", "pH_outlet", "chlorine_inlet", "chlorine_outlet", "flow_main", "temp_inlet", "temp_outlet")
 # alarm word bits (wt_ensemble_alarm_words)
 WORD_ACID, WORD_CHLORINE, WORD_FIRST_OUT_SHIFT = 1 << 8, 1 << 9, 12
 
@@ -80,34 +81,14 @@ class AlarmState:
                 np.stack([getattr(self, k) for k in REACTOR_ROWS]))
 
 
-def _codes(value, names, what) -> np.ndarray:
-    """Names or indices -> float64 codes (validity is checked by :func:`validate_block`)."""
-    a = np.asarray(value)
-    if a.dtype.kind in "US":
-        bad = [s for s in a.ravel() if str(s) not in names]
-        if bad:
-            raise ValueError(f"unknown {what} {str(bad[0])!r}: one of {names}")
-        return np.vectorize(lambda s: float(names.index(str(s))), otypes=[np.float64])(a)
-    return a.astype(np.float64)
-
-
 def slot_rows(alarm: Alarm, n: int, name: str = "alarm") -> np.ndarray:
     """(NA, N) rows of one slot."""
     if not isinstance(alarm, Alarm):
         raise TypeError(f"{name}: expected an Alarm, got {type(alarm).__name__}")
-    vals = {k: getattr(alarm, k) for k in PARAM_ROWS}
-    vals["kind"] = _codes(vals["kind"], KINDS, "kind")
-    vals["sensor"] = _codes(vals["sensor"], SENSOR_NAMES, "sensor")
-    vals["source"] = _codes(vals["source"], SOURCES, "source")
-    vals["on_bad"] = _codes(vals["on_bad"], ON_BAD, "on_bad")
-    vals["action"] = _codes("none" if vals["action"] is None else vals["action"], ACTIONS, "action")
-    rows = np.empty((NA, n))
-    for i, k in enumerate(PARAM_ROWS):
-        try:
-            rows[i] = np.broadcast_to(np.asarray(vals[k], dtype=np.float64), (n,))
-        except ValueError:
-            raise ValueError(f"{name}.{k}: expected a scalar or ({n},) values, got shape {np.shape(vals[k])}") from None
-    return rows
+    return field_rows(alarm, PARAM_ROWS, n, name, kind=codes(alarm.kind, KINDS, "kind"),
+                      sensor=codes(alarm.sensor, SENSOR_NAMES, "sensor"), source=codes(alarm.source, SOURCES, "source"),
+                      on_bad=codes(alarm.on_bad, ON_BAD, "on_bad"),
+                      action=codes("none" if alarm.action is None else alarm.action, ACTIONS, "action"))
 
 
 def validate_block(block: np.ndarray) -> None:
@@ -146,10 +127,4 @@ def alarm_block(n_reactors: int, *alarms: Alarm) -> np.ndarray:
     """The [WT_ALM_SLOTS][WT_NA][N] float64 block of ``wt_ensemble_alarm_set``, validated: slot k is the k-th alarm,
     the slots after the last are off."""
     n = int(n_reactors)
-    if len(alarms) > SLOTS:
-        raise ValueError(f"at most {SLOTS} alarms per program, got {len(alarms)}")
-    rows = [slot_rows(a, n, f"alarm {k}") for k, a in enumerate(alarms)]
-    rows += [np.zeros((NA, n))] * (SLOTS - len(alarms))
-    block = np.ascontiguousarray(np.stack(rows))
-    validate_block(block)
-    return block
+    return slot_block(alarms, n, SLOTS, "alarm", slot_rows, np.zeros((NA, n)), validate_block)

@@ -13,11 +13,12 @@ from typing import Optional, Union
 
 import numpy as np
 
+from ._program import SENSOR_NAMES, codes, field_rows
+
 LOOPS = ("chlorine", "acid")            # loop index order of the blocks
 NC, NCS = 9, 8                          # WT_NC, WT_NCS
 PARAM_ROWS = ("enable", "sensor", "direction", "setpoint", "kp", "ki", "bias", "out_min", "out_max")
 STATE_ROWS = ("integral", "output", "ise", "iae", "dose", "n_exec", "n_held", "n_sat")
-SENSOR_NAMES = ("pH_inlet", "pH_outlet", "chlorine_inlet", "chlorine_outlet", "flow_main", "temp_inlet", "temp_outlet")
 HOLDING_WORD = {"chlorine": 2, "acid": 0}    # first holding word of each loop's float32 output
 COMMAND_LIMIT = {"chlorine": 1.0, "acid": 2.0}   # validate_flow_rate's maxima (__main__.py:57-63, :236-242)
 
@@ -72,21 +73,6 @@ class ControlState:
         return np.stack([np.stack([getattr(getattr(self, loop), k) for k in STATE_ROWS]) for loop in LOOPS])
 
 
-def sensor_index(sensor) -> np.ndarray:
-    """Sensor names or indices -> float64 indices (validity is checked by :func:`control_block`)."""
-    if isinstance(sensor, str):
-        if sensor not in SENSOR_NAMES:
-            raise ValueError(f"unknown sensor {sensor!r}: one of {SENSOR_NAMES}")
-        return np.float64(SENSOR_NAMES.index(sensor))
-    a = np.asarray(sensor)
-    if a.dtype.kind in "US":
-        bad = [s for s in a.ravel() if str(s) not in SENSOR_NAMES]
-        if bad:
-            raise ValueError(f"unknown sensor {bad[0]!r}: one of {SENSOR_NAMES}")
-        return np.vectorize(lambda s: float(SENSOR_NAMES.index(str(s))), otypes=[np.float64])(a)
-    return a.astype(np.float64)
-
-
 def _off_rows(n: int) -> np.ndarray:
     rows = np.zeros((NC, n))
     rows[PARAM_ROWS.index("direction")] = 1.0
@@ -99,17 +85,8 @@ def loop_rows(loop: Optional[PILoop], name: str, n: int) -> np.ndarray:
         return _off_rows(n)
     if not isinstance(loop, PILoop):
         raise TypeError(f"{name}: expected a PILoop, got {type(loop).__name__}")
-    vals = {k: getattr(loop, k) for k in PARAM_ROWS}
-    if vals["out_max"] is None:
-        vals["out_max"] = COMMAND_LIMIT[name]
-    vals["sensor"] = sensor_index(vals["sensor"])
-    rows = np.empty((NC, n))
-    for i, k in enumerate(PARAM_ROWS):
-        try:
-            rows[i] = np.broadcast_to(np.asarray(vals[k], dtype=np.float64), (n,))
-        except ValueError:
-            raise ValueError(f"{name}.{k}: expected a scalar or ({n},) values, got shape {np.shape(vals[k])}") from None
-    return rows
+    return field_rows(loop, PARAM_ROWS, n, name, sensor=codes(loop.sensor, SENSOR_NAMES, "sensor"),
+                      out_max=COMMAND_LIMIT[name] if loop.out_max is None else loop.out_max)
 
 
 def validate_block(block: np.ndarray) -> None:

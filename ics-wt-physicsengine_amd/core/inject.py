@@ -14,11 +14,12 @@ from typing import Union
 
 import numpy as np
 
+from ._program import SENSOR_NAMES, codes, field_rows, slot_block
+
 SLOTS, NI, NIS = 4, 6, 4                 # WT_INJ_SLOTS, WT_NI, WT_NIS
 PARAM_ROWS = ("mode", "target", "start", "end", "a", "b")
 STATE_ROWS = ("n_applied", "t_first", "t_last", "held")
 MODES = ("off", "bias", "gain", "constant", "ramp", "freeze", "dropout", "fault")
-SENSOR_NAMES = ("pH_inlet", "pH_outlet", "chlorine_inlet", "chlorine_outlet", "flow_main", "temp_inlet", "temp_outlet")
 COMMAND_NAMES = ("acid_flow_rate", "chlorine_flow_rate", "inlet_flow_rate")
 TARGETS = SENSOR_NAMES + COMMAND_NAMES   # index = target code (WT_INJ_CMD_ACID = 7 ...)
 FAULT = MODES.index("fault")
@@ -60,17 +61,6 @@ class InjectionState:
         return np.stack([getattr(self, k) for k in STATE_ROWS], axis=1)
 
 
-def _codes(value, names, what) -> np.ndarray:
-    """Names or indices -> float64 codes (validity is checked by :func:`validate_block`)."""
-    a = np.asarray(value)
-    if a.dtype.kind in "US":
-        bad = [s for s in a.ravel() if str(s) not in names]
-        if bad:
-            raise ValueError(f"unknown {what} {str(bad[0])!r}: one of {names}")
-        return np.vectorize(lambda s: float(names.index(str(s))), otypes=[np.float64])(a)
-    return a.astype(np.float64)
-
-
 def _off_rows(n: int) -> np.ndarray:
     rows = np.zeros((NI, n))
     rows[PARAM_ROWS.index("end")] = np.inf
@@ -81,16 +71,8 @@ def slot_rows(inj: Injection, n: int, name: str = "injection") -> np.ndarray:
     """(NI, N) rows of one slot."""
     if not isinstance(inj, Injection):
         raise TypeError(f"{name}: expected an Injection, got {type(inj).__name__}")
-    vals = {k: getattr(inj, k) for k in PARAM_ROWS}
-    vals["mode"] = _codes(vals["mode"], MODES, "mode")
-    vals["target"] = _codes(vals["target"], TARGETS, "target")
-    rows = np.empty((NI, n))
-    for i, k in enumerate(PARAM_ROWS):
-        try:
-            rows[i] = np.broadcast_to(np.asarray(vals[k], dtype=np.float64), (n,))
-        except ValueError:
-            raise ValueError(f"{name}.{k}: expected a scalar or ({n},) values, got shape {np.shape(vals[k])}") from None
-    return rows
+    return field_rows(inj, PARAM_ROWS, n, name, mode=codes(inj.mode, MODES, "mode"),
+                      target=codes(inj.target, TARGETS, "target"))
 
 
 def validate_block(block: np.ndarray) -> None:
@@ -119,10 +101,4 @@ def injection_block(n_reactors: int, *injections: Injection) -> np.ndarray:
     """The [WT_INJ_SLOTS][WT_NI][N] float64 block of ``wt_ensemble_inject_set``, validated: slot k is the k-th
     injection, the slots after the last are off."""
     n = int(n_reactors)
-    if len(injections) > SLOTS:
-        raise ValueError(f"at most {SLOTS} injections per program, got {len(injections)}")
-    rows = [slot_rows(inj, n, f"injection {k}") for k, inj in enumerate(injections)]
-    rows += [_off_rows(n)] * (SLOTS - len(injections))
-    block = np.ascontiguousarray(np.stack(rows))
-    validate_block(block)
-    return block
+    return slot_block(injections, n, SLOTS, "injection", slot_rows, _off_rows(n), validate_block)

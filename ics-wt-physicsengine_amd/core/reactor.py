@@ -18,7 +18,7 @@ from typing import Dict, Iterable, List, Optional, Sequence, Union
 
 import numpy as np
 
-from . import _native, alarm, control, inject, params
+from . import _native, _program, alarm, control, inject, params
 
 logger = logging.getLogger(__name__)
 
@@ -461,7 +461,7 @@ class ReactorEnsemble:
         return out[0], out[1], out[2], fl
 
     # -- fused sensor suite (NEXT-1)
-    SENSOR_NAMES = ("pH_inlet", "pH_outlet", "chlorine_inlet", "chlorine_outlet", "flow_main", "temp_inlet", "temp_outlet")
+    SENSOR_NAMES = _program.SENSOR_NAMES
 
     def enable_sensors(self, seed: int = 0x5EED, reactor_base: int = 0, history: int = 0) -> None:
         """Attach the reference's seven-sensor suite (``create_realistic_sensor_suite`` +

@@ -184,22 +184,73 @@ void release_record_buffers(wt_ensemble *h)
     h->rec_cap = 0; h->rec_every = 1; h->rec_steps = 0;
 }
 
-void release_control_buffers(wt_ensemble *h)
+// The device arrays of one per-reactor scan program (PI control, injection, alarms): allocated together on first
+// use, [N] records of a fixed size each, and released together with the program's switch.
+struct ProgramArrays {
+    bool &on;
+    const char *name;                                   // prefix of an allocation error
+    std::vector<std::pair<void **, size_t>> arrays;     // where each pointer lives, bytes per reactor
+};
+
+ProgramArrays control_arrays(wt_ensemble *h)
 {
-    free_and_null(h->c_par); free_and_null(h->c_st);
-    h->ctl_on = false;
+    return {h->ctl_on, "control", {{(void **)&h->c_par, sizeof(double) * wtc::PAR_DOUBLES},
+                                   {(void **)&h->c_st, sizeof(double) * wtc::ST_DOUBLES}}};
 }
 
-void release_inject_buffers(wt_ensemble *h)
+ProgramArrays inject_arrays(wt_ensemble *h)
 {
-    free_and_null(h->i_par); free_and_null(h->i_st);
-    h->inj_on = false;
+    return {h->inj_on, "inject", {{(void **)&h->i_par, sizeof(double) * wti::PAR_DOUBLES},
+                                  {(void **)&h->i_st, sizeof(double) * wti::ST_DOUBLES}}};
 }
 
-void release_alarm_buffers(wt_ensemble *h)
+ProgramArrays alarm_arrays(wt_ensemble *h)
 {
-    free_and_null(h->a_par); free_and_null(h->a_st); free_and_null(h->a_rst); free_and_null(h->a_word);
-    h->alm_on = false;
+    return {h->alm_on, "alarm", {{(void **)&h->a_par, sizeof(double) * wta::PAR_DOUBLES},
+                                 {(void **)&h->a_st, sizeof(double) * wta::ST_DOUBLES},
+                                 {(void **)&h->a_rst, sizeof(double) * wta::RST_DOUBLES},
+                                 {(void **)&h->a_word, sizeof(uint16_t)}}};
+}
+
+void release_program(const ProgramArrays &p)
+{
+    for (const auto &a : p.arrays) free_and_null(*a.first);
+    p.on = false;
+}
+
+// allocates the program's arrays unless an earlier call did; on failure none is left behind
+int alloc_program(const ProgramArrays &p, int64_t N)
+{
+    if (*p.arrays[0].first) return WT_OK;
+    for (const auto &a : p.arrays) {
+        const hipError_t e = hipMalloc(a.first, a.second * (size_t)N);
+        if (e != hipSuccess) { release_program(p); return fail(WT_E_HIP, std::string(p.name) + ": " + hipGetErrorString(e)); }
+    }
+    return WT_OK;
+}
+
+// the body of control_disable, inject_clear and alarm_clear
+int stop_program(wt_ensemble *h, const ProgramArrays &p)
+{
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still use the records
+    release_program(p);
+    return WT_OK;
+}
+
+// [slots][fields][N] blocks of the C ABI <-> the device's [N][stride] records, slot s at s * fields of a record
+void blocks_to_records(const double *block, int slots, int fields, int64_t N, double *rec, int stride)
+{
+    for (int s = 0; s < slots; ++s)
+        for (int k = 0; k < fields; ++k)
+            for (int64_t r = 0; r < N; ++r) rec[r * stride + s * fields + k] = block[((int64_t)s * fields + k) * N + r];
+}
+
+void records_to_blocks(const double *rec, int stride, int slots, int fields, int64_t N, double *block)
+{
+    for (int s = 0; s < slots; ++s)
+        for (int k = 0; k < fields; ++k)
+            for (int64_t r = 0; r < N; ++r) block[((int64_t)s * fields + k) * N + r] = rec[r * stride + s * fields + k];
 }
 
 void release_plc_buffers(wt_ensemble *h)
@@ -299,10 +350,12 @@ int queue_workers(const wt_ensemble *h)
 
 const char *k_incomplete = "a step launch did not advance every wavefront-group (work-queue hand-off timed out or a group was left behind); the state on the device is incomplete";
 
-// queue the copy of the sticky launch-error word (pinned destination) behind what is already on the stream
-int fetch_sticky(wt_ensemble *h)
+// Synchronises the handle's stream, then fails if a launch has set the sticky record (host-coherent memory, valid
+// once the stream is synchronised): what was downloaded comes from an incomplete state.
+int sync_checked(wt_ensemble *h)
 {
-    (void)h;   // nothing to copy: the record lives in host-coherent memory, valid once the stream is synchronised
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (h->err_host[0] | h->err_host[1]) return fail(WT_E_HIP, k_incomplete);
     return WT_OK;
 }
 
@@ -426,21 +479,19 @@ int wt_ensemble_destroy(wt_ensemble *h)
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     if (h->trace) (void)hipFree(h->trace);
     void *ptrs[] = {h->par, h->bc, h->pH, h->Cl, h->T, h->time, h->flow, h->dH, h->dRho, h->dK, h->status, h->stats, h->wave_diag,
-                    h->bad_T, h->q_ctrl, h->q_slots, h->q_next, h->perm, h->cost, h->place_hist, h->snap_dev};
+                    h->bad_T, h->q_ctrl, h->q_slots, h->q_next, h->perm, h->cost, h->place_hist, h->snap_dev, h->sched,
+                    h->diag_out};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     for (int s = 0; s < WT_MAX_STREAMS; ++s) {
         if (h->sub_stream[s]) { (void)hipStreamSynchronize(h->sub_stream[s]); (void)hipStreamDestroy(h->sub_stream[s]); }
         if (h->sub_done[s]) (void)hipEventDestroy(h->sub_done[s]);
     }
     release_record_buffers(h);
-    release_control_buffers(h);
-    release_inject_buffers(h);
-    release_alarm_buffers(h);
-    if (h->sched) (void)hipFree(h->sched);
-    void *sp[] = {h->s_fs, h->s_full_scale, h->s_ring_t, h->s_ring_v, h->s_out_value, h->s_hist_value, h->s_ds, h->s_t_enable, h->s_is,
-                  h->s_ring_head, h->s_ring_cnt, h->s_hist_pos, h->s_out_status, h->s_out_fault, h->s_hist_status,
-                  h->s_hist_fault, h->p_ir, h->p_hr, h->p_loop_time, h->p_update_ok, h->diag_out};
-    for (void *p : sp) if (p) (void)hipFree(p);
+    release_sensor_buffers(h);
+    release_plc_buffers(h);
+    release_program(control_arrays(h));
+    release_program(inject_arrays(h));
+    release_program(alarm_arrays(h));
     if (h->snap_host) (void)hipHostFree(h->snap_host);
     if (h->err_host) (void)hipHostFree(h->err_host);
     for (hipEvent_t e : h->lt_pool) (void)hipEventDestroy(e);
@@ -706,9 +757,7 @@ int wt_ensemble_get_record(wt_ensemble *h, double *pH, double *Cl, double *T, do
         if (flow) HIP_TRY(hipMemcpyAsync(flow, h->rec_flow, sizeof(double) * per, hipMemcpyDeviceToHost, h->stream));
         if (status) HIP_TRY(hipMemcpyAsync(status, h->rec_status, sizeof(uint32_t) * per, hipMemcpyDeviceToHost, h->stream));
     }
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (h->err_host[0] | h->err_host[1]) return fail(WT_E_HIP, k_incomplete);
-    return WT_OK;
+    return sync_checked(h);
 }
 
 int wt_ensemble_launch_timing(wt_ensemble *h, int enable)
@@ -924,11 +973,7 @@ int control_load(wt_ensemble *h, const double *params, bool retune)
     std::vector<double> st((size_t)N * wtc::ST_DOUBLES, 0.0), lt((size_t)N);
     std::vector<uint16_t> hr((size_t)N * wtp::HR_WORDS);
     HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still read or write the old records
-    if (!h->c_par) {
-        hipError_t e = hipMalloc((void **)&h->c_par, par_bytes);
-        if (e == hipSuccess) e = hipMalloc((void **)&h->c_st, st_bytes);
-        if (e != hipSuccess) { release_control_buffers(h); return fail(WT_E_HIP, std::string("control: ") + hipGetErrorString(e)); }
-    }
+    if (int rc = alloc_program(control_arrays(h), N)) return rc;
     HIP_TRY(hipMemcpyAsync(hr.data(), h->p_hr, sizeof(uint16_t) * hr.size(), hipMemcpyDeviceToHost, h->stream));
     if (retune) {
         HIP_TRY(hipMemcpyAsync(st.data(), h->c_st, st_bytes, hipMemcpyDeviceToHost, h->stream));
@@ -937,12 +982,12 @@ int control_load(wt_ensemble *h, const double *params, bool retune)
         HIP_TRY(hipMemcpyAsync(lt.data(), h->p_loop_time, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost, h->stream));
     }
     HIP_TRY(hipStreamSynchronize(h->stream));
+    blocks_to_records(params, wtc::LOOPS, wtc::NC, N, par.data(), wtc::PAR_DOUBLES);
     for (int64_t r = 0; r < N; ++r) {
         double *s = st.data() + r * wtc::ST_DOUBLES;
         if (!retune) s[wtc::T_PREV] = lt[(size_t)r];
         for (int l = 0; l < wtc::LOOPS; ++l) {
-            double *c = par.data() + r * wtc::PAR_DOUBLES + l * wtc::NC;
-            for (int k = 0; k < wtc::NC; ++k) c[k] = params[((int64_t)l * wtc::NC + k) * N + r];
+            const double *c = par.data() + r * wtc::PAR_DOUBLES + l * wtc::NC;
             const bool was_on = retune && old[(size_t)(r * wtc::PAR_DOUBLES + l * wtc::NC + wtc::C_ENABLE)] == 1.0;
             if (c[wtc::C_ENABLE] != 1.0 || was_on) continue;
             const double y = std::fmin(std::fmax(c[wtc::C_BIAS], c[wtc::C_OUT_MIN]), c[wtc::C_OUT_MAX]);
@@ -987,22 +1032,15 @@ int wt_ensemble_control_get(wt_ensemble *h, double *state)
     const int64_t N = h->N;
     std::vector<double> st((size_t)N * wtc::ST_DOUBLES);
     HIP_TRY(hipMemcpyAsync(st.data(), h->c_st, sizeof(double) * st.size(), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (h->err_host[0] | h->err_host[1]) return fail(WT_E_HIP, k_incomplete);
-    for (int l = 0; l < wtc::LOOPS; ++l)
-        for (int k = 0; k < wtc::NCS; ++k)
-            for (int64_t r = 0; r < N; ++r)
-                state[((int64_t)l * wtc::NCS + k) * N + r] = st[(size_t)(r * wtc::ST_DOUBLES + l * wtc::NCS + k)];
+    if (int rc = sync_checked(h)) return rc;
+    records_to_blocks(st.data(), wtc::ST_DOUBLES, wtc::LOOPS, wtc::NCS, N, state);
     return WT_OK;
 }
 
 int wt_ensemble_control_disable(wt_ensemble *h)
 {
     if (!h) return fail(WT_E_ARG, "NULL handle");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still use the records
-    release_control_buffers(h);
-    return WT_OK;
+    return stop_program(h, control_arrays(h));
 }
 
 } // extern "C"
@@ -1051,18 +1089,14 @@ int wt_ensemble_inject_set(wt_ensemble *h, const double *params)
     const int64_t N = h->N;
     const size_t par_bytes = sizeof(double) * wti::PAR_DOUBLES * (size_t)N, st_bytes = sizeof(double) * wti::ST_DOUBLES * (size_t)N;
     std::vector<double> par((size_t)N * wti::PAR_DOUBLES), st((size_t)N * wti::ST_DOUBLES);
+    blocks_to_records(params, wti::SLOTS, wti::NI, N, par.data(), wti::PAR_DOUBLES);
     for (int64_t r = 0; r < N; ++r)
         for (int s = 0; s < wti::SLOTS; ++s) {
-            for (int k = 0; k < wti::NI; ++k) par[(size_t)(r * wti::PAR_DOUBLES + s * wti::NI + k)] = params[((int64_t)s * wti::NI + k) * N + r];
             double *q = st.data() + r * wti::ST_DOUBLES + s * wti::NIS;
             q[wti::IS_N_APPLIED] = 0.0; q[wti::IS_T_FIRST] = q[wti::IS_T_LAST] = q[wti::IS_HELD] = NAN;
         }
     HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still read or write the old records
-    if (!h->i_par) {
-        hipError_t e = hipMalloc((void **)&h->i_par, par_bytes);
-        if (e == hipSuccess) e = hipMalloc((void **)&h->i_st, st_bytes);
-        if (e != hipSuccess) { release_inject_buffers(h); return fail(WT_E_HIP, std::string("inject: ") + hipGetErrorString(e)); }
-    }
+    if (int rc = alloc_program(inject_arrays(h), N)) return rc;
     HIP_TRY(hipMemcpyAsync(h->i_par, par.data(), par_bytes, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(h->i_st, st.data(), st_bytes, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));   // the host vectors are freed on return
@@ -1078,22 +1112,15 @@ int wt_ensemble_inject_get(wt_ensemble *h, double *state)
     const int64_t N = h->N;
     std::vector<double> st((size_t)N * wti::ST_DOUBLES);
     HIP_TRY(hipMemcpyAsync(st.data(), h->i_st, sizeof(double) * st.size(), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (h->err_host[0] | h->err_host[1]) return fail(WT_E_HIP, k_incomplete);
-    for (int s = 0; s < wti::SLOTS; ++s)
-        for (int k = 0; k < wti::NIS; ++k)
-            for (int64_t r = 0; r < N; ++r)
-                state[((int64_t)s * wti::NIS + k) * N + r] = st[(size_t)(r * wti::ST_DOUBLES + s * wti::NIS + k)];
+    if (int rc = sync_checked(h)) return rc;
+    records_to_blocks(st.data(), wti::ST_DOUBLES, wti::SLOTS, wti::NIS, N, state);
     return WT_OK;
 }
 
 int wt_ensemble_inject_clear(wt_ensemble *h)
 {
     if (!h) return fail(WT_E_ARG, "NULL handle");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still use the records
-    release_inject_buffers(h);
-    return WT_OK;
+    return stop_program(h, inject_arrays(h));
 }
 
 } // extern "C"
@@ -1177,9 +1204,9 @@ int wt_ensemble_alarm_set(wt_ensemble *h, const double *params)
     const size_t rst_bytes = sizeof(double) * wta::RST_DOUBLES * (size_t)N, word_bytes = sizeof(uint16_t) * (size_t)N;
     std::vector<double> par((size_t)N * wta::PAR_DOUBLES), st((size_t)N * wta::ST_DOUBLES, 0.0), rst((size_t)N * wta::RST_DOUBLES, 0.0);
     std::vector<double> lt((size_t)N);
+    blocks_to_records(params, wta::SLOTS, wta::NA, N, par.data(), wta::PAR_DOUBLES);
     for (int64_t r = 0; r < N; ++r)
         for (int s = 0; s < wta::SLOTS; ++s) {
-            for (int k = 0; k < wta::NA; ++k) par[(size_t)(r * wta::PAR_DOUBLES + s * wta::NA + k)] = params[((int64_t)s * wta::NA + k) * N + r];
             double *q = st.data() + r * wta::ST_DOUBLES + s * wta::NAS;
             q[wta::AS_PENDING] = q[wta::AS_T_FIRST] = q[wta::AS_T_LAST] = NAN;
         }
@@ -1190,13 +1217,7 @@ int wt_ensemble_alarm_set(wt_ensemble *h, const double *params)
         double *q = rst.data() + r * wta::RST_DOUBLES;
         q[wta::AR_T_PREV] = lt[(size_t)r]; q[wta::AR_FIRST_OUT] = -1.0; q[wta::AR_OVR_ACID] = q[wta::AR_OVR_CHLORINE] = NAN;
     }
-    if (!h->a_par) {
-        hipError_t e = hipMalloc((void **)&h->a_par, par_bytes);
-        if (e == hipSuccess) e = hipMalloc((void **)&h->a_st, st_bytes);
-        if (e == hipSuccess) e = hipMalloc((void **)&h->a_rst, rst_bytes);
-        if (e == hipSuccess) e = hipMalloc((void **)&h->a_word, word_bytes);
-        if (e != hipSuccess) { release_alarm_buffers(h); return fail(WT_E_HIP, std::string("alarm: ") + hipGetErrorString(e)); }
-    }
+    if (int rc = alloc_program(alarm_arrays(h), N)) return rc;
     HIP_TRY(hipMemcpyAsync(h->a_par, par.data(), par_bytes, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(h->a_st, st.data(), st_bytes, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpyAsync(h->a_rst, rst.data(), rst_bytes, hipMemcpyHostToDevice, h->stream));
@@ -1215,16 +1236,9 @@ int wt_ensemble_alarm_get(wt_ensemble *h, double *slot_state, double *reactor_st
     std::vector<double> st((size_t)N * wta::ST_DOUBLES), rst((size_t)N * wta::RST_DOUBLES);
     HIP_TRY(hipMemcpyAsync(st.data(), h->a_st, sizeof(double) * st.size(), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipMemcpyAsync(rst.data(), h->a_rst, sizeof(double) * rst.size(), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (h->err_host[0] | h->err_host[1]) return fail(WT_E_HIP, k_incomplete);
-    if (slot_state)
-        for (int s = 0; s < wta::SLOTS; ++s)
-            for (int k = 0; k < wta::NAS; ++k)
-                for (int64_t r = 0; r < N; ++r)
-                    slot_state[((int64_t)s * wta::NAS + k) * N + r] = st[(size_t)(r * wta::ST_DOUBLES + s * wta::NAS + k)];
-    if (reactor_state)
-        for (int k = 0; k < wta::NAR; ++k)
-            for (int64_t r = 0; r < N; ++r) reactor_state[(int64_t)k * N + r] = rst[(size_t)(r * wta::RST_DOUBLES + k)];
+    if (int rc = sync_checked(h)) return rc;
+    if (slot_state) records_to_blocks(st.data(), wta::ST_DOUBLES, wta::SLOTS, wta::NAS, N, slot_state);
+    if (reactor_state) records_to_blocks(rst.data(), wta::RST_DOUBLES, 1, wta::NAR, N, reactor_state);
     return WT_OK;
 }
 
@@ -1240,8 +1254,7 @@ int wt_ensemble_alarm_reset(wt_ensemble *h, const uint8_t *mask)
     HIP_TRY(hipMemcpyAsync(st.data(), h->a_st, sizeof(double) * st.size(), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipMemcpyAsync(rst.data(), h->a_rst, sizeof(double) * rst.size(), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipMemcpyAsync(word.data(), h->a_word, sizeof(uint16_t) * word.size(), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (h->err_host[0] | h->err_host[1]) return fail(WT_E_HIP, k_incomplete);
+    if (int rc = sync_checked(h)) return rc;
     for (int64_t r = 0; r < N; ++r) {
         if (mask && !mask[r]) continue;
         const double *p = par.data() + r * wta::PAR_DOUBLES;
@@ -1267,9 +1280,7 @@ int wt_ensemble_alarm_words(wt_ensemble *h, uint16_t *words)
     if (!h->alm_on) return fail(WT_E_STATE, k_no_alarm);
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipMemcpyAsync(words, h->a_word, sizeof(uint16_t) * (size_t)h->N, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (h->err_host[0] | h->err_host[1]) return fail(WT_E_HIP, k_incomplete);
-    return WT_OK;
+    return sync_checked(h);
 }
 
 int wt_ensemble_alarm_device(wt_ensemble *h, void **word)
@@ -1283,10 +1294,7 @@ int wt_ensemble_alarm_device(wt_ensemble *h, void **word)
 int wt_ensemble_alarm_clear(wt_ensemble *h)
 {
     if (!h) return fail(WT_E_ARG, "NULL handle");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still use the records
-    release_alarm_buffers(h);
-    return WT_OK;
+    return stop_program(h, alarm_arrays(h));
 }
 
 int wt_ensemble_get_boundary(wt_ensemble *h, double *bc)
@@ -1397,8 +1405,6 @@ int wt_ensemble_queue_error(wt_ensemble *h, int *error)
 {
     if (!h || !error) return fail(WT_E_ARG, "NULL argument");
     HIP_TRY(hipSetDevice(h->device));
-    int rc;
-    if ((rc = fetch_sticky(h))) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));
     *error = (h->err_host[0] ? 1 : 0) | (h->err_host[1] ? 2 : 0);      // bit 0: hand-off timed out, bit 1: a group was left behind; sticky until the handle is destroyed
     return WT_OK;
@@ -1439,11 +1445,7 @@ int wt_ensemble_synchronize(wt_ensemble *h)
 {
     if (!h) return fail(WT_E_ARG, "NULL handle");
     HIP_TRY(hipSetDevice(h->device));
-    int rc;
-    if ((rc = fetch_sticky(h))) return rc;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (h->err_host[0] | h->err_host[1]) return fail(WT_E_HIP, k_incomplete);
-    return WT_OK;
+    return sync_checked(h);
 }
 
 static int d2h(wt_ensemble *h, void *dst, const void *src, size_t bytes)
@@ -1490,10 +1492,7 @@ int wt_ensemble_get_state(wt_ensemble *h, double *pH, double *Cl, double *T, dou
     if ((rc = d2h(h, T, h->T, b))) return rc;
     if ((rc = d2h(h, time, h->time, sizeof(double) * h->N))) return rc;
     if ((rc = d2h(h, flow, h->flow, sizeof(double) * h->N))) return rc;
-    if ((rc = fetch_sticky(h))) return rc;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (h->err_host[0] | h->err_host[1]) return fail(WT_E_HIP, k_incomplete);
-    return WT_OK;
+    return sync_checked(h);
 }
 
 int wt_ensemble_get_snapshot(wt_ensemble *h, double *pH, double *Cl, double *T, double *time, double *flow,
@@ -1508,10 +1507,7 @@ int wt_ensemble_get_snapshot(wt_ensemble *h, double *pH, double *Cl, double *T, 
     if ((rc = d2h(h, time, h->time, sizeof(double) * h->N)) || (rc = d2h(h, flow, h->flow, sizeof(double) * h->N))) return rc;
     if ((rc = d2h(h, H, h->dH, b)) || (rc = d2h(h, rho, h->dRho, b)) || (rc = d2h(h, kdecay, h->dK, b))) return rc;
     if ((rc = d2h(h, flags, h->status, sizeof(uint32_t) * h->N))) return rc;
-    if ((rc = fetch_sticky(h))) return rc;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (h->err_host[0] | h->err_host[1]) return fail(WT_E_HIP, k_incomplete);
-    return WT_OK;
+    return sync_checked(h);
 }
 
 int wt_ensemble_get_derived(wt_ensemble *h, double *H, double *rho, double *kdecay)
@@ -1532,11 +1528,7 @@ int wt_ensemble_get_status(wt_ensemble *h, uint32_t *flags)
     if (!h || !flags) return fail(WT_E_ARG, "NULL argument");
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipMemcpyAsync(flags, h->status, sizeof(uint32_t) * h->N, hipMemcpyDeviceToHost, h->stream));
-    int rc;
-    if ((rc = fetch_sticky(h))) return rc;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (h->err_host[0] | h->err_host[1]) return fail(WT_E_HIP, k_incomplete);
-    return WT_OK;
+    return sync_checked(h);
 }
 
 int wt_ensemble_clear_status(wt_ensemble *h)

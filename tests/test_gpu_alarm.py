@@ -8,29 +8,9 @@ from alarm_ref import AlarmRef
 from conftest import golden_json
 from control_ref import ControlRef
 from inject_ref import InjectRef
+from program_helpers import DT, K, MASTER, assert_all_equal, pi_loops, plant, plant_state
 
 pytestmark = pytest.mark.gpu
-
-DT, K = 10.0, 300
-MASTER = (0.5, 0.25, 6.0)      # acid, chlorine, inlet flow commands the master writes
-
-
-def _plant(wt, cols, bc, n, seed=11, history=0):
-    ens = wt.ReactorEnsemble(cols, n_zones=n)
-    ens.set_boundary(bc)
-    ens.enable_sensors(seed=seed, history=history)
-    ens.enable_plant_io()
-    return ens
-
-
-def _loops(wt, cols, seed=5):
-    N = len(cols["initial_chlorine"])
-    u = np.random.default_rng(seed).random((6, N))
-    chlorine = wt.PILoop("chlorine_outlet", setpoint=cols["initial_chlorine"] + u[0], kp=0.2 + 1.8 * u[1],
-                         ki=1e-4 + 2e-3 * u[2], bias=0.2)
-    acid = wt.PILoop("pH_outlet", setpoint=6.8 + 0.6 * u[3], kp=0.1 + 0.9 * u[4], ki=1e-4 + 1e-3 * u[5], direction=-1,
-                     bias=0.1)
-    return chlorine, acid
 
 
 def _program(wt, cols, seed=3):
@@ -51,23 +31,12 @@ def _program(wt, cols, seed=3):
     ]
 
 
-def _state(ens):
-    es = ens.state
-    v, s, f = ens.sensor_readings()
-    return (es.pH, es.chlorine, es.temperature, es.time, es.flow_rate, es.status, v, s, f, ens.boundary())
-
-
 def _alarms(ens):
     return ens.alarm_state().block() + (ens.alarm_words(),)
 
 
 def _ref_alarms(ref):
     return ref.st, ref.rst, ref.words
-
-
-def _assert_equal(ref, got, what):
-    for i, (a, b) in enumerate(zip(ref, got)):
-        assert np.array_equal(a, b, equal_nan=True), (what, i)
 
 
 def _decode(holding):
@@ -100,13 +69,13 @@ def _host_loop(wt, ens, ctl, alm, interval, n_steps):
 def test_inert_program_is_bit_invisible(gpu, wt):
     N, n = 1000, 8
     cols, bc = wt.make_ensemble(N, seed=41)
-    chlorine, acid = _loops(wt, cols)
+    chlorine, acid = pi_loops(wt, cols)
     progs = [[wt.Alarm(np.arange(N) % 7, "off", 5.0, action="trip_acid", trip_value=1.0)] * 4,
              [wt.Alarm("chlorine_outlet", "high", 1e6, action="trip_chlorine", trip_value=0.0, on_bad="hold"),
               wt.Alarm("flow_main", "low", -1e6, source="field", action="trip_acid", trip_value=2.0)]]
     got = []
     for prog in [None] + progs + ["cleared"]:
-        ens = _plant(wt, cols, bc, n)
+        ens = plant(wt, cols, bc, n)
         ens.set_schedule(0, 7)
         ens.enable_control(chlorine, acid)
         if prog == "cleared":
@@ -115,41 +84,41 @@ def test_inert_program_is_bit_invisible(gpu, wt):
         elif prog is not None:
             ens.set_alarms(*prog)
         ens.step(DT, n_steps=K, download=False)
-        got.append(_state(ens) + ens.input_image() + (ens.control_state().block(),))
+        got.append(plant_state(ens) + ens.input_image() + (ens.control_state().block(),))
         if prog not in (None, "cleared"):
             st = ens.alarm_state()
             assert not st.active.any() and not st.n_act.any() and np.isnan(st.ovr_acid).all()
             assert not st.n_ovr_acid.any() and not st.n_ovr_chlorine.any() and not ens.alarm_words().any()
         ens.close()
     for g in got[1:]:
-        _assert_equal(got[0], g, "inert")
+        assert_all_equal(got[0], g, "inert")
 
 
 @pytest.mark.parametrize("n, N", [(4, 2000), (8, 2000), (20, 1000), (32, 500)])
 def test_fused_alarms_equal_the_host_loop(gpu, wt, n, N):
     cols, bc = wt.make_ensemble(N, seed=777)
-    chlorine, acid = _loops(wt, cols)
+    chlorine, acid = pi_loops(wt, cols)
     prog = _program(wt, cols, seed=n)
     block = wt.alarm_block(N, *prog)
     cblock = wt.control_block(N, chlorine, acid)
     for interval in (1, 7, 50):
-        ens = _plant(wt, cols, bc, n)
+        ens = plant(wt, cols, bc, n)
         ens.set_schedule(0, interval)
         ctl, alm = ControlRef(cblock, np.zeros(N)), AlarmRef(block, np.zeros(N))
         _host_loop(wt, ens, ctl, alm, interval, K)
-        ref = _state(ens) + ens.input_image()
+        ref = plant_state(ens) + ens.input_image()
         assert not ref[5].any()
         assert np.mean(alm.st[:, 3].sum(axis=0) > 0) > 0.2, (n, interval)     # alarms activate in many reactors
         assert alm.rst[4:].sum() > 0, (n, interval)                          # and trips act
         ens.close()
-        ens = _plant(wt, cols, bc, n)
+        ens = plant(wt, cols, bc, n)
         ens.set_schedule(0, interval)
         ens.set_alarms(*prog)
         ens.enable_control(chlorine, acid)
         ens.step(DT, n_steps=K, download=False)
-        _assert_equal(ref, _state(ens) + ens.input_image(), (n, interval))
+        assert_all_equal(ref, plant_state(ens) + ens.input_image(), (n, interval))
         assert np.array_equal(ens.control_state().block(), ctl.st), (n, interval)
-        _assert_equal(_ref_alarms(alm), _alarms(ens), (n, interval, "alarms"))
+        assert_all_equal(_ref_alarms(alm), _alarms(ens), (n, interval, "alarms"))
         ens.close()
 
 
@@ -160,7 +129,7 @@ def test_field_and_image_under_spoofing(gpu, wt):
     spoof = wt.Injection("chlorine_outlet", "constant", a=0.0)
     prog = [wt.Alarm("chlorine_outlet", "high", 0.2, action="trip_chlorine", trip_value=trip),
             wt.Alarm("chlorine_outlet", "high", 0.2, source="field", latch=True, action="trip_chlorine", trip_value=trip)]
-    ens = _plant(wt, cols, bc, n, history=K)
+    ens = plant(wt, cols, bc, n, history=K)
     ens.set_schedule(0, c)
     ens.write_commands(*MASTER)
     ens.enable_control(chlorine=wt.PILoop("chlorine_outlet", setpoint=cols["initial_chlorine"], kp=2.0, ki=1e-3))
@@ -182,7 +151,7 @@ def test_field_and_image_under_spoofing(gpu, wt):
             image = inj.sensors(vh[k], fh[k], lt)
             assert not image[0][3].any()
             ref.scan(vh[k], fh[k], lt, image=image)
-    _assert_equal(_ref_alarms(ref), _alarms(ens), "spoofed")
+    assert_all_equal(_ref_alarms(ref), _alarms(ens), "spoofed")
     # from the scan after activation on, the plant doses the trip value
     on = st.t_first[1] < lt[0]
     assert on.mean() > 0.9
@@ -194,7 +163,7 @@ def test_override_is_downstream_of_command_tampering(gpu, wt):
     N, n = 512, 8
     cols, bc = wt.make_ensemble(N, seed=23)
     trip = 0.3
-    ens = _plant(wt, cols, bc, n)
+    ens = plant(wt, cols, bc, n)
     ens.set_schedule(0, 4)
     ens.write_commands(*MASTER)
     ens.set_injections(wt.Injection("chlorine_flow_rate", "constant", a=1.0))
@@ -224,7 +193,7 @@ def test_latch_and_masked_reset_across_calls(gpu, wt):
             wt.Alarm("chlorine_outlet", "low", np.asarray(cols["initial_chlorine"]) + rng.uniform(-0.5, 0.5, N),
                      deadband=0.05, latch=rng.random(N) < 0.5)]
     mask = rng.random(N) < 0.5
-    ens = _plant(wt, cols, bc, n, history=2 * K)
+    ens = plant(wt, cols, bc, n, history=2 * K)
     ens.set_schedule(0, c)
     ens.write_commands(*MASTER)
     ens.set_alarms(*prog)
@@ -242,8 +211,8 @@ def test_latch_and_masked_reset_across_calls(gpu, wt):
             ref.scan(vh[k], fh[k], lt)
         if k + 1 == K:
             ref.reset(mask)
-            _assert_equal(_ref_alarms(ref), ref_mid, "after reset")
-    _assert_equal(_ref_alarms(ref), _alarms(ens), "second call")
+            assert_all_equal(_ref_alarms(ref), ref_mid, "after reset")
+    assert_all_equal(_ref_alarms(ref), _alarms(ens), "second call")
     assert np.all(ens.alarm_state().active[1] == 1)                      # a standing condition is never reset
     ens.reset_alarms()
     assert np.all(ens.alarm_state().active[1] == 1)
@@ -254,7 +223,7 @@ def test_pH_warm_up(gpu, wt):
     N, n, c = 256, 4, 5
     cols, bc = wt.make_ensemble(N, seed=5)
     for on_bad in ("alarm", "hold"):
-        ens = _plant(wt, cols, bc, n)
+        ens = plant(wt, cols, bc, n)
         ens.set_schedule(0, c)
         ens.write_commands(*MASTER)
         ens.set_alarms(wt.Alarm("pH_outlet", "high", 100.0, source="field", on_bad=on_bad))
@@ -271,12 +240,12 @@ def test_pH_warm_up(gpu, wt):
 def test_schedules_placement_and_frozen_reactors(gpu, wt):
     N, n = 3000, 8
     cols, bc = wt.make_ensemble(N, seed=2024)
-    chlorine, acid = _loops(wt, cols, seed=9)
+    chlorine, acid = pi_loops(wt, cols, seed=9)
     prog = _program(wt, cols, seed=23)
     got = []
     for v in (dict(streams=0, chunk=1), dict(streams=3, chunk=1), dict(streams=0, chunk=1, fused=False),
               dict(streams=0, chunk=1, adaptive=True)):
-        ens = _plant(wt, cols, bc, n)
+        ens = plant(wt, cols, bc, n)
         ens.set_placement(v.get("adaptive", False))
         ens.set_schedule(v["streams"], v["chunk"])
         ens.enable_control(chlorine, acid)
@@ -286,11 +255,11 @@ def test_schedules_placement_and_frozen_reactors(gpu, wt):
             ens.step(DT, n_steps=40, fused=v.get("fused", True), download=False)
         if v.get("adaptive"):
             assert ens.schedule()["redeals"] >= 1 and not np.array_equal(ens.placement()[1], np.arange(N))
-        got.append(_state(ens) + ens.input_image() + (ens.control_state().block(),) + _alarms(ens))
+        got.append(plant_state(ens) + ens.input_image() + (ens.control_state().block(),) + _alarms(ens))
         ens.close()
     assert got[0][-3][:, 3].sum() > 0                                     # some slot activated
     for g, v in zip(got[1:], range(1, 4)):
-        _assert_equal(got[0], g, v)
+        assert_all_equal(got[0], g, v)
     # a reactor frozen by WT_ST_T_RANGE is not read, so its alarms are not evaluated any more
     g = golden_json("g4_faults.json")["cold_run"]
     cfg = wt.ReactorConfiguration(**g["config"])
@@ -331,7 +300,7 @@ def test_errors_and_lifetime(gpu, wt):
             call()
     # the n > 32 kernel carries no alarm section: such an ensemble refuses a program
     for big in (33, 40):
-        other = _plant(wt, cols, bc, big)
+        other = plant(wt, cols, bc, big)
         with pytest.raises(ValueError, match="up to 32 zones"):
             other.set_alarms(high)
         with pytest.raises(ValueError, match="no alarm program"):

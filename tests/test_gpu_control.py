@@ -4,43 +4,11 @@ import numpy as np
 import pytest
 
 from control_ref import CS_N_EXEC, CS_N_HELD, ControlRef
+from program_helpers import DT, K, assert_all_equal, pi_loops, plant, plant_state
 
 pytestmark = pytest.mark.gpu
 
-DT, K = 10.0, 300          # 3000 s: the pH sensors' 1800 s warm-up ends inside the run
 PH_OUT, CL_OUT = 1, 3      # sensor indices
-
-
-def _plant(wt, cols, bc, n, seed=11, history=0):
-    ens = wt.ReactorEnsemble(cols, n_zones=n)
-    ens.set_boundary(bc)
-    ens.enable_sensors(seed=seed, history=history)
-    ens.enable_plant_io()
-    return ens
-
-
-def _loops(wt, cols, seed=5):
-    """Both loops on, per-reactor gains and setpoints: chlorine dosing on the outlet DPD reading, acid dosing (reverse
-    acting: more acid while the pH is above its setpoint) on the outlet pH probe."""
-    N = len(cols["initial_chlorine"])
-    u = np.random.default_rng(seed).random((6, N))
-    chlorine = wt.PILoop("chlorine_outlet", setpoint=cols["initial_chlorine"] + u[0], kp=0.2 + 1.8 * u[1],
-                         ki=1e-4 + 2e-3 * u[2], bias=0.2)
-    acid = wt.PILoop(PH_OUT, setpoint=6.8 + 0.6 * u[3], kp=0.1 + 0.9 * u[4], ki=1e-4 + 1e-3 * u[5], direction=-1,
-                     bias=0.1)
-    return chlorine, acid
-
-
-def _outputs(ens):
-    es = ens.state
-    v, s, f = ens.sensor_readings()
-    img, ok = ens.input_image()
-    return (es.pH, es.chlorine, es.temperature, es.time, es.flow_rate, es.status, v, s, f, img, ok, ens.boundary())
-
-
-def _assert_equal(ref, got, what):
-    for i, (a, b) in enumerate(zip(ref, got)):
-        assert np.array_equal(a, b, equal_nan=True), (what, i)
 
 
 def _host_loop(ens, ref, interval, n_steps, dt=DT):
@@ -64,15 +32,15 @@ def _host_loop(ens, ref, interval, n_steps, dt=DT):
 @pytest.mark.parametrize("n, N", [(4, 2000), (8, 2000), (20, 1000), (40, 200)])
 def test_fused_controlled_call_equals_the_host_loop(gpu, wt, monkeypatch, n, N):
     cols, bc = wt.make_ensemble(N, seed=777)
-    chlorine, acid = _loops(wt, cols)
+    chlorine, acid = pi_loops(wt, cols)
     block = wt.control_block(N, chlorine, acid)
     refs = {}
     for interval in (1, 7, 50):
-        ens = _plant(wt, cols, bc, n)
+        ens = plant(wt, cols, bc, n)
         ens.set_schedule(0, interval)
         ref = ControlRef(block, np.zeros(N))
         _host_loop(ens, ref, interval, K)
-        out = _outputs(ens)
+        out = plant_state(ens) + ens.input_image()
         assert not out[5].any()
         # both loops act (a sensor that fails open or short reads NaN from then on: its loop holds for good)
         assert np.mean(ref.st[:, CS_N_EXEC] > 0, axis=1).min() > 0.9 and ref.st[1, CS_N_HELD].min() > 0
@@ -83,14 +51,14 @@ def test_fused_controlled_call_equals_the_host_loop(gpu, wt, monkeypatch, n, N):
     for v in variants:
         if v.get("tickets"):
             monkeypatch.setenv("WT_Q_TICKETS", "1")            # the long-call split: one item per group and launch
-        ens = _plant(wt, cols, bc, n)
+        ens = plant(wt, cols, bc, n)
         ens.set_schedule(v["streams"], v["chunk"])
         if v.get("tickets"):
             assert ens.item_steps(K) < K
         ens.enable_control(chlorine, acid)
         ens.step(DT, n_steps=K, fused=v.get("fused", True), download=False)
         out, ref = refs[1 if not v.get("fused", True) else v["chunk"]]
-        _assert_equal(out, _outputs(ens), v)
+        assert_all_equal(out, plant_state(ens) + ens.input_image(), v)
         assert np.array_equal(ens.control_state().block(), ref.st), v
         ens.close()
         monkeypatch.delenv("WT_Q_TICKETS", raising=False)
@@ -101,7 +69,7 @@ def test_anti_windup_and_retune(gpu, wt):
     on; a retune to a reachable setpoint leaves saturation at the first scan whose error is negative."""
     N, n, c = 512, 8, 5
     cols, bc = wt.make_ensemble(N, seed=31)
-    ens = _plant(wt, cols, bc, n)
+    ens = plant(wt, cols, bc, n)
     ens.set_schedule(0, c)
     chlorine = wt.PILoop("chlorine_outlet", setpoint=50.0, kp=0.5, ki=1e-3, bias=0.2)
     ens.enable_control(chlorine)
@@ -144,9 +112,9 @@ def test_hold_through_warm_up_and_faults(gpu, wt):
     clamped bias meanwhile.  A loop holds exactly on the scans whose reading is faulted or not finite."""
     N, n, c, steps = 4000, 4, 3, 300
     cols, bc = wt.make_ensemble(N, seed=99)
-    ens = _plant(wt, cols, bc, n, seed=3, history=steps)
+    ens = plant(wt, cols, bc, n, seed=3, history=steps)
     ens.set_schedule(0, c)
-    chlorine, acid = _loops(wt, cols, seed=8)
+    chlorine, acid = pi_loops(wt, cols, seed=8)
     acid.bias = 2.5                                         # clamped to out_max = 2.0
     ens.enable_control(chlorine, acid)
     block = wt.control_block(N, chlorine, acid)
@@ -180,10 +148,10 @@ def test_control_state_under_adaptive_placement(gpu, wt):
     """Control state is indexed by reactor: after adaptive re-deals it equals an identity-placement twin's."""
     N, n = 3000, 8
     cols, bc = wt.make_ensemble(N, seed=2024)
-    chlorine, acid = _loops(wt, cols, seed=9)
+    chlorine, acid = pi_loops(wt, cols, seed=9)
     got = []
     for adaptive in (True, False):
-        ens = _plant(wt, cols, bc, n)
+        ens = plant(wt, cols, bc, n)
         ens.set_placement(adaptive)
         ens.set_schedule(0, 4)
         ens.enable_control(chlorine, acid)
@@ -192,9 +160,9 @@ def test_control_state_under_adaptive_placement(gpu, wt):
         perm = ens.placement()[1]
         assert (ens.schedule()["redeals"] >= 1 and not np.array_equal(perm, np.arange(N))) if adaptive \
             else np.array_equal(perm, np.arange(N))
-        got.append((_outputs(ens), ens.control_state().block()))
+        got.append((plant_state(ens) + ens.input_image(), ens.control_state().block()))
         ens.close()
-    _assert_equal(got[1][0], got[0][0], "placement")
+    assert_all_equal(got[1][0], got[0][0], "placement")
     assert np.array_equal(got[0][1], got[1][1])
 
 
@@ -203,7 +171,7 @@ def test_errors_and_lifetime(gpu, wt):
     nat = import_module("ics-wt-physicsengine_amd.core._native")
     N, n = 256, 4
     cols, bc = wt.make_ensemble(N, seed=12)
-    chlorine, acid = _loops(wt, cols)
+    chlorine, acid = pi_loops(wt, cols)
     ens = wt.ReactorEnsemble(cols, n_zones=n)
     ens.set_boundary(bc)
     with pytest.raises(ValueError, match="plant I/O"):
@@ -230,7 +198,7 @@ def test_errors_and_lifetime(gpu, wt):
     ens.close()
 
     # after disable_control, a run equals a plant-I/O-only twin whose holding words got the same last outputs
-    ens = _plant(wt, cols, bc, n)
+    ens = plant(wt, cols, bc, n)
     ens.set_schedule(0, 5)
     ens.enable_control(chlorine, acid)
     ens.step(DT, n_steps=100, download=False)
@@ -239,12 +207,12 @@ def test_errors_and_lifetime(gpu, wt):
     with pytest.raises(ValueError, match="control is off"):
         ens.control_state()
     ens.step(DT, n_steps=60, download=False)
-    twin = _plant(wt, cols, bc, n)
+    twin = plant(wt, cols, bc, n)
     twin.set_schedule(0, 5)
     ref = ControlRef(wt.control_block(N, chlorine, acid), np.zeros(N))
     _host_loop(twin, ref, 5, 100)
     assert np.array_equal(ref.st, last.block())
     twin.step(DT, n_steps=60, download=False)
-    _assert_equal(_outputs(twin), _outputs(ens), "disabled")
+    assert_all_equal(plant_state(twin) + twin.input_image(), plant_state(ens) + ens.input_image(), "disabled")
     assert np.array_equal(ens.boundary()[6], last.chlorine.output.astype(np.float32).astype(np.float64).clip(0.0, 1.0))
     ens.close(); twin.close()

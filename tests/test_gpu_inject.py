@@ -8,29 +8,9 @@ import plc_oracle as PO
 from conftest import golden_json
 from control_ref import ControlRef
 from inject_ref import InjectRef
+from program_helpers import DT, K, MASTER, assert_all_equal, pi_loops, plant, plant_state
 
 pytestmark = pytest.mark.gpu
-
-DT, K = 10.0, 300
-MASTER = (0.5, 0.25, 6.0)      # acid, chlorine, inlet flow commands the master writes
-
-
-def _plant(wt, cols, bc, n, seed=11, history=0):
-    ens = wt.ReactorEnsemble(cols, n_zones=n)
-    ens.set_boundary(bc)
-    ens.enable_sensors(seed=seed, history=history)
-    ens.enable_plant_io()
-    return ens
-
-
-def _loops(wt, cols, seed=5):
-    N = len(cols["initial_chlorine"])
-    u = np.random.default_rng(seed).random((6, N))
-    chlorine = wt.PILoop("chlorine_outlet", setpoint=cols["initial_chlorine"] + u[0], kp=0.2 + 1.8 * u[1],
-                         ki=1e-4 + 2e-3 * u[2], bias=0.2)
-    acid = wt.PILoop("pH_outlet", setpoint=6.8 + 0.6 * u[3], kp=0.1 + 0.9 * u[4], ki=1e-4 + 1e-3 * u[5], direction=-1,
-                     bias=0.1)
-    return chlorine, acid
 
 
 def _sensor_program(wt, N, seed=3, span=K * DT):
@@ -47,17 +27,6 @@ def _sensor_program(wt, N, seed=3, span=K * DT):
         b = np.where(mode == 4, rng.uniform(-1e-3, 1e-3, N), 0.0)
         out.append(wt.Injection(rng.integers(0, 7, N), mode, start=start, end=end, a=a, b=b))
     return out
-
-
-def _state(ens):
-    es = ens.state
-    v, s, f = ens.sensor_readings()
-    return (es.pH, es.chlorine, es.temperature, es.time, es.flow_rate, es.status, v, s, f, ens.boundary())
-
-
-def _assert_equal(ref, got, what):
-    for i, (a, b) in enumerate(zip(ref, got)):
-        assert np.array_equal(a, b, equal_nan=True), (what, i)
 
 
 def _image_of(values, faults, sim_time):
@@ -97,12 +66,12 @@ def _host_loop(ens, ctl, inj, interval, n_steps):
 def test_inert_program_is_bit_invisible(gpu, wt):
     N, n = 1000, 8
     cols, bc = wt.make_ensemble(N, seed=41)
-    chlorine, acid = _loops(wt, cols)
+    chlorine, acid = pi_loops(wt, cols)
     progs = [[wt.Injection(np.arange(N) % 10, "off", a=5.0)] * 4,
              [wt.Injection(3, "constant", start=K * DT + 1.0, a=0.0), wt.Injection(8, "gain", start=1e9, a=0.0)]]
     got = []
     for prog in [None] + progs + ["cleared"]:
-        ens = _plant(wt, cols, bc, n)
+        ens = plant(wt, cols, bc, n)
         ens.set_schedule(0, 7)
         ens.enable_control(chlorine, acid)
         if prog == "cleared":
@@ -111,37 +80,37 @@ def test_inert_program_is_bit_invisible(gpu, wt):
         elif prog is not None:
             ens.set_injections(*prog)
         ens.step(DT, n_steps=K, download=False)
-        got.append(_state(ens) + ens.input_image() + (ens.control_state().block(),))
+        got.append(plant_state(ens) + ens.input_image() + (ens.control_state().block(),))
         if prog not in (None, "cleared"):
             st = ens.injection_state()
             assert not st.n_applied.any() and np.isnan(st.t_first).all() and np.isnan(st.held).all()
         ens.close()
     for g in got[1:]:
-        _assert_equal(got[0], g, "inert")
+        assert_all_equal(got[0], g, "inert")
 
 
 @pytest.mark.parametrize("n, N", [(4, 2000), (8, 2000), (20, 1000), (32, 500)])
 def test_sensor_spoofing_equals_the_host_loop(gpu, wt, n, N):
     cols, bc = wt.make_ensemble(N, seed=777)
-    chlorine, acid = _loops(wt, cols)
+    chlorine, acid = pi_loops(wt, cols)
     prog = _sensor_program(wt, N, seed=n)
     block = wt.injection_block(N, *prog)
     cblock = wt.control_block(N, chlorine, acid)
     for interval in (1, 7, 50):
-        ens = _plant(wt, cols, bc, n)
+        ens = plant(wt, cols, bc, n)
         ens.set_schedule(0, interval)
         ctl, inj = ControlRef(cblock, np.zeros(N)), InjectRef(block)
         vt, ft, sim_time = _host_loop(ens, ctl, inj, interval, K)
-        ref = _state(ens)
+        ref = plant_state(ens)
         assert not ref[5].any()
         assert np.mean(inj.st[:, 0].sum(axis=0) > 0) > 0.9         # nearly every reactor gets spoofed
         ens.close()
-        ens = _plant(wt, cols, bc, n)
+        ens = plant(wt, cols, bc, n)
         ens.set_schedule(0, interval)
         ens.set_injections(*prog)
         ens.enable_control(chlorine, acid)
         ens.step(DT, n_steps=K, download=False)
-        _assert_equal(ref, _state(ens), (n, interval))
+        assert_all_equal(ref, plant_state(ens), (n, interval))
         assert np.array_equal(ens.control_state().block(), ctl.st), (n, interval)
         assert np.array_equal(ens.injection_state().block(), inj.st, equal_nan=True), (n, interval)
         img, ok = ens.input_image()
@@ -171,7 +140,7 @@ def test_command_tampering_equals_the_host_loop(gpu, wt, interval):
     prog = _command_program(wt, N)
     inj = InjectRef(wt.injection_block(N, *prog))
     master = np.array(MASTER, dtype=np.float32)[:, None].repeat(N, axis=1)
-    ens = _plant(wt, cols, bc, n)
+    ens = plant(wt, cols, bc, n)
     ens.set_schedule(0, interval)
     lt, done = np.zeros(N), 0
     while done < K:                       # the host writes what the scan at the end of this call will decode
@@ -183,14 +152,14 @@ def test_command_tampering_equals_the_host_loop(gpu, wt, interval):
         ens.write_holding(np.concatenate([ens.encode_float32(tampered[i]) for i in range(3)], axis=1))
         ens.step(DT, n_steps=c, download=False)
         lt, done = t_scan, done + c
-    ref = _state(ens) + ens.input_image()
+    ref = plant_state(ens) + ens.input_image()
     ens.close()
-    ens = _plant(wt, cols, bc, n)
+    ens = plant(wt, cols, bc, n)
     ens.set_schedule(0, interval)
     ens.write_commands(*MASTER)
     ens.set_injections(*prog)
     ens.step(DT, n_steps=K, download=False)
-    _assert_equal(ref, _state(ens) + ens.input_image(), interval)
+    assert_all_equal(ref, plant_state(ens) + ens.input_image(), interval)
     assert np.array_equal(ens.injection_state().block(), inj.st, equal_nan=True)
     assert inj.st[0, 0].min() > 0                            # every reactor's first slot acted
     assert not np.isnan(ens.boundary()).any()
@@ -205,16 +174,16 @@ def test_sensor_program_with_control_off_changes_no_plant_bit(gpu, wt):
     N, n = 2000, 8
     cols, bc = wt.make_ensemble(N, seed=61)
     prog = _sensor_program(wt, N, seed=17)
-    twin = _plant(wt, cols, bc, n)
+    twin = plant(wt, cols, bc, n)
     twin.set_schedule(0, 7)
     twin.write_commands(*MASTER)
     twin.step(DT, n_steps=K, download=False)
-    ens = _plant(wt, cols, bc, n, history=K)
+    ens = plant(wt, cols, bc, n, history=K)
     ens.set_schedule(0, 7)
     ens.write_commands(*MASTER)
     ens.set_injections(*prog)
     ens.step(DT, n_steps=K, download=False)
-    _assert_equal(_state(twin), _state(ens), "plant")
+    assert_all_equal(plant_state(twin), plant_state(ens), "plant")
     # the image differs from the twin's exactly as the restated tampering of the scans' readings says
     vh, _, fh, filled = ens.sensor_history()
     assert np.all(filled == K)
@@ -239,7 +208,7 @@ def test_attack_consequences(gpu, wt):
     N, n, c = 512, 8, 5
     cols, bc = wt.make_ensemble(N, seed=71)
     # (a) CONSTANT 0 on the reading a chlorine PI uses: every executed scan in the window saturates
-    ens = _plant(wt, cols, bc, n)
+    ens = plant(wt, cols, bc, n)
     ens.set_schedule(0, c)
     ens.enable_control(chlorine=wt.PILoop("chlorine_outlet", setpoint=2.0, kp=5.0, ki=1e-4, bias=0.1, out_max=0.8))
     ens.set_injections(wt.Injection("chlorine_outlet", "constant", start=505.0, end=1505.0, a=0.0))
@@ -256,7 +225,7 @@ def test_attack_consequences(gpu, wt):
     assert np.array_equal(ens.boundary()[6][ran], np.full(ran.sum(), float(np.float32(0.8))))
     ens.close()
     # (b) a GAIN 0 man-in-the-middle on the chlorine command: the plant gets 0, the controller believes its output
-    ens = _plant(wt, cols, bc, n)
+    ens = plant(wt, cols, bc, n)
     ens.set_schedule(0, c)
     ens.enable_control(chlorine=wt.PILoop("chlorine_outlet", setpoint=cols["initial_chlorine"] + 2.0, kp=0.5, ki=1e-4,
                                           bias=0.3))
@@ -270,7 +239,7 @@ def test_attack_consequences(gpu, wt):
     assert np.array_equal(ens.boundary()[6], np.minimum(out.astype(np.float32).astype(np.float64), 1.0))
     ens.close()
     # (c) FAULT on pH_inlet: discrete bit 0 and system_status; a loop on that sensor holds
-    ens = _plant(wt, cols, bc, n)
+    ens = plant(wt, cols, bc, n)
     ens.set_schedule(0, c)
     ens.enable_control(acid=wt.PILoop("pH_inlet", setpoint=7.0, kp=0.5, direction=-1))
     ens.set_injections(wt.Injection("pH_inlet", "fault", start=2005.0, a=3))
@@ -287,7 +256,7 @@ def test_attack_consequences(gpu, wt):
 def test_out_of_range_spoof_leaves_the_image_stale(gpu, wt):
     N, n = 256, 4
     cols, bc = wt.make_ensemble(N, seed=81)
-    ens = _plant(wt, cols, bc, n)
+    ens = plant(wt, cols, bc, n)
     ens.set_schedule(0, 5)
     ens.step(DT, n_steps=10, download=False)
     img0, ok0 = ens.input_image()
@@ -302,13 +271,13 @@ def test_out_of_range_spoof_leaves_the_image_stale(gpu, wt):
 def test_schedules_placement_and_frozen_reactors(gpu, wt):
     N, n = 3000, 8
     cols, bc = wt.make_ensemble(N, seed=2024)
-    chlorine, acid = _loops(wt, cols, seed=9)
+    chlorine, acid = pi_loops(wt, cols, seed=9)
     prog = _sensor_program(wt, N, seed=23, span=200 * DT)
     prog[3] = wt.Injection(np.arange(N) % 3 + 7, "bias", start=300.0, end=1500.0, a=0.2)
     got = []
     for v in (dict(streams=0, chunk=1), dict(streams=3, chunk=1), dict(streams=0, chunk=1, fused=False),
               dict(streams=0, chunk=1, adaptive=True)):
-        ens = _plant(wt, cols, bc, n)
+        ens = plant(wt, cols, bc, n)
         ens.set_placement(v.get("adaptive", False))
         ens.set_schedule(v["streams"], v["chunk"])
         ens.enable_control(chlorine, acid)
@@ -317,10 +286,10 @@ def test_schedules_placement_and_frozen_reactors(gpu, wt):
             ens.step(DT, n_steps=40, fused=v.get("fused", True), download=False)
         if v.get("adaptive"):
             assert ens.schedule()["redeals"] >= 1 and not np.array_equal(ens.placement()[1], np.arange(N))
-        got.append(_state(ens) + ens.input_image() + (ens.control_state().block(), ens.injection_state().block()))
+        got.append(plant_state(ens) + ens.input_image() + (ens.control_state().block(), ens.injection_state().block()))
         ens.close()
     for g, v in zip(got[1:], range(1, 4)):
-        _assert_equal(got[0], g, v)
+        assert_all_equal(got[0], g, v)
     # a reactor frozen by WT_ST_T_RANGE is not read, so no slot applies to it any more
     g = golden_json("g4_faults.json")["cold_run"]
     cfg = wt.ReactorConfiguration(**g["config"])
@@ -358,7 +327,7 @@ def test_errors_and_lifetime(gpu, wt):
         ens.injection_state()
     # the n > 32 kernel carries no injection section: such an ensemble refuses a program
     for big in (33, 40, 64):
-        other = _plant(wt, cols, bc, big)
+        other = plant(wt, cols, bc, big)
         with pytest.raises(ValueError, match="up to 32 zones"):
             other.set_injections(spoof)
         with pytest.raises(ValueError, match="no injection program"):
