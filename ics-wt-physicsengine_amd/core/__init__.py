@@ -7,6 +7,7 @@ from .reactor import (BoundaryConditions, EnsembleState, IntegratedCSTR, Physics
 from .control import ControlState, LoopState, PILoop, control_block
 from .inject import Injection, InjectionState, injection_block
 from .alarm import Alarm, AlarmState, alarm_block
+from .actuator import Actuator, ActuatorState, actuator_block
 from .chemistry import AqueousChemistry, BufferSystem, solve_pH
 from .physics import (ArrheniusParameters, FlowParameters, GeometryParameters, SpatialModel, StratificationParameters,
                       TemperatureDependentKinetics, TransportModel, run_all_validations, validate_chemistry,
@@ -18,7 +19,7 @@ from .sharding import gather_state, shard_bounds
 __all__ = ["BoundaryConditions", "EnsembleState", "IntegratedCSTR", "PhysicsEngine", "ReactorConfiguration",
            "ReactorEnsemble", "ReactorState", "Trajectory", "boundary_block", "boundary_schedule_block",
            "PILoop", "ControlState", "LoopState", "control_block", "Injection", "InjectionState", "injection_block",
-           "Alarm", "AlarmState", "alarm_block",
+           "Alarm", "AlarmState", "alarm_block", "Actuator", "ActuatorState", "actuator_block",
            "AqueousChemistry", "BufferSystem", "solve_pH", "make_ensemble", "make_boundary_schedule", "params", "sharding", "gather_state", "shard_bounds",
            # the rest of wt_simulator.core's export list (core/__init__.py:238-263)
            "TemperatureDependentKinetics", "ArrheniusParameters", "TransportModel", "GeometryParameters", "FlowParameters",

@@ -36,7 +36,7 @@ class SolverStats(C.Structure):
 
 # what libwtphys.so is built from: wtphys.hip and exactly the headers it includes
 # (tests/test_host_api.py::test_build_staleness_list_matches_the_includes)
-BUILD_SOURCES = ("wtphys.hip", "wt_device.hpp", "wt_sensors.hpp", "wt_plc.hpp", "wt_ctl.hpp", "wt_inj.hpp", "wt_alm.hpp", "wt_diag.hpp", "wt_place.hpp")
+BUILD_SOURCES = ("wtphys.hip", "wt_device.hpp", "wt_sensors.hpp", "wt_plc.hpp", "wt_ctl.hpp", "wt_inj.hpp", "wt_alm.hpp", "wt_act.hpp", "wt_diag.hpp", "wt_place.hpp")
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
@@ -137,6 +137,9 @@ def lib():
     L.wt_ensemble_alarm_words.argtypes = [vp, C.POINTER(C.c_uint16)]
     L.wt_ensemble_alarm_device.argtypes = [vp, C.POINTER(vp)]
     L.wt_ensemble_alarm_clear.argtypes = [vp]
+    L.wt_ensemble_actuator_set.argtypes = [vp, dp]
+    L.wt_ensemble_actuator_get.argtypes = [vp, dp, dp, dp]
+    L.wt_ensemble_actuator_clear.argtypes = [vp]
     L.wt_ensemble_diagnostics.argtypes = [vp, dp]
     L.wt_ensemble_wave_diag.argtypes = [vp, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int64)]
     L.wt_ensemble_size.argtypes = [vp]
@@ -155,7 +158,8 @@ def lib():
                  "wt_ensemble_control_enable", "wt_ensemble_control_retune", "wt_ensemble_control_get",
                  "wt_ensemble_control_disable", "wt_ensemble_inject_set", "wt_ensemble_inject_get", "wt_ensemble_inject_clear",
                  "wt_ensemble_alarm_set", "wt_ensemble_alarm_get", "wt_ensemble_alarm_reset", "wt_ensemble_alarm_words",
-                 "wt_ensemble_alarm_device", "wt_ensemble_alarm_clear"):
+                 "wt_ensemble_alarm_device", "wt_ensemble_alarm_clear", "wt_ensemble_actuator_set", "wt_ensemble_actuator_get",
+                 "wt_ensemble_actuator_clear"):
         getattr(L, name).restype = C.c_int
     if L.wt_abi_version() != 1:
         raise ImportError("libwtphys.so ABI version mismatch; rebuild it")

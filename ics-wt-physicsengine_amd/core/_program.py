@@ -1,6 +1,6 @@
-"""What the per-reactor scan programs (:mod:`.control`, :mod:`.inject`, :mod:`.alarm`) share on the host: the sensor
-names, names -> codes, the rows of one loop or slot, and the packing of a slot program into its block.  Each module
-keeps its own fields, defaults, off rows and ``validate_block``."""
+"""What the per-reactor scan programs (:mod:`.control`, :mod:`.inject`, :mod:`.alarm`, :mod:`.actuator`) share on
+the host: the sensor names, names -> codes, the rows of one loop or slot, and the packing of a slot program into its
+block.  Each module keeps its own fields, defaults, off rows and ``validate_block``."""
 from __future__ import annotations
 
 import numpy as np

@@ -18,7 +18,7 @@ from typing import Dict, Iterable, List, Optional, Sequence, Union
 
 import numpy as np
 
-from . import _native, _program, alarm, control, inject, params
+from . import _native, _program, actuator, alarm, control, inject, params
 
 logger = logging.getLogger(__name__)
 
@@ -670,6 +670,29 @@ class ReactorEnsemble:
     def clear_alarms(self) -> None:
         """Stop the alarm program (trips in force end with it)."""
         self._control_call(_native.lib().wt_ensemble_alarm_clear)
+
+    # -- actuator programs at every PLC scan, on the device (wt_act.hpp)
+    def set_actuators(self, *actuators: "actuator.Actuator") -> None:
+        """Put a final element with dead time, lag, rate limit, backlash and a fault window on up to three channels
+        (one :class:`Actuator` each: "acid", "chlorine", "inlet").  At every PLC scan, inside the step call and
+        downstream of the whole command path (PI outputs, command tampering, interlock trips), the element's position
+        becomes the boundary row the next step integrates under.  Every element starts at its row in force.  Replaces
+        any program.  Needs :meth:`enable_plant_io` and at most 32 zones per reactor."""
+        blk = actuator.actuator_block(self.n_reactors, *actuators)
+        self._control_call(_native.lib().wt_ensemble_actuator_set, _native.dptr(blk))
+
+    def actuator_state(self) -> "actuator.ActuatorState":
+        """Channel state, demand queues and t_prev of the actuator program (one synchronisation)."""
+        N = self.n_reactors
+        st = np.empty((len(actuator.CHANNELS), actuator.NVS, N), dtype=np.float64)
+        q = np.empty((len(actuator.CHANNELS), actuator.MAX_DELAY, N), dtype=np.float64)
+        tp = np.empty(N, dtype=np.float64)
+        self._control_call(_native.lib().wt_ensemble_actuator_get, _native.dptr(st), _native.dptr(q), _native.dptr(tp))
+        return actuator.ActuatorState.from_block(st, q, tp)
+
+    def clear_actuators(self) -> None:
+        """Stop the actuator program: from the next scan on the commands reach the plant at once."""
+        self._control_call(_native.lib().wt_ensemble_actuator_clear)
 
     # -- diagnostics (NEXT-4)
     DIAGNOSTIC_FIELDS = ("total_chlorine_mg", "total_H_mol", "total_OH_mol", "charge_balance_mol", "thermal_energy_kJ",

@@ -40,6 +40,7 @@
 #include "wt_ctl.hpp"
 #include "wt_inj.hpp"
 #include "wt_alm.hpp"
+#include "wt_act.hpp"
 
 namespace wt {
 
@@ -306,6 +307,7 @@ struct StepArgs {
     wtc::CtlArgs ctl;    // per-reactor PI programs run at PLC scans (wt_ensemble_control_*; ctl.on == 0: none)
     wti::InjArgs inj;    // per-reactor injection programs run at PLC scans (wt_ensemble_inject_*; inj.on == 0: none)
     wta::AlmArgs alm;    // per-reactor alarm and interlock programs run at PLC scans (wt_ensemble_alarm_*; alm.on == 0: none)
+    wtv::ActArgs act;    // per-reactor actuator programs run at PLC scans (wt_ensemble_actuator_*; act.on == 0: none)
 };
 static_assert(sizeof(StepArgs) <= 4096, "the kernel-argument segment holds at most 4 KiB");
 constexpr int NB = 10;     // rows of a boundary block (WT_NB)
@@ -318,6 +320,9 @@ __host__ __device__ constexpr bool inj_in_item(int LV) { return LV <= 5; }
 // kernels that carry the alarm section (wt_alm.hpp).  The n > 32 kernel compiles it out for the same reason, and
 // wt_ensemble_alarm_set refuses ensembles of more than 32 zones.
 __host__ __device__ constexpr bool alm_in_item(int LV) { return LV <= 5; }
+// kernels that carry the actuator section (wt_act.hpp).  The n > 32 kernel compiles it out for the same reason, and
+// wt_ensemble_actuator_set refuses ensembles of more than 32 zones.
+__host__ __device__ constexpr bool act_in_item(int LV) { return LV <= 5; }
 enum { Q_AVAIL = 0, Q_HEAD = 1, Q_TAIL = 2, Q_ERROR = 3, Q_TRACE = 4, Q_DONE = 5, Q_WORDS = 16 };
 
 // ---------------------------------------------------------------- lane geometry and cross-lane moves
@@ -2392,10 +2397,16 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
                         if (inj) wti::tamper_sensors(fresh(pa)->inj, rr, &io.val[0][lane], &io.fault[0][lane], wts::RMAX, lt + dt);
                         wtp::pack_inputs(b->sens.pack, rr, &io.val[0][lane], &io.fault[0][lane], wts::RMAX, lt);   // update_modbus_inputs
                         double c[3];
-                        if (inj) wtp::apply_commands(b->sens.cmd, rr, c, wti::command_tamper(fresh(pa)->inj, rr, lt + dt));
-                        else wtp::apply_commands(b->sens.cmd, rr, c);    // read_modbus_commands + apply_boundary_conditions
+                        // an actuator program (wave-uniform flag) needs the inlet row as it was before this scan
+                        const bool act = act_in_item(LV) && WT_RARE(fresh(pa)->act.on);
+                        const double row0 = act ? b->sens.cmd.bc[rr] : 0.0;
+                        double inlet_v;
+                        if (inj) inlet_v = wtp::apply_commands(b->sens.cmd, rr, c, wti::command_tamper(fresh(pa)->inj, rr, lt + dt));
+                        else inlet_v = wtp::apply_commands(b->sens.cmd, rr, c);    // read_modbus_commands + apply_boundary_conditions
                         // an alarm program's trips in force (from the previous scan) replace the validated commands
                         if (alm_in_item(LV) && WT_RARE(fresh(pa)->alm.on)) wta::override_commands(fresh(pa)->alm, b->sens.cmd, rr, c);
+                        // the final elements, downstream of the whole command path: their positions are what the plant gets
+                        if (act) wtv::actuate(fresh(pa)->act, b->sens.cmd, rr, c, inlet_v, row0, lt + dt);
                         io.cmd[0][lane] = c[0]; io.cmd[1][lane] = c[1]; io.cmd[2][lane] = c[2];
                     }
                     b->sens.pack.loop_time[rr] = lt + dt;                 // sim_time += dt (__main__.py:446)

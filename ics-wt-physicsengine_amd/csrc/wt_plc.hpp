@@ -78,10 +78,11 @@ __device__ __forceinline__ double validate_flow_rate(float v, double max_value)
 struct NoTamper { __device__ __forceinline__ void operator()(float &, float &, float &) const {} };
 
 // read_modbus_commands validates, apply_boundary_conditions validates again (idempotent).  Writes the boundary
-// block and returns the three rows in force afterwards (cmd[0] inlet, cmd[1] acid, cmd[2] chlorine flow).
+// block and returns the three rows in force afterwards (cmd[0] inlet, cmd[1] acid, cmd[2] chlorine flow); the
+// function's value is the validated inlet word, significant or not (an actuator program's inlet demand, wt_act.hpp).
 // tamper: what a man-in-the-middle does to the three decoded floats (acid, chlorine, inlet) before they are
 // validated (wti::CommandTamper); the holding image is not touched.
-template <class A, class T = NoTamper> __device__ __forceinline__ void apply_commands(const A &a, int64_t r, double cmd[3], const T &tamper = T())
+template <class A, class T = NoTamper> __device__ __forceinline__ double apply_commands(const A &a, int64_t r, double cmd[3], const T &tamper = T())
 {
     const uint16_t *hr = a.hr + r * HR_WORDS;
     float acid = __uint_as_float(((uint32_t)hr[0] << 16) | hr[1]);
@@ -95,6 +96,7 @@ template <class A, class T = NoTamper> __device__ __forceinline__ void apply_com
     a.bc[4 * a.N + r] = cmd[1];
     a.bc[6 * a.N + r] = cmd[2];
     if (inlet_v > 0.1) a.bc[0 * a.N + r] = inlet_v;
+    return inlet_v;
 }
 
 } // namespace wtp

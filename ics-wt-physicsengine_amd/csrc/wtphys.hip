@@ -118,6 +118,9 @@ struct wt_ensemble {
     bool alm_on = false;
     double *a_par = nullptr, *a_st = nullptr, *a_rst = nullptr;   // [N][wta::PAR_DOUBLES], [N][wta::ST_DOUBLES], [N][wta::RST_DOUBLES]
     uint16_t *a_word = nullptr;                                   // [N]
+    // optional per-reactor actuator programs (wt_act.hpp), indexed by reactor
+    bool act_on = false;
+    double *v_par = nullptr, *v_st = nullptr, *v_q = nullptr, *v_tp = nullptr;   // [N][wtv::PAR_DOUBLES], [N][wtv::ST_DOUBLES], [N][wtv::Q_DOUBLES], [N]
 };
 
 namespace {
@@ -162,6 +165,7 @@ wt::StepArgs make_args(const wt_ensemble *h, double dt, int n_steps, int first_s
     a.ctl.on = h->ctl_on ? 1 : 0; a.ctl.par = h->c_par; a.ctl.st = h->c_st; a.ctl.hr = h->p_hr;
     a.inj.on = h->inj_on ? 1 : 0; a.inj.par = h->i_par; a.inj.st = h->i_st;
     a.alm.on = h->alm_on ? 1 : 0; a.alm.par = h->a_par; a.alm.st = h->a_st; a.alm.rst = h->a_rst; a.alm.word = h->a_word;
+    a.act.on = h->act_on ? 1 : 0; a.act.par = h->v_par; a.act.st = h->v_st; a.act.q = h->v_q; a.act.tp = h->v_tp;
     return a;
 }
 
@@ -212,6 +216,14 @@ ProgramArrays alarm_arrays(wt_ensemble *h)
                                  {(void **)&h->a_word, sizeof(uint16_t)}}};
 }
 
+ProgramArrays actuator_arrays(wt_ensemble *h)
+{
+    return {h->act_on, "actuator", {{(void **)&h->v_par, sizeof(double) * wtv::PAR_DOUBLES},
+                                    {(void **)&h->v_st, sizeof(double) * wtv::ST_DOUBLES},
+                                    {(void **)&h->v_q, sizeof(double) * wtv::Q_DOUBLES},
+                                    {(void **)&h->v_tp, sizeof(double)}}};
+}
+
 void release_program(const ProgramArrays &p)
 {
     for (const auto &a : p.arrays) free_and_null(*a.first);
@@ -229,7 +241,7 @@ int alloc_program(const ProgramArrays &p, int64_t N)
     return WT_OK;
 }
 
-// the body of control_disable, inject_clear and alarm_clear
+// the body of control_disable, inject_clear, alarm_clear and actuator_clear
 int stop_program(wt_ensemble *h, const ProgramArrays &p)
 {
     HIP_TRY(hipSetDevice(h->device));
@@ -492,6 +504,7 @@ int wt_ensemble_destroy(wt_ensemble *h)
     release_program(control_arrays(h));
     release_program(inject_arrays(h));
     release_program(alarm_arrays(h));
+    release_program(actuator_arrays(h));
     if (h->snap_host) (void)hipHostFree(h->snap_host);
     if (h->err_host) (void)hipHostFree(h->err_host);
     for (hipEvent_t e : h->lt_pool) (void)hipEventDestroy(e);
@@ -1295,6 +1308,112 @@ int wt_ensemble_alarm_clear(wt_ensemble *h)
 {
     if (!h) return fail(WT_E_ARG, "NULL handle");
     return stop_program(h, alarm_arrays(h));
+}
+
+} // extern "C"
+
+namespace {
+
+static_assert(WT_ACT_CHANNELS == wtv::CH && WT_NV == wtv::NV && WT_NVS == wtv::NVS && WT_ACT_MAX_DELAY == wtv::MAX_DELAY,
+              "actuator blocks of the C ABI");
+static_assert(WT_ACT_ACID == wtv::CH_ACID && WT_ACT_CHLORINE == wtv::CH_CHLORINE && WT_ACT_INLET == wtv::CH_INLET &&
+              WT_ACT_INLET + 7 == WT_INJ_CMD_INLET && WT_ACT_STUCK == wtv::F_STUCK && WT_ACT_FAIL_TO == wtv::F_FAIL_TO &&
+              WT_ACT_FAIL_TO + 1 == wtv::N_FAULTS, "actuator channels and faults of the C ABI");
+static_assert(WT_V_FAIL_VALUE == wtv::V_FAIL_VALUE && WT_VS_N_FAULT == wtv::VS_N_FAULT, "actuator rows of the C ABI");
+
+// Host-side checks of a [WT_ACT_CHANNELS][WT_NV][N] program; nullptr when it is valid.  core/actuator.py
+// validate_block makes the same checks in the same order.
+const char *actuator_params_error(const double *p, int64_t N)
+{
+    const auto is_int_in = [](double x, int lo, int hi) { return x == std::floor(x) && x >= lo && x <= hi; };
+    const auto at = [&](int k, int v, int64_t r) { return p[((int64_t)k * wtv::NV + v) * N + r]; };
+    for (int k = 0; k < wtv::CH; ++k)
+        for (int64_t r = 0; r < N; ++r)
+            for (int v = 0; v < wtv::NV; ++v) {
+                const double x = at(k, v, r);
+                const bool inf_ok = (v == wtv::V_RATE || v == wtv::V_T_REPAIR) && x == INFINITY;
+                if (!std::isfinite(x) && !inf_ok) return "actuator parameters must be finite (rate and t_repair may be +inf)";
+            }
+    for (int k = 0; k < wtv::CH; ++k)
+        for (int64_t r = 0; r < N; ++r) {
+            double c[wtv::NV];
+            for (int v = 0; v < wtv::NV; ++v) c[v] = at(k, v, r);
+            if (!is_int_in(c[wtv::V_ENABLE], 0, 1)) return "enable must be 0 or 1";
+            if (!(c[wtv::V_TAU] >= 0)) return "tau must be >= 0";
+            if (!(c[wtv::V_RATE] > 0)) return "rate must be > 0";
+            if (!(c[wtv::V_BACKLASH] >= 0)) return "backlash must be >= 0";
+            if (!is_int_in(c[wtv::V_DELAY], 0, wtv::MAX_DELAY)) return "delay must be an integer in 0..8";
+            if (!is_int_in(c[wtv::V_FAULT], 0, 2)) return "fault must be 0 (none), 1 (stuck) or 2 (fail_to)";
+            if (!(c[wtv::V_T_REPAIR] >= c[wtv::V_T_FAULT])) return "t_repair must be >= t_fault";
+            if (c[wtv::V_FAULT] == wtv::F_FAIL_TO) {
+                const double fv = c[wtv::V_FAIL_VALUE];
+                if (k == wtv::CH_INLET && !(fv > wtv::INLET_MIN && fv <= wtv::limit_of(k)))
+                    return "an inlet fail_to fail_value must be in (0.1, 20]";
+                if (k != wtv::CH_INLET && !(fv >= 0 && fv <= wtv::limit_of(k)))
+                    return "a fail_to fail_value must be in [0, limit]: 2 for acid, 1 for chlorine";
+            }
+        }
+    return nullptr;
+}
+
+const char *k_no_actuator = "no actuator program is set (wt_ensemble_actuator_set)";
+
+} // namespace
+
+extern "C" {
+
+int wt_ensemble_actuator_set(wt_ensemble *h, const double *params)
+{
+    if (!h || !params) return fail(WT_E_ARG, "NULL argument");
+    if (!h->plc_on) return fail(WT_E_STATE, "actuators act on the plant I/O scan: enable plant I/O first");
+    if (!wt::act_in_item(levels_for(h->n))) return fail(WT_E_STATE, "actuator programs run in the kernels for up to 32 zones");
+    if (const char *msg = actuator_params_error(params, h->N)) return fail(WT_E_ARG, msg);
+    HIP_TRY(hipSetDevice(h->device));
+    const int64_t N = h->N;
+    std::vector<double> par((size_t)N * wtv::PAR_DOUBLES), st((size_t)N * wtv::ST_DOUBLES, 0.0), q((size_t)N * wtv::Q_DOUBLES);
+    std::vector<double> lt((size_t)N), bc((size_t)N * wt::NB);
+    blocks_to_records(params, wtv::CH, wtv::NV, N, par.data(), wtv::PAR_DOUBLES);
+    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still read or write the old records
+    HIP_TRY(hipMemcpyAsync(lt.data(), h->p_loop_time, sizeof(double) * lt.size(), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(bc.data(), h->bc, sizeof(double) * bc.size(), hipMemcpyDeviceToHost, h->stream));
+    if (int rc = sync_checked(h)) return rc;
+    for (int64_t r = 0; r < N; ++r)
+        for (int k = 0; k < wtv::CH; ++k) {
+            const double row = bc[(size_t)(wtv::row_of(k) * N + r)];
+            double *s = st.data() + r * wtv::ST_DOUBLES + k * wtv::NVS;
+            s[wtv::VS_POSITION] = s[wtv::VS_APPLIED] = s[wtv::VS_PLAY] = s[wtv::VS_DEMAND] = row;
+            for (int i = 0; i < wtv::MAX_DELAY; ++i) q[(size_t)(r * wtv::Q_DOUBLES + k * wtv::MAX_DELAY + i)] = row;
+        }
+    if (int rc = alloc_program(actuator_arrays(h), N)) return rc;
+    HIP_TRY(hipMemcpyAsync(h->v_par, par.data(), sizeof(double) * par.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->v_st, st.data(), sizeof(double) * st.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->v_q, q.data(), sizeof(double) * q.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->v_tp, lt.data(), sizeof(double) * lt.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // the host vectors are freed on return
+    h->act_on = true;
+    return WT_OK;
+}
+
+int wt_ensemble_actuator_get(wt_ensemble *h, double *state, double *queue, double *t_prev)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    if (!h->act_on) return fail(WT_E_STATE, k_no_actuator);
+    HIP_TRY(hipSetDevice(h->device));
+    const int64_t N = h->N;
+    std::vector<double> st((size_t)N * wtv::ST_DOUBLES), q((size_t)N * wtv::Q_DOUBLES);
+    HIP_TRY(hipMemcpyAsync(st.data(), h->v_st, sizeof(double) * st.size(), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpyAsync(q.data(), h->v_q, sizeof(double) * q.size(), hipMemcpyDeviceToHost, h->stream));
+    if (t_prev) HIP_TRY(hipMemcpyAsync(t_prev, h->v_tp, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost, h->stream));
+    if (int rc = sync_checked(h)) return rc;
+    if (state) records_to_blocks(st.data(), wtv::ST_DOUBLES, wtv::CH, wtv::NVS, N, state);
+    if (queue) records_to_blocks(q.data(), wtv::Q_DOUBLES, wtv::CH, wtv::MAX_DELAY, N, queue);
+    return WT_OK;
+}
+
+int wt_ensemble_actuator_clear(wt_ensemble *h)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    return stop_program(h, actuator_arrays(h));
 }
 
 int wt_ensemble_get_boundary(wt_ensemble *h, double *bc)

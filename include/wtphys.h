@@ -398,6 +398,61 @@ int wt_ensemble_alarm_device(wt_ensemble *h, void **word);
 /* program off, buffers freed (no effect while none is set) */
 int wt_ensemble_alarm_clear(wt_ensemble *h);
 
+/* ---- per-reactor actuator programs: the dosing pumps and the inlet valve between the command path and the plant ----
+ * The reference's roadmap lists actuator dynamics (valves, pumps) next to its PID module.  One optional final element
+ * per reactor and channel: 0 acid (boundary row 4, limit 2.0), 1 chlorine (row 6, limit 1.0), 2 inlet (row 0, limit
+ * 20.0), the order of WT_INJ_CMD_*.  Parameters [WT_ACT_CHANNELS][WT_NV][N]: enable (0 or 1), tau >= 0 (seconds,
+ * first-order lag), rate > 0 (units per second, +inf: none), backlash >= 0, delay (an integer 0..WT_ACT_MAX_DELAY,
+ * scans), fault (0 NONE, 1 STUCK, 2 FAIL_TO), t_fault, t_repair >= t_fault (+inf: never), fail_value; all finite
+ * except rate and t_repair; under FAIL_TO fail_value in [0, limit] for acid and chlorine and in (0.1, 20] for the
+ * inlet; otherwise WT_E_ARG.  Channel state [WT_ACT_CHANNELS][WT_NVS][N]: position, applied, play, demand, delivered,
+ * travel, n_exec, n_rate, n_fault.  set replaces any program: every channel starts with position = play = demand =
+ * applied = its boundary row in force and the queue filled with that value, delivered, travel and the counts 0, and
+ * t_prev the reactor's loop time.  wt_ensemble_set_boundary later moves no actuator state.
+ * At every PLC scan of a reactor that stepped, right after read_modbus_commands decoded and validated the holding
+ * words (after any command tamper) and the alarm program's trips, with t = the loop time the scan stores, in fp64
+ * without fused multiply-adds:
+ *   h = t - t_prev; t_prev = t;
+ *   for each enabled channel k = 0..2:
+ *     u = acid: the acid command; chlorine: the chlorine command;
+ *         inlet: the validated inlet word if it is > 0.1, else demand (the positioner keeps its last setpoint);
+ *     delivered += applied * h;  demand = u;
+ *     ud = delay == 0 ? u : q[delay - 1];  q shifts by one, q[0] = u   (q: the last WT_ACT_MAX_DELAY demands, newest first)
+ *     half = backlash * 0.5;  play = fmax(ud - half, fmin(ud + half, play));
+ *     pl = tau > 0 ? (tau * position + h * play) / (tau + h) : play;           (backward Euler)
+ *     lim = rate * h;  d = pl - position;
+ *     pn = d > lim ? position + lim : d < -lim ? position - lim : pl;  n_rate += (pn != pl);
+ *     if fault != NONE and t_fault <= t < t_repair: pn = STUCK ? position : fail_value, n_fault += 1;
+ *     travel += fabs(pn - position);  position = pn;  n_exec += 1;
+ *     a = fmin(fmax(position, 0.0), limit);
+ *     acid, chlorine: applied = a, and a is the command and the boundary row;
+ *     inlet: if a > 0.1: applied = a, and a is the command and row 0; otherwise row 0 keeps the value it had before
+ *            the scan (the reference's inlet rule) and applied stays.
+ * The position is a double, not a float32 register: a channel with tau 0, rate +inf, backlash 0, delay 0 and no fault
+ * gives exactly the commands of no program.  A disabled channel never touches its row; reactors that did not step get
+ * no evaluation and keep t_prev.  The holding image keeps the master's words.  Needs plant I/O and n <= 32 zones
+ * (WT_E_STATE); all synchronise. */
+#define WT_ACT_CHANNELS 3
+#define WT_ACT_MAX_DELAY 8
+enum { WT_ACT_ACID = 0, WT_ACT_CHLORINE = 1, WT_ACT_INLET = 2 };
+enum { WT_ACT_NONE = 0, WT_ACT_STUCK = 1, WT_ACT_FAIL_TO = 2 };
+enum {
+    WT_V_ENABLE = 0, WT_V_TAU = 1, WT_V_RATE = 2, WT_V_BACKLASH = 3, WT_V_DELAY = 4, WT_V_FAULT = 5, WT_V_T_FAULT = 6,
+    WT_V_T_REPAIR = 7, WT_V_FAIL_VALUE = 8,
+    WT_NV = 9
+};
+enum {
+    WT_VS_POSITION = 0, WT_VS_APPLIED = 1, WT_VS_PLAY = 2, WT_VS_DEMAND = 3, WT_VS_DELIVERED = 4, WT_VS_TRAVEL = 5,
+    WT_VS_N_EXEC = 6, WT_VS_N_RATE = 7, WT_VS_N_FAULT = 8,
+    WT_NVS = 9
+};
+int wt_ensemble_actuator_set(wt_ensemble *h, const double *params /* [WT_ACT_CHANNELS][WT_NV][N] */);
+/* host [WT_ACT_CHANNELS][WT_NVS][N] channel state, [WT_ACT_CHANNELS][WT_ACT_MAX_DELAY][N] demand queues (newest
+ * first) and [N] t_prev (any may be NULL); WT_E_STATE while no program is set */
+int wt_ensemble_actuator_get(wt_ensemble *h, double *state, double *queue, double *t_prev);
+/* program off, buffers freed (no effect while none is set) */
+int wt_ensemble_actuator_clear(wt_ensemble *h);
+
 /* ---- reactor diagnostics (SURVEY.md section 8(f) NEXT-4): reductions over the zones of every reactor ----
  * out: host [WT_N_DIAG][N] doubles, rows
  *   0 total_chlorine_mg, 1 total_H_mol, 2 total_OH_mol, 3 charge_balance_mol, 4 thermal_energy_kJ
