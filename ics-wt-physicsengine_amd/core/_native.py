@@ -18,6 +18,7 @@ CSRC = os.path.join(_PKG, "csrc")
 LIB_PATH = os.environ.get("WTPHYS_LIB", os.path.join(CSRC, "libwtphys.so"))  # override: diagnostic builds
 
 WT_OK, WT_E_ARG, WT_E_HIP, WT_E_NOGPU, WT_E_STATE = 0, 1, 2, 3, 4
+WT_PROG_CONTROL, WT_PROG_INJECT, WT_PROG_ALARM, WT_PROG_ACTUATOR = 0, 1, 2, 3   # wt_program_check
 
 
 class WtError(RuntimeError):
@@ -140,6 +141,7 @@ def lib():
     L.wt_ensemble_actuator_set.argtypes = [vp, dp]
     L.wt_ensemble_actuator_get.argtypes = [vp, dp, dp, dp]
     L.wt_ensemble_actuator_clear.argtypes = [vp]
+    L.wt_program_check.argtypes = [C.c_int, dp, C.c_int64]
     L.wt_ensemble_diagnostics.argtypes = [vp, dp]
     L.wt_ensemble_wave_diag.argtypes = [vp, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int64)]
     L.wt_ensemble_size.argtypes = [vp]
@@ -159,7 +161,7 @@ def lib():
                  "wt_ensemble_control_disable", "wt_ensemble_inject_set", "wt_ensemble_inject_get", "wt_ensemble_inject_clear",
                  "wt_ensemble_alarm_set", "wt_ensemble_alarm_get", "wt_ensemble_alarm_reset", "wt_ensemble_alarm_words",
                  "wt_ensemble_alarm_device", "wt_ensemble_alarm_clear", "wt_ensemble_actuator_set", "wt_ensemble_actuator_get",
-                 "wt_ensemble_actuator_clear"):
+                 "wt_ensemble_actuator_clear", "wt_program_check"):
         getattr(L, name).restype = C.c_int
     if L.wt_abi_version() != 1:
         raise ImportError("libwtphys.so ABI version mismatch; rebuild it")

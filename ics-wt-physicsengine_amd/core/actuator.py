@@ -13,12 +13,11 @@ from typing import Union
 
 import numpy as np
 
-from ._program import codes, field_rows
+from . import _native
+from ._program import check, codes, field_rows
 
 CHANNELS = ("acid", "chlorine", "inlet")   # WT_ACT_ACID, WT_ACT_CHLORINE, WT_ACT_INLET: the order of WT_INJ_CMD_*
 ROWS = (4, 6, 0)                           # the boundary row of each channel
-LIMITS = (2.0, 1.0, 20.0)
-INLET_MIN = 0.1                            # an inlet command at or below this is insignificant
 NV, NVS, MAX_DELAY = 9, 9, 8               # WT_NV, WT_NVS, WT_ACT_MAX_DELAY
 PARAM_ROWS = ("enable", "tau", "rate", "backlash", "delay", "fault", "t_fault", "t_repair", "fail_value")
 STATE_ROWS = ("position", "applied", "play", "demand", "delivered", "travel", "n_exec", "n_rate", "n_fault")
@@ -81,42 +80,9 @@ def channel_rows(act: Actuator, n: int, name: str = "actuator") -> np.ndarray:
     return field_rows(act, PARAM_ROWS, n, name, enable=1.0, fault=codes(act.fault, FAULTS, "fault"))
 
 
-def validate_block(block: np.ndarray) -> None:
-    """The checks ``wt_ensemble_actuator_set`` makes, in its order; ``ValueError`` names the first one that fails."""
-    p = {k: block[:, i] for i, k in enumerate(PARAM_ROWS)}
-
-    def int_in(x, lo, hi):
-        return np.all((x == np.floor(x)) & (x >= lo) & (x <= hi))
-
-    inf_ok = np.zeros(block.shape, dtype=bool)
-    inf_ok[:, [PARAM_ROWS.index("rate"), PARAM_ROWS.index("t_repair")]] = True
-    if not np.all(np.isfinite(block) | (inf_ok & (block == np.inf))):
-        raise ValueError("actuator parameters must be finite (rate and t_repair may be +inf)")
-    if not int_in(p["enable"], 0, 1):
-        raise ValueError("enable must be 0 or 1")
-    if not np.all(p["tau"] >= 0):
-        raise ValueError("tau must be >= 0")
-    if not np.all(p["rate"] > 0):
-        raise ValueError("rate must be > 0")
-    if not np.all(p["backlash"] >= 0):
-        raise ValueError("backlash must be >= 0")
-    if not int_in(p["delay"], 0, MAX_DELAY):
-        raise ValueError("delay must be an integer in 0..8")
-    if not int_in(p["fault"], 0, 2):
-        raise ValueError("fault must be 0 (none), 1 (stuck) or 2 (fail_to)")
-    if not np.all(p["t_repair"] >= p["t_fault"]):
-        raise ValueError("t_repair must be >= t_fault")
-    fv, fail_to = p["fail_value"], p["fault"] == 2
-    if np.any(fail_to[2] & ~((fv[2] > INLET_MIN) & (fv[2] <= LIMITS[2]))):
-        raise ValueError("an inlet fail_to fail_value must be in (0.1, 20]")
-    for k in (0, 1):
-        if np.any(fail_to[k] & ~((fv[k] >= 0) & (fv[k] <= LIMITS[k]))):
-            raise ValueError("a fail_to fail_value must be in [0, limit]: 2 for acid, 1 for chlorine")
-
-
 def actuator_block(n_reactors: int, *actuators: Actuator) -> np.ndarray:
-    """The [WT_ACT_CHANNELS][WT_NV][N] float64 block of ``wt_ensemble_actuator_set``, validated: each actuator fills
-    the rows of its channel, a channel without one holds :data:`OFF_ROW` (the defaults with enable 0)."""
+    """The [WT_ACT_CHANNELS][WT_NV][N] float64 block of ``wt_ensemble_actuator_set``, checked by the library: each
+    actuator fills the rows of its channel, a channel without one holds :data:`OFF_ROW` (the defaults with enable 0)."""
     n = int(n_reactors)
     block = np.repeat(np.repeat(OFF_ROW[None, :, None], len(CHANNELS), axis=0), n, axis=2)
     seen = set()
@@ -129,5 +95,5 @@ def actuator_block(n_reactors: int, *actuators: Actuator) -> np.ndarray:
             raise ValueError(f"two actuators on the {act.channel} channel: at most one per channel")
         seen.add(act.channel)
         block[CHANNELS.index(act.channel)] = channel_rows(act, n, f"actuator {act.channel}")
-    validate_block(block)
+    check(_native.WT_PROG_ACTUATOR, block)
     return block

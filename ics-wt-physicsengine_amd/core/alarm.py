@@ -13,6 +13,7 @@ from typing import Optional, Union
 
 import numpy as np
 
+from . import _native
 from ._program import SENSOR_NAMES, codes, field_rows, slot_block
 
 SLOTS, NA, NAS, NAR = 4, 10, 8, 6        # WT_ALM_SLOTS, WT_NA, WT_NAS, WT_NAR
@@ -91,40 +92,8 @@ def slot_rows(alarm: Alarm, n: int, name: str = "alarm") -> np.ndarray:
                       action=codes("none" if alarm.action is None else alarm.action, ACTIONS, "action"))
 
 
-def validate_block(block: np.ndarray) -> None:
-    """The checks ``wt_ensemble_alarm_set`` makes, in its order; ``ValueError`` names the first one that fails."""
-    p = {k: block[:, i] for i, k in enumerate(PARAM_ROWS)}
-
-    def int_in(x, lo, hi):
-        return np.all((x == np.floor(x)) & (x >= lo) & (x <= hi))
-
-    if not np.isfinite(block).all():
-        raise ValueError("alarm parameters must be finite")
-    if not int_in(p["kind"], 0, 2):
-        raise ValueError("kind must be 0 (off), 1 (high) or 2 (low)")
-    if not int_in(p["sensor"], 0, len(SENSOR_NAMES) - 1):
-        raise ValueError("sensor must be an integer in 0..6")
-    if not int_in(p["source"], 0, 1):
-        raise ValueError("source must be 0 (image) or 1 (field)")
-    if np.any(p["deadband"] < 0):
-        raise ValueError("deadband must be >= 0")
-    if np.any(p["on_delay"] < 0):
-        raise ValueError("on_delay must be >= 0")
-    if not int_in(p["latch"], 0, 1):
-        raise ValueError("latch must be 0 or 1")
-    if not int_in(p["on_bad"], 0, 1):
-        raise ValueError("on_bad must be 0 (hold) or 1 (alarm)")
-    if not int_in(p["action"], 0, 2):
-        raise ValueError("action must be 0 (none), 1 (trip_acid) or 2 (trip_chlorine)")
-    tv = p["trip_value"]
-    if np.any((p["action"] == 1) & ~((tv >= 0) & (tv <= 2.0))):
-        raise ValueError("a trip_acid slot's trip_value must be in [0, 2]")
-    if np.any((p["action"] == 2) & ~((tv >= 0) & (tv <= 1.0))):
-        raise ValueError("a trip_chlorine slot's trip_value must be in [0, 1]")
-
-
 def alarm_block(n_reactors: int, *alarms: Alarm) -> np.ndarray:
-    """The [WT_ALM_SLOTS][WT_NA][N] float64 block of ``wt_ensemble_alarm_set``, validated: slot k is the k-th alarm,
-    the slots after the last are off."""
+    """The [WT_ALM_SLOTS][WT_NA][N] float64 block of ``wt_ensemble_alarm_set``, checked by the library: slot k is the
+    k-th alarm, the slots after the last are off."""
     n = int(n_reactors)
-    return slot_block(alarms, n, SLOTS, "alarm", slot_rows, np.zeros((NA, n)), validate_block)
+    return slot_block(alarms, n, SLOTS, "alarm", slot_rows, np.zeros((NA, n)), _native.WT_PROG_ALARM)

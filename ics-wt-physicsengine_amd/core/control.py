@@ -13,7 +13,8 @@ from typing import Optional, Union
 
 import numpy as np
 
-from ._program import SENSOR_NAMES, codes, field_rows
+from . import _native
+from ._program import SENSOR_NAMES, check, codes, field_rows
 
 LOOPS = ("chlorine", "acid")            # loop index order of the blocks
 NC, NCS = 9, 8                          # WT_NC, WT_NCS
@@ -89,27 +90,10 @@ def loop_rows(loop: Optional[PILoop], name: str, n: int) -> np.ndarray:
                       out_max=COMMAND_LIMIT[name] if loop.out_max is None else loop.out_max)
 
 
-def validate_block(block: np.ndarray) -> None:
-    """The checks ``wt_ensemble_control_enable`` makes; ``ValueError`` names the first one that fails."""
-    if not np.all(np.isfinite(block)):
-        raise ValueError("control parameters must be finite")
-    p = {k: block[:, i] for i, k in enumerate(PARAM_ROWS)}
-    if not np.all((p["enable"] == 0) | (p["enable"] == 1)):
-        raise ValueError("enable must be 0 or 1")
-    s = p["sensor"]
-    if not np.all((s == np.floor(s)) & (s >= 0) & (s < len(SENSOR_NAMES))):
-        raise ValueError("sensor must be an integer in 0..6")
-    if not np.all(np.abs(p["direction"]) == 1):
-        raise ValueError("direction must be +1 or -1")
-    if not np.all((p["kp"] >= 0) & (p["ki"] >= 0)):
-        raise ValueError("kp and ki must be >= 0")
-    if not np.all(p["out_min"] <= p["out_max"]):
-        raise ValueError("out_min must not exceed out_max")
-
-
 def control_block(n_reactors: int, chlorine: Optional[PILoop] = None, acid: Optional[PILoop] = None) -> np.ndarray:
-    """The [WT_CTL_LOOPS][WT_NC][N] float64 parameter block of ``wt_ensemble_control_enable``, validated."""
+    """The [WT_CTL_LOOPS][WT_NC][N] float64 parameter block of ``wt_ensemble_control_enable``, checked by the
+    library."""
     n = int(n_reactors)
     block = np.ascontiguousarray(np.stack([loop_rows(chlorine, "chlorine", n), loop_rows(acid, "acid", n)]))
-    validate_block(block)
+    check(_native.WT_PROG_CONTROL, block)
     return block

@@ -14,6 +14,7 @@ from typing import Union
 
 import numpy as np
 
+from . import _native
 from ._program import SENSOR_NAMES, codes, field_rows, slot_block
 
 SLOTS, NI, NIS = 4, 6, 4                 # WT_INJ_SLOTS, WT_NI, WT_NIS
@@ -22,7 +23,6 @@ STATE_ROWS = ("n_applied", "t_first", "t_last", "held")
 MODES = ("off", "bias", "gain", "constant", "ramp", "freeze", "dropout", "fault")
 COMMAND_NAMES = ("acid_flow_rate", "chlorine_flow_rate", "inlet_flow_rate")
 TARGETS = SENSOR_NAMES + COMMAND_NAMES   # index = target code (WT_INJ_CMD_ACID = 7 ...)
-FAULT = MODES.index("fault")
 
 Value = Union[float, int, str, np.ndarray]
 
@@ -75,30 +75,8 @@ def slot_rows(inj: Injection, n: int, name: str = "injection") -> np.ndarray:
                       target=codes(inj.target, TARGETS, "target"))
 
 
-def validate_block(block: np.ndarray) -> None:
-    """The checks ``wt_ensemble_inject_set`` makes; ``ValueError`` names the first one that fails."""
-    p = {k: block[:, i] for i, k in enumerate(PARAM_ROWS)}
-    finite = np.isfinite(block)
-    finite[:, PARAM_ROWS.index("end")] |= p["end"] == np.inf
-    if not finite.all():
-        raise ValueError("injection parameters must be finite (end may be +inf)")
-    m, tg = p["mode"], p["target"]
-    if not np.all((m == np.floor(m)) & (m >= 0) & (m < len(MODES))):
-        raise ValueError("mode must be an integer in 0..7")
-    if not np.all((tg == np.floor(tg)) & (tg >= 0) & (tg < len(TARGETS))):
-        raise ValueError("target must be an integer in 0..9")
-    if not np.all(p["start"] <= p["end"]):
-        raise ValueError("start must not exceed end")
-    fault = m == FAULT
-    if np.any(fault & (tg >= len(SENSOR_NAMES))):
-        raise ValueError("a FAULT slot must target a sensor")
-    a = p["a"]
-    if np.any(fault & ~((a == np.floor(a)) & (a >= 1) & (a <= 6))):
-        raise ValueError("a FAULT slot's fault code (a) must be an integer in 1..6")
-
-
 def injection_block(n_reactors: int, *injections: Injection) -> np.ndarray:
-    """The [WT_INJ_SLOTS][WT_NI][N] float64 block of ``wt_ensemble_inject_set``, validated: slot k is the k-th
-    injection, the slots after the last are off."""
+    """The [WT_INJ_SLOTS][WT_NI][N] float64 block of ``wt_ensemble_inject_set``, checked by the library: slot k is the
+    k-th injection, the slots after the last are off."""
     n = int(n_reactors)
-    return slot_block(injections, n, SLOTS, "injection", slot_rows, _off_rows(n), validate_block)
+    return slot_block(injections, n, SLOTS, "injection", slot_rows, _off_rows(n), _native.WT_PROG_INJECT)

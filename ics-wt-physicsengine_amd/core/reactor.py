@@ -591,7 +591,6 @@ class ReactorEnsemble:
         rows = [old[i] if loop is None else control.loop_rows(loop, name, self.n_reactors)
                 for i, (name, loop) in enumerate(zip(control.LOOPS, (chlorine, acid)))]
         blk = np.ascontiguousarray(np.stack(rows))
-        control.validate_block(blk)
         self._control_call(_native.lib().wt_ensemble_control_retune, _native.dptr(blk))
         self._control_params = blk
 

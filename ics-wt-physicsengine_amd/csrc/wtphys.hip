@@ -1074,11 +1074,11 @@ const char *inject_params_error(const double *p, int64_t N)
             for (int k = 0; k < wti::NI; ++k) c[k] = p[((int64_t)s * wti::NI + k) * N + r];
             for (int k = 0; k < wti::NI; ++k)
                 if (!std::isfinite(c[k]) && !(k == wti::I_T_END && c[k] == INFINITY))
-                    return "injection parameters must be finite (t_end may be +inf)";
+                    return "injection parameters must be finite (end may be +inf)";
             const double mode = c[wti::I_MODE], target = c[wti::I_TARGET];
             if (mode != std::floor(mode) || mode < 0 || mode >= wti::N_MODES) return "mode must be an integer in 0..7";
             if (target != std::floor(target) || target < 0 || target >= wti::N_TARGETS) return "target must be an integer in 0..9";
-            if (c[wti::I_T_START] > c[wti::I_T_END]) return "t_start must not exceed t_end";
+            if (c[wti::I_T_START] > c[wti::I_T_END]) return "start must not exceed end";
             if (mode == wti::M_FAULT) {
                 if (target >= wti::CMD_ACID) return "a FAULT slot must target a sensor";
                 const double a = c[wti::I_A];
@@ -1148,8 +1148,7 @@ static_assert(WT_ALM_HIGH == wta::K_HIGH && WT_ALM_LOW == wta::K_LOW && WT_ALM_F
 static_assert(WT_A_TRIP_VALUE == wta::A_TRIP_VALUE && WT_AS_N_BAD == wta::AS_N_BAD && WT_AR_N_OVR_CHLORINE == wta::AR_N_OVR_CHLORINE,
               "alarm rows of the C ABI");
 
-// Host-side checks of a [WT_ALM_SLOTS][WT_NA][N] program; nullptr when it is valid.  core/alarm.py validate_block
-// makes the same checks in the same order.
+// Host-side checks of a [WT_ALM_SLOTS][WT_NA][N] program; nullptr when it is valid.
 const char *alarm_params_error(const double *p, int64_t N)
 {
     const auto is_int_in = [](double x, int lo, int hi) { return x == std::floor(x) && x >= lo && x <= hi; };
@@ -1321,8 +1320,7 @@ static_assert(WT_ACT_ACID == wtv::CH_ACID && WT_ACT_CHLORINE == wtv::CH_CHLORINE
               WT_ACT_FAIL_TO + 1 == wtv::N_FAULTS, "actuator channels and faults of the C ABI");
 static_assert(WT_V_FAIL_VALUE == wtv::V_FAIL_VALUE && WT_VS_N_FAULT == wtv::VS_N_FAULT, "actuator rows of the C ABI");
 
-// Host-side checks of a [WT_ACT_CHANNELS][WT_NV][N] program; nullptr when it is valid.  core/actuator.py
-// validate_block makes the same checks in the same order.
+// Host-side checks of a [WT_ACT_CHANNELS][WT_NV][N] program; nullptr when it is valid.
 const char *actuator_params_error(const double *p, int64_t N)
 {
     const auto is_int_in = [](double x, int lo, int hi) { return x == std::floor(x) && x >= lo && x <= hi; };
@@ -1414,6 +1412,21 @@ int wt_ensemble_actuator_clear(wt_ensemble *h)
 {
     if (!h) return fail(WT_E_ARG, "NULL handle");
     return stop_program(h, actuator_arrays(h));
+}
+
+int wt_program_check(int program, const double *params, int64_t n_reactors)
+{
+    if (!params) return fail(WT_E_ARG, "params is NULL");
+    if (n_reactors < 1) return fail(WT_E_ARG, "n_reactors must be >= 1");
+    const char *msg;
+    switch (program) {
+    case WT_PROG_CONTROL: msg = control_params_error(params, n_reactors); break;
+    case WT_PROG_INJECT: msg = inject_params_error(params, n_reactors); break;
+    case WT_PROG_ALARM: msg = alarm_params_error(params, n_reactors); break;
+    case WT_PROG_ACTUATOR: msg = actuator_params_error(params, n_reactors); break;
+    default: return fail(WT_E_ARG, "unknown program");
+    }
+    return msg ? fail(WT_E_ARG, msg) : WT_OK;
 }
 
 int wt_ensemble_get_boundary(wt_ensemble *h, double *bc)

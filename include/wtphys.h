@@ -453,6 +453,15 @@ int wt_ensemble_actuator_get(wt_ensemble *h, double *state, double *queue, doubl
 /* program off, buffers freed (no effect while none is set) */
 int wt_ensemble_actuator_clear(wt_ensemble *h);
 
+/* ---- the parameter checks of the four scan programs, without a handle or a device ----
+ * params: host, the block the program's set or enable call takes, for n_reactors reactors (WT_PROG_CONTROL:
+ * wt_ensemble_control_enable / retune, WT_PROG_INJECT: wt_ensemble_inject_set, WT_PROG_ALARM: wt_ensemble_alarm_set,
+ * WT_PROG_ACTUATOR: wt_ensemble_actuator_set).  WT_OK when the block passes that call's checks; otherwise WT_E_ARG
+ * and wt_last_error() is the message the call gives for it.  A NULL params, n_reactors < 1 or an unknown program
+ * also give WT_E_ARG.  Makes no HIP call. */
+enum { WT_PROG_CONTROL = 0, WT_PROG_INJECT = 1, WT_PROG_ALARM = 2, WT_PROG_ACTUATOR = 3 };
+int wt_program_check(int program, const double *params, int64_t n_reactors);
+
 /* ---- reactor diagnostics (SURVEY.md section 8(f) NEXT-4): reductions over the zones of every reactor ----
  * out: host [WT_N_DIAG][N] doubles, rows
  *   0 total_chlorine_mg, 1 total_H_mol, 2 total_OH_mol, 3 charge_balance_mol, 4 thermal_energy_kJ

@@ -1,5 +1,6 @@
 """Helpers of the GPU tests of the per-reactor scan programs (test_gpu_control.py, test_gpu_inject.py,
-test_gpu_alarm.py): a plant with sensors and plant I/O, a pair of PI loops, the plant's observable state."""
+test_gpu_alarm.py): a plant with sensors and plant I/O, a pair of PI loops, the plant's observable state, the message
+of a refused parameter block."""
 import numpy as np
 
 DT, K = 10.0, 300          # 3000 s: the pH sensors' 1800 s warm-up ends inside the run
@@ -31,6 +32,13 @@ def plant_state(ens):
     es = ens.state
     v, s, f = ens.sensor_readings()
     return (es.pH, es.chlorine, es.temperature, es.time, es.flow_rate, es.status, v, s, f, ens.boundary())
+
+
+def refused_as_checked(nat, program, block) -> bool:
+    """The message of the set call just refused on ``block`` is the one wt_program_check gives for it."""
+    msg = nat.lib().wt_last_error()
+    return (nat.lib().wt_program_check(program, nat.dptr(block), block.shape[-1]) == nat.WT_E_ARG
+            and nat.lib().wt_last_error() == msg)
 
 
 def assert_all_equal(ref, got, what):

@@ -16,7 +16,7 @@ CL = 3     # chlorine_outlet
 
 
 @pytest.fixture(scope="module")
-def alm():
+def alm(native):
     return importlib.import_module("ics-wt-physicsengine_amd.core.alarm")
 
 
@@ -213,10 +213,11 @@ def test_alarm_state_block_round_trip(alm):
 def test_alarm_symbols_declared_and_exported():
     header = open(os.path.join(ROOT, "include", "wtphys.h")).read()
     names = ("wt_ensemble_alarm_set", "wt_ensemble_alarm_get", "wt_ensemble_alarm_reset", "wt_ensemble_alarm_words",
-             "wt_ensemble_alarm_device", "wt_ensemble_alarm_clear")
+             "wt_ensemble_alarm_device", "wt_ensemble_alarm_clear", "wt_program_check")
     for name in names:
         assert re.search(r"\bint " + name + r"\(", header), name
     assert re.search(r"#define WT_ALM_SLOTS 4\b", header)
+    assert re.search(r"WT_PROG_ALARM = 2\b", header)
     assert re.search(r"WT_NA = 10\b", header) and re.search(r"WT_NAS = 8\b", header) and re.search(r"WT_NAR = 6\b", header)
     assert re.search(r"WT_A_TRIP_VALUE = 9\b", header) and re.search(r"WT_AS_N_BAD = 7\b", header)
     assert re.search(r"WT_AR_N_OVR_CHLORINE = 5\b", header) and re.search(r"WT_ALM_TRIP_CHLORINE = 2\b", header)

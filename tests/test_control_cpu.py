@@ -16,7 +16,7 @@ NAN = np.float32("nan")
 
 
 @pytest.fixture(scope="module")
-def ctl():
+def ctl(native):
     return importlib.import_module("ics-wt-physicsengine_amd.core.control")
 
 
@@ -163,16 +163,17 @@ def test_control_block_shape_errors(ctl):
 def test_control_symbols_declared_and_exported():
     header = open(os.path.join(ROOT, "include", "wtphys.h")).read()
     for name in ("wt_ensemble_control_enable", "wt_ensemble_control_retune", "wt_ensemble_control_get",
-                 "wt_ensemble_control_disable"):
+                 "wt_ensemble_control_disable", "wt_program_check"):
         assert re.search(r"\bint " + name + r"\(", header), name
     assert re.search(r"#define WT_CTL_LOOPS 2\b", header)
+    assert re.search(r"WT_PROG_CONTROL = 0\b", header)
     assert re.search(r"WT_NC = 9\b", header) and re.search(r"WT_NCS = 8\b", header)
     assert re.search(r"#define WT_ABI_VERSION 1\b", header)
     native = importlib.import_module("ics-wt-physicsengine_amd.core._native")
     native.build()
     lib = ctypes.CDLL(native.LIB_PATH)
     for name in ("wt_ensemble_control_enable", "wt_ensemble_control_retune", "wt_ensemble_control_get",
-                 "wt_ensemble_control_disable"):
+                 "wt_ensemble_control_disable", "wt_program_check"):
         assert hasattr(lib, name), name
     wt = importlib.import_module("ics-wt-physicsengine_amd")
     for name in ("PILoop", "ControlState", "LoopState", "control_block"):

@@ -9,7 +9,7 @@ from alarm_ref import AlarmRef
 from conftest import golden_json
 from control_ref import ControlRef
 from inject_ref import InjectRef
-from program_helpers import DT, K, MASTER, assert_all_equal, pi_loops, plant, plant_state
+from program_helpers import DT, K, MASTER, assert_all_equal, pi_loops, plant, plant_state, refused_as_checked
 
 pytestmark = pytest.mark.gpu
 
@@ -381,6 +381,7 @@ def test_errors_and_lifetime(gpu, wt, native):
         if (ch, row) == (0, 5):
             bad[0, 8, 17] = 2.5                                  # acid FAIL_TO to 2.5
         assert native.lib().wt_ensemble_actuator_set(ens._h, native.dptr(bad)) == native.WT_E_ARG, (ch, row, value)
+        assert refused_as_checked(native, native.WT_PROG_ACTUATOR, bad), (ch, row, value)
     with pytest.raises(ValueError, match="no actuator program"):
         ens.actuator_state()                                     # a refused program leaves none behind
     ens.set_schedule(0, 5)

@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 
 from control_ref import CS_N_EXEC, CS_N_HELD, ControlRef
-from program_helpers import DT, K, assert_all_equal, pi_loops, plant, plant_state
+from program_helpers import DT, K, assert_all_equal, pi_loops, plant, plant_state, refused_as_checked
 
 pytestmark = pytest.mark.gpu
 
@@ -189,9 +189,12 @@ def test_errors_and_lifetime(gpu, wt):
         bad = good.copy()
         bad[0, row, 17] = value
         assert nat.lib().wt_ensemble_control_enable(ens._h, nat.dptr(bad)) == nat.WT_E_ARG, (row, value)
+        assert refused_as_checked(nat, nat.WT_PROG_CONTROL, bad), (row, value)
     with pytest.raises(ValueError):
         ens.enable_control(wt.PILoop("chlorine_outlet", 1.0, kp=-1.0))
     ens.enable_control(chlorine, acid)
+    with pytest.raises(ValueError, match="^kp and ki must be >= 0$"):     # checked by wt_ensemble_control_retune
+        ens.retune_control(acid=wt.PILoop("pH_outlet", 7.0, kp=-1.0))
     S = np.broadcast_to(bc, (3,) + bc.shape).copy()
     with pytest.raises(ValueError):
         ens.step(1.0, n_steps=3, boundary_schedule=S)

@@ -8,7 +8,7 @@ import plc_oracle as PO
 from conftest import golden_json
 from control_ref import ControlRef
 from inject_ref import InjectRef
-from program_helpers import DT, K, MASTER, assert_all_equal, pi_loops, plant, plant_state
+from program_helpers import DT, K, MASTER, assert_all_equal, pi_loops, plant, plant_state, refused_as_checked
 
 pytestmark = pytest.mark.gpu
 
@@ -341,6 +341,7 @@ def test_errors_and_lifetime(gpu, wt):
         bad = good.copy()
         bad[slot, row, 17] = value
         assert nat.lib().wt_ensemble_inject_set(ens._h, nat.dptr(bad)) == nat.WT_E_ARG, (slot, row, value)
+        assert refused_as_checked(nat, nat.WT_PROG_INJECT, bad), (slot, row, value)
     with pytest.raises(ValueError, match="no injection program"):
         ens.injection_state()                                 # a refused program leaves none behind
     ens.set_schedule(0, 5)

@@ -94,6 +94,50 @@ def test_library_exports_every_declared_symbol(native):
     assert lib.wt_abi_version() == 1
 
 
+def test_program_check_without_a_device(native, wt):
+    """wt_program_check runs the checks of each scan program's set call on the host: the off blocks pass, a bad block
+    gets the set call's message (the builder raises it as a ValueError), a malformed call is refused."""
+    L, N = native.lib(), 3
+    off = {native.WT_PROG_CONTROL: wt.control_block(N), native.WT_PROG_INJECT: wt.injection_block(N),
+           native.WT_PROG_ALARM: wt.alarm_block(N), native.WT_PROG_ACTUATOR: wt.actuator_block(N)}
+    for program, blk in off.items():
+        assert L.wt_program_check(program, native.dptr(blk), N) == native.WT_OK, program
+    blk = off[native.WT_PROG_CONTROL]
+    for program, params, n in ((4, blk, N), (-1, blk, N), (native.WT_PROG_CONTROL, None, N),
+                               (native.WT_PROG_CONTROL, blk, 0)):
+        assert L.wt_program_check(program, native.dptr(params), n) == native.WT_E_ARG, (program, n)
+    # a bad block per program: (program, a valid block, {(slot, row): value} that spoils it, message, builder call)
+    cases = (
+        (native.WT_PROG_CONTROL, wt.control_block(N, chlorine=wt.PILoop(3, 1.0)), {(0, 2): 0.0},
+         "direction must be +1 or -1", lambda: wt.control_block(N, chlorine=wt.PILoop(3, 1.0, direction=0))),
+        (native.WT_PROG_INJECT, wt.injection_block(N, wt.Injection(3, "bias")), {(0, 2): 50.0, (0, 3): 40.0},
+         "start must not exceed end", lambda: wt.injection_block(N, wt.Injection(3, "bias", start=50.0, end=40.0))),
+        (native.WT_PROG_INJECT, wt.injection_block(N, wt.Injection(3, "bias")), {(0, 3): -np.inf},
+         "injection parameters must be finite (end may be +inf)",
+         lambda: wt.injection_block(N, wt.Injection(3, "bias", end=-np.inf))),
+        (native.WT_PROG_ALARM, wt.alarm_block(N, wt.Alarm(3, "high", 1.0, action="trip_chlorine")), {(0, 9): 1.5},
+         "a trip_chlorine slot's trip_value must be in [0, 1]",
+         lambda: wt.alarm_block(N, wt.Alarm(3, "high", 1.0, action="trip_chlorine", trip_value=1.5))),
+        (native.WT_PROG_ACTUATOR, wt.actuator_block(N, wt.Actuator("inlet")), {(2, 4): 9.0},
+         "delay must be an integer in 0..8", lambda: wt.actuator_block(N, wt.Actuator("inlet", delay=9))),
+    )
+    for program, good, spoil, msg, build in cases:
+        assert L.wt_program_check(program, native.dptr(good), N) == native.WT_OK, msg
+        bad = good.copy()
+        for (slot, row), value in spoil.items():
+            bad[slot, row] = value
+        assert L.wt_program_check(program, native.dptr(bad), N) == native.WT_E_ARG, msg
+        assert L.wt_last_error().decode() == msg
+        with pytest.raises(ValueError) as ei:
+            build()
+        assert str(ei.value) == msg
+    # several bad fields in different reactors: the first failing check of the first bad reactor is the one named
+    bad = off[native.WT_PROG_ACTUATOR].copy()
+    bad[0, 4, 0], bad[0, 1, 1] = 9.0, -1.0
+    assert L.wt_program_check(native.WT_PROG_ACTUATOR, native.dptr(bad), N) == native.WT_E_ARG
+    assert L.wt_last_error() == b"delay must be an integer in 0..8"
+
+
 def test_no_silent_cpu_fallback(native, wt):
     """Without a HIP device the product path must fail loudly."""
     if native.device_count() > 0:

@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
-def inj():
+def inj(native):
     return importlib.import_module("ics-wt-physicsengine_amd.core.inject")
 
 
@@ -155,13 +155,14 @@ def test_injection_state_block_round_trip(inj):
 
 def test_inject_symbols_declared_and_exported():
     header = open(os.path.join(ROOT, "include", "wtphys.h")).read()
-    names = ("wt_ensemble_inject_set", "wt_ensemble_inject_get", "wt_ensemble_inject_clear")
+    names = ("wt_ensemble_inject_set", "wt_ensemble_inject_get", "wt_ensemble_inject_clear", "wt_program_check")
     for name in names:
         assert re.search(r"\bint " + name + r"\(", header), name
     assert re.search(r"#define WT_INJ_SLOTS 4\b", header)
     assert re.search(r"WT_NI = 6\b", header) and re.search(r"WT_NIS = 4\b", header)
     assert re.search(r"WT_INJ_CMD_ACID = 7\b", header) and re.search(r"WT_INJ_CMD_INLET = 9\b", header)
     assert re.search(r"WT_INJ_FAULT = 7\b", header)
+    assert re.search(r"WT_PROG_INJECT = 1\b", header)
     assert re.search(r"#define WT_ABI_VERSION 1\b", header)
     native = importlib.import_module("ics-wt-physicsengine_amd.core._native")
     native.build()
