@@ -313,16 +313,11 @@ static_assert(sizeof(StepArgs) <= 4096, "the kernel-argument segment holds at mo
 constexpr int NB = 10;     // rows of a boundary block (WT_NB)
 // kernels that record and reload the schedule inside a work item (n <= 32); the others take one outer step per launch
 __host__ __device__ constexpr bool x_in_item(int LV) { return LV <= 5; }
-// kernels that carry the injection section (wt_inj.hpp).  The n > 32 kernel has no register for it: every variant
-// tried cost it 8 B of scratch and 4 VGPR spills, with or without a program, so it compiles the section out and
-// wt_ensemble_inject_set refuses ensembles of more than 32 zones.
-__host__ __device__ constexpr bool inj_in_item(int LV) { return LV <= 5; }
-// kernels that carry the alarm section (wt_alm.hpp).  The n > 32 kernel compiles it out for the same reason, and
-// wt_ensemble_alarm_set refuses ensembles of more than 32 zones.
-__host__ __device__ constexpr bool alm_in_item(int LV) { return LV <= 5; }
-// kernels that carry the actuator section (wt_act.hpp).  The n > 32 kernel compiles it out for the same reason, and
-// wt_ensemble_actuator_set refuses ensembles of more than 32 zones.
-__host__ __device__ constexpr bool act_in_item(int LV) { return LV <= 5; }
+// kernels that carry the injection, alarm and actuator sections (wt_inj.hpp, wt_alm.hpp, wt_act.hpp).  The n > 32
+// kernel has no register for them: every variant tried cost it 8 B of scratch and 4 VGPR spills, with or without a
+// program, so it compiles the sections out and wt_ensemble_inject_set, _alarm_set and _actuator_set refuse ensembles
+// of more than 32 zones.
+__host__ __device__ constexpr bool prog_in_item(int LV) { return LV <= 5; }
 enum { Q_AVAIL = 0, Q_HEAD = 1, Q_TAIL = 2, Q_ERROR = 3, Q_TRACE = 4, Q_DONE = 5, Q_WORDS = 16 };
 
 // ---------------------------------------------------------------- lane geometry and cross-lane moves
@@ -2393,18 +2388,18 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
                     if (scan) {
                         // an injection program (wave-uniform flag) tampers with this lane's copy of the readings and
                         // with the decoded commands; t is the loop time this scan stores.  Not in the n > 32 kernel.
-                        const bool inj = inj_in_item(LV) && WT_RARE(fresh(pa)->inj.on);
+                        const bool inj = prog_in_item(LV) && WT_RARE(fresh(pa)->inj.on);
                         if (inj) wti::tamper_sensors(fresh(pa)->inj, rr, &io.val[0][lane], &io.fault[0][lane], wts::RMAX, lt + dt);
                         wtp::pack_inputs(b->sens.pack, rr, &io.val[0][lane], &io.fault[0][lane], wts::RMAX, lt);   // update_modbus_inputs
                         double c[3];
                         // an actuator program (wave-uniform flag) needs the inlet row as it was before this scan
-                        const bool act = act_in_item(LV) && WT_RARE(fresh(pa)->act.on);
+                        const bool act = prog_in_item(LV) && WT_RARE(fresh(pa)->act.on);
                         const double row0 = act ? b->sens.cmd.bc[rr] : 0.0;
                         double inlet_v;
                         if (inj) inlet_v = wtp::apply_commands(b->sens.cmd, rr, c, wti::command_tamper(fresh(pa)->inj, rr, lt + dt));
                         else inlet_v = wtp::apply_commands(b->sens.cmd, rr, c);    // read_modbus_commands + apply_boundary_conditions
                         // an alarm program's trips in force (from the previous scan) replace the validated commands
-                        if (alm_in_item(LV) && WT_RARE(fresh(pa)->alm.on)) wta::override_commands(fresh(pa)->alm, b->sens.cmd, rr, c);
+                        if (prog_in_item(LV) && WT_RARE(fresh(pa)->alm.on)) wta::override_commands(fresh(pa)->alm, b->sens.cmd, rr, c);
                         // the final elements, downstream of the whole command path: their positions are what the plant gets
                         if (act) wtv::actuate(fresh(pa)->act, b->sens.cmd, rr, c, inlet_v, row0, lt + dt);
                         io.cmd[0][lane] = c[0]; io.cmd[1][lane] = c[1]; io.cmd[2][lane] = c[2];
@@ -2420,7 +2415,7 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
                 }
                 // the alarm program, after the PLC program: IMAGE slots read this lane's (possibly tampered) copy,
                 // FIELD slots what the sensor lanes stored before the barrier above; its trips act from the next scan on
-                if (alm_in_item(LV) && scan && WT_RARE(fresh(pa)->alm.on) && lane < R && io.stepped[lane]) {
+                if (prog_in_item(LV) && scan && WT_RARE(fresh(pa)->alm.on) && lane < R && io.stepped[lane]) {
                     ArgPtr ap = fresh(pa);
                     const int64_t rr = rix[lane];
                     wta::evaluate(ap->alm, rr, ap->sens.N, &io.val[0][lane], &io.fault[0][lane], wts::RMAX, ap->sens.out_value,

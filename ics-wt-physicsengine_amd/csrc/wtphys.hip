@@ -84,18 +84,17 @@ struct wt_ensemble {
     hipStream_t sub_stream[WT_MAX_STREAMS] = {};
     hipEvent_t sub_done[WT_MAX_STREAMS] = {};
     hipEvent_t ev_fork = nullptr;
-    // optional fused sensor suite (wt_sensors.hpp)
-    bool sensors_on = false;
-    uint64_t sens_seed = 0; int64_t sens_reactor_base = 0;
-    float *s_fs = nullptr, *s_full_scale = nullptr, *s_ring_t = nullptr, *s_ring_v = nullptr, *s_out_value = nullptr, *s_hist_value = nullptr;
-    double *s_ds = nullptr, *s_t_enable = nullptr;
-    int32_t *s_is = nullptr, *s_ring_head = nullptr, *s_ring_cnt = nullptr, *s_hist_pos = nullptr;
-    uint8_t *s_out_status = nullptr, *s_out_fault = nullptr, *s_hist_status = nullptr, *s_hist_fault = nullptr;
-    int s_hist_cap = 0;
-    // optional plant I/O: Modbus register images per reactor (wt_plc.hpp); one PLC scan every chunk_steps outer steps
-    bool plc_on = false;
     double *diag_out = nullptr;
-    uint16_t *p_ir = nullptr, *p_hr = nullptr; double *p_loop_time = nullptr; uint8_t *p_update_ok = nullptr;
+    // The kernel's argument structs of the optional parts, as every launch passes them (make_args adds what is per
+    // call).  sens: fused sensor suite (wt_sensors.hpp, sens.on), plant I/O with its Modbus register images per reactor
+    // (wt_plc.hpp, sens.plc_on: one PLC scan every chunk_steps outer steps), the command path into the boundary block.
+    // ctl / inj / alm / act: per-reactor PI, injection, alarm and actuator programs (wt_ctl.hpp, wt_inj.hpp,
+    // wt_alm.hpp, wt_act.hpp), [N] records each.  The holding image lives in ctl.hr, which sens.cmd.hr repeats.
+    wts::SuiteArgs sens = {};
+    wtc::CtlArgs ctl = {};
+    wti::InjArgs inj = {};
+    wta::AlmArgs alm = {};
+    wtv::ActArgs act = {};
     // optional per-launch HIP-event timing (bench.py roofline accounting)
     bool time_launches = false;
     std::vector<hipEvent_t> lt_pool;   // start/stop pairs
@@ -103,30 +102,20 @@ struct wt_ensemble {
     // boundary schedule of wt_ensemble_step_scheduled ([n_steps][WT_NB][N], grown on demand); call_sched is set
     // only while such a call queues its launches
     double *sched = nullptr; size_t sched_bytes = 0; const double *call_sched = nullptr;
-    // trajectory records of wt_ensemble_record: [rec_cap][N][n] / [rec_cap][N]; rec_steps = outer steps since then
-    double *rec_pH = nullptr, *rec_Cl = nullptr, *rec_T = nullptr, *rec_time = nullptr, *rec_flow = nullptr;
-    uint32_t *rec_status = nullptr;
-    int rec_every = 1, rec_cap = 0;
-    int64_t rec_steps = 0;
-    // optional per-reactor PI programs (wt_ctl.hpp), indexed by reactor: parameter records and state
-    bool ctl_on = false;
-    double *c_par = nullptr, *c_st = nullptr;   // [N][wtc::PAR_DOUBLES], [N][wtc::ST_DOUBLES]
-    // optional per-reactor injection programs (wt_inj.hpp), indexed by reactor: slot records and slot state
-    bool inj_on = false;
-    double *i_par = nullptr, *i_st = nullptr;   // [N][wti::PAR_DOUBLES], [N][wti::ST_DOUBLES]
-    // optional per-reactor alarm and interlock programs (wt_alm.hpp), indexed by reactor
-    bool alm_on = false;
-    double *a_par = nullptr, *a_st = nullptr, *a_rst = nullptr;   // [N][wta::PAR_DOUBLES], [N][wta::ST_DOUBLES], [N][wta::RST_DOUBLES]
-    uint16_t *a_word = nullptr;                                   // [N]
-    // optional per-reactor actuator programs (wt_act.hpp), indexed by reactor
-    bool act_on = false;
-    double *v_par = nullptr, *v_st = nullptr, *v_q = nullptr, *v_tp = nullptr;   // [N][wtv::PAR_DOUBLES], [N][wtv::ST_DOUBLES], [N][wtv::Q_DOUBLES], [N]
+    // trajectory records of wt_ensemble_record
+    struct Recording {
+        double *pH = nullptr, *Cl = nullptr, *T = nullptr;   // [cap][N][n]
+        double *time = nullptr, *flow = nullptr;             // [cap][N]
+        uint32_t *status = nullptr;                          // [cap][N]
+        int every = 1, cap = 0;
+        int64_t steps = 0;                                   // outer steps since wt_ensemble_record
+    } rec;
 };
 
 namespace {
 
 // recording is on and has free slots (afterwards the launches carry no record pointers at all)
-bool recording_open(const wt_ensemble *h) { return h->rec_pH && h->rec_steps / h->rec_every < h->rec_cap; }
+bool recording_open(const wt_ensemble *h) { return h->rec.pH && h->rec.steps / h->rec.every < h->rec.cap; }
 
 wt::StepArgs make_args(const wt_ensemble *h, double dt, int n_steps, int first_step, int call_steps, int scan_every)
 {
@@ -142,133 +131,138 @@ wt::StepArgs make_args(const wt_ensemble *h, double dt, int n_steps, int first_s
     a.trace = h->trace; a.trace_cap = h->trace_cap;
     a.kt = wt::default_ktab(); a.rt = wt::default_rtab();
     a.kt.dense_bias = h->knob_dense ? 1.0 : 0.0;
-    wts::SuiteArgs &s = a.sens;
-    memset(&s, 0, sizeof s);
-    s.on = h->sensors_on ? 1 : 0; s.plc_on = h->plc_on ? 1 : 0; s.scan_every = scan_every > 0 ? scan_every : 1;
-    s.N = h->N; s.reactor_base = h->sens_reactor_base;
-    s.seed_lo = (uint32_t)(h->sens_seed & 0xffffffffu); s.seed_hi = (uint32_t)(h->sens_seed >> 32);
-    s.t_enable = h->s_t_enable; s.fs = h->s_fs; s.ds = h->s_ds; s.is = h->s_is; s.full_scale = h->s_full_scale;
-    s.ring_t = h->s_ring_t; s.ring_v = h->s_ring_v; s.ring_push = h->s_ring_head; s.ring_cursor = h->s_ring_cnt;
-    s.out_value = h->s_out_value; s.out_status = h->s_out_status; s.out_fault = h->s_out_fault;
-    s.hist_value = h->s_hist_value; s.hist_status = h->s_hist_status; s.hist_fault = h->s_hist_fault;
-    s.hist_cap = h->s_hist_cap; s.hist_pos = h->s_hist_pos;
-    s.pack.loop_time = h->p_loop_time; s.pack.ir = h->p_ir; s.pack.update_ok = h->p_update_ok;
-    s.cmd.N = h->N; s.cmd.hr = h->p_hr; s.cmd.bc = h->bc;
+    a.sens = h->sens; a.ctl = h->ctl; a.inj = h->inj; a.alm = h->alm; a.act = h->act;
+    a.sens.scan_every = scan_every > 0 ? scan_every : 1;
     a.sched = h->call_sched;
     const bool rec = recording_open(h);
-    a.rec_pH = rec ? h->rec_pH : nullptr; a.rec_Cl = h->rec_Cl; a.rec_T = h->rec_T;
-    a.rec_time = h->rec_time; a.rec_flow = h->rec_flow; a.rec_status = h->rec_status;
-    a.rec_every = h->rec_every; a.rec_cap = h->rec_cap;
-    a.rec_phase = rec ? (int)(h->rec_steps % h->rec_every) : 0;
-    a.rec_slot0 = rec ? (int)(h->rec_steps / h->rec_every) : 0;
+    a.rec_pH = rec ? h->rec.pH : nullptr; a.rec_Cl = h->rec.Cl; a.rec_T = h->rec.T;
+    a.rec_time = h->rec.time; a.rec_flow = h->rec.flow; a.rec_status = h->rec.status;
+    a.rec_every = h->rec.every; a.rec_cap = h->rec.cap;
+    a.rec_phase = rec ? (int)(h->rec.steps % h->rec.every) : 0;
+    a.rec_slot0 = rec ? (int)(h->rec.steps / h->rec.every) : 0;
     a.x_on = (a.sched || a.rec_pH) ? 1 : 0;
-    a.ctl.on = h->ctl_on ? 1 : 0; a.ctl.par = h->c_par; a.ctl.st = h->c_st; a.ctl.hr = h->p_hr;
-    a.inj.on = h->inj_on ? 1 : 0; a.inj.par = h->i_par; a.inj.st = h->i_st;
-    a.alm.on = h->alm_on ? 1 : 0; a.alm.par = h->a_par; a.alm.st = h->a_st; a.alm.rst = h->a_rst; a.alm.word = h->a_word;
-    a.act.on = h->act_on ? 1 : 0; a.act.par = h->v_par; a.act.st = h->v_st; a.act.q = h->v_q; a.act.tp = h->v_tp;
     return a;
 }
 
 template <class T> void free_and_null(T *&p) { if (p) (void)hipFree(p); p = nullptr; }
 
-void release_sensor_buffers(wt_ensemble *h)
-{
-    free_and_null(h->s_fs); free_and_null(h->s_full_scale); free_and_null(h->s_ring_t); free_and_null(h->s_ring_v);
-    free_and_null(h->s_out_value); free_and_null(h->s_hist_value); free_and_null(h->s_ds); free_and_null(h->s_t_enable);
-    free_and_null(h->s_is); free_and_null(h->s_ring_head); free_and_null(h->s_ring_cnt); free_and_null(h->s_hist_pos);
-    free_and_null(h->s_out_status); free_and_null(h->s_out_fault);
-    free_and_null(h->s_hist_status); free_and_null(h->s_hist_fault);
-    h->s_hist_cap = 0; h->sensors_on = false;
-}
-
-void release_record_buffers(wt_ensemble *h)
-{
-    free_and_null(h->rec_pH); free_and_null(h->rec_Cl); free_and_null(h->rec_T);
-    free_and_null(h->rec_time); free_and_null(h->rec_flow); free_and_null(h->rec_status);
-    h->rec_cap = 0; h->rec_every = 1; h->rec_steps = 0;
-}
-
-// The device arrays of one per-reactor scan program (PI control, injection, alarms): allocated together on first
-// use, [N] records of a fixed size each, and released together with the program's switch.
-struct ProgramArrays {
-    bool &on;
+// The device arrays of one part of the handle (core, sensor suite, plant I/O, recording, a scan program): allocated
+// together, all or none, and released together with the part's switch.
+struct ArrayGroup {
     const char *name;                                   // prefix of an allocation error
-    std::vector<std::pair<void **, size_t>> arrays;     // where each pointer lives, bytes per reactor
+    int *on;                                            // the part's switch (nullptr: none)
+    std::vector<std::pair<void **, size_t>> arrays;     // where each pointer lives, its bytes (0: not allocated)
 };
 
-ProgramArrays control_arrays(wt_ensemble *h)
+void release(const ArrayGroup &g)
 {
-    return {h->ctl_on, "control", {{(void **)&h->c_par, sizeof(double) * wtc::PAR_DOUBLES},
-                                   {(void **)&h->c_st, sizeof(double) * wtc::ST_DOUBLES}}};
+    for (const auto &a : g.arrays) free_and_null(*a.first);
+    if (g.on) *g.on = 0;
 }
 
-ProgramArrays inject_arrays(wt_ensemble *h)
+// allocates the group's arrays unless an earlier call did; on failure none is left behind
+int allocate(const ArrayGroup &g)
 {
-    return {h->inj_on, "inject", {{(void **)&h->i_par, sizeof(double) * wti::PAR_DOUBLES},
-                                  {(void **)&h->i_st, sizeof(double) * wti::ST_DOUBLES}}};
-}
-
-ProgramArrays alarm_arrays(wt_ensemble *h)
-{
-    return {h->alm_on, "alarm", {{(void **)&h->a_par, sizeof(double) * wta::PAR_DOUBLES},
-                                 {(void **)&h->a_st, sizeof(double) * wta::ST_DOUBLES},
-                                 {(void **)&h->a_rst, sizeof(double) * wta::RST_DOUBLES},
-                                 {(void **)&h->a_word, sizeof(uint16_t)}}};
-}
-
-ProgramArrays actuator_arrays(wt_ensemble *h)
-{
-    return {h->act_on, "actuator", {{(void **)&h->v_par, sizeof(double) * wtv::PAR_DOUBLES},
-                                    {(void **)&h->v_st, sizeof(double) * wtv::ST_DOUBLES},
-                                    {(void **)&h->v_q, sizeof(double) * wtv::Q_DOUBLES},
-                                    {(void **)&h->v_tp, sizeof(double)}}};
-}
-
-void release_program(const ProgramArrays &p)
-{
-    for (const auto &a : p.arrays) free_and_null(*a.first);
-    p.on = false;
-}
-
-// allocates the program's arrays unless an earlier call did; on failure none is left behind
-int alloc_program(const ProgramArrays &p, int64_t N)
-{
-    if (*p.arrays[0].first) return WT_OK;
-    for (const auto &a : p.arrays) {
-        const hipError_t e = hipMalloc(a.first, a.second * (size_t)N);
-        if (e != hipSuccess) { release_program(p); return fail(WT_E_HIP, std::string(p.name) + ": " + hipGetErrorString(e)); }
+    if (*g.arrays[0].first) return WT_OK;
+    for (const auto &a : g.arrays) {
+        const hipError_t e = a.second ? hipMalloc(a.first, a.second) : hipSuccess;
+        if (e != hipSuccess) { release(g); return fail(WT_E_HIP, std::string(g.name) + ": " + hipGetErrorString(e)); }
     }
     return WT_OK;
 }
 
+ArrayGroup core_arrays(wt_ensemble *h)
+{
+    const size_t N = (size_t)h->N, zone = sizeof(double) * N * (size_t)h->n;
+    return {"create", nullptr, {{(void **)&h->par, sizeof(double) * WT_NP * N}, {(void **)&h->bc, sizeof(double) * WT_NB * N},
+                                {(void **)&h->pH, zone}, {(void **)&h->Cl, zone}, {(void **)&h->T, zone},
+                                {(void **)&h->dH, zone}, {(void **)&h->dRho, zone}, {(void **)&h->dK, zone},
+                                {(void **)&h->time, sizeof(double) * N}, {(void **)&h->flow, sizeof(double) * N},
+                                {(void **)&h->status, sizeof(uint32_t) * N}, {(void **)&h->stats, sizeof(int32_t) * 5 * N},
+                                {(void **)&h->bad_T, sizeof(double) * N}, {(void **)&h->perm, sizeof(int32_t) * N},
+                                {(void **)&h->cost, sizeof(int32_t) * N},
+                                {(void **)&h->place_hist, sizeof(int32_t) * wtpl::BINS * ((N + wtpl::CHUNK - 1) / wtpl::CHUNK)},
+                                {(void **)&h->q_ctrl, sizeof(int32_t) * wt::Q_WORDS},
+                                {(void **)&h->q_slots, sizeof(unsigned long long) * (size_t)h->q_cap},
+                                {(void **)&h->q_next, sizeof(int32_t) * (size_t)h->n_groups}}};
+}
+
+// the history arrays only for hist_cap > 0
+ArrayGroup sensor_arrays(wt_ensemble *h, int hist_cap)
+{
+    wts::SuiteArgs &s = h->sens;
+    const size_t N = (size_t)h->N, hist = (size_t)hist_cap * wts::NSENS * N;
+    return {"sensors", &s.on, {{(void **)&s.fs, sizeof(float) * wts::NSENS * wts::NF * N},
+                               {(void **)&s.ds, sizeof(double) * wts::NSENS * wts::ND * N},
+                               {(void **)&s.is, sizeof(int32_t) * wts::NSENS * wts::NI * N},
+                               {(void **)&s.full_scale, sizeof(float) * N},
+                               {(void **)&s.ring_t, sizeof(float) * 2 * wts::RING * N},
+                               {(void **)&s.ring_v, sizeof(float) * 2 * wts::RING * N},
+                               {(void **)&s.ring_push, sizeof(int32_t) * 2 * N}, {(void **)&s.ring_cursor, sizeof(int32_t) * 2 * N},
+                               {(void **)&s.out_value, sizeof(float) * wts::NSENS * N},
+                               {(void **)&s.out_status, wts::NSENS * N}, {(void **)&s.out_fault, wts::NSENS * N},
+                               {(void **)&s.t_enable, sizeof(double) * N},
+                               {(void **)&s.hist_value, sizeof(float) * hist}, {(void **)&s.hist_status, hist},
+                               {(void **)&s.hist_fault, hist}, {(void **)&s.hist_pos, hist_cap > 0 ? sizeof(int32_t) * N : 0}}};
+}
+
+ArrayGroup plant_io_arrays(wt_ensemble *h)
+{
+    const size_t N = (size_t)h->N;
+    return {"plc_enable", &h->sens.plc_on, {{(void **)&h->sens.pack.ir, sizeof(uint16_t) * wtp::IR_WORDS * N},
+                                            {(void **)&h->ctl.hr, sizeof(uint16_t) * wtp::HR_WORDS * N},
+                                            {(void **)&h->sens.pack.loop_time, sizeof(double) * N},
+                                            {(void **)&h->sens.pack.update_ok, N}}};
+}
+
+ArrayGroup record_arrays(wt_ensemble *h, size_t records)   // records: capacity x N
+{
+    wt_ensemble::Recording &r = h->rec;
+    const size_t zone = sizeof(double) * records * (size_t)h->n;
+    return {"record", nullptr, {{(void **)&r.pH, zone}, {(void **)&r.Cl, zone}, {(void **)&r.T, zone},
+                                {(void **)&r.time, sizeof(double) * records}, {(void **)&r.flow, sizeof(double) * records},
+                                {(void **)&r.status, sizeof(uint32_t) * records}}};
+}
+
+ArrayGroup control_arrays(wt_ensemble *h)
+{
+    const size_t N = (size_t)h->N;
+    return {"control", &h->ctl.on, {{(void **)&h->ctl.par, sizeof(double) * wtc::PAR_DOUBLES * N},
+                                    {(void **)&h->ctl.st, sizeof(double) * wtc::ST_DOUBLES * N}}};
+}
+
+ArrayGroup inject_arrays(wt_ensemble *h)
+{
+    const size_t N = (size_t)h->N;
+    return {"inject", &h->inj.on, {{(void **)&h->inj.par, sizeof(double) * wti::PAR_DOUBLES * N},
+                                   {(void **)&h->inj.st, sizeof(double) * wti::ST_DOUBLES * N}}};
+}
+
+ArrayGroup alarm_arrays(wt_ensemble *h)
+{
+    const size_t N = (size_t)h->N;
+    return {"alarm", &h->alm.on, {{(void **)&h->alm.par, sizeof(double) * wta::PAR_DOUBLES * N},
+                                  {(void **)&h->alm.st, sizeof(double) * wta::ST_DOUBLES * N},
+                                  {(void **)&h->alm.rst, sizeof(double) * wta::RST_DOUBLES * N},
+                                  {(void **)&h->alm.word, sizeof(uint16_t) * N}}};
+}
+
+ArrayGroup actuator_arrays(wt_ensemble *h)
+{
+    const size_t N = (size_t)h->N;
+    return {"actuator", &h->act.on, {{(void **)&h->act.par, sizeof(double) * wtv::PAR_DOUBLES * N},
+                                     {(void **)&h->act.st, sizeof(double) * wtv::ST_DOUBLES * N},
+                                     {(void **)&h->act.q, sizeof(double) * wtv::Q_DOUBLES * N},
+                                     {(void **)&h->act.tp, sizeof(double) * N}}};
+}
+
 // the body of control_disable, inject_clear, alarm_clear and actuator_clear
-int stop_program(wt_ensemble *h, const ProgramArrays &p)
+int stop_program(wt_ensemble *h, const ArrayGroup &g)
 {
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still use the records
-    release_program(p);
+    release(g);
     return WT_OK;
-}
-
-// [slots][fields][N] blocks of the C ABI <-> the device's [N][stride] records, slot s at s * fields of a record
-void blocks_to_records(const double *block, int slots, int fields, int64_t N, double *rec, int stride)
-{
-    for (int s = 0; s < slots; ++s)
-        for (int k = 0; k < fields; ++k)
-            for (int64_t r = 0; r < N; ++r) rec[r * stride + s * fields + k] = block[((int64_t)s * fields + k) * N + r];
-}
-
-void records_to_blocks(const double *rec, int stride, int slots, int fields, int64_t N, double *block)
-{
-    for (int s = 0; s < slots; ++s)
-        for (int k = 0; k < fields; ++k)
-            for (int64_t r = 0; r < N; ++r) block[((int64_t)s * fields + k) * N + r] = rec[r * stride + s * fields + k];
-}
-
-void release_plc_buffers(wt_ensemble *h)
-{
-    free_and_null(h->p_ir); free_and_null(h->p_hr); free_and_null(h->p_loop_time); free_and_null(h->p_update_ok);
-    h->plc_on = false;
 }
 
 bool row_mode(int n) { return n == 2 || n == 4 || n == 8 || n == 16; }
@@ -371,6 +365,51 @@ int sync_checked(wt_ensemble *h)
     return WT_OK;
 }
 
+struct Copy { void *dst; const void *src; size_t bytes; };   // dst nullptr: not wanted
+
+// Every download: the copies queued on the handle's stream, then sync_checked.
+int download(wt_ensemble *h, const std::vector<Copy> &copies)
+{
+    for (const Copy &c : copies)
+        if (c.dst && c.bytes) HIP_TRY(hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost, h->stream));
+    return sync_checked(h);
+}
+
+// [slots][fields][N] blocks of the C ABI <-> the device's [N][stride] records, slot s at s * fields of a record
+void blocks_to_records(const double *block, int slots, int fields, int64_t N, double *rec, int stride)
+{
+    for (int s = 0; s < slots; ++s)
+        for (int k = 0; k < fields; ++k)
+            for (int64_t r = 0; r < N; ++r) rec[r * stride + s * fields + k] = block[((int64_t)s * fields + k) * N + r];
+}
+
+void records_to_blocks(const double *rec, int stride, int slots, int fields, int64_t N, double *block)
+{
+    for (int s = 0; s < slots; ++s)
+        for (int k = 0; k < fields; ++k)
+            for (int64_t r = 0; r < N; ++r) block[((int64_t)s * fields + k) * N + r] = rec[r * stride + s * fields + k];
+}
+
+struct Records { double *block; const double *rec; int stride, slots, fields; };   // block nullptr: not wanted
+
+// Downloads [N][stride] records (one synchronisation for all) into [slots][fields][N] blocks.
+int download_records(wt_ensemble *h, const std::vector<Records> &parts)
+{
+    const int64_t N = h->N;
+    size_t total = 0;
+    for (const Records &p : parts) total += p.block ? (size_t)(N * p.stride) : 0;
+    std::vector<double> host(total);
+    std::vector<Copy> copies;
+    double *at = host.data();
+    for (const Records &p : parts)
+        if (p.block) { copies.push_back({at, p.rec, sizeof(double) * (size_t)(N * p.stride)}); at += N * p.stride; }
+    if (int rc = download(h, copies)) return rc;
+    at = host.data();
+    for (const Records &p : parts)
+        if (p.block) { records_to_blocks(at, p.stride, p.slots, p.fields, N, p.block); at += N * p.stride; }
+    return WT_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -415,38 +454,15 @@ int wt_ensemble_create(int64_t n_reactors, int n_zones, int device, const double
     }
     const size_t N = (size_t)n_reactors, nz = (size_t)n_zones;
     auto cleanup = [&]() { wt_ensemble_destroy(h); };
-#define ALLOC(ptr, bytes)                                                                   \
-    do {                                                                                    \
-        hipError_t e_ = hipMalloc((void **)&(ptr), (bytes));                                \
-        if (e_ != hipSuccess) { cleanup(); return fail(WT_E_HIP, std::string("hipMalloc: ") + hipGetErrorString(e_)); } \
-    } while (0)
-    ALLOC(h->par, sizeof(double) * WT_NP * N);
-    ALLOC(h->bc, sizeof(double) * WT_NB * N);
-    ALLOC(h->pH, sizeof(double) * N * nz);
-    ALLOC(h->Cl, sizeof(double) * N * nz);
-    ALLOC(h->T, sizeof(double) * N * nz);
-    ALLOC(h->dH, sizeof(double) * N * nz);
-    ALLOC(h->dRho, sizeof(double) * N * nz);
-    ALLOC(h->dK, sizeof(double) * N * nz);
-    ALLOC(h->time, sizeof(double) * N);
-    ALLOC(h->flow, sizeof(double) * N);
-    ALLOC(h->status, sizeof(uint32_t) * N);
-    ALLOC(h->stats, sizeof(int32_t) * 5 * N);
-    ALLOC(h->bad_T, sizeof(double) * N);
-    ALLOC(h->perm, sizeof(int32_t) * N);
-    ALLOC(h->cost, sizeof(int32_t) * N);
-    ALLOC(h->place_hist, sizeof(int32_t) * wtpl::BINS * ((N + wtpl::CHUNK - 1) / wtpl::CHUNK));
     h->n_groups = (n_reactors + h->R - 1) / h->R;
     if (h->n_groups > 0x3fffffff) { cleanup(); return fail(WT_E_ARG, "too many reactors for one ensemble"); }
     h->q_cap = (int)(2 * h->n_groups + 64);
-    ALLOC(h->q_ctrl, sizeof(int32_t) * wt::Q_WORDS);
-    ALLOC(h->q_slots, sizeof(unsigned long long) * (size_t)h->q_cap);
-    ALLOC(h->q_next, sizeof(int32_t) * (size_t)h->n_groups);
+    if (int rc = allocate(core_arrays(h))) { cleanup(); return rc; }
     {   // small ensembles (the drop-in's N = 1 above all) are downloaded as one packed image through pinned memory
         const size_t image = sizeof(double) * (6 * N * nz + 2 * N) + sizeof(uint32_t) * (N + 1);
         if (image <= WT_SNAPSHOT_PACK_MAX) {
             h->snap_bytes = (image + 7) & ~(size_t)7;
-            ALLOC(h->snap_dev, h->snap_bytes);
+            if (hipMalloc(&h->snap_dev, h->snap_bytes) != hipSuccess) { cleanup(); return fail(WT_E_HIP, "hipMalloc failed"); }
             if (hipHostMalloc(&h->snap_host, h->snap_bytes, hipHostMallocDefault) != hipSuccess) { cleanup(); return fail(WT_E_HIP, "hipHostMalloc failed"); }
         }
         if (hipHostMalloc((void **)&h->err_host, 2 * sizeof(int32_t), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) { cleanup(); return fail(WT_E_HIP, "hipHostMalloc failed"); }
@@ -457,7 +473,8 @@ int wt_ensemble_create(int64_t n_reactors, int n_zones, int device, const double
     if (const char *e = getenv("WT_PLACE_MIN")) h->knob_place_min = atoll(e);
     if (const char *e = getenv("WT_Q_TICKETS")) h->knob_tickets = atoll(e);
     if (const char *e = getenv("WT_DENSE_COUPLING")) h->knob_dense = atoi(e) != 0;
-#undef ALLOC
+    h->sens.N = h->sens.cmd.N = h->N;
+    h->sens.cmd.bc = h->bc;
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { cleanup(); return fail(WT_E_HIP, "hipStreamCreate failed"); }
     h->own_stream = true;
     if (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess) { cleanup(); return fail(WT_E_HIP, "hipEventCreate failed"); }
@@ -489,22 +506,15 @@ int wt_ensemble_destroy(wt_ensemble *h)
     if (!h) return WT_OK;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    if (h->trace) (void)hipFree(h->trace);
-    void *ptrs[] = {h->par, h->bc, h->pH, h->Cl, h->T, h->time, h->flow, h->dH, h->dRho, h->dK, h->status, h->stats, h->wave_diag,
-                    h->bad_T, h->q_ctrl, h->q_slots, h->q_next, h->perm, h->cost, h->place_hist, h->snap_dev, h->sched,
-                    h->diag_out};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
+    for (const ArrayGroup &g : {core_arrays(h), sensor_arrays(h, h->sens.hist_cap), plant_io_arrays(h), record_arrays(h, 0),
+                                control_arrays(h), inject_arrays(h), alarm_arrays(h), actuator_arrays(h)})
+        release(g);
+    free_and_null(h->trace); free_and_null(h->wave_diag); free_and_null(h->snap_dev); free_and_null(h->sched);
+    free_and_null(h->diag_out);
     for (int s = 0; s < WT_MAX_STREAMS; ++s) {
         if (h->sub_stream[s]) { (void)hipStreamSynchronize(h->sub_stream[s]); (void)hipStreamDestroy(h->sub_stream[s]); }
         if (h->sub_done[s]) (void)hipEventDestroy(h->sub_done[s]);
     }
-    release_record_buffers(h);
-    release_sensor_buffers(h);
-    release_plc_buffers(h);
-    release_program(control_arrays(h));
-    release_program(inject_arrays(h));
-    release_program(alarm_arrays(h));
-    release_program(actuator_arrays(h));
     if (h->snap_host) (void)hipHostFree(h->snap_host);
     if (h->err_host) (void)hipHostFree(h->err_host);
     for (hipEvent_t e : h->lt_pool) (void)hipEventDestroy(e);
@@ -661,12 +671,12 @@ int run_steps(wt_ensemble *h, double dt, int n_steps, int fused)
         // (each starts from its own schedule row), a record copied from the state in memory after the steps that want one
         for (int s = 0; s < n_steps && rc == WT_OK; ++s) {
             rc = queue_steps(h, dt, 1, fused, s, n_steps);
-            const int64_t m = h->rec_steps + s + 1;
-            if (rc == WT_OK && rec && m % h->rec_every == 0 && m / h->rec_every <= h->rec_cap) {
-                const int64_t o = (m / h->rec_every - 1) * h->N;
+            const int64_t m = h->rec.steps + s + 1;
+            if (rc == WT_OK && rec && m % h->rec.every == 0 && m / h->rec.every <= h->rec.cap) {
+                const int64_t o = (m / h->rec.every - 1) * h->N;
                 const wt::RecordCopyArgs ca{0, h->N, h->n, h->pH, h->Cl, h->T, h->time, h->flow, h->status,
-                                            h->rec_pH + o * h->n, h->rec_Cl + o * h->n, h->rec_T + o * h->n,
-                                            h->rec_time + o, h->rec_flow + o, h->rec_status + o};
+                                            h->rec.pH + o * h->n, h->rec.Cl + o * h->n, h->rec.T + o * h->n,
+                                            h->rec.time + o, h->rec.flow + o, h->rec.status + o};
                 const int64_t cnt = h->N * h->n;
                 hipLaunchKernelGGL(wt::record_copy_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, h->stream, ca);
                 HIP_TRY(hipGetLastError());
@@ -675,7 +685,7 @@ int run_steps(wt_ensemble *h, double dt, int n_steps, int fused)
     } else {
         rc = queue_steps(h, dt, n_steps, fused, 0, n_steps);
     }
-    if (rc == WT_OK && h->rec_pH) h->rec_steps += n_steps;
+    if (rc == WT_OK && h->rec.pH) h->rec.steps += n_steps;
     return rc;
 }
 
@@ -698,7 +708,7 @@ int wt_ensemble_step_scheduled(wt_ensemble *h, double dt, int n_steps, int fused
 {
     if (!h) return fail(WT_E_ARG, "NULL handle");
     if (!bc_schedule) return fail(WT_E_ARG, "bc_schedule is NULL");
-    if (h->plc_on) return fail(WT_E_STATE, "a boundary schedule cannot be combined with plant I/O (the command path owns the boundary)");
+    if (h->sens.plc_on) return fail(WT_E_STATE, "a boundary schedule cannot be combined with plant I/O (the command path owns the boundary)");
     if (!h->have_state) return fail(WT_E_STATE, "set_state must precede step");
     if (!(dt > 0)) return fail(WT_E_ARG, "`max_step` must be positive."); // scipy validate_max_step (reactor.py:480)
     if (n_steps < 0) return fail(WT_E_ARG, "n_steps must be >= 0");
@@ -739,16 +749,11 @@ int wt_ensemble_record(wt_ensemble *h, int every, int capacity)
         return fail(WT_E_ARG, "record size overflows int64");
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still write the old records
-    release_record_buffers(h);
+    release(record_arrays(h, 0));
+    h->rec = {};
     if (capacity == 0) return WT_OK;
-    hipError_t e = hipMalloc((void **)&h->rec_pH, (size_t)zone);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->rec_Cl, (size_t)zone);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->rec_T, (size_t)zone);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->rec_time, (size_t)per);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->rec_flow, (size_t)per);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->rec_status, (size_t)per / 2);
-    if (e != hipSuccess) { release_record_buffers(h); return fail(WT_E_HIP, std::string("record: ") + hipGetErrorString(e)); }
-    h->rec_every = every; h->rec_cap = capacity; h->rec_steps = 0;
+    if (int rc = allocate(record_arrays(h, (size_t)capacity * (size_t)h->N))) return rc;
+    h->rec.every = every; h->rec.cap = capacity;
     return WT_OK;
 }
 
@@ -756,21 +761,14 @@ int wt_ensemble_get_record(wt_ensemble *h, double *pH, double *Cl, double *T, do
                            uint32_t *status, int *n_records)
 {
     if (!h) return fail(WT_E_ARG, "NULL handle");
-    if (!h->rec_pH) return fail(WT_E_STATE, "recording is off (wt_ensemble_record)");
+    if (!h->rec.pH) return fail(WT_E_STATE, "recording is off (wt_ensemble_record)");
     HIP_TRY(hipSetDevice(h->device));
-    const int64_t done = h->rec_steps / h->rec_every;
-    const int64_t nr = done < h->rec_cap ? done : h->rec_cap;
-    const size_t per = (size_t)nr * (size_t)h->N, zone = per * (size_t)h->n;
+    const int64_t done = h->rec.steps / h->rec.every;
+    const int64_t nr = done < h->rec.cap ? done : h->rec.cap;
+    const size_t per = (size_t)nr * (size_t)h->N, zone = sizeof(double) * per * (size_t)h->n;
     if (n_records) *n_records = (int)nr;
-    if (nr > 0) {
-        if (pH) HIP_TRY(hipMemcpyAsync(pH, h->rec_pH, sizeof(double) * zone, hipMemcpyDeviceToHost, h->stream));
-        if (Cl) HIP_TRY(hipMemcpyAsync(Cl, h->rec_Cl, sizeof(double) * zone, hipMemcpyDeviceToHost, h->stream));
-        if (T) HIP_TRY(hipMemcpyAsync(T, h->rec_T, sizeof(double) * zone, hipMemcpyDeviceToHost, h->stream));
-        if (time) HIP_TRY(hipMemcpyAsync(time, h->rec_time, sizeof(double) * per, hipMemcpyDeviceToHost, h->stream));
-        if (flow) HIP_TRY(hipMemcpyAsync(flow, h->rec_flow, sizeof(double) * per, hipMemcpyDeviceToHost, h->stream));
-        if (status) HIP_TRY(hipMemcpyAsync(status, h->rec_status, sizeof(uint32_t) * per, hipMemcpyDeviceToHost, h->stream));
-    }
-    return sync_checked(h);
+    return download(h, {{pH, h->rec.pH, zone}, {Cl, h->rec.Cl, zone}, {T, h->rec.T, zone}, {time, h->rec.time, sizeof(double) * per},
+                        {flow, h->rec.flow, sizeof(double) * per}, {status, h->rec.status, sizeof(uint32_t) * per}});
 }
 
 int wt_ensemble_launch_timing(wt_ensemble *h, int enable)
@@ -809,117 +807,95 @@ int wt_ensemble_sensors_enable(wt_ensemble *h, uint64_t seed, int64_t reactor_ba
 {
     if (!h || !cfg_flow || !cfg_chlorine || !cfg_temperature) return fail(WT_E_ARG, "NULL argument");
     if (history_capacity < 0) return fail(WT_E_ARG, "history_capacity must be >= 0");
-    if (h->sensors_on) return fail(WT_E_STATE, "sensor suite already enabled");
+    if (h->sens.on) return fail(WT_E_STATE, "sensor suite already enabled");
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));
-    const size_t N = (size_t)h->N;
+    const size_t N = (size_t)h->N, hist = (size_t)history_capacity * wts::NSENS * N;
+    wts::SuiteArgs &s = h->sens;
     double *cfg = nullptr;
     HIP_TRY(hipMalloc((void **)&cfg, sizeof(double) * 3 * N));
-#define SALLOC(ptr, bytes) do { if (hipMalloc((void **)&(ptr), (bytes)) != hipSuccess) { (void)hipFree(cfg); release_sensor_buffers(h); return fail(WT_E_HIP, "hipMalloc (sensors) failed"); } } while (0)
-    SALLOC(h->s_fs, sizeof(float) * wts::NSENS * wts::NF * N);
-    SALLOC(h->s_ds, sizeof(double) * wts::NSENS * wts::ND * N);
-    SALLOC(h->s_is, sizeof(int32_t) * wts::NSENS * wts::NI * N);
-    SALLOC(h->s_full_scale, sizeof(float) * N);
-    SALLOC(h->s_ring_t, sizeof(float) * 2 * wts::RING * N);
-    SALLOC(h->s_ring_v, sizeof(float) * 2 * wts::RING * N);
-    SALLOC(h->s_ring_head, sizeof(int32_t) * 2 * N);
-    SALLOC(h->s_ring_cnt, sizeof(int32_t) * 2 * N);
-    SALLOC(h->s_out_value, sizeof(float) * wts::NSENS * N);
-    SALLOC(h->s_out_status, wts::NSENS * N);
-    SALLOC(h->s_out_fault, wts::NSENS * N);
-    SALLOC(h->s_t_enable, sizeof(double) * N);
-    h->s_hist_cap = history_capacity;
+    const ArrayGroup arrays = sensor_arrays(h, history_capacity);
+    if (int rc = allocate(arrays)) { (void)hipFree(cfg); return rc; }
     if (history_capacity > 0) {
-        SALLOC(h->s_hist_value, sizeof(float) * (size_t)history_capacity * wts::NSENS * N);
-        SALLOC(h->s_hist_status, (size_t)history_capacity * wts::NSENS * N);
-        SALLOC(h->s_hist_fault, (size_t)history_capacity * wts::NSENS * N);
-        SALLOC(h->s_hist_pos, sizeof(int32_t) * N);
         // slots that are never written (a reactor whose step raised takes no reading) must not hold garbage
-        (void)hipMemsetAsync(h->s_hist_value, 0, sizeof(float) * (size_t)history_capacity * wts::NSENS * N, h->stream);
-        (void)hipMemsetAsync(h->s_hist_status, 0, (size_t)history_capacity * wts::NSENS * N, h->stream);
-        (void)hipMemsetAsync(h->s_hist_fault, 0, (size_t)history_capacity * wts::NSENS * N, h->stream);
+        (void)hipMemsetAsync(s.hist_value, 0, sizeof(float) * hist, h->stream);
+        (void)hipMemsetAsync(s.hist_status, 0, hist, h->stream);
+        (void)hipMemsetAsync(s.hist_fault, 0, hist, h->stream);
     }
-#undef SALLOC
     hipError_t e = hipMemcpy(cfg, cfg_flow, sizeof(double) * N, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(cfg + N, cfg_chlorine, sizeof(double) * N, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(cfg + 2 * N, cfg_temperature, sizeof(double) * N, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpyAsync(h->s_t_enable, h->time, sizeof(double) * N, hipMemcpyDeviceToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(h->s_ring_t, 0, sizeof(float) * 2 * wts::RING * N, h->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(h->s_ring_v, 0, sizeof(float) * 2 * wts::RING * N, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync((double *)s.t_enable, h->time, sizeof(double) * N, hipMemcpyDeviceToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(s.ring_t, 0, sizeof(float) * 2 * wts::RING * N, h->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(s.ring_v, 0, sizeof(float) * 2 * wts::RING * N, h->stream);
     if (e == hipSuccess) {
         wts::SensorInitArgs a;
         a.N = h->N; a.cfg_flow = cfg; a.cfg_cl = cfg + N; a.cfg_temp = cfg + 2 * N;
-        a.fs = h->s_fs; a.ds = h->s_ds; a.is = h->s_is; a.full_scale = h->s_full_scale;
-        a.ring_push = h->s_ring_head; a.ring_cursor = h->s_ring_cnt;
-        a.out_value = h->s_out_value; a.out_status = h->s_out_status; a.out_fault = h->s_out_fault; a.hist_pos = h->s_hist_pos;
+        a.fs = s.fs; a.ds = s.ds; a.is = s.is; a.full_scale = s.full_scale;
+        a.ring_push = s.ring_push; a.ring_cursor = s.ring_cursor;
+        a.out_value = s.out_value; a.out_status = s.out_status; a.out_fault = s.out_fault; a.hist_pos = s.hist_pos;
         hipLaunchKernelGGL(wts::sensor_init_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, h->stream, a);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     (void)hipFree(cfg);
-    if (e != hipSuccess) { release_sensor_buffers(h); return fail(WT_E_HIP, std::string("sensors_enable: ") + hipGetErrorString(e)); }
-    h->sens_seed = seed; h->sens_reactor_base = reactor_base;
-    h->sensors_on = true;
+    if (e != hipSuccess) { release(arrays); return fail(WT_E_HIP, std::string("sensors_enable: ") + hipGetErrorString(e)); }
+    s.seed_lo = (uint32_t)(seed & 0xffffffffu); s.seed_hi = (uint32_t)(seed >> 32); s.reactor_base = reactor_base;
+    s.hist_cap = history_capacity;
+    s.on = 1;
     return WT_OK;
 }
 
 int wt_ensemble_sensors_get(wt_ensemble *h, float *values, uint8_t *status, uint8_t *fault)
 {
     if (!h) return fail(WT_E_ARG, "NULL handle");
-    if (!h->sensors_on) return fail(WT_E_STATE, "sensor suite not enabled");
+    if (!h->sens.on) return fail(WT_E_STATE, "sensor suite not enabled");
     HIP_TRY(hipSetDevice(h->device));
     const size_t cnt = (size_t)wts::NSENS * h->N;
-    if (values) HIP_TRY(hipMemcpyAsync(values, h->s_out_value, sizeof(float) * cnt, hipMemcpyDeviceToHost, h->stream));
-    if (status) HIP_TRY(hipMemcpyAsync(status, h->s_out_status, cnt, hipMemcpyDeviceToHost, h->stream));
-    if (fault) HIP_TRY(hipMemcpyAsync(fault, h->s_out_fault, cnt, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return WT_OK;
+    return download(h, {{values, h->sens.out_value, sizeof(float) * cnt}, {status, h->sens.out_status, cnt},
+                        {fault, h->sens.out_fault, cnt}});
 }
 
 int wt_ensemble_sensors_history(wt_ensemble *h, float *values, uint8_t *status, uint8_t *fault, int32_t *n_filled)
 {
     if (!h) return fail(WT_E_ARG, "NULL handle");
-    if (!h->sensors_on || h->s_hist_cap <= 0) return fail(WT_E_STATE, "sensor history not enabled");
+    if (!h->sens.on || h->sens.hist_cap <= 0) return fail(WT_E_STATE, "sensor history not enabled");
     HIP_TRY(hipSetDevice(h->device));
-    const size_t cnt = (size_t)h->s_hist_cap * wts::NSENS * h->N;
-    if (values) HIP_TRY(hipMemcpyAsync(values, h->s_hist_value, sizeof(float) * cnt, hipMemcpyDeviceToHost, h->stream));
-    if (status) HIP_TRY(hipMemcpyAsync(status, h->s_hist_status, cnt, hipMemcpyDeviceToHost, h->stream));
-    if (fault) HIP_TRY(hipMemcpyAsync(fault, h->s_hist_fault, cnt, hipMemcpyDeviceToHost, h->stream));
-    if (n_filled) HIP_TRY(hipMemcpyAsync(n_filled, h->s_hist_pos, sizeof(int32_t) * h->N, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return WT_OK;
+    const size_t cnt = (size_t)h->sens.hist_cap * wts::NSENS * h->N;
+    return download(h, {{values, h->sens.hist_value, sizeof(float) * cnt}, {status, h->sens.hist_status, cnt},
+                        {fault, h->sens.hist_fault, cnt}, {n_filled, h->sens.hist_pos, sizeof(int32_t) * h->N}});
 }
 
 int wt_ensemble_plc_enable(wt_ensemble *h)
 {
     if (!h) return fail(WT_E_ARG, "NULL handle");
-    if (!h->sensors_on) return fail(WT_E_STATE, "the register image publishes sensor readings: enable the sensor suite first");
-    if (h->plc_on) return fail(WT_E_STATE, "plant I/O already enabled");
+    if (!h->sens.on) return fail(WT_E_STATE, "the register image publishes sensor readings: enable the sensor suite first");
+    if (h->sens.plc_on) return fail(WT_E_STATE, "plant I/O already enabled");
     HIP_TRY(hipSetDevice(h->device));
     const size_t N = (size_t)h->N;
-    hipError_t e = hipMalloc((void **)&h->p_ir, sizeof(uint16_t) * wtp::IR_WORDS * N);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->p_hr, sizeof(uint16_t) * wtp::HR_WORDS * N);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->p_loop_time, sizeof(double) * N);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->p_update_ok, N);
+    const ArrayGroup arrays = plant_io_arrays(h);
+    if (int rc = allocate(arrays)) return rc;
+    wtp::PackArgs &p = h->sens.pack;
     // ModbusSequentialDataBlock(0, [0] * size): every register starts at 0 (slave.py:134-137); sim_time = 0.0
-    if (e == hipSuccess) e = hipMemsetAsync(h->p_ir, 0, sizeof(uint16_t) * wtp::IR_WORDS * N, h->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(h->p_hr, 0, sizeof(uint16_t) * wtp::HR_WORDS * N, h->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(h->p_loop_time, 0, sizeof(double) * N, h->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(h->p_update_ok, 1, N, h->stream);
+    hipError_t e = hipMemsetAsync(p.ir, 0, sizeof(uint16_t) * wtp::IR_WORDS * N, h->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(h->ctl.hr, 0, sizeof(uint16_t) * wtp::HR_WORDS * N, h->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(p.loop_time, 0, sizeof(double) * N, h->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(p.update_ok, 1, N, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) { release_plc_buffers(h); return fail(WT_E_HIP, std::string("plc_enable: ") + hipGetErrorString(e)); }
-    h->plc_on = true;
+    if (e != hipSuccess) { release(arrays); return fail(WT_E_HIP, std::string("plc_enable: ") + hipGetErrorString(e)); }
+    h->sens.cmd.hr = h->ctl.hr;
+    h->sens.plc_on = 1;
     return WT_OK;
 }
 
 int wt_ensemble_plc_write_holding(wt_ensemble *h, const uint16_t *words, int64_t first_reactor, int64_t count)
 {
     if (!h || !words) return fail(WT_E_ARG, "NULL argument");
-    if (!h->plc_on) return fail(WT_E_STATE, "plant I/O not enabled");
+    if (!h->sens.plc_on) return fail(WT_E_STATE, "plant I/O not enabled");
     if (first_reactor < 0 || count < 0 || first_reactor + count > h->N) return fail(WT_E_ARG, "reactor range outside the ensemble");
     if (count == 0) return WT_OK;
     HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipMemcpyAsync(h->p_hr + first_reactor * wtp::HR_WORDS, words, sizeof(uint16_t) * wtp::HR_WORDS * (size_t)count,
+    HIP_TRY(hipMemcpyAsync(h->ctl.hr + first_reactor * wtp::HR_WORDS, words, sizeof(uint16_t) * wtp::HR_WORDS * (size_t)count,
                            hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));   // the caller's buffer is free on return
     return WT_OK;
@@ -928,20 +904,18 @@ int wt_ensemble_plc_write_holding(wt_ensemble *h, const uint16_t *words, int64_t
 int wt_ensemble_plc_read_inputs(wt_ensemble *h, uint16_t *words, uint8_t *update_ok)
 {
     if (!h) return fail(WT_E_ARG, "NULL handle");
-    if (!h->plc_on) return fail(WT_E_STATE, "plant I/O not enabled");
+    if (!h->sens.plc_on) return fail(WT_E_STATE, "plant I/O not enabled");
     HIP_TRY(hipSetDevice(h->device));
-    if (words) HIP_TRY(hipMemcpyAsync(words, h->p_ir, sizeof(uint16_t) * wtp::IR_WORDS * (size_t)h->N, hipMemcpyDeviceToHost, h->stream));
-    if (update_ok) HIP_TRY(hipMemcpyAsync(update_ok, h->p_update_ok, (size_t)h->N, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return WT_OK;
+    return download(h, {{words, h->sens.pack.ir, sizeof(uint16_t) * wtp::IR_WORDS * (size_t)h->N},
+                        {update_ok, h->sens.pack.update_ok, (size_t)h->N}});
 }
 
 int wt_ensemble_plc_device(wt_ensemble *h, void **input_image, void **holding_image)
 {
     if (!h) return fail(WT_E_ARG, "NULL handle");
-    if (!h->plc_on) return fail(WT_E_STATE, "plant I/O not enabled");
-    if (input_image) *input_image = h->p_ir;
-    if (holding_image) *holding_image = h->p_hr;
+    if (!h->sens.plc_on) return fail(WT_E_STATE, "plant I/O not enabled");
+    if (input_image) *input_image = h->sens.pack.ir;
+    if (holding_image) *holding_image = h->ctl.hr;
     return WT_OK;
 }
 
@@ -971,14 +945,27 @@ const char *control_params_error(const double *p, int64_t N)
     return nullptr;
 }
 
+// The preconditions shared by the set calls of the scan programs, in this order: the arguments, plant I/O on
+// (needs_plc: the refusal), the zone limit (zones: the refusal; nullptr: every kernel carries the program), a state
+// refusal of the caller's (nullptr: none), then the parameter block through wt_program_check.
+int check_program_set(const wt_ensemble *h, const double *params, int program, const char *needs_plc, const char *zones,
+                      const char *refusal = nullptr)
+{
+    if (!h || !params) return fail(WT_E_ARG, "NULL argument");
+    if (!h->sens.plc_on) return fail(WT_E_STATE, needs_plc);
+    if (zones && !wt::prog_in_item(levels_for(h->n))) return fail(WT_E_STATE, zones);
+    if (refusal) return fail(WT_E_STATE, refusal);
+    return wt_program_check(program, params, h->N);
+}
+
 // Enable (retune == false) or retune the PI programs.  A loop starts -- integral 0, output and holding words the
 // float32 of the clamped bias, metrics 0 -- where enable switches it on; retune keeps the state of the other loops.
 int control_load(wt_ensemble *h, const double *params, bool retune)
 {
     if (!params) return fail(WT_E_ARG, "params is NULL");
-    if (!h->plc_on) return fail(WT_E_STATE, "control writes the holding image: enable plant I/O first");
-    if (retune && !h->ctl_on) return fail(WT_E_STATE, "control is off (wt_ensemble_control_enable)");
-    if (const char *msg = control_params_error(params, h->N)) return fail(WT_E_ARG, msg);
+    if (int rc = check_program_set(h, params, WT_PROG_CONTROL, "control writes the holding image: enable plant I/O first", nullptr,
+                                   retune && !h->ctl.on ? "control is off (wt_ensemble_control_enable)" : nullptr))
+        return rc;
     HIP_TRY(hipSetDevice(h->device));
     const int64_t N = h->N;
     const size_t par_bytes = sizeof(double) * wtc::PAR_DOUBLES * (size_t)N, st_bytes = sizeof(double) * wtc::ST_DOUBLES * (size_t)N;
@@ -986,15 +973,11 @@ int control_load(wt_ensemble *h, const double *params, bool retune)
     std::vector<double> st((size_t)N * wtc::ST_DOUBLES, 0.0), lt((size_t)N);
     std::vector<uint16_t> hr((size_t)N * wtp::HR_WORDS);
     HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still read or write the old records
-    if (int rc = alloc_program(control_arrays(h), N)) return rc;
-    HIP_TRY(hipMemcpyAsync(hr.data(), h->p_hr, sizeof(uint16_t) * hr.size(), hipMemcpyDeviceToHost, h->stream));
-    if (retune) {
-        HIP_TRY(hipMemcpyAsync(st.data(), h->c_st, st_bytes, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipMemcpyAsync(old.data(), h->c_par, par_bytes, hipMemcpyDeviceToHost, h->stream));
-    } else {
-        HIP_TRY(hipMemcpyAsync(lt.data(), h->p_loop_time, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost, h->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (int rc = allocate(control_arrays(h))) return rc;
+    if (int rc = download(h, {{hr.data(), h->ctl.hr, sizeof(uint16_t) * hr.size()},
+                              {retune ? st.data() : nullptr, h->ctl.st, st_bytes}, {retune ? old.data() : nullptr, h->ctl.par, par_bytes},
+                              {retune ? nullptr : lt.data(), h->sens.pack.loop_time, sizeof(double) * (size_t)N}}))
+        return rc;
     blocks_to_records(params, wtc::LOOPS, wtc::NC, N, par.data(), wtc::PAR_DOUBLES);
     for (int64_t r = 0; r < N; ++r) {
         double *s = st.data() + r * wtc::ST_DOUBLES;
@@ -1013,11 +996,11 @@ int control_load(wt_ensemble *h, const double *params, bool retune)
             w[0] = (uint16_t)(b >> 16); w[1] = (uint16_t)(b & 0xffffu);
         }
     }
-    HIP_TRY(hipMemcpyAsync(h->c_par, par.data(), par_bytes, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->c_st, st.data(), st_bytes, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->p_hr, hr.data(), sizeof(uint16_t) * hr.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync((double *)h->ctl.par, par.data(), par_bytes, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->ctl.st, st.data(), st_bytes, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->ctl.hr, hr.data(), sizeof(uint16_t) * hr.size(), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));   // the host vectors are freed on return
-    h->ctl_on = true;
+    h->ctl.on = 1;
     return WT_OK;
 }
 
@@ -1040,14 +1023,9 @@ int wt_ensemble_control_retune(wt_ensemble *h, const double *params)
 int wt_ensemble_control_get(wt_ensemble *h, double *state)
 {
     if (!h || !state) return fail(WT_E_ARG, "NULL argument");
-    if (!h->ctl_on) return fail(WT_E_STATE, "control is off (wt_ensemble_control_enable)");
+    if (!h->ctl.on) return fail(WT_E_STATE, "control is off (wt_ensemble_control_enable)");
     HIP_TRY(hipSetDevice(h->device));
-    const int64_t N = h->N;
-    std::vector<double> st((size_t)N * wtc::ST_DOUBLES);
-    HIP_TRY(hipMemcpyAsync(st.data(), h->c_st, sizeof(double) * st.size(), hipMemcpyDeviceToHost, h->stream));
-    if (int rc = sync_checked(h)) return rc;
-    records_to_blocks(st.data(), wtc::ST_DOUBLES, wtc::LOOPS, wtc::NCS, N, state);
-    return WT_OK;
+    return download_records(h, {{state, h->ctl.st, wtc::ST_DOUBLES, wtc::LOOPS, wtc::NCS}});
 }
 
 int wt_ensemble_control_disable(wt_ensemble *h)
@@ -1094,10 +1072,9 @@ extern "C" {
 
 int wt_ensemble_inject_set(wt_ensemble *h, const double *params)
 {
-    if (!h || !params) return fail(WT_E_ARG, "NULL argument");
-    if (!h->plc_on) return fail(WT_E_STATE, "injection acts on the plant I/O images: enable plant I/O first");
-    if (!wt::inj_in_item(levels_for(h->n))) return fail(WT_E_STATE, "injection programs run in the kernels for up to 32 zones");
-    if (const char *msg = inject_params_error(params, h->N)) return fail(WT_E_ARG, msg);
+    if (int rc = check_program_set(h, params, WT_PROG_INJECT, "injection acts on the plant I/O images: enable plant I/O first",
+                                   "injection programs run in the kernels for up to 32 zones"))
+        return rc;
     HIP_TRY(hipSetDevice(h->device));
     const int64_t N = h->N;
     const size_t par_bytes = sizeof(double) * wti::PAR_DOUBLES * (size_t)N, st_bytes = sizeof(double) * wti::ST_DOUBLES * (size_t)N;
@@ -1109,25 +1086,20 @@ int wt_ensemble_inject_set(wt_ensemble *h, const double *params)
             q[wti::IS_N_APPLIED] = 0.0; q[wti::IS_T_FIRST] = q[wti::IS_T_LAST] = q[wti::IS_HELD] = NAN;
         }
     HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still read or write the old records
-    if (int rc = alloc_program(inject_arrays(h), N)) return rc;
-    HIP_TRY(hipMemcpyAsync(h->i_par, par.data(), par_bytes, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->i_st, st.data(), st_bytes, hipMemcpyHostToDevice, h->stream));
+    if (int rc = allocate(inject_arrays(h))) return rc;
+    HIP_TRY(hipMemcpyAsync((double *)h->inj.par, par.data(), par_bytes, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->inj.st, st.data(), st_bytes, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));   // the host vectors are freed on return
-    h->inj_on = true;
+    h->inj.on = 1;
     return WT_OK;
 }
 
 int wt_ensemble_inject_get(wt_ensemble *h, double *state)
 {
     if (!h || !state) return fail(WT_E_ARG, "NULL argument");
-    if (!h->inj_on) return fail(WT_E_STATE, "no injection program is set (wt_ensemble_inject_set)");
+    if (!h->inj.on) return fail(WT_E_STATE, "no injection program is set (wt_ensemble_inject_set)");
     HIP_TRY(hipSetDevice(h->device));
-    const int64_t N = h->N;
-    std::vector<double> st((size_t)N * wti::ST_DOUBLES);
-    HIP_TRY(hipMemcpyAsync(st.data(), h->i_st, sizeof(double) * st.size(), hipMemcpyDeviceToHost, h->stream));
-    if (int rc = sync_checked(h)) return rc;
-    records_to_blocks(st.data(), wti::ST_DOUBLES, wti::SLOTS, wti::NIS, N, state);
-    return WT_OK;
+    return download_records(h, {{state, h->inj.st, wti::ST_DOUBLES, wti::SLOTS, wti::NIS}});
 }
 
 int wt_ensemble_inject_clear(wt_ensemble *h)
@@ -1206,10 +1178,9 @@ extern "C" {
 
 int wt_ensemble_alarm_set(wt_ensemble *h, const double *params)
 {
-    if (!h || !params) return fail(WT_E_ARG, "NULL argument");
-    if (!h->plc_on) return fail(WT_E_STATE, "alarms act on the plant I/O scan: enable plant I/O first");
-    if (!wt::alm_in_item(levels_for(h->n))) return fail(WT_E_STATE, "alarm programs run in the kernels for up to 32 zones");
-    if (const char *msg = alarm_params_error(params, h->N)) return fail(WT_E_ARG, msg);
+    if (int rc = check_program_set(h, params, WT_PROG_ALARM, "alarms act on the plant I/O scan: enable plant I/O first",
+                                   "alarm programs run in the kernels for up to 32 zones"))
+        return rc;
     HIP_TRY(hipSetDevice(h->device));
     const int64_t N = h->N;
     const size_t par_bytes = sizeof(double) * wta::PAR_DOUBLES * (size_t)N, st_bytes = sizeof(double) * wta::ST_DOUBLES * (size_t)N;
@@ -1222,51 +1193,42 @@ int wt_ensemble_alarm_set(wt_ensemble *h, const double *params)
             double *q = st.data() + r * wta::ST_DOUBLES + s * wta::NAS;
             q[wta::AS_PENDING] = q[wta::AS_T_FIRST] = q[wta::AS_T_LAST] = NAN;
         }
-    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still read or write the old records
-    HIP_TRY(hipMemcpyAsync(lt.data(), h->p_loop_time, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    // (the download also waits for queued launches, which may still read or write the old records)
+    if (int rc = download(h, {{lt.data(), h->sens.pack.loop_time, sizeof(double) * (size_t)N}})) return rc;
     for (int64_t r = 0; r < N; ++r) {
         double *q = rst.data() + r * wta::RST_DOUBLES;
         q[wta::AR_T_PREV] = lt[(size_t)r]; q[wta::AR_FIRST_OUT] = -1.0; q[wta::AR_OVR_ACID] = q[wta::AR_OVR_CHLORINE] = NAN;
     }
-    if (int rc = alloc_program(alarm_arrays(h), N)) return rc;
-    HIP_TRY(hipMemcpyAsync(h->a_par, par.data(), par_bytes, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->a_st, st.data(), st_bytes, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->a_rst, rst.data(), rst_bytes, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemsetAsync(h->a_word, 0, word_bytes, h->stream));
+    if (int rc = allocate(alarm_arrays(h))) return rc;
+    HIP_TRY(hipMemcpyAsync((double *)h->alm.par, par.data(), par_bytes, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->alm.st, st.data(), st_bytes, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->alm.rst, rst.data(), rst_bytes, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemsetAsync(h->alm.word, 0, word_bytes, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));   // the host vectors are freed on return
-    h->alm_on = true;
+    h->alm.on = 1;
     return WT_OK;
 }
 
 int wt_ensemble_alarm_get(wt_ensemble *h, double *slot_state, double *reactor_state)
 {
     if (!h) return fail(WT_E_ARG, "NULL handle");
-    if (!h->alm_on) return fail(WT_E_STATE, k_no_alarm);
+    if (!h->alm.on) return fail(WT_E_STATE, k_no_alarm);
     HIP_TRY(hipSetDevice(h->device));
-    const int64_t N = h->N;
-    std::vector<double> st((size_t)N * wta::ST_DOUBLES), rst((size_t)N * wta::RST_DOUBLES);
-    HIP_TRY(hipMemcpyAsync(st.data(), h->a_st, sizeof(double) * st.size(), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(rst.data(), h->a_rst, sizeof(double) * rst.size(), hipMemcpyDeviceToHost, h->stream));
-    if (int rc = sync_checked(h)) return rc;
-    if (slot_state) records_to_blocks(st.data(), wta::ST_DOUBLES, wta::SLOTS, wta::NAS, N, slot_state);
-    if (reactor_state) records_to_blocks(rst.data(), wta::RST_DOUBLES, 1, wta::NAR, N, reactor_state);
-    return WT_OK;
+    return download_records(h, {{slot_state, h->alm.st, wta::ST_DOUBLES, wta::SLOTS, wta::NAS},
+                                {reactor_state, h->alm.rst, wta::RST_DOUBLES, 1, wta::NAR}});
 }
 
 int wt_ensemble_alarm_reset(wt_ensemble *h, const uint8_t *mask)
 {
     if (!h) return fail(WT_E_ARG, "NULL handle");
-    if (!h->alm_on) return fail(WT_E_STATE, k_no_alarm);
+    if (!h->alm.on) return fail(WT_E_STATE, k_no_alarm);
     HIP_TRY(hipSetDevice(h->device));
     const int64_t N = h->N;
     std::vector<double> par((size_t)N * wta::PAR_DOUBLES), st((size_t)N * wta::ST_DOUBLES), rst((size_t)N * wta::RST_DOUBLES);
     std::vector<uint16_t> word((size_t)N);
-    HIP_TRY(hipMemcpyAsync(par.data(), h->a_par, sizeof(double) * par.size(), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(st.data(), h->a_st, sizeof(double) * st.size(), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(rst.data(), h->a_rst, sizeof(double) * rst.size(), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(word.data(), h->a_word, sizeof(uint16_t) * word.size(), hipMemcpyDeviceToHost, h->stream));
-    if (int rc = sync_checked(h)) return rc;
+    if (int rc = download(h, {{par.data(), h->alm.par, sizeof(double) * par.size()}, {st.data(), h->alm.st, sizeof(double) * st.size()},
+                              {rst.data(), h->alm.rst, sizeof(double) * rst.size()}, {word.data(), h->alm.word, sizeof(uint16_t) * word.size()}}))
+        return rc;
     for (int64_t r = 0; r < N; ++r) {
         if (mask && !mask[r]) continue;
         const double *p = par.data() + r * wta::PAR_DOUBLES;
@@ -1279,9 +1241,9 @@ int wt_ensemble_alarm_reset(wt_ensemble *h, const uint8_t *mask)
         }
         word[(size_t)r] = alarm_settle(p, q, rst.data() + r * wta::RST_DOUBLES);
     }
-    HIP_TRY(hipMemcpyAsync(h->a_st, st.data(), sizeof(double) * st.size(), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->a_rst, rst.data(), sizeof(double) * rst.size(), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->a_word, word.data(), sizeof(uint16_t) * word.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->alm.st, st.data(), sizeof(double) * st.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->alm.rst, rst.data(), sizeof(double) * rst.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->alm.word, word.data(), sizeof(uint16_t) * word.size(), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     return WT_OK;
 }
@@ -1289,17 +1251,16 @@ int wt_ensemble_alarm_reset(wt_ensemble *h, const uint8_t *mask)
 int wt_ensemble_alarm_words(wt_ensemble *h, uint16_t *words)
 {
     if (!h || !words) return fail(WT_E_ARG, "NULL argument");
-    if (!h->alm_on) return fail(WT_E_STATE, k_no_alarm);
+    if (!h->alm.on) return fail(WT_E_STATE, k_no_alarm);
     HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipMemcpyAsync(words, h->a_word, sizeof(uint16_t) * (size_t)h->N, hipMemcpyDeviceToHost, h->stream));
-    return sync_checked(h);
+    return download(h, {{words, h->alm.word, sizeof(uint16_t) * (size_t)h->N}});
 }
 
 int wt_ensemble_alarm_device(wt_ensemble *h, void **word)
 {
     if (!h || !word) return fail(WT_E_ARG, "NULL argument");
-    if (!h->alm_on) return fail(WT_E_STATE, k_no_alarm);
-    *word = h->a_word;
+    if (!h->alm.on) return fail(WT_E_STATE, k_no_alarm);
+    *word = h->alm.word;
     return WT_OK;
 }
 
@@ -1362,19 +1323,17 @@ extern "C" {
 
 int wt_ensemble_actuator_set(wt_ensemble *h, const double *params)
 {
-    if (!h || !params) return fail(WT_E_ARG, "NULL argument");
-    if (!h->plc_on) return fail(WT_E_STATE, "actuators act on the plant I/O scan: enable plant I/O first");
-    if (!wt::act_in_item(levels_for(h->n))) return fail(WT_E_STATE, "actuator programs run in the kernels for up to 32 zones");
-    if (const char *msg = actuator_params_error(params, h->N)) return fail(WT_E_ARG, msg);
+    if (int rc = check_program_set(h, params, WT_PROG_ACTUATOR, "actuators act on the plant I/O scan: enable plant I/O first",
+                                   "actuator programs run in the kernels for up to 32 zones"))
+        return rc;
     HIP_TRY(hipSetDevice(h->device));
     const int64_t N = h->N;
     std::vector<double> par((size_t)N * wtv::PAR_DOUBLES), st((size_t)N * wtv::ST_DOUBLES, 0.0), q((size_t)N * wtv::Q_DOUBLES);
     std::vector<double> lt((size_t)N), bc((size_t)N * wt::NB);
     blocks_to_records(params, wtv::CH, wtv::NV, N, par.data(), wtv::PAR_DOUBLES);
-    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still read or write the old records
-    HIP_TRY(hipMemcpyAsync(lt.data(), h->p_loop_time, sizeof(double) * lt.size(), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(bc.data(), h->bc, sizeof(double) * bc.size(), hipMemcpyDeviceToHost, h->stream));
-    if (int rc = sync_checked(h)) return rc;
+    // (the download also waits for queued launches, which may still read or write the old records)
+    if (int rc = download(h, {{lt.data(), h->sens.pack.loop_time, sizeof(double) * lt.size()}, {bc.data(), h->bc, sizeof(double) * bc.size()}}))
+        return rc;
     for (int64_t r = 0; r < N; ++r)
         for (int k = 0; k < wtv::CH; ++k) {
             const double row = bc[(size_t)(wtv::row_of(k) * N + r)];
@@ -1382,30 +1341,23 @@ int wt_ensemble_actuator_set(wt_ensemble *h, const double *params)
             s[wtv::VS_POSITION] = s[wtv::VS_APPLIED] = s[wtv::VS_PLAY] = s[wtv::VS_DEMAND] = row;
             for (int i = 0; i < wtv::MAX_DELAY; ++i) q[(size_t)(r * wtv::Q_DOUBLES + k * wtv::MAX_DELAY + i)] = row;
         }
-    if (int rc = alloc_program(actuator_arrays(h), N)) return rc;
-    HIP_TRY(hipMemcpyAsync(h->v_par, par.data(), sizeof(double) * par.size(), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->v_st, st.data(), sizeof(double) * st.size(), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->v_q, q.data(), sizeof(double) * q.size(), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->v_tp, lt.data(), sizeof(double) * lt.size(), hipMemcpyHostToDevice, h->stream));
+    if (int rc = allocate(actuator_arrays(h))) return rc;
+    HIP_TRY(hipMemcpyAsync((double *)h->act.par, par.data(), sizeof(double) * par.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->act.st, st.data(), sizeof(double) * st.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->act.q, q.data(), sizeof(double) * q.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->act.tp, lt.data(), sizeof(double) * lt.size(), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));   // the host vectors are freed on return
-    h->act_on = true;
+    h->act.on = 1;
     return WT_OK;
 }
 
 int wt_ensemble_actuator_get(wt_ensemble *h, double *state, double *queue, double *t_prev)
 {
     if (!h) return fail(WT_E_ARG, "NULL handle");
-    if (!h->act_on) return fail(WT_E_STATE, k_no_actuator);
+    if (!h->act.on) return fail(WT_E_STATE, k_no_actuator);
     HIP_TRY(hipSetDevice(h->device));
-    const int64_t N = h->N;
-    std::vector<double> st((size_t)N * wtv::ST_DOUBLES), q((size_t)N * wtv::Q_DOUBLES);
-    HIP_TRY(hipMemcpyAsync(st.data(), h->v_st, sizeof(double) * st.size(), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(q.data(), h->v_q, sizeof(double) * q.size(), hipMemcpyDeviceToHost, h->stream));
-    if (t_prev) HIP_TRY(hipMemcpyAsync(t_prev, h->v_tp, sizeof(double) * (size_t)N, hipMemcpyDeviceToHost, h->stream));
-    if (int rc = sync_checked(h)) return rc;
-    if (state) records_to_blocks(st.data(), wtv::ST_DOUBLES, wtv::CH, wtv::NVS, N, state);
-    if (queue) records_to_blocks(q.data(), wtv::Q_DOUBLES, wtv::CH, wtv::MAX_DELAY, N, queue);
-    return WT_OK;
+    return download_records(h, {{state, h->act.st, wtv::ST_DOUBLES, wtv::CH, wtv::NVS},
+                                {queue, h->act.q, wtv::Q_DOUBLES, wtv::CH, wtv::MAX_DELAY}, {t_prev, h->act.tp, 1, 1, 1}});
 }
 
 int wt_ensemble_actuator_clear(wt_ensemble *h)
@@ -1434,9 +1386,7 @@ int wt_ensemble_get_boundary(wt_ensemble *h, double *bc)
     if (!h || !bc) return fail(WT_E_ARG, "NULL argument");
     if (!h->have_bc) return fail(WT_E_STATE, "set_boundary must precede get_boundary");
     HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipMemcpyAsync(bc, h->bc, sizeof(double) * WT_NB * (size_t)h->N, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return WT_OK;
+    return download(h, {{bc, h->bc, sizeof(double) * WT_NB * (size_t)h->N}});
 }
 
 int wt_ensemble_diagnostics(wt_ensemble *h, double *out)
@@ -1450,9 +1400,7 @@ int wt_ensemble_diagnostics(wt_ensemble *h, double *out)
     a.N = h->N; a.n = h->n; a.par = h->par; a.pH = h->pH; a.Cl = h->Cl; a.T = h->T; a.H = h->dH; a.out = h->diag_out;
     hipLaunchKernelGGL(wtd::diagnostics_kernel, dim3((unsigned)((h->N + 63) / 64)), dim3(64), 0, h->stream, a);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out, h->diag_out, bytes, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return WT_OK;
+    return download(h, {{out, h->diag_out, bytes}});
 }
 
 int wt_ensemble_set_placement(wt_ensemble *h, int mode)
@@ -1473,12 +1421,9 @@ int wt_ensemble_get_placement(wt_ensemble *h, int *mode, int32_t *perm)
 {
     if (!h) return fail(WT_E_ARG, "NULL handle");
     if (mode) *mode = h->placement;
-    if (perm) {
-        HIP_TRY(hipSetDevice(h->device));
-        HIP_TRY(hipMemcpyAsync(perm, h->perm, sizeof(int32_t) * (size_t)h->N, hipMemcpyDeviceToHost, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));
-    }
-    return WT_OK;
+    if (!perm) return WT_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    return download(h, {{perm, h->perm, sizeof(int32_t) * (size_t)h->N}});
 }
 
 int wt_ensemble_placement_info(wt_ensemble *h, int64_t *redeals, int64_t *history_steps)
@@ -1568,9 +1513,7 @@ int wt_ensemble_get_bad_temperature(wt_ensemble *h, double *value)
 {
     if (!h || !value) return fail(WT_E_ARG, "NULL argument");
     HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipMemcpyAsync(value, h->bad_T, sizeof(double) * h->N, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return WT_OK;
+    return download(h, {{value, h->bad_T, sizeof(double) * h->N}});
 }
 
 int wt_ensemble_synchronize(wt_ensemble *h)
@@ -1578,13 +1521,6 @@ int wt_ensemble_synchronize(wt_ensemble *h)
     if (!h) return fail(WT_E_ARG, "NULL handle");
     HIP_TRY(hipSetDevice(h->device));
     return sync_checked(h);
-}
-
-static int d2h(wt_ensemble *h, void *dst, const void *src, size_t bytes)
-{
-    if (!dst) return WT_OK;
-    HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream));
-    return WT_OK;
 }
 
 // Small ensembles: pack everything a snapshot can ask for into one device image, one copy into pinned memory, one
@@ -1617,14 +1553,8 @@ int wt_ensemble_get_state(wt_ensemble *h, double *pH, double *Cl, double *T, dou
     if (!h) return fail(WT_E_ARG, "NULL handle");
     HIP_TRY(hipSetDevice(h->device));
     if (h->snap_host) return packed_snapshot(h, pH, Cl, T, time, flow, nullptr, nullptr, nullptr, nullptr);
-    const size_t b = sizeof(double) * (size_t)h->N * h->n;
-    int rc;
-    if ((rc = d2h(h, pH, h->pH, b))) return rc;
-    if ((rc = d2h(h, Cl, h->Cl, b))) return rc;
-    if ((rc = d2h(h, T, h->T, b))) return rc;
-    if ((rc = d2h(h, time, h->time, sizeof(double) * h->N))) return rc;
-    if ((rc = d2h(h, flow, h->flow, sizeof(double) * h->N))) return rc;
-    return sync_checked(h);
+    const size_t b = sizeof(double) * (size_t)h->N * h->n, bn = sizeof(double) * h->N;
+    return download(h, {{pH, h->pH, b}, {Cl, h->Cl, b}, {T, h->T, b}, {time, h->time, bn}, {flow, h->flow, bn}});
 }
 
 int wt_ensemble_get_snapshot(wt_ensemble *h, double *pH, double *Cl, double *T, double *time, double *flow,
@@ -1633,13 +1563,9 @@ int wt_ensemble_get_snapshot(wt_ensemble *h, double *pH, double *Cl, double *T, 
     if (!h) return fail(WT_E_ARG, "NULL handle");
     HIP_TRY(hipSetDevice(h->device));
     if (h->snap_host) return packed_snapshot(h, pH, Cl, T, time, flow, H, rho, kdecay, flags);
-    const size_t b = sizeof(double) * (size_t)h->N * h->n;
-    int rc;
-    if ((rc = d2h(h, pH, h->pH, b)) || (rc = d2h(h, Cl, h->Cl, b)) || (rc = d2h(h, T, h->T, b))) return rc;
-    if ((rc = d2h(h, time, h->time, sizeof(double) * h->N)) || (rc = d2h(h, flow, h->flow, sizeof(double) * h->N))) return rc;
-    if ((rc = d2h(h, H, h->dH, b)) || (rc = d2h(h, rho, h->dRho, b)) || (rc = d2h(h, kdecay, h->dK, b))) return rc;
-    if ((rc = d2h(h, flags, h->status, sizeof(uint32_t) * h->N))) return rc;
-    return sync_checked(h);
+    const size_t b = sizeof(double) * (size_t)h->N * h->n, bn = sizeof(double) * h->N;
+    return download(h, {{pH, h->pH, b}, {Cl, h->Cl, b}, {T, h->T, b}, {time, h->time, bn}, {flow, h->flow, bn},
+                        {H, h->dH, b}, {rho, h->dRho, b}, {kdecay, h->dK, b}, {flags, h->status, sizeof(uint32_t) * h->N}});
 }
 
 int wt_ensemble_get_derived(wt_ensemble *h, double *H, double *rho, double *kdecay)
@@ -1647,20 +1573,14 @@ int wt_ensemble_get_derived(wt_ensemble *h, double *H, double *rho, double *kdec
     if (!h) return fail(WT_E_ARG, "NULL handle");
     HIP_TRY(hipSetDevice(h->device));
     const size_t b = sizeof(double) * (size_t)h->N * h->n;
-    int rc;
-    if ((rc = d2h(h, H, h->dH, b))) return rc;
-    if ((rc = d2h(h, rho, h->dRho, b))) return rc;
-    if ((rc = d2h(h, kdecay, h->dK, b))) return rc;
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return WT_OK;
+    return download(h, {{H, h->dH, b}, {rho, h->dRho, b}, {kdecay, h->dK, b}});
 }
 
 int wt_ensemble_get_status(wt_ensemble *h, uint32_t *flags)
 {
     if (!h || !flags) return fail(WT_E_ARG, "NULL argument");
     HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipMemcpyAsync(flags, h->status, sizeof(uint32_t) * h->N, hipMemcpyDeviceToHost, h->stream));
-    return sync_checked(h);
+    return download(h, {{flags, h->status, sizeof(uint32_t) * h->N}});
 }
 
 int wt_ensemble_clear_status(wt_ensemble *h)
@@ -1675,9 +1595,7 @@ int wt_ensemble_get_stats(wt_ensemble *h, wt_solver_stats *stats)
 {
     if (!h || !stats) return fail(WT_E_ARG, "NULL argument");
     HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipMemcpyAsync(stats, h->stats, sizeof(int32_t) * 5 * h->N, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return WT_OK;
+    return download(h, {{stats, h->stats, sizeof(int32_t) * 5 * h->N}});
 }
 
 int wt_ensemble_rhs(wt_ensemble *h, const double *pH, const double *Cl, const double *T,
