@@ -18,7 +18,7 @@ from typing import Dict, Iterable, List, Optional, Sequence, Union
 
 import numpy as np
 
-from . import _native, _program, actuator, alarm, control, inject, params
+from . import _native, _program, actuator, alarm, control, disturb, inject, params
 
 logger = logging.getLogger(__name__)
 
@@ -272,6 +272,7 @@ class ReactorEnsemble:
         self._boundary: Optional[np.ndarray] = None
         self._device_boundary_moved = False     # the command path (plant I/O) rewrites the device's boundary block
         self._plant_io = False
+        self._disturb_history = -1              # capacity of the disturbance program's history; -1: no program
         self._control_params: Optional[np.ndarray] = None   # the last block enable_control / retune_control sent
 
     # -- lifetime
@@ -312,6 +313,8 @@ class ReactorEnsemble:
         if boundary_schedule is not None:
             if boundaries is not None:
                 raise ValueError("give either boundaries or boundary_schedule, not both")
+            if self._disturb_history >= 0:
+                raise ValueError("a boundary schedule cannot be combined with a disturbance program (clear_disturbances)")
             blk = boundary_schedule_block(boundary_schedule, int(n_steps), self.n_reactors)
             try:
                 _native.check(_native.lib().wt_ensemble_step_scheduled(self._h, float(dt), int(n_steps), 1 if fused else 0,
@@ -334,8 +337,9 @@ class ReactorEnsemble:
             if e.code == _native.WT_E_ARG:
                 raise ValueError(e.message) from None
             raise
-        if getattr(self, "_plant_io", False):
-            self._device_boundary_moved = True    # every PLC scan rewrites the device's boundary rows 0 / 4 / 6
+        if getattr(self, "_plant_io", False) or self._disturb_history >= 0:
+            # every PLC scan rewrites the device's boundary rows 0 / 4 / 6, a disturbance program its targeted rows
+            self._device_boundary_moved = True
         return self.state if download else None
 
     def record(self, every: int = 1, capacity: int = 0) -> None:
@@ -692,6 +696,46 @@ class ReactorEnsemble:
     def clear_actuators(self) -> None:
         """Stop the actuator program: from the next scan on the commands reach the plant at once."""
         self._control_call(_native.lib().wt_ensemble_actuator_clear)
+
+    # -- disturbance programs after every outer step, on the device (wt_dst.hpp)
+    def set_disturbances(self, *disturbances: "disturb.Disturbance", seed: int = 0xD157, reactor_base: int = 0,
+                         history: int = 0) -> None:
+        """Move up to four boundary rows per reactor on their own (one :class:`Disturbance` per slot: steps, ramps,
+        sines, Ornstein-Uhlenbeck wandering) on the rows the command path does not own.  After every outer step,
+        inside the step call, the rows become ``clamp(base + offsets)`` for the reactor's next step; the base is the
+        boundary in force now (a later :meth:`set_boundary` replaces it).  ``seed`` and ``reactor_base`` key the OU
+        draws (shards of one ensemble pass their first global reactor); ``history`` > 0 keeps that many offsets per
+        reactor.  Replaces any program.  Not with ``boundary_schedule``; at most 32 zones per reactor."""
+        blk = disturb.disturbance_block(self.n_reactors, *disturbances)
+        self._control_call(_native.lib().wt_ensemble_disturb_set, _native.dptr(blk),
+                           C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), int(reactor_base), int(history))
+        self._disturb_history = int(history)
+        self._device_boundary_moved = True
+
+    def disturbance_state(self) -> "disturb.DisturbanceState":
+        """Slot state, base block and t_prev of the disturbance program (one synchronisation)."""
+        N = self.n_reactors
+        st = np.empty((disturb.SLOTS, disturb.NDS, N), dtype=np.float64)
+        base = np.empty((len(params.BOUNDARY_FIELDS), N), dtype=np.float64)
+        tp = np.empty(N, dtype=np.float64)
+        self._control_call(_native.lib().wt_ensemble_disturb_get, _native.dptr(st), _native.dptr(base), _native.dptr(tp))
+        return disturb.DisturbanceState.from_block(st, base, tp)
+
+    def disturbance_history(self):
+        """(offsets (H, 4, N), entries filled per reactor (N,)): entry k holds the offsets the reactor's k-th step
+        after :meth:`set_disturbances` integrated under (entry 0: those made at set time)."""
+        N, H = self.n_reactors, max(self._disturb_history, 0)
+        off = np.empty((H, disturb.SLOTS, N), dtype=np.float64)
+        filled = np.empty(N, dtype=np.int32)
+        self._control_call(_native.lib().wt_ensemble_disturb_history, _native.dptr(off) if H else None,
+                           filled.ctypes.data_as(C.POINTER(C.c_int32)))
+        return off, filled
+
+    def clear_disturbances(self) -> None:
+        """Stop the disturbance program: the targeted rows go back to the base."""
+        self._control_call(_native.lib().wt_ensemble_disturb_clear)
+        self._disturb_history = -1
+        self._device_boundary_moved = True
 
     # -- diagnostics (NEXT-4)
     DIAGNOSTIC_FIELDS = ("total_chlorine_mg", "total_H_mol", "total_OH_mol", "charge_balance_mol", "thermal_energy_kJ",

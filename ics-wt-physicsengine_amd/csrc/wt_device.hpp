@@ -41,6 +41,7 @@
 #include "wt_inj.hpp"
 #include "wt_alm.hpp"
 #include "wt_act.hpp"
+#include "wt_dst.hpp"
 
 namespace wt {
 
@@ -214,6 +215,9 @@ __device__ __forceinline__ double exp10_k(const KP &k, double x)
     return (x < k.t_lo) ? 0.0 : z;
 }
 
+// e^y by exp10_k with literal constants: the disturbance programs' exp (wt_dst.hpp)
+struct ExpK { __device__ __forceinline__ double operator()(double y) const { return exp10_k(kp_of(default_ktab()), y * wtd::LOG10_E); } };
+
 // The Radau constants of the solver sections, fetched the same way (radau.py:11-40 values, see rc::)
 struct alignas(64) RTab {
     double T00, T01, T02, T10, T11, T12, rtol, atol;                 // section Z: Z = T W, norm scales
@@ -308,15 +312,16 @@ struct StepArgs {
     wti::InjArgs inj;    // per-reactor injection programs run at PLC scans (wt_ensemble_inject_*; inj.on == 0: none)
     wta::AlmArgs alm;    // per-reactor alarm and interlock programs run at PLC scans (wt_ensemble_alarm_*; alm.on == 0: none)
     wtv::ActArgs act;    // per-reactor actuator programs run at PLC scans (wt_ensemble_actuator_*; act.on == 0: none)
+    wtd::DstArgs dst;    // per-reactor disturbance programs run after every outer step (wt_ensemble_disturb_*; dst.on == 0: none)
 };
 static_assert(sizeof(StepArgs) <= 4096, "the kernel-argument segment holds at most 4 KiB");
 constexpr int NB = 10;     // rows of a boundary block (WT_NB)
 // kernels that record and reload the schedule inside a work item (n <= 32); the others take one outer step per launch
 __host__ __device__ constexpr bool x_in_item(int LV) { return LV <= 5; }
-// kernels that carry the injection, alarm and actuator sections (wt_inj.hpp, wt_alm.hpp, wt_act.hpp).  The n > 32
-// kernel has no register for them: every variant tried cost it 8 B of scratch and 4 VGPR spills, with or without a
-// program, so it compiles the sections out and wt_ensemble_inject_set, _alarm_set and _actuator_set refuse ensembles
-// of more than 32 zones.
+// kernels that carry the injection, alarm, actuator and disturbance sections (wt_inj.hpp, wt_alm.hpp, wt_act.hpp,
+// wt_dst.hpp).  The n > 32 kernel has no register for them: every variant tried cost it 8 B of scratch and 4 VGPR
+// spills, with or without a program, so it compiles the sections out and wt_ensemble_inject_set, _alarm_set,
+// _actuator_set and _disturb_set refuse ensembles of more than 32 zones.
 __host__ __device__ constexpr bool prog_in_item(int LV) { return LV <= 5; }
 enum { Q_AVAIL = 0, Q_HEAD = 1, Q_TAIL = 2, Q_ERROR = 3, Q_TRACE = 4, Q_DONE = 5, Q_WORDS = 16 };
 
@@ -2361,6 +2366,22 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
         }
 
         WT_STAMP(6);       // post-step (derived, clamps)
+        // ================= the disturbance program (wave-uniform flag): the rows of the next outer step.  Before the
+        // plant-I/O section, whose scan reload then reads these rows from the boundary block while the command path
+        // writes rows 0 / 4 / 6 -- neither overwrites the other's rows.
+        if constexpr (prog_in_item(LV)) {
+          if (WT_RARE(fresh(pa)->dst.on)) {
+            ArgPtr d = fresh(pa);            // ---- section: disturbance program
+            const bool live = present && stepped && !(st & ST_T_RANGE_POST);   // the sensor section's test
+            if (live && L.z == 0) wtd::evaluate(d->dst, r, t_out, d->bc, d->N, ExpK());
+            __syncthreads();                 // the rows are in memory for every lane of the reactor
+            if (live) {
+                RK k1; load_reactor(d->par, d->bc, d->N, r, n_zones, k1); mask_reactor_for_lane(L, k1);
+                park_reactor(ks, k1);
+                f_valid = false;
+            }
+          }
+        }
         // ================= what follows reactor.step() in the reference's loop body (__main__.py:403-423)
         if (sens_on) {
             ArgPtr b = fresh(pa);            // ---- section: sensors and plant I/O

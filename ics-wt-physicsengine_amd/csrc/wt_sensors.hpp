@@ -106,20 +106,23 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
     out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }
 
+// Box-Muller on two 24-bit uniforms of one Philox output, u1 in (0,1]: one standard normal deviate.  Hardware
+// transcendentals: v_log_f32 (log2), v_sqrt_f32, v_cos_f32 (argument in revolutions, so u2 as it is); ~1e-6 absolute
+// on z -- two orders below what the fp32 signal path is held to (tests: 2e-5).  Also the disturbance programs' z
+// (wt_dst.hpp).
+__device__ __forceinline__ float box_muller(const uint32_t x[4])
+{
+    const float u1 = (float)((x[0] >> 8) + 1u) * (1.0f / 16777216.0f);
+    const float u2 = (float)(x[1] >> 8) * (1.0f / 16777216.0f);
+    const float l2 = __builtin_amdgcn_logf(u1);
+    return __builtin_amdgcn_sqrtf(-1.38629436111989061883f * l2) * __builtin_amdgcn_cosf(u2);
+}
+
 struct Rng {
     uint32_t reactor, sensor, draws, k0, k1;
     __device__ __forceinline__ void next(uint32_t x[4]) { philox4x32_10(reactor, sensor, draws, 0u, k0, k1, x); draws++; }
     __device__ __forceinline__ float uniform() { uint32_t x[4]; next(x); return (float)(x[0] >> 8) * (1.0f / 16777216.0f); }
-    __device__ __forceinline__ float normal(float scale)
-    {   // Box-Muller on two 24-bit uniforms, u1 in (0,1]
-        uint32_t x[4]; next(x);
-        const float u1 = (float)((x[0] >> 8) + 1u) * (1.0f / 16777216.0f);
-        const float u2 = (float)(x[1] >> 8) * (1.0f / 16777216.0f);
-        // hardware transcendentals: v_log_f32 (log2), v_sqrt_f32, v_cos_f32 (argument in revolutions, so u2 as it
-        // is); ~1e-6 absolute on z -- two orders below what the fp32 signal path is held to (tests: 2e-5)
-        const float l2 = __builtin_amdgcn_logf(u1);
-        return scale * (__builtin_amdgcn_sqrtf(-1.38629436111989061883f * l2) * __builtin_amdgcn_cosf(u2));
-    }
+    __device__ __forceinline__ float normal(float scale) { uint32_t x[4]; next(x); return scale * box_muller(x); }
 };
 
 // ---------------------------------------------------------------- suite constants (sensors/__init__.py:41-120)

@@ -95,6 +95,8 @@ struct wt_ensemble {
     wti::InjArgs inj = {};
     wta::AlmArgs alm = {};
     wtv::ActArgs act = {};
+    // dst: the per-reactor disturbance program (wt_dst.hpp), evaluated after every outer step
+    wtd::DstArgs dst = {};
     // optional per-launch HIP-event timing (bench.py roofline accounting)
     bool time_launches = false;
     std::vector<hipEvent_t> lt_pool;   // start/stop pairs
@@ -131,7 +133,7 @@ wt::StepArgs make_args(const wt_ensemble *h, double dt, int n_steps, int first_s
     a.trace = h->trace; a.trace_cap = h->trace_cap;
     a.kt = wt::default_ktab(); a.rt = wt::default_rtab();
     a.kt.dense_bias = h->knob_dense ? 1.0 : 0.0;
-    a.sens = h->sens; a.ctl = h->ctl; a.inj = h->inj; a.alm = h->alm; a.act = h->act;
+    a.sens = h->sens; a.ctl = h->ctl; a.inj = h->inj; a.alm = h->alm; a.act = h->act; a.dst = h->dst;
     a.sens.scan_every = scan_every > 0 ? scan_every : 1;
     a.sched = h->call_sched;
     const bool rec = recording_open(h);
@@ -254,6 +256,17 @@ ArrayGroup actuator_arrays(wt_ensemble *h)
                                      {(void **)&h->act.st, sizeof(double) * wtv::ST_DOUBLES * N},
                                      {(void **)&h->act.q, sizeof(double) * wtv::Q_DOUBLES * N},
                                      {(void **)&h->act.tp, sizeof(double) * N}}};
+}
+
+// the history array only for hist_cap > 0
+ArrayGroup disturb_arrays(wt_ensemble *h, int hist_cap)
+{
+    const size_t N = (size_t)h->N;
+    return {"disturb", &h->dst.on, {{(void **)&h->dst.par, sizeof(double) * wtd::PAR_DOUBLES * N},
+                                    {(void **)&h->dst.st, sizeof(double) * wtd::ST_DOUBLES * N},
+                                    {(void **)&h->dst.base, sizeof(double) * WT_NB * N},
+                                    {(void **)&h->dst.tp, sizeof(double) * N},
+                                    {(void **)&h->dst.hist, sizeof(double) * wtd::SLOTS * (size_t)hist_cap * N}}};
 }
 
 // the body of control_disable, inject_clear, alarm_clear and actuator_clear
@@ -410,6 +423,15 @@ int download_records(wt_ensemble *h, const std::vector<Records> &parts)
     return WT_OK;
 }
 
+// The disturbance program's host operations (wtd::host_op_kernel) on the handle's stream, not synchronised.
+int disturb_op(wt_ensemble *h, int op)
+{
+    const wtd::HostOpArgs a{h->dst, h->bc, h->time, h->N, op};
+    hipLaunchKernelGGL(wtd::host_op_kernel<wt::ExpK>, dim3((unsigned)((h->N + 255) / 256)), dim3(256), 0, h->stream, a);
+    HIP_TRY(hipGetLastError());
+    return WT_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -507,7 +529,8 @@ int wt_ensemble_destroy(wt_ensemble *h)
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     for (const ArrayGroup &g : {core_arrays(h), sensor_arrays(h, h->sens.hist_cap), plant_io_arrays(h), record_arrays(h, 0),
-                                control_arrays(h), inject_arrays(h), alarm_arrays(h), actuator_arrays(h)})
+                                control_arrays(h), inject_arrays(h), alarm_arrays(h), actuator_arrays(h),
+                                disturb_arrays(h, h->dst.hist_cap)})
         release(g);
     free_and_null(h->trace); free_and_null(h->wave_diag); free_and_null(h->snap_dev); free_and_null(h->sched);
     free_and_null(h->diag_out);
@@ -561,6 +584,10 @@ int wt_ensemble_set_boundary(wt_ensemble *h, const double *bc)
     if (!h || !bc) return fail(WT_E_ARG, "NULL argument");
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipMemcpyAsync(h->bc, bc, sizeof(double) * WT_NB * h->N, hipMemcpyHostToDevice, h->stream));
+    if (h->dst.on) {   // a disturbance program: the new block is its base, the targeted rows are recomposed (no draw)
+        HIP_TRY(hipMemcpyAsync(h->dst.base, h->bc, sizeof(double) * WT_NB * h->N, hipMemcpyDeviceToDevice, h->stream));
+        if (int rc = disturb_op(h, wtd::OP_COMPOSE)) return rc;
+    }
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->have_bc = true;
     return WT_OK;
@@ -709,6 +736,7 @@ int wt_ensemble_step_scheduled(wt_ensemble *h, double dt, int n_steps, int fused
     if (!h) return fail(WT_E_ARG, "NULL handle");
     if (!bc_schedule) return fail(WT_E_ARG, "bc_schedule is NULL");
     if (h->sens.plc_on) return fail(WT_E_STATE, "a boundary schedule cannot be combined with plant I/O (the command path owns the boundary)");
+    if (h->dst.on) return fail(WT_E_STATE, "a boundary schedule cannot be combined with a disturbance program (its STEP and RAMP slots script events)");
     if (!h->have_state) return fail(WT_E_STATE, "set_state must precede step");
     if (!(dt > 0)) return fail(WT_E_ARG, "`max_step` must be positive."); // scipy validate_max_step (reactor.py:480)
     if (n_steps < 0) return fail(WT_E_ARG, "n_steps must be >= 0");
@@ -1366,6 +1394,129 @@ int wt_ensemble_actuator_clear(wt_ensemble *h)
     return stop_program(h, actuator_arrays(h));
 }
 
+} // extern "C"
+
+namespace {
+
+static_assert(WT_DST_SLOTS == wtd::SLOTS && WT_ND == wtd::ND && WT_NDS == wtd::NDS && WT_NB == wtd::NB,
+              "disturbance blocks of the C ABI");
+static_assert(WT_DST_OU == wtd::K_OU && WT_DST_OU + 1 == wtd::N_KINDS && WT_D_C == wtd::D_C && WT_DS_N_DRAW == wtd::DS_N_DRAW,
+              "disturbance kinds and rows of the C ABI");
+
+// Host-side checks of a [WT_DST_SLOTS][WT_ND][N] program; nullptr when it is valid.
+const char *disturb_params_error(const double *p, int64_t N)
+{
+    const auto at = [&](int k, int v, int64_t r) { return p[((int64_t)k * wtd::ND + v) * N + r]; };
+    for (int k = 0; k < wtd::SLOTS; ++k)
+        for (int64_t r = 0; r < N; ++r)
+            for (int v = 0; v < wtd::ND; ++v) {
+                const double x = at(k, v, r);
+                if (!std::isfinite(x) && !(v == wtd::D_T_END && x == INFINITY))
+                    return "disturbance parameters must be finite (t_end may be +inf)";
+            }
+    for (int k = 0; k < wtd::SLOTS; ++k)
+        for (int64_t r = 0; r < N; ++r) {
+            double c[wtd::ND];
+            for (int v = 0; v < wtd::ND; ++v) c[v] = at(k, v, r);
+            const double kind = c[wtd::D_KIND], row = c[wtd::D_ROW];
+            if (kind != std::floor(kind) || kind < 0 || kind >= wtd::N_KINDS)
+                return "kind must be an integer in 0..4 (off, step, ramp, sine, ou)";
+            if (row != std::floor(row) || row < 0 || row >= wtd::NB)
+                return "row must be a boundary row: 1, 2, 3, 5, 7, 8 or 9";
+            if (!wtd::row_allowed((int)row))
+                return "rows 0, 4 and 6 (inlet, acid and chlorine flow) belong to the command path or the master";
+            if (!(c[wtd::D_T_END] >= c[wtd::D_T_START])) return "t_end must be >= t_start";
+            if (kind == wtd::K_SINE && !(c[wtd::D_B] > 0)) return "a sine needs b (the period) > 0";
+            if (kind == wtd::K_OU && !(c[wtd::D_A] >= 0)) return "an OU slot needs a (sigma) >= 0";
+            if (kind == wtd::K_OU && !(c[wtd::D_B] > 0)) return "an OU slot needs b (tau) > 0";
+        }
+    return nullptr;
+}
+
+const char *k_no_disturb = "no disturbance program is set (wt_ensemble_disturb_set)";
+
+// the body of disturb_clear and of a set over a program: the targeted rows back to the base, the arrays released
+int disturb_stop(wt_ensemble *h)
+{
+    HIP_TRY(hipSetDevice(h->device));
+    if (h->dst.on) {
+        if (int rc = disturb_op(h, wtd::OP_RESTORE)) return rc;
+        if (int rc = sync_checked(h)) return rc;
+    }
+    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still use the records
+    release(disturb_arrays(h, h->dst.hist_cap));
+    h->dst.hist_cap = 0;
+    return WT_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int wt_ensemble_disturb_set(wt_ensemble *h, const double *params, uint64_t seed, int64_t reactor_base, int history_capacity)
+{
+    if (!h || !params) return fail(WT_E_ARG, "NULL argument");
+    if (!h->have_state || !h->have_bc) return fail(WT_E_STATE, "set_state and set_boundary must precede disturb_set");
+    if (!wt::prog_in_item(levels_for(h->n))) return fail(WT_E_STATE, "disturbance programs run in the kernels for up to 32 zones");
+    if (history_capacity < 0) return fail(WT_E_ARG, "history_capacity must be >= 0 (0 = no history)");
+    int64_t hist = 0;
+    if (__builtin_mul_overflow((int64_t)history_capacity * wtd::SLOTS, h->N, &hist) ||
+        __builtin_mul_overflow(hist, (int64_t)sizeof(double), &hist))
+        return fail(WT_E_ARG, "history size overflows int64");
+    if (int rc = wt_program_check(WT_PROG_DISTURB, params, h->N)) return rc;
+    if (int rc = disturb_stop(h)) return rc;
+    const int64_t N = h->N;
+    std::vector<double> par((size_t)N * wtd::PAR_DOUBLES);
+    blocks_to_records(params, wtd::SLOTS, wtd::ND, N, par.data(), wtd::PAR_DOUBLES);
+    if (int rc = allocate(disturb_arrays(h, history_capacity))) return rc;
+    h->dst.hist_cap = history_capacity;
+    h->dst.seed_lo = (uint32_t)(seed & 0xffffffffu); h->dst.seed_hi = (uint32_t)(seed >> 32); h->dst.reactor_base = reactor_base;
+    HIP_TRY(hipMemcpyAsync((double *)h->dst.par, par.data(), sizeof(double) * par.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemsetAsync(h->dst.st, 0, sizeof(double) * wtd::ST_DOUBLES * (size_t)N, h->stream));
+    if (history_capacity > 0) HIP_TRY(hipMemsetAsync(h->dst.hist, 0, (size_t)hist, h->stream));   // entries not filled: 0
+    HIP_TRY(hipMemcpyAsync(h->dst.base, h->bc, sizeof(double) * WT_NB * (size_t)N, hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->dst.tp, h->time, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice, h->stream));
+    h->dst.on = 1;
+    if (int rc = disturb_op(h, wtd::OP_SET)) { release(disturb_arrays(h, h->dst.hist_cap)); return rc; }
+    if (int rc = sync_checked(h)) return rc;   // the host vector is freed on return
+    return WT_OK;
+}
+
+int wt_ensemble_disturb_get(wt_ensemble *h, double *slot_state, double *base, double *t_prev)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    if (!h->dst.on) return fail(WT_E_STATE, k_no_disturb);
+    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = download_records(h, {{slot_state, h->dst.st, wtd::ST_DOUBLES, wtd::SLOTS, wtd::NDS}, {t_prev, h->dst.tp, 1, 1, 1}}))
+        return rc;
+    return download(h, {{base, h->dst.base, sizeof(double) * WT_NB * (size_t)h->N}});
+}
+
+int wt_ensemble_disturb_history(wt_ensemble *h, double *offsets, int32_t *n_filled)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    if (!h->dst.on) return fail(WT_E_STATE, k_no_disturb);
+    HIP_TRY(hipSetDevice(h->device));
+    const int64_t N = h->N;
+    const int cap = h->dst.hist_cap;
+    std::vector<double> st((size_t)N * wtd::NDS);   // slot 0's state: n_eval
+    if (int rc = download_records(h, {{st.data(), h->dst.st, wtd::ST_DOUBLES, 1, wtd::NDS},
+                                      {cap > 0 ? offsets : nullptr, h->dst.hist, wtd::SLOTS * cap, cap, wtd::SLOTS}}))
+        return rc;
+    if (n_filled)
+        for (int64_t r = 0; r < N; ++r) {
+            const double e = st[(size_t)(wtd::DS_N_EVAL * N + r)];
+            n_filled[r] = (int32_t)(e < cap ? e : cap);
+        }
+    return WT_OK;
+}
+
+int wt_ensemble_disturb_clear(wt_ensemble *h)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    return disturb_stop(h);
+}
+
 int wt_program_check(int program, const double *params, int64_t n_reactors)
 {
     if (!params) return fail(WT_E_ARG, "params is NULL");
@@ -1376,6 +1527,7 @@ int wt_program_check(int program, const double *params, int64_t n_reactors)
     case WT_PROG_INJECT: msg = inject_params_error(params, n_reactors); break;
     case WT_PROG_ALARM: msg = alarm_params_error(params, n_reactors); break;
     case WT_PROG_ACTUATOR: msg = actuator_params_error(params, n_reactors); break;
+    case WT_PROG_DISTURB: msg = disturb_params_error(params, n_reactors); break;
     default: return fail(WT_E_ARG, "unknown program");
     }
     return msg ? fail(WT_E_ARG, msg) : WT_OK;

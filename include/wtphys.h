@@ -99,7 +99,8 @@ int wt_ensemble_set_boundary(wt_ensemble *h, const double *bc);
 
 /* IntegratedCSTR.step(dt, boundary) n_steps times (reactor.py:450-509); asynchronous, ordered after and
  * before other work on the handle's stream.  The boundary is held constant unless plant I/O is on (then the
- * command path rewrites it at every PLC scan).  fused == 0 makes every outer step a PLC scan, as the reference's
+ * command path rewrites rows 0 / 4 / 6 at every PLC scan) or a disturbance program is set (then it rewrites its
+ * targeted rows after every outer step, wt_ensemble_disturb_set).  fused == 0 makes every outer step a PLC scan, as the reference's
  * loop does; otherwise a scan happens every chunk_steps outer steps and at the end of the call.  Results do not
  * depend on the schedule (tests assert bitwise equality).  A time series of boundaries goes through
  * wt_ensemble_step_scheduled. */
@@ -109,7 +110,8 @@ int wt_ensemble_step(wt_ensemble *h, double dt, int n_steps, int fused);
  * and results as n_steps calls of wt_ensemble_set_boundary(row k) + wt_ensemble_step(h, dt, 1, fused), bit for bit.
  * The rows are uploaded into a device buffer of the handle (grown on demand) and the call synchronises the stream before
  * its launches.  Afterwards the handle's boundary block is row n_steps-1 (wt_ensemble_get_boundary, wt_ensemble_rhs and
- * later wt_ensemble_step calls see it).  WT_E_STATE while plant I/O is on (the command path owns the boundary). */
+ * later wt_ensemble_step calls see it).  WT_E_STATE while plant I/O is on (the command path owns the boundary) or a
+ * disturbance program is set (its STEP and RAMP slots script events). */
 int wt_ensemble_step_scheduled(wt_ensemble *h, double dt, int n_steps, int fused, const double *bc_schedule);
 /* Trajectory recording.  From this call on, the state after every `every`-th outer step of later step calls (scheduled
  * or not) goes into record i = (steps since this call) / every - 1, for i < capacity; after that, recording stops.
@@ -453,13 +455,57 @@ int wt_ensemble_actuator_get(wt_ensemble *h, double *state, double *queue, doubl
 /* program off, buffers freed (no effect while none is set) */
 int wt_ensemble_actuator_clear(wt_ensemble *h);
 
-/* ---- the parameter checks of the four scan programs, without a handle or a device ----
+/* ---- per-reactor disturbance programs: inlet and ambient disturbances generated on the device ----
+ * Up to WT_DST_SLOTS slots per reactor move the boundary rows the command path does not own.  Parameters
+ * [WT_DST_SLOTS][WT_ND][N]: kind (an integer 0..4: WT_DST_OFF, STEP, RAMP, SINE, OU), row (1 inlet_pH, 2
+ * inlet_chlorine, 3 inlet_temperature, 5 acid_concentration, 7 chlorine_concentration, 8 ambient_temperature, 9
+ * heat_loss_coefficient; rows 0, 4 and 6 belong to the command path or the master), t_start, t_end >= t_start (may be
+ * +inf), a, b, c; all finite except t_end; SINE needs b > 0, OU a >= 0 and b > 0; otherwise WT_E_ARG.
+ * Slot state [WT_DST_SLOTS][WT_NDS][N]: value (the offset d), x (the OU state), n_eval, n_draw.
+ * The program keeps a base block [WT_NB][N]: the boundary in force at set time.  Every row that at least one non-OFF
+ * slot targets is  clamp(base + d_s0 + d_s1 + ...)  over those slots in ascending order, in fp64 without fused
+ * multiply-adds; the clamp is [0, 14] for pH, [0, 100] for inlet temperature, none for ambient temperature and >= 0 for
+ * rows 2, 5, 7 and 9.  Rows no slot targets are never written.
+ * After every outer step of a reactor that stepped (the sensor suite's test: no ReactorState failure after the step),
+ * with t = its ReactorState.time after the step:  h = t - t_prev; t_prev = t;  then for every slot, "in window" being
+ * t_start <= t < t_end:
+ *   STEP  d = in window ? a : 0
+ *   RAMP  d = t < t_start ? 0 : a + b * (fmin(t, t_end) - t_start)     (holds its end value after the window)
+ *   SINE  d = in window ? a * sin(2 pi (t - t_start) / b + c) : 0
+ *   OU    (a = stationary sigma, b = tau in seconds) in window: if h > 0 { phi = exp(-h/b);
+ *         x = x * phi + (a * sqrt(-expm1(-2h/b))) * z;  n_draw += 1 }  d = x;  outside: d = 0, x kept
+ *   n_eval += 1;  history entry n_eval - 1 = d (while below the capacity)
+ * z is one standard normal deviate of the sensor suite's Philox4x32-10 + Box-Muller (fp32) on counter
+ * (reactor_base + r, slot, n_draw, 1) and key = seed: word 3 = 1 keeps it off every sensor stream.  The composed rows
+ * are the boundary of the reactor's next outer step (zero-order hold); with plant I/O that step integrates under both
+ * this step's commands and these rows.  Reactors that did not step get no evaluation and keep their rows.
+ * set replaces any program (the old one's rows go back to its base first, as clear does): x = 0, counts 0, t_prev =
+ * ReactorState.time, then one evaluation at that time on the device (history entry 0: what the first step after set
+ * integrates under).  Needs set_state and set_boundary and n <= 32 zones (WT_E_STATE); history_capacity >= 0
+ * (WT_E_ARG).  With a program set, wt_ensemble_set_boundary replaces the base and recomposes the targeted rows from
+ * the current offsets (no draw), and wt_ensemble_step_scheduled gives WT_E_STATE.  All calls synchronise. */
+#define WT_DST_SLOTS 4
+enum { WT_DST_OFF = 0, WT_DST_STEP = 1, WT_DST_RAMP = 2, WT_DST_SINE = 3, WT_DST_OU = 4 };
+enum { WT_D_KIND = 0, WT_D_ROW = 1, WT_D_T_START = 2, WT_D_T_END = 3, WT_D_A = 4, WT_D_B = 5, WT_D_C = 6, WT_ND = 7 };
+enum { WT_DS_VALUE = 0, WT_DS_X = 1, WT_DS_N_EVAL = 2, WT_DS_N_DRAW = 3, WT_NDS = 4 };
+int wt_ensemble_disturb_set(wt_ensemble *h, const double *params /* [WT_DST_SLOTS][WT_ND][N] */, uint64_t seed,
+                            int64_t reactor_base, int history_capacity);
+/* host [WT_DST_SLOTS][WT_NDS][N] slot state, [WT_NB][N] base and [N] t_prev (any may be NULL); WT_E_STATE while no
+ * program is set */
+int wt_ensemble_disturb_get(wt_ensemble *h, double *slot_state, double *base, double *t_prev);
+/* host [history_capacity][WT_DST_SLOTS][N] offsets (entry j: after evaluation j, entry 0 the one at set time; 0 while
+ * not filled) and [N] entries filled (either may be NULL); WT_E_STATE while no program is set */
+int wt_ensemble_disturb_history(wt_ensemble *h, double *offsets, int32_t *n_filled);
+/* program off, buffers freed, targeted rows back to the base (no effect while none is set) */
+int wt_ensemble_disturb_clear(wt_ensemble *h);
+
+/* ---- the parameter checks of the four scan programs and the disturbance program, without a handle or a device ----
  * params: host, the block the program's set or enable call takes, for n_reactors reactors (WT_PROG_CONTROL:
  * wt_ensemble_control_enable / retune, WT_PROG_INJECT: wt_ensemble_inject_set, WT_PROG_ALARM: wt_ensemble_alarm_set,
- * WT_PROG_ACTUATOR: wt_ensemble_actuator_set).  WT_OK when the block passes that call's checks; otherwise WT_E_ARG
+ * WT_PROG_ACTUATOR: wt_ensemble_actuator_set, WT_PROG_DISTURB: wt_ensemble_disturb_set).  WT_OK when the block passes that call's checks; otherwise WT_E_ARG
  * and wt_last_error() is the message the call gives for it.  A NULL params, n_reactors < 1 or an unknown program
  * also give WT_E_ARG.  Makes no HIP call. */
-enum { WT_PROG_CONTROL = 0, WT_PROG_INJECT = 1, WT_PROG_ALARM = 2, WT_PROG_ACTUATOR = 3 };
+enum { WT_PROG_CONTROL = 0, WT_PROG_INJECT = 1, WT_PROG_ALARM = 2, WT_PROG_ACTUATOR = 3, WT_PROG_DISTURB = 4 };
 int wt_program_check(int program, const double *params, int64_t n_reactors);
 
 /* ---- reactor diagnostics (SURVEY.md section 8(f) NEXT-4): reductions over the zones of every reactor ----

@@ -1,0 +1,176 @@
+"""CPU checks of the per-reactor disturbance programs: the restatement (disturb_ref.py) against worked answers, the block
+of ``disturbance_block`` with the library's checks, and the new C ABI symbols."""
+import importlib
+import math
+import os
+import re
+
+import numpy as np
+import pytest
+
+from disturb_ref import DS_N_DRAW, DS_N_EVAL, DS_VALUE, DS_X, DisturbRef, compose_rows
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+INF = np.inf
+
+
+@pytest.fixture(scope="module")
+def dst(native):
+    return importlib.import_module("ics-wt-physicsengine_amd.core.disturb")
+
+
+def _bc(n=1):
+    bc = np.zeros((10, n))
+    bc[0], bc[1], bc[2], bc[3], bc[5], bc[7], bc[8], bc[9] = 5.0, 7.2, 1.0, 18.0, 0.1, 0.12, 20.0, 5.0
+    return bc
+
+
+def _block(*slots, n=1):
+    """(4, 7, n) from (kind, row, t_start, t_end, a, b, c) tuples; the rest off."""
+    p = np.zeros((4, 7, n))
+    p[:, 1] = 1.0
+    p[:, 3] = INF
+    for k, s in enumerate(slots):
+        p[k] = np.asarray(s, dtype=np.float64)[:, None]
+    return p
+
+
+def _offsets(p, times, t0=0.0):
+    ref = DisturbRef(p, _bc(), [t0])
+    out = [ref.st[:, DS_VALUE, 0].copy()]
+    for t in times:
+        ref.evaluate([t])
+        out.append(ref.st[:, DS_VALUE, 0].copy())
+    return np.array(out), ref
+
+
+def test_step_ramp_sine_at_chosen_times_and_window_edges():
+    p = _block((1, 3, 100.0, 200.0, 2.5, 0, 0),          # STEP on inlet temperature
+               (2, 7, 100.0, 200.0, 0.01, 1e-4, 0),       # RAMP on chlorine stock
+               (3, 8, 100.0, 400.0, 3.0, 400.0, 0.5))     # SINE on ambient
+    off, ref = _offsets(p, [99.0, 100.0, 150.0, 199.0, 200.0, 300.0])
+    # times:           0     99    100   150   199   200   300
+    assert list(off[:, 0]) == [0, 0, 2.5, 2.5, 2.5, 0, 0]
+    assert list(off[:, 1]) == [0, 0, 0.01, 0.01 + 1e-4 * 50.0, 0.01 + 1e-4 * 99.0, 0.01 + 1e-4 * 100.0, 0.01 + 1e-4 * 100.0]
+    want = [0, 0] + [3.0 * math.sin(2 * math.pi * (t - 100.0) / 400.0 + 0.5) for t in (100.0, 150.0, 199.0, 200.0, 300.0)]
+    np.testing.assert_allclose(off[:, 2], want, rtol=0, atol=1e-15)
+    assert ref.bc[3, 0] == 18.0 and ref.bc[7, 0] == 0.12 + (0.01 + 1e-4 * 100.0) and ref.bc[8, 0] == 20.0 + off[-1, 2]
+    assert list(ref.st[:, DS_N_EVAL, 0]) == [7.0] * 4
+
+
+def test_ou_with_zero_sigma_stays_zero_and_draws():
+    p = _block((4, 2, 0.0, INF, 0.0, 600.0, 0))
+    off, ref = _offsets(p, [10.0 * k for k in range(1, 21)])
+    assert np.all(off[:, 0] == 0.0)
+    assert ref.st[0, DS_N_DRAW, 0] == 20.0 and ref.st[0, DS_X, 0] == 0.0
+
+
+def test_ou_one_step_variance():
+    sigma, tau, h, N = 0.3, 600.0, 10.0, 4000
+    p = _block((4, 1, 0.0, INF, sigma, tau, 0), n=N)
+    ref = DisturbRef(p, _bc(N), np.zeros(N), seed=7)
+    ref.evaluate(np.full(N, h))
+    x = ref.st[0, DS_X]
+    phi = math.exp(-h / tau)
+    var = sigma ** 2 * (1 - phi ** 2)
+    assert abs(x.mean()) < 4 * math.sqrt(var / N)
+    assert abs(x.var() / var - 1) < 4 * math.sqrt(2.0 / N)
+
+
+def test_clamps():
+    p = _block((1, 1, 0, INF, 20.0, 0, 0), (1, 3, 0, INF, -50.0, 0, 0), (1, 2, 0, INF, -5.0, 0, 0), (1, 8, 0, INF, -40.0, 0, 0))
+    ref = DisturbRef(p, _bc(), [0.0])
+    assert ref.bc[1, 0] == 14.0 and ref.bc[3, 0] == 0.0 and ref.bc[2, 0] == 0.0 and ref.bc[8, 0] == -20.0
+    p = _block((1, 3, 0, INF, 90.0, 0, 0), (1, 1, 0, INF, -9.0, 0, 0))
+    ref = DisturbRef(p, _bc(), [0.0])
+    assert ref.bc[3, 0] == 100.0 and ref.bc[1, 0] == 0.0
+
+
+def test_slots_on_one_row_add_in_slot_order():
+    p = _block((1, 2, 0, INF, 0.1, 0, 0), (1, 5, 0, INF, 0.2, 0, 0), (1, 2, 0, INF, 0.3, 0, 0))
+    ref = DisturbRef(p, _bc(), [0.0])
+    assert ref.bc[2, 0] == (1.0 + 0.1) + 0.3 and ref.bc[5, 0] == 0.1 + 0.2
+    assert np.array_equal(compose_rows(p, _bc(), ref.st[:, DS_VALUE]), ref.bc)
+
+
+def test_no_draw_when_time_does_not_advance():
+    p = _block((4, 2, 0.0, INF, 0.5, 100.0, 0))
+    ref = DisturbRef(p, _bc(), [0.0])
+    ref.evaluate([10.0])
+    x = ref.st[0, DS_X, 0]
+    ref.evaluate([10.0])          # h = 0
+    ref.evaluate([5.0])           # h < 0 (set_state moved time back)
+    assert ref.st[0, DS_N_DRAW, 0] == 1.0 and ref.st[0, DS_X, 0] == x and ref.st[0, DS_VALUE, 0] == x
+    ref.evaluate([50.0])
+    assert ref.st[0, DS_N_DRAW, 0] == 2.0
+
+
+def test_history_entry_zero_is_the_set_time_evaluation():
+    p = _block((1, 3, 5.0, INF, 1.0, 0, 0), n=2)
+    ref = DisturbRef(p, _bc(2), [0.0, 10.0], history=3)
+    ref.evaluate([10.0, 20.0])
+    ref.evaluate([20.0, 30.0], live=[True, False])
+    ref.evaluate([30.0, 30.0], live=[True, False])
+    assert list(ref.hist[:, 0, 0]) == [0.0, 1.0, 1.0] and list(ref.hist[:2, 0, 1]) == [1.0, 1.0]
+    assert list(ref.n_filled()) == [3, 2]
+
+
+def test_block_packing(dst, wt):
+    N = 3
+    blk = dst.disturbance_block(N, wt.Disturbance.ou("inlet_pH", 0.1, 600.0),
+                                wt.Disturbance.sine(3, [1.0, 2.0, 3.0], 86400.0, phase=0.5),
+                                wt.Disturbance.step("ambient_temperature", -5.0, 100.0, 200.0))
+    assert blk.shape == (4, 7, N) and blk.flags["C_CONTIGUOUS"]
+    assert np.all(blk[0, :, 0] == [4, 1, 0, INF, 0.1, 600.0, 0])
+    assert np.all(blk[1, 4] == [1.0, 2.0, 3.0]) and np.all(blk[1, :4, 2] == [3, 3, 0, INF]) and blk[1, 6, 0] == 0.5
+    assert np.all(blk[2, :5, 1] == [1, 8, 100.0, 200.0, -5.0])
+    assert np.all(blk[3, 0] == 0)
+    ramp = dst.disturbance_block(1, wt.Disturbance.ramp("chlorine_concentration", 1e-6, 10.0, 20.0, offset=0.5))
+    assert np.all(ramp[0, :, 0] == [2, 7, 10.0, 20.0, 0.5, 1e-6, 0])
+    with pytest.raises(ValueError, match="at most 4"):
+        dst.disturbance_block(1, *[wt.Disturbance.step(1, 0.1)] * 5)
+    with pytest.raises(ValueError, match="unknown boundary row"):
+        dst.disturbance_block(1, wt.Disturbance.step("pH", 0.1))
+
+
+@pytest.mark.parametrize("slot, msg", [
+    ((1, 0, 0, INF, 1, 0, 0), "rows 0, 4 and 6"),
+    ((1, 4, 0, INF, 1, 0, 0), "rows 0, 4 and 6"),
+    ((1, 6, 0, INF, 1, 0, 0), "rows 0, 4 and 6"),
+    ((1, 10, 0, INF, 1, 0, 0), "row must be a boundary row"),
+    ((5, 1, 0, INF, 1, 0, 0), "kind must be an integer in 0..4"),
+    ((1.5, 1, 0, INF, 1, 0, 0), "kind must be an integer in 0..4"),
+    ((1, 1, 0, INF, np.nan, 0, 0), "must be finite"),
+    ((1, 1, -INF, INF, 1, 0, 0), "must be finite"),
+    ((1, 1, 0, np.nan, 1, 0, 0), "must be finite"),
+    ((1, 1, 10, 5, 1, 0, 0), "t_end must be >= t_start"),
+    ((3, 1, 0, INF, 1, 0, 0), "sine needs b"),
+    ((3, 1, 0, INF, 1, -5, 0), "sine needs b"),
+    ((4, 1, 0, INF, 1, 0, 0), "OU slot needs b"),
+    ((4, 1, 0, INF, -1, 10, 0), "OU slot needs a"),
+])
+def test_program_check_refusals(native, slot, msg):
+    blk = np.ascontiguousarray(_block((1, 2, 0, INF, 0.1, 0, 0), slot, n=2))
+    assert native.lib().wt_program_check(native.WT_PROG_DISTURB, native.dptr(blk), 2) == native.WT_E_ARG
+    assert msg in native.lib().wt_last_error().decode()
+
+
+def test_program_check_accepts_valid_blocks(native):
+    blk = np.ascontiguousarray(_block((4, 1, 0, INF, 0.0, 1.0, 0), (3, 9, 5, 5, 1, 2, 3), (2, 5, 0, 10, -1, 1, 0), (0, 1, 0, INF, 0, 0, 0)))
+    assert native.lib().wt_program_check(native.WT_PROG_DISTURB, native.dptr(blk), 1) == native.WT_OK
+
+
+def test_symbols_declared_and_exported(native, wt):
+    hdr = open(os.path.join(ROOT, "include", "wtphys.h")).read()
+    L = native.lib()
+    for name in ("wt_ensemble_disturb_set", "wt_ensemble_disturb_get", "wt_ensemble_disturb_history", "wt_ensemble_disturb_clear"):
+        assert re.search(r"\bint " + name + r"\(", hdr), name
+        assert hasattr(L, name)
+    for name in ("WT_DST_SLOTS", "WT_DST_OFF", "WT_DST_STEP", "WT_DST_RAMP", "WT_DST_SINE", "WT_DST_OU", "WT_ND", "WT_NDS",
+                 "WT_PROG_DISTURB = 4"):
+        assert name in hdr, name
+    assert native.WT_PROG_DISTURB == 4
+    for name in ("Disturbance", "DisturbanceState", "disturbance_block"):
+        assert hasattr(wt, name) and name in wt.__all__, name
+    for name in ("set_disturbances", "disturbance_state", "disturbance_history", "clear_disturbances"):
+        assert hasattr(wt.ReactorEnsemble, name), name
