@@ -1,10 +1,17 @@
-"""Helpers of the GPU tests of the per-reactor scan programs (test_gpu_control.py, test_gpu_inject.py,
-test_gpu_alarm.py): a plant with sensors and plant I/O, a pair of PI loops, the plant's observable state, the message
-of a refused parameter block."""
+"""Helpers of the GPU tests and probes of the per-reactor scan programs (test_gpu_control.py, test_gpu_inject.py,
+test_gpu_alarm.py, test_gpu_actuator.py, tools/*_probe.py): a plant with sensors and plant I/O, a pair of PI loops, the
+plant's observable state, the message of a refused parameter block, and the host side of the PLC scan -- the calls of
+one scan interval, the device's scan order and the holding words of a host master."""
+import importlib
+
 import numpy as np
+
+from inject_ref import CMD_ACID, I_TARGET
 
 DT, K = 10.0, 300          # 3000 s: the pH sensors' 1800 s warm-up ends inside the run
 MASTER = (0.5, 0.25, 6.0)  # acid, chlorine, inlet flow commands the master writes
+
+_E = importlib.import_module("ics-wt-physicsengine_amd").ReactorEnsemble
 
 
 def plant(wt, cols, bc, n, seed=11, history=0):
@@ -44,3 +51,98 @@ def refused_as_checked(nat, program, block) -> bool:
 def assert_all_equal(ref, got, what):
     for i, (a, b) in enumerate(zip(ref, got)):
         assert np.array_equal(a, b, equal_nan=True), (what, i)
+
+
+def words(cmd):
+    """(3, N) (acid, chlorine, inlet) commands -> (N, 6) holding words."""
+    return np.concatenate([_E.encode_float32(cmd[i]) for i in range(3)], axis=1)
+
+
+def commands(holding):
+    """(N, 6) holding words -> (3, N) float32 (acid, chlorine, inlet) commands."""
+    return _E.decode_float32(np.asarray(holding).reshape(-1, 3, 2)).T.copy()
+
+
+def calls(n_steps, interval, lt=0.0, dt=DT):
+    """``n_steps`` outer steps as calls of one scan interval: yields each call's length and the loop time after it.  The
+    loop time advances by repeated addition of ``dt`` from ``lt``, as the device's does (c * dt rounds otherwise)."""
+    done = 0
+    while done < n_steps:
+        c = min(interval, n_steps - done)
+        for _ in range(c):
+            lt = lt + dt
+        yield c, lt
+        done += c
+
+
+class HostScan:
+    """The host side of the PLC scan of N reactors: the restatements of the programs that are on (``ctl`` ControlRef,
+    ``inj`` InjectRef, ``alm`` AlarmRef, ``act`` ActuatorRef; None for a program that is off) and the loop time ``lt``
+    (N,) of the next scan.
+
+    ``emulated``: the device runs plant I/O without these programs, and the host master emulates the command path in
+    the words it writes before a call (``holding``).  Otherwise the device runs them, and ``scan`` follows its command
+    path from the decoded commands it is given."""
+
+    def __init__(self, N, ctl=None, inj=None, alm=None, act=None, emulated=False, dt=DT):
+        self.ctl, self.inj, self.alm, self.act = ctl, inj, alm, act
+        self.emulated, self.dt = emulated, dt
+        self.lt = np.zeros(N)
+        # an injection program without command slots leaves the commands as they are: skip its copy of them
+        self.tampers = inj is not None and bool((inj.p[:, I_TARGET] >= CMD_ACID).any())
+
+    def calls(self, n_steps, interval):
+        """The lengths of ``calls``; inside the loop ``lt`` is the loop time the scan closing the call stores."""
+        for c, self.lt in calls(n_steps, interval, self.lt, self.dt):
+            yield c
+
+    def _command_path(self, cmd, stepped=None):
+        """The decoded commands (3, N) after the injection's command slots and then the alarm trips in force."""
+        if self.tampers:
+            cmd = self.inj.commands(cmd, self.lt, stepped)
+        if self.alm is not None:
+            cmd = self.alm.override(cmd, stepped)
+        return cmd
+
+    def holding(self, cmd=None):
+        """The words a host master writes before a call: those of ``cmd`` (3, N), by default the PI's holding words.
+        When ``emulated``, the injection's command slots and the alarm trips in force act on them here, at the loop time
+        of the scan that closes the call; the alarm program then counts its overrides here and not in ``scan``."""
+        if self.emulated and (self.tampers or self.alm is not None):
+            return words(self._command_path(commands(self.ctl.holding) if cmd is None else cmd))
+        return self.ctl.holding if cmd is None else words(cmd)
+
+    def scan(self, v, f, cmd=None, stepped=None):
+        """One PLC scan at loop time ``lt`` in the device's order (the plant-I/O section of ``run_item`` in
+        csrc/wt_device.hpp): the injection's sensor slots tamper the readings ``v`` / ``f`` (7, N), which the input
+        image then packs; the decoded commands ``cmd`` (3, N) go through the injection's command slots, the alarm trips
+        and the actuators (no command path with ``cmd`` None); PI runs on the tampered readings; the alarms evaluate,
+        FIELD slots on the raw readings and IMAGE slots on the tampered ones.  ``stepped`` (N,): reactors that took
+        the step (default: all).  Returns the tampered readings."""
+        assert cmd is None or not self.emulated, "an emulated command path runs in holding()"
+        t = self.lt
+        vt, ft = (v, f) if self.inj is None else self.inj.sensors(v, f, t, stepped)
+        if cmd is not None:
+            cmd = self._command_path(cmd, stepped)
+            if self.act is not None:
+                self.act.scan(cmd, t, stepped)
+        if self.ctl is not None:
+            self.ctl.scan(vt, ft, t, stepped)
+        if self.alm is not None:
+            self.alm.scan(v, f, t, stepped, image=(vt, ft))
+        return vt, ft
+
+    def run(self, ens, n_steps, interval, fused=True, image=False):
+        """The host loop a fused call replaces: calls of one scan interval, each after the master's write of
+        ``holding()`` and closed by ``scan`` of the readings (and, unless ``emulated``, of the commands written).
+        ``image``: read the input image after every call, as a host master would.  Returns the last scan's
+        tampered readings."""
+        for c in self.calls(n_steps, interval):
+            w = self.holding()
+            ens.write_holding(w)
+            ens.step(self.dt, n_steps=c, fused=fused, download=False)
+            v, _, f = ens.sensor_readings()
+            if image:
+                ens.input_image()
+            out = self.scan(v, f, None if self.emulated else commands(w))
+        return out

@@ -1,9 +1,6 @@
-"""CPU checks of the per-reactor alarm and interlock programs: the restatement (alarm_ref.py) against worked answers,
-the block of ``alarm_block`` with its validation, and the new C ABI symbols."""
-import ctypes
+"""CPU checks of the per-reactor alarm and interlock programs: the restatement (alarm_ref.py) against worked answers
+and the block of ``alarm_block`` with its validation (the C ABI symbols: test_host_api.py)."""
 import importlib
-import os
-import re
 
 import numpy as np
 import pytest
@@ -11,7 +8,6 @@ import pytest
 from alarm_ref import (AR_FIRST_OUT, AR_N_OVR_ACID, AR_N_OVR_CHLORINE, AR_OVR_ACID, AR_OVR_CHLORINE, AS_ACTIVE, AS_COND,
                        AS_N_ACT, AS_N_BAD, AS_PENDING, AS_T_FIRST, AS_T_LAST, AS_TIME_ACTIVE, AlarmRef)
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CL = 3     # chlorine_outlet
 
 
@@ -208,28 +204,3 @@ def test_alarm_state_block_round_trip(alm):
     assert np.array_equal(st.t_prev, reactors[0]) and np.array_equal(st.n_ovr_chlorine, reactors[5])
     s2, r2 = st.block()
     assert np.array_equal(s2, slots) and np.array_equal(r2, reactors)
-
-
-def test_alarm_symbols_declared_and_exported():
-    header = open(os.path.join(ROOT, "include", "wtphys.h")).read()
-    names = ("wt_ensemble_alarm_set", "wt_ensemble_alarm_get", "wt_ensemble_alarm_reset", "wt_ensemble_alarm_words",
-             "wt_ensemble_alarm_device", "wt_ensemble_alarm_clear", "wt_program_check")
-    for name in names:
-        assert re.search(r"\bint " + name + r"\(", header), name
-    assert re.search(r"#define WT_ALM_SLOTS 4\b", header)
-    assert re.search(r"WT_PROG_ALARM = 2\b", header)
-    assert re.search(r"WT_NA = 10\b", header) and re.search(r"WT_NAS = 8\b", header) and re.search(r"WT_NAR = 6\b", header)
-    assert re.search(r"WT_A_TRIP_VALUE = 9\b", header) and re.search(r"WT_AS_N_BAD = 7\b", header)
-    assert re.search(r"WT_AR_N_OVR_CHLORINE = 5\b", header) and re.search(r"WT_ALM_TRIP_CHLORINE = 2\b", header)
-    assert re.search(r"#define WT_ABI_VERSION 1\b", header)
-    native = importlib.import_module("ics-wt-physicsengine_amd.core._native")
-    native.build()
-    assert "wt_alm.hpp" in native.BUILD_SOURCES
-    lib = ctypes.CDLL(native.LIB_PATH)
-    for name in names:
-        assert hasattr(lib, name), name
-    wt = importlib.import_module("ics-wt-physicsengine_amd")
-    for name in ("Alarm", "AlarmState", "alarm_block"):
-        assert name in wt.__all__ and hasattr(wt, name)
-    for name in ("set_alarms", "alarm_state", "alarm_words", "reset_alarms", "clear_alarms"):
-        assert callable(getattr(wt.ReactorEnsemble, name))

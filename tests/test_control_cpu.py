@@ -1,17 +1,14 @@
-"""CPU checks of the per-reactor PI programs: the restatement (control_ref.py) against worked answers, the parameter
-block of ``control_block`` with its validation, and the new C ABI symbols."""
-import ctypes
+"""CPU checks of the per-reactor PI programs: the restatement (control_ref.py) against worked answers and the
+parameter block of ``control_block`` with its validation (the C ABI symbols: test_host_api.py)."""
 import importlib
-import os
-import re
 
 import numpy as np
 import pytest
 
 from control_ref import (CS_DOSE, CS_IAE, CS_INTEGRAL, CS_ISE, CS_N_EXEC, CS_N_HELD, CS_N_SAT, CS_OUTPUT, ControlRef,
                          float32_words)
+from program_helpers import calls
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAN = np.float32("nan")
 
 
@@ -94,12 +91,10 @@ def test_variable_h_across_chunked_scans(ctl):
     # scans after 7, 7 and 6 outer steps of 10 s (a 20-step call with chunk 7): h = 70, 70, 60
     ref = ControlRef(_one(ctl, ctl.PILoop("chlorine_outlet", 2.0, kp=0.0, ki=0.01, bias=0.0, out_max=10.0)), [0.0])
     lt, integral = 0.0, 0.0
-    for c in (7, 7, 6):
-        h0 = lt
-        for _ in range(c):
-            lt = lt + 10.0
-        ref.scan(*_readings(1.0), [lt])
-        integral = integral + (0.01 * 1.0) * (lt - h0)
+    for _, t in calls(20, 7, dt=10.0):
+        ref.scan(*_readings(1.0), [t])
+        integral = integral + (0.01 * 1.0) * (t - lt)
+        lt = t
         assert ref.st[0, CS_INTEGRAL, 0] == integral
     assert ref.st[0, CS_ISE, 0] == 70.0 + 70.0 + 60.0 and ref.t_prev[0] == lt
     # a reactor that did not step keeps its t_prev and state
@@ -158,25 +153,3 @@ def test_control_block_shape_errors(ctl):
         ctl.control_block(3, chlorine=ctl.PILoop("chlorine_outlet", 1.0, kp=np.ones(4)))
     with pytest.raises(TypeError):
         ctl.control_block(3, chlorine={"sensor": 3})
-
-
-def test_control_symbols_declared_and_exported():
-    header = open(os.path.join(ROOT, "include", "wtphys.h")).read()
-    for name in ("wt_ensemble_control_enable", "wt_ensemble_control_retune", "wt_ensemble_control_get",
-                 "wt_ensemble_control_disable", "wt_program_check"):
-        assert re.search(r"\bint " + name + r"\(", header), name
-    assert re.search(r"#define WT_CTL_LOOPS 2\b", header)
-    assert re.search(r"WT_PROG_CONTROL = 0\b", header)
-    assert re.search(r"WT_NC = 9\b", header) and re.search(r"WT_NCS = 8\b", header)
-    assert re.search(r"#define WT_ABI_VERSION 1\b", header)
-    native = importlib.import_module("ics-wt-physicsengine_amd.core._native")
-    native.build()
-    lib = ctypes.CDLL(native.LIB_PATH)
-    for name in ("wt_ensemble_control_enable", "wt_ensemble_control_retune", "wt_ensemble_control_get",
-                 "wt_ensemble_control_disable", "wt_program_check"):
-        assert hasattr(lib, name), name
-    wt = importlib.import_module("ics-wt-physicsengine_amd")
-    for name in ("PILoop", "ControlState", "LoopState", "control_block"):
-        assert name in wt.__all__ and hasattr(wt, name)
-    for name in ("enable_control", "retune_control", "disable_control", "control_state"):
-        assert callable(getattr(wt.ReactorEnsemble, name))

@@ -1,16 +1,13 @@
-"""CPU checks of the per-reactor disturbance programs: the restatement (disturb_ref.py) against worked answers, the block
-of ``disturbance_block`` with the library's checks, and the new C ABI symbols."""
+"""CPU checks of the per-reactor disturbance programs: the restatement (disturb_ref.py) against worked answers and
+the block of ``disturbance_block`` with the library's checks (the C ABI symbols: test_host_api.py)."""
 import importlib
 import math
-import os
-import re
 
 import numpy as np
 import pytest
 
 from disturb_ref import DS_N_DRAW, DS_N_EVAL, DS_VALUE, DS_X, DisturbRef, compose_rows
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INF = np.inf
 
 
@@ -158,19 +155,3 @@ def test_program_check_refusals(native, slot, msg):
 def test_program_check_accepts_valid_blocks(native):
     blk = np.ascontiguousarray(_block((4, 1, 0, INF, 0.0, 1.0, 0), (3, 9, 5, 5, 1, 2, 3), (2, 5, 0, 10, -1, 1, 0), (0, 1, 0, INF, 0, 0, 0)))
     assert native.lib().wt_program_check(native.WT_PROG_DISTURB, native.dptr(blk), 1) == native.WT_OK
-
-
-def test_symbols_declared_and_exported(native, wt):
-    hdr = open(os.path.join(ROOT, "include", "wtphys.h")).read()
-    L = native.lib()
-    for name in ("wt_ensemble_disturb_set", "wt_ensemble_disturb_get", "wt_ensemble_disturb_history", "wt_ensemble_disturb_clear"):
-        assert re.search(r"\bint " + name + r"\(", hdr), name
-        assert hasattr(L, name)
-    for name in ("WT_DST_SLOTS", "WT_DST_OFF", "WT_DST_STEP", "WT_DST_RAMP", "WT_DST_SINE", "WT_DST_OU", "WT_ND", "WT_NDS",
-                 "WT_PROG_DISTURB = 4"):
-        assert name in hdr, name
-    assert native.WT_PROG_DISTURB == 4
-    for name in ("Disturbance", "DisturbanceState", "disturbance_block"):
-        assert hasattr(wt, name) and name in wt.__all__, name
-    for name in ("set_disturbances", "disturbance_state", "disturbance_history", "clear_disturbances"):
-        assert hasattr(wt.ReactorEnsemble, name), name

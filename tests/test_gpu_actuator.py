@@ -9,20 +9,10 @@ from alarm_ref import AlarmRef
 from conftest import golden_json
 from control_ref import ControlRef
 from inject_ref import InjectRef
-from program_helpers import DT, K, MASTER, assert_all_equal, pi_loops, plant, plant_state, refused_as_checked
+from program_helpers import (DT, K, MASTER, HostScan, assert_all_equal, calls, pi_loops, plant, plant_state,
+                             refused_as_checked, words)
 
 pytestmark = pytest.mark.gpu
-
-
-def _encode(wt, cmd):
-    """(3, N) (acid, chlorine, inlet) commands -> (N, 6) holding words."""
-    return np.concatenate([wt.ReactorEnsemble.encode_float32(cmd[i]) for i in range(3)], axis=1)
-
-
-def _decode(holding):
-    """(N, 6) holding words -> (3, N) float32 commands (acid, chlorine, inlet)."""
-    w = np.asarray(holding).astype(np.uint32)
-    return ((w[:, 0::2] << 16) | w[:, 1::2]).view(np.float32).T.copy()
 
 
 def _acts(ens):
@@ -85,9 +75,7 @@ def test_inert_and_cleared_programs_are_bit_invisible(gpu, wt, native):
             st = ens.actuator_state()
             assert not st.n_exec.any() and not st.delivered.any() and not st.travel.any()
             assert np.array_equal(st.position, bc[[4, 6, 0]]) and np.array_equal(st.queue[:, 5], bc[[4, 6, 0]])
-            lt = 0.0
-            for _ in range(K):
-                lt += DT
+            _, lt = next(calls(K, K))                        # the loop time after one call of K steps
             assert np.all(st.t_prev == lt)
         ens.close()
     for g, prog in zip(got[1:], ("none", "disabled", "cleared")):
@@ -119,32 +107,19 @@ def test_pass_through_elements_give_the_bits_of_no_program(gpu, wt, n, N):
         assert_all_equal(out[0], out[1], (n, interval))
 
 
-def _scripted_loop(wt, ens, ref, interval, n_steps, rng, inj=None, alm=None):
+def _scripted_loop(ens, hs, interval, n_steps, rng):
     """Calls of one scan interval with scripted holding words; after each, the device's actuator state, queues, t_prev
     and rows equal the restatement's (fed with the words after the injection tamper and the alarm trips)."""
-    N = ens.n_reactors
-    lt = np.zeros(N)
-    done = calls = 0
-    while done < n_steps:
-        c = min(interval, n_steps - done)
-        words = _words(rng, N)
-        ens.write_holding(_encode(wt, words))
+    n_calls = 0
+    for c in hs.calls(n_steps, interval):
+        cmd = _words(rng, ens.n_reactors)
+        ens.write_holding(words(cmd))
         ens.step(DT, n_steps=c, download=False)
-        for _ in range(c):
-            lt = lt + DT
-        u = words
-        if inj is not None:
-            u = inj.commands(u, lt)
-        if alm is not None:
-            u = alm.override(u)
-        ref.scan(u, lt)
-        if alm is not None:
-            v, _, f = ens.sensor_readings()
-            alm.scan(v, f, lt)
-        assert_all_equal(_ref_acts(ref), _acts(ens), (interval, done))
-        done += c
-        calls += 1
-    return calls
+        v, _, f = ens.sensor_readings()
+        hs.scan(v, f, cmd)
+        assert_all_equal(_ref_acts(hs.act), _acts(ens), (interval, n_calls))
+        n_calls += 1
+    return n_calls
 
 
 @pytest.mark.parametrize("n", [8, 20])
@@ -158,7 +133,7 @@ def test_device_follows_the_restatement_under_scripted_words(gpu, wt, n):
         ens.set_schedule(0, interval)
         ens.set_actuators(*prog)
         ref = ActuatorRef(block, ens.boundary(), np.zeros(N))
-        _scripted_loop(wt, ens, ref, interval, steps, np.random.default_rng(interval))
+        _scripted_loop(ens, HostScan(N, act=ref), interval, steps, np.random.default_rng(interval))
         assert not ens.state.status.any()
         st = ref.st
         assert (st[:, VS_N_RATE] > 0).mean() > 0.05 and (st[:, VS_N_FAULT] > 0).mean() > 0.2, interval
@@ -183,9 +158,10 @@ def test_tampered_and_tripped_commands_go_through_the_element(gpu, wt):
         ens.set_actuators(*prog)
         ref = ActuatorRef(block, ens.boundary(), np.zeros(N))
         inj, alm = InjectRef(wt.injection_block(N, *injections)), AlarmRef(wt.alarm_block(N, trip), np.zeros(N))
-        calls = _scripted_loop(wt, ens, ref, interval, steps, np.random.default_rng(10 + interval), inj, alm)
+        n_calls = _scripted_loop(ens, HostScan(N, inj=inj, alm=alm, act=ref), interval, steps,
+                                 np.random.default_rng(10 + interval))
         st = ens.alarm_state()
-        assert np.all(st.n_ovr_chlorine == calls - 1)                    # the trip acted at every scan after the first
+        assert np.all(st.n_ovr_chlorine == n_calls - 1)                  # the trip acted at every scan after the first
         ens.close()
 
 
@@ -208,22 +184,19 @@ def test_end_to_end_equals_a_master_writing_the_applied_flows(gpu, wt):
                                 t_repair=t_fault + np.floor(rng.uniform(0, 0.4 * t_end, N)),
                                 fail_value=rng.integers(8 if ch == "inlet" else 0, lim * 64 + 1, N) / 64.0))
     block = wt.actuator_block(N, *prog)
-    calls = -(-steps // interval)
-    words = []
-    for _ in range(calls):
+    scripted = []
+    for _ in range(-(-steps // interval)):
         w = np.stack([rng.integers(-8, 2 * 64 + 24, N), rng.integers(-8, 64 + 16, N),
                       rng.integers(-32, 22 * 64, N)]).astype(np.float64) / 64.0
         small = rng.random(N) < 0.25
         w[2, small] = rng.integers(0, 7, small.sum()) / 64.0
         w = w.astype(np.float32)
         w[rng.random((3, N)) < 0.03] = np.nan
-        words.append(w)
+        scripted.append(w)
     ref = ActuatorRef(block, bc, np.zeros(N))
-    lt, applied = np.zeros(N), []
-    for i in range(calls):
-        for _ in range(min(interval, steps - i * interval)):
-            lt = lt + DT
-        ref.scan(words[i], lt)
+    applied = []
+    for (_, lt), w in zip(calls(steps, interval, np.zeros(N)), scripted):
+        ref.scan(w, lt)
         applied.append(ref.st[:, 1].astype(np.float32))
         assert np.array_equal(ref.st[:, 1], applied[-1].astype(np.float64))   # the grid keeps them float32-exact
     assert (ref.st[:, VS_N_FAULT] > 0).mean() > 0.3
@@ -233,32 +206,15 @@ def test_end_to_end_equals_a_master_writing_the_applied_flows(gpu, wt):
         ens.set_schedule(0, interval)
         if act:
             ens.set_actuators(*prog)
-        for i in range(calls):
-            ens.write_holding(_encode(wt, words[i] if act else applied[i]))
-            ens.step(DT, n_steps=min(interval, steps - i * interval), download=False)
+        for (c, _), w in zip(calls(steps, interval), scripted if act else applied):
+            ens.write_holding(words(w))
+            ens.step(DT, n_steps=c, download=False)
         out.append(plant_state(ens) + ens.input_image())
         if act:
             assert_all_equal(_ref_acts(ref), _acts(ens), "end to end")
         ens.close()
     assert not out[0][5].any()
     assert_all_equal(out[0], out[1], "end to end")
-
-
-def _pi_host_loop(wt, ens, ctl, act, interval, n_steps):
-    """PI on the host, actuators on the device: calls of one scan interval, the PI's words written before each."""
-    lt = np.zeros(ens.n_reactors)
-    done = 0
-    while done < n_steps:
-        c = min(interval, n_steps - done)
-        words = _decode(ctl.holding)
-        ens.write_holding(ctl.holding)
-        ens.step(DT, n_steps=c, download=False)
-        for _ in range(c):
-            lt = lt + DT
-        act.scan(words, lt)
-        v, _, f = ens.sensor_readings()
-        ctl.scan(v, f, lt)
-        done += c
 
 
 def test_fused_calls_equal_the_host_loop(gpu, wt, monkeypatch):
@@ -273,9 +229,9 @@ def test_fused_calls_equal_the_host_loop(gpu, wt, monkeypatch):
         ens.set_schedule(0, interval)
         ens.write_commands(*MASTER)
         ens.set_actuators(*prog)
-        ctl = ControlRef(cblock, np.zeros(N), holding=_encode(wt, np.array([[MASTER[0]], [MASTER[1]], [MASTER[2]]]) * np.ones(N)))
+        ctl = ControlRef(cblock, np.zeros(N), holding=words(np.array(MASTER)[:, None] * np.ones(N)))
         act = ActuatorRef(block, ens.boundary(), np.zeros(N))
-        _pi_host_loop(wt, ens, ctl, act, interval, K)
+        HostScan(N, ctl=ctl, act=act).run(ens, K, interval)     # PI on the host, actuators on the device
         out = plant_state(ens) + ens.input_image() + (ctl.st,) + _acts(ens)
         assert not out[5].any()
         assert_all_equal(_ref_acts(act), _acts(ens), ("host loop", interval))
@@ -295,9 +251,8 @@ def test_fused_calls_equal_the_host_loop(gpu, wt, monkeypatch):
         ens.write_commands(*MASTER)
         ens.set_actuators(*prog)
         ens.enable_control(chlorine, acid)
-        calls = 5 if v.get("adaptive") else 1
-        for _ in range(calls):
-            ens.step(DT, n_steps=K // calls, fused=v.get("fused", True), download=False)
+        for c, _ in calls(K, K // 5 if v.get("adaptive") else K):
+            ens.step(DT, n_steps=c, fused=v.get("fused", True), download=False)
         if v.get("adaptive"):
             assert ens.schedule()["redeals"] >= 1 and not np.array_equal(ens.placement()[1], np.arange(N))
         got = plant_state(ens) + ens.input_image() + (ens.control_state().block(),) + _acts(ens)

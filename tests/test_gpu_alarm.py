@@ -8,7 +8,7 @@ from alarm_ref import AlarmRef
 from conftest import golden_json
 from control_ref import ControlRef
 from inject_ref import InjectRef
-from program_helpers import DT, K, MASTER, assert_all_equal, pi_loops, plant, plant_state, refused_as_checked
+from program_helpers import DT, K, MASTER, HostScan, assert_all_equal, pi_loops, plant, plant_state, refused_as_checked
 
 pytestmark = pytest.mark.gpu
 
@@ -37,33 +37,6 @@ def _alarms(ens):
 
 def _ref_alarms(ref):
     return ref.st, ref.rst, ref.words
-
-
-def _decode(holding):
-    """(N, 6) holding words -> (3, N) float32 commands (acid, chlorine, inlet)."""
-    w = np.asarray(holding).astype(np.uint32)
-    return ((w[:, 0::2] << 16) | w[:, 1::2]).view(np.float32).T.copy()
-
-
-def _encode(wt, cmd):
-    return np.concatenate([wt.ReactorEnsemble.encode_float32(cmd[i]) for i in range(3)], axis=1)
-
-
-def _host_loop(wt, ens, ctl, alm, interval, n_steps):
-    """PI and alarms without the feature: calls of one scan interval; before each, the PI words with the tripped
-    channels replaced by float32(trip value); after each, the readings and the PI and alarm restatements."""
-    lt = np.zeros(ens.n_reactors)
-    done = 0
-    while done < n_steps:
-        c = min(interval, n_steps - done)
-        ens.write_holding(_encode(wt, alm.override(_decode(ctl.holding))))
-        ens.step(DT, n_steps=c, download=False)
-        for _ in range(c):
-            lt = lt + DT
-        v, _, f = ens.sensor_readings()
-        ctl.scan(v, f, lt)
-        alm.scan(v, f, lt)
-        done += c
 
 
 def test_inert_program_is_bit_invisible(gpu, wt):
@@ -105,7 +78,7 @@ def test_fused_alarms_equal_the_host_loop(gpu, wt, n, N):
         ens = plant(wt, cols, bc, n)
         ens.set_schedule(0, interval)
         ctl, alm = ControlRef(cblock, np.zeros(N)), AlarmRef(block, np.zeros(N))
-        _host_loop(wt, ens, ctl, alm, interval, K)
+        HostScan(N, ctl=ctl, alm=alm, emulated=True).run(ens, K, interval)     # PI and alarms without the feature
         ref = plant_state(ens) + ens.input_image()
         assert not ref[5].any()
         assert np.mean(alm.st[:, 3].sum(axis=0) > 0) > 0.2, (n, interval)     # alarms activate in many reactors
@@ -143,17 +116,15 @@ def test_field_and_image_under_spoofing(gpu, wt):
     vh, _, fh, filled = ens.sensor_history()
     assert np.all(filled == K)
     inj, ref = InjectRef(wt.injection_block(N, spoof)), AlarmRef(wt.alarm_block(N, *prog), np.zeros(N))
-    lt = np.zeros(N)
-    for k in range(K):
-        lt = lt + DT
-        if (k + 1) % c == 0 or k + 1 == K:
-            ref.override(np.zeros((3, N), dtype=np.float32))
-            image = inj.sensors(vh[k], fh[k], lt)
-            assert not image[0][3].any()
-            ref.scan(vh[k], fh[k], lt, image=image)
+    hs = HostScan(N, inj=inj, alm=ref)
+    k = -1
+    for steps in hs.calls(K, c):
+        k += steps
+        vt, _ = hs.scan(vh[k], fh[k], np.zeros((3, N), dtype=np.float32))
+        assert not vt[3].any()
     assert_all_equal(_ref_alarms(ref), _alarms(ens), "spoofed")
     # from the scan after activation on, the plant doses the trip value
-    on = st.t_first[1] < lt[0]
+    on = st.t_first[1] < hs.lt[0]
     assert on.mean() > 0.9
     assert np.all(ens.boundary()[6][on] == float(np.float32(trip)))
     ens.close()
@@ -203,13 +174,13 @@ def test_latch_and_masked_reset_across_calls(gpu, wt):
     ens.step(DT, n_steps=K, download=False)
     vh, _, fh, _ = ens.sensor_history()
     ref = AlarmRef(wt.alarm_block(N, *prog), np.zeros(N))
-    lt = np.zeros(N)
-    for k in range(2 * K):
-        lt = lt + DT
-        if (k + 1) % c == 0 or k + 1 == K or k + 1 == 2 * K:
-            ref.override(np.zeros((3, N), dtype=np.float32))
-            ref.scan(vh[k], fh[k], lt)
-        if k + 1 == K:
+    hs = HostScan(N, alm=ref)
+    k = -1
+    for call in range(2):
+        for steps in hs.calls(K, c):
+            k += steps
+            hs.scan(vh[k], fh[k], np.zeros((3, N), dtype=np.float32))
+        if call == 0:
             ref.reset(mask)
             assert_all_equal(_ref_alarms(ref), ref_mid, "after reset")
     assert_all_equal(_ref_alarms(ref), _alarms(ens), "second call")

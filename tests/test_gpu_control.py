@@ -4,29 +4,11 @@ import numpy as np
 import pytest
 
 from control_ref import CS_N_EXEC, CS_N_HELD, ControlRef
-from program_helpers import DT, K, assert_all_equal, pi_loops, plant, plant_state, refused_as_checked
+from program_helpers import DT, K, HostScan, assert_all_equal, pi_loops, plant, plant_state, refused_as_checked
 
 pytestmark = pytest.mark.gpu
 
 PH_OUT, CL_OUT = 1, 3      # sensor indices
-
-
-def _host_loop(ens, ref, interval, n_steps, dt=DT):
-    """The closed loop a controlled call replaces: calls of one scan interval, each followed by the readings, the
-    restatement and a holding-register write.  Returns the loop time after the last call."""
-    lt = ref.t_prev.copy()
-    done = 0
-    ens.write_holding(ref.holding)
-    while done < n_steps:
-        c = min(interval, n_steps - done)
-        ens.step(dt, n_steps=c, download=False)
-        for _ in range(c):
-            lt = lt + dt
-        v, _, f = ens.sensor_readings()
-        ref.scan(v, f, lt)
-        ens.write_holding(ref.holding)
-        done += c
-    return lt
 
 
 @pytest.mark.parametrize("n, N", [(4, 2000), (8, 2000), (20, 1000), (40, 200)])
@@ -39,7 +21,7 @@ def test_fused_controlled_call_equals_the_host_loop(gpu, wt, monkeypatch, n, N):
         ens = plant(wt, cols, bc, n)
         ens.set_schedule(0, interval)
         ref = ControlRef(block, np.zeros(N))
-        _host_loop(ens, ref, interval, K)
+        HostScan(N, ctl=ref, emulated=True).run(ens, K, interval)
         out = plant_state(ens) + ens.input_image()
         assert not out[5].any()
         # both loops act (a sensor that fails open or short reads NaN from then on: its loop holds for good)
@@ -74,13 +56,11 @@ def test_anti_windup_and_retune(gpu, wt):
     chlorine = wt.PILoop("chlorine_outlet", setpoint=50.0, kp=0.5, ki=1e-3, bias=0.2)
     ens.enable_control(chlorine)
     ref = ControlRef(wt.control_block(N, chlorine), np.zeros(N))
-    lt = np.zeros(N)
-    for call in range(12):
-        ens.step(DT, n_steps=c, download=False)
-        for _ in range(c):
-            lt = lt + DT
+    hs = HostScan(N, ctl=ref)
+    for call, steps in enumerate(hs.calls(12 * c, c)):
+        ens.step(DT, n_steps=steps, download=False)
         v, _, f = ens.sensor_readings()
-        ref.scan(v, f, lt)
+        hs.scan(v, f)
         st = ens.control_state()
         assert np.array_equal(st.block(), ref.st), call
         ran = st.chlorine.n_exec > 0                            # (the DPD reading warms up for 60 s: the first scan holds)
@@ -93,12 +73,10 @@ def test_anti_windup_and_retune(gpu, wt):
     ens.retune_control(chlorine=retuned)
     ref.retune(wt.control_block(N, retuned))
     left = np.zeros(N, dtype=bool)
-    for call in range(6):
-        ens.step(DT, n_steps=c, download=False)
-        for _ in range(c):
-            lt = lt + DT
+    for call, steps in enumerate(hs.calls(6 * c, c)):
+        ens.step(DT, n_steps=steps, download=False)
         v, _, f = ens.sensor_readings()
-        ref.scan(v, f, lt)
+        hs.scan(v, f)
         st = ens.control_state()
         assert np.array_equal(st.block(), ref.st), call
         left |= st.chlorine.output < 1.0
@@ -126,16 +104,16 @@ def test_hold_through_warm_up_and_faults(gpu, wt):
     v, s, f, filled = ens.sensor_history()
     assert np.all(filled == steps)
     ref = ControlRef(block, np.zeros(N))
-    lt = np.zeros(N)
+    hs = HostScan(N, ctl=ref)
     held = np.zeros((2, N))
     fault_held = np.zeros(N)
-    for k in range(steps):
-        lt = lt + DT
-        if (k + 1) % c == 0:                                # 150 and 300 are multiples of c: no extra call-end scan
-            ref.scan(v[k], f[k], lt)
-            for l, sensor in ((0, CL_OUT), (1, PH_OUT)):
-                held[l] += ~np.isfinite(v[k, sensor]) | (f[k, sensor] != 0)
-            fault_held += f[k, CL_OUT] != 0
+    k = -1
+    for steps_c in hs.calls(steps, c):                      # 150 and 300 are multiples of c: the scans of one call
+        k += steps_c
+        hs.scan(v[k], f[k])
+        for l, sensor in ((0, CL_OUT), (1, PH_OUT)):
+            held[l] += ~np.isfinite(v[k, sensor]) | (f[k, sensor] != 0)
+        fault_held += f[k, CL_OUT] != 0
     assert np.array_equal(ens.control_state().block(), ref.st)
     assert np.array_equal(ref.st[:, CS_N_HELD], held)
     assert not np.isfinite(v[:179, PH_OUT]).any()           # warming up until the read at 1800 s
@@ -213,7 +191,9 @@ def test_errors_and_lifetime(gpu, wt):
     twin = plant(wt, cols, bc, n)
     twin.set_schedule(0, 5)
     ref = ControlRef(wt.control_block(N, chlorine, acid), np.zeros(N))
-    _host_loop(twin, ref, 5, 100)
+    hs = HostScan(N, ctl=ref, emulated=True)
+    hs.run(twin, 100, 5)
+    twin.write_holding(hs.holding())
     assert np.array_equal(ref.st, last.block())
     twin.step(DT, n_steps=60, download=False)
     assert_all_equal(plant_state(twin) + twin.input_image(), plant_state(ens) + ens.input_image(), "disabled")

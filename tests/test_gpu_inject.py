@@ -8,7 +8,7 @@ import plc_oracle as PO
 from conftest import golden_json
 from control_ref import ControlRef
 from inject_ref import InjectRef
-from program_helpers import DT, K, MASTER, assert_all_equal, pi_loops, plant, plant_state, refused_as_checked
+from program_helpers import DT, K, MASTER, HostScan, assert_all_equal, pi_loops, plant, plant_state, refused_as_checked
 
 pytestmark = pytest.mark.gpu
 
@@ -41,26 +41,6 @@ def _image_of(values, faults, sim_time):
         img[r, 16:19] = io.ir[100:103]
         img[r, 19] = io.di[0] | (io.di[1] << 1) | (io.di[2] << 2)
     return img, ok
-
-
-def _host_loop(ens, ctl, inj, interval, n_steps):
-    """Sensor spoofing and PI without the feature: calls of one scan interval, each followed by the readings, the
-    injection and PI restatements and a holding-register write.  Returns the last scan's tampered readings and the
-    image's sim_time."""
-    lt = np.zeros(ens.n_reactors)
-    done = 0
-    ens.write_holding(ctl.holding)
-    while done < n_steps:
-        c = min(interval, n_steps - done)
-        ens.step(DT, n_steps=c, download=False)
-        for _ in range(c):
-            lt = lt + DT
-        v, _, f = ens.sensor_readings()
-        vt, ft = inj.sensors(v, f, lt)
-        ctl.scan(vt, ft, lt)
-        ens.write_holding(ctl.holding)
-        done += c
-    return vt, ft, lt - DT
 
 
 def test_inert_program_is_bit_invisible(gpu, wt):
@@ -100,7 +80,8 @@ def test_sensor_spoofing_equals_the_host_loop(gpu, wt, n, N):
         ens = plant(wt, cols, bc, n)
         ens.set_schedule(0, interval)
         ctl, inj = ControlRef(cblock, np.zeros(N)), InjectRef(block)
-        vt, ft, sim_time = _host_loop(ens, ctl, inj, interval, K)
+        hs = HostScan(N, ctl=ctl, inj=inj, emulated=True)
+        vt, ft = hs.run(ens, K, interval)                       # sensor spoofing and PI without the feature
         ref = plant_state(ens)
         assert not ref[5].any()
         assert np.mean(inj.st[:, 0].sum(axis=0) > 0) > 0.9         # nearly every reactor gets spoofed
@@ -114,7 +95,7 @@ def test_sensor_spoofing_equals_the_host_loop(gpu, wt, n, N):
         assert np.array_equal(ens.control_state().block(), ctl.st), (n, interval)
         assert np.array_equal(ens.injection_state().block(), inj.st, equal_nan=True), (n, interval)
         img, ok = ens.input_image()
-        want_img, want_ok = _image_of(vt, ft, sim_time)
+        want_img, want_ok = _image_of(vt, ft, hs.lt - DT)
         assert np.array_equal(ok, want_ok) and np.array_equal(img, want_img), (n, interval)
         ens.close()
 
@@ -142,16 +123,10 @@ def test_command_tampering_equals_the_host_loop(gpu, wt, interval):
     master = np.array(MASTER, dtype=np.float32)[:, None].repeat(N, axis=1)
     ens = plant(wt, cols, bc, n)
     ens.set_schedule(0, interval)
-    lt, done = np.zeros(N), 0
-    while done < K:                       # the host writes what the scan at the end of this call will decode
-        c = min(interval, K - done)
-        t_scan = lt.copy()
-        for _ in range(c):
-            t_scan = t_scan + DT
-        tampered = inj.commands(master, t_scan)
-        ens.write_holding(np.concatenate([ens.encode_float32(tampered[i]) for i in range(3)], axis=1))
+    hs = HostScan(N, inj=inj, emulated=True)
+    for c in hs.calls(K, interval):       # the host writes what the scan at the end of this call will decode
+        ens.write_holding(hs.holding(master))
         ens.step(DT, n_steps=c, download=False)
-        lt, done = t_scan, done + c
     ref = plant_state(ens) + ens.input_image()
     ens.close()
     ens = plant(wt, cols, bc, n)
@@ -188,16 +163,16 @@ def test_sensor_program_with_control_off_changes_no_plant_bit(gpu, wt):
     vh, _, fh, filled = ens.sensor_history()
     assert np.all(filled == K)
     inj = InjectRef(wt.injection_block(N, *prog))
-    lt = np.zeros(N)
-    for k in range(K):
-        lt = lt + DT
-        if (k + 1) % 7 == 0 or k + 1 == K:
-            vt, ft = inj.sensors(vh[k], fh[k], lt)
+    hs = HostScan(N, inj=inj)
+    k = -1
+    for c in hs.calls(K, 7):
+        k += c
+        vt, ft = hs.scan(vh[k], fh[k])
     img, ok = ens.input_image()
-    want_img, want_ok = _image_of(vt, ft, lt - DT)
+    want_img, want_ok = _image_of(vt, ft, hs.lt - DT)
     assert np.array_equal(img, want_img) and np.array_equal(ok, want_ok)
     twin_img, twin_ok = twin.input_image()
-    want_img, want_ok = _image_of(vh[K - 1], fh[K - 1], lt - DT)
+    want_img, want_ok = _image_of(vh[K - 1], fh[K - 1], hs.lt - DT)
     assert np.array_equal(twin_img, want_img) and np.array_equal(twin_ok, want_ok)
     assert (img != twin_img).any()
     assert np.array_equal(ens.injection_state().block(), inj.st, equal_nan=True)

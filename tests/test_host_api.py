@@ -279,6 +279,60 @@ def test_host_modules_are_not_transliterations():
         assert share < 0.25, (name, share)
 
 
+# per scan program: its C entry points (besides wt_program_check), the header constants and values tests rely on, its
+# device source, its package exports and its ReactorEnsemble methods
+PROGRAMS = {
+    "control": (("wt_ensemble_control_enable", "wt_ensemble_control_retune", "wt_ensemble_control_get",
+                 "wt_ensemble_control_disable"),
+                (r"#define WT_CTL_LOOPS 2\b", r"WT_PROG_CONTROL = 0\b", r"WT_NC = 9\b", r"WT_NCS = 8\b"),
+                "wt_ctl.hpp", ("PILoop", "ControlState", "LoopState", "control_block"),
+                ("enable_control", "retune_control", "disable_control", "control_state")),
+    "inject": (("wt_ensemble_inject_set", "wt_ensemble_inject_get", "wt_ensemble_inject_clear"),
+               (r"#define WT_INJ_SLOTS 4\b", r"WT_NI = 6\b", r"WT_NIS = 4\b", r"WT_INJ_CMD_ACID = 7\b",
+                r"WT_INJ_CMD_INLET = 9\b", r"WT_INJ_FAULT = 7\b", r"WT_PROG_INJECT = 1\b"),
+               "wt_inj.hpp", ("Injection", "InjectionState", "injection_block"),
+               ("set_injections", "injection_state", "clear_injections")),
+    "alarm": (("wt_ensemble_alarm_set", "wt_ensemble_alarm_get", "wt_ensemble_alarm_reset", "wt_ensemble_alarm_words",
+               "wt_ensemble_alarm_device", "wt_ensemble_alarm_clear"),
+              (r"#define WT_ALM_SLOTS 4\b", r"WT_PROG_ALARM = 2\b", r"WT_NA = 10\b", r"WT_NAS = 8\b", r"WT_NAR = 6\b",
+               r"WT_A_TRIP_VALUE = 9\b", r"WT_AS_N_BAD = 7\b", r"WT_AR_N_OVR_CHLORINE = 5\b",
+               r"WT_ALM_TRIP_CHLORINE = 2\b"),
+              "wt_alm.hpp", ("Alarm", "AlarmState", "alarm_block"),
+              ("set_alarms", "alarm_state", "alarm_words", "reset_alarms", "clear_alarms")),
+    "actuator": (("wt_ensemble_actuator_set", "wt_ensemble_actuator_get", "wt_ensemble_actuator_clear"),
+                 (r"#define WT_ACT_CHANNELS 3\b", r"#define WT_ACT_MAX_DELAY 8\b", r"WT_NV = 9\b", r"WT_NVS = 9\b",
+                  r"WT_V_FAIL_VALUE = 8\b", r"WT_VS_N_FAULT = 8\b", r"WT_ACT_FAIL_TO = 2\b", r"WT_ACT_INLET = 2\b",
+                  r"WT_PROG_ACTUATOR = 3\b"),
+                 "wt_act.hpp", ("Actuator", "ActuatorState", "actuator_block"),
+                 ("set_actuators", "actuator_state", "clear_actuators")),
+    "disturb": (("wt_ensemble_disturb_set", "wt_ensemble_disturb_get", "wt_ensemble_disturb_history",
+                 "wt_ensemble_disturb_clear"),
+                (r"WT_DST_SLOTS\b", r"WT_DST_OFF\b", r"WT_DST_STEP\b", r"WT_DST_RAMP\b", r"WT_DST_SINE\b",
+                 r"WT_DST_OU\b", r"WT_ND\b", r"WT_NDS\b", r"WT_PROG_DISTURB = 4\b"),
+                "wt_dst.hpp", ("Disturbance", "DisturbanceState", "disturbance_block"),
+                ("set_disturbances", "disturbance_state", "disturbance_history", "clear_disturbances")),
+}
+
+
+@pytest.mark.parametrize("program", list(PROGRAMS))
+def test_program_symbols_declared_and_exported(native, wt, program):
+    entries, constants, source, exports, methods = PROGRAMS[program]
+    entries += ("wt_program_check",)
+    header = open(os.path.join(ROOT, "include", "wtphys.h")).read()
+    for name in entries:
+        assert re.search(r"\bint " + name + r"\(", header), name
+        assert hasattr(native.lib(), name), name
+    for pattern in constants + (r"#define WT_ABI_VERSION 1\b",):
+        assert re.search(pattern, header), pattern
+    code = "WT_PROG_" + program.upper()                      # wt_program_check's code: the package's equals the header's
+    assert getattr(native, code) == int(re.search(code + r" = (\d)\b", header).group(1))
+    assert source in native.BUILD_SOURCES
+    for name in exports:
+        assert name in wt.__all__ and hasattr(wt, name), name
+    for name in methods:
+        assert callable(getattr(wt.ReactorEnsemble, name)), name
+
+
 def test_build_staleness_list_matches_the_includes():
     """``_native.build`` rebuilds when any source is newer than the library: the list must be wtphys.hip plus exactly
     the local headers it (transitively) includes -- no stale names, nothing missing."""

@@ -1,16 +1,11 @@
-"""CPU checks of the per-reactor injection programs: the restatement (inject_ref.py) against worked answers, the block
-of ``injection_block`` with its validation, and the new C ABI symbols."""
-import ctypes
+"""CPU checks of the per-reactor injection programs: the restatement (inject_ref.py) against worked answers and the
+block of ``injection_block`` with its validation (the C ABI symbols: test_host_api.py)."""
 import importlib
-import os
-import re
 
 import numpy as np
 import pytest
 
 from inject_ref import IS_HELD, IS_N_APPLIED, IS_T_FIRST, IS_T_LAST, InjectRef
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
@@ -151,27 +146,3 @@ def test_injection_state_block_round_trip(inj):
     st = inj.InjectionState.from_block(blk)
     assert np.array_equal(st.n_applied, blk[:, 0]) and np.array_equal(st.held, blk[:, 3])
     assert np.array_equal(st.block(), blk)
-
-
-def test_inject_symbols_declared_and_exported():
-    header = open(os.path.join(ROOT, "include", "wtphys.h")).read()
-    names = ("wt_ensemble_inject_set", "wt_ensemble_inject_get", "wt_ensemble_inject_clear", "wt_program_check")
-    for name in names:
-        assert re.search(r"\bint " + name + r"\(", header), name
-    assert re.search(r"#define WT_INJ_SLOTS 4\b", header)
-    assert re.search(r"WT_NI = 6\b", header) and re.search(r"WT_NIS = 4\b", header)
-    assert re.search(r"WT_INJ_CMD_ACID = 7\b", header) and re.search(r"WT_INJ_CMD_INLET = 9\b", header)
-    assert re.search(r"WT_INJ_FAULT = 7\b", header)
-    assert re.search(r"WT_PROG_INJECT = 1\b", header)
-    assert re.search(r"#define WT_ABI_VERSION 1\b", header)
-    native = importlib.import_module("ics-wt-physicsengine_amd.core._native")
-    native.build()
-    assert "wt_inj.hpp" in native.BUILD_SOURCES
-    lib = ctypes.CDLL(native.LIB_PATH)
-    for name in names:
-        assert hasattr(lib, name), name
-    wt = importlib.import_module("ics-wt-physicsengine_amd")
-    for name in ("Injection", "InjectionState", "injection_block"):
-        assert name in wt.__all__ and hasattr(wt, name)
-    for name in ("set_injections", "injection_state", "clear_injections"):
-        assert callable(getattr(wt.ReactorEnsemble, name))

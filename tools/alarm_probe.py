@@ -18,6 +18,7 @@ import numpy as np
 from alarm_ref import AlarmRef
 from control_ref import ControlRef
 from inject_ref import InjectRef
+from program_helpers import HostScan
 wt = importlib.import_module("ics-wt-physicsengine_amd")
 
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 10000
@@ -57,15 +58,6 @@ def outputs(ens):
         (ens.boundary(), ens.control_state().block())
 
 
-def decode(holding):
-    w = np.asarray(holding).astype(np.uint32)
-    return ((w[:, 0::2] << 16) | w[:, 1::2]).view(np.float32).T.copy()
-
-
-def encode(cmd):
-    return np.concatenate([wt.ReactorEnsemble.encode_float32(cmd[i]) for i in range(3)], axis=1)
-
-
 warm = plant()                                   # module load, first launches
 warm.enable_control(chlorine, acid); warm.set_injections(*program); warm.set_alarms(*alarms)
 warm.step(DT, n_steps=2, download=False); warm.alarm_state(); warm.close()
@@ -75,18 +67,9 @@ def host_loop():
     ens = plant()
     ctl, inj, alm = ControlRef(cblock, np.zeros(N)), InjectRef(iblock), AlarmRef(ablock, np.zeros(N))
     ens.enable_control()                         # both loops off: control_state() is kept for the comparison
-    lt = np.zeros(N)
     ens.synchronize()
     t0 = time.perf_counter()
-    for _ in range(K):
-        ens.write_holding(encode(alm.override(decode(ctl.holding))))
-        ens.step(DT, n_steps=1, fused=False, download=False)
-        v, _, f = ens.sensor_readings()
-        ens.input_image()
-        lt = lt + DT
-        vt, ft = inj.sensors(v, f, lt)
-        ctl.scan(vt, ft, lt)
-        alm.scan(v, f, lt, image=(vt, ft))
+    HostScan(N, ctl=ctl, inj=inj, alm=alm, emulated=True, dt=DT).run(ens, K, 1, fused=False, image=True)
     dt = time.perf_counter() - t0
     out = outputs(ens)[:-1]
     ens.close()

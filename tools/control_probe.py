@@ -14,6 +14,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 from control_ref import ControlRef
+from program_helpers import HostScan
 wt = importlib.import_module("ics-wt-physicsengine_amd")
 
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 10000
@@ -50,17 +51,9 @@ warm.enable_control(chlorine, acid); warm.step(DT, n_steps=2, download=False); w
 def host_loop():
     ens = plant()
     ref = ControlRef(block, np.zeros(N))
-    ens.write_holding(ref.holding)
-    lt = np.zeros(N)
     ens.synchronize()
     t0 = time.perf_counter()
-    for _ in range(K):
-        ens.step(DT, n_steps=1, fused=False, download=False)
-        v, _, f = ens.sensor_readings()
-        ens.input_image()
-        lt = lt + DT
-        ref.scan(v, f, lt)
-        ens.write_holding(ref.holding)
+    HostScan(N, ctl=ref, emulated=True, dt=DT).run(ens, K, 1, fused=False, image=True)
     dt = time.perf_counter() - t0
     out = outputs(ens)
     ens.close()

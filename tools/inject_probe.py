@@ -14,6 +14,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 from control_ref import ControlRef
 from inject_ref import InjectRef
+from program_helpers import HostScan
 wt = importlib.import_module("ics-wt-physicsengine_amd")
 
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 10000
@@ -56,18 +57,9 @@ def host_loop():
     ens = plant()
     ctl, inj = ControlRef(cblock, np.zeros(N)), InjectRef(iblock)
     ens.enable_control()                         # both loops off: control_state() is kept for the comparison
-    ens.write_holding(ctl.holding)
-    lt = np.zeros(N)
     ens.synchronize()
     t0 = time.perf_counter()
-    for _ in range(K):
-        ens.step(DT, n_steps=1, fused=False, download=False)
-        v, _, f = ens.sensor_readings()
-        ens.input_image()
-        lt = lt + DT
-        vt, ft = inj.sensors(v, f, lt)
-        ctl.scan(vt, ft, lt)
-        ens.write_holding(ctl.holding)
+    HostScan(N, ctl=ctl, inj=inj, emulated=True, dt=DT).run(ens, K, 1, fused=False, image=True)
     dt = time.perf_counter() - t0
     out = outputs(ens)[:-1]
     ens.close()
