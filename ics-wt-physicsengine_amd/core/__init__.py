@@ -9,6 +9,7 @@ from .inject import Injection, InjectionState, injection_block
 from .alarm import Alarm, AlarmState, alarm_block
 from .actuator import Actuator, ActuatorState, actuator_block
 from .disturb import Disturbance, DisturbanceState, disturbance_block
+from .score import Score, ScoreCurve, ScoreState, score_block
 from .chemistry import AqueousChemistry, BufferSystem, solve_pH
 from .physics import (ArrheniusParameters, FlowParameters, GeometryParameters, SpatialModel, StratificationParameters,
                       TemperatureDependentKinetics, TransportModel, run_all_validations, validate_chemistry,
@@ -21,7 +22,7 @@ __all__ = ["BoundaryConditions", "EnsembleState", "IntegratedCSTR", "PhysicsEngi
            "ReactorEnsemble", "ReactorState", "Trajectory", "boundary_block", "boundary_schedule_block",
            "PILoop", "ControlState", "LoopState", "control_block", "Injection", "InjectionState", "injection_block",
            "Alarm", "AlarmState", "alarm_block", "Actuator", "ActuatorState", "actuator_block",
-           "Disturbance", "DisturbanceState", "disturbance_block",
+           "Disturbance", "DisturbanceState", "disturbance_block", "Score", "ScoreCurve", "ScoreState", "score_block",
            "AqueousChemistry", "BufferSystem", "solve_pH", "make_ensemble", "make_boundary_schedule", "params", "sharding", "gather_state", "shard_bounds",
            # the rest of wt_simulator.core's export list (core/__init__.py:238-263)
            "TemperatureDependentKinetics", "ArrheniusParameters", "TransportModel", "GeometryParameters", "FlowParameters",

@@ -18,7 +18,7 @@ from typing import Dict, Iterable, List, Optional, Sequence, Union
 
 import numpy as np
 
-from . import _native, _program, actuator, alarm, control, disturb, inject, params
+from . import _native, _program, actuator, alarm, control, disturb, inject, params, score
 
 logger = logging.getLogger(__name__)
 
@@ -273,6 +273,7 @@ class ReactorEnsemble:
         self._device_boundary_moved = False     # the command path (plant I/O) rewrites the device's boundary block
         self._plant_io = False
         self._disturb_history = -1              # capacity of the disturbance program's history; -1: no program
+        self._score_curve = None                # (capacity, bins, edges) of the score program's curve; None: no program
         self._control_params: Optional[np.ndarray] = None   # the last block enable_control / retune_control sent
 
     # -- lifetime
@@ -736,6 +737,61 @@ class ReactorEnsemble:
         self._control_call(_native.lib().wt_ensemble_disturb_clear)
         self._disturb_history = -1
         self._device_boundary_moved = True
+
+    # -- score programs after every outer step, on the device (wt_scr.hpp)
+    def set_scores(self, *scores: "score.Score", curve: int = 0, bins: int = 0, fan_range=None) -> None:
+        """Judge the true reactor state after every outer step, inside the step call: one :class:`Score` per slot (up
+        to four) accumulates per reactor the time below and above its band, the deficit and excess areas, the
+        exposure integral and the excursion runs (:meth:`score_state`).  ``curve`` > 0 keeps that many outer steps of
+        the ensemble curve (:meth:`score_curve`): reactors scored, below and above per step and slot.  ``bins`` in
+        1..32 adds a histogram of the scored value per step between ``fan_range`` = (lo, hi), scalars or one pair of
+        values per slot.  Nothing in the plant changes.  Replaces any program; at most 32 zones per reactor."""
+        blk = score.score_block(self.n_reactors, *scores)
+        cap, B = int(curve), int(bins)
+        lo = hi = edges = None
+        if B > 0:
+            if fan_range is None:
+                raise ValueError("bins > 0 needs fan_range=(lo, hi)")
+            try:
+                lo = np.ascontiguousarray(np.broadcast_to(np.asarray(fan_range[0], dtype=np.float64), (score.SLOTS,)))
+                hi = np.ascontiguousarray(np.broadcast_to(np.asarray(fan_range[1], dtype=np.float64), (score.SLOTS,)))
+            except ValueError:
+                raise ValueError("fan_range: expected (lo, hi), each a scalar or one value per slot (4,)") from None
+        self._control_call(_native.lib().wt_ensemble_score_set, _native.dptr(blk), cap, B,
+                           None if lo is None else _native.dptr(lo), None if hi is None else _native.dptr(hi))
+        if B > 0 and cap > 0:
+            edges = score.fan_edges(lo, hi, B)
+        self._score_curve = (cap, B if cap > 0 else 0, edges)
+
+    def score_state(self) -> "score.ScoreState":
+        """The per-reactor accumulators of the score program (one synchronisation)."""
+        st = np.empty((score.SLOTS, score.NSS, self.n_reactors), dtype=np.float64)
+        tp = np.empty(self.n_reactors, dtype=np.float64)
+        self._control_call(_native.lib().wt_ensemble_score_get, _native.dptr(st), _native.dptr(tp))
+        return score.ScoreState.from_block(st, tp)
+
+    def score_curve(self) -> "score.ScoreCurve":
+        """The ensemble curve of the score program: the outer steps taken since :meth:`set_scores` or
+        :meth:`reset_scores`, up to the curve's capacity (one synchronisation)."""
+        cap, B, edges = self._score_curve if self._score_curve is not None else (0, 0, None)
+        counts = np.zeros((cap, score.SLOTS, 3), dtype=np.int32)
+        fan = np.zeros((cap, score.SLOTS, B + 2), dtype=np.int32) if B > 0 else None
+        i32p, k = C.POINTER(C.c_int32), C.c_int(0)
+        self._control_call(_native.lib().wt_ensemble_score_curve, counts.ctypes.data_as(i32p) if cap else None,
+                           fan.ctypes.data_as(i32p) if fan is not None else None, C.byref(k))
+        K = k.value
+        return score.ScoreCurve(counts[:K, :, 0].copy(), counts[:K, :, 1].copy(), counts[:K, :, 2].copy(),
+                                None if fan is None else fan[:K].copy(), edges)
+
+    def reset_scores(self) -> None:
+        """Accumulators and curve back to their values at :meth:`set_scores`, the parameters kept: scoring starts over
+        at the current time (after a warm-up)."""
+        self._control_call(_native.lib().wt_ensemble_score_reset)
+
+    def clear_scores(self) -> None:
+        """Stop the score program and free its buffers."""
+        self._control_call(_native.lib().wt_ensemble_score_clear)
+        self._score_curve = None
 
     # -- diagnostics (NEXT-4)
     DIAGNOSTIC_FIELDS = ("total_chlorine_mg", "total_H_mol", "total_OH_mol", "charge_balance_mol", "thermal_energy_kJ",

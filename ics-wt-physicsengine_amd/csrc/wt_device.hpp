@@ -42,6 +42,7 @@
 #include "wt_alm.hpp"
 #include "wt_act.hpp"
 #include "wt_dst.hpp"
+#include "wt_scr.hpp"
 
 namespace wt {
 
@@ -313,15 +314,16 @@ struct StepArgs {
     wta::AlmArgs alm;    // per-reactor alarm and interlock programs run at PLC scans (wt_ensemble_alarm_*; alm.on == 0: none)
     wtv::ActArgs act;    // per-reactor actuator programs run at PLC scans (wt_ensemble_actuator_*; act.on == 0: none)
     wtd::DstArgs dst;    // per-reactor disturbance programs run after every outer step (wt_ensemble_disturb_*; dst.on == 0: none)
+    wtsc::ScrArgs scr;   // per-reactor score programs run after every outer step (wt_ensemble_score_*; scr.on == 0: none)
 };
 static_assert(sizeof(StepArgs) <= 4096, "the kernel-argument segment holds at most 4 KiB");
 constexpr int NB = 10;     // rows of a boundary block (WT_NB)
 // kernels that record and reload the schedule inside a work item (n <= 32); the others take one outer step per launch
 __host__ __device__ constexpr bool x_in_item(int LV) { return LV <= 5; }
-// kernels that carry the injection, alarm, actuator and disturbance sections (wt_inj.hpp, wt_alm.hpp, wt_act.hpp,
-// wt_dst.hpp).  The n > 32 kernel has no register for them: every variant tried cost it 8 B of scratch and 4 VGPR
-// spills, with or without a program, so it compiles the sections out and wt_ensemble_inject_set, _alarm_set,
-// _actuator_set and _disturb_set refuse ensembles of more than 32 zones.
+// kernels that carry the injection, alarm, actuator, disturbance and score sections (wt_inj.hpp, wt_alm.hpp,
+// wt_act.hpp, wt_dst.hpp, wt_scr.hpp).  The n > 32 kernel has no register for them: every variant tried cost it 8 B of
+// scratch and 4 VGPR spills, with or without a program, so it compiles the sections out and wt_ensemble_inject_set,
+// _alarm_set, _actuator_set, _disturb_set and _score_set refuse ensembles of more than 32 zones.
 __host__ __device__ constexpr bool prog_in_item(int LV) { return LV <= 5; }
 enum { Q_AVAIL = 0, Q_HEAD = 1, Q_TAIL = 2, Q_ERROR = 3, Q_TRACE = 4, Q_DONE = 5, Q_WORDS = 16 };
 
@@ -2366,6 +2368,17 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
         }
 
         WT_STAMP(6);       // post-step (derived, clamps)
+        // ================= the score program (wave-uniform flag): excursion metrics of the true state after the step.
+        // It reads y0 and t_out and writes its own arrays only: no reload of the reactor constants, f(y0) stays valid.
+        if constexpr (prog_in_item(LV)) {
+          if (WT_RARE(fresh(pa)->scr.on)) {
+            ArgPtr s = fresh(pa);            // ---- section: score program
+            static_assert(M::TAIL_DOUBLES >= wtsc::STAGE_DOUBLES, "the score program stages the zones' state in the factor store");
+            const bool live = present && stepped && !(st & ST_T_RANGE_POST);   // the sensor section's test
+            wtsc::evaluate(s->scr, live, L.z, n_zones, lane, L.base, r, t_out, y0, lds_factors,
+                           s->scr.step0 + s->first_step + step0 + k);
+          }
+        }
         // ================= the disturbance program (wave-uniform flag): the rows of the next outer step.  Before the
         // plant-I/O section, whose scan reload then reads these rows from the boundary block while the command path
         // writes rows 0 / 4 / 6 -- neither overwrites the other's rows.

@@ -97,6 +97,10 @@ struct wt_ensemble {
     wtv::ActArgs act = {};
     // dst: the per-reactor disturbance program (wt_dst.hpp), evaluated after every outer step
     wtd::DstArgs dst = {};
+    // scr: the per-reactor score program (wt_scr.hpp), evaluated after every outer step; scr_steps: outer steps the
+    // step calls have taken since score_set / score_reset (the index of the ensemble curve's next entry)
+    wtsc::ScrArgs scr = {};
+    int64_t scr_steps = 0;
     // optional per-launch HIP-event timing (bench.py roofline accounting)
     bool time_launches = false;
     std::vector<hipEvent_t> lt_pool;   // start/stop pairs
@@ -133,7 +137,11 @@ wt::StepArgs make_args(const wt_ensemble *h, double dt, int n_steps, int first_s
     a.trace = h->trace; a.trace_cap = h->trace_cap;
     a.kt = wt::default_ktab(); a.rt = wt::default_rtab();
     a.kt.dense_bias = h->knob_dense ? 1.0 : 0.0;
-    a.sens = h->sens; a.ctl = h->ctl; a.inj = h->inj; a.alm = h->alm; a.act = h->act; a.dst = h->dst;
+    a.sens = h->sens; a.ctl = h->ctl; a.inj = h->inj; a.alm = h->alm; a.act = h->act; a.dst = h->dst; a.scr = h->scr;
+    // a full curve takes no more entries: the launches then carry no curve pointer at all
+    const bool curve = h->scr.counts && h->scr_steps < h->scr.curve_cap;
+    if (!curve) a.scr.counts = nullptr;
+    a.scr.step0 = curve ? (int)h->scr_steps : 0;
     a.sens.scan_every = scan_every > 0 ? scan_every : 1;
     a.sched = h->call_sched;
     const bool rec = recording_open(h);
@@ -269,7 +277,18 @@ ArrayGroup disturb_arrays(wt_ensemble *h, int hist_cap)
                                     {(void **)&h->dst.hist, sizeof(double) * wtd::SLOTS * (size_t)hist_cap * N}}};
 }
 
-// the body of control_disable, inject_clear, alarm_clear and actuator_clear
+// the curve arrays only for curve_cap > 0, the fan only for bins > 0
+ArrayGroup score_arrays(wt_ensemble *h, int curve_cap, int bins)
+{
+    const size_t N = (size_t)h->N, cells = (size_t)curve_cap * wtsc::SLOTS;
+    return {"score", &h->scr.on, {{(void **)&h->scr.par, sizeof(double) * wtsc::PAR_DOUBLES * N},
+                                  {(void **)&h->scr.st, sizeof(double) * wtsc::ST_DOUBLES * N},
+                                  {(void **)&h->scr.tp, sizeof(double) * N},
+                                  {(void **)&h->scr.counts, sizeof(int32_t) * 3 * cells},
+                                  {(void **)&h->scr.fan, bins > 0 ? sizeof(int32_t) * (size_t)(bins + 2) * cells : 0}}};
+}
+
+// the body of control_disable, inject_clear, alarm_clear, actuator_clear and score_clear
 int stop_program(wt_ensemble *h, const ArrayGroup &g)
 {
     HIP_TRY(hipSetDevice(h->device));
@@ -530,7 +549,7 @@ int wt_ensemble_destroy(wt_ensemble *h)
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     for (const ArrayGroup &g : {core_arrays(h), sensor_arrays(h, h->sens.hist_cap), plant_io_arrays(h), record_arrays(h, 0),
                                 control_arrays(h), inject_arrays(h), alarm_arrays(h), actuator_arrays(h),
-                                disturb_arrays(h, h->dst.hist_cap)})
+                                disturb_arrays(h, h->dst.hist_cap), score_arrays(h, h->scr.curve_cap, h->scr.bins)})
         release(g);
     free_and_null(h->trace); free_and_null(h->wave_diag); free_and_null(h->snap_dev); free_and_null(h->sched);
     free_and_null(h->diag_out);
@@ -713,6 +732,7 @@ int run_steps(wt_ensemble *h, double dt, int n_steps, int fused)
         rc = queue_steps(h, dt, n_steps, fused, 0, n_steps);
     }
     if (rc == WT_OK && h->rec.pH) h->rec.steps += n_steps;
+    if (rc == WT_OK && h->scr.on) h->scr_steps += n_steps;
     return rc;
 }
 
@@ -1517,6 +1537,124 @@ int wt_ensemble_disturb_clear(wt_ensemble *h)
     return disturb_stop(h);
 }
 
+} // extern "C"
+
+namespace {
+
+static_assert(WT_SCR_SLOTS == wtsc::SLOTS && WT_NSP == wtsc::NSP && WT_NSS == wtsc::NSS && WT_SCR_MAX_BINS == wtsc::MAX_BINS,
+              "score blocks of the C ABI");
+static_assert(WT_SCR_BAND + 1 == wtsc::N_KINDS && WT_SQ_TEMPERATURE + 1 == wtsc::N_QUANTITIES && WT_SR_MEAN + 1 == wtsc::N_REDUCES &&
+              WT_SP_T_END == wtsc::P_T_END && WT_SS_RUN_MAX == wtsc::S_RUN_MAX, "score kinds and rows of the C ABI");
+
+// Host-side checks of a [WT_SCR_SLOTS][WT_NSP][N] program; nullptr when it is valid.
+const char *score_params_error(const double *p, int64_t N)
+{
+    const auto whole = [](double x, double lo, double hi) { return x == std::floor(x) && x >= lo && x <= hi; };
+    for (int k = 0; k < wtsc::SLOTS; ++k)
+        for (int64_t r = 0; r < N; ++r) {
+            double c[wtsc::NSP];
+            for (int v = 0; v < wtsc::NSP; ++v) c[v] = p[((int64_t)k * wtsc::NSP + v) * N + r];
+            if (!whole(c[wtsc::P_KIND], 0, wtsc::N_KINDS - 1)) return "kind must be 0 (off) or 1 (band)";
+            if (!whole(c[wtsc::P_QUANTITY], 0, wtsc::N_QUANTITIES - 1)) return "quantity must be 0 (pH), 1 (chlorine) or 2 (temperature)";
+            if (!whole(c[wtsc::P_REDUCE], 0, wtsc::N_REDUCES - 1)) return "reduce must be an integer in 0..3 (zone, min, max, mean)";
+            if (!whole(c[wtsc::P_ZONE], -1, 31)) return "zone must be an integer in -1..31 (-1: the last zone, the outlet)";
+            if (std::isnan(c[wtsc::P_LO]) || std::isnan(c[wtsc::P_HI])) return "lo and hi must not be NaN (-inf and +inf leave a side open)";
+            if (!(c[wtsc::P_LO] <= c[wtsc::P_HI])) return "lo must be <= hi";
+            if (!(c[wtsc::P_T_END] >= c[wtsc::P_T_START])) return "t_end must be >= t_start, neither NaN";
+        }
+    return nullptr;
+}
+
+const char *k_no_score = "no score program is set (wt_ensemble_score_set)";
+
+// The accumulators and the curve at their set-time values, t_prev = ReactorState.time, j = 0: on the handle's stream,
+// not synchronised.
+int score_restart(wt_ensemble *h)
+{
+    const size_t cells = (size_t)h->scr.curve_cap * wtsc::SLOTS;
+    const wtsc::HostOpArgs a{h->scr.st, h->scr.tp, h->time, h->N};
+    hipLaunchKernelGGL(wtsc::host_op_kernel, dim3((unsigned)((h->N + 255) / 256)), dim3(256), 0, h->stream, a);
+    HIP_TRY(hipGetLastError());
+    if (h->scr.counts) HIP_TRY(hipMemsetAsync(h->scr.counts, 0, sizeof(int32_t) * 3 * cells, h->stream));
+    if (h->scr.fan) HIP_TRY(hipMemsetAsync(h->scr.fan, 0, sizeof(int32_t) * (size_t)(h->scr.bins + 2) * cells, h->stream));
+    h->scr_steps = 0;
+    return WT_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int wt_ensemble_score_set(wt_ensemble *h, const double *params, int curve_capacity, int bins, const double *fan_lo, const double *fan_hi)
+{
+    if (!h || !params) return fail(WT_E_ARG, "NULL argument");
+    if (!h->have_state) return fail(WT_E_STATE, "set_state must precede score_set");
+    if (!wt::prog_in_item(levels_for(h->n))) return fail(WT_E_STATE, "score programs run in the kernels for up to 32 zones");
+    if (curve_capacity < 0) return fail(WT_E_ARG, "curve_capacity must be >= 0 (0 = no ensemble curve)");
+    if (bins < 0 || bins > wtsc::MAX_BINS) return fail(WT_E_ARG, "bins must be in 0..32 (0 = no fan)");
+    if (bins > 0 && (!fan_lo || !fan_hi)) return fail(WT_E_ARG, "a fan needs fan_lo and fan_hi");
+    for (int k = 0; bins > 0 && k < wtsc::SLOTS; ++k)
+        if (!(std::isfinite(fan_lo[k]) && std::isfinite(fan_hi[k]) && fan_lo[k] < fan_hi[k]))
+            return fail(WT_E_ARG, "fan_lo < fan_hi, both finite, for every slot");
+    int64_t cells = 0;
+    if (__builtin_mul_overflow((int64_t)curve_capacity * wtsc::SLOTS * (int64_t)sizeof(int32_t), (int64_t)(bins + 2), &cells))
+        return fail(WT_E_ARG, "curve size overflows int64");
+    if (int rc = wt_program_check(WT_PROG_SCORE, params, h->N)) return rc;
+    const int64_t N = h->N;
+    for (int k = 0; k < wtsc::SLOTS; ++k)
+        for (int64_t r = 0; r < N; ++r)
+            if (params[((int64_t)k * wtsc::NSP + wtsc::P_ZONE) * N + r] >= h->n) return fail(WT_E_ARG, "zone must be below the ensemble's zone count");
+    if (int rc = stop_program(h, score_arrays(h, h->scr.curve_cap, h->scr.bins))) return rc;   // set replaces any program
+    std::vector<double> par((size_t)N * wtsc::PAR_DOUBLES);
+    blocks_to_records(params, wtsc::SLOTS, wtsc::NSP, N, par.data(), wtsc::PAR_DOUBLES);
+    if (int rc = allocate(score_arrays(h, curve_capacity, bins))) return rc;
+    h->scr.curve_cap = curve_capacity; h->scr.bins = curve_capacity > 0 ? bins : 0;
+    for (int k = 0; k < wtsc::SLOTS; ++k) {
+        h->scr.fan_lo[k] = bins > 0 ? fan_lo[k] : 0.0; h->scr.fan_hi[k] = bins > 0 ? fan_hi[k] : 0.0;
+        h->scr.fan_scale[k] = bins > 0 ? (double)bins / (fan_hi[k] - fan_lo[k]) : 0.0;
+    }
+    HIP_TRY(hipMemcpyAsync((double *)h->scr.par, par.data(), sizeof(double) * par.size(), hipMemcpyHostToDevice, h->stream));
+    h->scr.on = 1;
+    if (int rc = score_restart(h)) { release(score_arrays(h, h->scr.curve_cap, h->scr.bins)); return rc; }
+    return sync_checked(h);   // the host vector is freed on return
+}
+
+int wt_ensemble_score_get(wt_ensemble *h, double *slot_state, double *t_prev)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    if (!h->scr.on) return fail(WT_E_STATE, k_no_score);
+    HIP_TRY(hipSetDevice(h->device));
+    return download_records(h, {{slot_state, h->scr.st, wtsc::ST_DOUBLES, wtsc::SLOTS, wtsc::NSS}, {t_prev, h->scr.tp, 1, 1, 1}});
+}
+
+int wt_ensemble_score_curve(wt_ensemble *h, int32_t *counts, int32_t *fan, int *n_steps)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    if (!h->scr.on) return fail(WT_E_STATE, k_no_score);
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t cells = (size_t)h->scr.curve_cap * wtsc::SLOTS;
+    if (n_steps) *n_steps = (int)(h->scr_steps < h->scr.curve_cap ? h->scr_steps : h->scr.curve_cap);
+    return download(h, {{h->scr.counts ? counts : nullptr, h->scr.counts, sizeof(int32_t) * 3 * cells},
+                        {h->scr.fan ? fan : nullptr, h->scr.fan, sizeof(int32_t) * (size_t)(h->scr.bins + 2) * cells}});
+}
+
+int wt_ensemble_score_reset(wt_ensemble *h)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    if (!h->scr.on) return fail(WT_E_STATE, k_no_score);
+    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = score_restart(h)) return rc;
+    return sync_checked(h);
+}
+
+int wt_ensemble_score_clear(wt_ensemble *h)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    if (int rc = stop_program(h, score_arrays(h, h->scr.curve_cap, h->scr.bins))) return rc;
+    h->scr.curve_cap = 0; h->scr.bins = 0; h->scr_steps = 0;
+    return WT_OK;
+}
+
 int wt_program_check(int program, const double *params, int64_t n_reactors)
 {
     if (!params) return fail(WT_E_ARG, "params is NULL");
@@ -1528,6 +1666,7 @@ int wt_program_check(int program, const double *params, int64_t n_reactors)
     case WT_PROG_ALARM: msg = alarm_params_error(params, n_reactors); break;
     case WT_PROG_ACTUATOR: msg = actuator_params_error(params, n_reactors); break;
     case WT_PROG_DISTURB: msg = disturb_params_error(params, n_reactors); break;
+    case WT_PROG_SCORE: msg = score_params_error(params, n_reactors); break;
     default: return fail(WT_E_ARG, "unknown program");
     }
     return msg ? fail(WT_E_ARG, msg) : WT_OK;

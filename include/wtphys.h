@@ -499,13 +499,75 @@ int wt_ensemble_disturb_history(wt_ensemble *h, double *offsets, int32_t *n_fill
 /* program off, buffers freed, targeted rows back to the base (no effect while none is set) */
 int wt_ensemble_disturb_clear(wt_ensemble *h);
 
-/* ---- the parameter checks of the four scan programs and the disturbance program, without a handle or a device ----
+/* ---- per-reactor score programs: ground-truth excursion metrics and ensemble curves ----
+ * Up to WT_SCR_SLOTS slots per reactor judge the true ReactorState after every outer step against a band; nothing in
+ * the plant changes (state, readings, images and program states keep their bits).  Parameters [WT_SCR_SLOTS][WT_NSP][N]:
+ * kind (0 WT_SCR_OFF, 1 WT_SCR_BAND), quantity (0 pH, 1 chlorine, 2 temperature: the ReactorState arrays after the
+ * step and its clamps), reduce (0 ZONE, 1 MIN, 2 MAX, 3 MEAN over the reactor's zones), zone (an integer -1..31; -1 is
+ * the last zone, the outlet; only ZONE reads it), lo <= hi (lo may be -inf, hi +inf, neither NaN), t_start, t_end >=
+ * t_start (-inf and +inf allowed, NaN not); otherwise WT_E_ARG.  The set call also refuses zone >= n_zones.
+ * Slot state [WT_SCR_SLOTS][WT_NSS][N]: n_eval, time, integral, t_low, t_high, area_low, area_high, v_min, v_max, last,
+ * out, n_exc, t_first_out, run, run_max; and a per-reactor t_prev [N].  set zeroes everything except v_min, v_max,
+ * last and t_first_out (NaN) and t_prev (ReactorState.time); nothing is evaluated at set time.
+ * After every outer step of a reactor that stepped (the sensor suite's test: no ReactorState failure after the step),
+ * with t = its ReactorState.time after the step, in fp64 without fused multiply-adds:
+ *   h = t - t_prev;  t_prev = t
+ *   for each slot s in ascending order with kind != OFF and t_start <= t < t_end:
+ *     x[z] = quantity in zone z, n zones
+ *     v = ZONE: x[zone < 0 ? n-1 : zone]
+ *         MIN:  v = x[0]; for z = 1..n-1: v = x[z] < v ? x[z] : v          (MAX likewise with >)
+ *         MEAN: (((x[0] + x[1]) + x[2]) + ... + x[n-1]) / n                 (ascending zone order)
+ *     n_eval += 1;  time += h;  integral += v * h;  last = v
+ *     v_min = n_eval == 1 ? v : (v < v_min ? v : v_min);   v_max likewise
+ *     low = v < lo;  high = v > hi
+ *     if low:  t_low  += h;  area_low  += (lo - v) * h
+ *     if high: t_high += h;  area_high += (v - hi) * h
+ *     if low or high: { if out == 0: n_exc += 1;  if t_first_out is NaN: t_first_out = t;
+ *                       out = 1;  run += h;  run_max = run > run_max ? run : run_max }
+ *     else:           { out = 0;  run = 0 }
+ * Slots outside their window and reactors that did not step change nothing.  (integral of outlet chlorine is the CT
+ * exposure, area_low the disinfection deficit, run_max the longest contiguous violation.)
+ * Ensemble curve: with curve_capacity C > 0, let j be the number of outer steps the step calls have taken since set or
+ * reset (counted for the whole ensemble, as wt_ensemble_record counts).  For j < C every slot evaluation in its window
+ * adds 1 to the int32 counts[j][s][0] (scored), to [1] if low and to [2] if high; with bins B in 1..WT_SCR_MAX_BINS
+ * also to fan[j][s][b],  b = v < fan_lo[s] ? 0 : v >= fan_hi[s] ? B + 1 : 1 + min(B - 1, (int)((v - fan_lo[s]) * scale)),
+ * scale = B / (fan_hi[s] - fan_lo[s]) in fp64 (fan_lo < fan_hi, both finite, else WT_E_ARG; the fan needs C > 0).  The
+ * counters are integers added atomically: their values depend neither on the schedule nor on the placement, and those
+ * of the shards of one ensemble simply add.
+ * set replaces any program.  Needs set_state and n <= 32 zones (WT_E_STATE); neither sensors nor plant I/O.  Works
+ * with wt_ensemble_step and wt_ensemble_step_scheduled, every schedule and any split into calls.  All calls synchronise. */
+#define WT_SCR_SLOTS 4
+#define WT_SCR_MAX_BINS 32
+enum { WT_SCR_OFF = 0, WT_SCR_BAND = 1 };
+enum { WT_SQ_PH = 0, WT_SQ_CHLORINE = 1, WT_SQ_TEMPERATURE = 2 };
+enum { WT_SR_ZONE = 0, WT_SR_MIN = 1, WT_SR_MAX = 2, WT_SR_MEAN = 3 };
+enum { WT_SP_KIND = 0, WT_SP_QUANTITY = 1, WT_SP_REDUCE = 2, WT_SP_ZONE = 3, WT_SP_LO = 4, WT_SP_HI = 5, WT_SP_T_START = 6,
+       WT_SP_T_END = 7, WT_NSP = 8 };
+enum { WT_SS_N_EVAL = 0, WT_SS_TIME = 1, WT_SS_INTEGRAL = 2, WT_SS_T_LOW = 3, WT_SS_T_HIGH = 4, WT_SS_AREA_LOW = 5,
+       WT_SS_AREA_HIGH = 6, WT_SS_V_MIN = 7, WT_SS_V_MAX = 8, WT_SS_LAST = 9, WT_SS_OUT = 10, WT_SS_N_EXC = 11,
+       WT_SS_T_FIRST_OUT = 12, WT_SS_RUN = 13, WT_SS_RUN_MAX = 14, WT_NSS = 15 };
+/* fan_lo, fan_hi: host [WT_SCR_SLOTS], read only for bins > 0 */
+int wt_ensemble_score_set(wt_ensemble *h, const double *params /* [WT_SCR_SLOTS][WT_NSP][N] */, int curve_capacity, int bins,
+                          const double *fan_lo, const double *fan_hi);
+/* host [WT_SCR_SLOTS][WT_NSS][N] slot state and [N] t_prev (either may be NULL); WT_E_STATE while no program is set */
+int wt_ensemble_score_get(wt_ensemble *h, double *slot_state, double *t_prev);
+/* host [curve_capacity][WT_SCR_SLOTS][3] counts, [curve_capacity][WT_SCR_SLOTS][bins + 2] fan and n_steps = min(C, j), the
+ * entries filled (any may be NULL; entries beyond n_steps are 0); WT_E_STATE while no program is set */
+int wt_ensemble_score_curve(wt_ensemble *h, int32_t *counts, int32_t *fan, int *n_steps);
+/* accumulators and curve back to their set-time values, j = 0, t_prev = the current ReactorState.time; the parameters
+ * stay (scoring after a warm-up); WT_E_STATE while no program is set */
+int wt_ensemble_score_reset(wt_ensemble *h);
+/* program off, buffers freed (no effect while none is set) */
+int wt_ensemble_score_clear(wt_ensemble *h);
+
+/* ---- the parameter checks of the four scan programs, the disturbance and the score program, without a handle or a device ----
  * params: host, the block the program's set or enable call takes, for n_reactors reactors (WT_PROG_CONTROL:
  * wt_ensemble_control_enable / retune, WT_PROG_INJECT: wt_ensemble_inject_set, WT_PROG_ALARM: wt_ensemble_alarm_set,
- * WT_PROG_ACTUATOR: wt_ensemble_actuator_set, WT_PROG_DISTURB: wt_ensemble_disturb_set).  WT_OK when the block passes that call's checks; otherwise WT_E_ARG
+ * WT_PROG_ACTUATOR: wt_ensemble_actuator_set, WT_PROG_DISTURB: wt_ensemble_disturb_set, WT_PROG_SCORE:
+ * wt_ensemble_score_set).  WT_OK when the block passes that call's checks; otherwise WT_E_ARG
  * and wt_last_error() is the message the call gives for it.  A NULL params, n_reactors < 1 or an unknown program
  * also give WT_E_ARG.  Makes no HIP call. */
-enum { WT_PROG_CONTROL = 0, WT_PROG_INJECT = 1, WT_PROG_ALARM = 2, WT_PROG_ACTUATOR = 3, WT_PROG_DISTURB = 4 };
+enum { WT_PROG_CONTROL = 0, WT_PROG_INJECT = 1, WT_PROG_ALARM = 2, WT_PROG_ACTUATOR = 3, WT_PROG_DISTURB = 4, WT_PROG_SCORE = 5 };
 int wt_program_check(int program, const double *params, int64_t n_reactors);
 
 /* ---- reactor diagnostics (SURVEY.md section 8(f) NEXT-4): reductions over the zones of every reactor ----
