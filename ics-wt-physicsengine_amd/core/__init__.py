@@ -5,11 +5,12 @@ from .reactor import (BoundaryConditions, EnsembleState, IntegratedCSTR, Physics
                       ReactorConfiguration, ReactorEnsemble, ReactorState, Trajectory, boundary_block,
                       boundary_schedule_block)
 from .control import ControlState, LoopState, PILoop, control_block
-from .inject import Injection, InjectionState, injection_block
+from .inject import Injection, InjectionState, attack_window, injection_block
 from .alarm import Alarm, AlarmState, alarm_block
 from .actuator import Actuator, ActuatorState, actuator_block
 from .disturb import Disturbance, DisturbanceState, disturbance_block
 from .score import Score, ScoreCurve, ScoreState, score_block
+from .detect import Detector, DetectorState, detector_block
 from .chemistry import AqueousChemistry, BufferSystem, solve_pH
 from .physics import (ArrheniusParameters, FlowParameters, GeometryParameters, SpatialModel, StratificationParameters,
                       TemperatureDependentKinetics, TransportModel, run_all_validations, validate_chemistry,
@@ -23,6 +24,7 @@ __all__ = ["BoundaryConditions", "EnsembleState", "IntegratedCSTR", "PhysicsEngi
            "PILoop", "ControlState", "LoopState", "control_block", "Injection", "InjectionState", "injection_block",
            "Alarm", "AlarmState", "alarm_block", "Actuator", "ActuatorState", "actuator_block",
            "Disturbance", "DisturbanceState", "disturbance_block", "Score", "ScoreCurve", "ScoreState", "score_block",
+           "Detector", "DetectorState", "detector_block", "attack_window",
            "AqueousChemistry", "BufferSystem", "solve_pH", "make_ensemble", "make_boundary_schedule", "params", "sharding", "gather_state", "shard_bounds",
            # the rest of wt_simulator.core's export list (core/__init__.py:238-263)
            "TemperatureDependentKinetics", "ArrheniusParameters", "TransportModel", "GeometryParameters", "FlowParameters",

@@ -80,3 +80,14 @@ def injection_block(n_reactors: int, *injections: Injection) -> np.ndarray:
     k-th injection, the slots after the last are off."""
     n = int(n_reactors)
     return slot_block(injections, n, SLOTS, "injection", slot_rows, _off_rows(n), _native.WT_PROG_INJECT)
+
+
+def attack_window(block: np.ndarray):
+    """Per reactor, the (earliest start, latest end) over the slots of a [WT_INJ_SLOTS][WT_NI][N] injection block that
+    are not OFF; (+inf, +inf) where every slot is off.  The ground-truth label of a detector program:
+    ``set_detectors(..., attack=attack_window(injection_block(...)))``."""
+    block = np.asarray(block, dtype=np.float64)
+    on = block[:, PARAM_ROWS.index("mode")] != MODES.index("off")
+    start = np.where(on, block[:, PARAM_ROWS.index("start")], np.inf).min(axis=0)
+    end = np.where(on, block[:, PARAM_ROWS.index("end")], -np.inf).max(axis=0)
+    return start, np.where(on.any(axis=0), end, np.inf)

@@ -18,7 +18,7 @@ from typing import Dict, Iterable, List, Optional, Sequence, Union
 
 import numpy as np
 
-from . import _native, _program, actuator, alarm, control, disturb, inject, params, score
+from . import _native, _program, actuator, alarm, control, detect, disturb, inject, params, score
 
 logger = logging.getLogger(__name__)
 
@@ -274,6 +274,7 @@ class ReactorEnsemble:
         self._plant_io = False
         self._disturb_history = -1              # capacity of the disturbance program's history; -1: no program
         self._score_curve = None                # (capacity, bins, edges) of the score program's curve; None: no program
+        self._detect_labels: Optional[np.ndarray] = None    # the label block of the detector program; None: no program
         self._control_params: Optional[np.ndarray] = None   # the last block enable_control / retune_control sent
 
     # -- lifetime
@@ -737,6 +738,36 @@ class ReactorEnsemble:
         self._control_call(_native.lib().wt_ensemble_disturb_clear)
         self._disturb_history = -1
         self._device_boundary_moved = True
+
+    # -- anomaly detector programs at every PLC scan, on the device (wt_det.hpp)
+    def set_detectors(self, *detectors: "detect.Detector", attack=None) -> None:
+        """Run a detector program of up to four :class:`Detector` slots at every PLC scan, inside the step call, last in
+        the scan: each slot keeps a CUSUM, EWMA or flat-line statistic of one reading's residual, raises its alarm
+        above the slot's limit and counts the scans against the ground-truth window ``attack`` = (start, end), scalars
+        or (N,) arrays of loop times (default: never attacked; ``inject.attack_window`` gives the window of an
+        injection block).  The program is passive: the plant and the other programs keep their bits.  Replaces any
+        earlier program and resets its state.  Needs plant I/O and at most 32 zones."""
+        blk = detect.detector_block(self.n_reactors, *detectors)
+        lab = detect.label_block(self.n_reactors, attack)
+        self._control_call(_native.lib().wt_ensemble_detect_set, _native.dptr(blk), _native.dptr(lab))
+        self._detect_labels = lab
+
+    def detector_state(self) -> "detect.DetectorState":
+        """Slot state, t_prev and label of the detector program (one synchronisation)."""
+        st = np.empty((detect.SLOTS, detect.NKS, self.n_reactors), dtype=np.float64)
+        tp = np.empty(self.n_reactors, dtype=np.float64)
+        self._control_call(_native.lib().wt_ensemble_detect_get, _native.dptr(st), _native.dptr(tp))
+        return detect.DetectorState.from_block(st, tp, self._detect_labels)
+
+    def reset_detectors(self) -> None:
+        """Statistics, alarms and counts back to their values at :meth:`set_detectors`, at the current loop time; the
+        parameters and the label stay (detection after a warm-up)."""
+        self._control_call(_native.lib().wt_ensemble_detect_reset)
+
+    def clear_detectors(self) -> None:
+        """Stop the detector program and free its buffers."""
+        self._control_call(_native.lib().wt_ensemble_detect_clear)
+        self._detect_labels = None
 
     # -- score programs after every outer step, on the device (wt_scr.hpp)
     def set_scores(self, *scores: "score.Score", curve: int = 0, bins: int = 0, fan_range=None) -> None:

@@ -101,6 +101,8 @@ struct wt_ensemble {
     // step calls have taken since score_set / score_reset (the index of the ensemble curve's next entry)
     wtsc::ScrArgs scr = {};
     int64_t scr_steps = 0;
+    // det: the per-reactor anomaly detector program (wt_det.hpp), evaluated last in every PLC scan
+    wtk::DetArgs det = {};
     // optional per-launch HIP-event timing (bench.py roofline accounting)
     bool time_launches = false;
     std::vector<hipEvent_t> lt_pool;   // start/stop pairs
@@ -137,7 +139,7 @@ wt::StepArgs make_args(const wt_ensemble *h, double dt, int n_steps, int first_s
     a.trace = h->trace; a.trace_cap = h->trace_cap;
     a.kt = wt::default_ktab(); a.rt = wt::default_rtab();
     a.kt.dense_bias = h->knob_dense ? 1.0 : 0.0;
-    a.sens = h->sens; a.ctl = h->ctl; a.inj = h->inj; a.alm = h->alm; a.act = h->act; a.dst = h->dst; a.scr = h->scr;
+    a.sens = h->sens; a.ctl = h->ctl; a.inj = h->inj; a.alm = h->alm; a.act = h->act; a.dst = h->dst; a.scr = h->scr; a.det = h->det;
     // a full curve takes no more entries: the launches then carry no curve pointer at all
     const bool curve = h->scr.counts && h->scr_steps < h->scr.curve_cap;
     if (!curve) a.scr.counts = nullptr;
@@ -288,7 +290,16 @@ ArrayGroup score_arrays(wt_ensemble *h, int curve_cap, int bins)
                                   {(void **)&h->scr.fan, bins > 0 ? sizeof(int32_t) * (size_t)(bins + 2) * cells : 0}}};
 }
 
-// the body of control_disable, inject_clear, alarm_clear, actuator_clear and score_clear
+ArrayGroup detect_arrays(wt_ensemble *h)
+{
+    const size_t N = (size_t)h->N;
+    return {"detect", &h->det.on, {{(void **)&h->det.par, sizeof(double) * wtk::PAR_DOUBLES * N},
+                                   {(void **)&h->det.st, sizeof(double) * wtk::ST_DOUBLES * N},
+                                   {(void **)&h->det.lab, sizeof(double) * wtk::NKR * N},
+                                   {(void **)&h->det.tp, sizeof(double) * N}}};
+}
+
+// the body of control_disable, inject_clear, alarm_clear, actuator_clear, score_clear and detect_clear
 int stop_program(wt_ensemble *h, const ArrayGroup &g)
 {
     HIP_TRY(hipSetDevice(h->device));
@@ -549,7 +560,7 @@ int wt_ensemble_destroy(wt_ensemble *h)
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     for (const ArrayGroup &g : {core_arrays(h), sensor_arrays(h, h->sens.hist_cap), plant_io_arrays(h), record_arrays(h, 0),
                                 control_arrays(h), inject_arrays(h), alarm_arrays(h), actuator_arrays(h),
-                                disturb_arrays(h, h->dst.hist_cap), score_arrays(h, h->scr.curve_cap, h->scr.bins)})
+                                disturb_arrays(h, h->dst.hist_cap), score_arrays(h, h->scr.curve_cap, h->scr.bins), detect_arrays(h)})
         release(g);
     free_and_null(h->trace); free_and_null(h->wave_diag); free_and_null(h->snap_dev); free_and_null(h->sched);
     free_and_null(h->diag_out);
@@ -1655,6 +1666,127 @@ int wt_ensemble_score_clear(wt_ensemble *h)
     return WT_OK;
 }
 
+} // extern "C"
+
+namespace {
+
+static_assert(WT_DET_SLOTS == wtk::SLOTS && WT_NK == wtk::NK && WT_NKS == wtk::NKS && WT_NKR == wtk::NKR, "detector blocks of the C ABI");
+static_assert(WT_DET_CUSUM == wtk::D_CUSUM && WT_DET_EWMA == wtk::D_EWMA && WT_DET_FLATLINE == wtk::D_FLATLINE &&
+              WT_DET_FLATLINE + 1 == wtk::N_KINDS && WT_DET_FIELD == wtk::SRC_FIELD && WT_DET_SENSOR == wtk::REF_SENSOR &&
+              WT_DET_TRACK == wtk::REF_TRACK && WT_DET_TRACK + 1 == wtk::N_REFS && WT_DET_ALARM == wtk::ON_BAD_ALARM,
+              "detector kinds, sources, references and policies of the C ABI");
+static_assert(WT_K_REF_ARG == wtk::K_REF_ARG && WT_K_ON_BAD == wtk::K_ON_BAD && WT_KS_X_PREV == wtk::KS_X_PREV &&
+              WT_KS_T_DETECT == wtk::KS_T_DETECT && WT_KS_N_FN == wtk::KS_N_FN && WT_KR_LABEL_END == wtk::KR_LABEL_END,
+              "detector rows of the C ABI");
+static_assert(wtk::NK % 2 == 0 && wtk::NKS % 2 == 0 && wtk::NKR == 2, "the detector's records are read in 16-byte pairs");
+
+// Host-side checks of a [WT_DET_SLOTS][WT_NK][N] program; nullptr when it is valid.
+const char *detect_params_error(const double *p, int64_t N)
+{
+    const auto is_int_in = [](double x, int lo, int hi) { return x == std::floor(x) && x >= lo && x <= hi; };
+    for (int s = 0; s < wtk::SLOTS; ++s)
+        for (int64_t r = 0; r < N; ++r) {
+            double c[wtk::NK];
+            for (int k = 0; k < wtk::NK; ++k) c[k] = p[((int64_t)s * wtk::NK + k) * N + r];
+            for (int k = 0; k < wtk::NK; ++k)
+                if (!std::isfinite(c[k]) && !(k == wtk::K_T_ARM && c[k] == -INFINITY))
+                    return "detector parameters must be finite (t_arm may be -inf)";
+            const double kind = c[wtk::K_KIND], ref = c[wtk::K_REF], slack = c[wtk::K_SLACK];
+            if (!is_int_in(kind, 0, wtk::N_KINDS - 1)) return "kind must be 0 (off), 1 (cusum), 2 (ewma) or 3 (flatline)";
+            if (kind == wtk::D_OFF) continue;                      // the other rows of an OFF slot are not read
+            if (!is_int_in(c[wtk::K_SENSOR], 0, WT_N_SENSORS - 1)) return "sensor must be an integer in 0..6";
+            if (!is_int_in(c[wtk::K_SOURCE], 0, 1)) return "source must be 0 (image) or 1 (field)";
+            if (!is_int_in(ref, 0, wtk::N_REFS - 1)) return "ref must be 0 (const), 1 (sensor) or 2 (track)";
+            if (ref == wtk::REF_SENSOR) {
+                if (!is_int_in(c[wtk::K_REF_ARG], 0, WT_N_SENSORS - 1)) return "a SENSOR reference's ref_arg must be a sensor index in 0..6";
+                if (!is_int_in(c[wtk::K_REF_SOURCE], 0, 1)) return "ref_source must be 0 (image) or 1 (field)";
+            }
+            if (ref == wtk::REF_TRACK && !(c[wtk::K_REF_ARG] > 0)) return "a TRACK reference's ref_arg (tau) must be > 0";
+            if (!(c[wtk::K_SIGMA] > 0)) return "sigma must be > 0";
+            if (kind == wtk::D_CUSUM && !(slack >= 0)) return "a CUSUM slot's slack (k) must be >= 0";
+            if (kind == wtk::D_EWMA && !(slack > 0 && slack <= 1)) return "an EWMA slot's slack (lambda) must be in (0, 1]";
+            if (kind == wtk::D_FLATLINE && !(slack >= 0)) return "a FLATLINE slot's slack (eps) must be >= 0";
+            if (!(c[wtk::K_LIMIT] > 0)) return "limit must be > 0";
+            if (!is_int_in(c[wtk::K_ON_BAD], 0, 1)) return "on_bad must be 0 (hold) or 1 (alarm)";
+        }
+    return nullptr;
+}
+
+const char *k_no_detect = "no detector program is set (wt_ensemble_detect_set)";
+
+// Slot state and t_prev at their set-time values, t_prev = the reactors' loop time now: uploaded and synchronised.
+int detect_restart(wt_ensemble *h)
+{
+    const int64_t N = h->N;
+    std::vector<double> st((size_t)N * wtk::ST_DOUBLES, 0.0), lt((size_t)N);
+    for (int64_t r = 0; r < N; ++r)
+        for (int s = 0; s < wtk::SLOTS; ++s) {
+            double *q = st.data() + r * wtk::ST_DOUBLES + s * wtk::NKS;
+            q[wtk::KS_BASELINE] = q[wtk::KS_X_PREV] = q[wtk::KS_T_FIRST] = q[wtk::KS_T_DETECT] = NAN;
+        }
+    // (the download also waits for queued launches, which may still read or write the old records)
+    if (int rc = download(h, {{lt.data(), h->sens.pack.loop_time, sizeof(double) * (size_t)N}})) return rc;
+    HIP_TRY(hipMemcpyAsync(h->det.st, st.data(), sizeof(double) * st.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->det.tp, lt.data(), sizeof(double) * lt.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // the host vectors are freed on return
+    return WT_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int wt_ensemble_detect_set(wt_ensemble *h, const double *params, const double *labels)
+{
+    if (int rc = check_program_set(h, params, WT_PROG_DETECT, "detectors read the plant I/O scan: enable plant I/O first",
+                                   "detector programs run in the kernels for up to 32 zones"))
+        return rc;
+    if (!labels) return fail(WT_E_ARG, "NULL argument");
+    const int64_t N = h->N;
+    for (int64_t r = 0; r < N; ++r) {
+        const double t0 = labels[wtk::KR_LABEL_START * N + r], t1 = labels[wtk::KR_LABEL_END * N + r];
+        if (std::isnan(t0) || std::isnan(t1)) return fail(WT_E_ARG, "label_start and label_end must not be NaN");
+        if (!(t1 >= t0)) return fail(WT_E_ARG, "label_end must be >= label_start");
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    std::vector<double> par((size_t)N * wtk::PAR_DOUBLES), lab((size_t)N * wtk::NKR);
+    blocks_to_records(params, wtk::SLOTS, wtk::NK, N, par.data(), wtk::PAR_DOUBLES);
+    blocks_to_records(labels, 1, wtk::NKR, N, lab.data(), wtk::NKR);
+    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still read or write the old records
+    const bool fresh_arrays = !h->det.par;
+    if (int rc = allocate(detect_arrays(h))) return rc;
+    HIP_TRY(hipMemcpyAsync((double *)h->det.par, par.data(), sizeof(double) * par.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync((double *)h->det.lab, lab.data(), sizeof(double) * lab.size(), hipMemcpyHostToDevice, h->stream));
+    if (int rc = detect_restart(h)) {
+        if (fresh_arrays) release(detect_arrays(h));
+        return rc;
+    }
+    h->det.on = 1;
+    return WT_OK;
+}
+
+int wt_ensemble_detect_get(wt_ensemble *h, double *slot_state, double *t_prev)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    if (!h->det.on) return fail(WT_E_STATE, k_no_detect);
+    HIP_TRY(hipSetDevice(h->device));
+    return download_records(h, {{slot_state, h->det.st, wtk::ST_DOUBLES, wtk::SLOTS, wtk::NKS}, {t_prev, h->det.tp, 1, 1, 1}});
+}
+
+int wt_ensemble_detect_reset(wt_ensemble *h)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    if (!h->det.on) return fail(WT_E_STATE, k_no_detect);
+    HIP_TRY(hipSetDevice(h->device));
+    return detect_restart(h);
+}
+
+int wt_ensemble_detect_clear(wt_ensemble *h)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    return stop_program(h, detect_arrays(h));
+}
+
 int wt_program_check(int program, const double *params, int64_t n_reactors)
 {
     if (!params) return fail(WT_E_ARG, "params is NULL");
@@ -1667,6 +1799,7 @@ int wt_program_check(int program, const double *params, int64_t n_reactors)
     case WT_PROG_ACTUATOR: msg = actuator_params_error(params, n_reactors); break;
     case WT_PROG_DISTURB: msg = disturb_params_error(params, n_reactors); break;
     case WT_PROG_SCORE: msg = score_params_error(params, n_reactors); break;
+    case WT_PROG_DETECT: msg = detect_params_error(params, n_reactors); break;
     default: return fail(WT_E_ARG, "unknown program");
     }
     return msg ? fail(WT_E_ARG, msg) : WT_OK;

@@ -560,14 +560,84 @@ int wt_ensemble_score_reset(wt_ensemble *h);
 /* program off, buffers freed (no effect while none is set) */
 int wt_ensemble_score_clear(wt_ensemble *h);
 
-/* ---- the parameter checks of the four scan programs, the disturbance and the score program, without a handle or a device ----
+/* ---- per-reactor anomaly detector programs: a change-detection statistic at every PLC scan, judged against a label ----
+ * What an intrusion- or fault-detection study evaluates: up to WT_DET_SLOTS slots per reactor keep a statistic of the
+ * residual of one reading (a limit alarm has no memory of it), raise an alarm where it exceeds a threshold, and count
+ * the scans against the reactor's ground-truth attack window.  The program is passive: nothing in the plant changes
+ * (state, readings, images, boundary and the other programs' states keep their bits).
+ * Parameters [WT_DET_SLOTS][WT_NK][N]: kind (0 OFF, 1 CUSUM, 2 EWMA, 3 FLATLINE), sensor (0..6, WT_N_SENSORS order),
+ * source (0 IMAGE, 1 FIELD: the alarm program's meaning), ref (0 CONST, 1 SENSOR, 2 TRACK: what the reading is compared
+ * with), ref_arg (CONST: the value; SENSOR: the second sensor's index 0..6; TRACK: the time constant tau > 0 in
+ * seconds), ref_source (source of the second sensor, read only for SENSOR), mu (expected residual), sigma > 0 (residual
+ * scale), slack (CUSUM: k >= 0; EWMA: lambda in (0, 1]; FLATLINE: eps >= 0 in the sensor's units), limit (CUSUM / EWMA:
+ * threshold > 0 on the statistic; FLATLINE: seconds > 0), t_arm (the slot is skipped while t < t_arm: sensor warm-up;
+ * finite or -inf), on_bad (0 HOLD, 1 ALARM).  No row may be NaN or infinite (t_arm may be -inf); the rows of an OFF
+ * slot after kind are not read and not range-checked.  Otherwise WT_E_ARG.
+ * Label [WT_NKR][N]: label_start, label_end, the attack window.  Neither is NaN, label_end >= label_start, both may be
+ * infinite (+inf, +inf: never attacked).
+ * Slot state [WT_DET_SLOTS][WT_NKS][N]: gp, gn, baseline, x_prev, stat, stat_max, alarm, n_eval, n_bad, n_alarm, n_raise,
+ * t_first, t_detect, n_tp, n_fp, n_fn; and a per-reactor t_prev [N].  set gives all 0 except baseline, x_prev, t_first,
+ * t_detect NaN and t_prev = the reactor's loop time.
+ * At every PLC scan of a reactor that stepped, after its alarm program (last in the scan), with t = the loop time the
+ * scan stores, in fp64 with IEEE add, multiply, divide, compare, fmax and fabs only, no fused multiply-adds:
+ *   h = t - t_prev;  t_prev = t;  attacked = label_start <= t && t < label_end
+ *   for each slot s ascending with kind != OFF and t >= t_arm:
+ *     was = alarm
+ *     v, f = float32 reading and fault code of `sensor` from `source`;  bad = !isfinite(v) || f != 0
+ *     if ref == SENSOR: w, g = reading and fault of sensor (int)ref_arg from ref_source;  bad = bad || !isfinite(w) || g != 0
+ *     if bad:  n_bad += 1;  if on_bad == ALARM: alarm = 1     (HOLD: alarm keeps its value; no statistic changes either way)
+ *     else:
+ *       x = (double)v
+ *       base = CONST: ref_arg | SENSOR: (double)w | TRACK: (baseline is NaN ? x : baseline)
+ *       if ref == TRACK: baseline = base + (h / (ref_arg + h)) * (x - base)       (after base was taken)
+ *       z = ((x - base) - mu) / sigma
+ *       CUSUM:    gp = fmax(0, (gp + z) - slack);  gn = fmax(0, (gn - z) - slack);  stat = fmax(gp, gn)
+ *       EWMA:     gp = gp + slack * (z - gp);  stat = fabs(gp)
+ *       FLATLINE: gp = (x_prev is not NaN && fabs(x - x_prev) <= slack) ? gp + h : 0;  stat = gp
+ *       x_prev = x;  alarm = stat > limit;  stat_max = stat > stat_max ? stat : stat_max
+ *     n_eval += 1
+ *     if alarm: n_alarm += 1;  if !was: n_raise += 1;  if t_first is NaN: t_first = t
+ *               if t >= label_start && t_detect is NaN: t_detect = t
+ *     attacked ? (alarm ? n_tp : n_fn) += 1 : (alarm ? n_fp += 1 : nothing)      (true negatives = n_eval - n_tp - n_fn - n_fp)
+ * Reactors that did not step and slots before t_arm change nothing.  Alarms do not latch and the statistics are not
+ * reset by an alarm.  set replaces any program.  Needs plant I/O and n <= 32 zones (WT_E_STATE), neither an injection
+ * nor a control program; all calls synchronise. */
+#define WT_DET_SLOTS 4
+enum { WT_DET_OFF = 0, WT_DET_CUSUM = 1, WT_DET_EWMA = 2, WT_DET_FLATLINE = 3 };
+enum { WT_DET_IMAGE = 0, WT_DET_FIELD = 1 };
+enum { WT_DET_CONST = 0, WT_DET_SENSOR = 1, WT_DET_TRACK = 2 };
+enum { WT_DET_HOLD = 0, WT_DET_ALARM = 1 };
+enum {
+    WT_K_KIND = 0, WT_K_SENSOR = 1, WT_K_SOURCE = 2, WT_K_REF = 3, WT_K_REF_ARG = 4, WT_K_REF_SOURCE = 5, WT_K_MU = 6,
+    WT_K_SIGMA = 7, WT_K_SLACK = 8, WT_K_LIMIT = 9, WT_K_T_ARM = 10, WT_K_ON_BAD = 11,
+    WT_NK = 12
+};
+enum {
+    WT_KS_GP = 0, WT_KS_GN = 1, WT_KS_BASELINE = 2, WT_KS_X_PREV = 3, WT_KS_STAT = 4, WT_KS_STAT_MAX = 5, WT_KS_ALARM = 6,
+    WT_KS_N_EVAL = 7, WT_KS_N_BAD = 8, WT_KS_N_ALARM = 9, WT_KS_N_RAISE = 10, WT_KS_T_FIRST = 11, WT_KS_T_DETECT = 12,
+    WT_KS_N_TP = 13, WT_KS_N_FP = 14, WT_KS_N_FN = 15,
+    WT_NKS = 16
+};
+enum { WT_KR_LABEL_START = 0, WT_KR_LABEL_END = 1, WT_NKR = 2 };
+int wt_ensemble_detect_set(wt_ensemble *h, const double *params /* [WT_DET_SLOTS][WT_NK][N] */, const double *labels /* [WT_NKR][N] */);
+/* host [WT_DET_SLOTS][WT_NKS][N] slot state and [N] t_prev (either may be NULL); WT_E_STATE while no program is set */
+int wt_ensemble_detect_get(wt_ensemble *h, double *slot_state, double *t_prev);
+/* slot state and t_prev back to their set-time values at the current loop time; parameters and labels stay (detection
+ * after a warm-up); WT_E_STATE while no program is set */
+int wt_ensemble_detect_reset(wt_ensemble *h);
+/* program off, buffers freed (no effect while none is set) */
+int wt_ensemble_detect_clear(wt_ensemble *h);
+
+/* ---- the parameter checks of the scan programs, the disturbance and the score program, without a handle or a device ----
  * params: host, the block the program's set or enable call takes, for n_reactors reactors (WT_PROG_CONTROL:
  * wt_ensemble_control_enable / retune, WT_PROG_INJECT: wt_ensemble_inject_set, WT_PROG_ALARM: wt_ensemble_alarm_set,
  * WT_PROG_ACTUATOR: wt_ensemble_actuator_set, WT_PROG_DISTURB: wt_ensemble_disturb_set, WT_PROG_SCORE:
- * wt_ensemble_score_set).  WT_OK when the block passes that call's checks; otherwise WT_E_ARG
+ * wt_ensemble_score_set, WT_PROG_DETECT: the slot block of wt_ensemble_detect_set, whose label block that call checks
+ * itself).  WT_OK when the block passes that call's checks; otherwise WT_E_ARG
  * and wt_last_error() is the message the call gives for it.  A NULL params, n_reactors < 1 or an unknown program
  * also give WT_E_ARG.  Makes no HIP call. */
-enum { WT_PROG_CONTROL = 0, WT_PROG_INJECT = 1, WT_PROG_ALARM = 2, WT_PROG_ACTUATOR = 3, WT_PROG_DISTURB = 4, WT_PROG_SCORE = 5 };
+enum { WT_PROG_CONTROL = 0, WT_PROG_INJECT = 1, WT_PROG_ALARM = 2, WT_PROG_ACTUATOR = 3, WT_PROG_DISTURB = 4, WT_PROG_SCORE = 5,
+       WT_PROG_DETECT = 6 };
 int wt_program_check(int program, const double *params, int64_t n_reactors);
 
 /* ---- reactor diagnostics (SURVEY.md section 8(f) NEXT-4): reductions over the zones of every reactor ----
