@@ -1,7 +1,8 @@
 """Helpers of the GPU tests and probes of the per-reactor scan programs (test_gpu_control.py, test_gpu_inject.py,
-test_gpu_alarm.py, test_gpu_actuator.py, tools/*_probe.py): a plant with sensors and plant I/O, a pair of PI loops, the
+test_gpu_alarm.py, test_gpu_actuator.py, test_gpu_program_shapes.py, tools/*_probe.py): a plant with sensors and plant I/O, a pair of PI loops, the
 plant's observable state, the message of a refused parameter block, and the host side of the PLC scan -- the calls of
-one scan interval, the device's scan order and the holding words of a host master."""
+one scan interval, the device's scan order and the holding words of a host master; the zone count -> kernel instantiation
+rule and the wavefront packing."""
 import importlib
 
 import numpy as np
@@ -12,6 +13,44 @@ DT, K = 10.0, 300          # 3000 s: the pH sensors' 1800 s warm-up ends inside 
 MASTER = (0.5, 0.25, 6.0)  # acid, chlorine, inlet flow commands the master writes
 
 _E = importlib.import_module("ics-wt-physicsengine_amd").ReactorEnsemble
+_native = importlib.import_module("ics-wt-physicsengine_amd.core._native")
+
+
+def instantiation(n):
+    """(level, row mode) of the step kernel that serves ``n`` zones, as ``with_step_kernel`` in csrc/wtphys.hip picks
+    it: level = smallest l >= 1 with 2^l >= n, row mode for the zone counts that fill DPP rows exactly."""
+    level = 1
+    while (1 << level) < n:
+        level += 1
+    return level, n in (2, 4, 8, 16)
+
+
+def ragged_size(n, groups=5):
+    """(R, N): reactors per wavefront at ``n`` zones, and ``groups`` full wavefront-groups plus a last one that holds a
+    single reactor."""
+    R = 64 // n
+    return R, groups * R + 1
+
+
+def wavefront_groups(ens):
+    """Wavefront-groups the library deals the ensemble's reactors into (it spreads a small ensemble over more wavefronts
+    than 64 // n reactors each would need).  Ask after the last step: the call also switches the wave diagnostics on."""
+    import ctypes
+    nw = ctypes.c_int64(0)
+    _native.check(_native.lib().wt_ensemble_wave_diag(ens._h, None, 0, ctypes.byref(nw)))
+    return int(nw.value)
+
+
+def assert_equal_by_reactor(ref, got, what, R):
+    """``assert_all_equal`` for arrays whose last axis is the reactor: a mismatch names the reactors and, for the identity
+    placement, their (wavefront-group, slot)."""
+    for i, (a, b) in enumerate(zip(ref, got)):
+        a, b = np.asarray(a), np.asarray(b)
+        assert a.shape == b.shape, (what, i, a.shape, b.shape)
+        bad = ~((a == b) | (np.isnan(a) & np.isnan(b)))
+        if bad.any():
+            rs = np.unique(np.nonzero(bad)[-1])
+            raise AssertionError((what, i, "reactors", rs[:8].tolist(), "(group, slot)", [(int(r) // R, int(r) % R) for r in rs[:8]]))
 
 
 def plant(wt, cols, bc, n, seed=11, history=0):
