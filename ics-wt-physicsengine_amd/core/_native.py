@@ -20,6 +20,7 @@ LIB_PATH = os.environ.get("WTPHYS_LIB", os.path.join(CSRC, "libwtphys.so"))  # o
 WT_OK, WT_E_ARG, WT_E_HIP, WT_E_NOGPU, WT_E_STATE = 0, 1, 2, 3, 4
 WT_PROG_CONTROL, WT_PROG_INJECT, WT_PROG_ALARM, WT_PROG_ACTUATOR, WT_PROG_DISTURB, WT_PROG_SCORE = 0, 1, 2, 3, 4, 5   # wt_program_check
 WT_PROG_DETECT = 6
+WT_PROG_TREND = 7
 
 
 class WtError(RuntimeError):
@@ -38,7 +39,7 @@ class SolverStats(C.Structure):
 
 # what libwtphys.so is built from: wtphys.hip and exactly the headers it includes
 # (tests/test_host_api.py::test_build_staleness_list_matches_the_includes)
-BUILD_SOURCES = ("wtphys.hip", "wt_device.hpp", "wt_sensors.hpp", "wt_plc.hpp", "wt_ctl.hpp", "wt_inj.hpp", "wt_alm.hpp", "wt_det.hpp", "wt_act.hpp", "wt_dst.hpp", "wt_scr.hpp", "wt_diag.hpp", "wt_place.hpp")
+BUILD_SOURCES = ("wtphys.hip", "wt_device.hpp", "wt_sensors.hpp", "wt_plc.hpp", "wt_ctl.hpp", "wt_inj.hpp", "wt_alm.hpp", "wt_det.hpp", "wt_trd.hpp", "wt_act.hpp", "wt_dst.hpp", "wt_scr.hpp", "wt_diag.hpp", "wt_place.hpp")
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
@@ -155,6 +156,11 @@ def lib():
     L.wt_ensemble_detect_get.argtypes = [vp, dp, dp]
     L.wt_ensemble_detect_reset.argtypes = [vp]
     L.wt_ensemble_detect_clear.argtypes = [vp]
+    L.wt_ensemble_trend_set.argtypes = [vp, dp, C.c_int64, C.c_int]
+    L.wt_ensemble_trend_get.argtypes = [vp, dp]
+    L.wt_ensemble_trend_data.argtypes = [vp, dp, dp]
+    L.wt_ensemble_trend_reset.argtypes = [vp]
+    L.wt_ensemble_trend_clear.argtypes = [vp]
     L.wt_program_check.argtypes = [C.c_int, dp, C.c_int64]
     L.wt_ensemble_diagnostics.argtypes = [vp, dp]
     L.wt_ensemble_wave_diag.argtypes = [vp, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int64)]
@@ -178,7 +184,9 @@ def lib():
                  "wt_ensemble_actuator_clear", "wt_ensemble_disturb_set", "wt_ensemble_disturb_get",
                  "wt_ensemble_disturb_history", "wt_ensemble_disturb_clear", "wt_ensemble_score_set", "wt_ensemble_score_get",
                  "wt_ensemble_score_curve", "wt_ensemble_score_reset", "wt_ensemble_score_clear", "wt_ensemble_detect_set",
-                 "wt_ensemble_detect_get", "wt_ensemble_detect_reset", "wt_ensemble_detect_clear", "wt_program_check"):
+                 "wt_ensemble_detect_get", "wt_ensemble_detect_reset", "wt_ensemble_detect_clear", "wt_ensemble_trend_set",
+                 "wt_ensemble_trend_get", "wt_ensemble_trend_data", "wt_ensemble_trend_reset", "wt_ensemble_trend_clear",
+                 "wt_program_check"):
         getattr(L, name).restype = C.c_int
     if L.wt_abi_version() != 1:
         raise ImportError("libwtphys.so ABI version mismatch; rebuild it")

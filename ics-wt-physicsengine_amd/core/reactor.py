@@ -18,7 +18,7 @@ from typing import Dict, Iterable, List, Optional, Sequence, Union
 
 import numpy as np
 
-from . import _native, _program, actuator, alarm, control, detect, disturb, inject, params, score
+from . import _native, _program, actuator, alarm, control, detect, disturb, inject, params, score, trend
 
 logger = logging.getLogger(__name__)
 
@@ -275,6 +275,7 @@ class ReactorEnsemble:
         self._disturb_history = -1              # capacity of the disturbance program's history; -1: no program
         self._score_curve = None                # (capacity, bins, edges) of the score program's curve; None: no program
         self._detect_labels: Optional[np.ndarray] = None    # the label block of the detector program; None: no program
+        self._trend_capacity = 0                # samples per slot and reactor of the trend program's store; 0: no program
         self._control_params: Optional[np.ndarray] = None   # the last block enable_control / retune_control sent
 
     # -- lifetime
@@ -768,6 +769,44 @@ class ReactorEnsemble:
         """Stop the detector program and free its buffers."""
         self._control_call(_native.lib().wt_ensemble_detect_clear)
         self._detect_labels = None
+
+    # -- trend recorder programs at every PLC scan, on the device (wt_trd.hpp)
+    def set_trends(self, *trends: "trend.Trend", capacity: int, wrap: bool = False) -> None:
+        """Record up to eight :class:`Trend` slots at every PLC scan, inside the step call, last in the scan: each slot
+        appends (loop time, value) of one reading, fault code, command or entry of another program's state to a store
+        of ``capacity`` samples per slot and reactor.  A full store drops further samples (``trend_state().n_dropped``
+        counts them) or, with ``wrap``, overwrites the oldest.  The program is passive: the plant and the other
+        programs keep their bits.  Replaces any earlier program, its state and its data.  Needs plant I/O and at most
+        32 zones."""
+        blk = trend.trend_block(self.n_reactors, *trends)
+        self._control_call(_native.lib().wt_ensemble_trend_set, _native.dptr(blk), int(capacity), int(bool(wrap)))
+        self._trend_capacity = int(capacity)
+
+    def trend_state(self) -> "trend.TrendState":
+        """Slot state of the trend program (one synchronisation)."""
+        st = np.empty((trend.SLOTS, trend.NTS, self.n_reactors), dtype=np.float64)
+        self._control_call(_native.lib().wt_ensemble_trend_get, _native.dptr(st))
+        return trend.TrendState.from_block(st)
+
+    def trend_data(self) -> "trend.TrendData":
+        """The recorded series, oldest sample first (a wrapped store is unwrapped), NaN past the samples held."""
+        st = np.empty((trend.SLOTS, trend.NTS, self.n_reactors), dtype=np.float64)
+        self._control_call(_native.lib().wt_ensemble_trend_get, _native.dptr(st))
+        t = np.empty((trend.SLOTS, self._trend_capacity, self.n_reactors), dtype=np.float64)
+        x = np.empty_like(t)
+        self._control_call(_native.lib().wt_ensemble_trend_data, _native.dptr(t), _native.dptr(x))
+        count = np.minimum(st[:, trend.STATE_ROWS.index("n_recorded")], self._trend_capacity).astype(np.int64)
+        return trend.TrendData(t, x, count)
+
+    def reset_trends(self) -> None:
+        """Slot state and data back to their values at :meth:`set_trends`; the slots, the capacity and ``wrap`` stay
+        (recording after a warm-up)."""
+        self._control_call(_native.lib().wt_ensemble_trend_reset)
+
+    def clear_trends(self) -> None:
+        """Stop the trend program and free its buffers."""
+        self._control_call(_native.lib().wt_ensemble_trend_clear)
+        self._trend_capacity = 0
 
     # -- score programs after every outer step, on the device (wt_scr.hpp)
     def set_scores(self, *scores: "score.Score", curve: int = 0, bins: int = 0, fan_range=None) -> None:

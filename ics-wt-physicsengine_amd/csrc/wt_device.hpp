@@ -41,6 +41,7 @@
 #include "wt_inj.hpp"
 #include "wt_alm.hpp"
 #include "wt_det.hpp"
+#include "wt_trd.hpp"
 #include "wt_act.hpp"
 #include "wt_dst.hpp"
 #include "wt_scr.hpp"
@@ -317,15 +318,16 @@ struct StepArgs {
     wtd::DstArgs dst;    // per-reactor disturbance programs run after every outer step (wt_ensemble_disturb_*; dst.on == 0: none)
     wtsc::ScrArgs scr;   // per-reactor score programs run after every outer step (wt_ensemble_score_*; scr.on == 0: none)
     wtk::DetArgs det;    // per-reactor anomaly detector programs run at PLC scans (wt_ensemble_detect_*; det.on == 0: none)
+    wtt::TrdArgs trd;    // per-reactor trend recorder programs run at PLC scans (wt_ensemble_trend_*; trd.on == 0: none)
 };
 static_assert(sizeof(StepArgs) <= 4096, "the kernel-argument segment holds at most 4 KiB");
 constexpr int NB = 10;     // rows of a boundary block (WT_NB)
 // kernels that record and reload the schedule inside a work item (n <= 32); the others take one outer step per launch
 __host__ __device__ constexpr bool x_in_item(int LV) { return LV <= 5; }
-// kernels that carry the injection, alarm, actuator, disturbance, score and detector sections (wt_inj.hpp, wt_alm.hpp,
-// wt_act.hpp, wt_dst.hpp, wt_scr.hpp, wt_det.hpp).  The n > 32 kernel has no register for them: every variant tried cost it 8 B of
+// kernels that carry the injection, alarm, actuator, disturbance, score, detector and trend recorder sections (wt_inj.hpp,
+// wt_alm.hpp, wt_act.hpp, wt_dst.hpp, wt_scr.hpp, wt_det.hpp, wt_trd.hpp).  The n > 32 kernel has no register for them: every variant tried cost it 8 B of
 // scratch and 4 VGPR spills, with or without a program, so it compiles the sections out and wt_ensemble_inject_set,
-// _alarm_set, _actuator_set, _disturb_set, _score_set and _detect_set refuse ensembles of more than 32 zones.
+// _alarm_set, _actuator_set, _disturb_set, _score_set, _detect_set and _trend_set refuse ensembles of more than 32 zones.
 __host__ __device__ constexpr bool prog_in_item(int LV) { return LV <= 5; }
 enum { Q_AVAIL = 0, Q_HEAD = 1, Q_TAIL = 2, Q_ERROR = 3, Q_TRACE = 4, Q_DONE = 5, Q_WORDS = 16 };
 
@@ -2457,13 +2459,21 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
                     wta::evaluate(ap->alm, rr, ap->sens.N, &io.val[0][lane], &io.fault[0][lane], wts::RMAX, ap->sens.out_value,
                                   ap->sens.out_fault, ap->sens.pack.loop_time[rr]);
                 }
-                // the detector program, last in the scan: the same inputs as the alarm program's, its own arrays only
+                // the detector program, after the alarm program: the same inputs as the alarm program's, its own arrays only
                 if constexpr (prog_in_item(LV)) {
                   if (scan && WT_RARE(fresh(pa)->det.on) && lane < R && io.stepped[lane]) {
                     ArgPtr dp = fresh(pa);
                     const int64_t rr = rix[lane];
                     wtk::evaluate(dp->det, rr, dp->sens.N, &io.val[0][lane], &io.fault[0][lane], wts::RMAX, dp->sens.out_value,
                                   dp->sens.out_fault, dp->sens.pack.loop_time[rr]);
+                  }
+                }
+                // the trend recorder, last in the scan: what this lane's programs left in their records, its own arrays only
+                if constexpr (prog_in_item(LV)) {
+                  if (scan && WT_RARE(fresh(pa)->trd.on) && lane < R && io.stepped[lane]) {
+                    ArgPtr tp = fresh(pa);
+                    const int64_t rr = rix[lane];
+                    wtt::record(*tp, rr, &io.val[0][lane], &io.fault[0][lane], &io.cmd[0][lane], wts::RMAX, tp->sens.pack.loop_time[rr]);
                   }
                 }
                 if (scan) {

@@ -103,6 +103,8 @@ struct wt_ensemble {
     int64_t scr_steps = 0;
     // det: the per-reactor anomaly detector program (wt_det.hpp), evaluated last in every PLC scan
     wtk::DetArgs det = {};
+    // trd: the per-reactor trend recorder program (wt_trd.hpp), run last in every PLC scan
+    wtt::TrdArgs trd = {};
     // optional per-launch HIP-event timing (bench.py roofline accounting)
     bool time_launches = false;
     std::vector<hipEvent_t> lt_pool;   // start/stop pairs
@@ -139,7 +141,7 @@ wt::StepArgs make_args(const wt_ensemble *h, double dt, int n_steps, int first_s
     a.trace = h->trace; a.trace_cap = h->trace_cap;
     a.kt = wt::default_ktab(); a.rt = wt::default_rtab();
     a.kt.dense_bias = h->knob_dense ? 1.0 : 0.0;
-    a.sens = h->sens; a.ctl = h->ctl; a.inj = h->inj; a.alm = h->alm; a.act = h->act; a.dst = h->dst; a.scr = h->scr; a.det = h->det;
+    a.sens = h->sens; a.ctl = h->ctl; a.inj = h->inj; a.alm = h->alm; a.act = h->act; a.dst = h->dst; a.scr = h->scr; a.det = h->det; a.trd = h->trd;
     // a full curve takes no more entries: the launches then carry no curve pointer at all
     const bool curve = h->scr.counts && h->scr_steps < h->scr.curve_cap;
     if (!curve) a.scr.counts = nullptr;
@@ -299,7 +301,16 @@ ArrayGroup detect_arrays(wt_ensemble *h)
                                    {(void **)&h->det.tp, sizeof(double) * N}}};
 }
 
-// the body of control_disable, inject_clear, alarm_clear, actuator_clear, score_clear and detect_clear
+// cap: samples per slot and reactor of the store
+ArrayGroup trend_arrays(wt_ensemble *h, int64_t cap)
+{
+    const size_t N = (size_t)h->N;
+    return {"trend", &h->trd.on, {{(void **)&h->trd.par, sizeof(double) * wtt::PAR_DOUBLES * N},
+                                  {(void **)&h->trd.st, sizeof(double) * wtt::ST_DOUBLES * N},
+                                  {(void **)&h->trd.store, sizeof(double2) * wtt::SLOTS * (size_t)cap * N}}};
+}
+
+// the body of control_disable, inject_clear, alarm_clear, actuator_clear, score_clear, detect_clear and trend_clear
 int stop_program(wt_ensemble *h, const ArrayGroup &g)
 {
     HIP_TRY(hipSetDevice(h->device));
@@ -560,7 +571,8 @@ int wt_ensemble_destroy(wt_ensemble *h)
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     for (const ArrayGroup &g : {core_arrays(h), sensor_arrays(h, h->sens.hist_cap), plant_io_arrays(h), record_arrays(h, 0),
                                 control_arrays(h), inject_arrays(h), alarm_arrays(h), actuator_arrays(h),
-                                disturb_arrays(h, h->dst.hist_cap), score_arrays(h, h->scr.curve_cap, h->scr.bins), detect_arrays(h)})
+                                disturb_arrays(h, h->dst.hist_cap), score_arrays(h, h->scr.curve_cap, h->scr.bins), detect_arrays(h),
+                                trend_arrays(h, h->trd.cap)})
         release(g);
     free_and_null(h->trace); free_and_null(h->wave_diag); free_and_null(h->snap_dev); free_and_null(h->sched);
     free_and_null(h->diag_out);
@@ -1787,6 +1799,139 @@ int wt_ensemble_detect_clear(wt_ensemble *h)
     return stop_program(h, detect_arrays(h));
 }
 
+} // extern "C"
+
+namespace {
+
+static_assert(WT_TRD_SLOTS == wtt::SLOTS && WT_NT == wtt::NT && WT_NTS == wtt::NTS, "trend blocks of the C ABI");
+static_assert(WT_TRD_IMAGE_VALUE == wtt::G_IMAGE_VALUE && WT_TRD_FIELD_FAULT == wtt::G_FIELD_FAULT && WT_TRD_COMMAND == wtt::G_COMMAND &&
+              WT_TRD_CONTROL == wtt::G_CONTROL && WT_TRD_INJECT == wtt::G_INJECT && WT_TRD_ALARM == wtt::G_ALARM &&
+              WT_TRD_ALARM_WORD == wtt::G_ALARM_WORD && WT_TRD_ACTUATOR == wtt::G_ACTUATOR && WT_TRD_DETECT == wtt::G_DETECT &&
+              WT_TRD_DETECT + 1 == wtt::N_TAGS, "trend tags of the C ABI");
+static_assert(WT_T_T_END == wtt::T_T_END && WT_TS_LAST == wtt::TS_LAST, "trend rows of the C ABI");
+static_assert(wtt::NT % 2 == 0 && wtt::NTS % 2 == 0, "the recorder's records are read in 16-byte pairs");
+static_assert(wtt::index_range(wtt::G_IMAGE_VALUE) == WT_N_SENSORS && wtt::index_range(wtt::G_CONTROL) == WT_CTL_LOOPS * WT_NCS &&
+              wtt::index_range(wtt::G_INJECT) == WT_INJ_SLOTS * WT_NIS && wtt::index_range(wtt::G_ALARM) == WT_ALM_SLOTS * WT_NAS &&
+              wtt::index_range(wtt::G_ACTUATOR) == WT_ACT_CHANNELS * WT_NVS && wtt::index_range(wtt::G_DETECT) == WT_DET_SLOTS * WT_NKS,
+              "a trend index names an entry of the block the program's get call returns");
+// COMMAND channels in WT_INJ_CMD_* order
+static_assert(WT_INJ_CMD_ACID + 1 == WT_INJ_CMD_CHLORINE && WT_INJ_CMD_CHLORINE + 1 == WT_INJ_CMD_INLET, "acid, chlorine, inlet");
+
+// Host-side checks of a [WT_TRD_SLOTS][WT_NT][N] program; nullptr when it is valid.
+const char *trend_params_error(const double *p, int64_t N)
+{
+    for (int s = 0; s < wtt::SLOTS; ++s)
+        for (int64_t r = 0; r < N; ++r) {
+            double c[wtt::NT];
+            for (int k = 0; k < wtt::NT; ++k) c[k] = p[((int64_t)s * wtt::NT + k) * N + r];
+            const double tag = c[wtt::T_TAG], index = c[wtt::T_INDEX], every = c[wtt::T_EVERY];
+            if (!(tag == std::floor(tag) && tag >= 0 && tag <= wtt::N_TAGS - 1)) return "tag must be an integer in 0..11 (0: off)";
+            if (tag == wtt::G_OFF) continue;                       // the other rows of an OFF slot are not read
+            if (!(index == std::floor(index) && index >= 0 && index < wtt::index_range((int)tag)))
+                return "index must be an integer within the tag's range";
+            if (!(every == std::floor(every) && every >= 1 && every < 9007199254740992.0)) return "every must be an integer >= 1";
+            if (std::isnan(c[wtt::T_DEADBAND])) return "deadband must not be NaN (negative: every candidate is recorded)";
+            if (std::isnan(c[wtt::T_T_START]) || std::isnan(c[wtt::T_T_END])) return "t_start and t_end must not be NaN";
+            if (!(c[wtt::T_T_END] >= c[wtt::T_T_START])) return "t_end must be >= t_start";
+        }
+    return nullptr;
+}
+
+const char *k_no_trend = "no trend program is set (wt_ensemble_trend_set)";
+
+// Slot state at its set-time values (0, 0, 0, NaN) and an all-NaN store: on the handle's stream, synchronised.
+int trend_restart(wt_ensemble *h)
+{
+    const int64_t N = h->N;
+    std::vector<double> st((size_t)N * wtt::ST_DOUBLES, 0.0);
+    for (int64_t i = 0; i < N * wtt::SLOTS; ++i) st[(size_t)i * wtt::NTS + wtt::TS_LAST] = NAN;
+    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still write the old records
+    HIP_TRY(hipMemcpyAsync(h->trd.st, st.data(), sizeof(double) * st.size(), hipMemcpyHostToDevice, h->stream));
+    // every byte 0xff: a NaN in both halves of every sample
+    HIP_TRY(hipMemsetAsync(h->trd.store, 0xff, sizeof(double2) * wtt::SLOTS * (size_t)h->trd.cap * (size_t)N, h->stream));
+    return sync_checked(h);                     // the host vector is freed on return
+}
+
+} // namespace
+
+extern "C" {
+
+int wt_ensemble_trend_set(wt_ensemble *h, const double *params, int64_t capacity, int wrap)
+{
+    if (int rc = check_program_set(h, params, WT_PROG_TREND, "trends read the plant I/O scan: enable plant I/O first",
+                                   "trend programs run in the kernels for up to 32 zones"))
+        return rc;
+    if (capacity < 1) return fail(WT_E_ARG, "capacity must be >= 1");
+    int64_t bytes = 0;
+    if (__builtin_mul_overflow(capacity, (int64_t)(wtt::SLOTS * sizeof(double2)), &bytes) || __builtin_mul_overflow(bytes, h->N, &bytes))
+        return fail(WT_E_ARG, "store size overflows int64");
+    const int64_t N = h->N;
+    if (int rc = stop_program(h, trend_arrays(h, h->trd.cap))) return rc;   // set replaces any program (and its capacity)
+    h->trd.cap = 0;
+    std::vector<double> par((size_t)N * wtt::PAR_DOUBLES);
+    blocks_to_records(params, wtt::SLOTS, wtt::NT, N, par.data(), wtt::PAR_DOUBLES);
+    if (int rc = allocate(trend_arrays(h, capacity))) return rc;
+    h->trd.cap = capacity; h->trd.wrap = wrap ? 1 : 0;
+    HIP_TRY(hipMemcpyAsync((double *)h->trd.par, par.data(), sizeof(double) * par.size(), hipMemcpyHostToDevice, h->stream));
+    if (int rc = trend_restart(h)) {
+        release(trend_arrays(h, h->trd.cap));
+        h->trd.cap = 0;
+        return rc;
+    }
+    h->trd.on = 1;
+    return WT_OK;
+}
+
+int wt_ensemble_trend_get(wt_ensemble *h, double *slot_state)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    if (!h->trd.on) return fail(WT_E_STATE, k_no_trend);
+    HIP_TRY(hipSetDevice(h->device));
+    return download_records(h, {{slot_state, h->trd.st, wtt::ST_DOUBLES, wtt::SLOTS, wtt::NTS}});
+}
+
+int wt_ensemble_trend_data(wt_ensemble *h, double *time, double *value)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    if (!h->trd.on) return fail(WT_E_STATE, k_no_trend);
+    HIP_TRY(hipSetDevice(h->device));
+    const int64_t N = h->N, cap = h->trd.cap;
+    std::vector<double> st((size_t)N * wtt::ST_DOUBLES);
+    std::vector<double2> store((size_t)N * wtt::SLOTS * (size_t)cap);
+    if (int rc = download(h, {{st.data(), h->trd.st, sizeof(double) * st.size()}, {store.data(), h->trd.store, sizeof(double2) * store.size()}}))
+        return rc;
+    for (int64_t r = 0; r < N; ++r)
+        for (int s = 0; s < wtt::SLOTS; ++s) {
+            const double n_rec = st[(size_t)((r * wtt::SLOTS + s) * wtt::NTS + wtt::TS_N_RECORDED)];
+            const int64_t held = n_rec < (double)cap ? (int64_t)n_rec : cap;
+            const int64_t first = n_rec > (double)cap ? (int64_t)std::fmod(n_rec, (double)cap) : 0;   // the oldest sample of a wrapped ring
+            const double2 *ring = store.data() + (size_t)((r * wtt::SLOTS + s) * cap);
+            for (int64_t k = 0; k < cap; ++k) {
+                const double2 v = k < held ? ring[(first + k) % cap] : make_double2(NAN, NAN);
+                const size_t o = (size_t)(((int64_t)s * cap + k) * N + r);
+                if (time) time[o] = v.x;
+                if (value) value[o] = v.y;
+            }
+        }
+    return WT_OK;
+}
+
+int wt_ensemble_trend_reset(wt_ensemble *h)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    if (!h->trd.on) return fail(WT_E_STATE, k_no_trend);
+    HIP_TRY(hipSetDevice(h->device));
+    return trend_restart(h);
+}
+
+int wt_ensemble_trend_clear(wt_ensemble *h)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    if (int rc = stop_program(h, trend_arrays(h, h->trd.cap))) return rc;
+    h->trd.cap = 0;
+    return WT_OK;
+}
+
 int wt_program_check(int program, const double *params, int64_t n_reactors)
 {
     if (!params) return fail(WT_E_ARG, "params is NULL");
@@ -1800,6 +1945,7 @@ int wt_program_check(int program, const double *params, int64_t n_reactors)
     case WT_PROG_DISTURB: msg = disturb_params_error(params, n_reactors); break;
     case WT_PROG_SCORE: msg = score_params_error(params, n_reactors); break;
     case WT_PROG_DETECT: msg = detect_params_error(params, n_reactors); break;
+    case WT_PROG_TREND: msg = trend_params_error(params, n_reactors); break;
     default: return fail(WT_E_ARG, "unknown program");
     }
     return msg ? fail(WT_E_ARG, msg) : WT_OK;

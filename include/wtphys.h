@@ -628,16 +628,75 @@ int wt_ensemble_detect_reset(wt_ensemble *h);
 /* program off, buffers freed (no effect while none is set) */
 int wt_ensemble_detect_clear(wt_ensemble *h);
 
+/* ---- per-reactor trend recorder programs: the historian, a time series per slot at the PLC scan rate ----
+ * A fused call returns end-of-call state.  The series a study plots at the scan rate -- a PI output, a detector's
+ * statistic, valve position against command, the alarm word -- are recorded inside the call: up to WT_TRD_SLOTS slots
+ * per reactor each take one value of every scan, thin it and append (time, value) to a store of `capacity` samples per
+ * slot and reactor.  The program is passive (it writes its own arrays only) and its values are copies, so a series is
+ * bit for bit what a host loop of one call per scan reads from the getters named below.
+ * Parameters [WT_TRD_SLOTS][WT_NT][N]: tag, index, every (whole, >= 1: a candidate every that many scans seen), deadband
+ * (< 0: every candidate is recorded; otherwise only a value that differs from the last recorded one by more than it;
+ * not NaN), t_start, t_end (the slot sees a scan while t_start <= t < t_end; neither NaN, t_end >= t_start, both may be
+ * infinite).  The rows of an OFF slot after tag are not read and not checked.  Otherwise WT_E_ARG.
+ * tag and the entries index selects (a whole number in the range given), the value taken as fp64:
+ *   0 OFF
+ *   1 IMAGE_VALUE  sensor 0..6 (WT_N_SENSORS order): this scan's copy of the reading after any injection program
+ *   2 IMAGE_FAULT  sensor 0..6: its fault code
+ *   3 FIELD_VALUE  sensor 0..6: the instrument's own reading of this step (wt_ensemble_sensors_get)
+ *   4 FIELD_FAULT  sensor 0..6: its fault code
+ *   5 COMMAND      channel 0 acid, 1 chlorine, 2 inlet (WT_INJ_CMD_* order): what this scan hands to the plant, the
+ *                  value rows 4 / 6 / 0 of wt_ensemble_get_boundary hold after a call that ends at this scan
+ *   6 CONTROL      loop * WT_NCS + row: that entry of the wt_ensemble_control_get block at the end of this scan
+ *   7 INJECT       slot * WT_NIS + row: likewise of wt_ensemble_inject_get
+ *   8 ALARM        slot * WT_NAS + row: likewise of the slot state of wt_ensemble_alarm_get
+ *   9 ALARM_WORD   0: the reactor's alarm word (wt_ensemble_alarm_words)
+ *  10 ACTUATOR     channel * WT_NVS + row: likewise of the channel state of wt_ensemble_actuator_get
+ *  11 DETECT       slot * WT_NKS + row: likewise of the slot state of wt_ensemble_detect_get
+ * Tags 6-11 read another program's record; while that program is off the value is NaN.
+ * Slot state [WT_TRD_SLOTS][WT_NTS][N]: n_seen, n_recorded, n_dropped, last.  set gives 0, 0, 0, NaN.
+ * At every PLC scan of a reactor that stepped, after every other program of the scan (last in the scan), with t = the
+ * loop time the scan stores, for each slot ascending with tag != OFF and t_start <= t < t_end:
+ *   n_seen += 1;  the scan is a candidate if (n_seen - 1) % every == 0
+ *   x = the tag's value;  a candidate is taken if n_recorded == 0, or deadband < 0, or
+ *       (x == x || last == last) && !(fabs(x - last) <= deadband)       (NaN to NaN: no change; NaN to or from a number: a change)
+ *   a sample taken: wrap == 0 and n_recorded == capacity: n_dropped += 1, nothing stored;
+ *                   otherwise (t, x) goes to position n_recorded % capacity (wrap != 0 overwrites the oldest) and n_recorded += 1;
+ *                   last = x either way, so the deadband thins the same at any capacity
+ * n_recorded counts the samples stored or overwritten; min(n_recorded, capacity) are held.  Reactors that did not step
+ * and slots outside their window change nothing.  set replaces any program.  Needs plant I/O and n <= 32 zones
+ * (WT_E_STATE); all calls synchronise. */
+#define WT_TRD_SLOTS 8
+enum {
+    WT_TRD_OFF = 0, WT_TRD_IMAGE_VALUE = 1, WT_TRD_IMAGE_FAULT = 2, WT_TRD_FIELD_VALUE = 3, WT_TRD_FIELD_FAULT = 4,
+    WT_TRD_COMMAND = 5, WT_TRD_CONTROL = 6, WT_TRD_INJECT = 7, WT_TRD_ALARM = 8, WT_TRD_ALARM_WORD = 9, WT_TRD_ACTUATOR = 10,
+    WT_TRD_DETECT = 11
+};
+enum { WT_T_TAG = 0, WT_T_INDEX = 1, WT_T_EVERY = 2, WT_T_DEADBAND = 3, WT_T_T_START = 4, WT_T_T_END = 5, WT_NT = 6 };
+enum { WT_TS_N_SEEN = 0, WT_TS_N_RECORDED = 1, WT_TS_N_DROPPED = 2, WT_TS_LAST = 3, WT_NTS = 4 };
+/* capacity >= 1 samples per slot and reactor (WT_E_ARG otherwise, or if the store's size overflows int64) */
+int wt_ensemble_trend_set(wt_ensemble *h, const double *params /* [WT_TRD_SLOTS][WT_NT][N] */, int64_t capacity, int wrap);
+/* host [WT_TRD_SLOTS][WT_NTS][N] slot state; WT_E_STATE while no program is set */
+int wt_ensemble_trend_get(wt_ensemble *h, double *slot_state);
+/* host [WT_TRD_SLOTS][capacity][N] each (either may be NULL): every slot's samples in chronological order (a wrapped ring
+ * is unwrapped: row k is the k-th oldest sample held); rows past the number held are NaN in both arrays.  WT_E_STATE
+ * while no program is set */
+int wt_ensemble_trend_data(wt_ensemble *h, double *time, double *value);
+/* slot state and store as after set; the parameters, capacity and wrap stay (recording after a warm-up); WT_E_STATE
+ * while no program is set */
+int wt_ensemble_trend_reset(wt_ensemble *h);
+/* program off, buffers freed (no effect while none is set) */
+int wt_ensemble_trend_clear(wt_ensemble *h);
+
 /* ---- the parameter checks of the scan programs, the disturbance and the score program, without a handle or a device ----
  * params: host, the block the program's set or enable call takes, for n_reactors reactors (WT_PROG_CONTROL:
  * wt_ensemble_control_enable / retune, WT_PROG_INJECT: wt_ensemble_inject_set, WT_PROG_ALARM: wt_ensemble_alarm_set,
  * WT_PROG_ACTUATOR: wt_ensemble_actuator_set, WT_PROG_DISTURB: wt_ensemble_disturb_set, WT_PROG_SCORE:
  * wt_ensemble_score_set, WT_PROG_DETECT: the slot block of wt_ensemble_detect_set, whose label block that call checks
- * itself).  WT_OK when the block passes that call's checks; otherwise WT_E_ARG
+ * itself, WT_PROG_TREND: wt_ensemble_trend_set).  WT_OK when the block passes that call's checks; otherwise WT_E_ARG
  * and wt_last_error() is the message the call gives for it.  A NULL params, n_reactors < 1 or an unknown program
  * also give WT_E_ARG.  Makes no HIP call. */
 enum { WT_PROG_CONTROL = 0, WT_PROG_INJECT = 1, WT_PROG_ALARM = 2, WT_PROG_ACTUATOR = 3, WT_PROG_DISTURB = 4, WT_PROG_SCORE = 5,
-       WT_PROG_DETECT = 6 };
+       WT_PROG_DETECT = 6, WT_PROG_TREND = 7 };
 int wt_program_check(int program, const double *params, int64_t n_reactors);
 
 /* ---- reactor diagnostics (SURVEY.md section 8(f) NEXT-4): reductions over the zones of every reactor ----

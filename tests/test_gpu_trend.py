@@ -1,0 +1,301 @@
+"""Per-reactor trend recorder programs at every PLC scan (include/wtphys.h ``wt_ensemble_trend_*``): what one fused call
+records is, bit for bit, what a host loop of one call per scan reads from the public getters and thins with the
+restatement in trend_ref.py; the program changes nothing else; its data depend on the scan times only."""
+import ctypes
+
+import numpy as np
+import pytest
+
+import trend_ref as TR
+from inject_ref import InjectRef
+from program_helpers import DT, MASTER, HostScan, assert_all_equal, assert_equal_by_reactor, instantiation, pi_loops, plant, plant_state, ragged_size
+from trend_ref import TrendRef
+
+pytestmark = pytest.mark.gpu
+
+STEPS, CHUNK = 40, 4               # ten scans, at 40, 80, ... 400 s
+HORIZON = STEPS * DT
+CAPACITY = 16
+
+
+@pytest.fixture
+def full_waves(monkeypatch):
+    """Packs 64 // n reactors into every wavefront, as a large ensemble is packed (WT_FULL_WAVES is read when an
+    ensemble is created); without it a small ensemble is spread over one wavefront per reactor."""
+    monkeypatch.setenv("WT_FULL_WAVES", "1")
+
+
+def _injections(wt, N):
+    r = np.arange(N)
+    return [wt.Injection("chlorine_outlet", "bias", start=0.2 * HORIZON, end=0.6 * HORIZON, a=0.8),
+            wt.Injection("flow_main", np.where(r % 2 == 0, "fault", "off"), start=0.3 * HORIZON, end=0.7 * HORIZON, a=3.0),
+            wt.Injection("chlorine_flow_rate", "gain", start=0.5 * HORIZON, end=0.8 * HORIZON, a=0.5)]
+
+
+def _closed(wt, cols, bc, n):
+    """Plant I/O with both PI loops and one program each of injection, alarm, actuator and detector."""
+    N = len(cols["initial_chlorine"])
+    ens = plant(wt, cols, bc, n)
+    ens.set_placement(False)
+    ens.set_schedule(0, CHUNK)
+    ens.write_commands(*MASTER)
+    ens.enable_control(*pi_loops(wt, cols))
+    ens.set_injections(*_injections(wt, N))
+    ens.set_alarms(wt.Alarm("chlorine_outlet", "low", 1.0, deadband=0.1, source="field", action="trip_chlorine", trip_value=0.6),
+                   wt.Alarm("flow_main", "high", 50.0, on_bad="alarm"))      # stands while the flow reading is faulted
+    ens.set_actuators(wt.Actuator("chlorine", tau=40.0, rate=0.05), wt.Actuator("acid", delay=2))
+    lim = np.geomspace(0.5, 5.0, N)
+    ens.set_detectors(wt.Detector("chlorine_outlet", "cusum", lim, sigma=0.05, ref="track", tau=100.0),
+                      wt.Detector("chlorine_outlet", "cusum", lim, sigma=0.05, ref="chlorine_outlet", ref_source="field"),
+                      attack=(0.2 * HORIZON, 0.6 * HORIZON))
+    return ens
+
+
+def _trends(wt, N):
+    """All eight slots and all eleven tags: per-reactor tags and indices, every 1 and 3, a deadband, a window that opens
+    mid-run, and a slot that records changes only."""
+    r = np.arange(N)
+    return [wt.Trend("image_value", "chlorine_outlet"),
+            wt.Trend(np.choose(r % 3, [TR.IMAGE_FAULT, TR.FIELD_FAULT, TR.FIELD_VALUE]), np.choose(r % 3, [4, 4, r % 7]), every=3),
+            wt.Trend("command", r % 3, deadband=0.0),
+            wt.Trend("control", ("chlorine", "output"), t_start=0.4 * HORIZON - 5.0),
+            wt.Trend(np.choose(r % 2, [TR.INJECT, TR.ALARM]), np.choose(r % 2, [0 * 4 + 0, 0 * 8 + 6]), every=np.choose(r % 4 // 2, [1, 3])),
+            wt.Trend("alarm_word", deadband=0.0),
+            wt.Trend("actuator", ("chlorine", "position"), deadband=np.where(r % 2 == 0, 0.0, 0.5), t_end=0.9 * HORIZON),
+            wt.Trend("detect", (r % 2, "stat"), every=3)]
+
+
+def _values(ens, image):
+    """Every tag's values at the scan that closed the last call, from the public getters (and the image the scan saw)."""
+    N = ens.n_reactors
+    v, _, f = ens.sensor_readings()
+    vt, ft = image(v, f)
+    return {TR.IMAGE_VALUE: vt.astype(np.float64), TR.IMAGE_FAULT: ft.astype(np.float64), TR.FIELD_VALUE: v.astype(np.float64),
+            TR.FIELD_FAULT: f.astype(np.float64), TR.COMMAND: ens.boundary()[[4, 6, 0]],
+            TR.CONTROL: ens.control_state().block().reshape(-1, N), TR.INJECT: ens.injection_state().block().reshape(-1, N),
+            TR.ALARM: ens.alarm_state().block()[0].reshape(-1, N), TR.ALARM_WORD: ens.alarm_words().astype(np.float64),
+            TR.ACTUATOR: ens.actuator_state().block()[0].reshape(-1, N), TR.DETECT: ens.detector_state().block()[0].reshape(-1, N)}
+
+
+def _data(ens):
+    d = ens.trend_data()
+    return d.time, d.value, d.count, ens.trend_state().block()
+
+
+@pytest.mark.parametrize("n", [4, 8, 20, 32])
+def test_fused_call_equals_the_host_loop(gpu, wt, full_waves, n):
+    R, N = ragged_size(n)
+    assert instantiation(n) in ((2, True), (3, True), (5, False))
+    cols, bc = wt.make_ensemble(N, seed=1500 + n)
+    trends = _trends(wt, N)
+    # the host loop: a call per scan interval on an ensemble without trends, the getters after each, the restatement
+    ens = _closed(wt, cols, bc, n)
+    ref = TrendRef(wt.trend_block(N, *trends), CAPACITY)
+    hs = HostScan(N, inj=InjectRef(wt.injection_block(N, *_injections(wt, N))))
+    seen = {}
+    for c in hs.calls(STEPS, CHUNK):
+        ens.step(DT, n_steps=c, download=False)
+        vals = _values(ens, hs.scan)
+        ref.scan(vals, hs.lt)
+        for tag, x in vals.items():
+            seen.setdefault(tag, []).append(np.array(x))
+    assert not ens.state.status.any() and np.all(ens.state.time == HORIZON)
+    ens.close()
+    # one fused call with the recorder on
+    ens = _closed(wt, cols, bc, n)
+    ens.set_trends(*trends, capacity=CAPACITY)
+    ens.step(DT, n_steps=STEPS, download=False)
+    time, value, count, state = _data(ens)
+    d = ens.trend_data()
+    ens.close()
+    rt, rx, rc = ref.data()
+    assert_equal_by_reactor((rc, ref.st[:, TR.TS_N_SEEN], ref.st[:, TR.TS_N_RECORDED], ref.st[:, TR.TS_N_DROPPED], ref.st[:, TR.TS_LAST]),
+                            (count, state[:, 0], state[:, 1], state[:, 2], state[:, 3]), (n, "state"), R)
+    assert_equal_by_reactor((rt, rx), (time, value), (n, "data"), R)
+    t, x = d.series(0, N - 1)
+    assert np.array_equal(t, CHUNK * DT * np.arange(1, 11)) and np.array_equal(x, rx[0, :10, N - 1], equal_nan=True)
+    # non-vacuity, on the expectation: every tag moved, the thinning thinned, nothing was dropped
+    scans = STEPS // CHUNK
+    assert np.all(rc[0] == scans) and np.all(rc[1] == 4) and np.all(rc[3] == 7) and np.all(rc[7] == 4) and not ref.st[:, TR.TS_N_DROPPED].any()
+    assert np.all(rt[3, 0] == 0.4 * HORIZON) and np.all(ref.st[6, TR.TS_N_SEEN] == 8)
+    print("samples held per slot (min, max)", n, [(int(c.min()), int(c.max())) for c in rc])
+    assert (rc[2] < scans).any() and (rc[5] < scans).any() and (rc[5] > 1).any() and (rc[6] < 8).any() and (rc[6] > 1).any()
+    for tag, series in seen.items():
+        s = np.nan_to_num(np.array(series))
+        assert tag == TR.FIELD_FAULT or (s != s[0]).any(), (n, tag)          # (the instruments may run without a fault of their own)
+
+
+def _everything(ens):
+    return (plant_state(ens) + ens.input_image() + (ens.control_state().block(), ens.injection_state().block(), ens.alarm_words())
+            + tuple(ens.alarm_state().block()) + tuple(ens.actuator_state().block()) + tuple(ens.detector_state().block()))
+
+
+@pytest.mark.parametrize("n", [8, 20])
+def test_changes_nothing(gpu, wt, full_waves, n):
+    R, N = ragged_size(n)
+    cols, bc = wt.make_ensemble(N, seed=1600 + n)
+    outs = []
+    for variant in ("none", "eight", "off", "cleared"):
+        ens = _closed(wt, cols, bc, n)
+        if variant == "eight":
+            ens.set_trends(*_trends(wt, N), capacity=3, wrap=True)
+        elif variant == "off":
+            ens.set_trends(*[wt.Trend("off", np.arange(N) % 7)] * 8, capacity=2)
+        elif variant == "cleared":
+            ens.set_trends(*_trends(wt, N), capacity=CAPACITY)
+            ens.clear_trends()
+        ens.step(DT, n_steps=STEPS, download=False)
+        outs.append(_everything(ens))
+        if variant == "eight":
+            assert np.all(ens.trend_state().n_recorded[0] == STEPS // CHUNK) and np.all(ens.trend_data().count[0] == 3)
+        elif variant == "off":
+            assert not np.nan_to_num(ens.trend_state().block()).any() and not ens.trend_data().count.any()
+        ens.close()
+    assert not outs[0][5].any()
+    for v, o in zip(("eight", "off", "cleared"), outs[1:]):
+        assert_all_equal(outs[0], o, (n, v))
+
+
+def test_schedules_placement_and_calls(gpu, wt):
+    N, n = 600, 8
+    cols, bc = wt.make_ensemble(N, seed=1700)
+    trends = _trends(wt, N)
+
+    def run(calls=(STEPS,), streams=0, adaptive=False, capacity=64, wrap=False, warm_up=0, reset=False):
+        ens = _closed(wt, cols, bc, n)
+        ens.set_placement(adaptive)
+        ens.set_schedule(streams, CHUNK)
+        if warm_up and not reset:
+            ens.step(DT, n_steps=warm_up, download=False)
+        ens.set_trends(*trends, capacity=capacity, wrap=wrap)
+        if warm_up and reset:
+            ens.step(DT, n_steps=warm_up, download=False)
+            assert ens.trend_state().n_seen[0].all()
+            ens.reset_trends()
+            assert not np.nan_to_num(ens.trend_state().block()).any() and not ens.trend_data().count.any()
+        for c in calls:
+            ens.step(DT, n_steps=c, download=False)
+        if adaptive and len(calls) > 1 and not streams:          # (only the queue schedule re-deals)
+            assert ens.schedule()["redeals"] >= 1 and not np.array_equal(ens.placement()[1], np.arange(N))
+        out = _data(ens)
+        ens.close()
+        return out
+
+    base = run()
+    assert np.all(base[2][0] == STEPS // CHUNK) and base[2].max() < 64
+    for v in (dict(calls=(12, 28)), dict(streams=3), dict(adaptive=True, calls=(36, 4)), dict(adaptive=True, calls=(36, 4), streams=3)):
+        assert_all_equal(base, run(**v), v)
+    # a wrapped store of 4 holds the tail of the long one
+    time, value, count, state = run(capacity=4, wrap=True)
+    assert np.array_equal(state[:, :2], base[3][:, :2]) and np.array_equal(state[:, 3], base[3][:, 3], equal_nan=True) and not state[:, 2].any()
+    assert np.array_equal(count, np.minimum(base[2], 4)) and (base[2] > 4).any() and (base[2] < 4).any()
+    for s, r in ((0, 0), (0, N - 1), (1, 7), (2, 5), (5, 11), (6, 3), (7, 2)):
+        k, m = int(base[2][s, r]), int(count[s, r])
+        assert np.array_equal(time[s, :m, r], base[0][s, k - m:k, r]) and np.array_equal(value[s, :m, r], base[1][s, k - m:k, r], equal_nan=True)
+        assert np.isnan(time[s, m:, r]).all() and np.isnan(value[s, m:, r]).all()
+    k = np.arange(4)[None, :, None]
+    tail = np.take_along_axis(base[0], np.maximum(base[2] - count, 0)[:, None, :] + k, axis=1)
+    assert np.array_equal(np.where(k < count[:, None, :], tail, np.nan), time, equal_nan=True)
+    # without wrap the same store keeps the head and counts the rest
+    time, value, count, state = run(capacity=4)
+    assert np.array_equal(time, base[0][:, :4], equal_nan=True) and np.array_equal(value, base[1][:, :4], equal_nan=True)
+    assert np.array_equal(state[:, 2], np.maximum(base[2] - 4, 0)) and np.array_equal(state[:, 3], base[3][:, 3], equal_nan=True)
+    # reset_trends, then the same call: the data of a program set on a fresh ensemble in that state
+    assert_all_equal(run(warm_up=20), run(warm_up=20, reset=True), "reset")
+
+
+def test_a_program_that_is_off_reads_nan(gpu, wt):
+    N, n = 64, 4
+    cols, bc = wt.make_ensemble(N, seed=1800)
+    ens = plant(wt, cols, bc, n)
+    ens.set_schedule(0, CHUNK)
+    ens.write_commands(*MASTER)
+    ens.set_trends(wt.Trend("control", ("chlorine", "output"), deadband=0.0), wt.Trend("alarm_word"), wt.Trend("detect", (0, "stat"), every=3),
+                   wt.Trend("command", "chlorine"), capacity=CAPACITY)
+    ens.step(DT, n_steps=STEPS, download=False)
+    d, st = ens.trend_data(), ens.trend_state()
+    ens.close()
+    assert np.all(d.count[0] == 1) and np.all(d.time[0, 0] == CHUNK * DT) and np.isnan(d.value[0]).all() and np.isnan(d.time[0, 1:]).all()
+    assert np.all(st.n_seen[:4] == 10) and np.all(st.n_recorded[0] == 1) and np.isnan(st.last[:3]).all() and not st.n_dropped.any()
+    assert np.all(d.count[1] == 10) and np.isnan(d.value[1]).all() and np.array_equal(d.time[1, :10, 5], CHUNK * DT * np.arange(1, 11))
+    assert np.all(d.count[2] == 4) and np.isnan(d.value[2]).all()
+    assert np.all(d.value[3, :10] == MASTER[1]) and not d.count[4:].any()                  # a program that is on, next to them
+
+
+def test_errors_and_lifetime(gpu, wt):
+    from importlib import import_module
+    nat = import_module("ics-wt-physicsengine_amd.core._native")
+    N, n = 128, 4
+    cols, bc = wt.make_ensemble(N, seed=13)
+    word = wt.Trend("alarm_word")
+    ens = wt.ReactorEnsemble(cols, n_zones=n)
+    ens.set_boundary(bc)
+    with pytest.raises(ValueError, match="enable plant I/O first"):
+        ens.set_trends(word, capacity=4)
+    ens.enable_sensors(seed=4)
+    with pytest.raises(ValueError, match="trends read the plant I/O scan"):
+        ens.set_trends(word, capacity=4)
+    ens.enable_plant_io()
+    for call in (ens.trend_state, ens.trend_data, ens.reset_trends):
+        with pytest.raises(ValueError, match="no trend program"):
+            call()
+    t = np.empty((8, 4, N))
+    assert nat.lib().wt_ensemble_trend_get(ens._h, None) == nat.WT_E_STATE
+    assert nat.lib().wt_ensemble_trend_data(ens._h, nat.dptr(t), None) == nat.WT_E_STATE
+    assert nat.lib().wt_ensemble_trend_reset(ens._h) == nat.WT_E_STATE
+    other = plant(wt, cols, bc, 64)                              # the n > 32 kernel carries no trend section
+    with pytest.raises(ValueError, match="trend programs run in the kernels for up to 32 zones"):
+        other.set_trends(word, capacity=4)
+    with pytest.raises(ValueError, match="no trend program"):
+        other.trend_state()
+    other.close()
+    for capacity in (0, -3):
+        with pytest.raises(ValueError, match="capacity must be >= 1"):
+            ens.set_trends(word, capacity=capacity)
+    good = wt.trend_block(N, word)
+    assert nat.lib().wt_ensemble_trend_set(ens._h, nat.dptr(good), 0, 0) == nat.WT_E_ARG
+    assert nat.lib().wt_ensemble_trend_set(ens._h, nat.dptr(good), 2 ** 62, 0) == nat.WT_E_ARG           # the store's size overflows
+    assert nat.lib().wt_ensemble_trend_set(ens._h, None, 4, 0) == nat.WT_E_ARG
+    with pytest.raises(ValueError, match="at most 8"):
+        ens.set_trends(*[word] * 9, capacity=4)
+    with pytest.raises(ValueError, match="index must be an integer within the tag's range"):
+        ens.set_trends(wt.Trend("command", 3), capacity=4)
+    bad = good.copy()
+    bad[0, 2, 17] = 0.0
+    assert nat.lib().wt_ensemble_trend_set(ens._h, nat.dptr(bad), 4, 0) == nat.WT_E_ARG
+    assert nat.lib().wt_last_error() == b"every must be an integer >= 1"
+    with pytest.raises(ValueError, match="no trend program"):
+        ens.trend_state()                                        # a refused program leaves none behind
+    ens.set_schedule(0, 5)
+    ens.write_commands(*MASTER)
+    ens.step(DT, n_steps=10, download=False)
+    sim = wt.Trend("field_value", "flow_main")
+    ens.set_trends(sim, word, capacity=4)
+    d, st = ens.trend_data(), ens.trend_state()
+    assert d.time.shape == d.value.shape == (8, 4, N) and np.isnan(d.time).all() and np.isnan(d.value).all() and not d.count.any()
+    assert not np.nan_to_num(st.block()).any() and np.isnan(st.last).all()
+    ens.step(DT, n_steps=30, download=False)                     # six scans, 150 ... 400 s: four stored, two dropped
+    d, st = ens.trend_data(), ens.trend_state()
+    assert np.all(d.count[:2] == 4) and np.all(d.time[0] == np.array([150.0, 200.0, 250.0, 300.0])[:, None])
+    assert np.all(st.n_seen[:2] == 6) and np.all(st.n_recorded[:2] == 4) and np.all(st.n_dropped[:2] == 2) and np.isnan(d.value[1]).all()
+    assert np.array_equal(st.last[0], ens.sensor_readings()[0][4].astype(np.float64), equal_nan=True)      # last follows the dropped samples
+    ens.clear_trends()
+    with pytest.raises(ValueError, match="no trend program"):
+        ens.trend_data()
+    ens.clear_trends()                                           # no effect while none is set
+    ens.set_trends(sim, capacity=9, wrap=True)                   # another capacity: the store is allocated anew
+    ens.step(DT, n_steps=10, download=False)
+    d = ens.trend_data()
+    assert d.time.shape == (8, 9, N) and np.all(d.count[0] == 2) and np.all(d.time[0, :2] == np.array([450.0, 500.0])[:, None])
+    ens.set_trends(word, sim, capacity=2)                        # set over a program replaces it, data and capacity
+    d = ens.trend_data()
+    assert d.time.shape == (8, 2, N) and not d.count.any() and np.isnan(d.value).all()
+    ens.step(DT, n_steps=5, download=False)
+    assert np.all(ens.trend_data().count[:2] == 1) and np.all(ens.trend_data().time[1, 0] == 550.0)
+    # destroying a handle whose program is still set releases its arrays without an error
+    rc = nat.lib().wt_ensemble_destroy(ens._h)
+    ens._h = ctypes.c_void_p()
+    assert rc == nat.WT_OK
+    free = plant(wt, cols, bc, n)                                # and the device still serves a new ensemble
+    free.set_trends(word, capacity=1)
+    free.close()
