@@ -18,9 +18,8 @@ CSRC = os.path.join(_PKG, "csrc")
 LIB_PATH = os.environ.get("WTPHYS_LIB", os.path.join(CSRC, "libwtphys.so"))  # override: diagnostic builds
 
 WT_OK, WT_E_ARG, WT_E_HIP, WT_E_NOGPU, WT_E_STATE = 0, 1, 2, 3, 4
-WT_PROG_CONTROL, WT_PROG_INJECT, WT_PROG_ALARM, WT_PROG_ACTUATOR, WT_PROG_DISTURB, WT_PROG_SCORE = 0, 1, 2, 3, 4, 5   # wt_program_check
-WT_PROG_DETECT = 6
-WT_PROG_TREND = 7
+(WT_PROG_CONTROL, WT_PROG_INJECT, WT_PROG_ALARM, WT_PROG_ACTUATOR, WT_PROG_DISTURB, WT_PROG_SCORE, WT_PROG_DETECT,
+ WT_PROG_TREND) = range(8)   # wt_program_check
 
 
 class WtError(RuntimeError):

@@ -570,8 +570,8 @@ class ReactorEnsemble:
         _native.check(_native.lib().wt_ensemble_get_boundary(self._h, _native.dptr(out)))
         return out
 
-    # -- PI dosing programs at every PLC scan, on the device (wt_ctl.hpp)
-    def _control_call(self, fn, *args) -> None:
+    def _program_call(self, fn, *args) -> None:
+        """A call of one of the eight per-reactor programs: a refusal is the caller's ValueError."""
         try:
             _native.check(fn(self._h, *args))
         except _native.WtError as e:
@@ -579,6 +579,7 @@ class ReactorEnsemble:
                 raise ValueError(e.message) from None
             raise
 
+    # -- PI dosing programs at every PLC scan, on the device (wt_ctl.hpp)
     def enable_control(self, chlorine: Optional["control.PILoop"] = None, acid: Optional["control.PILoop"] = None) -> None:
         """Run up to two PI loops per reactor at every PLC scan, inside the step call: ``chlorine`` writes the
         chlorine_flow_rate holding register, ``acid`` the acid_flow_rate one; a loop left out stays off and its
@@ -586,7 +587,7 @@ class ReactorEnsemble:
         ``clip(bias, out_min, out_max)``.  The output acts from the next scan on, exactly as a host master writing
         between two calls of one scan interval would.  Needs :meth:`enable_plant_io`."""
         blk = control.control_block(self.n_reactors, chlorine, acid)
-        self._control_call(_native.lib().wt_ensemble_control_enable, _native.dptr(blk))
+        self._program_call(_native.lib().wt_ensemble_control_enable, _native.dptr(blk))
         self._control_params = blk
 
     def retune_control(self, chlorine=None, acid=None) -> None:
@@ -598,18 +599,18 @@ class ReactorEnsemble:
         rows = [old[i] if loop is None else control.loop_rows(loop, name, self.n_reactors)
                 for i, (name, loop) in enumerate(zip(control.LOOPS, (chlorine, acid)))]
         blk = np.ascontiguousarray(np.stack(rows))
-        self._control_call(_native.lib().wt_ensemble_control_retune, _native.dptr(blk))
+        self._program_call(_native.lib().wt_ensemble_control_retune, _native.dptr(blk))
         self._control_params = blk
 
     def disable_control(self) -> None:
         """Stop the PI programs; the holding registers keep their last outputs."""
-        self._control_call(_native.lib().wt_ensemble_control_disable)
+        self._program_call(_native.lib().wt_ensemble_control_disable)
         self._control_params = None
 
     def control_state(self) -> "control.ControlState":
         """Integral, output and metrics of both loops by reactor (one synchronisation)."""
         blk = np.empty((len(control.LOOPS), control.NCS, self.n_reactors), dtype=np.float64)
-        self._control_call(_native.lib().wt_ensemble_control_get, _native.dptr(blk))
+        self._program_call(_native.lib().wt_ensemble_control_get, _native.dptr(blk))
         return control.ControlState.from_block(blk)
 
     # -- injection programs at every PLC scan, on the device (wt_inj.hpp)
@@ -620,18 +621,18 @@ class ReactorEnsemble:
         registers keep what the master wrote).  Replaces any program and resets the state.  Needs
         :meth:`enable_plant_io` and at most 32 zones per reactor."""
         blk = inject.injection_block(self.n_reactors, *injections)
-        self._control_call(_native.lib().wt_ensemble_inject_set, _native.dptr(blk))
+        self._program_call(_native.lib().wt_ensemble_inject_set, _native.dptr(blk))
 
     def injection_state(self) -> "inject.InjectionState":
         """Applications, first and last application time and the FREEZE value of every slot by reactor (one
         synchronisation)."""
         blk = np.empty((inject.SLOTS, inject.NIS, self.n_reactors), dtype=np.float64)
-        self._control_call(_native.lib().wt_ensemble_inject_get, _native.dptr(blk))
+        self._program_call(_native.lib().wt_ensemble_inject_get, _native.dptr(blk))
         return inject.InjectionState.from_block(blk)
 
     def clear_injections(self) -> None:
         """Stop the injection program."""
-        self._control_call(_native.lib().wt_ensemble_inject_clear)
+        self._program_call(_native.lib().wt_ensemble_inject_clear)
 
     # -- alarm and interlock programs at every PLC scan, on the device (wt_alm.hpp)
     def set_alarms(self, *alarms: "alarm.Alarm") -> None:
@@ -641,27 +642,27 @@ class ReactorEnsemble:
         holding registers keep what the master wrote).  Replaces any program and resets the state.  Needs
         :meth:`enable_plant_io` and at most 32 zones per reactor."""
         blk = alarm.alarm_block(self.n_reactors, *alarms)
-        self._control_call(_native.lib().wt_ensemble_alarm_set, _native.dptr(blk))
+        self._program_call(_native.lib().wt_ensemble_alarm_set, _native.dptr(blk))
 
     def alarm_state(self) -> "alarm.AlarmState":
         """Slot and reactor state of the alarm program (one synchronisation)."""
         slots = np.empty((alarm.SLOTS, alarm.NAS, self.n_reactors), dtype=np.float64)
         reactors = np.empty((alarm.NAR, self.n_reactors), dtype=np.float64)
-        self._control_call(_native.lib().wt_ensemble_alarm_get, _native.dptr(slots), _native.dptr(reactors))
+        self._program_call(_native.lib().wt_ensemble_alarm_get, _native.dptr(slots), _native.dptr(reactors))
         return alarm.AlarmState.from_block(slots, reactors)
 
     def alarm_words(self) -> np.ndarray:
         """(N,) uint16 alarm words: bits 0-3 active slots, 4-7 their conditions, 8 acid trip, 9 chlorine trip,
         12-14 first-out slot + 1."""
         w = np.empty(self.n_reactors, dtype=np.uint16)
-        self._control_call(_native.lib().wt_ensemble_alarm_words, w.ctypes.data_as(C.POINTER(C.c_uint16)))
+        self._program_call(_native.lib().wt_ensemble_alarm_words, w.ctypes.data_as(C.POINTER(C.c_uint16)))
         return w
 
     def reset_alarms(self, reactors=None) -> None:
         """Acknowledge latched alarms: in the given reactors (indices or an (N,) bool mask; None: all), every latched
         slot whose condition has cleared becomes inactive; one whose condition still stands stays active."""
         if reactors is None:
-            self._control_call(_native.lib().wt_ensemble_alarm_reset, None)
+            self._program_call(_native.lib().wt_ensemble_alarm_reset, None)
             return
         r = np.asarray(reactors)
         mask = np.zeros(self.n_reactors, dtype=np.uint8)
@@ -671,11 +672,11 @@ class ReactorEnsemble:
             mask[r] = 1
         else:
             mask[r.astype(np.int64)] = 1
-        self._control_call(_native.lib().wt_ensemble_alarm_reset, mask.ctypes.data_as(C.POINTER(C.c_uint8)))
+        self._program_call(_native.lib().wt_ensemble_alarm_reset, mask.ctypes.data_as(C.POINTER(C.c_uint8)))
 
     def clear_alarms(self) -> None:
         """Stop the alarm program (trips in force end with it)."""
-        self._control_call(_native.lib().wt_ensemble_alarm_clear)
+        self._program_call(_native.lib().wt_ensemble_alarm_clear)
 
     # -- actuator programs at every PLC scan, on the device (wt_act.hpp)
     def set_actuators(self, *actuators: "actuator.Actuator") -> None:
@@ -685,7 +686,7 @@ class ReactorEnsemble:
         becomes the boundary row the next step integrates under.  Every element starts at its row in force.  Replaces
         any program.  Needs :meth:`enable_plant_io` and at most 32 zones per reactor."""
         blk = actuator.actuator_block(self.n_reactors, *actuators)
-        self._control_call(_native.lib().wt_ensemble_actuator_set, _native.dptr(blk))
+        self._program_call(_native.lib().wt_ensemble_actuator_set, _native.dptr(blk))
 
     def actuator_state(self) -> "actuator.ActuatorState":
         """Channel state, demand queues and t_prev of the actuator program (one synchronisation)."""
@@ -693,12 +694,12 @@ class ReactorEnsemble:
         st = np.empty((len(actuator.CHANNELS), actuator.NVS, N), dtype=np.float64)
         q = np.empty((len(actuator.CHANNELS), actuator.MAX_DELAY, N), dtype=np.float64)
         tp = np.empty(N, dtype=np.float64)
-        self._control_call(_native.lib().wt_ensemble_actuator_get, _native.dptr(st), _native.dptr(q), _native.dptr(tp))
+        self._program_call(_native.lib().wt_ensemble_actuator_get, _native.dptr(st), _native.dptr(q), _native.dptr(tp))
         return actuator.ActuatorState.from_block(st, q, tp)
 
     def clear_actuators(self) -> None:
         """Stop the actuator program: from the next scan on the commands reach the plant at once."""
-        self._control_call(_native.lib().wt_ensemble_actuator_clear)
+        self._program_call(_native.lib().wt_ensemble_actuator_clear)
 
     # -- disturbance programs after every outer step, on the device (wt_dst.hpp)
     def set_disturbances(self, *disturbances: "disturb.Disturbance", seed: int = 0xD157, reactor_base: int = 0,
@@ -710,7 +711,7 @@ class ReactorEnsemble:
         draws (shards of one ensemble pass their first global reactor); ``history`` > 0 keeps that many offsets per
         reactor.  Replaces any program.  Not with ``boundary_schedule``; at most 32 zones per reactor."""
         blk = disturb.disturbance_block(self.n_reactors, *disturbances)
-        self._control_call(_native.lib().wt_ensemble_disturb_set, _native.dptr(blk),
+        self._program_call(_native.lib().wt_ensemble_disturb_set, _native.dptr(blk),
                            C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), int(reactor_base), int(history))
         self._disturb_history = int(history)
         self._device_boundary_moved = True
@@ -721,7 +722,7 @@ class ReactorEnsemble:
         st = np.empty((disturb.SLOTS, disturb.NDS, N), dtype=np.float64)
         base = np.empty((len(params.BOUNDARY_FIELDS), N), dtype=np.float64)
         tp = np.empty(N, dtype=np.float64)
-        self._control_call(_native.lib().wt_ensemble_disturb_get, _native.dptr(st), _native.dptr(base), _native.dptr(tp))
+        self._program_call(_native.lib().wt_ensemble_disturb_get, _native.dptr(st), _native.dptr(base), _native.dptr(tp))
         return disturb.DisturbanceState.from_block(st, base, tp)
 
     def disturbance_history(self):
@@ -730,13 +731,13 @@ class ReactorEnsemble:
         N, H = self.n_reactors, max(self._disturb_history, 0)
         off = np.empty((H, disturb.SLOTS, N), dtype=np.float64)
         filled = np.empty(N, dtype=np.int32)
-        self._control_call(_native.lib().wt_ensemble_disturb_history, _native.dptr(off) if H else None,
+        self._program_call(_native.lib().wt_ensemble_disturb_history, _native.dptr(off) if H else None,
                            filled.ctypes.data_as(C.POINTER(C.c_int32)))
         return off, filled
 
     def clear_disturbances(self) -> None:
         """Stop the disturbance program: the targeted rows go back to the base."""
-        self._control_call(_native.lib().wt_ensemble_disturb_clear)
+        self._program_call(_native.lib().wt_ensemble_disturb_clear)
         self._disturb_history = -1
         self._device_boundary_moved = True
 
@@ -750,24 +751,24 @@ class ReactorEnsemble:
         earlier program and resets its state.  Needs plant I/O and at most 32 zones."""
         blk = detect.detector_block(self.n_reactors, *detectors)
         lab = detect.label_block(self.n_reactors, attack)
-        self._control_call(_native.lib().wt_ensemble_detect_set, _native.dptr(blk), _native.dptr(lab))
+        self._program_call(_native.lib().wt_ensemble_detect_set, _native.dptr(blk), _native.dptr(lab))
         self._detect_labels = lab
 
     def detector_state(self) -> "detect.DetectorState":
         """Slot state, t_prev and label of the detector program (one synchronisation)."""
         st = np.empty((detect.SLOTS, detect.NKS, self.n_reactors), dtype=np.float64)
         tp = np.empty(self.n_reactors, dtype=np.float64)
-        self._control_call(_native.lib().wt_ensemble_detect_get, _native.dptr(st), _native.dptr(tp))
+        self._program_call(_native.lib().wt_ensemble_detect_get, _native.dptr(st), _native.dptr(tp))
         return detect.DetectorState.from_block(st, tp, self._detect_labels)
 
     def reset_detectors(self) -> None:
         """Statistics, alarms and counts back to their values at :meth:`set_detectors`, at the current loop time; the
         parameters and the label stay (detection after a warm-up)."""
-        self._control_call(_native.lib().wt_ensemble_detect_reset)
+        self._program_call(_native.lib().wt_ensemble_detect_reset)
 
     def clear_detectors(self) -> None:
         """Stop the detector program and free its buffers."""
-        self._control_call(_native.lib().wt_ensemble_detect_clear)
+        self._program_call(_native.lib().wt_ensemble_detect_clear)
         self._detect_labels = None
 
     # -- trend recorder programs at every PLC scan, on the device (wt_trd.hpp)
@@ -779,33 +780,33 @@ class ReactorEnsemble:
         programs keep their bits.  Replaces any earlier program, its state and its data.  Needs plant I/O and at most
         32 zones."""
         blk = trend.trend_block(self.n_reactors, *trends)
-        self._control_call(_native.lib().wt_ensemble_trend_set, _native.dptr(blk), int(capacity), int(bool(wrap)))
+        self._program_call(_native.lib().wt_ensemble_trend_set, _native.dptr(blk), int(capacity), int(bool(wrap)))
         self._trend_capacity = int(capacity)
 
     def trend_state(self) -> "trend.TrendState":
         """Slot state of the trend program (one synchronisation)."""
         st = np.empty((trend.SLOTS, trend.NTS, self.n_reactors), dtype=np.float64)
-        self._control_call(_native.lib().wt_ensemble_trend_get, _native.dptr(st))
+        self._program_call(_native.lib().wt_ensemble_trend_get, _native.dptr(st))
         return trend.TrendState.from_block(st)
 
     def trend_data(self) -> "trend.TrendData":
         """The recorded series, oldest sample first (a wrapped store is unwrapped), NaN past the samples held."""
         st = np.empty((trend.SLOTS, trend.NTS, self.n_reactors), dtype=np.float64)
-        self._control_call(_native.lib().wt_ensemble_trend_get, _native.dptr(st))
+        self._program_call(_native.lib().wt_ensemble_trend_get, _native.dptr(st))
         t = np.empty((trend.SLOTS, self._trend_capacity, self.n_reactors), dtype=np.float64)
         x = np.empty_like(t)
-        self._control_call(_native.lib().wt_ensemble_trend_data, _native.dptr(t), _native.dptr(x))
+        self._program_call(_native.lib().wt_ensemble_trend_data, _native.dptr(t), _native.dptr(x))
         count = np.minimum(st[:, trend.STATE_ROWS.index("n_recorded")], self._trend_capacity).astype(np.int64)
         return trend.TrendData(t, x, count)
 
     def reset_trends(self) -> None:
         """Slot state and data back to their values at :meth:`set_trends`; the slots, the capacity and ``wrap`` stay
         (recording after a warm-up)."""
-        self._control_call(_native.lib().wt_ensemble_trend_reset)
+        self._program_call(_native.lib().wt_ensemble_trend_reset)
 
     def clear_trends(self) -> None:
         """Stop the trend program and free its buffers."""
-        self._control_call(_native.lib().wt_ensemble_trend_clear)
+        self._program_call(_native.lib().wt_ensemble_trend_clear)
         self._trend_capacity = 0
 
     # -- score programs after every outer step, on the device (wt_scr.hpp)
@@ -827,7 +828,7 @@ class ReactorEnsemble:
                 hi = np.ascontiguousarray(np.broadcast_to(np.asarray(fan_range[1], dtype=np.float64), (score.SLOTS,)))
             except ValueError:
                 raise ValueError("fan_range: expected (lo, hi), each a scalar or one value per slot (4,)") from None
-        self._control_call(_native.lib().wt_ensemble_score_set, _native.dptr(blk), cap, B,
+        self._program_call(_native.lib().wt_ensemble_score_set, _native.dptr(blk), cap, B,
                            None if lo is None else _native.dptr(lo), None if hi is None else _native.dptr(hi))
         if B > 0 and cap > 0:
             edges = score.fan_edges(lo, hi, B)
@@ -837,7 +838,7 @@ class ReactorEnsemble:
         """The per-reactor accumulators of the score program (one synchronisation)."""
         st = np.empty((score.SLOTS, score.NSS, self.n_reactors), dtype=np.float64)
         tp = np.empty(self.n_reactors, dtype=np.float64)
-        self._control_call(_native.lib().wt_ensemble_score_get, _native.dptr(st), _native.dptr(tp))
+        self._program_call(_native.lib().wt_ensemble_score_get, _native.dptr(st), _native.dptr(tp))
         return score.ScoreState.from_block(st, tp)
 
     def score_curve(self) -> "score.ScoreCurve":
@@ -847,7 +848,7 @@ class ReactorEnsemble:
         counts = np.zeros((cap, score.SLOTS, 3), dtype=np.int32)
         fan = np.zeros((cap, score.SLOTS, B + 2), dtype=np.int32) if B > 0 else None
         i32p, k = C.POINTER(C.c_int32), C.c_int(0)
-        self._control_call(_native.lib().wt_ensemble_score_curve, counts.ctypes.data_as(i32p) if cap else None,
+        self._program_call(_native.lib().wt_ensemble_score_curve, counts.ctypes.data_as(i32p) if cap else None,
                            fan.ctypes.data_as(i32p) if fan is not None else None, C.byref(k))
         K = k.value
         return score.ScoreCurve(counts[:K, :, 0].copy(), counts[:K, :, 1].copy(), counts[:K, :, 2].copy(),
@@ -856,11 +857,11 @@ class ReactorEnsemble:
     def reset_scores(self) -> None:
         """Accumulators and curve back to their values at :meth:`set_scores`, the parameters kept: scoring starts over
         at the current time (after a warm-up)."""
-        self._control_call(_native.lib().wt_ensemble_score_reset)
+        self._program_call(_native.lib().wt_ensemble_score_reset)
 
     def clear_scores(self) -> None:
         """Stop the score program and free its buffers."""
-        self._control_call(_native.lib().wt_ensemble_score_clear)
+        self._program_call(_native.lib().wt_ensemble_score_clear)
         self._score_curve = None
 
     # -- diagnostics (NEXT-4)

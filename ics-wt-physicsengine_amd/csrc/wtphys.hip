@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -88,22 +89,18 @@ struct wt_ensemble {
     // The kernel's argument structs of the optional parts, as every launch passes them (make_args adds what is per
     // call).  sens: fused sensor suite (wt_sensors.hpp, sens.on), plant I/O with its Modbus register images per reactor
     // (wt_plc.hpp, sens.plc_on: one PLC scan every chunk_steps outer steps), the command path into the boundary block.
-    // ctl / inj / alm / act: per-reactor PI, injection, alarm and actuator programs (wt_ctl.hpp, wt_inj.hpp,
-    // wt_alm.hpp, wt_act.hpp), [N] records each.  The holding image lives in ctl.hr, which sens.cmd.hr repeats.
+    // The holding image lives in ctl.hr, which sens.cmd.hr repeats.  Then the eight per-reactor programs, [N] records
+    // each, in WT_PROG_* order: k_programs below describes the host side of each.  scr_steps: outer
+    // steps the step calls have taken since score_set / score_reset (the index of the ensemble curve's next entry).
     wts::SuiteArgs sens = {};
     wtc::CtlArgs ctl = {};
     wti::InjArgs inj = {};
     wta::AlmArgs alm = {};
     wtv::ActArgs act = {};
-    // dst: the per-reactor disturbance program (wt_dst.hpp), evaluated after every outer step
     wtd::DstArgs dst = {};
-    // scr: the per-reactor score program (wt_scr.hpp), evaluated after every outer step; scr_steps: outer steps the
-    // step calls have taken since score_set / score_reset (the index of the ensemble curve's next entry)
     wtsc::ScrArgs scr = {};
     int64_t scr_steps = 0;
-    // det: the per-reactor anomaly detector program (wt_det.hpp), evaluated last in every PLC scan
     wtk::DetArgs det = {};
-    // trd: the per-reactor trend recorder program (wt_trd.hpp), run last in every PLC scan
     wtt::TrdArgs trd = {};
     // optional per-launch HIP-event timing (bench.py roofline accounting)
     bool time_launches = false;
@@ -160,18 +157,21 @@ wt::StepArgs make_args(const wt_ensemble *h, double dt, int n_steps, int first_s
 
 template <class T> void free_and_null(T *&p) { if (p) (void)hipFree(p); p = nullptr; }
 
-// The device arrays of one part of the handle (core, sensor suite, plant I/O, recording, a scan program): allocated
-// together, all or none, and released together with the part's switch.
+// The device arrays of one part of the handle (core, sensor suite, plant I/O, recording, a program): allocated
+// together, all or none, and released together with the part's switch.  The sizes come from the handle alone: a call
+// stores a new capacity there before it allocates, and release puts it back to 0, as a fresh handle has it.
 struct ArrayGroup {
     const char *name;                                   // prefix of an allocation error
     int *on;                                            // the part's switch (nullptr: none)
     std::vector<std::pair<void **, size_t>> arrays;     // where each pointer lives, its bytes (0: not allocated)
+    std::function<void()> zero;                         // zeroes the capacities the bytes come from (empty: none)
 };
 
 void release(const ArrayGroup &g)
 {
     for (const auto &a : g.arrays) free_and_null(*a.first);
     if (g.on) *g.on = 0;
+    if (g.zero) g.zero();
 }
 
 // allocates the group's arrays unless an earlier call did; on failure none is left behind
@@ -202,10 +202,10 @@ ArrayGroup core_arrays(wt_ensemble *h)
 }
 
 // the history arrays only for hist_cap > 0
-ArrayGroup sensor_arrays(wt_ensemble *h, int hist_cap)
+ArrayGroup sensor_arrays(wt_ensemble *h)
 {
     wts::SuiteArgs &s = h->sens;
-    const size_t N = (size_t)h->N, hist = (size_t)hist_cap * wts::NSENS * N;
+    const size_t N = (size_t)h->N, hist = (size_t)s.hist_cap * wts::NSENS * N;
     return {"sensors", &s.on, {{(void **)&s.fs, sizeof(float) * wts::NSENS * wts::NF * N},
                                {(void **)&s.ds, sizeof(double) * wts::NSENS * wts::ND * N},
                                {(void **)&s.is, sizeof(int32_t) * wts::NSENS * wts::NI * N},
@@ -217,7 +217,8 @@ ArrayGroup sensor_arrays(wt_ensemble *h, int hist_cap)
                                {(void **)&s.out_status, wts::NSENS * N}, {(void **)&s.out_fault, wts::NSENS * N},
                                {(void **)&s.t_enable, sizeof(double) * N},
                                {(void **)&s.hist_value, sizeof(float) * hist}, {(void **)&s.hist_status, hist},
-                               {(void **)&s.hist_fault, hist}, {(void **)&s.hist_pos, hist_cap > 0 ? sizeof(int32_t) * N : 0}}};
+                               {(void **)&s.hist_fault, hist}, {(void **)&s.hist_pos, s.hist_cap > 0 ? sizeof(int32_t) * N : 0}},
+            [h] { h->sens.hist_cap = 0; }};
 }
 
 ArrayGroup plant_io_arrays(wt_ensemble *h)
@@ -229,13 +230,14 @@ ArrayGroup plant_io_arrays(wt_ensemble *h)
                                             {(void **)&h->sens.pack.update_ok, N}}};
 }
 
-ArrayGroup record_arrays(wt_ensemble *h, size_t records)   // records: capacity x N
+ArrayGroup record_arrays(wt_ensemble *h)
 {
     wt_ensemble::Recording &r = h->rec;
-    const size_t zone = sizeof(double) * records * (size_t)h->n;
+    const size_t records = (size_t)r.cap * (size_t)h->N, zone = sizeof(double) * records * (size_t)h->n;
     return {"record", nullptr, {{(void **)&r.pH, zone}, {(void **)&r.Cl, zone}, {(void **)&r.T, zone},
                                 {(void **)&r.time, sizeof(double) * records}, {(void **)&r.flow, sizeof(double) * records},
-                                {(void **)&r.status, sizeof(uint32_t) * records}}};
+                                {(void **)&r.status, sizeof(uint32_t) * records}},
+            [h] { h->rec = {}; }};
 }
 
 ArrayGroup control_arrays(wt_ensemble *h)
@@ -271,25 +273,28 @@ ArrayGroup actuator_arrays(wt_ensemble *h)
 }
 
 // the history array only for hist_cap > 0
-ArrayGroup disturb_arrays(wt_ensemble *h, int hist_cap)
+ArrayGroup disturb_arrays(wt_ensemble *h)
 {
     const size_t N = (size_t)h->N;
     return {"disturb", &h->dst.on, {{(void **)&h->dst.par, sizeof(double) * wtd::PAR_DOUBLES * N},
                                     {(void **)&h->dst.st, sizeof(double) * wtd::ST_DOUBLES * N},
                                     {(void **)&h->dst.base, sizeof(double) * WT_NB * N},
                                     {(void **)&h->dst.tp, sizeof(double) * N},
-                                    {(void **)&h->dst.hist, sizeof(double) * wtd::SLOTS * (size_t)hist_cap * N}}};
+                                    {(void **)&h->dst.hist, sizeof(double) * wtd::SLOTS * (size_t)h->dst.hist_cap * N}},
+            [h] { h->dst.hist_cap = 0; }};
 }
 
 // the curve arrays only for curve_cap > 0, the fan only for bins > 0
-ArrayGroup score_arrays(wt_ensemble *h, int curve_cap, int bins)
+ArrayGroup score_arrays(wt_ensemble *h)
 {
-    const size_t N = (size_t)h->N, cells = (size_t)curve_cap * wtsc::SLOTS;
+    const int bins = h->scr.bins;
+    const size_t N = (size_t)h->N, cells = (size_t)h->scr.curve_cap * wtsc::SLOTS;
     return {"score", &h->scr.on, {{(void **)&h->scr.par, sizeof(double) * wtsc::PAR_DOUBLES * N},
                                   {(void **)&h->scr.st, sizeof(double) * wtsc::ST_DOUBLES * N},
                                   {(void **)&h->scr.tp, sizeof(double) * N},
                                   {(void **)&h->scr.counts, sizeof(int32_t) * 3 * cells},
-                                  {(void **)&h->scr.fan, bins > 0 ? sizeof(int32_t) * (size_t)(bins + 2) * cells : 0}}};
+                                  {(void **)&h->scr.fan, bins > 0 ? sizeof(int32_t) * (size_t)(bins + 2) * cells : 0}},
+            [h] { h->scr.curve_cap = h->scr.bins = 0; h->scr_steps = 0; }};
 }
 
 ArrayGroup detect_arrays(wt_ensemble *h)
@@ -301,22 +306,13 @@ ArrayGroup detect_arrays(wt_ensemble *h)
                                    {(void **)&h->det.tp, sizeof(double) * N}}};
 }
 
-// cap: samples per slot and reactor of the store
-ArrayGroup trend_arrays(wt_ensemble *h, int64_t cap)
+ArrayGroup trend_arrays(wt_ensemble *h)
 {
     const size_t N = (size_t)h->N;
     return {"trend", &h->trd.on, {{(void **)&h->trd.par, sizeof(double) * wtt::PAR_DOUBLES * N},
                                   {(void **)&h->trd.st, sizeof(double) * wtt::ST_DOUBLES * N},
-                                  {(void **)&h->trd.store, sizeof(double2) * wtt::SLOTS * (size_t)cap * N}}};
-}
-
-// the body of control_disable, inject_clear, alarm_clear, actuator_clear, score_clear, detect_clear and trend_clear
-int stop_program(wt_ensemble *h, const ArrayGroup &g)
-{
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still use the records
-    release(g);
-    return WT_OK;
+                                  {(void **)&h->trd.store, sizeof(double2) * wtt::SLOTS * (size_t)h->trd.cap * N}},
+            [h] { h->trd.cap = 0; }};
 }
 
 bool row_mode(int n) { return n == 2 || n == 4 || n == 8 || n == 16; }
@@ -564,33 +560,6 @@ int wt_ensemble_create(int64_t n_reactors, int n_zones, int device, const double
     return WT_OK;
 }
 
-int wt_ensemble_destroy(wt_ensemble *h)
-{
-    if (!h) return WT_OK;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (const ArrayGroup &g : {core_arrays(h), sensor_arrays(h, h->sens.hist_cap), plant_io_arrays(h), record_arrays(h, 0),
-                                control_arrays(h), inject_arrays(h), alarm_arrays(h), actuator_arrays(h),
-                                disturb_arrays(h, h->dst.hist_cap), score_arrays(h, h->scr.curve_cap, h->scr.bins), detect_arrays(h),
-                                trend_arrays(h, h->trd.cap)})
-        release(g);
-    free_and_null(h->trace); free_and_null(h->wave_diag); free_and_null(h->snap_dev); free_and_null(h->sched);
-    free_and_null(h->diag_out);
-    for (int s = 0; s < WT_MAX_STREAMS; ++s) {
-        if (h->sub_stream[s]) { (void)hipStreamSynchronize(h->sub_stream[s]); (void)hipStreamDestroy(h->sub_stream[s]); }
-        if (h->sub_done[s]) (void)hipEventDestroy(h->sub_done[s]);
-    }
-    if (h->snap_host) (void)hipHostFree(h->snap_host);
-    if (h->err_host) (void)hipHostFree(h->err_host);
-    for (hipEvent_t e : h->lt_pool) (void)hipEventDestroy(e);
-    if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
-    return WT_OK;
-}
-
 int wt_ensemble_set_stream(wt_ensemble *h, void *hip_stream)
 {
     if (!h) return fail(WT_E_ARG, "NULL handle");
@@ -820,12 +789,10 @@ int wt_ensemble_record(wt_ensemble *h, int every, int capacity)
         return fail(WT_E_ARG, "record size overflows int64");
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still write the old records
-    release(record_arrays(h, 0));
-    h->rec = {};
+    release(record_arrays(h));
     if (capacity == 0) return WT_OK;
-    if (int rc = allocate(record_arrays(h, (size_t)capacity * (size_t)h->N))) return rc;
     h->rec.every = every; h->rec.cap = capacity;
-    return WT_OK;
+    return allocate(record_arrays(h));
 }
 
 int wt_ensemble_get_record(wt_ensemble *h, double *pH, double *Cl, double *T, double *time, double *flow,
@@ -885,7 +852,8 @@ int wt_ensemble_sensors_enable(wt_ensemble *h, uint64_t seed, int64_t reactor_ba
     wts::SuiteArgs &s = h->sens;
     double *cfg = nullptr;
     HIP_TRY(hipMalloc((void **)&cfg, sizeof(double) * 3 * N));
-    const ArrayGroup arrays = sensor_arrays(h, history_capacity);
+    s.hist_cap = history_capacity;
+    const ArrayGroup arrays = sensor_arrays(h);
     if (int rc = allocate(arrays)) { (void)hipFree(cfg); return rc; }
     if (history_capacity > 0) {
         // slots that are never written (a reactor whose step raised takes no reading) must not hold garbage
@@ -912,7 +880,6 @@ int wt_ensemble_sensors_enable(wt_ensemble *h, uint64_t seed, int64_t reactor_ba
     (void)hipFree(cfg);
     if (e != hipSuccess) { release(arrays); return fail(WT_E_HIP, std::string("sensors_enable: ") + hipGetErrorString(e)); }
     s.seed_lo = (uint32_t)(seed & 0xffffffffu); s.seed_hi = (uint32_t)(seed >> 32); s.reactor_base = reactor_base;
-    s.hist_cap = history_capacity;
     s.on = 1;
     return WT_OK;
 }
@@ -994,49 +961,462 @@ int wt_ensemble_plc_device(wt_ensemble *h, void **input_image, void **holding_im
 
 namespace {
 
+// ---- The per-reactor programs: one description each, one lifecycle for all ----
+
 static_assert(WT_CTL_LOOPS == wtc::LOOPS && WT_NC == wtc::NC && WT_NCS == wtc::NCS, "control blocks of the C ABI");
 
-// Host-side checks of a [WT_CTL_LOOPS][WT_NC][N] parameter block; nullptr when it is valid.
-const char *control_params_error(const double *p, int64_t N)
+static_assert(WT_INJ_SLOTS == wti::SLOTS && WT_NI == wti::NI && WT_NIS == wti::NIS, "injection blocks of the C ABI");
+static_assert(WT_INJ_N_TARGETS == wti::N_TARGETS && WT_INJ_CMD_ACID == wti::CMD_ACID && WT_INJ_CMD_CHLORINE == wti::CMD_CHLORINE &&
+              WT_INJ_CMD_INLET == wti::CMD_INLET && WT_INJ_FAULT == wti::M_FAULT && WT_INJ_FAULT + 1 == wti::N_MODES,
+              "injection targets and modes of the C ABI");
+
+static_assert(WT_ALM_SLOTS == wta::SLOTS && WT_NA == wta::NA && WT_NAS == wta::NAS && WT_NAR == wta::NAR, "alarm blocks of the C ABI");
+static_assert(WT_ALM_HIGH == wta::K_HIGH && WT_ALM_LOW == wta::K_LOW && WT_ALM_FIELD == wta::SRC_FIELD &&
+              WT_ALM_ALARM == wta::ON_BAD_ALARM && WT_ALM_TRIP_ACID == wta::ACT_TRIP_ACID &&
+              WT_ALM_TRIP_CHLORINE == wta::ACT_TRIP_CHLORINE && WT_ALM_TRIP_CHLORINE + 1 == wta::N_ACTIONS,
+              "alarm kinds, sources and actions of the C ABI");
+static_assert(WT_A_TRIP_VALUE == wta::A_TRIP_VALUE && WT_AS_N_BAD == wta::AS_N_BAD && WT_AR_N_OVR_CHLORINE == wta::AR_N_OVR_CHLORINE,
+              "alarm rows of the C ABI");
+
+static_assert(WT_ACT_CHANNELS == wtv::CH && WT_NV == wtv::NV && WT_NVS == wtv::NVS && WT_ACT_MAX_DELAY == wtv::MAX_DELAY,
+              "actuator blocks of the C ABI");
+static_assert(WT_ACT_ACID == wtv::CH_ACID && WT_ACT_CHLORINE == wtv::CH_CHLORINE && WT_ACT_INLET == wtv::CH_INLET &&
+              WT_ACT_INLET + 7 == WT_INJ_CMD_INLET && WT_ACT_STUCK == wtv::F_STUCK && WT_ACT_FAIL_TO == wtv::F_FAIL_TO &&
+              WT_ACT_FAIL_TO + 1 == wtv::N_FAULTS, "actuator channels and faults of the C ABI");
+static_assert(WT_V_FAIL_VALUE == wtv::V_FAIL_VALUE && WT_VS_N_FAULT == wtv::VS_N_FAULT, "actuator rows of the C ABI");
+
+static_assert(WT_DST_SLOTS == wtd::SLOTS && WT_ND == wtd::ND && WT_NDS == wtd::NDS && WT_NB == wtd::NB,
+              "disturbance blocks of the C ABI");
+static_assert(WT_DST_OU == wtd::K_OU && WT_DST_OU + 1 == wtd::N_KINDS && WT_D_C == wtd::D_C && WT_DS_N_DRAW == wtd::DS_N_DRAW,
+              "disturbance kinds and rows of the C ABI");
+
+static_assert(WT_SCR_SLOTS == wtsc::SLOTS && WT_NSP == wtsc::NSP && WT_NSS == wtsc::NSS && WT_SCR_MAX_BINS == wtsc::MAX_BINS,
+              "score blocks of the C ABI");
+static_assert(WT_SCR_BAND + 1 == wtsc::N_KINDS && WT_SQ_TEMPERATURE + 1 == wtsc::N_QUANTITIES && WT_SR_MEAN + 1 == wtsc::N_REDUCES &&
+              WT_SP_T_END == wtsc::P_T_END && WT_SS_RUN_MAX == wtsc::S_RUN_MAX, "score kinds and rows of the C ABI");
+
+static_assert(WT_DET_SLOTS == wtk::SLOTS && WT_NK == wtk::NK && WT_NKS == wtk::NKS && WT_NKR == wtk::NKR, "detector blocks of the C ABI");
+static_assert(WT_DET_CUSUM == wtk::D_CUSUM && WT_DET_EWMA == wtk::D_EWMA && WT_DET_FLATLINE == wtk::D_FLATLINE &&
+              WT_DET_FLATLINE + 1 == wtk::N_KINDS && WT_DET_FIELD == wtk::SRC_FIELD && WT_DET_SENSOR == wtk::REF_SENSOR &&
+              WT_DET_TRACK == wtk::REF_TRACK && WT_DET_TRACK + 1 == wtk::N_REFS && WT_DET_ALARM == wtk::ON_BAD_ALARM,
+              "detector kinds, sources, references and policies of the C ABI");
+static_assert(WT_K_REF_ARG == wtk::K_REF_ARG && WT_K_ON_BAD == wtk::K_ON_BAD && WT_KS_X_PREV == wtk::KS_X_PREV &&
+              WT_KS_T_DETECT == wtk::KS_T_DETECT && WT_KS_N_FN == wtk::KS_N_FN && WT_KR_LABEL_END == wtk::KR_LABEL_END,
+              "detector rows of the C ABI");
+static_assert(wtk::NK % 2 == 0 && wtk::NKS % 2 == 0 && wtk::NKR == 2, "the detector's records are read in 16-byte pairs");
+
+static_assert(WT_TRD_SLOTS == wtt::SLOTS && WT_NT == wtt::NT && WT_NTS == wtt::NTS, "trend blocks of the C ABI");
+static_assert(WT_TRD_IMAGE_VALUE == wtt::G_IMAGE_VALUE && WT_TRD_FIELD_FAULT == wtt::G_FIELD_FAULT && WT_TRD_COMMAND == wtt::G_COMMAND &&
+              WT_TRD_CONTROL == wtt::G_CONTROL && WT_TRD_INJECT == wtt::G_INJECT && WT_TRD_ALARM == wtt::G_ALARM &&
+              WT_TRD_ALARM_WORD == wtt::G_ALARM_WORD && WT_TRD_ACTUATOR == wtt::G_ACTUATOR && WT_TRD_DETECT == wtt::G_DETECT &&
+              WT_TRD_DETECT + 1 == wtt::N_TAGS, "trend tags of the C ABI");
+static_assert(WT_T_T_END == wtt::T_T_END && WT_TS_LAST == wtt::TS_LAST, "trend rows of the C ABI");
+static_assert(wtt::NT % 2 == 0 && wtt::NTS % 2 == 0, "the recorder's records are read in 16-byte pairs");
+static_assert(wtt::index_range(wtt::G_IMAGE_VALUE) == WT_N_SENSORS && wtt::index_range(wtt::G_CONTROL) == WT_CTL_LOOPS * WT_NCS &&
+              wtt::index_range(wtt::G_INJECT) == WT_INJ_SLOTS * WT_NIS && wtt::index_range(wtt::G_ALARM) == WT_ALM_SLOTS * WT_NAS &&
+              wtt::index_range(wtt::G_ACTUATOR) == WT_ACT_CHANNELS * WT_NVS && wtt::index_range(wtt::G_DETECT) == WT_DET_SLOTS * WT_NKS,
+              "a trend index names an entry of the block the program's get call returns");
+// COMMAND channels in WT_INJ_CMD_* order
+static_assert(WT_INJ_CMD_ACID + 1 == WT_INJ_CMD_CHLORINE && WT_INJ_CMD_CHLORINE + 1 == WT_INJ_CMD_INLET, "acid, chlorine, inlet");
+
+// -- parameter rules: the checks of one slot's row vector c[fields] (slot: its index in the block); nullptr when it passes
+
+using Rule = const char *(*)(int slot, const double *c);
+
+bool whole_in(double x, double lo, double hi) { return x == std::floor(x) && x >= lo && x <= hi; }
+
+const char *control_rule(int, const double *c)
 {
-    for (int l = 0; l < wtc::LOOPS; ++l)
+    for (int k = 0; k < wtc::NC; ++k)
+        if (!std::isfinite(c[k])) return "control parameters must be finite";
+    if (c[wtc::C_ENABLE] != 0.0 && c[wtc::C_ENABLE] != 1.0) return "enable must be 0 or 1";
+    if (!whole_in(c[wtc::C_SENSOR], 0, WT_N_SENSORS - 1)) return "sensor must be an integer in 0..6";
+    if (c[wtc::C_DIRECTION] != 1.0 && c[wtc::C_DIRECTION] != -1.0) return "direction must be +1 or -1";
+    if (!(c[wtc::C_KP] >= 0) || !(c[wtc::C_KI] >= 0)) return "kp and ki must be >= 0";
+    if (!(c[wtc::C_OUT_MIN] <= c[wtc::C_OUT_MAX])) return "out_min must not exceed out_max";
+    return nullptr;
+}
+
+const char *inject_rule(int, const double *c)
+{
+    for (int k = 0; k < wti::NI; ++k)
+        if (!std::isfinite(c[k]) && !(k == wti::I_T_END && c[k] == INFINITY))
+            return "injection parameters must be finite (end may be +inf)";
+    const double mode = c[wti::I_MODE], target = c[wti::I_TARGET];
+    if (!whole_in(mode, 0, wti::N_MODES - 1)) return "mode must be an integer in 0..7";
+    if (!whole_in(target, 0, wti::N_TARGETS - 1)) return "target must be an integer in 0..9";
+    if (c[wti::I_T_START] > c[wti::I_T_END]) return "start must not exceed end";
+    if (mode == wti::M_FAULT) {
+        if (target >= wti::CMD_ACID) return "a FAULT slot must target a sensor";
+        if (!whole_in(c[wti::I_A], 1, 6)) return "a FAULT slot's fault code (a) must be an integer in 1..6";
+    }
+    return nullptr;
+}
+
+const char *alarm_rule(int, const double *c)
+{
+    for (int k = 0; k < wta::NA; ++k)
+        if (!std::isfinite(c[k])) return "alarm parameters must be finite";
+    if (!whole_in(c[wta::A_KIND], 0, 2)) return "kind must be 0 (off), 1 (high) or 2 (low)";
+    if (!whole_in(c[wta::A_SENSOR], 0, WT_N_SENSORS - 1)) return "sensor must be an integer in 0..6";
+    if (!whole_in(c[wta::A_SOURCE], 0, 1)) return "source must be 0 (image) or 1 (field)";
+    if (c[wta::A_DEADBAND] < 0) return "deadband must be >= 0";
+    if (c[wta::A_ON_DELAY] < 0) return "on_delay must be >= 0";
+    if (!whole_in(c[wta::A_LATCH], 0, 1)) return "latch must be 0 or 1";
+    if (!whole_in(c[wta::A_ON_BAD], 0, 1)) return "on_bad must be 0 (hold) or 1 (alarm)";
+    if (!whole_in(c[wta::A_ACTION], 0, 2)) return "action must be 0 (none), 1 (trip_acid) or 2 (trip_chlorine)";
+    const double tv = c[wta::A_TRIP_VALUE];
+    if (c[wta::A_ACTION] == wta::ACT_TRIP_ACID && !(tv >= 0 && tv <= 2.0)) return "a trip_acid slot's trip_value must be in [0, 2]";
+    if (c[wta::A_ACTION] == wta::ACT_TRIP_CHLORINE && !(tv >= 0 && tv <= 1.0)) return "a trip_chlorine slot's trip_value must be in [0, 1]";
+    return nullptr;
+}
+
+const char *actuator_finite(int, const double *c)
+{
+    for (int v = 0; v < wtv::NV; ++v)
+        if (!std::isfinite(c[v]) && !((v == wtv::V_RATE || v == wtv::V_T_REPAIR) && c[v] == INFINITY))
+            return "actuator parameters must be finite (rate and t_repair may be +inf)";
+    return nullptr;
+}
+
+const char *actuator_rule(int k, const double *c)
+{
+    if (!whole_in(c[wtv::V_ENABLE], 0, 1)) return "enable must be 0 or 1";
+    if (!(c[wtv::V_TAU] >= 0)) return "tau must be >= 0";
+    if (!(c[wtv::V_RATE] > 0)) return "rate must be > 0";
+    if (!(c[wtv::V_BACKLASH] >= 0)) return "backlash must be >= 0";
+    if (!whole_in(c[wtv::V_DELAY], 0, wtv::MAX_DELAY)) return "delay must be an integer in 0..8";
+    if (!whole_in(c[wtv::V_FAULT], 0, 2)) return "fault must be 0 (none), 1 (stuck) or 2 (fail_to)";
+    if (!(c[wtv::V_T_REPAIR] >= c[wtv::V_T_FAULT])) return "t_repair must be >= t_fault";
+    if (c[wtv::V_FAULT] == wtv::F_FAIL_TO) {
+        const double fv = c[wtv::V_FAIL_VALUE];
+        if (k == wtv::CH_INLET && !(fv > wtv::INLET_MIN && fv <= wtv::limit_of(k)))
+            return "an inlet fail_to fail_value must be in (0.1, 20]";
+        if (k != wtv::CH_INLET && !(fv >= 0 && fv <= wtv::limit_of(k)))
+            return "a fail_to fail_value must be in [0, limit]: 2 for acid, 1 for chlorine";
+    }
+    return nullptr;
+}
+
+const char *disturb_finite(int, const double *c)
+{
+    for (int v = 0; v < wtd::ND; ++v)
+        if (!std::isfinite(c[v]) && !(v == wtd::D_T_END && c[v] == INFINITY))
+            return "disturbance parameters must be finite (t_end may be +inf)";
+    return nullptr;
+}
+
+const char *disturb_rule(int, const double *c)
+{
+    const double kind = c[wtd::D_KIND], row = c[wtd::D_ROW];
+    if (!whole_in(kind, 0, wtd::N_KINDS - 1)) return "kind must be an integer in 0..4 (off, step, ramp, sine, ou)";
+    if (!whole_in(row, 0, wtd::NB - 1)) return "row must be a boundary row: 1, 2, 3, 5, 7, 8 or 9";
+    if (!wtd::row_allowed((int)row))
+        return "rows 0, 4 and 6 (inlet, acid and chlorine flow) belong to the command path or the master";
+    if (!(c[wtd::D_T_END] >= c[wtd::D_T_START])) return "t_end must be >= t_start";
+    if (kind == wtd::K_SINE && !(c[wtd::D_B] > 0)) return "a sine needs b (the period) > 0";
+    if (kind == wtd::K_OU && !(c[wtd::D_A] >= 0)) return "an OU slot needs a (sigma) >= 0";
+    if (kind == wtd::K_OU && !(c[wtd::D_B] > 0)) return "an OU slot needs b (tau) > 0";
+    return nullptr;
+}
+
+const char *score_rule(int, const double *c)
+{
+    if (!whole_in(c[wtsc::P_KIND], 0, wtsc::N_KINDS - 1)) return "kind must be 0 (off) or 1 (band)";
+    if (!whole_in(c[wtsc::P_QUANTITY], 0, wtsc::N_QUANTITIES - 1)) return "quantity must be 0 (pH), 1 (chlorine) or 2 (temperature)";
+    if (!whole_in(c[wtsc::P_REDUCE], 0, wtsc::N_REDUCES - 1)) return "reduce must be an integer in 0..3 (zone, min, max, mean)";
+    if (!whole_in(c[wtsc::P_ZONE], -1, 31)) return "zone must be an integer in -1..31 (-1: the last zone, the outlet)";
+    if (std::isnan(c[wtsc::P_LO]) || std::isnan(c[wtsc::P_HI])) return "lo and hi must not be NaN (-inf and +inf leave a side open)";
+    if (!(c[wtsc::P_LO] <= c[wtsc::P_HI])) return "lo must be <= hi";
+    if (!(c[wtsc::P_T_END] >= c[wtsc::P_T_START])) return "t_end must be >= t_start, neither NaN";
+    return nullptr;
+}
+
+const char *detect_rule(int, const double *c)
+{
+    for (int k = 0; k < wtk::NK; ++k)
+        if (!std::isfinite(c[k]) && !(k == wtk::K_T_ARM && c[k] == -INFINITY))
+            return "detector parameters must be finite (t_arm may be -inf)";
+    const double kind = c[wtk::K_KIND], ref = c[wtk::K_REF], slack = c[wtk::K_SLACK];
+    if (!whole_in(kind, 0, wtk::N_KINDS - 1)) return "kind must be 0 (off), 1 (cusum), 2 (ewma) or 3 (flatline)";
+    if (kind == wtk::D_OFF) return nullptr;                // the other rows of an OFF slot are not read
+    if (!whole_in(c[wtk::K_SENSOR], 0, WT_N_SENSORS - 1)) return "sensor must be an integer in 0..6";
+    if (!whole_in(c[wtk::K_SOURCE], 0, 1)) return "source must be 0 (image) or 1 (field)";
+    if (!whole_in(ref, 0, wtk::N_REFS - 1)) return "ref must be 0 (const), 1 (sensor) or 2 (track)";
+    if (ref == wtk::REF_SENSOR) {
+        if (!whole_in(c[wtk::K_REF_ARG], 0, WT_N_SENSORS - 1)) return "a SENSOR reference's ref_arg must be a sensor index in 0..6";
+        if (!whole_in(c[wtk::K_REF_SOURCE], 0, 1)) return "ref_source must be 0 (image) or 1 (field)";
+    }
+    if (ref == wtk::REF_TRACK && !(c[wtk::K_REF_ARG] > 0)) return "a TRACK reference's ref_arg (tau) must be > 0";
+    if (!(c[wtk::K_SIGMA] > 0)) return "sigma must be > 0";
+    if (kind == wtk::D_CUSUM && !(slack >= 0)) return "a CUSUM slot's slack (k) must be >= 0";
+    if (kind == wtk::D_EWMA && !(slack > 0 && slack <= 1)) return "an EWMA slot's slack (lambda) must be in (0, 1]";
+    if (kind == wtk::D_FLATLINE && !(slack >= 0)) return "a FLATLINE slot's slack (eps) must be >= 0";
+    if (!(c[wtk::K_LIMIT] > 0)) return "limit must be > 0";
+    if (!whole_in(c[wtk::K_ON_BAD], 0, 1)) return "on_bad must be 0 (hold) or 1 (alarm)";
+    return nullptr;
+}
+
+const char *trend_rule(int, const double *c)
+{
+    const double tag = c[wtt::T_TAG];
+    if (!whole_in(tag, 0, wtt::N_TAGS - 1)) return "tag must be an integer in 0..11 (0: off)";
+    if (tag == wtt::G_OFF) return nullptr;                 // the other rows of an OFF slot are not read
+    if (!whole_in(c[wtt::T_INDEX], 0, wtt::index_range((int)tag) - 1)) return "index must be an integer within the tag's range";
+    if (!whole_in(c[wtt::T_EVERY], 1, 9007199254740991.0)) return "every must be an integer >= 1";   // whole numbers below 2^53
+    if (std::isnan(c[wtt::T_DEADBAND])) return "deadband must not be NaN (negative: every candidate is recorded)";
+    if (std::isnan(c[wtt::T_T_START]) || std::isnan(c[wtt::T_T_END])) return "t_start and t_end must not be NaN";
+    if (!(c[wtt::T_T_END] >= c[wtt::T_T_START])) return "t_end must be >= t_start";
+    return nullptr;
+}
+
+// Walks a [slots][fields][N] block slot by slot, reactor by reactor, and hands each row vector to `rule`: the first
+// message, so the first failing rule of the first bad reactor of the first bad slot is the one named.
+const char *block_error(const double *p, int slots, int fields, int64_t N, Rule rule)
+{
+    std::vector<double> c((size_t)fields);
+    for (int s = 0; s < slots; ++s)
         for (int64_t r = 0; r < N; ++r) {
-            double c[wtc::NC];
-            for (int k = 0; k < wtc::NC; ++k) {
-                c[k] = p[((int64_t)l * wtc::NC + k) * N + r];
-                if (!std::isfinite(c[k])) return "control parameters must be finite";
-            }
-            if (c[wtc::C_ENABLE] != 0.0 && c[wtc::C_ENABLE] != 1.0) return "enable must be 0 or 1";
-            const double sensor = c[wtc::C_SENSOR];
-            if (sensor != std::floor(sensor) || sensor < 0 || sensor >= WT_N_SENSORS) return "sensor must be an integer in 0..6";
-            if (c[wtc::C_DIRECTION] != 1.0 && c[wtc::C_DIRECTION] != -1.0) return "direction must be +1 or -1";
-            if (!(c[wtc::C_KP] >= 0) || !(c[wtc::C_KI] >= 0)) return "kp and ki must be >= 0";
-            if (!(c[wtc::C_OUT_MIN] <= c[wtc::C_OUT_MAX])) return "out_min must not exceed out_max";
+            for (int k = 0; k < fields; ++k) c[(size_t)k] = p[((int64_t)s * fields + k) * N + r];
+            if (const char *msg = rule(s, c.data())) return msg;
         }
     return nullptr;
 }
 
-// The preconditions shared by the set calls of the scan programs, in this order: the arguments, plant I/O on
-// (needs_plc: the refusal), the zone limit (zones: the refusal; nullptr: every kernel carries the program), a state
-// refusal of the caller's (nullptr: none), then the parameter block through wt_program_check.
-int check_program_set(const wt_ensemble *h, const double *params, int program, const char *needs_plc, const char *zones,
-                      const char *refusal = nullptr)
+// -- restart functions: the program's state at its set-time values (set, and reset where the program has one).  The
+// arrays exist; the work is queued on the handle's stream, and a restart that uploads from host vectors synchronises
+// before it returns them.
+
+int upload(wt_ensemble *h, double *dst, const std::vector<double> &src)
 {
+    HIP_TRY(hipMemcpyAsync(dst, src.data(), sizeof(double) * src.size(), hipMemcpyHostToDevice, h->stream));
+    return WT_OK;
+}
+
+// the reactors' loop time now (the download also waits for queued launches, which may still use the old records)
+int loop_time(wt_ensemble *h, std::vector<double> &lt)
+{
+    lt.resize((size_t)h->N);
+    return download(h, {{lt.data(), h->sens.pack.loop_time, sizeof(double) * lt.size()}});
+}
+
+int inject_restart(wt_ensemble *h)
+{
+    std::vector<double> st((size_t)h->N * wti::ST_DOUBLES);
+    for (size_t i = 0; i < st.size(); i += wti::NIS) {
+        double *q = st.data() + i;
+        q[wti::IS_N_APPLIED] = 0.0; q[wti::IS_T_FIRST] = q[wti::IS_T_LAST] = q[wti::IS_HELD] = NAN;
+    }
+    if (int rc = upload(h, h->inj.st, st)) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));   // the host vector is freed on return
+    return WT_OK;
+}
+
+int alarm_restart(wt_ensemble *h)
+{
+    const int64_t N = h->N;
+    std::vector<double> st((size_t)N * wta::ST_DOUBLES, 0.0), rst((size_t)N * wta::RST_DOUBLES, 0.0), lt;
+    for (size_t i = 0; i < st.size(); i += wta::NAS) {
+        double *q = st.data() + i;
+        q[wta::AS_PENDING] = q[wta::AS_T_FIRST] = q[wta::AS_T_LAST] = NAN;
+    }
+    if (int rc = loop_time(h, lt)) return rc;
+    for (int64_t r = 0; r < N; ++r) {
+        double *q = rst.data() + r * wta::RST_DOUBLES;
+        q[wta::AR_T_PREV] = lt[(size_t)r]; q[wta::AR_FIRST_OUT] = -1.0; q[wta::AR_OVR_ACID] = q[wta::AR_OVR_CHLORINE] = NAN;
+    }
+    if (int rc = upload(h, h->alm.st, st)) return rc;
+    if (int rc = upload(h, h->alm.rst, rst)) return rc;
+    HIP_TRY(hipMemsetAsync(h->alm.word, 0, sizeof(uint16_t) * (size_t)N, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // the host vectors are freed on return
+    return WT_OK;
+}
+
+// every element at its boundary row in force, the queue filled with it, t_prev the loop time
+int actuator_restart(wt_ensemble *h)
+{
+    const int64_t N = h->N;
+    std::vector<double> st((size_t)N * wtv::ST_DOUBLES, 0.0), q((size_t)N * wtv::Q_DOUBLES), lt((size_t)N), bc((size_t)N * wt::NB);
+    // (the download also waits for queued launches, which may still read or write the old records)
+    if (int rc = download(h, {{lt.data(), h->sens.pack.loop_time, sizeof(double) * lt.size()}, {bc.data(), h->bc, sizeof(double) * bc.size()}}))
+        return rc;
+    for (int64_t r = 0; r < N; ++r)
+        for (int k = 0; k < wtv::CH; ++k) {
+            const double row = bc[(size_t)(wtv::row_of(k) * N + r)];
+            double *s = st.data() + r * wtv::ST_DOUBLES + k * wtv::NVS;
+            s[wtv::VS_POSITION] = s[wtv::VS_APPLIED] = s[wtv::VS_PLAY] = s[wtv::VS_DEMAND] = row;
+            for (int i = 0; i < wtv::MAX_DELAY; ++i) q[(size_t)(r * wtv::Q_DOUBLES + k * wtv::MAX_DELAY + i)] = row;
+        }
+    if (int rc = upload(h, h->act.st, st)) return rc;
+    if (int rc = upload(h, h->act.q, q)) return rc;
+    if (int rc = upload(h, h->act.tp, lt)) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));   // the host vectors are freed on return
+    return WT_OK;
+}
+
+// x = 0, counts 0, an empty history, base = the boundary in force, t_prev = ReactorState.time, then one evaluation
+int disturb_restart(wt_ensemble *h)
+{
+    const size_t N = (size_t)h->N;
+    HIP_TRY(hipMemsetAsync(h->dst.st, 0, sizeof(double) * wtd::ST_DOUBLES * N, h->stream));
+    if (h->dst.hist) HIP_TRY(hipMemsetAsync(h->dst.hist, 0, sizeof(double) * wtd::SLOTS * (size_t)h->dst.hist_cap * N, h->stream));   // entries not filled: 0
+    HIP_TRY(hipMemcpyAsync(h->dst.base, h->bc, sizeof(double) * WT_NB * N, hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->dst.tp, h->time, sizeof(double) * N, hipMemcpyDeviceToDevice, h->stream));
+    return disturb_op(h, wtd::OP_SET);
+}
+
+// the accumulators and the curve at their set-time values, t_prev = ReactorState.time, j = 0
+int score_restart(wt_ensemble *h)
+{
+    const size_t cells = (size_t)h->scr.curve_cap * wtsc::SLOTS;
+    const wtsc::HostOpArgs a{h->scr.st, h->scr.tp, h->time, h->N};
+    hipLaunchKernelGGL(wtsc::host_op_kernel, dim3((unsigned)((h->N + 255) / 256)), dim3(256), 0, h->stream, a);
+    HIP_TRY(hipGetLastError());
+    if (h->scr.counts) HIP_TRY(hipMemsetAsync(h->scr.counts, 0, sizeof(int32_t) * 3 * cells, h->stream));
+    if (h->scr.fan) HIP_TRY(hipMemsetAsync(h->scr.fan, 0, sizeof(int32_t) * (size_t)(h->scr.bins + 2) * cells, h->stream));
+    h->scr_steps = 0;
+    return WT_OK;
+}
+
+// slot state and t_prev at their set-time values, t_prev = the reactors' loop time now
+int detect_restart(wt_ensemble *h)
+{
+    std::vector<double> st((size_t)h->N * wtk::ST_DOUBLES, 0.0), lt;
+    for (size_t i = 0; i < st.size(); i += wtk::NKS) {
+        double *q = st.data() + i;
+        q[wtk::KS_BASELINE] = q[wtk::KS_X_PREV] = q[wtk::KS_T_FIRST] = q[wtk::KS_T_DETECT] = NAN;
+    }
+    if (int rc = loop_time(h, lt)) return rc;
+    if (int rc = upload(h, h->det.st, st)) return rc;
+    if (int rc = upload(h, h->det.tp, lt)) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));   // the host vectors are freed on return
+    return WT_OK;
+}
+
+// slot state at its set-time values (0, 0, 0, NaN) and an all-NaN store
+int trend_restart(wt_ensemble *h)
+{
+    std::vector<double> st((size_t)h->N * wtt::ST_DOUBLES, 0.0);
+    for (size_t i = 0; i < st.size(); i += wtt::NTS) st[i + wtt::TS_LAST] = NAN;
+    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still write the old records
+    if (int rc = upload(h, h->trd.st, st)) return rc;
+    // every byte 0xff: a NaN in both halves of every sample
+    HIP_TRY(hipMemsetAsync(h->trd.store, 0xff, sizeof(double2) * wtt::SLOTS * (size_t)h->trd.cap * (size_t)h->N, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // the host vector is freed on return
+    return WT_OK;
+}
+
+// -- the descriptors, indexed by WT_PROG_*
+
+enum Needs { NEEDS_PLANT_IO, NEEDS_STATE, NEEDS_STATE_AND_BOUNDARY };
+
+struct Program {
+    const char *not_set;                  // refusal of get, reset and the other read calls while no program is set
+    Needs needs; const char *needs_text;  // what a set call needs first, and its refusal
+    const char *zones;                    // refusal above 32 zones (nullptr: every kernel carries the program)
+    int slots, fields;                    // the parameter block is [slots][fields][N], a record slots * fields doubles
+    Rule first_pass, rule;                // first_pass (nullptr: none) runs over the whole block before rule does
+    ArrayGroup (*arrays)(wt_ensemble *);  // switch and arrays; the parameter records are the group's first array
+    int (*restart)(wt_ensemble *);        // nullptr: control_load builds the state, loop by loop
+};
+
+const Program k_programs[] = {
+    {"control is off (wt_ensemble_control_enable)", NEEDS_PLANT_IO, "control writes the holding image: enable plant I/O first",
+     nullptr, wtc::LOOPS, wtc::NC, nullptr, control_rule, control_arrays, nullptr},
+    {"no injection program is set (wt_ensemble_inject_set)", NEEDS_PLANT_IO, "injection acts on the plant I/O images: enable plant I/O first",
+     "injection programs run in the kernels for up to 32 zones", wti::SLOTS, wti::NI, nullptr, inject_rule, inject_arrays, inject_restart},
+    {"no alarm program is set (wt_ensemble_alarm_set)", NEEDS_PLANT_IO, "alarms act on the plant I/O scan: enable plant I/O first",
+     "alarm programs run in the kernels for up to 32 zones", wta::SLOTS, wta::NA, nullptr, alarm_rule, alarm_arrays, alarm_restart},
+    {"no actuator program is set (wt_ensemble_actuator_set)", NEEDS_PLANT_IO, "actuators act on the plant I/O scan: enable plant I/O first",
+     "actuator programs run in the kernels for up to 32 zones", wtv::CH, wtv::NV, actuator_finite, actuator_rule, actuator_arrays, actuator_restart},
+    {"no disturbance program is set (wt_ensemble_disturb_set)", NEEDS_STATE_AND_BOUNDARY, "set_state and set_boundary must precede disturb_set",
+     "disturbance programs run in the kernels for up to 32 zones", wtd::SLOTS, wtd::ND, disturb_finite, disturb_rule, disturb_arrays, disturb_restart},
+    {"no score program is set (wt_ensemble_score_set)", NEEDS_STATE, "set_state must precede score_set",
+     "score programs run in the kernels for up to 32 zones", wtsc::SLOTS, wtsc::NSP, nullptr, score_rule, score_arrays, score_restart},
+    {"no detector program is set (wt_ensemble_detect_set)", NEEDS_PLANT_IO, "detectors read the plant I/O scan: enable plant I/O first",
+     "detector programs run in the kernels for up to 32 zones", wtk::SLOTS, wtk::NK, nullptr, detect_rule, detect_arrays, detect_restart},
+    {"no trend program is set (wt_ensemble_trend_set)", NEEDS_PLANT_IO, "trends read the plant I/O scan: enable plant I/O first",
+     "trend programs run in the kernels for up to 32 zones", wtt::SLOTS, wtt::NT, nullptr, trend_rule, trend_arrays, trend_restart},
+};
+constexpr int N_PROGRAMS = (int)(sizeof k_programs / sizeof *k_programs);
+static_assert(WT_PROG_CONTROL == 0 && WT_PROG_INJECT == 1 && WT_PROG_ALARM == 2 && WT_PROG_ACTUATOR == 3 && WT_PROG_DISTURB == 4 &&
+              WT_PROG_SCORE == 5 && WT_PROG_DETECT == 6 && WT_PROG_TREND == 7 && N_PROGRAMS == 8, "k_programs is indexed by WT_PROG_*");
+
+// -- the lifecycle
+
+// The preconditions of a set call, in this order: the arguments, what the program needs first, the zone limit.  The
+// parameter block itself goes through wt_program_check.
+int check_program_set(const wt_ensemble *h, int program, const double *params)
+{
+    const Program &p = k_programs[program];
     if (!h || !params) return fail(WT_E_ARG, "NULL argument");
-    if (!h->sens.plc_on) return fail(WT_E_STATE, needs_plc);
-    if (zones && !wt::prog_in_item(levels_for(h->n))) return fail(WT_E_STATE, zones);
-    if (refusal) return fail(WT_E_STATE, refusal);
-    return wt_program_check(program, params, h->N);
+    const bool met = p.needs == NEEDS_PLANT_IO ? h->sens.plc_on != 0 : h->have_state && (p.needs == NEEDS_STATE || h->have_bc);
+    if (!met) return fail(WT_E_STATE, p.needs_text);
+    if (p.zones && !wt::prog_in_item(levels_for(h->n))) return fail(WT_E_STATE, p.zones);
+    return WT_OK;
+}
+
+// The rest of a set call once the call is accepted and its sizes and settings are in the handle: the arrays (those of
+// a running program are used again), the parameter records, the restart function, the switch.  A failure leaves the
+// program off, with neither arrays nor capacities.
+int load_program(wt_ensemble *h, int program, const double *params)
+{
+    const Program &p = k_programs[program];
+    const ArrayGroup g = p.arrays(h);
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still read or write the old records
+    if (int rc = allocate(g)) return rc;
+    std::vector<double> par((size_t)h->N * p.slots * p.fields);
+    blocks_to_records(params, p.slots, p.fields, h->N, par.data(), p.slots * p.fields);
+    int rc = upload(h, (double *)*g.arrays[0].first, par);
+    if (rc == WT_OK) rc = p.restart(h);
+    if (rc == WT_OK) rc = sync_checked(h);      // the host vector is freed on return
+    if (rc != WT_OK) { release(g); return rc; }
+    *g.on = 1;
+    return WT_OK;
+}
+
+// The start of get, reset and every other call that needs a program set: the handle, the refusal, the device.
+int program_ready(wt_ensemble *h, int program)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    if (!*k_programs[program].arrays(h).on) return fail(WT_E_STATE, k_programs[program].not_set);
+    HIP_TRY(hipSetDevice(h->device));
+    return WT_OK;
+}
+
+int get_program(wt_ensemble *h, int program, const std::vector<Records> &records)
+{
+    if (int rc = program_ready(h, program)) return rc;
+    return download_records(h, records);
+}
+
+int reset_program(wt_ensemble *h, int program)
+{
+    if (int rc = program_ready(h, program)) return rc;
+    if (int rc = k_programs[program].restart(h)) return rc;
+    return sync_checked(h);
+}
+
+// clear, and a set that replaces a program whose capacities may change: program off, arrays released, capacities 0
+int stop_program(wt_ensemble *h, int program)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still use the records
+    release(k_programs[program].arrays(h));
+    return WT_OK;
 }
 
 // Enable (retune == false) or retune the PI programs.  A loop starts -- integral 0, output and holding words the
 // float32 of the clamped bias, metrics 0 -- where enable switches it on; retune keeps the state of the other loops.
 int control_load(wt_ensemble *h, const double *params, bool retune)
 {
+    if (!h) return fail(WT_E_ARG, "NULL handle");
     if (!params) return fail(WT_E_ARG, "params is NULL");
-    if (int rc = check_program_set(h, params, WT_PROG_CONTROL, "control writes the holding image: enable plant I/O first", nullptr,
-                                   retune && !h->ctl.on ? "control is off (wt_ensemble_control_enable)" : nullptr))
-        return rc;
+    if (int rc = check_program_set(h, WT_PROG_CONTROL, params)) return rc;
+    if (retune && !h->ctl.on) return fail(WT_E_STATE, k_programs[WT_PROG_CONTROL].not_set);
+    if (int rc = wt_program_check(WT_PROG_CONTROL, params, h->N)) return rc;
     HIP_TRY(hipSetDevice(h->device));
     const int64_t N = h->N;
     const size_t par_bytes = sizeof(double) * wtc::PAR_DOUBLES * (size_t)N, st_bytes = sizeof(double) * wtc::ST_DOUBLES * (size_t)N;
@@ -1075,147 +1455,6 @@ int control_load(wt_ensemble *h, const double *params, bool retune)
     return WT_OK;
 }
 
-} // namespace
-
-extern "C" {
-
-int wt_ensemble_control_enable(wt_ensemble *h, const double *params)
-{
-    if (!h) return fail(WT_E_ARG, "NULL handle");
-    return control_load(h, params, false);
-}
-
-int wt_ensemble_control_retune(wt_ensemble *h, const double *params)
-{
-    if (!h) return fail(WT_E_ARG, "NULL handle");
-    return control_load(h, params, true);
-}
-
-int wt_ensemble_control_get(wt_ensemble *h, double *state)
-{
-    if (!h || !state) return fail(WT_E_ARG, "NULL argument");
-    if (!h->ctl.on) return fail(WT_E_STATE, "control is off (wt_ensemble_control_enable)");
-    HIP_TRY(hipSetDevice(h->device));
-    return download_records(h, {{state, h->ctl.st, wtc::ST_DOUBLES, wtc::LOOPS, wtc::NCS}});
-}
-
-int wt_ensemble_control_disable(wt_ensemble *h)
-{
-    if (!h) return fail(WT_E_ARG, "NULL handle");
-    return stop_program(h, control_arrays(h));
-}
-
-} // extern "C"
-
-namespace {
-
-static_assert(WT_INJ_SLOTS == wti::SLOTS && WT_NI == wti::NI && WT_NIS == wti::NIS, "injection blocks of the C ABI");
-static_assert(WT_INJ_N_TARGETS == wti::N_TARGETS && WT_INJ_CMD_ACID == wti::CMD_ACID && WT_INJ_CMD_CHLORINE == wti::CMD_CHLORINE &&
-              WT_INJ_CMD_INLET == wti::CMD_INLET && WT_INJ_FAULT == wti::M_FAULT && WT_INJ_FAULT + 1 == wti::N_MODES,
-              "injection targets and modes of the C ABI");
-
-// Host-side checks of a [WT_INJ_SLOTS][WT_NI][N] program; nullptr when it is valid.
-const char *inject_params_error(const double *p, int64_t N)
-{
-    for (int s = 0; s < wti::SLOTS; ++s)
-        for (int64_t r = 0; r < N; ++r) {
-            double c[wti::NI];
-            for (int k = 0; k < wti::NI; ++k) c[k] = p[((int64_t)s * wti::NI + k) * N + r];
-            for (int k = 0; k < wti::NI; ++k)
-                if (!std::isfinite(c[k]) && !(k == wti::I_T_END && c[k] == INFINITY))
-                    return "injection parameters must be finite (end may be +inf)";
-            const double mode = c[wti::I_MODE], target = c[wti::I_TARGET];
-            if (mode != std::floor(mode) || mode < 0 || mode >= wti::N_MODES) return "mode must be an integer in 0..7";
-            if (target != std::floor(target) || target < 0 || target >= wti::N_TARGETS) return "target must be an integer in 0..9";
-            if (c[wti::I_T_START] > c[wti::I_T_END]) return "start must not exceed end";
-            if (mode == wti::M_FAULT) {
-                if (target >= wti::CMD_ACID) return "a FAULT slot must target a sensor";
-                const double a = c[wti::I_A];
-                if (a != std::floor(a) || a < 1 || a > 6) return "a FAULT slot's fault code (a) must be an integer in 1..6";
-            }
-        }
-    return nullptr;
-}
-
-} // namespace
-
-extern "C" {
-
-int wt_ensemble_inject_set(wt_ensemble *h, const double *params)
-{
-    if (int rc = check_program_set(h, params, WT_PROG_INJECT, "injection acts on the plant I/O images: enable plant I/O first",
-                                   "injection programs run in the kernels for up to 32 zones"))
-        return rc;
-    HIP_TRY(hipSetDevice(h->device));
-    const int64_t N = h->N;
-    const size_t par_bytes = sizeof(double) * wti::PAR_DOUBLES * (size_t)N, st_bytes = sizeof(double) * wti::ST_DOUBLES * (size_t)N;
-    std::vector<double> par((size_t)N * wti::PAR_DOUBLES), st((size_t)N * wti::ST_DOUBLES);
-    blocks_to_records(params, wti::SLOTS, wti::NI, N, par.data(), wti::PAR_DOUBLES);
-    for (int64_t r = 0; r < N; ++r)
-        for (int s = 0; s < wti::SLOTS; ++s) {
-            double *q = st.data() + r * wti::ST_DOUBLES + s * wti::NIS;
-            q[wti::IS_N_APPLIED] = 0.0; q[wti::IS_T_FIRST] = q[wti::IS_T_LAST] = q[wti::IS_HELD] = NAN;
-        }
-    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still read or write the old records
-    if (int rc = allocate(inject_arrays(h))) return rc;
-    HIP_TRY(hipMemcpyAsync((double *)h->inj.par, par.data(), par_bytes, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->inj.st, st.data(), st_bytes, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));   // the host vectors are freed on return
-    h->inj.on = 1;
-    return WT_OK;
-}
-
-int wt_ensemble_inject_get(wt_ensemble *h, double *state)
-{
-    if (!h || !state) return fail(WT_E_ARG, "NULL argument");
-    if (!h->inj.on) return fail(WT_E_STATE, "no injection program is set (wt_ensemble_inject_set)");
-    HIP_TRY(hipSetDevice(h->device));
-    return download_records(h, {{state, h->inj.st, wti::ST_DOUBLES, wti::SLOTS, wti::NIS}});
-}
-
-int wt_ensemble_inject_clear(wt_ensemble *h)
-{
-    if (!h) return fail(WT_E_ARG, "NULL handle");
-    return stop_program(h, inject_arrays(h));
-}
-
-} // extern "C"
-
-namespace {
-
-static_assert(WT_ALM_SLOTS == wta::SLOTS && WT_NA == wta::NA && WT_NAS == wta::NAS && WT_NAR == wta::NAR, "alarm blocks of the C ABI");
-static_assert(WT_ALM_HIGH == wta::K_HIGH && WT_ALM_LOW == wta::K_LOW && WT_ALM_FIELD == wta::SRC_FIELD &&
-              WT_ALM_ALARM == wta::ON_BAD_ALARM && WT_ALM_TRIP_ACID == wta::ACT_TRIP_ACID &&
-              WT_ALM_TRIP_CHLORINE == wta::ACT_TRIP_CHLORINE && WT_ALM_TRIP_CHLORINE + 1 == wta::N_ACTIONS,
-              "alarm kinds, sources and actions of the C ABI");
-static_assert(WT_A_TRIP_VALUE == wta::A_TRIP_VALUE && WT_AS_N_BAD == wta::AS_N_BAD && WT_AR_N_OVR_CHLORINE == wta::AR_N_OVR_CHLORINE,
-              "alarm rows of the C ABI");
-
-// Host-side checks of a [WT_ALM_SLOTS][WT_NA][N] program; nullptr when it is valid.
-const char *alarm_params_error(const double *p, int64_t N)
-{
-    const auto is_int_in = [](double x, int lo, int hi) { return x == std::floor(x) && x >= lo && x <= hi; };
-    for (int s = 0; s < wta::SLOTS; ++s)
-        for (int64_t r = 0; r < N; ++r) {
-            double c[wta::NA];
-            for (int k = 0; k < wta::NA; ++k) c[k] = p[((int64_t)s * wta::NA + k) * N + r];
-            for (int k = 0; k < wta::NA; ++k)
-                if (!std::isfinite(c[k])) return "alarm parameters must be finite";
-            if (!is_int_in(c[wta::A_KIND], 0, 2)) return "kind must be 0 (off), 1 (high) or 2 (low)";
-            if (!is_int_in(c[wta::A_SENSOR], 0, WT_N_SENSORS - 1)) return "sensor must be an integer in 0..6";
-            if (!is_int_in(c[wta::A_SOURCE], 0, 1)) return "source must be 0 (image) or 1 (field)";
-            if (c[wta::A_DEADBAND] < 0) return "deadband must be >= 0";
-            if (c[wta::A_ON_DELAY] < 0) return "on_delay must be >= 0";
-            if (!is_int_in(c[wta::A_LATCH], 0, 1)) return "latch must be 0 or 1";
-            if (!is_int_in(c[wta::A_ON_BAD], 0, 1)) return "on_bad must be 0 (hold) or 1 (alarm)";
-            if (!is_int_in(c[wta::A_ACTION], 0, 2)) return "action must be 0 (none), 1 (trip_acid) or 2 (trip_chlorine)";
-            const double tv = c[wta::A_TRIP_VALUE];
-            if (c[wta::A_ACTION] == wta::ACT_TRIP_ACID && !(tv >= 0 && tv <= 2.0)) return "a trip_acid slot's trip_value must be in [0, 2]";
-            if (c[wta::A_ACTION] == wta::ACT_TRIP_CHLORINE && !(tv >= 0 && tv <= 1.0)) return "a trip_chlorine slot's trip_value must be in [0, 1]";
-        }
-    return nullptr;
-}
-
 // ovr_*, first_out and the word of reactor r from its slot records and state (after a reset)
 uint16_t alarm_settle(const double *par, const double *st, double *rst)
 {
@@ -1241,59 +1480,97 @@ uint16_t alarm_settle(const double *par, const double *st, double *rst)
     return (uint16_t)word;
 }
 
-const char *k_no_alarm = "no alarm program is set (wt_ensemble_alarm_set)";
+// before a disturbance program's arrays go (clear, a set over a program): the targeted rows back to the base
+int disturb_restore(wt_ensemble *h)
+{
+    HIP_TRY(hipSetDevice(h->device));
+    if (!h->dst.on) return WT_OK;
+    if (int rc = disturb_op(h, wtd::OP_RESTORE)) return rc;
+    return sync_checked(h);
+}
 
 } // namespace
 
 extern "C" {
 
+int wt_ensemble_destroy(wt_ensemble *h)
+{
+    if (!h) return WT_OK;
+    (void)hipSetDevice(h->device);
+    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    for (const auto arrays : {core_arrays, sensor_arrays, plant_io_arrays, record_arrays}) release(arrays(h));
+    for (const Program &p : k_programs) release(p.arrays(h));
+    free_and_null(h->trace); free_and_null(h->wave_diag); free_and_null(h->snap_dev); free_and_null(h->sched);
+    free_and_null(h->diag_out);
+    for (int s = 0; s < WT_MAX_STREAMS; ++s) {
+        if (h->sub_stream[s]) { (void)hipStreamSynchronize(h->sub_stream[s]); (void)hipStreamDestroy(h->sub_stream[s]); }
+        if (h->sub_done[s]) (void)hipEventDestroy(h->sub_done[s]);
+    }
+    if (h->snap_host) (void)hipHostFree(h->snap_host);
+    if (h->err_host) (void)hipHostFree(h->err_host);
+    for (hipEvent_t e : h->lt_pool) (void)hipEventDestroy(e);
+    if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
+    if (h->ev0) (void)hipEventDestroy(h->ev0);
+    if (h->ev1) (void)hipEventDestroy(h->ev1);
+    if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
+    delete h;
+    return WT_OK;
+}
+
+int wt_program_check(int program, const double *params, int64_t n_reactors)
+{
+    if (!params) return fail(WT_E_ARG, "params is NULL");
+    if (n_reactors < 1) return fail(WT_E_ARG, "n_reactors must be >= 1");
+    if (program < 0 || program >= N_PROGRAMS) return fail(WT_E_ARG, "unknown program");
+    const Program &p = k_programs[program];
+    const char *msg = p.first_pass ? block_error(params, p.slots, p.fields, n_reactors, p.first_pass) : nullptr;
+    if (!msg) msg = block_error(params, p.slots, p.fields, n_reactors, p.rule);
+    return msg ? fail(WT_E_ARG, msg) : WT_OK;
+}
+
+int wt_ensemble_control_enable(wt_ensemble *h, const double *params) { return control_load(h, params, false); }
+int wt_ensemble_control_retune(wt_ensemble *h, const double *params) { return control_load(h, params, true); }
+
+int wt_ensemble_control_get(wt_ensemble *h, double *state)
+{
+    if (!h || !state) return fail(WT_E_ARG, "NULL argument");
+    return get_program(h, WT_PROG_CONTROL, {{state, h->ctl.st, wtc::ST_DOUBLES, wtc::LOOPS, wtc::NCS}});
+}
+
+int wt_ensemble_control_disable(wt_ensemble *h) { return stop_program(h, WT_PROG_CONTROL); }
+
+int wt_ensemble_inject_set(wt_ensemble *h, const double *params)
+{
+    if (int rc = check_program_set(h, WT_PROG_INJECT, params)) return rc;
+    if (int rc = wt_program_check(WT_PROG_INJECT, params, h->N)) return rc;
+    return load_program(h, WT_PROG_INJECT, params);
+}
+
+int wt_ensemble_inject_get(wt_ensemble *h, double *state)
+{
+    if (!h || !state) return fail(WT_E_ARG, "NULL argument");
+    return get_program(h, WT_PROG_INJECT, {{state, h->inj.st, wti::ST_DOUBLES, wti::SLOTS, wti::NIS}});
+}
+
+int wt_ensemble_inject_clear(wt_ensemble *h) { return stop_program(h, WT_PROG_INJECT); }
+
 int wt_ensemble_alarm_set(wt_ensemble *h, const double *params)
 {
-    if (int rc = check_program_set(h, params, WT_PROG_ALARM, "alarms act on the plant I/O scan: enable plant I/O first",
-                                   "alarm programs run in the kernels for up to 32 zones"))
-        return rc;
-    HIP_TRY(hipSetDevice(h->device));
-    const int64_t N = h->N;
-    const size_t par_bytes = sizeof(double) * wta::PAR_DOUBLES * (size_t)N, st_bytes = sizeof(double) * wta::ST_DOUBLES * (size_t)N;
-    const size_t rst_bytes = sizeof(double) * wta::RST_DOUBLES * (size_t)N, word_bytes = sizeof(uint16_t) * (size_t)N;
-    std::vector<double> par((size_t)N * wta::PAR_DOUBLES), st((size_t)N * wta::ST_DOUBLES, 0.0), rst((size_t)N * wta::RST_DOUBLES, 0.0);
-    std::vector<double> lt((size_t)N);
-    blocks_to_records(params, wta::SLOTS, wta::NA, N, par.data(), wta::PAR_DOUBLES);
-    for (int64_t r = 0; r < N; ++r)
-        for (int s = 0; s < wta::SLOTS; ++s) {
-            double *q = st.data() + r * wta::ST_DOUBLES + s * wta::NAS;
-            q[wta::AS_PENDING] = q[wta::AS_T_FIRST] = q[wta::AS_T_LAST] = NAN;
-        }
-    // (the download also waits for queued launches, which may still read or write the old records)
-    if (int rc = download(h, {{lt.data(), h->sens.pack.loop_time, sizeof(double) * (size_t)N}})) return rc;
-    for (int64_t r = 0; r < N; ++r) {
-        double *q = rst.data() + r * wta::RST_DOUBLES;
-        q[wta::AR_T_PREV] = lt[(size_t)r]; q[wta::AR_FIRST_OUT] = -1.0; q[wta::AR_OVR_ACID] = q[wta::AR_OVR_CHLORINE] = NAN;
-    }
-    if (int rc = allocate(alarm_arrays(h))) return rc;
-    HIP_TRY(hipMemcpyAsync((double *)h->alm.par, par.data(), par_bytes, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->alm.st, st.data(), st_bytes, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->alm.rst, rst.data(), rst_bytes, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemsetAsync(h->alm.word, 0, word_bytes, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));   // the host vectors are freed on return
-    h->alm.on = 1;
-    return WT_OK;
+    if (int rc = check_program_set(h, WT_PROG_ALARM, params)) return rc;
+    if (int rc = wt_program_check(WT_PROG_ALARM, params, h->N)) return rc;
+    return load_program(h, WT_PROG_ALARM, params);
 }
 
 int wt_ensemble_alarm_get(wt_ensemble *h, double *slot_state, double *reactor_state)
 {
     if (!h) return fail(WT_E_ARG, "NULL handle");
-    if (!h->alm.on) return fail(WT_E_STATE, k_no_alarm);
-    HIP_TRY(hipSetDevice(h->device));
-    return download_records(h, {{slot_state, h->alm.st, wta::ST_DOUBLES, wta::SLOTS, wta::NAS},
-                                {reactor_state, h->alm.rst, wta::RST_DOUBLES, 1, wta::NAR}});
+    return get_program(h, WT_PROG_ALARM, {{slot_state, h->alm.st, wta::ST_DOUBLES, wta::SLOTS, wta::NAS},
+                                          {reactor_state, h->alm.rst, wta::RST_DOUBLES, 1, wta::NAR}});
 }
 
 int wt_ensemble_alarm_reset(wt_ensemble *h, const uint8_t *mask)
 {
-    if (!h) return fail(WT_E_ARG, "NULL handle");
-    if (!h->alm.on) return fail(WT_E_STATE, k_no_alarm);
-    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = program_ready(h, WT_PROG_ALARM)) return rc;
     const int64_t N = h->N;
     std::vector<double> par((size_t)N * wta::PAR_DOUBLES), st((size_t)N * wta::ST_DOUBLES), rst((size_t)N * wta::RST_DOUBLES);
     std::vector<uint16_t> word((size_t)N);
@@ -1312,8 +1589,8 @@ int wt_ensemble_alarm_reset(wt_ensemble *h, const uint8_t *mask)
         }
         word[(size_t)r] = alarm_settle(p, q, rst.data() + r * wta::RST_DOUBLES);
     }
-    HIP_TRY(hipMemcpyAsync(h->alm.st, st.data(), sizeof(double) * st.size(), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->alm.rst, rst.data(), sizeof(double) * rst.size(), hipMemcpyHostToDevice, h->stream));
+    if (int rc = upload(h, h->alm.st, st)) return rc;
+    if (int rc = upload(h, h->alm.rst, rst)) return rc;
     HIP_TRY(hipMemcpyAsync(h->alm.word, word.data(), sizeof(uint16_t) * word.size(), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     return WT_OK;
@@ -1322,224 +1599,63 @@ int wt_ensemble_alarm_reset(wt_ensemble *h, const uint8_t *mask)
 int wt_ensemble_alarm_words(wt_ensemble *h, uint16_t *words)
 {
     if (!h || !words) return fail(WT_E_ARG, "NULL argument");
-    if (!h->alm.on) return fail(WT_E_STATE, k_no_alarm);
-    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = program_ready(h, WT_PROG_ALARM)) return rc;
     return download(h, {{words, h->alm.word, sizeof(uint16_t) * (size_t)h->N}});
 }
 
 int wt_ensemble_alarm_device(wt_ensemble *h, void **word)
 {
     if (!h || !word) return fail(WT_E_ARG, "NULL argument");
-    if (!h->alm.on) return fail(WT_E_STATE, k_no_alarm);
+    if (int rc = program_ready(h, WT_PROG_ALARM)) return rc;
     *word = h->alm.word;
     return WT_OK;
 }
 
-int wt_ensemble_alarm_clear(wt_ensemble *h)
-{
-    if (!h) return fail(WT_E_ARG, "NULL handle");
-    return stop_program(h, alarm_arrays(h));
-}
-
-} // extern "C"
-
-namespace {
-
-static_assert(WT_ACT_CHANNELS == wtv::CH && WT_NV == wtv::NV && WT_NVS == wtv::NVS && WT_ACT_MAX_DELAY == wtv::MAX_DELAY,
-              "actuator blocks of the C ABI");
-static_assert(WT_ACT_ACID == wtv::CH_ACID && WT_ACT_CHLORINE == wtv::CH_CHLORINE && WT_ACT_INLET == wtv::CH_INLET &&
-              WT_ACT_INLET + 7 == WT_INJ_CMD_INLET && WT_ACT_STUCK == wtv::F_STUCK && WT_ACT_FAIL_TO == wtv::F_FAIL_TO &&
-              WT_ACT_FAIL_TO + 1 == wtv::N_FAULTS, "actuator channels and faults of the C ABI");
-static_assert(WT_V_FAIL_VALUE == wtv::V_FAIL_VALUE && WT_VS_N_FAULT == wtv::VS_N_FAULT, "actuator rows of the C ABI");
-
-// Host-side checks of a [WT_ACT_CHANNELS][WT_NV][N] program; nullptr when it is valid.
-const char *actuator_params_error(const double *p, int64_t N)
-{
-    const auto is_int_in = [](double x, int lo, int hi) { return x == std::floor(x) && x >= lo && x <= hi; };
-    const auto at = [&](int k, int v, int64_t r) { return p[((int64_t)k * wtv::NV + v) * N + r]; };
-    for (int k = 0; k < wtv::CH; ++k)
-        for (int64_t r = 0; r < N; ++r)
-            for (int v = 0; v < wtv::NV; ++v) {
-                const double x = at(k, v, r);
-                const bool inf_ok = (v == wtv::V_RATE || v == wtv::V_T_REPAIR) && x == INFINITY;
-                if (!std::isfinite(x) && !inf_ok) return "actuator parameters must be finite (rate and t_repair may be +inf)";
-            }
-    for (int k = 0; k < wtv::CH; ++k)
-        for (int64_t r = 0; r < N; ++r) {
-            double c[wtv::NV];
-            for (int v = 0; v < wtv::NV; ++v) c[v] = at(k, v, r);
-            if (!is_int_in(c[wtv::V_ENABLE], 0, 1)) return "enable must be 0 or 1";
-            if (!(c[wtv::V_TAU] >= 0)) return "tau must be >= 0";
-            if (!(c[wtv::V_RATE] > 0)) return "rate must be > 0";
-            if (!(c[wtv::V_BACKLASH] >= 0)) return "backlash must be >= 0";
-            if (!is_int_in(c[wtv::V_DELAY], 0, wtv::MAX_DELAY)) return "delay must be an integer in 0..8";
-            if (!is_int_in(c[wtv::V_FAULT], 0, 2)) return "fault must be 0 (none), 1 (stuck) or 2 (fail_to)";
-            if (!(c[wtv::V_T_REPAIR] >= c[wtv::V_T_FAULT])) return "t_repair must be >= t_fault";
-            if (c[wtv::V_FAULT] == wtv::F_FAIL_TO) {
-                const double fv = c[wtv::V_FAIL_VALUE];
-                if (k == wtv::CH_INLET && !(fv > wtv::INLET_MIN && fv <= wtv::limit_of(k)))
-                    return "an inlet fail_to fail_value must be in (0.1, 20]";
-                if (k != wtv::CH_INLET && !(fv >= 0 && fv <= wtv::limit_of(k)))
-                    return "a fail_to fail_value must be in [0, limit]: 2 for acid, 1 for chlorine";
-            }
-        }
-    return nullptr;
-}
-
-const char *k_no_actuator = "no actuator program is set (wt_ensemble_actuator_set)";
-
-} // namespace
-
-extern "C" {
+int wt_ensemble_alarm_clear(wt_ensemble *h) { return stop_program(h, WT_PROG_ALARM); }
 
 int wt_ensemble_actuator_set(wt_ensemble *h, const double *params)
 {
-    if (int rc = check_program_set(h, params, WT_PROG_ACTUATOR, "actuators act on the plant I/O scan: enable plant I/O first",
-                                   "actuator programs run in the kernels for up to 32 zones"))
-        return rc;
-    HIP_TRY(hipSetDevice(h->device));
-    const int64_t N = h->N;
-    std::vector<double> par((size_t)N * wtv::PAR_DOUBLES), st((size_t)N * wtv::ST_DOUBLES, 0.0), q((size_t)N * wtv::Q_DOUBLES);
-    std::vector<double> lt((size_t)N), bc((size_t)N * wt::NB);
-    blocks_to_records(params, wtv::CH, wtv::NV, N, par.data(), wtv::PAR_DOUBLES);
-    // (the download also waits for queued launches, which may still read or write the old records)
-    if (int rc = download(h, {{lt.data(), h->sens.pack.loop_time, sizeof(double) * lt.size()}, {bc.data(), h->bc, sizeof(double) * bc.size()}}))
-        return rc;
-    for (int64_t r = 0; r < N; ++r)
-        for (int k = 0; k < wtv::CH; ++k) {
-            const double row = bc[(size_t)(wtv::row_of(k) * N + r)];
-            double *s = st.data() + r * wtv::ST_DOUBLES + k * wtv::NVS;
-            s[wtv::VS_POSITION] = s[wtv::VS_APPLIED] = s[wtv::VS_PLAY] = s[wtv::VS_DEMAND] = row;
-            for (int i = 0; i < wtv::MAX_DELAY; ++i) q[(size_t)(r * wtv::Q_DOUBLES + k * wtv::MAX_DELAY + i)] = row;
-        }
-    if (int rc = allocate(actuator_arrays(h))) return rc;
-    HIP_TRY(hipMemcpyAsync((double *)h->act.par, par.data(), sizeof(double) * par.size(), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->act.st, st.data(), sizeof(double) * st.size(), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->act.q, q.data(), sizeof(double) * q.size(), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->act.tp, lt.data(), sizeof(double) * lt.size(), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));   // the host vectors are freed on return
-    h->act.on = 1;
-    return WT_OK;
+    if (int rc = check_program_set(h, WT_PROG_ACTUATOR, params)) return rc;
+    if (int rc = wt_program_check(WT_PROG_ACTUATOR, params, h->N)) return rc;
+    return load_program(h, WT_PROG_ACTUATOR, params);
 }
 
 int wt_ensemble_actuator_get(wt_ensemble *h, double *state, double *queue, double *t_prev)
 {
     if (!h) return fail(WT_E_ARG, "NULL handle");
-    if (!h->act.on) return fail(WT_E_STATE, k_no_actuator);
-    HIP_TRY(hipSetDevice(h->device));
-    return download_records(h, {{state, h->act.st, wtv::ST_DOUBLES, wtv::CH, wtv::NVS},
-                                {queue, h->act.q, wtv::Q_DOUBLES, wtv::CH, wtv::MAX_DELAY}, {t_prev, h->act.tp, 1, 1, 1}});
+    return get_program(h, WT_PROG_ACTUATOR, {{state, h->act.st, wtv::ST_DOUBLES, wtv::CH, wtv::NVS},
+                                             {queue, h->act.q, wtv::Q_DOUBLES, wtv::CH, wtv::MAX_DELAY}, {t_prev, h->act.tp, 1, 1, 1}});
 }
 
-int wt_ensemble_actuator_clear(wt_ensemble *h)
-{
-    if (!h) return fail(WT_E_ARG, "NULL handle");
-    return stop_program(h, actuator_arrays(h));
-}
-
-} // extern "C"
-
-namespace {
-
-static_assert(WT_DST_SLOTS == wtd::SLOTS && WT_ND == wtd::ND && WT_NDS == wtd::NDS && WT_NB == wtd::NB,
-              "disturbance blocks of the C ABI");
-static_assert(WT_DST_OU == wtd::K_OU && WT_DST_OU + 1 == wtd::N_KINDS && WT_D_C == wtd::D_C && WT_DS_N_DRAW == wtd::DS_N_DRAW,
-              "disturbance kinds and rows of the C ABI");
-
-// Host-side checks of a [WT_DST_SLOTS][WT_ND][N] program; nullptr when it is valid.
-const char *disturb_params_error(const double *p, int64_t N)
-{
-    const auto at = [&](int k, int v, int64_t r) { return p[((int64_t)k * wtd::ND + v) * N + r]; };
-    for (int k = 0; k < wtd::SLOTS; ++k)
-        for (int64_t r = 0; r < N; ++r)
-            for (int v = 0; v < wtd::ND; ++v) {
-                const double x = at(k, v, r);
-                if (!std::isfinite(x) && !(v == wtd::D_T_END && x == INFINITY))
-                    return "disturbance parameters must be finite (t_end may be +inf)";
-            }
-    for (int k = 0; k < wtd::SLOTS; ++k)
-        for (int64_t r = 0; r < N; ++r) {
-            double c[wtd::ND];
-            for (int v = 0; v < wtd::ND; ++v) c[v] = at(k, v, r);
-            const double kind = c[wtd::D_KIND], row = c[wtd::D_ROW];
-            if (kind != std::floor(kind) || kind < 0 || kind >= wtd::N_KINDS)
-                return "kind must be an integer in 0..4 (off, step, ramp, sine, ou)";
-            if (row != std::floor(row) || row < 0 || row >= wtd::NB)
-                return "row must be a boundary row: 1, 2, 3, 5, 7, 8 or 9";
-            if (!wtd::row_allowed((int)row))
-                return "rows 0, 4 and 6 (inlet, acid and chlorine flow) belong to the command path or the master";
-            if (!(c[wtd::D_T_END] >= c[wtd::D_T_START])) return "t_end must be >= t_start";
-            if (kind == wtd::K_SINE && !(c[wtd::D_B] > 0)) return "a sine needs b (the period) > 0";
-            if (kind == wtd::K_OU && !(c[wtd::D_A] >= 0)) return "an OU slot needs a (sigma) >= 0";
-            if (kind == wtd::K_OU && !(c[wtd::D_B] > 0)) return "an OU slot needs b (tau) > 0";
-        }
-    return nullptr;
-}
-
-const char *k_no_disturb = "no disturbance program is set (wt_ensemble_disturb_set)";
-
-// the body of disturb_clear and of a set over a program: the targeted rows back to the base, the arrays released
-int disturb_stop(wt_ensemble *h)
-{
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->dst.on) {
-        if (int rc = disturb_op(h, wtd::OP_RESTORE)) return rc;
-        if (int rc = sync_checked(h)) return rc;
-    }
-    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still use the records
-    release(disturb_arrays(h, h->dst.hist_cap));
-    h->dst.hist_cap = 0;
-    return WT_OK;
-}
-
-} // namespace
-
-extern "C" {
+int wt_ensemble_actuator_clear(wt_ensemble *h) { return stop_program(h, WT_PROG_ACTUATOR); }
 
 int wt_ensemble_disturb_set(wt_ensemble *h, const double *params, uint64_t seed, int64_t reactor_base, int history_capacity)
 {
-    if (!h || !params) return fail(WT_E_ARG, "NULL argument");
-    if (!h->have_state || !h->have_bc) return fail(WT_E_STATE, "set_state and set_boundary must precede disturb_set");
-    if (!wt::prog_in_item(levels_for(h->n))) return fail(WT_E_STATE, "disturbance programs run in the kernels for up to 32 zones");
+    if (int rc = check_program_set(h, WT_PROG_DISTURB, params)) return rc;
     if (history_capacity < 0) return fail(WT_E_ARG, "history_capacity must be >= 0 (0 = no history)");
     int64_t hist = 0;
     if (__builtin_mul_overflow((int64_t)history_capacity * wtd::SLOTS, h->N, &hist) ||
         __builtin_mul_overflow(hist, (int64_t)sizeof(double), &hist))
         return fail(WT_E_ARG, "history size overflows int64");
     if (int rc = wt_program_check(WT_PROG_DISTURB, params, h->N)) return rc;
-    if (int rc = disturb_stop(h)) return rc;
-    const int64_t N = h->N;
-    std::vector<double> par((size_t)N * wtd::PAR_DOUBLES);
-    blocks_to_records(params, wtd::SLOTS, wtd::ND, N, par.data(), wtd::PAR_DOUBLES);
-    if (int rc = allocate(disturb_arrays(h, history_capacity))) return rc;
+    if (int rc = disturb_restore(h)) return rc;
+    if (int rc = stop_program(h, WT_PROG_DISTURB)) return rc;   // set replaces any program (and its capacity)
     h->dst.hist_cap = history_capacity;
     h->dst.seed_lo = (uint32_t)(seed & 0xffffffffu); h->dst.seed_hi = (uint32_t)(seed >> 32); h->dst.reactor_base = reactor_base;
-    HIP_TRY(hipMemcpyAsync((double *)h->dst.par, par.data(), sizeof(double) * par.size(), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemsetAsync(h->dst.st, 0, sizeof(double) * wtd::ST_DOUBLES * (size_t)N, h->stream));
-    if (history_capacity > 0) HIP_TRY(hipMemsetAsync(h->dst.hist, 0, (size_t)hist, h->stream));   // entries not filled: 0
-    HIP_TRY(hipMemcpyAsync(h->dst.base, h->bc, sizeof(double) * WT_NB * (size_t)N, hipMemcpyDeviceToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->dst.tp, h->time, sizeof(double) * (size_t)N, hipMemcpyDeviceToDevice, h->stream));
-    h->dst.on = 1;
-    if (int rc = disturb_op(h, wtd::OP_SET)) { release(disturb_arrays(h, h->dst.hist_cap)); return rc; }
-    if (int rc = sync_checked(h)) return rc;   // the host vector is freed on return
-    return WT_OK;
+    return load_program(h, WT_PROG_DISTURB, params);
 }
 
 int wt_ensemble_disturb_get(wt_ensemble *h, double *slot_state, double *base, double *t_prev)
 {
     if (!h) return fail(WT_E_ARG, "NULL handle");
-    if (!h->dst.on) return fail(WT_E_STATE, k_no_disturb);
-    HIP_TRY(hipSetDevice(h->device));
-    if (int rc = download_records(h, {{slot_state, h->dst.st, wtd::ST_DOUBLES, wtd::SLOTS, wtd::NDS}, {t_prev, h->dst.tp, 1, 1, 1}}))
+    if (int rc = get_program(h, WT_PROG_DISTURB, {{slot_state, h->dst.st, wtd::ST_DOUBLES, wtd::SLOTS, wtd::NDS}, {t_prev, h->dst.tp, 1, 1, 1}}))
         return rc;
     return download(h, {{base, h->dst.base, sizeof(double) * WT_NB * (size_t)h->N}});
 }
 
 int wt_ensemble_disturb_history(wt_ensemble *h, double *offsets, int32_t *n_filled)
 {
-    if (!h) return fail(WT_E_ARG, "NULL handle");
-    if (!h->dst.on) return fail(WT_E_STATE, k_no_disturb);
-    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = program_ready(h, WT_PROG_DISTURB)) return rc;
     const int64_t N = h->N;
     const int cap = h->dst.hist_cap;
     std::vector<double> st((size_t)N * wtd::NDS);   // slot 0's state: n_eval
@@ -1557,62 +1673,13 @@ int wt_ensemble_disturb_history(wt_ensemble *h, double *offsets, int32_t *n_fill
 int wt_ensemble_disturb_clear(wt_ensemble *h)
 {
     if (!h) return fail(WT_E_ARG, "NULL handle");
-    return disturb_stop(h);
+    if (int rc = disturb_restore(h)) return rc;
+    return stop_program(h, WT_PROG_DISTURB);
 }
-
-} // extern "C"
-
-namespace {
-
-static_assert(WT_SCR_SLOTS == wtsc::SLOTS && WT_NSP == wtsc::NSP && WT_NSS == wtsc::NSS && WT_SCR_MAX_BINS == wtsc::MAX_BINS,
-              "score blocks of the C ABI");
-static_assert(WT_SCR_BAND + 1 == wtsc::N_KINDS && WT_SQ_TEMPERATURE + 1 == wtsc::N_QUANTITIES && WT_SR_MEAN + 1 == wtsc::N_REDUCES &&
-              WT_SP_T_END == wtsc::P_T_END && WT_SS_RUN_MAX == wtsc::S_RUN_MAX, "score kinds and rows of the C ABI");
-
-// Host-side checks of a [WT_SCR_SLOTS][WT_NSP][N] program; nullptr when it is valid.
-const char *score_params_error(const double *p, int64_t N)
-{
-    const auto whole = [](double x, double lo, double hi) { return x == std::floor(x) && x >= lo && x <= hi; };
-    for (int k = 0; k < wtsc::SLOTS; ++k)
-        for (int64_t r = 0; r < N; ++r) {
-            double c[wtsc::NSP];
-            for (int v = 0; v < wtsc::NSP; ++v) c[v] = p[((int64_t)k * wtsc::NSP + v) * N + r];
-            if (!whole(c[wtsc::P_KIND], 0, wtsc::N_KINDS - 1)) return "kind must be 0 (off) or 1 (band)";
-            if (!whole(c[wtsc::P_QUANTITY], 0, wtsc::N_QUANTITIES - 1)) return "quantity must be 0 (pH), 1 (chlorine) or 2 (temperature)";
-            if (!whole(c[wtsc::P_REDUCE], 0, wtsc::N_REDUCES - 1)) return "reduce must be an integer in 0..3 (zone, min, max, mean)";
-            if (!whole(c[wtsc::P_ZONE], -1, 31)) return "zone must be an integer in -1..31 (-1: the last zone, the outlet)";
-            if (std::isnan(c[wtsc::P_LO]) || std::isnan(c[wtsc::P_HI])) return "lo and hi must not be NaN (-inf and +inf leave a side open)";
-            if (!(c[wtsc::P_LO] <= c[wtsc::P_HI])) return "lo must be <= hi";
-            if (!(c[wtsc::P_T_END] >= c[wtsc::P_T_START])) return "t_end must be >= t_start, neither NaN";
-        }
-    return nullptr;
-}
-
-const char *k_no_score = "no score program is set (wt_ensemble_score_set)";
-
-// The accumulators and the curve at their set-time values, t_prev = ReactorState.time, j = 0: on the handle's stream,
-// not synchronised.
-int score_restart(wt_ensemble *h)
-{
-    const size_t cells = (size_t)h->scr.curve_cap * wtsc::SLOTS;
-    const wtsc::HostOpArgs a{h->scr.st, h->scr.tp, h->time, h->N};
-    hipLaunchKernelGGL(wtsc::host_op_kernel, dim3((unsigned)((h->N + 255) / 256)), dim3(256), 0, h->stream, a);
-    HIP_TRY(hipGetLastError());
-    if (h->scr.counts) HIP_TRY(hipMemsetAsync(h->scr.counts, 0, sizeof(int32_t) * 3 * cells, h->stream));
-    if (h->scr.fan) HIP_TRY(hipMemsetAsync(h->scr.fan, 0, sizeof(int32_t) * (size_t)(h->scr.bins + 2) * cells, h->stream));
-    h->scr_steps = 0;
-    return WT_OK;
-}
-
-} // namespace
-
-extern "C" {
 
 int wt_ensemble_score_set(wt_ensemble *h, const double *params, int curve_capacity, int bins, const double *fan_lo, const double *fan_hi)
 {
-    if (!h || !params) return fail(WT_E_ARG, "NULL argument");
-    if (!h->have_state) return fail(WT_E_STATE, "set_state must precede score_set");
-    if (!wt::prog_in_item(levels_for(h->n))) return fail(WT_E_STATE, "score programs run in the kernels for up to 32 zones");
+    if (int rc = check_program_set(h, WT_PROG_SCORE, params)) return rc;
     if (curve_capacity < 0) return fail(WT_E_ARG, "curve_capacity must be >= 0 (0 = no ensemble curve)");
     if (bins < 0 || bins > wtsc::MAX_BINS) return fail(WT_E_ARG, "bins must be in 0..32 (0 = no fan)");
     if (bins > 0 && (!fan_lo || !fan_hi)) return fail(WT_E_ARG, "a fan needs fan_lo and fan_hi");
@@ -1627,132 +1694,37 @@ int wt_ensemble_score_set(wt_ensemble *h, const double *params, int curve_capaci
     for (int k = 0; k < wtsc::SLOTS; ++k)
         for (int64_t r = 0; r < N; ++r)
             if (params[((int64_t)k * wtsc::NSP + wtsc::P_ZONE) * N + r] >= h->n) return fail(WT_E_ARG, "zone must be below the ensemble's zone count");
-    if (int rc = stop_program(h, score_arrays(h, h->scr.curve_cap, h->scr.bins))) return rc;   // set replaces any program
-    std::vector<double> par((size_t)N * wtsc::PAR_DOUBLES);
-    blocks_to_records(params, wtsc::SLOTS, wtsc::NSP, N, par.data(), wtsc::PAR_DOUBLES);
-    if (int rc = allocate(score_arrays(h, curve_capacity, bins))) return rc;
+    if (int rc = stop_program(h, WT_PROG_SCORE)) return rc;   // set replaces any program (and its capacities)
     h->scr.curve_cap = curve_capacity; h->scr.bins = curve_capacity > 0 ? bins : 0;
     for (int k = 0; k < wtsc::SLOTS; ++k) {
         h->scr.fan_lo[k] = bins > 0 ? fan_lo[k] : 0.0; h->scr.fan_hi[k] = bins > 0 ? fan_hi[k] : 0.0;
         h->scr.fan_scale[k] = bins > 0 ? (double)bins / (fan_hi[k] - fan_lo[k]) : 0.0;
     }
-    HIP_TRY(hipMemcpyAsync((double *)h->scr.par, par.data(), sizeof(double) * par.size(), hipMemcpyHostToDevice, h->stream));
-    h->scr.on = 1;
-    if (int rc = score_restart(h)) { release(score_arrays(h, h->scr.curve_cap, h->scr.bins)); return rc; }
-    return sync_checked(h);   // the host vector is freed on return
+    return load_program(h, WT_PROG_SCORE, params);
 }
 
 int wt_ensemble_score_get(wt_ensemble *h, double *slot_state, double *t_prev)
 {
     if (!h) return fail(WT_E_ARG, "NULL handle");
-    if (!h->scr.on) return fail(WT_E_STATE, k_no_score);
-    HIP_TRY(hipSetDevice(h->device));
-    return download_records(h, {{slot_state, h->scr.st, wtsc::ST_DOUBLES, wtsc::SLOTS, wtsc::NSS}, {t_prev, h->scr.tp, 1, 1, 1}});
+    return get_program(h, WT_PROG_SCORE, {{slot_state, h->scr.st, wtsc::ST_DOUBLES, wtsc::SLOTS, wtsc::NSS}, {t_prev, h->scr.tp, 1, 1, 1}});
 }
 
 int wt_ensemble_score_curve(wt_ensemble *h, int32_t *counts, int32_t *fan, int *n_steps)
 {
-    if (!h) return fail(WT_E_ARG, "NULL handle");
-    if (!h->scr.on) return fail(WT_E_STATE, k_no_score);
-    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = program_ready(h, WT_PROG_SCORE)) return rc;
     const size_t cells = (size_t)h->scr.curve_cap * wtsc::SLOTS;
     if (n_steps) *n_steps = (int)(h->scr_steps < h->scr.curve_cap ? h->scr_steps : h->scr.curve_cap);
     return download(h, {{h->scr.counts ? counts : nullptr, h->scr.counts, sizeof(int32_t) * 3 * cells},
                         {h->scr.fan ? fan : nullptr, h->scr.fan, sizeof(int32_t) * (size_t)(h->scr.bins + 2) * cells}});
 }
 
-int wt_ensemble_score_reset(wt_ensemble *h)
-{
-    if (!h) return fail(WT_E_ARG, "NULL handle");
-    if (!h->scr.on) return fail(WT_E_STATE, k_no_score);
-    HIP_TRY(hipSetDevice(h->device));
-    if (int rc = score_restart(h)) return rc;
-    return sync_checked(h);
-}
-
-int wt_ensemble_score_clear(wt_ensemble *h)
-{
-    if (!h) return fail(WT_E_ARG, "NULL handle");
-    if (int rc = stop_program(h, score_arrays(h, h->scr.curve_cap, h->scr.bins))) return rc;
-    h->scr.curve_cap = 0; h->scr.bins = 0; h->scr_steps = 0;
-    return WT_OK;
-}
-
-} // extern "C"
-
-namespace {
-
-static_assert(WT_DET_SLOTS == wtk::SLOTS && WT_NK == wtk::NK && WT_NKS == wtk::NKS && WT_NKR == wtk::NKR, "detector blocks of the C ABI");
-static_assert(WT_DET_CUSUM == wtk::D_CUSUM && WT_DET_EWMA == wtk::D_EWMA && WT_DET_FLATLINE == wtk::D_FLATLINE &&
-              WT_DET_FLATLINE + 1 == wtk::N_KINDS && WT_DET_FIELD == wtk::SRC_FIELD && WT_DET_SENSOR == wtk::REF_SENSOR &&
-              WT_DET_TRACK == wtk::REF_TRACK && WT_DET_TRACK + 1 == wtk::N_REFS && WT_DET_ALARM == wtk::ON_BAD_ALARM,
-              "detector kinds, sources, references and policies of the C ABI");
-static_assert(WT_K_REF_ARG == wtk::K_REF_ARG && WT_K_ON_BAD == wtk::K_ON_BAD && WT_KS_X_PREV == wtk::KS_X_PREV &&
-              WT_KS_T_DETECT == wtk::KS_T_DETECT && WT_KS_N_FN == wtk::KS_N_FN && WT_KR_LABEL_END == wtk::KR_LABEL_END,
-              "detector rows of the C ABI");
-static_assert(wtk::NK % 2 == 0 && wtk::NKS % 2 == 0 && wtk::NKR == 2, "the detector's records are read in 16-byte pairs");
-
-// Host-side checks of a [WT_DET_SLOTS][WT_NK][N] program; nullptr when it is valid.
-const char *detect_params_error(const double *p, int64_t N)
-{
-    const auto is_int_in = [](double x, int lo, int hi) { return x == std::floor(x) && x >= lo && x <= hi; };
-    for (int s = 0; s < wtk::SLOTS; ++s)
-        for (int64_t r = 0; r < N; ++r) {
-            double c[wtk::NK];
-            for (int k = 0; k < wtk::NK; ++k) c[k] = p[((int64_t)s * wtk::NK + k) * N + r];
-            for (int k = 0; k < wtk::NK; ++k)
-                if (!std::isfinite(c[k]) && !(k == wtk::K_T_ARM && c[k] == -INFINITY))
-                    return "detector parameters must be finite (t_arm may be -inf)";
-            const double kind = c[wtk::K_KIND], ref = c[wtk::K_REF], slack = c[wtk::K_SLACK];
-            if (!is_int_in(kind, 0, wtk::N_KINDS - 1)) return "kind must be 0 (off), 1 (cusum), 2 (ewma) or 3 (flatline)";
-            if (kind == wtk::D_OFF) continue;                      // the other rows of an OFF slot are not read
-            if (!is_int_in(c[wtk::K_SENSOR], 0, WT_N_SENSORS - 1)) return "sensor must be an integer in 0..6";
-            if (!is_int_in(c[wtk::K_SOURCE], 0, 1)) return "source must be 0 (image) or 1 (field)";
-            if (!is_int_in(ref, 0, wtk::N_REFS - 1)) return "ref must be 0 (const), 1 (sensor) or 2 (track)";
-            if (ref == wtk::REF_SENSOR) {
-                if (!is_int_in(c[wtk::K_REF_ARG], 0, WT_N_SENSORS - 1)) return "a SENSOR reference's ref_arg must be a sensor index in 0..6";
-                if (!is_int_in(c[wtk::K_REF_SOURCE], 0, 1)) return "ref_source must be 0 (image) or 1 (field)";
-            }
-            if (ref == wtk::REF_TRACK && !(c[wtk::K_REF_ARG] > 0)) return "a TRACK reference's ref_arg (tau) must be > 0";
-            if (!(c[wtk::K_SIGMA] > 0)) return "sigma must be > 0";
-            if (kind == wtk::D_CUSUM && !(slack >= 0)) return "a CUSUM slot's slack (k) must be >= 0";
-            if (kind == wtk::D_EWMA && !(slack > 0 && slack <= 1)) return "an EWMA slot's slack (lambda) must be in (0, 1]";
-            if (kind == wtk::D_FLATLINE && !(slack >= 0)) return "a FLATLINE slot's slack (eps) must be >= 0";
-            if (!(c[wtk::K_LIMIT] > 0)) return "limit must be > 0";
-            if (!is_int_in(c[wtk::K_ON_BAD], 0, 1)) return "on_bad must be 0 (hold) or 1 (alarm)";
-        }
-    return nullptr;
-}
-
-const char *k_no_detect = "no detector program is set (wt_ensemble_detect_set)";
-
-// Slot state and t_prev at their set-time values, t_prev = the reactors' loop time now: uploaded and synchronised.
-int detect_restart(wt_ensemble *h)
-{
-    const int64_t N = h->N;
-    std::vector<double> st((size_t)N * wtk::ST_DOUBLES, 0.0), lt((size_t)N);
-    for (int64_t r = 0; r < N; ++r)
-        for (int s = 0; s < wtk::SLOTS; ++s) {
-            double *q = st.data() + r * wtk::ST_DOUBLES + s * wtk::NKS;
-            q[wtk::KS_BASELINE] = q[wtk::KS_X_PREV] = q[wtk::KS_T_FIRST] = q[wtk::KS_T_DETECT] = NAN;
-        }
-    // (the download also waits for queued launches, which may still read or write the old records)
-    if (int rc = download(h, {{lt.data(), h->sens.pack.loop_time, sizeof(double) * (size_t)N}})) return rc;
-    HIP_TRY(hipMemcpyAsync(h->det.st, st.data(), sizeof(double) * st.size(), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->det.tp, lt.data(), sizeof(double) * lt.size(), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));   // the host vectors are freed on return
-    return WT_OK;
-}
-
-} // namespace
-
-extern "C" {
+int wt_ensemble_score_reset(wt_ensemble *h) { return reset_program(h, WT_PROG_SCORE); }
+int wt_ensemble_score_clear(wt_ensemble *h) { return stop_program(h, WT_PROG_SCORE); }
 
 int wt_ensemble_detect_set(wt_ensemble *h, const double *params, const double *labels)
 {
-    if (int rc = check_program_set(h, params, WT_PROG_DETECT, "detectors read the plant I/O scan: enable plant I/O first",
-                                   "detector programs run in the kernels for up to 32 zones"))
-        return rc;
+    if (int rc = check_program_set(h, WT_PROG_DETECT, params)) return rc;
+    if (int rc = wt_program_check(WT_PROG_DETECT, params, h->N)) return rc;
     if (!labels) return fail(WT_E_ARG, "NULL argument");
     const int64_t N = h->N;
     for (int64_t r = 0; r < N; ++r) {
@@ -1760,141 +1732,47 @@ int wt_ensemble_detect_set(wt_ensemble *h, const double *params, const double *l
         if (std::isnan(t0) || std::isnan(t1)) return fail(WT_E_ARG, "label_start and label_end must not be NaN");
         if (!(t1 >= t0)) return fail(WT_E_ARG, "label_end must be >= label_start");
     }
-    HIP_TRY(hipSetDevice(h->device));
-    std::vector<double> par((size_t)N * wtk::PAR_DOUBLES), lab((size_t)N * wtk::NKR);
-    blocks_to_records(params, wtk::SLOTS, wtk::NK, N, par.data(), wtk::PAR_DOUBLES);
+    // the labels go up first (load_program finds the arrays there and synchronises before `lab` is freed)
+    std::vector<double> lab((size_t)N * wtk::NKR);
     blocks_to_records(labels, 1, wtk::NKR, N, lab.data(), wtk::NKR);
-    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still read or write the old records
-    const bool fresh_arrays = !h->det.par;
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still read the old labels
     if (int rc = allocate(detect_arrays(h))) return rc;
-    HIP_TRY(hipMemcpyAsync((double *)h->det.par, par.data(), sizeof(double) * par.size(), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync((double *)h->det.lab, lab.data(), sizeof(double) * lab.size(), hipMemcpyHostToDevice, h->stream));
-    if (int rc = detect_restart(h)) {
-        if (fresh_arrays) release(detect_arrays(h));
-        return rc;
-    }
-    h->det.on = 1;
-    return WT_OK;
+    if (int rc = upload(h, (double *)h->det.lab, lab)) { release(detect_arrays(h)); return rc; }
+    return load_program(h, WT_PROG_DETECT, params);
 }
 
 int wt_ensemble_detect_get(wt_ensemble *h, double *slot_state, double *t_prev)
 {
     if (!h) return fail(WT_E_ARG, "NULL handle");
-    if (!h->det.on) return fail(WT_E_STATE, k_no_detect);
-    HIP_TRY(hipSetDevice(h->device));
-    return download_records(h, {{slot_state, h->det.st, wtk::ST_DOUBLES, wtk::SLOTS, wtk::NKS}, {t_prev, h->det.tp, 1, 1, 1}});
+    return get_program(h, WT_PROG_DETECT, {{slot_state, h->det.st, wtk::ST_DOUBLES, wtk::SLOTS, wtk::NKS}, {t_prev, h->det.tp, 1, 1, 1}});
 }
 
-int wt_ensemble_detect_reset(wt_ensemble *h)
-{
-    if (!h) return fail(WT_E_ARG, "NULL handle");
-    if (!h->det.on) return fail(WT_E_STATE, k_no_detect);
-    HIP_TRY(hipSetDevice(h->device));
-    return detect_restart(h);
-}
-
-int wt_ensemble_detect_clear(wt_ensemble *h)
-{
-    if (!h) return fail(WT_E_ARG, "NULL handle");
-    return stop_program(h, detect_arrays(h));
-}
-
-} // extern "C"
-
-namespace {
-
-static_assert(WT_TRD_SLOTS == wtt::SLOTS && WT_NT == wtt::NT && WT_NTS == wtt::NTS, "trend blocks of the C ABI");
-static_assert(WT_TRD_IMAGE_VALUE == wtt::G_IMAGE_VALUE && WT_TRD_FIELD_FAULT == wtt::G_FIELD_FAULT && WT_TRD_COMMAND == wtt::G_COMMAND &&
-              WT_TRD_CONTROL == wtt::G_CONTROL && WT_TRD_INJECT == wtt::G_INJECT && WT_TRD_ALARM == wtt::G_ALARM &&
-              WT_TRD_ALARM_WORD == wtt::G_ALARM_WORD && WT_TRD_ACTUATOR == wtt::G_ACTUATOR && WT_TRD_DETECT == wtt::G_DETECT &&
-              WT_TRD_DETECT + 1 == wtt::N_TAGS, "trend tags of the C ABI");
-static_assert(WT_T_T_END == wtt::T_T_END && WT_TS_LAST == wtt::TS_LAST, "trend rows of the C ABI");
-static_assert(wtt::NT % 2 == 0 && wtt::NTS % 2 == 0, "the recorder's records are read in 16-byte pairs");
-static_assert(wtt::index_range(wtt::G_IMAGE_VALUE) == WT_N_SENSORS && wtt::index_range(wtt::G_CONTROL) == WT_CTL_LOOPS * WT_NCS &&
-              wtt::index_range(wtt::G_INJECT) == WT_INJ_SLOTS * WT_NIS && wtt::index_range(wtt::G_ALARM) == WT_ALM_SLOTS * WT_NAS &&
-              wtt::index_range(wtt::G_ACTUATOR) == WT_ACT_CHANNELS * WT_NVS && wtt::index_range(wtt::G_DETECT) == WT_DET_SLOTS * WT_NKS,
-              "a trend index names an entry of the block the program's get call returns");
-// COMMAND channels in WT_INJ_CMD_* order
-static_assert(WT_INJ_CMD_ACID + 1 == WT_INJ_CMD_CHLORINE && WT_INJ_CMD_CHLORINE + 1 == WT_INJ_CMD_INLET, "acid, chlorine, inlet");
-
-// Host-side checks of a [WT_TRD_SLOTS][WT_NT][N] program; nullptr when it is valid.
-const char *trend_params_error(const double *p, int64_t N)
-{
-    for (int s = 0; s < wtt::SLOTS; ++s)
-        for (int64_t r = 0; r < N; ++r) {
-            double c[wtt::NT];
-            for (int k = 0; k < wtt::NT; ++k) c[k] = p[((int64_t)s * wtt::NT + k) * N + r];
-            const double tag = c[wtt::T_TAG], index = c[wtt::T_INDEX], every = c[wtt::T_EVERY];
-            if (!(tag == std::floor(tag) && tag >= 0 && tag <= wtt::N_TAGS - 1)) return "tag must be an integer in 0..11 (0: off)";
-            if (tag == wtt::G_OFF) continue;                       // the other rows of an OFF slot are not read
-            if (!(index == std::floor(index) && index >= 0 && index < wtt::index_range((int)tag)))
-                return "index must be an integer within the tag's range";
-            if (!(every == std::floor(every) && every >= 1 && every < 9007199254740992.0)) return "every must be an integer >= 1";
-            if (std::isnan(c[wtt::T_DEADBAND])) return "deadband must not be NaN (negative: every candidate is recorded)";
-            if (std::isnan(c[wtt::T_T_START]) || std::isnan(c[wtt::T_T_END])) return "t_start and t_end must not be NaN";
-            if (!(c[wtt::T_T_END] >= c[wtt::T_T_START])) return "t_end must be >= t_start";
-        }
-    return nullptr;
-}
-
-const char *k_no_trend = "no trend program is set (wt_ensemble_trend_set)";
-
-// Slot state at its set-time values (0, 0, 0, NaN) and an all-NaN store: on the handle's stream, synchronised.
-int trend_restart(wt_ensemble *h)
-{
-    const int64_t N = h->N;
-    std::vector<double> st((size_t)N * wtt::ST_DOUBLES, 0.0);
-    for (int64_t i = 0; i < N * wtt::SLOTS; ++i) st[(size_t)i * wtt::NTS + wtt::TS_LAST] = NAN;
-    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still write the old records
-    HIP_TRY(hipMemcpyAsync(h->trd.st, st.data(), sizeof(double) * st.size(), hipMemcpyHostToDevice, h->stream));
-    // every byte 0xff: a NaN in both halves of every sample
-    HIP_TRY(hipMemsetAsync(h->trd.store, 0xff, sizeof(double2) * wtt::SLOTS * (size_t)h->trd.cap * (size_t)N, h->stream));
-    return sync_checked(h);                     // the host vector is freed on return
-}
-
-} // namespace
-
-extern "C" {
+int wt_ensemble_detect_reset(wt_ensemble *h) { return reset_program(h, WT_PROG_DETECT); }
+int wt_ensemble_detect_clear(wt_ensemble *h) { return stop_program(h, WT_PROG_DETECT); }
 
 int wt_ensemble_trend_set(wt_ensemble *h, const double *params, int64_t capacity, int wrap)
 {
-    if (int rc = check_program_set(h, params, WT_PROG_TREND, "trends read the plant I/O scan: enable plant I/O first",
-                                   "trend programs run in the kernels for up to 32 zones"))
-        return rc;
+    if (int rc = check_program_set(h, WT_PROG_TREND, params)) return rc;
+    if (int rc = wt_program_check(WT_PROG_TREND, params, h->N)) return rc;
     if (capacity < 1) return fail(WT_E_ARG, "capacity must be >= 1");
     int64_t bytes = 0;
     if (__builtin_mul_overflow(capacity, (int64_t)(wtt::SLOTS * sizeof(double2)), &bytes) || __builtin_mul_overflow(bytes, h->N, &bytes))
         return fail(WT_E_ARG, "store size overflows int64");
-    const int64_t N = h->N;
-    if (int rc = stop_program(h, trend_arrays(h, h->trd.cap))) return rc;   // set replaces any program (and its capacity)
-    h->trd.cap = 0;
-    std::vector<double> par((size_t)N * wtt::PAR_DOUBLES);
-    blocks_to_records(params, wtt::SLOTS, wtt::NT, N, par.data(), wtt::PAR_DOUBLES);
-    if (int rc = allocate(trend_arrays(h, capacity))) return rc;
+    if (int rc = stop_program(h, WT_PROG_TREND)) return rc;   // set replaces any program (and its capacity)
     h->trd.cap = capacity; h->trd.wrap = wrap ? 1 : 0;
-    HIP_TRY(hipMemcpyAsync((double *)h->trd.par, par.data(), sizeof(double) * par.size(), hipMemcpyHostToDevice, h->stream));
-    if (int rc = trend_restart(h)) {
-        release(trend_arrays(h, h->trd.cap));
-        h->trd.cap = 0;
-        return rc;
-    }
-    h->trd.on = 1;
-    return WT_OK;
+    return load_program(h, WT_PROG_TREND, params);
 }
 
 int wt_ensemble_trend_get(wt_ensemble *h, double *slot_state)
 {
     if (!h) return fail(WT_E_ARG, "NULL handle");
-    if (!h->trd.on) return fail(WT_E_STATE, k_no_trend);
-    HIP_TRY(hipSetDevice(h->device));
-    return download_records(h, {{slot_state, h->trd.st, wtt::ST_DOUBLES, wtt::SLOTS, wtt::NTS}});
+    return get_program(h, WT_PROG_TREND, {{slot_state, h->trd.st, wtt::ST_DOUBLES, wtt::SLOTS, wtt::NTS}});
 }
 
 int wt_ensemble_trend_data(wt_ensemble *h, double *time, double *value)
 {
-    if (!h) return fail(WT_E_ARG, "NULL handle");
-    if (!h->trd.on) return fail(WT_E_STATE, k_no_trend);
-    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = program_ready(h, WT_PROG_TREND)) return rc;
     const int64_t N = h->N, cap = h->trd.cap;
     std::vector<double> st((size_t)N * wtt::ST_DOUBLES);
     std::vector<double2> store((size_t)N * wtt::SLOTS * (size_t)cap);
@@ -1916,40 +1794,8 @@ int wt_ensemble_trend_data(wt_ensemble *h, double *time, double *value)
     return WT_OK;
 }
 
-int wt_ensemble_trend_reset(wt_ensemble *h)
-{
-    if (!h) return fail(WT_E_ARG, "NULL handle");
-    if (!h->trd.on) return fail(WT_E_STATE, k_no_trend);
-    HIP_TRY(hipSetDevice(h->device));
-    return trend_restart(h);
-}
-
-int wt_ensemble_trend_clear(wt_ensemble *h)
-{
-    if (!h) return fail(WT_E_ARG, "NULL handle");
-    if (int rc = stop_program(h, trend_arrays(h, h->trd.cap))) return rc;
-    h->trd.cap = 0;
-    return WT_OK;
-}
-
-int wt_program_check(int program, const double *params, int64_t n_reactors)
-{
-    if (!params) return fail(WT_E_ARG, "params is NULL");
-    if (n_reactors < 1) return fail(WT_E_ARG, "n_reactors must be >= 1");
-    const char *msg;
-    switch (program) {
-    case WT_PROG_CONTROL: msg = control_params_error(params, n_reactors); break;
-    case WT_PROG_INJECT: msg = inject_params_error(params, n_reactors); break;
-    case WT_PROG_ALARM: msg = alarm_params_error(params, n_reactors); break;
-    case WT_PROG_ACTUATOR: msg = actuator_params_error(params, n_reactors); break;
-    case WT_PROG_DISTURB: msg = disturb_params_error(params, n_reactors); break;
-    case WT_PROG_SCORE: msg = score_params_error(params, n_reactors); break;
-    case WT_PROG_DETECT: msg = detect_params_error(params, n_reactors); break;
-    case WT_PROG_TREND: msg = trend_params_error(params, n_reactors); break;
-    default: return fail(WT_E_ARG, "unknown program");
-    }
-    return msg ? fail(WT_E_ARG, msg) : WT_OK;
-}
+int wt_ensemble_trend_reset(wt_ensemble *h) { return reset_program(h, WT_PROG_TREND); }
+int wt_ensemble_trend_clear(wt_ensemble *h) { return stop_program(h, WT_PROG_TREND); }
 
 int wt_ensemble_get_boundary(wt_ensemble *h, double *bc)
 {

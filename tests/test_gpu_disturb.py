@@ -258,7 +258,7 @@ def test_errors_and_lifetime(gpu, wt):
     bad = np.ascontiguousarray(wt.disturbance_block(N, wt.Disturbance.step(1, 0.1)))
     bad[0, 1] = 4.0
     with pytest.raises(ValueError):
-        ens._control_call(nat.lib().wt_ensemble_disturb_set, nat.dptr(bad), C.c_uint64(1), 0, 0)
+        ens._program_call(nat.lib().wt_ensemble_disturb_set, nat.dptr(bad), C.c_uint64(1), 0, 0)
     assert refused_as_checked(nat, nat.WT_PROG_DISTURB, bad)
     with pytest.raises(ValueError, match="no disturbance program"):
         ens.disturbance_state()

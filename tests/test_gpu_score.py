@@ -252,7 +252,7 @@ def test_errors_and_lifetime(gpu, wt):
     bad = np.ascontiguousarray(wt.score_block(N, wt.Score("pH")))
     bad[0, 2] = 7.0
     with pytest.raises(ValueError, match="reduce must be"):
-        ens._control_call(L.wt_ensemble_score_set, nat.dptr(bad), 0, 0, None, None)
+        ens._program_call(L.wt_ensemble_score_set, nat.dptr(bad), 0, 0, None, None)
     assert refused_as_checked(nat, nat.WT_PROG_SCORE, bad)
     for zone in (n, 31):
         with pytest.raises(ValueError, match="below the ensemble's zone count"):

@@ -311,6 +311,23 @@ PROGRAMS = {
                  r"WT_DST_OU\b", r"WT_ND\b", r"WT_NDS\b", r"WT_PROG_DISTURB = 4\b"),
                 "wt_dst.hpp", ("Disturbance", "DisturbanceState", "disturbance_block"),
                 ("set_disturbances", "disturbance_state", "disturbance_history", "clear_disturbances")),
+    "score": (("wt_ensemble_score_set", "wt_ensemble_score_get", "wt_ensemble_score_curve", "wt_ensemble_score_reset",
+               "wt_ensemble_score_clear"),
+              (r"#define WT_SCR_SLOTS 4\b", r"#define WT_SCR_MAX_BINS 32\b", r"WT_SCR_BAND = 1\b", r"WT_SP_T_END = 7\b",
+               r"WT_NSP = 8\b", r"WT_SS_RUN_MAX = 14\b", r"WT_NSS = 15\b", r"WT_PROG_SCORE = 5\b"),
+              "wt_scr.hpp", ("Score", "ScoreState", "ScoreCurve", "score_block"),
+              ("set_scores", "score_state", "score_curve", "reset_scores", "clear_scores")),
+    "detect": (("wt_ensemble_detect_set", "wt_ensemble_detect_get", "wt_ensemble_detect_reset", "wt_ensemble_detect_clear"),
+               (r"#define WT_DET_SLOTS 4\b", r"WT_DET_FLATLINE = 3\b", r"WT_NK = 12\b", r"WT_NKS = 16\b",
+                r"WT_KR_LABEL_END = 1\b", r"WT_NKR = 2\b", r"WT_PROG_DETECT = 6\b"),
+               "wt_det.hpp", ("Detector", "DetectorState", "detector_block"),
+               ("set_detectors", "detector_state", "reset_detectors", "clear_detectors")),
+    "trend": (("wt_ensemble_trend_set", "wt_ensemble_trend_get", "wt_ensemble_trend_data", "wt_ensemble_trend_reset",
+               "wt_ensemble_trend_clear"),
+              (r"#define WT_TRD_SLOTS 8\b", r"WT_TRD_DETECT = 11\b", r"WT_T_T_END = 5\b", r"WT_NT = 6\b", r"WT_TS_LAST = 3\b",
+               r"WT_NTS = 4\b", r"WT_PROG_TREND = 7\b"),
+              "wt_trd.hpp", ("Trend", "TrendState", "TrendData", "trend_block"),
+              ("set_trends", "trend_state", "trend_data", "reset_trends", "clear_trends")),
 }
 
 
