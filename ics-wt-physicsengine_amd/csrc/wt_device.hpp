@@ -267,6 +267,14 @@ constexpr RTab RT0 = default_rtab();
 __device__ __forceinline__ KZ lit_kz() { return {RT0.T00, RT0.T01, RT0.T02, RT0.T10, RT0.T11, RT0.T12, RT0.rtol, RT0.atol}; }
 __device__ __forceinline__ KE lit_ke() { return {RT0.E0, RT0.E1, RT0.E2}; }
 __device__ __forceinline__ KA lit_ka() { return {{RT0.P[0], RT0.P[1], RT0.P[2], RT0.P[3], RT0.P[4], RT0.P[5], RT0.P[6], RT0.P[7], RT0.P[8]}}; }
+// Z = T W (radau.py:124) of species q: Z[2] = W0 + W1.  The caller brings the constants, literal or loaded (see above).
+struct ZRow { double z0, z1, z2; };
+__device__ __forceinline__ ZRow z_of_w(const KZ &kz, const double (&W)[3][3], int q)
+{
+    return {kz.T00 * W[0][q] + kz.T01 * W[1][q] + kz.T02 * W[2][q],
+            kz.T10 * W[0][q] + kz.T11 * W[1][q] + kz.T12 * W[2][q],
+            W[0][q] + W[1][q]};
+}
 
 
 struct StepArgs {
@@ -2004,14 +2012,12 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
                 const KZ kz = lit_kz(); const KA ka = lit_ka();
 #pragma unroll
                 for (int q = 0; q < 3; ++q) {
-                    const double z0 = kz.T00 * W[0][q] + kz.T01 * W[1][q] + kz.T02 * W[2][q];
-                    const double z1 = kz.T10 * W[0][q] + kz.T11 * W[1][q] + kz.T12 * W[2][q];
-                    const double z2 = W[0][q] + W[1][q];
+                    const ZRow z = z_of_w(kz, W, q);
                     y_old_a[q].set(yc[q]);
-                    Qa[q][0].set(z0 * ka.P[0] + z1 * ka.P[3] + z2 * ka.P[6]);  // Q = Z^T P  radau.py:541-543
-                    Qa[q][1].set(z0 * ka.P[1] + z1 * ka.P[4] + z2 * ka.P[7]);
-                    Qa[q][2].set(z0 * ka.P[2] + z1 * ka.P[5] + z2 * ka.P[8]);
-                    yc[q] = yc[q] + z2;
+                    Qa[q][0].set(z.z0 * ka.P[0] + z.z1 * ka.P[3] + z.z2 * ka.P[6]);  // Q = Z^T P  radau.py:541-543
+                    Qa[q][1].set(z.z0 * ka.P[1] + z.z1 * ka.P[4] + z.z2 * ka.P[7]);
+                    Qa[q][2].set(z.z0 * ka.P[2] + z.z1 * ka.P[5] + z.z2 * ka.P[8]);
+                    yc[q] = yc[q] + z.z2;
                 }
                 sol_t_old_a.set(t); sol_h_a.set(t_new - t); have_sol = true;
                 t = t_new;
@@ -2125,11 +2131,9 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
                     const KZ kzp = load_kz(&fresh(pa)->rt);
 #pragma unroll
                     for (int q = 0; q < 3; ++q) {
-                        const double z0 = kzp.T00 * W[0][q] + kzp.T01 * W[1][q] + kzp.T02 * W[2][q];
-                        const double z1 = kzp.T10 * W[0][q] + kzp.T11 * W[1][q] + kzp.T12 * W[2][q];
-                        const double z2 = W[0][q] + W[1][q];
-                        if (newton) ye[0][q] = yc[q] + z0;
-                        ye[1][q] = yc[q] + z1; ye[2][q] = yc[q] + z2;
+                        const ZRow z = z_of_w(kzp, W, q);
+                        if (newton) ye[0][q] = yc[q] + z.z0;
+                        ye[1][q] = yc[q] + z.z1; ye[2][q] = yc[q] + z.z2;
                     }
                 };
                 // formed only on trips that evaluate them (+1 % at n = 8) -- except in the n = 17...32 kernel, where the
@@ -2250,12 +2254,10 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
                         const KZ kze = lit_kz(); const KE ke = lit_ke();
 #pragma unroll
                         for (int q = 0; q < 3; ++q) {
-                            const double z0 = kze.T00 * W[0][q] + kze.T01 * W[1][q] + kze.T02 * W[2][q];
-                            const double z1 = kze.T10 * W[0][q] + kze.T11 * W[1][q] + kze.T12 * W[2][q];
-                            const double z2 = W[0][q] + W[1][q];
-                            const double ZE = (z0 * ke.E0 + z1 * ke.E1 + z2 * ke.E2) * ih_e;
+                            const ZRow z = z_of_w(kze, W, q);
+                            const double ZE = (z.z0 * ke.E0 + z.z1 * ke.E1 + z.z2 * ke.E2) * ih_e;
                             err[q] = f[q] + ZE;
-                            esc[q] = kze.atol + fmax(fabs(yc[q]), fabs(yc[q] + z2)) * kze.rtol;
+                            esc[q] = kze.atol + fmax(fabs(yc[q]), fabs(yc[q] + z.z2)) * kze.rtol;
                         }
                         solve_real<ROW, LV>(L, Jc, F, err, __ballot(j_dense) == 0ull);
                         error_norm = rms3<ROW, LV>(L, err, esc);
@@ -2277,12 +2279,10 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
                     const KZ kze = lit_kz(); const KE ke = lit_ke();
 #pragma unroll
                     for (int q = 0; q < 3; ++q) {
-                        const double z0 = kze.T00 * W[0][q] + kze.T01 * W[1][q] + kze.T02 * W[2][q];
-                        const double z1 = kze.T10 * W[0][q] + kze.T11 * W[1][q] + kze.T12 * W[2][q];
-                        const double z2 = W[0][q] + W[1][q];
-                        const double ZE = (z0 * ke.E0 + z1 * ke.E1 + z2 * ke.E2) * ih_e;
+                        const ZRow z = z_of_w(kze, W, q);
+                        const double ZE = (z.z0 * ke.E0 + z.z1 * ke.E1 + z.z2 * ke.E2) * ih_e;
                         err[q] = Fe[0][q] + ZE;
-                        esc[q] = kze.atol + fmax(fabs(yc[q]), fabs(yc[q] + z2)) * kze.rtol;
+                        esc[q] = kze.atol + fmax(fabs(yc[q]), fabs(yc[q] + z.z2)) * kze.rtol;
                     }
                     solve_real<ROW, LV>(L, Jc, F, err, __ballot(j_dense) == 0ull);
                     error_norm = rms3<ROW, LV>(L, err, esc);
