@@ -1,12 +1,14 @@
-"""Helpers of the GPU tests and probes of the per-reactor scan programs (test_gpu_control.py, test_gpu_inject.py,
-test_gpu_alarm.py, test_gpu_actuator.py, test_gpu_program_shapes.py, tools/*_probe.py): a plant with sensors and plant I/O, a pair of PI loops, the
-plant's observable state, the message of a refused parameter block, and the host side of the PLC scan -- the calls of
-one scan interval, the device's scan order and the holding words of a host master; the zone count -> kernel instantiation
-rule and the wavefront packing."""
+"""Helpers of the GPU tests and probes of the per-reactor programs (test_gpu_control.py ... test_gpu_trend.py,
+test_gpu_program_shapes.py, tools/*_probe.py): a plant with sensors and plant I/O, a pair of PI loops, the plant's
+observable state and every program's, the message of a refused parameter block, and the host side of the PLC scan --
+the calls of one scan interval, the device's whole scan order (``HostScan.scan``) and the holding words of a host
+master; the zone count -> kernel instantiation rule and the wavefront packing."""
 import importlib
 
 import numpy as np
+import pytest
 
+import trend_ref as TR
 from inject_ref import CMD_ACID, I_TARGET
 
 DT, K = 10.0, 300          # 3000 s: the pH sensors' 1800 s warm-up ends inside the run
@@ -23,6 +25,14 @@ def instantiation(n):
     while (1 << level) < n:
         level += 1
     return level, n in (2, 4, 8, 16)
+
+
+@pytest.fixture
+def full_waves(monkeypatch):
+    """The library spreads an ensemble smaller than the device's wavefront slots over more wavefronts than it needs
+    (down to one reactor each); WT_FULL_WAVES, read when an ensemble is created, packs 64 // n reactors into each, as
+    a large ensemble is packed.  Test modules import the fixture by name."""
+    monkeypatch.setenv("WT_FULL_WAVES", "1")
 
 
 def ragged_size(n, groups=5):
@@ -80,6 +90,73 @@ def plant_state(ens):
     return (es.pH, es.chlorine, es.temperature, es.time, es.flow_rate, es.status, v, s, f, ens.boundary())
 
 
+def alarms(ens):
+    """The device's alarm state, reset state and words; ``ref_alarms`` is the restatement's side of the comparison."""
+    return ens.alarm_state().block() + (ens.alarm_words(),)
+
+
+def ref_alarms(ref):
+    return ref.st, ref.rst, ref.words
+
+
+def acts(ens):
+    """The device's actuator state, queues, t_prev and the boundary rows the elements drive; ``ref_acts`` likewise."""
+    return ens.actuator_state().block() + (ens.boundary()[[0, 4, 6]],)
+
+
+def ref_acts(ref):
+    return ref.st, ref.q, ref.t_prev, ref.rows()
+
+
+def _disturbance(ens):
+    d = ens.disturbance_state()
+    return d.value, d.x, d.n_eval, d.n_draw, d.base, d.t_prev
+
+
+def _score(ens):
+    c = ens.score_curve()
+    return tuple(vars(ens.score_state()).values()) + (c.n_scored, c.n_low, c.n_high)
+
+
+# what ``everything`` returns of each program, in its order
+_STATE = dict(control=lambda ens: (ens.control_state().block(),), inject=lambda ens: (ens.injection_state().block(),),
+              alarm=alarms, actuator=acts, detect=lambda ens: tuple(ens.detector_state().block()), disturb=_disturbance,
+              score=_score)
+SCAN_PROGRAMS = ("control", "inject", "alarm", "actuator")
+
+
+def everything(ens, *, programs=SCAN_PROGRAMS):
+    """State, readings, boundary and input image of every reactor, then the state blocks of the named programs (each
+    must be set), in the fixed order control, inject, alarm, actuator, detect, disturb, score."""
+    assert set(programs) <= set(_STATE), programs
+    out = plant_state(ens) + ens.input_image()
+    for name, state in _STATE.items():
+        if name in programs:
+            out += tuple(state(ens))
+    return out
+
+
+def trend_tag_values(ens, image=None):
+    """Tag -> rows of the trend recorder's values at the scan that closed the last call, from the public getters of an
+    ensemble with all of control, injection, alarm, actuator and detector programs set.  ``image``: the (values, faults)
+    that scan saw, for the reading tags; without it they are left to ``HostScan.tag_values``."""
+    N = ens.n_reactors
+    rows = lambda block: block.reshape(-1, N)
+    out = {TR.COMMAND: ens.boundary()[[4, 6, 0]], TR.CONTROL: rows(ens.control_state().block()),
+           TR.INJECT: rows(ens.injection_state().block()), TR.ALARM: rows(ens.alarm_state().block()[0]),
+           TR.ALARM_WORD: ens.alarm_words().astype(np.float64), TR.ACTUATOR: rows(ens.actuator_state().block()[0]),
+           TR.DETECT: rows(ens.detector_state().block()[0])}
+    if image is not None:
+        v, _, f = ens.sensor_readings()
+        out.update(_reading_tags(v, f, *image))
+    return out
+
+
+def _reading_tags(v, f, vt, ft):
+    return {TR.IMAGE_VALUE: np.asarray(vt, dtype=np.float64), TR.IMAGE_FAULT: np.asarray(ft, dtype=np.float64),
+            TR.FIELD_VALUE: np.asarray(v, dtype=np.float64), TR.FIELD_FAULT: np.asarray(f, dtype=np.float64)}
+
+
 def refused_as_checked(nat, program, block) -> bool:
     """The message of the set call just refused on ``block`` is the one wt_program_check gives for it."""
     msg = nat.lib().wt_last_error()
@@ -115,18 +192,21 @@ def calls(n_steps, interval, lt=0.0, dt=DT):
 
 
 class HostScan:
-    """The host side of the PLC scan of N reactors: the restatements of the programs that are on (``ctl`` ControlRef,
-    ``inj`` InjectRef, ``alm`` AlarmRef, ``act`` ActuatorRef; None for a program that is off) and the loop time ``lt``
-    (N,) of the next scan.
+    """The host side of the PLC scan of N reactors, the one host-side statement of the device's scan order: inject ->
+    pack -> apply commands -> alarm override -> actuator -> loop time -> PI -> alarm -> detector -> trend.  It holds the
+    restatements of the programs that are on (``ctl`` ControlRef, ``inj`` InjectRef, ``alm`` AlarmRef, ``act``
+    ActuatorRef, ``det`` DetectRef, ``trd`` TrendRef; None for a program that is off) and the loop time ``lt`` (N,) of
+    the next scan.  The disturbance and score programs run after every outer step, not in the scan, and stay outside.
 
     ``emulated``: the device runs plant I/O without these programs, and the host master emulates the command path in
     the words it writes before a call (``holding``).  Otherwise the device runs them, and ``scan`` follows its command
     path from the decoded commands it is given."""
 
-    def __init__(self, N, ctl=None, inj=None, alm=None, act=None, emulated=False, dt=DT):
-        self.ctl, self.inj, self.alm, self.act = ctl, inj, alm, act
+    def __init__(self, N, ctl=None, inj=None, alm=None, act=None, det=None, trd=None, emulated=False, dt=DT):
+        self.ctl, self.inj, self.alm, self.act, self.det, self.trd = ctl, inj, alm, act, det, trd
         self.emulated, self.dt = emulated, dt
         self.lt = np.zeros(N)
+        self.values = None         # the tag -> rows dict the trend recorder saw at the last scan
         # an injection program without command slots leaves the commands as they are: skip its copy of them
         self.tampers = inj is not None and bool((inj.p[:, I_TARGET] >= CMD_ACID).any())
 
@@ -151,13 +231,37 @@ class HostScan:
             return words(self._command_path(commands(self.ctl.holding) if cmd is None else cmd))
         return self.ctl.holding if cmd is None else words(cmd)
 
-    def scan(self, v, f, cmd=None, stepped=None):
-        """One PLC scan at loop time ``lt`` in the device's order (the plant-I/O section of ``run_item`` in
-        csrc/wt_device.hpp): the injection's sensor slots tamper the readings ``v`` / ``f`` (7, N), which the input
-        image then packs; the decoded commands ``cmd`` (3, N) go through the injection's command slots, the alarm trips
-        and the actuators (no command path with ``cmd`` None); PI runs on the tampered readings; the alarms evaluate,
-        FIELD slots on the raw readings and IMAGE slots on the tampered ones.  ``stepped`` (N,): reactors that took
-        the step (default: all).  Returns the tampered readings."""
+    def tag_values(self, v, f, vt, ft):
+        """Tag -> rows of what a trend slot can read at the end of a scan, for every tag whose source is held here:
+        the image (``vt``, ``ft``) and field (``v``, ``f``) readings and fault codes, and the state of the restatements
+        that are on, laid out as the device's get blocks (row = ``unit * rows + row``).  A tag without a source is
+        absent and reads NaN, as on the device; COMMAND is the caller's (``scan``'s ``tags``): the validated command
+        rows are the device's ``boundary()``."""
+        N = len(self.lt)
+        out = _reading_tags(v, f, vt, ft)
+        for tag, ref in ((TR.CONTROL, self.ctl), (TR.INJECT, self.inj), (TR.ALARM, self.alm), (TR.ACTUATOR, self.act),
+                         (TR.DETECT, self.det)):
+            if ref is not None:
+                out[tag] = ref.st.reshape(-1, N)
+        if self.alm is not None:
+            out[TR.ALARM_WORD] = self.alm.words.astype(np.float64)
+        return out
+
+    def scan(self, v, f, cmd=None, stepped=None, tags=None):
+        """One PLC scan at loop time ``lt`` in the device's order (the blocks under ``if (plc_on)`` of ``run_item`` in
+        csrc/wt_device.hpp):
+          inject          the injection's sensor slots tamper the readings ``v`` / ``f`` (7, N),
+          pack            which the input image then packs;
+          apply commands  the decoded commands ``cmd`` (3, N) go through the injection's command slots,
+          alarm override  the alarm trips in force
+          actuator        and the actuators (no command path with ``cmd`` None);
+          loop time       the scan stores ``lt``;
+          PI              runs on the tampered readings;
+          alarm           FIELD slots on the raw readings, IMAGE slots on the tampered ones;
+          detector        likewise;
+          trend           last: a sample is an entry of ``tag_values`` as it stands at the end of this scan, with the
+                          entries of ``tags`` (tag -> rows) added or put in their place.
+        ``stepped`` (N,): reactors that took the step (default: all).  Returns the tampered readings."""
         assert cmd is None or not self.emulated, "an emulated command path runs in holding()"
         t = self.lt
         vt, ft = (v, f) if self.inj is None else self.inj.sensors(v, f, t, stepped)
@@ -169,13 +273,18 @@ class HostScan:
             self.ctl.scan(vt, ft, t, stepped)
         if self.alm is not None:
             self.alm.scan(v, f, t, stepped, image=(vt, ft))
+        if self.det is not None:
+            self.det.scan(v, f, t, stepped, image=(vt, ft))
+        if self.trd is not None:
+            self.values = {**self.tag_values(v, f, vt, ft), **(tags or {})}
+            self.trd.scan(self.values, t, stepped)
         return vt, ft
 
     def run(self, ens, n_steps, interval, fused=True, image=False):
         """The host loop a fused call replaces: calls of one scan interval, each after the master's write of
         ``holding()`` and closed by ``scan`` of the readings (and, unless ``emulated``, of the commands written).
-        ``image``: read the input image after every call, as a host master would.  Returns the last scan's
-        tampered readings."""
+        ``image``: read the input image after every call, as a host master would.  A trend recorder gets its COMMAND
+        rows from the device's ``boundary()``.  Returns the last scan's tampered readings."""
         for c in self.calls(n_steps, interval):
             w = self.holding()
             ens.write_holding(w)
@@ -183,5 +292,6 @@ class HostScan:
             v, _, f = ens.sensor_readings()
             if image:
                 ens.input_image()
-            out = self.scan(v, f, None if self.emulated else commands(w))
+            tags = None if self.trd is None else {TR.COMMAND: ens.boundary()[[4, 6, 0]]}
+            out = self.scan(v, f, None if self.emulated else commands(w), tags=tags)
         return out

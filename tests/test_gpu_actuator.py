@@ -9,18 +9,10 @@ from alarm_ref import AlarmRef
 from conftest import golden_json
 from control_ref import ControlRef
 from inject_ref import InjectRef
-from program_helpers import (DT, K, MASTER, HostScan, assert_all_equal, calls, pi_loops, plant, plant_state,
+from program_helpers import (DT, K, MASTER, HostScan, acts, assert_all_equal, calls, everything, pi_loops, plant, ref_acts,
                              refused_as_checked, words)
 
 pytestmark = pytest.mark.gpu
-
-
-def _acts(ens):
-    return ens.actuator_state().block() + (ens.boundary()[[0, 4, 6]],)
-
-
-def _ref_acts(ref):
-    return ref.st, ref.q, ref.t_prev, ref.rows()
 
 
 def _realistic(wt, N, seed, t_end):
@@ -70,7 +62,7 @@ def test_inert_and_cleared_programs_are_bit_invisible(gpu, wt, native):
             ens.set_actuators(*_realistic(wt, N, 2, K * DT))
             ens.clear_actuators()
         ens.step(DT, n_steps=K, download=False)
-        got.append(plant_state(ens) + ens.input_image() + (ens.control_state().block(),))
+        got.append(everything(ens, programs=("control",)))
         if prog in ("none", "disabled"):
             st = ens.actuator_state()
             assert not st.n_exec.any() and not st.delivered.any() and not st.travel.any()
@@ -96,7 +88,7 @@ def test_pass_through_elements_give_the_bits_of_no_program(gpu, wt, n, N):
             if prog:
                 ens.set_actuators(wt.Actuator("inlet"), wt.Actuator("acid"), wt.Actuator("chlorine"))
             ens.step(DT, n_steps=K, download=False)
-            out.append(plant_state(ens) + ens.input_image() + (ens.control_state().block(),))
+            out.append(everything(ens, programs=("control",)))
             if prog:
                 st, b = ens.actuator_state(), ens.boundary()
                 assert np.array_equal(st.position, st.demand) and np.array_equal(st.position, st.applied)
@@ -117,7 +109,7 @@ def _scripted_loop(ens, hs, interval, n_steps, rng):
         ens.step(DT, n_steps=c, download=False)
         v, _, f = ens.sensor_readings()
         hs.scan(v, f, cmd)
-        assert_all_equal(_ref_acts(hs.act), _acts(ens), (interval, n_calls))
+        assert_all_equal(ref_acts(hs.act), acts(ens), (interval, n_calls))
         n_calls += 1
     return n_calls
 
@@ -209,9 +201,9 @@ def test_end_to_end_equals_a_master_writing_the_applied_flows(gpu, wt):
         for (c, _), w in zip(calls(steps, interval), scripted if act else applied):
             ens.write_holding(words(w))
             ens.step(DT, n_steps=c, download=False)
-        out.append(plant_state(ens) + ens.input_image())
+        out.append(everything(ens, programs=()))
         if act:
-            assert_all_equal(_ref_acts(ref), _acts(ens), "end to end")
+            assert_all_equal(ref_acts(ref), acts(ens), "end to end")
         ens.close()
     assert not out[0][5].any()
     assert_all_equal(out[0], out[1], "end to end")
@@ -232,9 +224,9 @@ def test_fused_calls_equal_the_host_loop(gpu, wt, monkeypatch):
         ctl = ControlRef(cblock, np.zeros(N), holding=words(np.array(MASTER)[:, None] * np.ones(N)))
         act = ActuatorRef(block, ens.boundary(), np.zeros(N))
         HostScan(N, ctl=ctl, act=act).run(ens, K, interval)     # PI on the host, actuators on the device
-        out = plant_state(ens) + ens.input_image() + (ctl.st,) + _acts(ens)
+        out = everything(ens, programs=()) + (ctl.st,) + acts(ens)
         assert not out[5].any()
-        assert_all_equal(_ref_acts(act), _acts(ens), ("host loop", interval))
+        assert_all_equal(ref_acts(act), acts(ens), ("host loop", interval))
         refs[interval] = out
         ens.close()
     variants = [dict(streams=0, chunk=1), dict(streams=0, chunk=7), dict(streams=0, chunk=50), dict(streams=3, chunk=7),
@@ -255,7 +247,7 @@ def test_fused_calls_equal_the_host_loop(gpu, wt, monkeypatch):
             ens.step(DT, n_steps=c, fused=v.get("fused", True), download=False)
         if v.get("adaptive"):
             assert ens.schedule()["redeals"] >= 1 and not np.array_equal(ens.placement()[1], np.arange(N))
-        got = plant_state(ens) + ens.input_image() + (ens.control_state().block(),) + _acts(ens)
+        got = everything(ens, programs=("control", "actuator"))
         assert_all_equal(refs[1 if not v.get("fused", True) else v["chunk"]], got, v)
         ens.close()
         monkeypatch.delenv("WT_Q_TICKETS", raising=False)

@@ -8,7 +8,8 @@ from alarm_ref import AlarmRef
 from conftest import golden_json
 from control_ref import ControlRef
 from inject_ref import InjectRef
-from program_helpers import DT, K, MASTER, HostScan, assert_all_equal, pi_loops, plant, plant_state, refused_as_checked
+from program_helpers import (DT, K, MASTER, HostScan, alarms, assert_all_equal, everything, pi_loops, plant, ref_alarms,
+                             refused_as_checked)
 
 pytestmark = pytest.mark.gpu
 
@@ -31,14 +32,6 @@ def _program(wt, cols, seed=3):
     ]
 
 
-def _alarms(ens):
-    return ens.alarm_state().block() + (ens.alarm_words(),)
-
-
-def _ref_alarms(ref):
-    return ref.st, ref.rst, ref.words
-
-
 def test_inert_program_is_bit_invisible(gpu, wt):
     N, n = 1000, 8
     cols, bc = wt.make_ensemble(N, seed=41)
@@ -57,7 +50,7 @@ def test_inert_program_is_bit_invisible(gpu, wt):
         elif prog is not None:
             ens.set_alarms(*prog)
         ens.step(DT, n_steps=K, download=False)
-        got.append(plant_state(ens) + ens.input_image() + (ens.control_state().block(),))
+        got.append(everything(ens, programs=("control",)))
         if prog not in (None, "cleared"):
             st = ens.alarm_state()
             assert not st.active.any() and not st.n_act.any() and np.isnan(st.ovr_acid).all()
@@ -79,7 +72,7 @@ def test_fused_alarms_equal_the_host_loop(gpu, wt, n, N):
         ens.set_schedule(0, interval)
         ctl, alm = ControlRef(cblock, np.zeros(N)), AlarmRef(block, np.zeros(N))
         HostScan(N, ctl=ctl, alm=alm, emulated=True).run(ens, K, interval)     # PI and alarms without the feature
-        ref = plant_state(ens) + ens.input_image()
+        ref = everything(ens, programs=())
         assert not ref[5].any()
         assert np.mean(alm.st[:, 3].sum(axis=0) > 0) > 0.2, (n, interval)     # alarms activate in many reactors
         assert alm.rst[4:].sum() > 0, (n, interval)                          # and trips act
@@ -89,9 +82,9 @@ def test_fused_alarms_equal_the_host_loop(gpu, wt, n, N):
         ens.set_alarms(*prog)
         ens.enable_control(chlorine, acid)
         ens.step(DT, n_steps=K, download=False)
-        assert_all_equal(ref, plant_state(ens) + ens.input_image(), (n, interval))
+        assert_all_equal(ref, everything(ens, programs=()), (n, interval))
         assert np.array_equal(ens.control_state().block(), ctl.st), (n, interval)
-        assert_all_equal(_ref_alarms(alm), _alarms(ens), (n, interval, "alarms"))
+        assert_all_equal(ref_alarms(alm), alarms(ens), (n, interval, "alarms"))
         ens.close()
 
 
@@ -122,7 +115,7 @@ def test_field_and_image_under_spoofing(gpu, wt):
         k += steps
         vt, _ = hs.scan(vh[k], fh[k], np.zeros((3, N), dtype=np.float32))
         assert not vt[3].any()
-    assert_all_equal(_ref_alarms(ref), _alarms(ens), "spoofed")
+    assert_all_equal(ref_alarms(ref), alarms(ens), "spoofed")
     # from the scan after activation on, the plant doses the trip value
     on = st.t_first[1] < hs.lt[0]
     assert on.mean() > 0.9
@@ -170,7 +163,7 @@ def test_latch_and_masked_reset_across_calls(gpu, wt):
     ens.set_alarms(*prog)
     ens.step(DT, n_steps=K, download=False)
     ens.reset_alarms(mask)
-    ref_mid = _alarms(ens)
+    ref_mid = alarms(ens)
     ens.step(DT, n_steps=K, download=False)
     vh, _, fh, _ = ens.sensor_history()
     ref = AlarmRef(wt.alarm_block(N, *prog), np.zeros(N))
@@ -182,8 +175,8 @@ def test_latch_and_masked_reset_across_calls(gpu, wt):
             hs.scan(vh[k], fh[k], np.zeros((3, N), dtype=np.float32))
         if call == 0:
             ref.reset(mask)
-            assert_all_equal(_ref_alarms(ref), ref_mid, "after reset")
-    assert_all_equal(_ref_alarms(ref), _alarms(ens), "second call")
+            assert_all_equal(ref_alarms(ref), ref_mid, "after reset")
+    assert_all_equal(ref_alarms(ref), alarms(ens), "second call")
     assert np.all(ens.alarm_state().active[1] == 1)                      # a standing condition is never reset
     ens.reset_alarms()
     assert np.all(ens.alarm_state().active[1] == 1)
@@ -226,7 +219,7 @@ def test_schedules_placement_and_frozen_reactors(gpu, wt):
             ens.step(DT, n_steps=40, fused=v.get("fused", True), download=False)
         if v.get("adaptive"):
             assert ens.schedule()["redeals"] >= 1 and not np.array_equal(ens.placement()[1], np.arange(N))
-        got.append(plant_state(ens) + ens.input_image() + (ens.control_state().block(),) + _alarms(ens))
+        got.append(everything(ens, programs=("control", "alarm")))
         ens.close()
     assert got[0][-3][:, 3].sum() > 0                                     # some slot activated
     for g, v in zip(got[1:], range(1, 4)):

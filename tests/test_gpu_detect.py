@@ -7,7 +7,7 @@ import pytest
 from conftest import golden_json
 from detect_ref import DetectRef
 from inject_ref import InjectRef
-from program_helpers import DT, K, MASTER, HostScan, assert_all_equal, pi_loops, plant, plant_state, refused_as_checked
+from program_helpers import DT, K, MASTER, SCAN_PROGRAMS, HostScan, assert_all_equal, everything, pi_loops, plant, refused_as_checked
 
 pytestmark = pytest.mark.gpu
 
@@ -73,12 +73,11 @@ def _restate(wt, ens, N, interval, iblock, dblock, labels):
     vh, _, fh, filled = ens.sensor_history()
     assert np.all(filled == K)
     ref = DetectRef(dblock, labels, np.zeros(N))
-    hs = HostScan(N, inj=InjectRef(iblock))
+    hs = HostScan(N, inj=InjectRef(iblock), det=ref)
     k = -1
     for steps in hs.calls(K, interval):
         k += steps
-        vt, ft = hs.scan(vh[k], fh[k])
-        ref.scan(vh[k], fh[k], hs.lt, image=(vt, ft))
+        hs.scan(vh[k], fh[k])
     return ref
 
 
@@ -145,12 +144,7 @@ def _closed(wt, cols, bc, n, horizon):
     return ens
 
 
-def _everything(ens):
-    c = ens.score_curve()
-    return (plant_state(ens) + ens.input_image() + (ens.control_state().block(),) + tuple(ens.alarm_state().block())
-            + (ens.alarm_words(),) + tuple(ens.actuator_state().block()) + (ens.injection_state().block(),)
-            + (lambda d: (d.value, d.x, d.n_eval, d.n_draw, d.base, d.t_prev))(ens.disturbance_state())
-            + tuple(vars(ens.score_state()).values()) + (c.n_scored, c.n_low, c.n_high))
+EVERYTHING = SCAN_PROGRAMS + ("disturb", "score")           # all that _closed sets
 
 
 def _four(wt, N, horizon):
@@ -177,7 +171,7 @@ def test_changes_nothing(gpu, wt, n):
             ens.set_detectors(*_four(wt, N, steps * DT))
             ens.clear_detectors()
         ens.step(DT, n_steps=steps, download=False)
-        outs.append(_everything(ens))
+        outs.append(everything(ens, programs=EVERYTHING))
         if variant == "four":
             st = ens.detector_state()
             assert np.all(st.n_eval == 9) and st.n_alarm[3].sum() > 0 and st.n_tp.sum() > 0 and st.n_bad[1].sum() > 0

@@ -1,6 +1,6 @@
 """The per-reactor programs at the step-kernel instantiations the other program tests do not reach (csrc/wtphys.hip
 ``with_step_kernel``): wavefronts with idle lanes, an odd number of reactors per wavefront, a last wavefront-group that
-holds one reactor, and reactors that do not step while their wavefront neighbours do.  With all seven programs on, the
+holds one reactor, and reactors that do not step while their wavefront neighbours do.  With all eight programs on, the
 device's program state is the restatements' bit for bit after every call; one fused call is the call-per-interval loop;
 and programs that are off change nothing."""
 import numpy as np
@@ -13,11 +13,11 @@ import detect_ref as KR
 import disturb_ref as DR
 import inject_ref as IR
 import score_ref as SR
-from program_helpers import (DT, MASTER, HostScan, assert_all_equal, assert_equal_by_reactor, calls, instantiation, plant,
-                             plant_state, ragged_size, wavefront_groups, words)
-from test_gpu_actuator import _acts, _ref_acts, _words
-from test_gpu_alarm import _alarms, _ref_alarms
-from test_gpu_detect import _closed, _everything, _four
+import trend_ref as TR
+from program_helpers import (DT, MASTER, HostScan, acts, alarms, assert_all_equal, assert_equal_by_reactor, calls, everything,
+                             full_waves, instantiation, plant, ragged_size, ref_acts, ref_alarms, wavefront_groups, words)
+from test_gpu_actuator import _words
+from test_gpu_detect import EVERYTHING, _closed, _four
 from test_gpu_score import ROWS
 
 ZONES = (2, 3, 5, 7, 12, 16, 17)           # one or two per instantiation without a program test, and the lower edge of <5,false>
@@ -29,14 +29,6 @@ LABEL = (300.0, 800.0)
 SINE_AMPLITUDE, OU_SIGMA = 5.0, 0.3
 BINS = 16
 DT_PLACED = {16: 2.0, 17: 2.0}             # outer step of the adaptive-placement twins where 10 s gives the sort nothing to do
-
-
-@pytest.fixture
-def full_waves(monkeypatch):
-    """The library spreads an ensemble smaller than the device's wavefront slots over more wavefronts than it needs
-    (down to one reactor each); WT_FULL_WAVES, read when an ensemble is created, packs 64 // n reactors into each, as
-    a large ensemble is packed.  Without it nothing in this module would share a wavefront."""
-    monkeypatch.setenv("WT_FULL_WAVES", "1")
 
 
 def test_zone_counts_reach_every_program_instantiation():
@@ -78,7 +70,7 @@ def _window(cls, rng, shift=0):
 
 
 def _programs(wt, cols, bc, n, cls):
-    """All seven programs.  Each scan program has one slot forced to act at every scan of every reactor that steps and
+    """All eight programs.  Each scan program has one slot forced to act at every scan of every reactor that steps and
     realistic slots with per-reactor parameters around the reactor's own start."""
     N = len(cls)
     rng = np.random.default_rng(100 + n)
@@ -145,8 +137,15 @@ def _programs(wt, cols, bc, n, cls):
               wt.Score("temperature", hi=0.0, reduce=np.choose(r % 2, ["min", "max"])),
               wt.Score("chlorine", lo=cl0 - 0.2, reduce="mean", t_start=100.0, t_end=1000.0)]
     fan = ([0.0, 6.0, 5.0, 0.0], [6.0, 9.0, 35.0, 5.0])
+    # trends: a tag of every other scan program, an image value and a field fault code; slots 0, 1, 4, 5 and 7 record
+    # every candidate (every 1, 2 or 3), slots 2, 3 and 6 changes only
+    trends = [wt.Trend("control", ("chlorine", "output")), wt.Trend("inject", (0, "n_applied"), every=3),
+              wt.Trend("alarm", (1, "time_active"), deadband=0.0), wt.Trend("alarm_word", deadband=0.0),
+              wt.Trend("actuator", ("chlorine", "position")),
+              wt.Trend("detect", r % 4 * 16 + KR.KS_STAT, every=np.choose(r % 2, [1, 2])),
+              wt.Trend("image_value", "chlorine_outlet", deadband=0.0), wt.Trend("field_fault", "pH_outlet", every=3)]
     return dict(loops=(chlorine, acid), injections=injections, alarms=alarms, actuators=actuators, detectors=detectors,
-                disturbances=disturbances, scores=scores, fan=fan)
+                disturbances=disturbances, scores=scores, fan=fan, trends=trends)
 
 
 def _set_all(wt, ens, p):
@@ -157,6 +156,7 @@ def _set_all(wt, ens, p):
     ens.set_detectors(*p["detectors"], attack=LABEL)
     ens.set_disturbances(*p["disturbances"], seed=99, reactor_base=5, history=STEPS + 1)
     ens.set_scores(*p["scores"], curve=STEPS, bins=BINS, fan_range=p["fan"])
+    ens.set_trends(*p["trends"], capacity=STEPS)           # a scan per step at the most: nothing is dropped
 
 
 def _shares(flag, among):
@@ -173,7 +173,7 @@ def test_everything_on_equals_the_restatements(gpu, wt, full_waves, n):
     blocks = dict(ctl=wt.control_block(N, *p["loops"]), inj=wt.injection_block(N, *p["injections"]),
                   alm=wt.alarm_block(N, *p["alarms"]), act=wt.actuator_block(N, *p["actuators"]),
                   det=wt.detector_block(N, *p["detectors"]), dst=wt.disturbance_block(N, *p["disturbances"]),
-                  scr=wt.score_block(N, *p["scores"]))
+                  scr=wt.score_block(N, *p["scores"]), trd=wt.trend_block(N, *p["trends"]))
     labels = np.array(LABEL)[:, None] * np.ones(N)
     dst_ref, times = None, None
     for interval in (1, 7):
@@ -190,7 +190,8 @@ def test_everything_on_equals_the_restatements(gpu, wt, full_waves, n):
         zero = np.zeros(N)
         ctl, inj, alm = CR.ControlRef(blocks["ctl"], zero), IR.InjectRef(blocks["inj"]), LR.AlarmRef(blocks["alm"], zero)
         act, det = AR.ActuatorRef(blocks["act"], bc0, zero), KR.DetectRef(blocks["det"], labels, zero)
-        hs = HostScan(N, ctl=ctl, inj=inj, alm=alm, act=act)
+        trd = TR.TrendRef(blocks["trd"], STEPS)
+        hs = HostScan(N, ctl=ctl, inj=inj, alm=alm, act=act, det=det, trd=trd)          # no COMMAND slot: every tag is held
         rng = np.random.default_rng(10 * n + interval)
         t_before, done, scans = np.zeros(N), 0, np.zeros(N)
         for k, c in enumerate(hs.calls(STEPS, interval)):
@@ -208,14 +209,14 @@ def test_everything_on_equals_the_restatements(gpu, wt, full_waves, n):
             t_before = t_now
             scans += stepped
             v, _, f = ens.sensor_readings()
-            image = hs.scan(v, f, cmd, stepped)
-            det.scan(v, f, hs.lt, stepped, image=image)
+            hs.scan(v, f, cmd, stepped)
             what = (n, interval, k)
             assert_equal_by_reactor((ctl.st,), (ens.control_state().block(),), what + ("control",), R)
             assert_equal_by_reactor((inj.st,), (ens.injection_state().block(),), what + ("injection",), R)
-            assert_equal_by_reactor(_ref_alarms(alm), _alarms(ens), what + ("alarm",), R)
-            assert_equal_by_reactor(_ref_acts(act), _acts(ens), what + ("actuator",), R)
+            assert_equal_by_reactor(ref_alarms(alm), alarms(ens), what + ("alarm",), R)
+            assert_equal_by_reactor(ref_acts(act), acts(ens), what + ("actuator",), R)
             assert_equal_by_reactor((det.st, det.t_prev), ens.detector_state().block(), what + ("detector",), R)
+            assert_equal_by_reactor((trd.st,), (ens.trend_state().block(),), what + ("trend",), R)
         assert done == STEPS
         # who stepped: the ensemble did what the roles say
         es = ens.state
@@ -225,6 +226,9 @@ def test_everything_on_equals_the_restatements(gpu, wt, full_waves, n):
         assert np.all(es.status[never] & 64) and np.all(es.status[stopped] & 1) and not (es.status[through] & FROZEN).any()
         assert np.array_equal(scans, -(-took // interval)), (n, interval)
         assert np.array_equal(ens.sensor_history()[3], took)
+        d = ens.trend_data()
+        held = trd.data()
+        assert_equal_by_reactor(held, (d.time, d.value, d.count), (n, interval, "trend data"), R)
         # the disturbance and score programs against the recorded per-step times and true trajectory
         tr = ens.trajectory()
         assert len(tr) == STEPS
@@ -276,6 +280,17 @@ def test_everything_on_equals_the_restatements(gpu, wt, full_waves, n):
         assert np.array_equal(scr.st[2, SR.S_N_EVAL], took) and np.array_equal(scr.st[2, SR.S_T_HIGH], took * DT)
         assert np.array_equal(alm.st[2, LR.AS_N_BAD], scans)                     # both on_bad policies ran on bad readings
         assert np.array_equal(det.st[2, KR.KS_N_BAD], scans)
+        # every trend slot recorded at every reactor that was scanned, the lone one included: the first candidate always,
+        # every candidate without a deadband; nothing was dropped, and the slots that record changes saw some
+        every = blocks["trd"][:, TR.T_EVERY]
+        assert np.array_equal(trd.st[:, TR.TS_N_SEEN], np.tile(scans, (8, 1))) and not trd.st[:, TR.TS_N_DROPPED].any()
+        assert np.all(held[2][:, through] >= 1) and np.all(held[2][:, N - 1] >= 1) and not held[2][:, never].any()
+        for slot in (0, 1, 4, 5, 7):
+            assert np.array_equal(held[2][slot], -(-scans // every[slot])), (n, interval, slot)
+        for slot in (2, 3, 6):
+            assert (held[2][slot, through] > 1).any(), (n, interval, slot)
+        assert np.isfinite(held[1][[0, 1, 2, 3, 4, 5, 7], 0][:, through]).all()     # state entries, the word and a fault code
+        print("trend samples held per slot (min, max)", n, interval, [(int(c.min()), int(c.max())) for c in held[2][:, through]])
         chl = ctl.st[0]
         share = dict(
             pi=((chl[CR.CS_N_SAT] > 0), (chl[CR.CS_N_EXEC] > 0) & (chl[CR.CS_N_SAT] == 0)),
@@ -311,7 +326,7 @@ def _run_closed(wt, cols, bc, n, steps, *, chunk=7, streams=0, adaptive=False, p
         ens.step(dt, n_steps=c, download=False)
     if adaptive:
         assert ens.schedule()["redeals"] >= 1 and not np.array_equal(ens.placement()[1], np.arange(N))
-    out = _everything(ens) + ens.detector_state().block()
+    out = everything(ens, programs=EVERYTHING) + ens.detector_state().block()
     assert wavefront_groups(ens) == 6
     ens.close()
     return out
@@ -361,7 +376,7 @@ def test_programs_that_are_off_change_nothing(gpu, wt, full_waves, n):
             ens.set_disturbances(wt.Disturbance("inlet_pH"), wt.Disturbance(8, "off"), history=5)
             ens.set_scores(*[wt.Score("chlorine", 0.0, 1.0, kind="off")] * 4, curve=steps)
         ens.step(DT, n_steps=steps, download=False)
-        outs.append(plant_state(ens) + ens.input_image())
+        outs.append(everything(ens, programs=()))
         if off:
             assert not ens.actuator_state().n_exec.any() and not ens.injection_state().n_applied.any()
             assert not ens.alarm_words().any() and not ens.score_state().n_eval.any() and not ens.detector_state().n_eval.any()

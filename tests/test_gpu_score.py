@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 import score_ref as SR
-from program_helpers import DT, MASTER, assert_all_equal, pi_loops, plant, plant_state, refused_as_checked
+from program_helpers import DT, MASTER, SCAN_PROGRAMS, assert_all_equal, everything, pi_loops, plant, plant_state, refused_as_checked
 from score_ref import ScoreRef
 
 pytestmark = pytest.mark.gpu
@@ -107,12 +107,6 @@ def _closed(wt, cols, bc, n, N, horizon):
     return ens
 
 
-def _everything(ens):
-    return (plant_state(ens) + ens.input_image() + (ens.control_state().block(),) + tuple(ens.alarm_state().block())
-            + tuple(ens.actuator_state().block()) + (ens.injection_state().block(),)
-            + (lambda d: (d.value, d.x, d.n_eval, d.n_draw, d.base, d.t_prev))(ens.disturbance_state()))
-
-
 @pytest.mark.parametrize("n", [4, 8, 20, 32])
 def test_changes_nothing(gpu, wt, n):
     N, K = 96, 60
@@ -125,7 +119,7 @@ def test_changes_nothing(gpu, wt, n):
         if scored:
             ens.set_scores(*scores, curve=K, bins=32, fan_range=fan)
         ens.step(DT, n_steps=K, download=False)
-        outs.append(_everything(ens))
+        outs.append(everything(ens, programs=SCAN_PROGRAMS + ("disturb",)))
         if scored:
             assert np.all(ens.score_state().n_eval[0] == K) and np.all(ens.score_curve().n_scored[:, 0] == N)
         ens.close()

@@ -8,7 +8,8 @@ import pytest
 
 import trend_ref as TR
 from inject_ref import InjectRef
-from program_helpers import DT, MASTER, HostScan, assert_all_equal, assert_equal_by_reactor, instantiation, pi_loops, plant, plant_state, ragged_size
+from program_helpers import (DT, MASTER, SCAN_PROGRAMS, HostScan, assert_all_equal, assert_equal_by_reactor, everything, full_waves,
+                             instantiation, pi_loops, plant, ragged_size, trend_tag_values)
 from trend_ref import TrendRef
 
 pytestmark = pytest.mark.gpu
@@ -16,13 +17,6 @@ pytestmark = pytest.mark.gpu
 STEPS, CHUNK = 40, 4               # ten scans, at 40, 80, ... 400 s
 HORIZON = STEPS * DT
 CAPACITY = 16
-
-
-@pytest.fixture
-def full_waves(monkeypatch):
-    """Packs 64 // n reactors into every wavefront, as a large ensemble is packed (WT_FULL_WAVES is read when an
-    ensemble is created); without it a small ensemble is spread over one wavefront per reactor."""
-    monkeypatch.setenv("WT_FULL_WAVES", "1")
 
 
 def _injections(wt, N):
@@ -65,18 +59,6 @@ def _trends(wt, N):
             wt.Trend("detect", (r % 2, "stat"), every=3)]
 
 
-def _values(ens, image):
-    """Every tag's values at the scan that closed the last call, from the public getters (and the image the scan saw)."""
-    N = ens.n_reactors
-    v, _, f = ens.sensor_readings()
-    vt, ft = image(v, f)
-    return {TR.IMAGE_VALUE: vt.astype(np.float64), TR.IMAGE_FAULT: ft.astype(np.float64), TR.FIELD_VALUE: v.astype(np.float64),
-            TR.FIELD_FAULT: f.astype(np.float64), TR.COMMAND: ens.boundary()[[4, 6, 0]],
-            TR.CONTROL: ens.control_state().block().reshape(-1, N), TR.INJECT: ens.injection_state().block().reshape(-1, N),
-            TR.ALARM: ens.alarm_state().block()[0].reshape(-1, N), TR.ALARM_WORD: ens.alarm_words().astype(np.float64),
-            TR.ACTUATOR: ens.actuator_state().block()[0].reshape(-1, N), TR.DETECT: ens.detector_state().block()[0].reshape(-1, N)}
-
-
 def _data(ens):
     d = ens.trend_data()
     return d.time, d.value, d.count, ens.trend_state().block()
@@ -89,15 +71,17 @@ def test_fused_call_equals_the_host_loop(gpu, wt, full_waves, n):
     cols, bc = wt.make_ensemble(N, seed=1500 + n)
     trends = _trends(wt, N)
     # the host loop: a call per scan interval on an ensemble without trends, the getters after each, the restatement
+    # (the injection's for the image the scan saw, the recorder's for the thinning and the store)
     ens = _closed(wt, cols, bc, n)
     ref = TrendRef(wt.trend_block(N, *trends), CAPACITY)
-    hs = HostScan(N, inj=InjectRef(wt.injection_block(N, *_injections(wt, N))))
+    hs = HostScan(N, inj=InjectRef(wt.injection_block(N, *_injections(wt, N))), trd=ref)
     seen = {}
     for c in hs.calls(STEPS, CHUNK):
         ens.step(DT, n_steps=c, download=False)
-        vals = _values(ens, hs.scan)
-        ref.scan(vals, hs.lt)
-        for tag, x in vals.items():
+        v, _, f = ens.sensor_readings()
+        hs.scan(v, f, tags=trend_tag_values(ens))
+        assert len(hs.values) == 11
+        for tag, x in hs.values.items():
             seen.setdefault(tag, []).append(np.array(x))
     assert not ens.state.status.any() and np.all(ens.state.time == HORIZON)
     ens.close()
@@ -125,11 +109,6 @@ def test_fused_call_equals_the_host_loop(gpu, wt, full_waves, n):
         assert tag == TR.FIELD_FAULT or (s != s[0]).any(), (n, tag)          # (the instruments may run without a fault of their own)
 
 
-def _everything(ens):
-    return (plant_state(ens) + ens.input_image() + (ens.control_state().block(), ens.injection_state().block(), ens.alarm_words())
-            + tuple(ens.alarm_state().block()) + tuple(ens.actuator_state().block()) + tuple(ens.detector_state().block()))
-
-
 @pytest.mark.parametrize("n", [8, 20])
 def test_changes_nothing(gpu, wt, full_waves, n):
     R, N = ragged_size(n)
@@ -145,7 +124,7 @@ def test_changes_nothing(gpu, wt, full_waves, n):
             ens.set_trends(*_trends(wt, N), capacity=CAPACITY)
             ens.clear_trends()
         ens.step(DT, n_steps=STEPS, download=False)
-        outs.append(_everything(ens))
+        outs.append(everything(ens, programs=SCAN_PROGRAMS + ("detect",)))
         if variant == "eight":
             assert np.all(ens.trend_state().n_recorded[0] == STEPS // CHUNK) and np.all(ens.trend_data().count[0] == 3)
         elif variant == "off":

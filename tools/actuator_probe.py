@@ -7,20 +7,13 @@ step, one fused call each:
 The three alternate over five repeats, the order rotating; the medians are reported.  (c) also integrates the plant
 under different doses, so its time is not the evaluation's alone.  Prints one JSON line.
    python tools/actuator_probe.py [N] [n] [steps]"""
-import importlib, json, os, sys, time
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import json, sys
 import numpy as np
-wt = importlib.import_module("ics-wt-physicsengine_amd")
+from probe_common import arguments, outputs, pi_loops, plant, rotate, same, timed_step, wt
 
-N = int(sys.argv[1]) if len(sys.argv) > 1 else 10000
-n = int(sys.argv[2]) if len(sys.argv) > 2 else 8
-K = int(sys.argv[3]) if len(sys.argv) > 3 else 120
+N, n, K, cols, bc = arguments(120)
 DT = 10.0
-cols, bc = wt.make_ensemble(N)
-u = np.random.default_rng(3).random((12, N))
-chlorine = wt.PILoop("chlorine_outlet", setpoint=cols["initial_chlorine"] + 0.5, kp=0.5 + 1.5 * u[0], ki=1e-3 * u[1], bias=0.2)
-acid = wt.PILoop("pH_outlet", setpoint=7.0 + 0.4 * u[2], kp=0.5, ki=1e-4 + 1e-3 * u[3], direction=-1, bias=0.1)
+chlorine, acid, u = pi_loops(cols, N, 12)
 passthrough = [wt.Actuator("acid"), wt.Actuator("chlorine"), wt.Actuator("inlet")]
 realistic = [wt.Actuator("acid", tau=30.0 + 90.0 * u[4], rate=0.002 + 0.01 * u[5], backlash=0.02,
                          delay=1 + (u[6] * 3).astype(int) % 3),
@@ -30,33 +23,14 @@ realistic = [wt.Actuator("acid", tau=30.0 + 90.0 * u[4], rate=0.002 + 0.01 * u[5
 VARIANTS = {"a": None, "b": passthrough, "c": realistic}
 
 
-def plant():
-    ens = wt.ReactorEnsemble(cols, n_zones=n)
-    ens.set_boundary(bc)
-    ens.enable_sensors(seed=1)
-    ens.enable_plant_io()
-    ens.set_schedule(0, 1)
+def run(name, rep=0):
+    ens = plant(cols, bc, n)
     ens.write_commands(0.5, 0.25, 6.0)
     ens.enable_control(chlorine, acid)
-    return ens
-
-
-def outputs(ens):
-    es = ens.state
-    return (es.pH, es.chlorine, es.temperature, es.time, es.flow_rate, es.status) + ens.sensor_readings() + \
-        (ens.boundary(), ens.control_state().block()) + ens.input_image()
-
-
-def run(name):
-    ens = plant()
     if VARIANTS[name] is not None:
         ens.set_actuators(*VARIANTS[name])
-    ens.synchronize()
-    t0 = time.perf_counter()
-    ens.step(DT, n_steps=K, download=False)
-    ens.synchronize()
-    dt = time.perf_counter() - t0
-    out = outputs(ens)
+    _, dt = timed_step(ens, DT, K)
+    out = outputs(ens, "sensor_readings", "boundary", "control_state", "input_image")
     st = ens.actuator_state() if VARIANTS[name] is not None else None
     ens.close()
     return dt, out, st
@@ -64,26 +38,15 @@ def run(name):
 
 run("c")                                         # module load, first launches
 REPEATS = 5
-times = {k: [] for k in VARIANTS}
-orders = ("abc", "bca", "cab")
-for rep in range(REPEATS):
-    for name in orders[rep % 3]:
-        t, out, st = run(name)
-        times[name].append(t)
-        if name == "a":
-            out_a = out
-        elif name == "b":
-            out_b = out
-        else:
-            st_c = st
-med = {k: float(np.median(v)) for k, v in times.items()}
-same = all(np.array_equal(x, y, equal_nan=True) for x, y in zip(out_a, out_b))
+times, med, last = rotate("abc", REPEATS, run)
+st_c = last["c"][2]
+equal = same(last["a"][1], last["b"][1])
 print(json.dumps({"N": N, "n": n, "steps": K, "control_only_s": round(med["a"], 4), "passthrough_s": round(med["b"], 4),
                   "realistic_s": round(med["c"], 4), "passthrough_over_control": round(med["b"] / med["a"], 3),
                   "realistic_over_control": round(med["c"] / med["a"], 3), "repeats": REPEATS,
                   "stuck_reactors": int(np.sum(st_c.n_fault[1] > 0)),
                   "rate_limited_scans": int(st_c.n_rate.sum()),
                   "all_s": {k: [round(t, 4) for t in v] for k, v in times.items()},
-                  "passthrough_bitwise_equal": bool(same)}))
-if not same:
+                  "passthrough_bitwise_equal": bool(equal)}))
+if not equal:
     sys.exit(1)

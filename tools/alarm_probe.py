@@ -10,30 +10,18 @@
 bitwise the same states, readings, boundaries, controller, injection and alarm states and alarm words, and prints one
 JSON line.
    python tools/alarm_probe.py [N] [n] [steps]"""
-import importlib, json, os, sys, time
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import json, sys, time
 import numpy as np
+from probe_common import arguments, injections, outputs, pi_loops, plant, rotate, same, timed_step, wt
 from alarm_ref import AlarmRef
 from control_ref import ControlRef
 from inject_ref import InjectRef
 from program_helpers import HostScan
-wt = importlib.import_module("ics-wt-physicsengine_amd")
 
-N = int(sys.argv[1]) if len(sys.argv) > 1 else 10000
-n = int(sys.argv[2]) if len(sys.argv) > 2 else 8
-K = int(sys.argv[3]) if len(sys.argv) > 3 else 120
+N, n, K, cols, bc = arguments(120)
 DT = 10.0
-cols, bc = wt.make_ensemble(N)
-u = np.random.default_rng(3).random((8, N))
-chlorine = wt.PILoop("chlorine_outlet", setpoint=cols["initial_chlorine"] + 0.5, kp=0.5 + 1.5 * u[0], ki=1e-3 * u[1], bias=0.2)
-acid = wt.PILoop("pH_outlet", setpoint=7.0 + 0.4 * u[2], kp=0.5, ki=1e-4 + 1e-3 * u[3], direction=-1, bias=0.1)
-span = K * DT
-program = [wt.Injection("chlorine_outlet", "constant", start=0.25 * span, end=0.5 * span, a=0.0),      # spoofed low
-           wt.Injection("pH_outlet", "freeze", start=span * u[4], end=span * u[4] + 0.3 * span),         # frozen probe
-           wt.Injection("chlorine_outlet", "bias", start=0.6 * span, a=-0.5 * u[5]),
-           wt.Injection("pH_inlet", "fault", start=0.8 * span, a=3)]
+chlorine, acid, u = pi_loops(cols, N, 8)
+program = injections(u, K * DT)
 cl0 = np.asarray(cols["initial_chlorine"])
 alarms = [wt.Alarm("chlorine_outlet", "high", cl0 + 0.8, deadband=0.1, on_delay=30.0, latch=True, source="field",
                    action="trip_chlorine", trip_value=0.05),                                         # the trip that fires
@@ -42,52 +30,34 @@ alarms = [wt.Alarm("chlorine_outlet", "high", cl0 + 0.8, deadband=0.1, on_delay=
           wt.Alarm("pH_inlet", "high", 9.5, on_bad="alarm")]
 cblock, iblock, ablock = wt.control_block(N, chlorine, acid), wt.injection_block(N, *program), wt.alarm_block(N, *alarms)
 
+OUT = ("sensor_readings", "boundary", "control_state")
 
-def plant():
-    ens = wt.ReactorEnsemble(cols, n_zones=n)
-    ens.set_boundary(bc)
-    ens.enable_sensors(seed=1)
-    ens.enable_plant_io()
-    ens.set_schedule(0, 1)
-    return ens
-
-
-def outputs(ens):
-    es = ens.state
-    return (es.pH, es.chlorine, es.temperature, es.time, es.flow_rate, es.status) + ens.sensor_readings() + \
-        (ens.boundary(), ens.control_state().block())
-
-
-warm = plant()                                   # module load, first launches
+warm = plant(cols, bc, n)                                   # module load, first launches
 warm.enable_control(chlorine, acid); warm.set_injections(*program); warm.set_alarms(*alarms)
 warm.step(DT, n_steps=2, download=False); warm.alarm_state(); warm.close()
 
 
 def host_loop():
-    ens = plant()
+    ens = plant(cols, bc, n)
     ctl, inj, alm = ControlRef(cblock, np.zeros(N)), InjectRef(iblock), AlarmRef(ablock, np.zeros(N))
     ens.enable_control()                         # both loops off: control_state() is kept for the comparison
     ens.synchronize()
     t0 = time.perf_counter()
     HostScan(N, ctl=ctl, inj=inj, alm=alm, emulated=True, dt=DT).run(ens, K, 1, fused=False, image=True)
     dt = time.perf_counter() - t0
-    out = outputs(ens)[:-1]
+    out = outputs(ens, *OUT)[:-1]
     ens.close()
     return dt, out + (ctl.st,), (inj.st, alm.st, alm.rst, alm.words)
 
 
-def fused(alarm):
-    ens = plant()
+def fused(alarm, rep):
+    ens = plant(cols, bc, n)
     ens.enable_control(chlorine, acid)
     ens.set_injections(*program)
     if alarm:
         ens.set_alarms(*alarms)
-    ens.synchronize()
-    t0 = time.perf_counter()
-    ens.step(DT, n_steps=K, download=False)
-    ens.synchronize()
-    dt = time.perf_counter() - t0
-    out = outputs(ens)
+    _, dt = timed_step(ens, DT, K)
+    out = outputs(ens, *OUT)
     st = (ens.injection_state().block(),) + ens.alarm_state().block() + (ens.alarm_words(),) if alarm else None
     ens.close()
     return dt, out, st
@@ -95,22 +65,16 @@ def fused(alarm):
 
 REPEATS = 5
 ta, out_a, st_a = host_loop()
-tb_all, tc_all = [], []
-for rep in range(REPEATS):                       # the two fused variants alternate, in both orders
-    for alarm in ((True, False) if rep % 2 == 0 else (False, True)):
-        t, out, st = fused(alarm)
-        (tb_all if alarm else tc_all).append(t)
-        if alarm:
-            out_b, st_b = out, st
-tb, tc = float(np.median(tb_all)), float(np.median(tc_all))
-same = all(np.array_equal(a, b, equal_nan=True) for a, b in zip(out_a, out_b)) and \
-    all(np.array_equal(a, b, equal_nan=True) for a, b in zip(st_a, st_b))
+times, med, last = rotate((True, False), REPEATS, fused)     # the two fused variants alternate, in both orders
+tb_all, tc_all, tb, tc = times[True], times[False], med[True], med[False]
+_, out_b, st_b = last[True]
+equal = same(out_a, out_b) and same(st_a, st_b)
 trips = int(np.sum(st_a[2][4:]))
 print(json.dumps({"N": N, "n": n, "steps": K, "host_loop_s": round(ta, 4), "fused_alarm_s": round(tb, 4),
                   "without_alarm_s": round(tc, 4), "loop_over_fused": round(ta / tb, 2),
                   "alarm_over_without": round(tb / tc, 3), "repeats": REPEATS,
                   "reactors_tripped": int(np.sum(st_a[1][0, 3] > 0)), "overridden_scans": trips,
                   "fused_alarm_all_s": [round(t, 4) for t in tb_all], "without_alarm_all_s": [round(t, 4) for t in tc_all],
-                  "bitwise_equal": bool(same)}))
-if not same:
+                  "bitwise_equal": bool(equal)}))
+if not equal:
     sys.exit(1)

@@ -11,19 +11,13 @@ The seven alternate over five repeats, the order rotating; the medians are repor
 equal (a)'s bit for bit, the curves of (e) and (f) must agree, and (f)'s rows must equal the restatement's of (g).
 Prints one JSON line.
    python tools/score_probe.py [N] [n] [steps]"""
-import importlib, json, os, sys, time
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
+import json, sys, time
 import numpy as np
+from probe_common import arguments, ensemble, outputs, rotate, same, timed_step, wt
 from score_ref import ScoreRef
-wt = importlib.import_module("ics-wt-physicsengine_amd")
 
-N = int(sys.argv[1]) if len(sys.argv) > 1 else 10000
-n = int(sys.argv[2]) if len(sys.argv) > 2 else 8
-K = int(sys.argv[3]) if len(sys.argv) > 3 else 500
+N, n, K, cols, bc = arguments(500)
 DT = 10.0
-cols, bc = wt.make_ensemble(N)
 S = wt.Score
 OFF = tuple(S(q, kind="off") for q in ("pH", "chlorine", "temperature", "chlorine"))
 ZONE = (S("chlorine", 0.2, 4.0), S("pH", 6.5, 8.5), S("temperature", hi=25.0), S("temperature", hi=25.0, zone=0))
@@ -34,22 +28,13 @@ VARIANTS = {"a": None, "b": (OFF, {}), "c": (ZONE, {}), "d": (MIXED, {}), "e": (
             "f": (MIXED, dict(curve=K, bins=32, fan_range=FAN)), "g": None}
 
 
-def outputs(ens):
-    es = ens.state
-    return (es.pH, es.chlorine, es.temperature, es.time, es.flow_rate, es.status)
-
-
-def run(name):
-    ens = wt.ReactorEnsemble(cols, n_zones=n)
-    ens.set_boundary(bc)
+def run(name, rep=0):
+    ens = ensemble(cols, bc, n)
     if VARIANTS[name] is not None:
         ens.set_scores(*VARIANTS[name][0], **VARIANTS[name][1])
     if name == "g":
         ens.record(every=1, capacity=K)
-    ens.synchronize()
-    t0 = time.perf_counter()
-    ens.step(DT, n_steps=K, download=False)
-    ens.synchronize()
+    t0, _ = timed_step(ens, DT, K)
     extra = None
     if name == "g":
         tr = ens.trajectory()
@@ -70,23 +55,18 @@ def run(name):
 run("f")                                         # module load, first launches
 REPEATS = 5
 names = "abcdefg"
-times = {k: [] for k in names}
-outs, extras = {}, {}
-for rep in range(REPEATS):
-    for name in names[rep % 7:] + names[:rep % 7]:
-        t, outs[name], extras[name] = run(name)
-        times[name].append(t)
-med = {k: float(np.median(v)) for k, v in times.items()}
-same = all(np.array_equal(x, y, equal_nan=True) for k in names[1:] for x, y in zip(outs["a"], outs[k]))
+times, med, last = rotate(names, REPEATS, run)
+extras = {k: last[k][2] for k in names}
+equal = all(same(last["a"][1], last[k][1]) for k in names[1:])
 curves = np.array_equal(extras["e"][1], extras["f"][1])
-exact = all(np.array_equal(x, y, equal_nan=True) for x, y in zip(extras["f"], extras["g"]))
+exact = same(extras["f"], extras["g"])
 labels = {"a": "none", "b": "all_off", "c": "zone", "d": "mixed", "e": "curve", "f": "fan", "g": "record_and_host"}
 res = {"N": N, "n": n, "steps": K, "repeats": REPEATS}
 res.update({labels[k] + "_s": round(med[k], 4) for k in names})
 res.update({labels[k] + "_over_none": round(med[k] / med["a"], 3) for k in names[1:]})
 res.update({"record_bytes": int(K * N * (3 * n + 2) * 8 + K * N * 4),
             "all_s": {k: [round(t, 4) for t in v] for k, v in times.items()},
-            "state_bitwise_equal": bool(same), "curve_equals_fan_run": bool(curves), "fan_run_equals_restatement": bool(exact)})
+            "state_bitwise_equal": bool(equal), "curve_equals_fan_run": bool(curves), "fan_run_equals_restatement": bool(exact)})
 print(json.dumps(res))
-if not (same and curves and exact):
+if not (equal and curves and exact):
     sys.exit(1)

@@ -12,20 +12,13 @@ alternate over nine repeats in rotating order; the medians and the minima of the
 time of one download of the whole store (all eight slots' capacity, used or not).  Checks that every plant state of
 (b), (c) and (d) is bitwise (a)'s and that (c)'s series is (d)'s, and prints one JSON line.
    python tools/trend_probe.py [N] [n] [steps]"""
-import importlib, json, os, sys, time
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import json, sys, time
 import numpy as np
-wt = importlib.import_module("ics-wt-physicsengine_amd")
+from probe_common import arguments, outputs, pi_loops, plant, rotate, same, timed_step, wt
 
-N = int(sys.argv[1]) if len(sys.argv) > 1 else 10000
-n = int(sys.argv[2]) if len(sys.argv) > 2 else 8
-K = int(sys.argv[3]) if len(sys.argv) > 3 else 500
+N, n, K, cols, bc = arguments(500)
 DT, CAPACITY, WARMUP = 1.0, 512, 100
-cols, bc = wt.make_ensemble(N)
-u = np.random.default_rng(3).random((4, N))
-chlorine = wt.PILoop("chlorine_outlet", setpoint=cols["initial_chlorine"] + 0.5, kp=0.5 + 1.5 * u[0], ki=1e-3 * u[1], bias=0.2)
-acid = wt.PILoop("pH_outlet", setpoint=7.0 + 0.4 * u[2], kp=0.5, ki=1e-4 + 1e-3 * u[3], direction=-1, bias=0.1)
+chlorine, acid, _ = pi_loops(cols, N)
 one = [wt.Trend("control", ("chlorine", "output"))]
 eight = one + [wt.Trend("image_value", "chlorine_outlet"), wt.Trend("field_value", "chlorine_outlet"), wt.Trend("command", "chlorine"),
                wt.Trend("control", ("acid", "output")), wt.Trend("control", ("chlorine", "ise")), wt.Trend("alarm_word"),
@@ -33,52 +26,31 @@ eight = one + [wt.Trend("image_value", "chlorine_outlet"), wt.Trend("field_value
 off = [wt.Trend("off")] * 8
 
 
-def outputs(ens):
-    es = ens.state
-    return (es.pH, es.chlorine, es.temperature, es.time, es.flow_rate, es.status) + ens.sensor_readings() + ens.input_image() + \
-        (ens.boundary(), ens.control_state().block())
-
-
-def run(variant, download=False):
-    ens = wt.ReactorEnsemble(cols, n_zones=n)
-    ens.set_boundary(bc)
-    ens.enable_sensors(seed=1)
-    ens.enable_plant_io()
-    ens.set_schedule(0, 1)
+def run(variant, rep=0):
+    download = rep == REPEATS - 1 and variant in ("one", "eight")          # the series once, at the end
+    ens = plant(cols, bc, n)
     ens.enable_control(chlorine, acid)
     if variant != "none":
         ens.set_trends(*{"off": off, "one": one, "eight": eight}[variant], capacity=CAPACITY)
     ens.step(DT, n_steps=WARMUP, download=False)
     if variant != "none":
         ens.reset_trends()
-    ens.synchronize()
-    t0 = time.perf_counter()
-    ens.step(DT, n_steps=K, download=False)
-    ens.synchronize()
-    t_step = time.perf_counter() - t0
+    _, t_step = timed_step(ens, DT, K)
     data, t_data = None, 0.0
     if download:
         t0 = time.perf_counter()
         data = ens.trend_data()
         t_data = time.perf_counter() - t0
-    out = outputs(ens)
+    out = outputs(ens, "sensor_readings", "input_image", "boundary", "control_state")
     ens.close()
     return t_step, t_data, out, data
 
 
-run("none")                                      # module load, first launches
 VARIANTS, REPEATS = ("none", "off", "one", "eight"), 9
-times, downloads, outs, data = {v: [] for v in VARIANTS}, {}, {}, {}
-for rep in range(REPEATS):
-    for i in range(len(VARIANTS)):
-        v = VARIANTS[(i + rep) % len(VARIANTS)]
-        t, t_data, outs[v], d = run(v, download=rep == REPEATS - 1 and v in ("one", "eight"))      # the series once, at the end
-        times[v].append(t)
-        if d is not None:
-            data[v], downloads[v] = d, t_data
-med = {v: float(np.median(times[v])) for v in VARIANTS}
-same = lambda a, b: all(np.array_equal(x, y, equal_nan=True) for x, y in zip(a, b))
-plant_equal = all(same(outs["none"], outs[v]) for v in VARIANTS[1:])
+run("none")                                      # module load, first launches
+times, med, last = rotate(VARIANTS, REPEATS, run)
+downloads, data = {v: last[v][1] for v in ("one", "eight")}, {v: last[v][3] for v in ("one", "eight")}
+plant_equal = all(same(last["none"][2], last[v][2]) for v in VARIANTS[1:])
 series_equal = same((data["one"].time[0], data["one"].value[0]), (data["eight"].time[0], data["eight"].value[0]))
 held = data["eight"].count
 print(json.dumps({"N": N, "n": n, "steps": K, "warmup": WARMUP, "capacity": CAPACITY, "repeats": REPEATS, "none_s": round(med["none"], 4),
