@@ -38,7 +38,7 @@ class SolverStats(C.Structure):
 
 # what libwtphys.so is built from: wtphys.hip and exactly the headers it includes
 # (tests/test_host_api.py::test_build_staleness_list_matches_the_includes)
-BUILD_SOURCES = ("wtphys.hip", "wt_device.hpp", "wt_sensors.hpp", "wt_plc.hpp", "wt_ctl.hpp", "wt_inj.hpp", "wt_alm.hpp", "wt_det.hpp", "wt_trd.hpp", "wt_act.hpp", "wt_dst.hpp", "wt_scr.hpp", "wt_diag.hpp", "wt_place.hpp")
+BUILD_SOURCES = ("wtphys.hip", "wt_device.hpp", "wt_tables.hpp", "wt_args.hpp", "wt_lanes.hpp", "wt_rhs.hpp", "wt_pcr.hpp", "wt_numjac.hpp", "wt_queue.hpp", "wt_step.hpp", "wt_sensors.hpp", "wt_plc.hpp", "wt_ctl.hpp", "wt_inj.hpp", "wt_alm.hpp", "wt_det.hpp", "wt_trd.hpp", "wt_act.hpp", "wt_dst.hpp", "wt_scr.hpp", "wt_diag.hpp", "wt_place.hpp")
 
 
 def build(force: bool = False, verbose: bool = False) -> str:

@@ -218,7 +218,7 @@ def transport_columns(cfg: Dict[str, np.ndarray], n_zones: int) -> Dict[str, np.
 def exchange_matrix(k_exchange_per_s: float, q_per_v: float, n_zones: int) -> np.ndarray:
     """The constant inter-zone exchange operator [1/s] (transport.py:256-336): nearest-neighbour exchange with a
     zero row sum, and the outflow sink on the top zone.  The kernel never forms it: it is a three-point stencil
-    (csrc/wt_device.hpp, mix3)."""
+    (csrc/wt_rhs.hpp, mix3)."""
     K = k_exchange_per_s * (np.eye(n_zones, k=1) + np.eye(n_zones, k=-1))
     K -= np.diag(K.sum(axis=1))
     K[-1, -1] -= q_per_v

@@ -72,7 +72,7 @@ class TemperatureDependentKinetics:
         return _plain(params.arrhenius(temp_c, law.k_ref, law.E_a, law.T_ref))
 
     def chlorine_decay_rate(self, temp_c):
-        """Per-zone k(T) of the step (csrc/wt_device.hpp: prop_T_n)."""
+        """Per-zone k(T) of the step (csrc/wt_rhs.hpp: prop_T_n)."""
         law = self.CHLORINE_DECAY
         return _plain(params.arrhenius(temp_c, law.k_ref, law.E_a, law.T_ref))
 
@@ -172,7 +172,7 @@ class StratificationParameters:
 
 class SpatialModel:
     """Density profile and stratification switch of one water column on the host, for diagnostics; inside ``step()``
-    the same relations run per zone per evaluation in the kernel (k_above in csrc/wt_device.hpp).  Brunt-Vaisala
+    the same relations run per zone per evaluation in the kernel (k_above in csrc/wt_rhs.hpp).  Brunt-Vaisala
     frequency, jet penetration and dead-zone listing are not provided."""
 
     G_GRAVITY = params.G_GRAVITY

@@ -9,7 +9,7 @@
 //                          apply_boundary_conditions :255-271, ModbusDecoder.registers_to_float32 protocols.py:155-177
 //
 // Both are byte movers over a few dozen bytes per reactor; they run inside the physics kernel
-// (wt_device.hpp), right behind the fused sensor suite of an outer step that is a PLC scan: one lane
+// (run_item, wt_step.hpp), right behind the fused sensor suite of an outer step that is a PLC scan: one lane
 // per reactor of the wavefront takes the seven readings from LDS, publishes the image and decodes the
 // holding registers; the new setpoints go back through LDS to the lanes that integrate the reactor.
 // Image layout (array of structures: a Modbus server answers "registers a..b of unit r" from one

@@ -13,7 +13,7 @@
 //   FlowSensor.read            sensors/flow_sensor.py:125-219     (magnetic)
 //   TemperatureSensor.read     sensors/temperature_sensor.py:110-171 (RTD Pt100)
 //
-// Mapping: the suite runs INSIDE the physics kernel (wt_device.hpp) at the end of every outer step, on the
+// Mapping: the suite runs INSIDE the physics kernel (run_item, wt_step.hpp) at the end of every outer step, on the
 // lanes of the wavefront that has just integrated the reactors: the seven taps the sensors look at (pH, Cl, T
 // of zones 0 and n-1, flow) go from the physics lanes' registers through a few hundred bytes of LDS to the
 // sensor lanes -- no tap buffer in HBM, no second kernel.  The suite splits into five groups that do not

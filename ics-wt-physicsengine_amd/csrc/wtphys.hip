@@ -58,7 +58,7 @@ struct wt_ensemble {
     int32_t *perm = nullptr, *cost = nullptr, *place_hist = nullptr;
     int placement = WT_PLACE_ADAPTIVE;
     int64_t cost_steps = 0;       // outer steps the cost history covers
-    // device-side work queue of the default schedule (wt_device.hpp): control words, FIFO slots, next step per group
+    // device-side work queue of the default schedule (wt_queue.hpp): control words, FIFO slots, next step per group
     int32_t *q_ctrl = nullptr; unsigned long long *q_slots = nullptr; int32_t *q_next = nullptr;
     int q_cap = 0, q_workers = 0;
     int64_t n_groups = 0;

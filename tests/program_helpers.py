@@ -249,7 +249,7 @@ class HostScan:
 
     def scan(self, v, f, cmd=None, stepped=None, tags=None):
         """One PLC scan at loop time ``lt`` in the device's order (the blocks under ``if (plc_on)`` of ``run_item`` in
-        csrc/wt_device.hpp):
+        csrc/wt_step.hpp):
           inject          the injection's sensor slots tamper the readings ``v`` / ``f`` (7, N),
           pack            which the input image then packs;
           apply commands  the decoded commands ``cmd`` (3, N) go through the injection's command slots,

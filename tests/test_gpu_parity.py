@@ -233,7 +233,7 @@ def test_placement_changes_no_bit(gpu, wt, n):
 @pytest.mark.parametrize("n", [5, 8, 12, 20, 40])
 def test_solve_fast_paths_change_no_bit(gpu, wt, monkeypatch, n):
     """A wavefront none of whose Jacobians couples a row to a neighbour's temperature skips those terms in every solve,
-    and at the row-straddling zone counts solves the T and the pH system in lock step (wt_device.hpp: jac_t_dense,
+    and at the row-straddling zone counts solves the T and the pH system in lock step (wt_pcr.hpp: jac_t_dense,
     pcr_rc_pair).  Which path a reactor takes depends on the other reactors of its wavefront, so the paths must agree
     bit for bit: WT_DENSE_COUPLING sends every solve down the general path, and state, status and solver counters are
     those of the default run."""

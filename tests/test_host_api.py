@@ -367,6 +367,30 @@ def test_build_staleness_list_matches_the_includes():
     assert not [f for f in os.listdir(native.CSRC) if f.endswith((".hpp", ".hip")) and f not in seen], "dead source in csrc/"
 
 
+def test_every_header_compiles_when_included_alone(tmp_path):
+    """Each header in csrc/ names what it uses: a translation unit that includes it and nothing else passes the device
+    compiler's front end (nothing is instantiated, so no code is generated)."""
+    import importlib, shutil, subprocess
+    from concurrent.futures import ThreadPoolExecutor
+    native = importlib.import_module("ics-wt-physicsengine_amd.core._native")
+    if shutil.which("hipcc") is None:
+        pytest.skip("hipcc is not on the path")
+    headers = sorted(f for f in os.listdir(native.CSRC) if f.endswith(".hpp"))
+    assert set(headers) == {f for f in native.BUILD_SOURCES if f.endswith(".hpp")}
+
+    def alone(h):
+        unit = tmp_path / (h[:-4] + "_alone.hip")
+        unit.write_text(f'#include "{h}"\n')
+        p = subprocess.run(["hipcc", "--offload-arch=gfx950", "-std=c++17", "--cuda-device-only", "-fsyntax-only", "-x", "hip",
+                            "-I", native.CSRC, str(unit)], capture_output=True, text=True)
+        return h, p.returncode, p.stderr[-2000:]
+
+    # one compiler call per header, four at a time (one after the other they take longer than any other CPU test)
+    with ThreadPoolExecutor(4) as pool:
+        failed = {h: err for h, rc, err in pool.map(alone, headers) if rc != 0}
+    assert not failed, failed
+
+
 def test_step_kernels_fit_the_register_file_and_four_wavefronts_per_cu(tmp_path):
     """Code-object metadata of the built library (what the loader sees): every step kernel up to 32 zones (LV <= 5,
     BASELINE config 3's n = 20 among them) runs without scratch memory, and its LDS leaves room for four wavefronts per

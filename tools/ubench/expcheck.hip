@@ -1,57 +1,24 @@
-// Own exp / exp10 (constants as operands, wt_device.hpp) against OCML's on the device, bit for bit.
-//   hipcc --offload-arch=gfx950 -O3 -o tools/scratch/expcheck tools/ubench/expcheck.hip && tools/scratch/expcheck
+// The shipped exp / exp10 (wt::exp_k / wt::exp10_k with the product's constant table, wt_tables.hpp) against OCML's on
+// the device, bit for bit.
+//   hipcc --offload-arch=gfx950 -O3 -I ics-wt-physicsengine_amd/csrc -o tools/scratch/expcheck tools/ubench/expcheck.hip && tools/scratch/expcheck
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdint>
 #include <vector>
 #include <cmath>
+#include "wt_tables.hpp"
 
-struct ExpTab { double c[10]; double log2e, ln2_hi, ln2_lo; double log2_10, lg2_hi, lg2_lo, ln10_hi, ln10_lo; double e_hi, e_lo, t_hi, t_lo; };
-
-__device__ __forceinline__ double poly(const ExpTab &k, double t, double dn)
-{
-    double p = k.c[0];
-#pragma unroll
-    for (int i = 1; i < 10; ++i) p = __builtin_fma(t, p, k.c[i]);
-    p = __builtin_fma(t, p, 1.0); p = __builtin_fma(t, p, 1.0);
-    return __builtin_amdgcn_ldexp(p, (int)dn);
-}
-__device__ __forceinline__ double my_exp(const ExpTab &k, double x)
-{
-    const double dn = __builtin_rint(x * k.log2e);
-    const double t = __builtin_fma(-dn, k.ln2_lo, __builtin_fma(-dn, k.ln2_hi, x));
-    double z = poly(k, t, dn);
-    z = (x > k.e_hi) ? __builtin_inf() : z;
-    z = (x < k.e_lo) ? 0.0 : z;
-    return z;
-}
-__device__ __forceinline__ double my_exp10(const ExpTab &k, double x)
-{
-    const double dn = __builtin_rint(x * k.log2_10);
-    const double u = __builtin_fma(-dn, k.lg2_lo, __builtin_fma(-dn, k.lg2_hi, x));
-    const double t = __builtin_fma(u, k.ln10_hi, u * k.ln10_lo);
-    double z = poly(k, t, dn);
-    z = (x > k.t_hi) ? __builtin_inf() : z;
-    z = (x < k.t_lo) ? 0.0 : z;
-    return z;
-}
-
-__global__ void chk(ExpTab k, const double *x, int n, int which, unsigned long long *mism, double *worst)
+__global__ void chk(const double *x, int n, int which, unsigned long long *mism, double *worst)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const double a = which ? my_exp10(k, x[i]) : my_exp(k, x[i]);
+    const double a = which ? wt::exp10_k(wt::kp_of(wt::default_ktab()), x[i]) : wt::exp_k(wt::kt_of(wt::default_ktab()), x[i]);
     const double b = which ? exp10(x[i]) : exp(x[i]);
     if (__double_as_longlong(a) != __double_as_longlong(b) && !(a != a && b != b)) { atomicAdd(mism, 1ull); worst[which] = x[i]; }
 }
 
 int main()
 {
-    ExpTab k = {{0x1.ade156a5dcb37p-26, 0x1.28af3fca7ab0cp-22, 0x1.71dee623fde64p-19, 0x1.a01997c89e6b0p-16, 0x1.a01a014761f6ep-13,
-                 0x1.6c16c1852b7b0p-10, 0x1.1111111122322p-7, 0x1.55555555502a1p-5, 0x1.5555555555511p-3, 0x1.000000000000bp-1},
-                0x1.71547652b82fep+0, 0x1.62e42fefa39efp-1, 0x1.abc9e3b39803fp-56,
-                0x1.a934f0979a371p+1, 0x1.34413509f79ffp-2, -0x1.9dc1da994fd21p-59, 0x1.26bb1bbb55516p+1, -0x1.f48ad494ea3e9p-53,
-                0x1.62e42fefa39efp+9, -0x1.74910d52d3051p+9, 0x1.34413509f79ffp+8, -0x1.434e6420f4374p+8};
     const int n = 1 << 22;
     std::vector<double> h(n);
     double *d; unsigned long long *m; double *w;
@@ -65,7 +32,7 @@ int main()
         h[0] = c.lo; h[1] = c.hi; h[2] = 0.0; h[3] = -0.0; h[4] = NAN; h[5] = INFINITY; h[6] = -INFINITY; h[7] = 1e300; h[8] = -1e300;
         hipMemcpy(d, h.data(), n * sizeof(double), hipMemcpyHostToDevice);
         hipMemset(m, 0, 8);
-        hipLaunchKernelGGL(chk, dim3(n / 256), dim3(256), 0, 0, k, d, n, c.which, m, w);
+        hipLaunchKernelGGL(chk, dim3(n / 256), dim3(256), 0, 0, d, n, c.which, m, w);
         unsigned long long mm; double ww[2];
         hipMemcpy(&mm, m, 8, hipMemcpyDeviceToHost); hipMemcpy(ww, w, 16, hipMemcpyDeviceToHost);
         printf("%-42s %d samples: %llu mismatches vs OCML%s\n", c.name, n, mm, mm ? "" : " (bit-identical)");
