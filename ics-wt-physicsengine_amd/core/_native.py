@@ -38,7 +38,7 @@ class SolverStats(C.Structure):
 
 # what libwtphys.so is built from: wtphys.hip and exactly the headers it includes
 # (tests/test_host_api.py::test_build_staleness_list_matches_the_includes)
-BUILD_SOURCES = ("wtphys.hip", "wt_device.hpp", "wt_tables.hpp", "wt_args.hpp", "wt_lanes.hpp", "wt_rhs.hpp", "wt_pcr.hpp", "wt_numjac.hpp", "wt_queue.hpp", "wt_step.hpp", "wt_sensors.hpp", "wt_plc.hpp", "wt_ctl.hpp", "wt_inj.hpp", "wt_alm.hpp", "wt_det.hpp", "wt_trd.hpp", "wt_act.hpp", "wt_dst.hpp", "wt_scr.hpp", "wt_diag.hpp", "wt_place.hpp")
+BUILD_SOURCES = ("wtphys.hip", "wt_device.hpp", "wt_tables.hpp", "wt_args.hpp", "wt_lanes.hpp", "wt_rhs.hpp", "wt_pcr.hpp", "wt_numjac.hpp", "wt_queue.hpp", "wt_step.hpp", "wt_sensors.hpp", "wt_plc.hpp", "wt_ctl.hpp", "wt_inj.hpp", "wt_alm.hpp", "wt_det.hpp", "wt_trd.hpp", "wt_act.hpp", "wt_dst.hpp", "wt_scr.hpp", "wt_trn.hpp", "wt_diag.hpp", "wt_place.hpp")
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
@@ -161,6 +161,10 @@ def lib():
     L.wt_ensemble_trend_reset.argtypes = [vp]
     L.wt_ensemble_trend_clear.argtypes = [vp]
     L.wt_program_check.argtypes = [C.c_int, dp, C.c_int64]
+    L.wt_ensemble_train_set.argtypes = [vp, C.c_int, dp]
+    L.wt_ensemble_train_get.argtypes = [vp, ip, ip, dp]
+    L.wt_ensemble_train_clear.argtypes = [vp]
+    L.wt_train_check.argtypes = [C.c_int, C.c_int, C.c_int64, dp]
     L.wt_ensemble_diagnostics.argtypes = [vp, dp]
     L.wt_ensemble_wave_diag.argtypes = [vp, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int64)]
     L.wt_ensemble_size.argtypes = [vp]
@@ -185,7 +189,8 @@ def lib():
                  "wt_ensemble_score_curve", "wt_ensemble_score_reset", "wt_ensemble_score_clear", "wt_ensemble_detect_set",
                  "wt_ensemble_detect_get", "wt_ensemble_detect_reset", "wt_ensemble_detect_clear", "wt_ensemble_trend_set",
                  "wt_ensemble_trend_get", "wt_ensemble_trend_data", "wt_ensemble_trend_reset", "wt_ensemble_trend_clear",
-                 "wt_program_check"):
+                 "wt_program_check", "wt_ensemble_train_set", "wt_ensemble_train_get", "wt_ensemble_train_clear",
+                 "wt_train_check"):
         getattr(L, name).restype = C.c_int
     if L.wt_abi_version() != 1:
         raise ImportError("libwtphys.so ABI version mismatch; rebuild it")

@@ -18,7 +18,7 @@ from typing import Dict, Iterable, List, Optional, Sequence, Union
 
 import numpy as np
 
-from . import _native, _program, actuator, alarm, control, detect, disturb, inject, params, score, trend
+from . import _native, _program, actuator, alarm, control, detect, disturb, inject, params, score, train, trend
 
 logger = logging.getLogger(__name__)
 
@@ -275,6 +275,7 @@ class ReactorEnsemble:
         self._disturb_history = -1              # capacity of the disturbance program's history; -1: no program
         self._score_curve = None                # (capacity, bins, edges) of the score program's curve; None: no program
         self._detect_labels: Optional[np.ndarray] = None    # the label block of the detector program; None: no program
+        self._trains = False                    # a train program is set
         self._trend_capacity = 0                # samples per slot and reactor of the trend program's store; 0: no program
         self._control_params: Optional[np.ndarray] = None   # the last block enable_control / retune_control sent
 
@@ -318,6 +319,8 @@ class ReactorEnsemble:
                 raise ValueError("give either boundaries or boundary_schedule, not both")
             if self._disturb_history >= 0:
                 raise ValueError("a boundary schedule cannot be combined with a disturbance program (clear_disturbances)")
+            if self._trains:
+                raise ValueError("a boundary schedule cannot be combined with a train program (clear_trains)")
             blk = boundary_schedule_block(boundary_schedule, int(n_steps), self.n_reactors)
             try:
                 _native.check(_native.lib().wt_ensemble_step_scheduled(self._h, float(dt), int(n_steps), 1 if fused else 0,
@@ -340,8 +343,9 @@ class ReactorEnsemble:
             if e.code == _native.WT_E_ARG:
                 raise ValueError(e.message) from None
             raise
-        if getattr(self, "_plant_io", False) or self._disturb_history >= 0:
-            # every PLC scan rewrites the device's boundary rows 0 / 4 / 6, a disturbance program its targeted rows
+        if getattr(self, "_plant_io", False) or self._disturb_history >= 0 or self._trains:
+            # every PLC scan rewrites the device's boundary rows 0 / 4 / 6, a disturbance program its targeted rows, a
+            # train program the linked reactors' rows 1 / 2 / 3
             self._device_boundary_moved = True
         return self.state if download else None
 
@@ -742,6 +746,38 @@ class ReactorEnsemble:
         self._device_boundary_moved = True
 
     # -- anomaly detector programs at every PLC scan, on the device (wt_det.hpp)
+    # -- the train program: stages feed their downstream after every outer step, on the device (wt_trn.hpp)
+    def set_trains(self, length: int, linked=True, rows=train.ALL_ROWS) -> None:
+        """Read the ensemble as ``N / length`` treatment trains of ``length`` stages: reactor r is stage ``r % length``
+        of train ``r // length``.  After every outer step its upstream took, a linked stage gets the upstream's outlet
+        zone in its boundary rows inlet_pH / inlet_chlorine / inlet_temperature (``rows``: names, or masks 1 | 2 | 4),
+        the boundary of its next outer step -- the bits of a host loop of one-step calls that copies outlets into
+        ``set_boundary`` between them.  ``linked`` and ``rows`` take a scalar or an (N,) array; first stages are never
+        linked.  Flows are not carried.  The stages of a train share a wavefront: ``2 <= length <= 64 // n_zones`` and
+        ``N % length == 0``.  A shard of a sharded ensemble must hold whole trains (``shard_bounds`` does not know
+        about trains: choose sizes that are multiples of ``length``).  Replaces any program; :meth:`clear_trains`."""
+        blk = train.train_block(self.n_reactors, self.n_zones, length, linked, rows)
+        self._program_call(_native.lib().wt_ensemble_train_set, int(length), _native.dptr(blk))
+        self._trains = True
+        self._device_boundary_moved = True      # set feeds every link from the current state
+        self._diag_on = False                   # the wave diagnostics of the old shape are gone
+
+    def train_state(self) -> "train.TrainState":
+        """Feeds counted per reactor, the upstream's time at the last one, the train length and the reactors per
+        wavefront in force (one synchronisation)."""
+        st = np.empty((train.NTRS, self.n_reactors), dtype=np.float64)
+        length, per = C.c_int(0), C.c_int(0)
+        self._program_call(_native.lib().wt_ensemble_train_get, C.byref(length), C.byref(per), _native.dptr(st))
+        return train.TrainState.from_block(st, length.value, per.value)
+
+    def clear_trains(self) -> None:
+        """Stop the train program: the linked rows go back to what ``set_boundary`` last gave, the handle to the
+        wavefront packing it had before."""
+        self._program_call(_native.lib().wt_ensemble_train_clear)
+        self._trains = False
+        self._device_boundary_moved = True
+        self._diag_on = False
+
     def set_detectors(self, *detectors: "detect.Detector", attack=None) -> None:
         """Run a detector program of up to four :class:`Detector` slots at every PLC scan, inside the step call, last in
         the scan: each slot keeps a CUSUM, EWMA or flat-line statistic of one reading's residual, raises its alarm

@@ -634,16 +634,25 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
                            s->scr.step0 + s->first_step + step0 + k);
           }
         }
-        // ================= the disturbance program (wave-uniform flag): the rows of the next outer step.  Before the
-        // plant-I/O section, whose scan reload then reads these rows from the boundary block while the command path
-        // writes rows 0 / 4 / 6 -- neither overwrites the other's rows.
+        // ================= the disturbance program and the train program (wave-uniform flags): the rows of the next
+        // outer step.  Before the plant-I/O section, whose scan reload then reads these rows from the boundary block
+        // while the command path writes rows 0 / 4 / 6 -- neither overwrites the other's rows.  A disturbance slot never
+        // targets a row the train feeds (the set calls refuse it), so the two write different cells; one barrier and one
+        // reload serve both.
         if constexpr (prog_in_item(LV)) {
-          if (WT_RARE(fresh(pa)->dst.on)) {
-            ArgPtr d = fresh(pa);            // ---- section: disturbance program
+          const int dst_on = fresh(pa)->dst.on, trn_on = fresh(pa)->trn.on;
+          if (WT_RARE((dst_on | trn_on) != 0)) {
+            ArgPtr d = fresh(pa);            // ---- section: disturbance program, train program
             const bool live = present && stepped && !(st & ST_T_RANGE_POST);   // the sensor section's test
-            if (live && L.z == 0) wtd::evaluate(d->dst, r, t_out, d->bc, d->N, ExpK());
+            bool reload = false;
+            if (dst_on) {
+                if (live && L.z == 0) wtd::evaluate(d->dst, r, t_out, d->bc, d->N, ExpK());
+                reload = live;
+            }
+            // a stage's outlet lane stores its state into the next stage's rows 1..3; fed: this lane's reactor got rows
+            if (trn_on) reload = wtr::feed(d->trn, live, !L.has_hi, seg, n_zones, r, t_out, y0, d->bc, d->N) || reload;
             __syncthreads();                 // the rows are in memory for every lane of the reactor
-            if (live) {
+            if (reload) {
                 RK k1; load_reactor(d->par, d->bc, d->N, r, n_zones, k1); mask_reactor_for_lane(L, k1);
                 park_reactor(ks, k1);
                 f_valid = false;

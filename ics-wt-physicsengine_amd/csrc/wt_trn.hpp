@@ -1,0 +1,85 @@
+// wt_trn.hpp -- gfx950 device code of the train program (wt_ensemble_train_*): reactors coupled into treatment trains.
+// An ensemble of N reactors is read as N / length trains of `length` stages; reactor r is stage r % length of train
+// r / length.  After every outer step its upstream took, a linked stage gets the upstream's outlet zone (zone n - 1:
+// pH, Cl, T) in rows 1, 2, 3 of its boundary block -- the boundary of its next outer step (zero-order hold).  Flows
+// are not carried: row 0 belongs to the command path or the master, every tank keeps its own inlet flow.
+//
+//   feed      runs in the end-of-outer-step section of run_item that the disturbance program shares, before the
+//             sensor and plant-I/O section.  The host deals whole trains into consecutive slots of one
+//             wavefront-group (h->R is a multiple of length, wt_place.hpp deals units of length), so the upstream of
+//             the reactor in segment s sits in segment s - 1 of the same wavefront and has just ended the same outer
+//             step: the upstream's outlet lane stores its own state into the downstream's rows (vector stores, no
+//             LDS), and the downstream's lanes learn from one ballot whether they were fed.
+//   host_op   one thread per reactor: FEED writes every link from the state in memory (train_set, set_boundary and
+//             set_state with a program set), RESTORE writes the base back into the linked rows (clear, a set over a
+//             program).
+//
+// Device layout (indexed by reactor: placement changes nothing):
+//   lk   [N] int32        0: not linked; otherwise LINKED | rows mask (1 pH, 2 Cl, 4 T)
+//   st   [N][NTRS] fp64   n_fed (feeds written by the step kernel), t_last (the upstream's time at the last of them)
+//   base [3][N] fp64      rows 1..3 as wt_ensemble_set_boundary last gave them
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace wtr {
+
+constexpr int NTR = 2, NTRS = 2, FED_ROWS = 3, LINKED = 8;
+enum { P_LINK = 0, P_ROWS };
+enum { S_N_FED = 0, S_T_LAST };
+
+struct TrnArgs {
+    int on;                  // 0: no program (the step kernel's section reads this flag only)
+    int length;              // stages per train
+    const int32_t *lk;       // [N]
+    double *st;              // [N][NTRS]
+    double *base;            // [FED_ROWS][N]
+};
+
+// the rows of reactor d that word w names, from (pH, Cl, T)
+__device__ __forceinline__ void store_rows(int w, double *bc, int64_t N, int64_t d, double pH, double Cl, double T)
+{
+    if (w & 1) bc[1 * N + d] = pH;
+    if (w & 2) bc[2 * N + d] = Cl;
+    if (w & 4) bc[3 * N + d] = T;
+}
+
+// One outer step's feeds of a wavefront; every lane calls it.  live: this lane's reactor r stepped and its state
+// stands (the sensor section's test); outlet: this lane holds zone n - 1; y: the lane's state after the step; t: the
+// reactor's time after it.  Returns whether this lane's reactor was fed (its lanes then reload the reactor constants).
+template <class A>
+__device__ __forceinline__ bool feed(const A &a, bool live, bool outlet, int seg, int n_zones, int64_t r, double t,
+                                     const double y[3], double *bc, int64_t N)
+{
+    const int stage = (int)((uint32_t)r % (uint32_t)a.length);   // (reactor indices fit 31 bits: perm is int32)
+    if (live && outlet && stage != a.length - 1) {
+        const int64_t d = r + 1;                          // segment seg + 1 of this wavefront
+        const int w = a.lk[d];
+        if (w) {
+            store_rows(w, bc, N, d, y[0], y[1], y[2]);
+            double *s = a.st + d * NTRS;
+            s[S_N_FED] = s[S_N_FED] + 1.0; s[S_T_LAST] = t;
+        }
+    }
+    const unsigned long long m = __ballot(live);
+    const int up = seg > 0 ? (seg - 1) * n_zones : 0;     // first lane of the upstream's segment
+    return stage != 0 && ((m >> up) & 1ull) != 0ull && a.lk[r] != 0;
+}
+
+enum { OP_FEED = 0, OP_RESTORE };
+struct HostOpArgs { TrnArgs t; double *bc; const double *pH, *Cl, *T; int64_t N; int n; int op; };
+__global__ __launch_bounds__(256) void host_op_kernel(const HostOpArgs a)
+{
+    const int64_t d = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (d >= a.N) return;
+    const int w = a.t.lk[d];
+    if (!w) return;                                       // (a first stage is never linked)
+    if (a.op == OP_FEED) {
+        const int64_t o = (d - 1) * a.n + (a.n - 1);      // the upstream's outlet zone
+        store_rows(w, a.bc, a.N, d, a.pH[o], a.Cl[o], a.T[o]);
+    } else {
+        store_rows(w, a.bc, a.N, d, a.t.base[d], a.t.base[a.N + d], a.t.base[2 * a.N + d]);
+    }
+}
+
+} // namespace wtr

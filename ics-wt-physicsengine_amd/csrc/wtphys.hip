@@ -102,6 +102,11 @@ struct wt_ensemble {
     int64_t scr_steps = 0;
     wtk::DetArgs det = {};
     wtt::TrdArgs trd = {};
+    // The train program (wt_trn.hpp; not one of k_programs: it changes the handle's shape).  trn_lk: host copy of trn.lk
+    // (the disturbance conflict check reads it).  R0: reactors per wavefront as create chose them, what clear restores.
+    wtr::TrnArgs trn = {};
+    std::vector<int32_t> trn_lk;
+    int R0 = 0;
     // optional per-launch HIP-event timing (bench.py roofline accounting)
     bool time_launches = false;
     std::vector<hipEvent_t> lt_pool;   // start/stop pairs
@@ -138,7 +143,7 @@ wt::StepArgs make_args(const wt_ensemble *h, double dt, int n_steps, int first_s
     a.trace = h->trace; a.trace_cap = h->trace_cap;
     a.kt = wt::default_ktab(); a.rt = wt::default_rtab();
     a.kt.dense_bias = h->knob_dense ? 1.0 : 0.0;
-    a.sens = h->sens; a.ctl = h->ctl; a.inj = h->inj; a.alm = h->alm; a.act = h->act; a.dst = h->dst; a.scr = h->scr; a.det = h->det; a.trd = h->trd;
+    a.sens = h->sens; a.ctl = h->ctl; a.inj = h->inj; a.alm = h->alm; a.act = h->act; a.dst = h->dst; a.scr = h->scr; a.det = h->det; a.trd = h->trd; a.trn = h->trn;
     // a full curve takes no more entries: the launches then carry no curve pointer at all
     const bool curve = h->scr.counts && h->scr_steps < h->scr.curve_cap;
     if (!curve) a.scr.counts = nullptr;
@@ -196,9 +201,14 @@ ArrayGroup core_arrays(wt_ensemble *h)
                                 {(void **)&h->bad_T, sizeof(double) * N}, {(void **)&h->perm, sizeof(int32_t) * N},
                                 {(void **)&h->cost, sizeof(int32_t) * N},
                                 {(void **)&h->place_hist, sizeof(int32_t) * wtpl::BINS * ((N + wtpl::CHUNK - 1) / wtpl::CHUNK)},
-                                {(void **)&h->q_ctrl, sizeof(int32_t) * wt::Q_WORDS},
-                                {(void **)&h->q_slots, sizeof(unsigned long long) * (size_t)h->q_cap},
-                                {(void **)&h->q_next, sizeof(int32_t) * (size_t)h->n_groups}}};
+                                {(void **)&h->q_ctrl, sizeof(int32_t) * wt::Q_WORDS}}};
+}
+
+// the work queue's arrays that are sized by the group count: a train program changes it (reshape)
+ArrayGroup queue_arrays(wt_ensemble *h)
+{
+    return {"queue", nullptr, {{(void **)&h->q_slots, sizeof(unsigned long long) * (size_t)h->q_cap},
+                               {(void **)&h->q_next, sizeof(int32_t) * (size_t)h->n_groups}}};
 }
 
 // the history arrays only for hist_cap > 0
@@ -306,6 +316,15 @@ ArrayGroup detect_arrays(wt_ensemble *h)
                                    {(void **)&h->det.tp, sizeof(double) * N}}};
 }
 
+ArrayGroup train_arrays(wt_ensemble *h)
+{
+    const size_t N = (size_t)h->N;
+    return {"train", &h->trn.on, {{(void **)&h->trn.lk, sizeof(int32_t) * N},
+                                  {(void **)&h->trn.st, sizeof(double) * wtr::NTRS * N},
+                                  {(void **)&h->trn.base, sizeof(double) * wtr::FED_ROWS * N}},
+            [h] { h->trn.length = 0; h->trn_lk.clear(); }};
+}
+
 ArrayGroup trend_arrays(wt_ensemble *h)
 {
     const size_t N = (size_t)h->N;
@@ -313,6 +332,20 @@ ArrayGroup trend_arrays(wt_ensemble *h)
                                   {(void **)&h->trd.st, sizeof(double) * wtt::ST_DOUBLES * N},
                                   {(void **)&h->trd.store, sizeof(double2) * wtt::SLOTS * (size_t)h->trd.cap * N}},
             [h] { h->trd.cap = 0; }};
+}
+
+// Units (reactors, or trains under a train program) per wavefront, at most `most`.  A small ensemble is spread over all
+// SIMDs rather than packed into full wavefronts: a wavefront costs what its slowest reactor costs, so fewer per
+// wavefront is faster as long as every wavefront still finds a SIMD (about 4 per CU).  Results do not depend on it.
+int units_per_wavefront(int device, int64_t units, int most)
+{
+    int cus = 256; hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
+    const int64_t slots = (int64_t)cus * 4;
+    int64_t r = (units + slots - 1) / slots;
+    if (const char *e = getenv("WT_FULL_WAVES")) if (atoi(e) != 0) r = most;      // tuning knob (tools/)
+    if (r < 1) r = 1;
+    return r < most ? (int)r : most;
 }
 
 bool row_mode(int n) { return n == 2 || n == 4 || n == 8 || n == 16; }
@@ -469,6 +502,15 @@ int disturb_op(wt_ensemble *h, int op)
     return WT_OK;
 }
 
+// The train program's host operations (wtr::host_op_kernel) on the handle's stream, not synchronised.
+int train_op(wt_ensemble *h, int op)
+{
+    const wtr::HostOpArgs a{h->trn, h->bc, h->pH, h->Cl, h->T, h->N, h->n, op};
+    hipLaunchKernelGGL(wtr::host_op_kernel, dim3((unsigned)((h->N + 255) / 256)), dim3(256), 0, h->stream, a);
+    HIP_TRY(hipGetLastError());
+    return WT_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -499,24 +541,15 @@ int wt_ensemble_create(int64_t n_reactors, int n_zones, int device, const double
     if (device < 0 || device >= ndev) return fail(WT_E_ARG, "bad device index");
     HIP_TRY(hipSetDevice(device));
     wt_ensemble *h = new wt_ensemble();
-    h->N = n_reactors; h->n = n_zones; h->R = 64 / n_zones; h->device = device;
-    {   // A small ensemble is spread over all SIMDs rather than packed into full wavefronts: a wavefront costs what
-        // its slowest reactor costs, so fewer reactors per wavefront is faster as long as every wavefront still
-        // finds a SIMD (about 4 per CU).  Results do not depend on it (reactors never interact).
-        int cus = 256; hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
-        const int64_t slots = (int64_t)cus * 4;
-        int64_t r = (n_reactors + slots - 1) / slots;
-        if (const char *e = getenv("WT_FULL_WAVES")) if (atoi(e) != 0) r = h->R;      // tuning knob (tools/)
-        if (r < 1) r = 1;
-        if (r < h->R) h->R = (int)r;
-    }
+    h->N = n_reactors; h->n = n_zones; h->device = device;
+    h->R = h->R0 = units_per_wavefront(device, n_reactors, 64 / n_zones);
     const size_t N = (size_t)n_reactors, nz = (size_t)n_zones;
     auto cleanup = [&]() { wt_ensemble_destroy(h); };
     h->n_groups = (n_reactors + h->R - 1) / h->R;
     if (h->n_groups > 0x3fffffff) { cleanup(); return fail(WT_E_ARG, "too many reactors for one ensemble"); }
     h->q_cap = (int)(2 * h->n_groups + 64);
     if (int rc = allocate(core_arrays(h))) { cleanup(); return rc; }
+    if (int rc = allocate(queue_arrays(h))) { cleanup(); return rc; }
     {   // small ensembles (the drop-in's N = 1 above all) are downloaded as one packed image through pinned memory
         const size_t image = sizeof(double) * (6 * N * nz + 2 * N) + sizeof(uint32_t) * (N + 1);
         if (image <= WT_SNAPSHOT_PACK_MAX) {
@@ -585,6 +618,7 @@ int wt_ensemble_set_state(wt_ensemble *h, const double *pH, const double *Cl, co
     hipLaunchKernelGGL(wt::derived_placeholder_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, h->stream, pa);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemsetAsync(h->status, 0, sizeof(uint32_t) * h->N, h->stream));
+    if (h->trn.on) if (int rc = train_op(h, wtr::OP_FEED)) return rc;   // a train program: every link from the new state
     HIP_TRY(hipStreamSynchronize(h->stream));   // the caller's buffers are free on return
     h->have_state = true;
     return WT_OK;
@@ -598,6 +632,10 @@ int wt_ensemble_set_boundary(wt_ensemble *h, const double *bc)
     if (h->dst.on) {   // a disturbance program: the new block is its base, the targeted rows are recomposed (no draw)
         HIP_TRY(hipMemcpyAsync(h->dst.base, h->bc, sizeof(double) * WT_NB * h->N, hipMemcpyDeviceToDevice, h->stream));
         if (int rc = disturb_op(h, wtd::OP_COMPOSE)) return rc;
+    }
+    if (h->trn.on) {   // a train program: rows 1..3 of the new block are its base, every link is fed from the current state
+        HIP_TRY(hipMemcpyAsync(h->trn.base, bc + h->N, sizeof(double) * wtr::FED_ROWS * h->N, hipMemcpyHostToDevice, h->stream));
+        if (int rc = train_op(h, wtr::OP_FEED)) return rc;
     }
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->have_bc = true;
@@ -628,8 +666,9 @@ int queue_steps(wt_ensemble *h, double dt, int n_steps, int fused, int first, in
         const int64_t min_steps = h->knob_place_min > 0 ? h->knob_place_min : WT_PLACE_MIN_STEPS;
         auto redeal = [&]() {
             if (h->placement != WT_PLACE_ADAPTIVE || h->cost_steps < min_steps) return;
-            const int blocks = (int)((h->N + wtpl::CHUNK - 1) / wtpl::CHUNK);
-            const wtpl::PlaceArgs pa{h->N, h->cost, (int)(h->cost_steps > 0x7fffffff ? 0x7fffffff : h->cost_steps), h->place_hist, h->perm};
+            const int unit = h->trn.on ? h->trn.length : 1;      // a train program: whole trains are dealt
+            const int blocks = (int)((h->N / unit + wtpl::CHUNK - 1) / wtpl::CHUNK);
+            const wtpl::PlaceArgs pa{h->N, h->cost, (int)(h->cost_steps > 0x7fffffff ? 0x7fffffff : h->cost_steps), h->place_hist, h->perm, unit};
             hipLaunchKernelGGL(wtpl::place_count_kernel, dim3(blocks), dim3(wtpl::BINS), 0, h->stream, pa);
             hipLaunchKernelGGL(wtpl::place_scan_kernel, dim3(1), dim3(wtpl::BINS), 0, h->stream, pa, blocks);
             hipLaunchKernelGGL(wtpl::place_scatter_kernel, dim3(blocks), dim3(wtpl::BINS), 0, h->stream, pa);
@@ -749,6 +788,7 @@ int wt_ensemble_step_scheduled(wt_ensemble *h, double dt, int n_steps, int fused
     if (!bc_schedule) return fail(WT_E_ARG, "bc_schedule is NULL");
     if (h->sens.plc_on) return fail(WT_E_STATE, "a boundary schedule cannot be combined with plant I/O (the command path owns the boundary)");
     if (h->dst.on) return fail(WT_E_STATE, "a boundary schedule cannot be combined with a disturbance program (its STEP and RAMP slots script events)");
+    if (h->trn.on) return fail(WT_E_STATE, "a boundary schedule cannot be combined with a train program (the run itself sets the linked rows)");
     if (!h->have_state) return fail(WT_E_STATE, "set_state must precede step");
     if (!(dt > 0)) return fail(WT_E_ARG, "`max_step` must be positive."); // scipy validate_max_step (reactor.py:480)
     if (n_steps < 0) return fail(WT_E_ARG, "n_steps must be >= 0");
@@ -1480,6 +1520,65 @@ uint16_t alarm_settle(const double *par, const double *st, double *rst)
     return (uint16_t)word;
 }
 
+// -- the train program (wt_trn.hpp): not one of k_programs, because setting it changes the handle's shape
+
+const char *k_train_not_set = "no train program is set (wt_ensemble_train_set)";
+const char *k_train_conflict = "a disturbance slot targets an inlet row (1, 2 or 3) that the train program feeds into that reactor";
+
+// some non-OFF slot of a [WT_DST_SLOTS][WT_ND][N] disturbance block targets a row that lk (wtr::TrnArgs::lk) feeds
+bool train_conflict(const int32_t *lk, const double *blk, int64_t N)
+{
+    for (int s = 0; s < wtd::SLOTS; ++s)
+        for (int64_t r = 0; r < N; ++r) {
+            const double row = blk[((int64_t)s * wtd::ND + wtd::D_ROW) * N + r];
+            if (blk[((int64_t)s * wtd::ND + wtd::D_KIND) * N + r] != (double)wtd::K_OFF && row >= 1.0 && row <= 3.0 &&
+                ((lk[r] >> ((int)row - 1)) & 1))
+                return true;
+        }
+    return false;
+}
+
+// The handle's shape for R reactors per wavefront: the group count and what is sized by it -- the queue's arrays, the
+// stream ranges of the default schedule, the workers.  The developer buffers of the old shape (wave diagnostics, item
+// trace) are released; their next call allocates them again.  The stream is idle.  A failure leaves the old shape.
+int reshape(wt_ensemble *h, int R)
+{
+    free_and_null(h->wave_diag); free_and_null(h->trace); h->trace_cap = 0;
+    if (R == h->R) return WT_OK;
+    const int64_t groups = (h->N + R - 1) / R;
+    if (groups > 0x3fffffff) return fail(WT_E_ARG, "too many reactors for one ensemble");
+    unsigned long long *slots = h->q_slots; int32_t *next = h->q_next;
+    const int old_R = h->R, old_cap = h->q_cap; const int64_t old_groups = h->n_groups;
+    h->q_slots = nullptr; h->q_next = nullptr;
+    h->R = R; h->n_groups = groups; h->q_cap = (int)(2 * groups + 64);
+    if (int rc = allocate(queue_arrays(h))) {
+        h->q_slots = slots; h->q_next = next; h->R = old_R; h->n_groups = old_groups; h->q_cap = old_cap;
+        return rc;
+    }
+    (void)hipFree(slots); (void)hipFree(next);
+    if (h->sched_mode == WT_SCHED_QUEUE) h->n_sub = default_streams(h->N, h->R);
+    h->q_workers = queue_workers(h);
+    return WT_OK;
+}
+
+// n_fed = 0, t_last = NaN, base = rows 1..3 of the boundary in force, reactor r in slot r with an empty cost history
+// (whole trains in consecutive slots), then every link fed from the current state
+int train_restart(wt_ensemble *h)
+{
+    const size_t N = (size_t)h->N;
+    std::vector<double> st(N * wtr::NTRS, 0.0);
+    for (size_t r = 0; r < N; ++r) st[r * wtr::NTRS + wtr::S_T_LAST] = NAN;
+    if (int rc = upload(h, h->trn.st, st)) return rc;
+    HIP_TRY(hipMemcpyAsync((void *)h->trn.lk, h->trn_lk.data(), sizeof(int32_t) * N, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->trn.base, h->bc + N, sizeof(double) * wtr::FED_ROWS * N, hipMemcpyDeviceToDevice, h->stream));
+    hipLaunchKernelGGL(wtpl::iota_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, h->stream, h->perm, h->N);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemsetAsync(h->cost, 0, sizeof(int32_t) * N, h->stream));
+    h->cost_steps = 0;
+    if (int rc = train_op(h, wtr::OP_FEED)) return rc;
+    return sync_checked(h);                     // the host vector is freed on return
+}
+
 // before a disturbance program's arrays go (clear, a set over a program): the targeted rows back to the base
 int disturb_restore(wt_ensemble *h)
 {
@@ -1498,7 +1597,7 @@ int wt_ensemble_destroy(wt_ensemble *h)
     if (!h) return WT_OK;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (const auto arrays : {core_arrays, sensor_arrays, plant_io_arrays, record_arrays}) release(arrays(h));
+    for (const auto arrays : {core_arrays, queue_arrays, sensor_arrays, plant_io_arrays, record_arrays, train_arrays}) release(arrays(h));
     for (const Program &p : k_programs) release(p.arrays(h));
     free_and_null(h->trace); free_and_null(h->wave_diag); free_and_null(h->snap_dev); free_and_null(h->sched);
     free_and_null(h->diag_out);
@@ -1638,6 +1737,7 @@ int wt_ensemble_disturb_set(wt_ensemble *h, const double *params, uint64_t seed,
         __builtin_mul_overflow(hist, (int64_t)sizeof(double), &hist))
         return fail(WT_E_ARG, "history size overflows int64");
     if (int rc = wt_program_check(WT_PROG_DISTURB, params, h->N)) return rc;
+    if (h->trn.on && train_conflict(h->trn_lk.data(), params, h->N)) return fail(WT_E_STATE, k_train_conflict);
     if (int rc = disturb_restore(h)) return rc;
     if (int rc = stop_program(h, WT_PROG_DISTURB)) return rc;   // set replaces any program (and its capacity)
     h->dst.hist_cap = history_capacity;
@@ -1675,6 +1775,82 @@ int wt_ensemble_disturb_clear(wt_ensemble *h)
     if (!h) return fail(WT_E_ARG, "NULL handle");
     if (int rc = disturb_restore(h)) return rc;
     return stop_program(h, WT_PROG_DISTURB);
+}
+
+int wt_train_check(int length, int n_zones, int64_t n_reactors, const double *params)
+{
+    if (n_reactors < 1) return fail(WT_E_ARG, "n_reactors must be >= 1");
+    if (n_zones < 2 || n_zones > WT_MAX_ZONES) return fail(WT_E_ARG, "n_zones must be in 2..64");
+    if (length < 2 || length > 64 / n_zones)
+        return fail(WT_E_ARG, "length must be at least 2 and at most 64 / n_zones (the stages of a train share a wavefront)");
+    if (n_reactors % length != 0) return fail(WT_E_ARG, "n_reactors must be a multiple of length (an ensemble holds whole trains)");
+    if (!params) return WT_OK;                  // every stage after the first linked, rows 7
+    for (int64_t r = 0; r < n_reactors; ++r) {
+        const double link = params[WT_TR_LINK * n_reactors + r], rows = params[WT_TR_ROWS * n_reactors + r];
+        if (!(link == 0.0 || link == 1.0)) return fail(WT_E_ARG, "link must be 0 or 1");
+        if (link != 0.0 && r % length == 0) return fail(WT_E_ARG, "the first stage of a train has no upstream: its link must be 0");
+        if (!whole_in(rows, 0, 7)) return fail(WT_E_ARG, "rows must be an integer in 0..7 (1 pH, 2 chlorine, 4 temperature)");
+    }
+    return WT_OK;
+}
+
+int wt_ensemble_train_set(wt_ensemble *h, int length, const double *params)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    if (!h->have_state || !h->have_bc) return fail(WT_E_STATE, "set_state and set_boundary must precede train_set");
+    if (int rc = wt_train_check(length, h->n, h->N, params)) return rc;
+    const int64_t N = h->N;
+    std::vector<int32_t> lk((size_t)N);
+    for (int64_t r = 0; r < N; ++r) {
+        const bool linked = params ? params[WT_TR_LINK * N + r] == 1.0 : r % length != 0;
+        lk[(size_t)r] = linked ? (wtr::LINKED | (params ? (int)params[WT_TR_ROWS * N + r] : 7)) : 0;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still use the records and the old shape
+    if (h->dst.on) {                            // the other direction: wt_ensemble_disturb_set with a train program set
+        std::vector<double> rec((size_t)N * wtd::PAR_DOUBLES), blk(rec.size());
+        if (int rc = download(h, {{rec.data(), h->dst.par, sizeof(double) * rec.size()}})) return rc;
+        records_to_blocks(rec.data(), wtd::PAR_DOUBLES, wtd::SLOTS, wtd::ND, N, blk.data());
+        if (train_conflict(lk.data(), blk.data(), N)) return fail(WT_E_STATE, k_train_conflict);
+    }
+    if (h->trn.on) {                            // set replaces a program: its rows go back to its base first
+        if (int rc = train_op(h, wtr::OP_RESTORE)) return rc;
+        if (int rc = sync_checked(h)) return rc;
+    }
+    // whole trains per wavefront: the small-ensemble rule of wt_ensemble_create, counted in trains
+    const int k = units_per_wavefront(h->device, N / length, 64 / h->n / length);
+    if (int rc = reshape(h, length * k)) return rc;
+    const ArrayGroup g = train_arrays(h);
+    int rc = allocate(g);
+    if (rc == WT_OK) {
+        h->trn.length = length; h->trn_lk = lk;
+        rc = train_restart(h);
+    }
+    if (rc != WT_OK) { release(g); (void)reshape(h, h->R0); return rc; }
+    h->trn.on = 1;
+    return WT_OK;
+}
+
+int wt_ensemble_train_get(wt_ensemble *h, int *length, int *per_wavefront, double *state)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    if (!h->trn.on) return fail(WT_E_STATE, k_train_not_set);
+    HIP_TRY(hipSetDevice(h->device));
+    if (length) *length = h->trn.length;
+    if (per_wavefront) *per_wavefront = h->R;
+    return download_records(h, {{state, h->trn.st, wtr::NTRS, 1, wtr::NTRS}});
+}
+
+int wt_ensemble_train_clear(wt_ensemble *h)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    if (!h->trn.on) return WT_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still use the records and the shape
+    if (int rc = train_op(h, wtr::OP_RESTORE)) return rc;
+    if (int rc = sync_checked(h)) return rc;
+    release(train_arrays(h));
+    return reshape(h, h->R0);
 }
 
 int wt_ensemble_score_set(wt_ensemble *h, const double *params, int curve_capacity, int bins, const double *fan_lo, const double *fan_hi)

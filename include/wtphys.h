@@ -147,7 +147,8 @@ int wt_ensemble_queue_error(wt_ensemble *h, int *error);
  * together (they wait for the slowest of them), which is what makes the end of an outer step a
  * wavefront-uniform point for the sensor suite and the PLC scan.  Results never depended on it. */
 int wt_ensemble_set_sync(wt_ensemble *h, int sync_outer);
-/* Placement of reactors into wavefronts.  Reactors never interact, so which of them share a wavefront changes no
+/* Placement of reactors into wavefronts.  Reactors never interact (but for the stages of a train, which are dealt
+ * together: wt_ensemble_train_set), so which of them share a wavefront changes no
  * result bit -- but a wavefront costs what its slowest reactor costs.  WT_PLACE_ADAPTIVE (default): once the cost
  * history (the solver's RHS evaluations per reactor) covers WT_PLACE_MIN_STEPS outer steps, the next wt_ensemble_step
  * call re-deals the wavefront slots in order of cost (device-side stable counting sort on the handle's stream, no
@@ -686,6 +687,59 @@ int wt_ensemble_trend_data(wt_ensemble *h, double *time, double *value);
 int wt_ensemble_trend_reset(wt_ensemble *h);
 /* program off, buffers freed (no effect while none is set) */
 int wt_ensemble_trend_clear(wt_ensemble *h);
+
+/* ---- the train program: reactors coupled into treatment trains ----
+ * An ensemble of N reactors is read as N / length trains of `length` stages (rapid mix, contact tank, clearwell ...):
+ * reactor r is stage r % length of train r / length, and the upstream of a stage s >= 1 is reactor r - 1.
+ * Parameters [WT_NTR][N]: link (0 or 1; a first stage has no upstream, its link must be 0), rows (a whole number 0..7:
+ * WT_TRN_PH 1 | WT_TRN_CHLORINE 2 | WT_TRN_TEMPERATURE 4, the rows a feed writes).  NULL: every stage after the first
+ * linked, rows 7.
+ * Feed.  After every outer step in which the upstream reactor stepped and did not end T_RANGE_POST (the sensor suite's
+ * test), pH, Cl and T of the upstream's outlet zone (zone n - 1) are written into rows 1, 2, 3 (inlet_pH,
+ * inlet_chlorine, inlet_temperature) of the linked downstream reactor's boundary block, each only if `rows` has its
+ * bit, whether or not the downstream reactor itself stepped.  The fed rows are the boundary of the downstream
+ * reactor's next outer step (zero-order hold); with plant I/O that step integrates under both this step's commands and
+ * these rows.  The state is already clamped to the ranges the rows allow, so no clamp is applied.  An upstream that
+ * did not step (a frozen reactor) feeds nothing: its downstream keeps the rows it holds and goes on stepping.
+ * Flows are not carried: row 0 belongs to the command path or the master, and every tank keeps its own inlet flow.
+ * Definition (the fused call gives its bits): on a handle without a program, feed every link from the current state,
+ * then repeat { one outer step; wt_ensemble_get_state; for every linked reactor whose upstream stepped, rows 1..3 of
+ * wt_ensemble_get_boundary <- the upstream's zone n - 1; wt_ensemble_set_boundary }.
+ * Feeds outside a step, from the state in memory, to every link: wt_ensemble_train_set itself, wt_ensemble_set_boundary
+ * with a program set (after it has stored rows 1..3 of the new block as the program's base), wt_ensemble_set_state.
+ * State [WT_NTRS][N]: n_fed (feeds the step kernel wrote into this reactor; those outside a step do not count),
+ * t_last (the upstream's ReactorState.time at the last of them, NaN before the first).
+ * Where the stages sit.  A train's stages share a wavefront, so length is 2..floor(64 / n_zones) (no train above 32
+ * zones) and N a multiple of length.  With a program set the handle holds length * k reactors per wavefront, k chosen
+ * like the reactors per wavefront at creation but counted in trains; the placement deals whole trains into consecutive
+ * slots in stage order (set starts from reactor r in slot r with an empty cost history).  Wave diagnostics and item
+ * trace buffers of the old shape are released by set and clear; their next call starts them again.
+ * set replaces any program (the old one's rows go back to its base first, as clear does) and needs set_state and
+ * set_boundary (WT_E_STATE: "set_state and set_boundary must precede train_set").  Refused with WT_E_ARG:
+ *   "length must be at least 2 and at most 64 / n_zones (the stages of a train share a wavefront)"
+ *   "n_reactors must be a multiple of length (an ensemble holds whole trains)"
+ *   "link must be 0 or 1"
+ *   "the first stage of a train has no upstream: its link must be 0"
+ *   "rows must be an integer in 0..7 (1 pH, 2 chlorine, 4 temperature)"
+ * in this order, reactor by reactor.  A disturbance slot (not OFF) on row 1, 2 or 3 of a linked reactor whose rows
+ * mask has that row would write the cell the train feeds: whichever of wt_ensemble_train_set / wt_ensemble_disturb_set
+ * comes second gives WT_E_STATE, "a disturbance slot targets an inlet row (1, 2 or 3) that the train program feeds
+ * into that reactor".  While a program is set wt_ensemble_step_scheduled gives WT_E_STATE, "a boundary schedule
+ * cannot be combined with a train program (the run itself sets the linked rows)".
+ * clear writes the base back into the linked rows (those of the rows mask) and restores the handle's shape; no effect
+ * while no program is set.  get gives WT_E_STATE, "no train program is set (wt_ensemble_train_set)", while none is.
+ * A shard of a sharded ensemble must hold whole trains.  The program takes no code of wt_program_check:
+ * wt_train_check is its check.  All calls synchronise. */
+enum { WT_TR_LINK = 0, WT_TR_ROWS = 1, WT_NTR = 2 };
+enum { WT_TRS_N_FED = 0, WT_TRS_T_LAST = 1, WT_NTRS = 2 };
+enum { WT_TRN_PH = 1, WT_TRN_CHLORINE = 2, WT_TRN_TEMPERATURE = 4 };
+int wt_ensemble_train_set(wt_ensemble *h, int length, const double *params /* [WT_NTR][N] or NULL */);
+/* the train length, the reactors per wavefront in force and the host [WT_NTRS][N] state (any may be NULL) */
+int wt_ensemble_train_get(wt_ensemble *h, int *length, int *per_wavefront, double *state);
+int wt_ensemble_train_clear(wt_ensemble *h);
+/* the checks wt_ensemble_train_set makes on its arguments, with no handle and no device: WT_OK or WT_E_ARG with that
+ * call's message (also "n_reactors must be >= 1", "n_zones must be in 2..64").  Makes no HIP call. */
+int wt_train_check(int length, int n_zones, int64_t n_reactors, const double *params);
 
 /* ---- the parameter checks of the scan programs, the disturbance and the score program, without a handle or a device ----
  * params: host, the block the program's set or enable call takes, for n_reactors reactors (WT_PROG_CONTROL:

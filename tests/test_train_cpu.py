@@ -1,0 +1,153 @@
+"""CPU checks of the train program (include/wtphys.h ``wt_ensemble_train_*``): the block builder, every refusal of
+``wt_train_check`` with its text, the symbols and constants, and the restatement's bookkeeping (train_ref.py)."""
+import importlib
+import os
+import re
+import types
+
+import numpy as np
+import pytest
+
+from train_ref import TrainRef, feed_rows, params
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+E_LENGTH = "length must be at least 2 and at most 64 / n_zones (the stages of a train share a wavefront)"
+E_MULTIPLE = "n_reactors must be a multiple of length (an ensemble holds whole trains)"
+E_LINK = "link must be 0 or 1"
+E_FIRST = "the first stage of a train has no upstream: its link must be 0"
+E_ROWS = "rows must be an integer in 0..7 (1 pH, 2 chlorine, 4 temperature)"
+
+
+@pytest.fixture(scope="module")
+def trn(native):
+    return importlib.import_module("ics-wt-physicsengine_amd.core.train")
+
+
+def _check(native, length, n, N, blk):
+    rc = native.lib().wt_train_check(length, n, N, native.dptr(None if blk is None else np.ascontiguousarray(blk, dtype=np.float64)))
+    return rc, native.lib().wt_last_error().decode()
+
+
+def test_block_packing_and_row_names(trn, wt):
+    blk = wt.train_block(6, 8, 3)
+    assert blk.shape == (2, 6) and blk.flags["C_CONTIGUOUS"] and blk.dtype == np.float64
+    assert blk[0].tolist() == [0, 1, 1, 0, 1, 1] and blk[1].tolist() == [7] * 6
+    # names -> mask; the link of a first stage is zeroed whatever the caller says
+    blk = wt.train_block(4, 8, 2, linked=[1, 0, 1, 1], rows=("chlorine",))
+    assert blk[0].tolist() == [0, 0, 0, 1] and blk[1].tolist() == [2] * 4
+    assert wt.train_block(4, 4, 2, rows="temperature")[1].tolist() == [4] * 4
+    assert wt.train_block(4, 4, 2, rows=("pH", "temperature"))[1].tolist() == [5] * 4
+    assert wt.train_block(4, 4, 2, rows=())[1].tolist() == [0] * 4
+    assert wt.train_block(4, 4, 2, rows=[7, 2, 0, 4])[1].tolist() == [7, 2, 0, 4]
+    assert wt.train_block(4, 4, 2, linked=False)[0].tolist() == [0] * 4
+    assert float(trn.rows_mask(trn.ALL_ROWS)) == 7.0
+    with pytest.raises(ValueError, match="unknown train row 'flow'"):
+        wt.train_block(4, 4, 2, rows=("pH", "flow"))
+    with pytest.raises(ValueError, match=r"train.linked: expected a scalar or \(4,\) values"):
+        wt.train_block(4, 4, 2, linked=[1, 0, 1])
+
+
+@pytest.mark.parametrize("length, n, N, spoil, msg", [
+    (1, 8, 8, None, E_LENGTH),
+    (0, 8, 8, None, E_LENGTH),
+    (9, 8, 18, None, E_LENGTH),               # floor(64 / 8) = 8
+    (4, 20, 8, None, E_LENGTH),               # floor(64 / 20) = 3
+    (2, 33, 8, None, E_LENGTH),               # no train above 32 zones
+    (2, 64, 8, None, E_LENGTH),
+    (3, 8, 8, None, E_MULTIPLE),
+    (2, 8, 7, None, E_MULTIPLE),
+    (2, 8, 8, (0, 3, 2.0), E_LINK),
+    (2, 8, 8, (0, 3, 0.5), E_LINK),
+    (2, 8, 8, (0, 3, np.nan), E_LINK),
+    (2, 8, 8, (0, 4, 1.0), E_FIRST),
+    (4, 8, 8, (0, 0, 1.0), E_FIRST),
+    (2, 8, 8, (1, 5, 8.0), E_ROWS),
+    (2, 8, 8, (1, 5, -1.0), E_ROWS),
+    (2, 8, 8, (1, 5, 2.5), E_ROWS),
+    (2, 8, 8, (1, 0, np.nan), E_ROWS),        # rows are checked at unlinked reactors too
+    (2, 8, 0, None, "n_reactors must be >= 1"),
+    (2, 1, 8, None, "n_zones must be in 2..64"),
+    (2, 65, 8, None, "n_zones must be in 2..64"),
+])
+def test_train_check_refusals(native, length, n, N, spoil, msg):
+    blk = None
+    if spoil is not None:
+        blk = np.stack(params(N, length)).astype(np.float64)
+        blk[spoil[0], spoil[1]] = spoil[2]
+    rc, text = _check(native, length, n, N, blk)
+    assert rc == native.WT_E_ARG and text == msg
+
+
+def test_train_check_accepts_and_orders_its_messages(native):
+    for length, n, N in ((2, 32, 4), (3, 20, 9), (8, 8, 16), (16, 4, 32), (32, 2, 64), (5, 5, 10)):
+        assert _check(native, length, n, N, None)[0] == native.WT_OK
+        assert _check(native, length, n, N, np.stack(params(N, length)))[0] == native.WT_OK
+    assert _check(native, 2, 8, 4, np.array([[0, 0, 0, 1.0], [0, 3, 5, 6.0]]))[0] == native.WT_OK
+    # the first failing check of the first bad reactor is the one named
+    blk = np.array([[0, 1, 1.0, 1], [9.0, 7, 7, 7]])
+    assert _check(native, 2, 8, 4, blk) == (native.WT_E_ARG, E_ROWS)
+    blk = np.array([[0, 1, 2.0, 1], [7.0, 7, 9, 7]])
+    assert _check(native, 2, 8, 4, blk) == (native.WT_E_ARG, E_LINK)
+    assert _check(native, 3, 8, 4, blk) == (native.WT_E_ARG, E_MULTIPLE)
+
+
+def test_builder_raises_the_library_text(wt):
+    for call, msg in ((lambda: wt.train_block(8, 8, 9), E_LENGTH), (lambda: wt.train_block(8, 20, 4), E_LENGTH),
+                      (lambda: wt.train_block(8, 40, 2), E_LENGTH), (lambda: wt.train_block(7, 8, 2), E_MULTIPLE),
+                      (lambda: wt.train_block(8, 8, 2, linked=2.0), E_LINK),
+                      (lambda: wt.train_block(8, 8, 2, rows=8), E_ROWS),
+                      (lambda: wt.train_block(8, 8, 2, rows=[1, 2, 3, 4, 5, 6, 7, 1.5]), E_ROWS)):
+        with pytest.raises(ValueError) as ei:
+            call()
+        assert str(ei.value) == msg
+
+
+def test_symbols_constants_and_exports(native, wt, trn):
+    header = open(os.path.join(ROOT, "include", "wtphys.h")).read()
+    entries = ("wt_ensemble_train_set", "wt_ensemble_train_get", "wt_ensemble_train_clear", "wt_train_check")
+    plain = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
+    assert sorted(n for n in set(re.findall(r"\b(wt_[a-z_0-9]+)\s*\(", plain)) if "train" in n) == sorted(entries)
+    for name in entries:
+        assert re.search(r"\bint " + name + r"\(", header), name
+        assert hasattr(native.lib(), name), name
+    for pattern in (r"WT_TR_LINK = 0\b", r"WT_TR_ROWS = 1\b", rf"WT_NTR = {trn.NTR}\b", r"WT_TRS_N_FED = 0\b", r"WT_TRS_T_LAST = 1\b",
+                    rf"WT_NTRS = {trn.NTRS}\b", rf"WT_TRN_PH = {trn.ROW_BITS['pH']}\b", rf"WT_TRN_CHLORINE = {trn.ROW_BITS['chlorine']}\b",
+                    rf"WT_TRN_TEMPERATURE = {trn.ROW_BITS['temperature']}\b", r"#define WT_ABI_VERSION 1\b"):
+        assert re.search(pattern, header), pattern
+    assert trn.PARAM_ROWS == ("link", "rows") and trn.STATE_ROWS == ("n_fed", "t_last")
+    # every message the header promises is one the library gives
+    for msg in (E_LENGTH, E_MULTIPLE, E_LINK, E_FIRST, E_ROWS):
+        assert msg in re.sub(r"\s*\n \*\s*", " ", header), msg
+    assert "wt_trn.hpp" in native.BUILD_SOURCES
+    for name in ("TrainState", "train_block"):
+        assert name in wt.__all__ and hasattr(wt, name), name
+    for name in ("set_trains", "train_state", "clear_trains"):
+        assert callable(getattr(wt.ReactorEnsemble, name)), name
+    st = wt.TrainState.from_block(np.arange(8.0).reshape(2, 4), 2, 4)
+    assert np.array_equal(st.block(), np.arange(8.0).reshape(2, 4)) and (st.length, st.per_wavefront) == (2, 4)
+
+
+def test_the_train_program_takes_no_program_code(native, wt):
+    blk = wt.train_block(4, 8, 2)
+    assert native.lib().wt_program_check(8, native.dptr(blk), 4) == native.WT_E_ARG
+    assert native.lib().wt_last_error() == b"unknown program"
+    assert native.lib().wt_abi_version() == 1
+
+
+def test_restatement_feeds_and_counts():
+    N, L, n = 6, 3, 4
+    link, rows = params(N, L, rows=[7, 7, 2, 7, 0, 5])
+    assert link.tolist() == [0, 1, 1, 0, 1, 1]
+    z = np.arange(N * n, dtype=np.float64).reshape(N, n)
+    es = types.SimpleNamespace(pH=z + 0.25, chlorine=z + 0.5, temperature=z + 0.75, time=np.full(N, 10.0),
+                               status=np.array([0, 0, 0, 32, 0, 0], dtype=np.uint32))
+    es.time[1] = 0.0                                       # reactor 1 did not step, reactor 3 ended T_RANGE_POST
+    ref = TrainRef(N, L, rows=rows)
+    fed = ref.after_step(np.zeros(N), es)
+    assert fed.tolist() == [False, True, False, False, False, True]
+    assert ref.n_fed.tolist() == [0, 1, 0, 0, 0, 1] and ref.t_last[[1, 5]].tolist() == [10.0, 10.0] and np.isnan(ref.t_last[[0, 2, 3, 4]]).all()
+    bc = feed_rows(np.zeros((10, N)), es, link, rows, fed)
+    assert bc[1:4, 1].tolist() == [3.25, 3.5, 3.75]        # zone n - 1 of reactor 0
+    assert bc[1:4, 5].tolist() == [19.25, 0.0, 19.75]      # rows 5: pH and temperature
+    assert not bc[:, [0, 2, 3, 4]].any() and not bc[[0, 4, 5, 6, 7, 8, 9]].any()

@@ -1,0 +1,47 @@
+"""What the train program costs in an open-loop run, at 10 000 x 8 read as 2 500 trains of 4, over 500 steps of 10 s:
+  (a) no program (the reference point), one fused call;
+  (b) a program with every link off, one fused call: its bits must equal (a)'s;
+  (c) every stage after the first linked, one fused call;
+  (d) the host-fed loop (c) replaces -- one-step calls with the outlets copied into set_boundary between them
+      (tests/train_ref.py): its bits must equal (c)'s.
+The four alternate over five repeats, the order rotating; the medians are reported.  (c) and (d) also integrate the
+plant under moving inlets, so (c) / (a) is not the feed's cost alone.  Prints one JSON line.
+   python tools/train_probe.py [N] [n] [steps] [length]"""
+import json, sys, time
+from probe_common import arguments, ensemble, outputs, rotate, same, timed_step
+from train_ref import host_fed_loop
+
+N, n, K, cols, bc = arguments(500)
+L = int(sys.argv[4]) if len(sys.argv) > 4 else 4
+DT = 10.0
+
+
+def run(name, rep=0):
+    ens = ensemble(cols, bc, n)
+    if name == "d":
+        ens.synchronize()
+        t0 = time.perf_counter()
+        host_fed_loop(ens, K, L, dt=DT)
+        ens.synchronize()
+        dt = time.perf_counter() - t0
+    else:
+        if name in "bc":
+            ens.set_trains(L, linked=(name == "c"))
+        _, dt = timed_step(ens, DT, K)
+    out = outputs(ens, "boundary")
+    ens.close()
+    return dt, out
+
+
+run("c")                                         # module load, first launches
+REPEATS = 5
+times, med, last = rotate("abcd", REPEATS, run)
+off_same, loop_same = same(last["a"][1], last["b"][1]), same(last["c"][1], last["d"][1])
+print(json.dumps({"N": N, "n": n, "steps": K, "length": L, "none_s": round(med["a"], 4), "unlinked_s": round(med["b"], 4),
+                  "linked_s": round(med["c"], 4), "host_loop_s": round(med["d"], 4),
+                  "unlinked_over_none": round(med["b"] / med["a"], 3), "linked_over_none": round(med["c"] / med["a"], 3),
+                  "host_loop_over_linked": round(med["d"] / med["c"], 2), "repeats": REPEATS,
+                  "all_s": {k: [round(t, 4) for t in v] for k, v in times.items()},
+                  "unlinked_bitwise_equal": bool(off_same), "linked_equals_host_loop_bitwise": bool(loop_same)}))
+if not (off_same and loop_same):
+    sys.exit(1)
