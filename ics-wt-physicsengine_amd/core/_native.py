@@ -165,6 +165,10 @@ def lib():
     L.wt_ensemble_train_get.argtypes = [vp, ip, ip, dp]
     L.wt_ensemble_train_clear.argtypes = [vp]
     L.wt_train_check.argtypes = [C.c_int, C.c_int, C.c_int64, dp]
+    L.wt_ensemble_pipe_set.argtypes = [vp, dp]
+    L.wt_ensemble_pipe_get.argtypes = [vp, ip, dp, dp, dp]
+    L.wt_ensemble_pipe_clear.argtypes = [vp]
+    L.wt_pipe_check.argtypes = [C.c_int64, dp, dp]
     L.wt_ensemble_diagnostics.argtypes = [vp, dp]
     L.wt_ensemble_wave_diag.argtypes = [vp, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int64)]
     L.wt_ensemble_size.argtypes = [vp]
@@ -190,7 +194,7 @@ def lib():
                  "wt_ensemble_detect_get", "wt_ensemble_detect_reset", "wt_ensemble_detect_clear", "wt_ensemble_trend_set",
                  "wt_ensemble_trend_get", "wt_ensemble_trend_data", "wt_ensemble_trend_reset", "wt_ensemble_trend_clear",
                  "wt_program_check", "wt_ensemble_train_set", "wt_ensemble_train_get", "wt_ensemble_train_clear",
-                 "wt_train_check"):
+                 "wt_train_check", "wt_ensemble_pipe_set", "wt_ensemble_pipe_get", "wt_ensemble_pipe_clear", "wt_pipe_check"):
         getattr(L, name).restype = C.c_int
     if L.wt_abi_version() != 1:
         raise ImportError("libwtphys.so ABI version mismatch; rebuild it")

@@ -276,6 +276,7 @@ class ReactorEnsemble:
         self._score_curve = None                # (capacity, bins, edges) of the score program's curve; None: no program
         self._detect_labels: Optional[np.ndarray] = None    # the label block of the detector program; None: no program
         self._trains = False                    # a train program is set
+        self._train_shape = None                # (length, link row) of it: what set_pipes builds its delays against
         self._trend_capacity = 0                # samples per slot and reactor of the trend program's store; 0: no program
         self._control_params: Optional[np.ndarray] = None   # the last block enable_control / retune_control sent
 
@@ -298,6 +299,8 @@ class ReactorEnsemble:
         t = None if time is None else np.ascontiguousarray(np.broadcast_to(np.asarray(time, dtype=np.float64), (self.n_reactors,)))
         _native.check(_native.lib().wt_ensemble_set_state(self._h, _native.dptr(a[0]), _native.dptr(a[1]),
                                                           _native.dptr(a[2]), _native.dptr(t)))
+        if getattr(self, "_trains", False):
+            self._device_boundary_moved = True      # a train program feeds every link from the new state
 
     def set_boundary(self, boundaries) -> None:
         blk = boundary_block(boundaries, self.n_reactors)
@@ -759,6 +762,7 @@ class ReactorEnsemble:
         blk = train.train_block(self.n_reactors, self.n_zones, length, linked, rows)
         self._program_call(_native.lib().wt_ensemble_train_set, int(length), _native.dptr(blk))
         self._trains = True
+        self._train_shape = (int(length), blk[0].copy())
         self._device_boundary_moved = True      # set feeds every link from the current state
         self._diag_on = False                   # the wave diagnostics of the old shape are gone
 
@@ -775,8 +779,47 @@ class ReactorEnsemble:
         wavefront packing it had before."""
         self._program_call(_native.lib().wt_ensemble_train_clear)
         self._trains = False
+        self._train_shape = None
         self._device_boundary_moved = True
         self._diag_on = False
+
+    # -- the pipe program: dead time between the stages of a train, on the device (wt_trn.hpp)
+    def set_pipes(self, delay) -> None:
+        """Give the links of the train program a dead time of ``delay`` whole outer steps (a scalar or an (N,) array,
+        0..4095; ``train.pipe_delay`` converts seconds): the upstream's outlet reaches the downstream's rows through a
+        FIFO of that many samples, which starts full of the water the upstream holds now -- the bits of the train
+        program's host loop with a FIFO per link.  First stages and stages that are not linked get 0.  A link with
+        delay 0 behaves as it does without pipes.  Needs a train program; replaces any pipe program;
+        :meth:`clear_pipes`.  ``set_trains`` and ``clear_trains`` clear the pipes."""
+        if self._train_shape is None:
+            self._program_call(_native.lib().wt_ensemble_pipe_set, None)    # the library's refusal
+        length, link = self._train_shape
+        d = train.pipe_block(self.n_reactors, length, delay, link)
+        self._program_call(_native.lib().wt_ensemble_pipe_set, _native.dptr(d))
+        self._device_boundary_moved = True      # set delivers every link again
+
+    def pipe_state(self) -> "train.PipeState":
+        """Feeds through each line, the time stamp of the sample last delivered, the delays and the ring slots (one
+        synchronisation)."""
+        N = self.n_reactors
+        st, d, slots = np.empty((train.NPS, N), dtype=np.float64), np.empty(N, dtype=np.float64), C.c_int(0)
+        self._program_call(_native.lib().wt_ensemble_pipe_get, C.byref(slots), _native.dptr(d), _native.dptr(st), None)
+        return train.PipeState(np.array(st[0]), np.array(st[1]), d.astype(np.int64), slots.value)
+
+    def pipe_lines(self) -> np.ndarray:
+        """(Dmax, 4, N): the samples in flight in every line, oldest first -- pH, chlorine, temperature of the
+        upstream's outlet zone and the upstream's time when they were taken (NaN for the initial fill) -- padded with
+        NaN beyond a line's own delay.  Dmax is the largest delay of the program."""
+        slots = C.c_int(0)
+        self._program_call(_native.lib().wt_ensemble_pipe_get, C.byref(slots), None, None, None)
+        lines = np.empty((max(slots.value - 1, 0), len(train.PIPE_SAMPLE), self.n_reactors), dtype=np.float64)
+        if lines.size:
+            self._program_call(_native.lib().wt_ensemble_pipe_get, None, None, None, _native.dptr(lines))
+        return lines
+
+    def clear_pipes(self) -> None:
+        """Stop the pipe program: the linked rows stay as they are, the next feed is undelayed."""
+        self._program_call(_native.lib().wt_ensemble_pipe_clear)
 
     def set_detectors(self, *detectors: "detect.Detector", attack=None) -> None:
         """Run a detector program of up to four :class:`Detector` slots at every PLC scan, inside the step call, last in

@@ -325,6 +325,17 @@ ArrayGroup train_arrays(wt_ensemble *h)
             [h] { h->trn.length = 0; h->trn_lk.clear(); }};
 }
 
+// the pipe program's arrays (wt_trn.hpp); the ring is sized by pipe.slots, which the set call stores first
+ArrayGroup pipe_arrays(wt_ensemble *h)
+{
+    wtr::PipeArgs &p = h->trn.pipe;
+    const size_t N = (size_t)h->N;
+    return {"pipe", &p.on, {{(void **)&p.delay, sizeof(int32_t) * N}, {(void **)&p.head, sizeof(int32_t) * N},
+                            {(void **)&p.st, sizeof(double) * wtr::NPS * N},
+                            {(void **)&p.ring, sizeof(double) * wtr::PIPE_Q * (size_t)p.slots * N}},
+            [h] { h->trn.pipe.slots = 0; }};
+}
+
 ArrayGroup trend_arrays(wt_ensemble *h)
 {
     const size_t N = (size_t)h->N;
@@ -618,6 +629,8 @@ int wt_ensemble_set_state(wt_ensemble *h, const double *pH, const double *Cl, co
     hipLaunchKernelGGL(wt::derived_placeholder_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, h->stream, pa);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemsetAsync(h->status, 0, sizeof(uint32_t) * h->N, h->stream));
+    // a pipe program: a new state is a new plant -- every line full of it, the pipe state from the start
+    if (h->trn.pipe.on) if (int rc = train_op(h, wtr::OP_PIPE_FILL)) return rc;
     if (h->trn.on) if (int rc = train_op(h, wtr::OP_FEED)) return rc;   // a train program: every link from the new state
     HIP_TRY(hipStreamSynchronize(h->stream));   // the caller's buffers are free on return
     h->have_state = true;
@@ -633,7 +646,9 @@ int wt_ensemble_set_boundary(wt_ensemble *h, const double *bc)
         HIP_TRY(hipMemcpyAsync(h->dst.base, h->bc, sizeof(double) * WT_NB * h->N, hipMemcpyDeviceToDevice, h->stream));
         if (int rc = disturb_op(h, wtd::OP_COMPOSE)) return rc;
     }
-    if (h->trn.on) {   // a train program: rows 1..3 of the new block are its base, every link is fed from the current state
+    // a train program: rows 1..3 of the new block are its base, every link is fed from the current state (a link with
+    // a pipe: the sample its line last delivered)
+    if (h->trn.on) {
         HIP_TRY(hipMemcpyAsync(h->trn.base, bc + h->N, sizeof(double) * wtr::FED_ROWS * h->N, hipMemcpyHostToDevice, h->stream));
         if (int rc = train_op(h, wtr::OP_FEED)) return rc;
     }
@@ -1579,6 +1594,22 @@ int train_restart(wt_ensemble *h)
     return sync_checked(h);                     // the host vector is freed on return
 }
 
+// -- the pipe program (wt_trn.hpp) on top of a train program
+const char *k_pipe_not_set = "no pipe program is set (wt_ensemble_pipe_set)";
+
+// the first refusal of a delay array, reactor by reactor; linked(r): reactor r has an upstream that feeds it
+template <class Linked> const char *pipe_error(int64_t N, const double *delay, Linked linked)
+{
+    for (int64_t r = 0; r < N; ++r) {
+        if (!whole_in(delay[r], 0, WT_PIPE_MAX_DELAY)) return "delay must be a whole number in 0..4095 (outer steps)";
+        if (delay[r] != 0.0 && !linked(r)) return "a stage that is not linked has no pipe: its delay must be 0";
+    }
+    return nullptr;
+}
+
+// the stream is idle: the lines go, the linked rows stay as they are
+void pipe_release(wt_ensemble *h) { release(pipe_arrays(h)); }
+
 // before a disturbance program's arrays go (clear, a set over a program): the targeted rows back to the base
 int disturb_restore(wt_ensemble *h)
 {
@@ -1597,7 +1628,7 @@ int wt_ensemble_destroy(wt_ensemble *h)
     if (!h) return WT_OK;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (const auto arrays : {core_arrays, queue_arrays, sensor_arrays, plant_io_arrays, record_arrays, train_arrays}) release(arrays(h));
+    for (const auto arrays : {core_arrays, queue_arrays, sensor_arrays, plant_io_arrays, record_arrays, pipe_arrays, train_arrays}) release(arrays(h));
     for (const Program &p : k_programs) release(p.arrays(h));
     free_and_null(h->trace); free_and_null(h->wave_diag); free_and_null(h->snap_dev); free_and_null(h->sched);
     free_and_null(h->diag_out);
@@ -1816,6 +1847,7 @@ int wt_ensemble_train_set(wt_ensemble *h, int length, const double *params)
     if (h->trn.on) {                            // set replaces a program: its rows go back to its base first
         if (int rc = train_op(h, wtr::OP_RESTORE)) return rc;
         if (int rc = sync_checked(h)) return rc;
+        pipe_release(h);                        // and its pipes go with it
     }
     // whole trains per wavefront: the small-ensemble rule of wt_ensemble_create, counted in trains
     const int k = units_per_wavefront(h->device, N / length, 64 / h->n / length);
@@ -1849,8 +1881,81 @@ int wt_ensemble_train_clear(wt_ensemble *h)
     HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still use the records and the shape
     if (int rc = train_op(h, wtr::OP_RESTORE)) return rc;
     if (int rc = sync_checked(h)) return rc;
+    pipe_release(h);
     release(train_arrays(h));
     return reshape(h, h->R0);
+}
+
+int wt_pipe_check(int64_t n_reactors, const double *train_params, const double *delay)
+{
+    if (n_reactors < 1) return fail(WT_E_ARG, "n_reactors must be >= 1");
+    if (!train_params || !delay) return fail(WT_E_ARG, "NULL argument");
+    const char *msg = pipe_error(n_reactors, delay, [&](int64_t r) { return train_params[WT_TR_LINK * n_reactors + r] == 1.0; });
+    return msg ? fail(WT_E_ARG, msg) : WT_OK;
+}
+
+int wt_ensemble_pipe_set(wt_ensemble *h, const double *delay)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    if (!h->trn.on) return fail(WT_E_STATE, k_train_not_set);
+    if (!delay) return fail(WT_E_ARG, "delay is NULL");
+    const int64_t N = h->N;
+    if (const char *msg = pipe_error(N, delay, [&](int64_t r) { return h->trn_lk[(size_t)r] != 0; })) return fail(WT_E_ARG, msg);
+    std::vector<int32_t> d((size_t)N);
+    int most = 0;
+    for (int64_t r = 0; r < N; ++r) { d[(size_t)r] = (int32_t)delay[r]; most = std::max(most, (int)d[(size_t)r]); }
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still use the old lines
+    pipe_release(h);                            // set replaces any program
+    h->trn.pipe.slots = most + 1;
+    int rc = allocate(pipe_arrays(h));
+    if (rc == WT_OK) {
+        h->trn.pipe.on = 1;                     // (the re-delivery below reads the lines)
+        hipError_t e = hipMemcpyAsync((void *)h->trn.pipe.delay, d.data(), sizeof(int32_t) * (size_t)N, hipMemcpyHostToDevice, h->stream);
+        if (e != hipSuccess) rc = fail(WT_E_HIP, hipGetErrorString(e));
+        if (rc == WT_OK) rc = train_op(h, wtr::OP_PIPE_FILL);   // every line full of the upstream's outlet as it is now
+        if (rc == WT_OK) rc = train_op(h, wtr::OP_FEED);        // and every link delivered from it
+        if (rc == WT_OK) rc = sync_checked(h);  // the host vector is freed on return
+    }
+    if (rc != WT_OK) { (void)hipStreamSynchronize(h->stream); pipe_release(h); return rc; }
+    return WT_OK;
+}
+
+int wt_ensemble_pipe_get(wt_ensemble *h, int *slots, double *delay, double *state, double *lines)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    if (!h->trn.pipe.on) return fail(WT_E_STATE, k_pipe_not_set);
+    HIP_TRY(hipSetDevice(h->device));
+    const wtr::PipeArgs &p = h->trn.pipe;
+    const size_t N = (size_t)h->N;
+    if (slots) *slots = p.slots;
+    if (int rc = download_records(h, {{state, p.st, wtr::NPS, 1, wtr::NPS}})) return rc;
+    if (!delay && !lines) return WT_OK;
+    std::vector<int32_t> d(N), head(N);
+    std::vector<double> ring(lines ? (size_t)wtr::PIPE_Q * (size_t)p.slots * N : 0);
+    if (int rc = download(h, {{d.data(), p.delay, sizeof(int32_t) * N}, {head.data(), p.head, sizeof(int32_t) * N},
+                              {lines ? ring.data() : nullptr, p.ring, sizeof(double) * ring.size()}}))
+        return rc;
+    if (delay) for (size_t r = 0; r < N; ++r) delay[r] = (double)d[r];
+    if (lines)   // [slots - 1][4][N]: the samples in flight, oldest first -- the D slots after head, in ring order
+        for (int i = 0; i + 1 < p.slots; ++i)
+            for (int q = 0; q < wtr::PIPE_Q; ++q)
+                for (size_t r = 0; r < N; ++r) {
+                    const int D = d[r];
+                    lines[((size_t)i * wtr::PIPE_Q + q) * N + r] =
+                        i < D ? ring[((size_t)((head[r] + 1 + i) % (D + 1)) * wtr::PIPE_Q + q) * N + r] : NAN;
+                }
+    return WT_OK;
+}
+
+int wt_ensemble_pipe_clear(wt_ensemble *h)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    if (!h->trn.pipe.on) return WT_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still use the lines
+    pipe_release(h);
+    return WT_OK;
 }
 
 int wt_ensemble_score_set(wt_ensemble *h, const double *params, int curve_capacity, int bins, const double *fan_lo, const double *fan_hi)

@@ -741,6 +741,50 @@ int wt_ensemble_train_clear(wt_ensemble *h);
  * call's message (also "n_reactors must be >= 1", "n_zones must be in 2..64").  Makes no HIP call. */
 int wt_train_check(int length, int n_zones, int64_t n_reactors, const double *params);
 
+/* ---- the pipe program: dead time between the stages of a treatment train ----
+ * On top of a set train program, link d (into reactor d, from reactor d - 1) may have a delay line of delay[d] = D
+ * whole outer steps, 0..WT_PIPE_MAX_DELAY, between its upstream's outlet and its own inlet rows.  D must be 0 for a
+ * reactor that is not linked; the first stage of a train is never linked, so it has no pipe.
+ * Line.  The line of link d is a FIFO of exactly D samples.  A sample is (pH, Cl, T of the upstream's outlet zone, the
+ * upstream's ReactorState.time when it was taken).  wt_ensemble_pipe_set fills it with D copies of the upstream's
+ * outlet from the state in memory, time stamp NaN: the pipe starts full of the water the upstream holds now.
+ * Feed.  A feed of link d is the train program's feed: after an outer step in which the upstream stepped and did not
+ * end T_RANGE_POST, whether or not the downstream stepped.  The current sample is appended, the oldest is popped, and
+ * the popped sample is written into rows 1 / 2 / 3 of reactor d as the link's rows mask says.  All three quantities
+ * travel through the line whatever the mask says; the mask only limits what is written at delivery.  A link with
+ * D = 0 has no line: it behaves in every call exactly as it does without a pipe program.  An upstream that does not
+ * feed (frozen, T_RANGE) pushes nothing and pops nothing: the line stalls and the downstream keeps the rows it holds.
+ * Definition (the fused call gives its bits): the train program's host loop with a FIFO per link between
+ * wt_ensemble_get_state and wt_ensemble_set_boundary.
+ * State [WT_NPS][N]: n_sent (feeds that went through this reactor's line inside step calls; 0 where D = 0), t_sent
+ * (the time stamp of the sample last delivered by a step call; NaN before the first delivery and while samples of the
+ * initial fill are still coming out).  n_fed / t_last of the train program keep their meaning: they count deliveries
+ * and hold the upstream's time at the delivery.
+ * Outside a step, with a pipe program set: wt_ensemble_set_state refills every line from the new state and restarts
+ * the pipe state (a new state is a new plant); wt_ensemble_set_boundary stores rows 1..3 as the train program's base
+ * and writes the linked rows again -- D = 0: the upstream's outlet from the state in memory, D >= 1: the sample the
+ * line last delivered (after a set or a refill: the sample it was filled with).
+ * wt_ensemble_pipe_set needs a train program (WT_E_STATE, "no train program is set (wt_ensemble_train_set)"), fills
+ * the lines, delivers every link again from the state in memory and replaces any pipe program.  Refused with WT_E_ARG:
+ *   "delay must be a whole number in 0..4095 (outer steps)"
+ *   "a stage that is not linked has no pipe: its delay must be 0"
+ * in this order, reactor by reactor.  wt_ensemble_pipe_clear turns the program off and frees the lines: the linked
+ * rows stay as they are and the next feed is undelayed; no effect while none is set.  wt_ensemble_train_clear, and a
+ * wt_ensemble_train_set over a program, clear the pipes first.  wt_ensemble_pipe_get gives WT_E_STATE, "no pipe
+ * program is set (wt_ensemble_pipe_set)", while none is.  Not modelled: a dead time that follows the flow (V / Q),
+ * dispersion or lag along the pipe, carried flows, merges and splits.  All calls synchronise. */
+#define WT_PIPE_MAX_DELAY 4095
+enum { WT_PS_N_SENT = 0, WT_PS_T_SENT = 1, WT_NPS = 2 };
+int wt_ensemble_pipe_set(wt_ensemble *h, const double *delay /* [N] */);
+/* slots: the largest delay + 1; delay: host [N]; state: host [WT_NPS][N]; lines: host [slots - 1][4][N], the samples in
+ * flight of every line (pH, Cl, T, time stamp), oldest first, NaN beyond a line's own D (any may be NULL) */
+int wt_ensemble_pipe_get(wt_ensemble *h, int *slots, double *delay, double *state, double *lines);
+int wt_ensemble_pipe_clear(wt_ensemble *h);
+/* the checks wt_ensemble_pipe_set makes on delay [N], with no handle and no device, against the link row of a
+ * [WT_NTR][N] parameter block of wt_ensemble_train_set: WT_OK or WT_E_ARG with that call's message (also
+ * "n_reactors must be >= 1", "NULL argument").  Makes no HIP call. */
+int wt_pipe_check(int64_t n_reactors, const double *train_params, const double *delay);
+
 /* ---- the parameter checks of the scan programs, the disturbance and the score program, without a handle or a device ----
  * params: host, the block the program's set or enable call takes, for n_reactors reactors (WT_PROG_CONTROL:
  * wt_ensemble_control_enable / retune, WT_PROG_INJECT: wt_ensemble_inject_set, WT_PROG_ALARM: wt_ensemble_alarm_set,

@@ -3,17 +3,21 @@
   (b) a program with every link off, one fused call: its bits must equal (a)'s;
   (c) every stage after the first linked, one fused call;
   (d) the host-fed loop (c) replaces -- one-step calls with the outlets copied into set_boundary between them
-      (tests/train_ref.py): its bits must equal (c)'s.
-The four alternate over five repeats, the order rotating; the medians are reported.  (c) and (d) also integrate the
-plant under moving inlets, so (c) / (a) is not the feed's cost alone.  Prints one JSON line.
+      (tests/train_ref.py): its bits must equal (c)'s;
+  (e) (c) with a pipe program whose every delay is 0: its bits must equal (c)'s;
+  (f) (c) with every linked stage behind a pipe of PIPE_DELAY outer steps.
+The six alternate over five repeats, the order rotating; the medians are reported.  (c) and (d) also integrate the
+plant under moving inlets, so (c) / (a) is not the feed's cost alone.  After the rotation the host loop with a FIFO per
+link (tests/pipe_ref.py) runs once, untimed: its bits must equal (f)'s.  Prints one JSON line.
    python tools/train_probe.py [N] [n] [steps] [length]"""
 import json, sys, time
 from probe_common import arguments, ensemble, outputs, rotate, same, timed_step
+from pipe_ref import host_piped_loop
 from train_ref import host_fed_loop
 
 N, n, K, cols, bc = arguments(500)
 L = int(sys.argv[4]) if len(sys.argv) > 4 else 4
-DT = 10.0
+DT, PIPE_DELAY = 10.0, 5
 
 
 def run(name, rep=0):
@@ -25,8 +29,10 @@ def run(name, rep=0):
         ens.synchronize()
         dt = time.perf_counter() - t0
     else:
-        if name in "bc":
-            ens.set_trains(L, linked=(name == "c"))
+        if name in "bcef":
+            ens.set_trains(L, linked=(name != "b"))
+        if name in "ef":
+            ens.set_pipes(PIPE_DELAY if name == "f" else 0)
         _, dt = timed_step(ens, DT, K)
     out = outputs(ens, "boundary")
     ens.close()
@@ -35,13 +41,22 @@ def run(name, rep=0):
 
 run("c")                                         # module load, first launches
 REPEATS = 5
-times, med, last = rotate("abcd", REPEATS, run)
+times, med, last = rotate("abcdef", REPEATS, run)
 off_same, loop_same = same(last["a"][1], last["b"][1]), same(last["c"][1], last["d"][1])
+zero_same = same(last["c"][1], last["e"][1])
+ens = ensemble(cols, bc, n)
+host_piped_loop(ens, K, L, PIPE_DELAY, dt=DT)
+piped_same = same(outputs(ens, "boundary"), last["f"][1])
+ens.close()
 print(json.dumps({"N": N, "n": n, "steps": K, "length": L, "none_s": round(med["a"], 4), "unlinked_s": round(med["b"], 4),
                   "linked_s": round(med["c"], 4), "host_loop_s": round(med["d"], 4),
                   "unlinked_over_none": round(med["b"] / med["a"], 3), "linked_over_none": round(med["c"] / med["a"], 3),
-                  "host_loop_over_linked": round(med["d"] / med["c"], 2), "repeats": REPEATS,
+                  "host_loop_over_linked": round(med["d"] / med["c"], 2),
+                  "pipes_zero_s": round(med["e"], 4), "pipes_s": round(med["f"], 4), "pipe_delay": PIPE_DELAY,
+                  "pipes_zero_over_linked": round(med["e"] / med["c"], 3), "pipes_over_linked": round(med["f"] / med["c"], 3),
+                  "repeats": REPEATS,
                   "all_s": {k: [round(t, 4) for t in v] for k, v in times.items()},
-                  "unlinked_bitwise_equal": bool(off_same), "linked_equals_host_loop_bitwise": bool(loop_same)}))
-if not (off_same and loop_same):
+                  "unlinked_bitwise_equal": bool(off_same), "linked_equals_host_loop_bitwise": bool(loop_same),
+                  "pipes_zero_equals_linked_bitwise": bool(zero_same), "pipes_equal_host_loop_bitwise": bool(piped_same)}))
+if not (off_same and loop_same and zero_same and piped_same):
     sys.exit(1)
