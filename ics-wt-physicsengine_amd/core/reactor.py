@@ -269,16 +269,8 @@ class ReactorEnsemble:
                        np.broadcast_to(np.asarray(cols["initial_chlorine"], dtype=np.float64)[:, None], shape),
                        np.broadcast_to(np.asarray(cols["temperature"], dtype=np.float64)[:, None], shape),
                        np.zeros(self.n_reactors))
-        self._boundary: Optional[np.ndarray] = None
-        self._device_boundary_moved = False     # the command path (plant I/O) rewrites the device's boundary block
-        self._plant_io = False
-        self._disturb_history = -1              # capacity of the disturbance program's history; -1: no program
-        self._score_curve = None                # (capacity, bins, edges) of the score program's curve; None: no program
-        self._detect_labels: Optional[np.ndarray] = None    # the label block of the detector program; None: no program
-        self._trains = False                    # a train program is set
-        self._train_shape = None                # (length, link row) of it: what set_pipes builds its delays against
-        self._trend_capacity = 0                # samples per slot and reactor of the trend program's store; 0: no program
-        self._control_params: Optional[np.ndarray] = None   # the last block enable_control / retune_control sent
+        # nothing else is kept here: what is switched on, every capacity and the boundary block last uploaded live in
+        # the handle, and the methods below ask it (info, and the library's own getters)
 
     # -- lifetime
     def close(self) -> None:
@@ -299,16 +291,18 @@ class ReactorEnsemble:
         t = None if time is None else np.ascontiguousarray(np.broadcast_to(np.asarray(time, dtype=np.float64), (self.n_reactors,)))
         _native.check(_native.lib().wt_ensemble_set_state(self._h, _native.dptr(a[0]), _native.dptr(a[1]),
                                                           _native.dptr(a[2]), _native.dptr(t)))
-        if getattr(self, "_trains", False):
-            self._device_boundary_moved = True      # a train program feeds every link from the new state
 
     def set_boundary(self, boundaries) -> None:
+        """The boundary of every reactor from now on.  The library uploads the block unless the device still holds
+        exactly these bytes (``info(WT_INFO_BOUNDARY_UPLOADS)`` counts the uploads)."""
         blk = boundary_block(boundaries, self.n_reactors)
-        if self._boundary is not None and not self._device_boundary_moved and np.array_equal(blk, self._boundary):
-            return                      # what the device already holds
         _native.check(_native.lib().wt_ensemble_set_boundary(self._h, _native.dptr(blk)))
-        self._boundary = blk.copy()
-        self._device_boundary_moved = False
+
+    def info(self, what: int) -> int:
+        """One of the handle's switches, capacities or counters (``_native.WT_INFO_*``); no synchronisation."""
+        v = C.c_int64(0)
+        _native.check(_native.lib().wt_ensemble_info(self._h, int(what), C.byref(v)))
+        return int(v.value)
 
     def step(self, dt: float, boundaries=None, n_steps: int = 1, fused: bool = True,
              download: bool = True, boundary_schedule=None) -> Optional[EnsembleState]:
@@ -320,10 +314,6 @@ class ReactorEnsemble:
         if boundary_schedule is not None:
             if boundaries is not None:
                 raise ValueError("give either boundaries or boundary_schedule, not both")
-            if self._disturb_history >= 0:
-                raise ValueError("a boundary schedule cannot be combined with a disturbance program (clear_disturbances)")
-            if self._trains:
-                raise ValueError("a boundary schedule cannot be combined with a train program (clear_trains)")
             blk = boundary_schedule_block(boundary_schedule, int(n_steps), self.n_reactors)
             try:
                 _native.check(_native.lib().wt_ensemble_step_scheduled(self._h, float(dt), int(n_steps), 1 if fused else 0,
@@ -332,24 +322,15 @@ class ReactorEnsemble:
                 if e.code in (_native.WT_E_ARG, _native.WT_E_STATE):
                     raise ValueError(e.message) from None
                 raise
-            if blk.shape[0] > 0:
-                self._boundary = blk[-1].copy()     # what the device's boundary block now holds
-                self._device_boundary_moved = False
             return self.state if download else None
         if boundaries is not None:
             self.set_boundary(boundaries)
-        if self._boundary is None:
-            raise ValueError("boundary conditions have not been set")
         try:
             _native.check(_native.lib().wt_ensemble_step(self._h, float(dt), int(n_steps), 1 if fused else 0))
         except _native.WtError as e:
-            if e.code == _native.WT_E_ARG:
+            if e.code in (_native.WT_E_ARG, _native.WT_E_STATE):
                 raise ValueError(e.message) from None
             raise
-        if getattr(self, "_plant_io", False) or self._disturb_history >= 0 or self._trains:
-            # every PLC scan rewrites the device's boundary rows 0 / 4 / 6, a disturbance program its targeted rows, a
-            # train program the linked reactors' rows 1 / 2 / 3
-            self._device_boundary_moved = True
         return self.state if download else None
 
     def record(self, every: int = 1, capacity: int = 0) -> None:
@@ -487,7 +468,6 @@ class ReactorEnsemble:
         _native.check(_native.lib().wt_ensemble_sensors_enable(
             self._h, C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), int(reactor_base), _native.dptr(col("flow_rate")),
             _native.dptr(col("initial_chlorine")), _native.dptr(col("temperature")), int(history)))
-        self._sensor_history = int(history)
 
     def sensor_readings(self):
         """(values float32 (7, N), status uint8 (7, N), fault uint8 (7, N)) of the last read."""
@@ -500,7 +480,7 @@ class ReactorEnsemble:
 
     def sensor_history(self):
         """(values (H, 7, N), status, fault, reads per reactor (N,)) recorded since enable_sensors(history=H)."""
-        N, H = self.n_reactors, self._sensor_history
+        N, H = self.n_reactors, self.info(_native.WT_INFO_SENSOR_HISTORY)
         v = np.empty((H, 7, N), dtype=np.float32); s = np.empty((H, 7, N), dtype=np.uint8); f = np.empty((H, 7, N), dtype=np.uint8)
         n = np.zeros(N, dtype=np.int32)
         u8 = C.POINTER(C.c_uint8)
@@ -521,8 +501,6 @@ class ReactorEnsemble:
         input image is refreshed from the sensor readings (``update_modbus_inputs``) and the holding image
         is validated into the boundary conditions (``read_modbus_commands`` + ``apply_boundary_conditions``)."""
         _native.check(_native.lib().wt_ensemble_plc_enable(self._h))
-        self._plant_io = True
-        self._device_boundary_moved = True
 
     @staticmethod
     def encode_float32(values) -> np.ndarray:
@@ -595,24 +573,21 @@ class ReactorEnsemble:
         between two calls of one scan interval would.  Needs :meth:`enable_plant_io`."""
         blk = control.control_block(self.n_reactors, chlorine, acid)
         self._program_call(_native.lib().wt_ensemble_control_enable, _native.dptr(blk))
-        self._control_params = blk
 
     def retune_control(self, chlorine=None, acid=None) -> None:
         """New parameters for running loops: a :class:`PILoop` replaces a loop's parameters, ``None`` keeps them,
         ``False`` switches the loop off.  Integral, output and metrics stay; a loop switched on starts as at enable."""
-        old = getattr(self, "_control_params", None)
-        if old is None:
-            raise ValueError("control is off (enable_control)")
-        rows = [old[i] if loop is None else control.loop_rows(loop, name, self.n_reactors)
-                for i, (name, loop) in enumerate(zip(control.LOOPS, (chlorine, acid)))]
-        blk = np.ascontiguousarray(np.stack(rows))
+        blk = np.empty((len(control.LOOPS), control.NC, self.n_reactors), dtype=np.float64)
+        if chlorine is None or acid is None:    # a loop that is kept: its rows as the library holds them
+            self._program_call(_native.lib().wt_ensemble_program_params, _native.WT_PROG_CONTROL, _native.dptr(blk))
+        for i, (name, loop) in enumerate(zip(control.LOOPS, (chlorine, acid))):
+            if loop is not None:
+                blk[i] = control.loop_rows(loop, name, self.n_reactors)
         self._program_call(_native.lib().wt_ensemble_control_retune, _native.dptr(blk))
-        self._control_params = blk
 
     def disable_control(self) -> None:
         """Stop the PI programs; the holding registers keep their last outputs."""
         self._program_call(_native.lib().wt_ensemble_control_disable)
-        self._control_params = None
 
     def control_state(self) -> "control.ControlState":
         """Integral, output and metrics of both loops by reactor (one synchronisation)."""
@@ -720,8 +695,6 @@ class ReactorEnsemble:
         blk = disturb.disturbance_block(self.n_reactors, *disturbances)
         self._program_call(_native.lib().wt_ensemble_disturb_set, _native.dptr(blk),
                            C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), int(reactor_base), int(history))
-        self._disturb_history = int(history)
-        self._device_boundary_moved = True
 
     def disturbance_state(self) -> "disturb.DisturbanceState":
         """Slot state, base block and t_prev of the disturbance program (one synchronisation)."""
@@ -735,7 +708,7 @@ class ReactorEnsemble:
     def disturbance_history(self):
         """(offsets (H, 4, N), entries filled per reactor (N,)): entry k holds the offsets the reactor's k-th step
         after :meth:`set_disturbances` integrated under (entry 0: those made at set time)."""
-        N, H = self.n_reactors, max(self._disturb_history, 0)
+        N, H = self.n_reactors, self.info(_native.WT_INFO_DISTURB_HISTORY)
         off = np.empty((H, disturb.SLOTS, N), dtype=np.float64)
         filled = np.empty(N, dtype=np.int32)
         self._program_call(_native.lib().wt_ensemble_disturb_history, _native.dptr(off) if H else None,
@@ -745,8 +718,6 @@ class ReactorEnsemble:
     def clear_disturbances(self) -> None:
         """Stop the disturbance program: the targeted rows go back to the base."""
         self._program_call(_native.lib().wt_ensemble_disturb_clear)
-        self._disturb_history = -1
-        self._device_boundary_moved = True
 
     # -- anomaly detector programs at every PLC scan, on the device (wt_det.hpp)
     # -- the train program: stages feed their downstream after every outer step, on the device (wt_trn.hpp)
@@ -761,10 +732,6 @@ class ReactorEnsemble:
         about trains: choose sizes that are multiples of ``length``).  Replaces any program; :meth:`clear_trains`."""
         blk = train.train_block(self.n_reactors, self.n_zones, length, linked, rows)
         self._program_call(_native.lib().wt_ensemble_train_set, int(length), _native.dptr(blk))
-        self._trains = True
-        self._train_shape = (int(length), blk[0].copy())
-        self._device_boundary_moved = True      # set feeds every link from the current state
-        self._diag_on = False                   # the wave diagnostics of the old shape are gone
 
     def train_state(self) -> "train.TrainState":
         """Feeds counted per reactor, the upstream's time at the last one, the train length and the reactors per
@@ -778,10 +745,6 @@ class ReactorEnsemble:
         """Stop the train program: the linked rows go back to what ``set_boundary`` last gave, the handle to the
         wavefront packing it had before."""
         self._program_call(_native.lib().wt_ensemble_train_clear)
-        self._trains = False
-        self._train_shape = None
-        self._device_boundary_moved = True
-        self._diag_on = False
 
     # -- the pipe program: dead time between the stages of a train, on the device (wt_trn.hpp)
     def set_pipes(self, delay) -> None:
@@ -791,12 +754,10 @@ class ReactorEnsemble:
         program's host loop with a FIFO per link.  First stages and stages that are not linked get 0.  A link with
         delay 0 behaves as it does without pipes.  Needs a train program; replaces any pipe program;
         :meth:`clear_pipes`.  ``set_trains`` and ``clear_trains`` clear the pipes."""
-        if self._train_shape is None:
-            self._program_call(_native.lib().wt_ensemble_pipe_set, None)    # the library's refusal
-        length, link = self._train_shape
-        d = train.pipe_block(self.n_reactors, length, delay, link)
+        par = np.empty((train.NTR, self.n_reactors), dtype=np.float64)
+        self._program_call(_native.lib().wt_ensemble_train_params, _native.dptr(par))   # refused without a train program
+        d = train.pipe_block(self.n_reactors, self.info(_native.WT_INFO_TRAIN_LENGTH), delay, par[0])
         self._program_call(_native.lib().wt_ensemble_pipe_set, _native.dptr(d))
-        self._device_boundary_moved = True      # set delivers every link again
 
     def pipe_state(self) -> "train.PipeState":
         """Feeds through each line, the time stamp of the sample last delivered, the delays and the ring slots (one
@@ -831,14 +792,15 @@ class ReactorEnsemble:
         blk = detect.detector_block(self.n_reactors, *detectors)
         lab = detect.label_block(self.n_reactors, attack)
         self._program_call(_native.lib().wt_ensemble_detect_set, _native.dptr(blk), _native.dptr(lab))
-        self._detect_labels = lab
 
     def detector_state(self) -> "detect.DetectorState":
-        """Slot state, t_prev and label of the detector program (one synchronisation)."""
+        """Slot state, t_prev and label of the detector program (two downloads, each synchronises)."""
         st = np.empty((detect.SLOTS, detect.NKS, self.n_reactors), dtype=np.float64)
         tp = np.empty(self.n_reactors, dtype=np.float64)
+        lab = np.empty((detect.NKR, self.n_reactors), dtype=np.float64)
         self._program_call(_native.lib().wt_ensemble_detect_get, _native.dptr(st), _native.dptr(tp))
-        return detect.DetectorState.from_block(st, tp, self._detect_labels)
+        self._program_call(_native.lib().wt_ensemble_detect_labels, _native.dptr(lab))
+        return detect.DetectorState.from_block(st, tp, lab)
 
     def reset_detectors(self) -> None:
         """Statistics, alarms and counts back to their values at :meth:`set_detectors`, at the current loop time; the
@@ -848,7 +810,6 @@ class ReactorEnsemble:
     def clear_detectors(self) -> None:
         """Stop the detector program and free its buffers."""
         self._program_call(_native.lib().wt_ensemble_detect_clear)
-        self._detect_labels = None
 
     # -- trend recorder programs at every PLC scan, on the device (wt_trd.hpp)
     def set_trends(self, *trends: "trend.Trend", capacity: int, wrap: bool = False) -> None:
@@ -860,7 +821,6 @@ class ReactorEnsemble:
         32 zones."""
         blk = trend.trend_block(self.n_reactors, *trends)
         self._program_call(_native.lib().wt_ensemble_trend_set, _native.dptr(blk), int(capacity), int(bool(wrap)))
-        self._trend_capacity = int(capacity)
 
     def trend_state(self) -> "trend.TrendState":
         """Slot state of the trend program (one synchronisation)."""
@@ -872,10 +832,11 @@ class ReactorEnsemble:
         """The recorded series, oldest sample first (a wrapped store is unwrapped), NaN past the samples held."""
         st = np.empty((trend.SLOTS, trend.NTS, self.n_reactors), dtype=np.float64)
         self._program_call(_native.lib().wt_ensemble_trend_get, _native.dptr(st))
-        t = np.empty((trend.SLOTS, self._trend_capacity, self.n_reactors), dtype=np.float64)
+        cap = self.info(_native.WT_INFO_TREND_CAPACITY)
+        t = np.empty((trend.SLOTS, cap, self.n_reactors), dtype=np.float64)
         x = np.empty_like(t)
         self._program_call(_native.lib().wt_ensemble_trend_data, _native.dptr(t), _native.dptr(x))
-        count = np.minimum(st[:, trend.STATE_ROWS.index("n_recorded")], self._trend_capacity).astype(np.int64)
+        count = np.minimum(st[:, trend.STATE_ROWS.index("n_recorded")], cap).astype(np.int64)
         return trend.TrendData(t, x, count)
 
     def reset_trends(self) -> None:
@@ -886,7 +847,6 @@ class ReactorEnsemble:
     def clear_trends(self) -> None:
         """Stop the trend program and free its buffers."""
         self._program_call(_native.lib().wt_ensemble_trend_clear)
-        self._trend_capacity = 0
 
     # -- score programs after every outer step, on the device (wt_scr.hpp)
     def set_scores(self, *scores: "score.Score", curve: int = 0, bins: int = 0, fan_range=None) -> None:
@@ -898,7 +858,7 @@ class ReactorEnsemble:
         values per slot.  Nothing in the plant changes.  Replaces any program; at most 32 zones per reactor."""
         blk = score.score_block(self.n_reactors, *scores)
         cap, B = int(curve), int(bins)
-        lo = hi = edges = None
+        lo = hi = None
         if B > 0:
             if fan_range is None:
                 raise ValueError("bins > 0 needs fan_range=(lo, hi)")
@@ -909,9 +869,6 @@ class ReactorEnsemble:
                 raise ValueError("fan_range: expected (lo, hi), each a scalar or one value per slot (4,)") from None
         self._program_call(_native.lib().wt_ensemble_score_set, _native.dptr(blk), cap, B,
                            None if lo is None else _native.dptr(lo), None if hi is None else _native.dptr(hi))
-        if B > 0 and cap > 0:
-            edges = score.fan_edges(lo, hi, B)
-        self._score_curve = (cap, B if cap > 0 else 0, edges)
 
     def score_state(self) -> "score.ScoreState":
         """The per-reactor accumulators of the score program (one synchronisation)."""
@@ -923,13 +880,17 @@ class ReactorEnsemble:
     def score_curve(self) -> "score.ScoreCurve":
         """The ensemble curve of the score program: the outer steps taken since :meth:`set_scores` or
         :meth:`reset_scores`, up to the curve's capacity (one synchronisation)."""
-        cap, B, edges = self._score_curve if self._score_curve is not None else (0, 0, None)
+        cap, B = self.info(_native.WT_INFO_SCORE_CURVE), self.info(_native.WT_INFO_SCORE_BINS)
         counts = np.zeros((cap, score.SLOTS, 3), dtype=np.int32)
         fan = np.zeros((cap, score.SLOTS, B + 2), dtype=np.int32) if B > 0 else None
         i32p, k = C.POINTER(C.c_int32), C.c_int(0)
         self._program_call(_native.lib().wt_ensemble_score_curve, counts.ctypes.data_as(i32p) if cap else None,
                            fan.ctypes.data_as(i32p) if fan is not None else None, C.byref(k))
-        K = k.value
+        K, edges = k.value, None
+        if B > 0:
+            lo, hi = np.empty(score.SLOTS), np.empty(score.SLOTS)
+            self._program_call(_native.lib().wt_ensemble_score_fan_range, _native.dptr(lo), _native.dptr(hi))
+            edges = score.fan_edges(lo, hi, B)
         return score.ScoreCurve(counts[:K, :, 0].copy(), counts[:K, :, 1].copy(), counts[:K, :, 2].copy(),
                                 None if fan is None else fan[:K].copy(), edges)
 
@@ -941,7 +902,6 @@ class ReactorEnsemble:
     def clear_scores(self) -> None:
         """Stop the score program and free its buffers."""
         self._program_call(_native.lib().wt_ensemble_score_clear)
-        self._score_curve = None
 
     # -- diagnostics (NEXT-4)
     DIAGNOSTIC_FIELDS = ("total_chlorine_mg", "total_H_mol", "total_OH_mol", "charge_balance_mol", "thermal_energy_kJ",
@@ -964,11 +924,10 @@ class ReactorEnsemble:
         call only switches recording on and returns None."""
         nw = C.c_int64(0)
         L = _native.lib()
-        if not getattr(self, "_diag_on", False):
-            _native.check(L.wt_ensemble_wave_diag(self._h, None, 0, C.byref(nw)))
-            self._diag_on = True
+        on = self.info(_native.WT_INFO_WAVE_DIAG)
+        _native.check(L.wt_ensemble_wave_diag(self._h, None, 0, C.byref(nw)))     # not allocated: switches them on
+        if not on:
             return None
-        _native.check(L.wt_ensemble_wave_diag(self._h, None, 0, C.byref(nw)))
         out = np.zeros((nw.value, L.wt_wave_diag_slots()), dtype=np.int64)
         _native.check(L.wt_ensemble_wave_diag(self._h, out.ctypes.data_as(C.POINTER(C.c_int64)), nw.value, C.byref(nw)))
         return out

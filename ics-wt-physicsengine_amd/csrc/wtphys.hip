@@ -66,6 +66,13 @@ struct wt_ensemble {
     int64_t *trace = nullptr; int trace_cap = 0;   // developer item trace (wt_ensemble_item_trace)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool have_bc = false, have_state = false;
+    // The boundary block as the host last sent it (wt_ensemble_set_boundary, or the last row of a schedule), and whether
+    // the device's block still is that block: then set_boundary of the same bytes has nothing to upload.  Whoever
+    // writes bc on the device says so: disturb_op, train_op, and run_steps under plant I/O, a disturbance or a train
+    // program.  bc_uploads counts the set_boundary calls that did upload.
+    std::vector<double> bc_sent;
+    bool bc_known = false;
+    int64_t bc_uploads = 0;
     // Schedule.  WT_SCHED_QUEUE (default): one launch per wt_ensemble_step call, worker wavefronts take
     // (wavefront-group, next few outer steps) items from a device-side FIFO.  WT_SCHED_STREAMS (round-1
     // schedule, kept for comparison): n_sub contiguous reactor ranges on their own HIP streams, launches of
@@ -507,6 +514,7 @@ int download_records(wt_ensemble *h, const std::vector<Records> &parts)
 // The disturbance program's host operations (wtd::host_op_kernel) on the handle's stream, not synchronised.
 int disturb_op(wt_ensemble *h, int op)
 {
+    h->bc_known = false;   // every op writes the targeted rows
     const wtd::HostOpArgs a{h->dst, h->bc, h->time, h->N, op};
     hipLaunchKernelGGL(wtd::host_op_kernel<wt::ExpK>, dim3((unsigned)((h->N + 255) / 256)), dim3(256), 0, h->stream, a);
     HIP_TRY(hipGetLastError());
@@ -516,9 +524,35 @@ int disturb_op(wt_ensemble *h, int op)
 // The train program's host operations (wtr::host_op_kernel) on the handle's stream, not synchronised.
 int train_op(wt_ensemble *h, int op)
 {
+    h->bc_known = false;   // a feed, a restore or a delivery writes the linked rows
     const wtr::HostOpArgs a{h->trn, h->bc, h->pH, h->Cl, h->T, h->N, h->n, op};
     hipLaunchKernelGGL(wtr::host_op_kernel, dim3((unsigned)((h->N + 255) / 256)), dim3(256), 0, h->stream, a);
     HIP_TRY(hipGetLastError());
+    return WT_OK;
+}
+
+// The device work of wt_ensemble_set_boundary.  The block is "known" once its copy is queued and before the programs'
+// ops run: under a disturbance or a train program they leave it unknown again, which is what the device then holds.
+int upload_boundary(wt_ensemble *h, const double *bc)
+{
+    const size_t cells = (size_t)WT_NB * (size_t)h->N;
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipMemcpyAsync(h->bc, bc, sizeof(double) * cells, hipMemcpyHostToDevice, h->stream));
+    h->bc_sent.assign(bc, bc + cells);
+    h->bc_known = true;
+    ++h->bc_uploads;
+    if (h->dst.on) {   // a disturbance program: the new block is its base, the targeted rows are recomposed (no draw)
+        HIP_TRY(hipMemcpyAsync(h->dst.base, h->bc, sizeof(double) * cells, hipMemcpyDeviceToDevice, h->stream));
+        if (int rc = disturb_op(h, wtd::OP_COMPOSE)) return rc;
+    }
+    // a train program: rows 1..3 of the new block are its base, every link is fed from the current state (a link with
+    // a pipe: the sample its line last delivered)
+    if (h->trn.on) {
+        HIP_TRY(hipMemcpyAsync(h->trn.base, bc + h->N, sizeof(double) * wtr::FED_ROWS * h->N, hipMemcpyHostToDevice, h->stream));
+        if (int rc = train_op(h, wtr::OP_FEED)) return rc;
+    }
+    HIP_TRY(hipStreamSynchronize(h->stream));   // the caller's block is free on return
+    h->have_bc = true;
     return WT_OK;
 }
 
@@ -640,21 +674,12 @@ int wt_ensemble_set_state(wt_ensemble *h, const double *pH, const double *Cl, co
 int wt_ensemble_set_boundary(wt_ensemble *h, const double *bc)
 {
     if (!h || !bc) return fail(WT_E_ARG, "NULL argument");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipMemcpyAsync(h->bc, bc, sizeof(double) * WT_NB * h->N, hipMemcpyHostToDevice, h->stream));
-    if (h->dst.on) {   // a disturbance program: the new block is its base, the targeted rows are recomposed (no draw)
-        HIP_TRY(hipMemcpyAsync(h->dst.base, h->bc, sizeof(double) * WT_NB * h->N, hipMemcpyDeviceToDevice, h->stream));
-        if (int rc = disturb_op(h, wtd::OP_COMPOSE)) return rc;
-    }
-    // a train program: rows 1..3 of the new block are its base, every link is fed from the current state (a link with
-    // a pipe: the sample its line last delivered)
-    if (h->trn.on) {
-        HIP_TRY(hipMemcpyAsync(h->trn.base, bc + h->N, sizeof(double) * wtr::FED_ROWS * h->N, hipMemcpyHostToDevice, h->stream));
-        if (int rc = train_op(h, wtr::OP_FEED)) return rc;
-    }
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    h->have_bc = true;
-    return WT_OK;
+    // the bytes the device already holds: nothing to do, no device call at all (the drop-in's step() sends its
+    // boundary with every call)
+    if (h->bc_known && std::memcmp(bc, h->bc_sent.data(), sizeof(double) * h->bc_sent.size()) == 0) return WT_OK;
+    const int rc = upload_boundary(h, bc);
+    if (rc != WT_OK) h->bc_known = false;
+    return rc;
 }
 
 } // extern "C"
@@ -758,6 +783,8 @@ int run_steps(wt_ensemble *h, double dt, int n_steps, int fused)
 {
     const bool rec = recording_open(h);
     int rc = WT_OK;
+    // the command path, a disturbance program and a train program write the boundary block inside the launches
+    if (h->sens.plc_on | h->dst.on | h->trn.on) h->bc_known = false;
     if ((h->call_sched || rec) && !wt::x_in_item(levels_for(h->n))) {
         // the n > 32 kernel neither reloads the schedule nor records inside a work item: one outer step per launch
         // (each starts from its own schedule row), a record copied from the state in memory after the steps that want one
@@ -826,9 +853,14 @@ int wt_ensemble_step_scheduled(wt_ensemble *h, double dt, int n_steps, int fused
     const int rc = run_steps(h, dt, n_steps, fused);
     h->call_sched = nullptr;
     if (rc != WT_OK) return rc;
-    // the boundary block is the last row from now on (get_boundary, rhs, later plain step calls)
+    // the boundary block is the last row from now on (get_boundary, rhs, later plain step calls, and a set_boundary
+    // of that row, which finds it there)
+    h->bc_known = false;
     HIP_TRY(hipMemcpyAsync(h->bc, h->sched + (size_t)(n_steps - 1) * (size_t)row, sizeof(double) * (size_t)row,
                            hipMemcpyDeviceToDevice, h->stream));
+    const double *last = bc_schedule + (size_t)(n_steps - 1) * (size_t)row;
+    h->bc_sent.assign(last, last + row);
+    h->bc_known = true;
     h->have_bc = true;
     return WT_OK;
 }
@@ -1396,6 +1428,7 @@ const Program k_programs[] = {
 constexpr int N_PROGRAMS = (int)(sizeof k_programs / sizeof *k_programs);
 static_assert(WT_PROG_CONTROL == 0 && WT_PROG_INJECT == 1 && WT_PROG_ALARM == 2 && WT_PROG_ACTUATOR == 3 && WT_PROG_DISTURB == 4 &&
               WT_PROG_SCORE == 5 && WT_PROG_DETECT == 6 && WT_PROG_TREND == 7 && N_PROGRAMS == 8, "k_programs is indexed by WT_PROG_*");
+static_assert(WT_INFO_PROGRAM + N_PROGRAMS == WT_INFO_TRAIN, "wt_ensemble_info: one code per program, then the rest");
 
 // -- the lifecycle
 
@@ -1873,6 +1906,19 @@ int wt_ensemble_train_get(wt_ensemble *h, int *length, int *per_wavefront, doubl
     return download_records(h, {{state, h->trn.st, wtr::NTRS, 1, wtr::NTRS}});
 }
 
+int wt_ensemble_train_params(wt_ensemble *h, double *params)
+{
+    if (!h || !params) return fail(WT_E_ARG, "NULL argument");
+    if (!h->trn.on) return fail(WT_E_STATE, k_train_not_set);
+    const int64_t N = h->N;
+    for (int64_t r = 0; r < N; ++r) {
+        const int32_t lk = h->trn_lk[(size_t)r];
+        params[WT_TR_LINK * N + r] = (lk & wtr::LINKED) ? 1.0 : 0.0;
+        params[WT_TR_ROWS * N + r] = (double)(lk & 7);
+    }
+    return WT_OK;
+}
+
 int wt_ensemble_train_clear(wt_ensemble *h)
 {
     if (!h) return fail(WT_E_ARG, "NULL handle");
@@ -1999,6 +2045,16 @@ int wt_ensemble_score_curve(wt_ensemble *h, int32_t *counts, int32_t *fan, int *
                         {h->scr.fan ? fan : nullptr, h->scr.fan, sizeof(int32_t) * (size_t)(h->scr.bins + 2) * cells}});
 }
 
+int wt_ensemble_score_fan_range(wt_ensemble *h, double *fan_lo, double *fan_hi)
+{
+    if (int rc = program_ready(h, WT_PROG_SCORE)) return rc;
+    for (int k = 0; k < wtsc::SLOTS; ++k) {
+        if (fan_lo) fan_lo[k] = h->scr.fan_lo[k];
+        if (fan_hi) fan_hi[k] = h->scr.fan_hi[k];
+    }
+    return WT_OK;
+}
+
 int wt_ensemble_score_reset(wt_ensemble *h) { return reset_program(h, WT_PROG_SCORE); }
 int wt_ensemble_score_clear(wt_ensemble *h) { return stop_program(h, WT_PROG_SCORE); }
 
@@ -2027,6 +2083,12 @@ int wt_ensemble_detect_get(wt_ensemble *h, double *slot_state, double *t_prev)
 {
     if (!h) return fail(WT_E_ARG, "NULL handle");
     return get_program(h, WT_PROG_DETECT, {{slot_state, h->det.st, wtk::ST_DOUBLES, wtk::SLOTS, wtk::NKS}, {t_prev, h->det.tp, 1, 1, 1}});
+}
+
+int wt_ensemble_detect_labels(wt_ensemble *h, double *labels)
+{
+    if (!h || !labels) return fail(WT_E_ARG, "NULL argument");
+    return get_program(h, WT_PROG_DETECT, {{labels, h->det.lab, wtk::NKR, 1, wtk::NKR}});
 }
 
 int wt_ensemble_detect_reset(wt_ensemble *h) { return reset_program(h, WT_PROG_DETECT); }
@@ -2084,6 +2146,39 @@ int wt_ensemble_get_boundary(wt_ensemble *h, double *bc)
     if (!h->have_bc) return fail(WT_E_STATE, "set_boundary must precede get_boundary");
     HIP_TRY(hipSetDevice(h->device));
     return download(h, {{bc, h->bc, sizeof(double) * WT_NB * (size_t)h->N}});
+}
+
+int wt_ensemble_info(wt_ensemble *h, int what, int64_t *value)
+{
+    if (!h || !value) return fail(WT_E_ARG, "NULL argument");
+    if (what >= WT_INFO_PROGRAM && what < WT_INFO_PROGRAM + N_PROGRAMS) {
+        *value = *k_programs[what - WT_INFO_PROGRAM].arrays(h).on != 0;
+        return WT_OK;
+    }
+    switch (what) {
+    case WT_INFO_PLANT_IO: *value = h->sens.plc_on != 0; break;
+    case WT_INFO_TRAIN: *value = h->trn.on != 0; break;
+    case WT_INFO_PIPE: *value = h->trn.pipe.on != 0; break;
+    case WT_INFO_SENSOR_HISTORY: *value = h->sens.hist_cap; break;
+    case WT_INFO_DISTURB_HISTORY: *value = h->dst.hist_cap; break;
+    case WT_INFO_SCORE_CURVE: *value = h->scr.curve_cap; break;
+    case WT_INFO_SCORE_BINS: *value = h->scr.bins; break;
+    case WT_INFO_TREND_CAPACITY: *value = h->trd.cap; break;
+    case WT_INFO_TRAIN_LENGTH: *value = h->trn.length; break;
+    case WT_INFO_WAVE_DIAG: *value = h->wave_diag != nullptr; break;
+    case WT_INFO_BOUNDARY_UPLOADS: *value = h->bc_uploads; break;
+    default: return fail(WT_E_ARG, "unknown info code");
+    }
+    return WT_OK;
+}
+
+int wt_ensemble_program_params(wt_ensemble *h, int program, double *params)
+{
+    if (!h || !params) return fail(WT_E_ARG, "NULL argument");
+    if (program < 0 || program >= N_PROGRAMS) return fail(WT_E_ARG, "unknown program");
+    const Program &p = k_programs[program];
+    const double *rec = (const double *)*p.arrays(h).arrays[0].first;   // the parameter records: the group's first array
+    return get_program(h, program, {{params, rec, p.slots * p.fields, p.slots, p.fields}});
 }
 
 int wt_ensemble_diagnostics(wt_ensemble *h, double *out)

@@ -94,7 +94,12 @@ int wt_ensemble_destroy(wt_ensemble *h);
  * Host arrays [N][n]; `time` [N] may be NULL (keeps current).  Clears status. */
 int wt_ensemble_set_state(wt_ensemble *h, const double *pH, const double *Cl, const double *T,
                           const double *time);
-/* BoundaryConditions for every reactor (reactor.py:150-186), host [WT_NB][N]. */
+/* BoundaryConditions for every reactor (reactor.py:150-186), host [WT_NB][N].  The handle keeps the bytes it last
+ * uploaded and knows whether the device's block still is that block: a call with the same bytes (memcmp: -0.0 is not
+ * 0.0, a NaN equals only the same NaN) then returns WT_OK without a device call.  The device's block stops being the
+ * host's where the library writes it: a step call under plant I/O, a disturbance or a train program, and every host
+ * operation of those two programs (set, clear, set_boundary itself, set_state under a train program, pipe_set); the
+ * next call uploads whatever its bytes.  wt_ensemble_info(WT_INFO_BOUNDARY_UPLOADS) counts the calls that uploaded. */
 int wt_ensemble_set_boundary(wt_ensemble *h, const double *bc);
 
 /* IntegratedCSTR.step(dt, boundary) n_steps times (reactor.py:450-509); asynchronous, ordered after and
@@ -110,7 +115,8 @@ int wt_ensemble_step(wt_ensemble *h, double dt, int n_steps, int fused);
  * and results as n_steps calls of wt_ensemble_set_boundary(row k) + wt_ensemble_step(h, dt, 1, fused), bit for bit.
  * The rows are uploaded into a device buffer of the handle (grown on demand) and the call synchronises the stream before
  * its launches.  Afterwards the handle's boundary block is row n_steps-1 (wt_ensemble_get_boundary, wt_ensemble_rhs and
- * later wt_ensemble_step calls see it).  WT_E_STATE while plant I/O is on (the command path owns the boundary) or a
+ * later wt_ensemble_step calls see it, and a wt_ensemble_set_boundary of that row has nothing to upload).  WT_E_STATE
+ * while plant I/O is on (the command path owns the boundary) or a
  * disturbance program is set (its STEP and RAMP slots script events). */
 int wt_ensemble_step_scheduled(wt_ensemble *h, double dt, int n_steps, int fused, const double *bc_schedule);
 /* Trajectory recording.  From this call on, the state after every `every`-th outer step of later step calls (scheduled
@@ -259,6 +265,26 @@ int wt_ensemble_plc_read_inputs(wt_ensemble *h, uint16_t *words, uint8_t *update
 int wt_ensemble_plc_device(wt_ensemble *h, void **input_image, void **holding_image);
 /* current boundary block [WT_NB][N] (after the command path acted on it) */
 int wt_ensemble_get_boundary(wt_ensemble *h, double *bc);
+
+/* ---- what the handle holds, for callers that ask instead of remembering ----
+ * One host value per code, no device call and no synchronisation: switches give 0 or 1, capacities the size the
+ * download of that name fills (0 while its part is off).  WT_INFO_PROGRAM + WT_PROG_*: that program is set.
+ * WT_INFO_SCORE_BINS is 0 without a curve, as the fan is.  WT_INFO_WAVE_DIAG: the wave diagnostics are allocated (the
+ * next wt_ensemble_wave_diag call copies instead of switching on).  WT_INFO_BOUNDARY_UPLOADS: wt_ensemble_set_boundary
+ * calls that uploaded since creation.  An unknown code gives WT_E_ARG. */
+enum {
+    WT_INFO_PLANT_IO = 0,
+    WT_INFO_PROGRAM = 1,                  /* + WT_PROG_CONTROL .. WT_PROG_TREND: codes 1..8 */
+    WT_INFO_TRAIN = 9, WT_INFO_PIPE = 10,
+    WT_INFO_SENSOR_HISTORY = 11,          /* history_capacity of wt_ensemble_sensors_enable */
+    WT_INFO_DISTURB_HISTORY = 12,         /* history_capacity of wt_ensemble_disturb_set */
+    WT_INFO_SCORE_CURVE = 13, WT_INFO_SCORE_BINS = 14,   /* curve_capacity and bins of wt_ensemble_score_set */
+    WT_INFO_TREND_CAPACITY = 15,          /* capacity of wt_ensemble_trend_set */
+    WT_INFO_TRAIN_LENGTH = 16,            /* length of wt_ensemble_train_set */
+    WT_INFO_WAVE_DIAG = 17,
+    WT_INFO_BOUNDARY_UPLOADS = 18
+};
+int wt_ensemble_info(wt_ensemble *h, int what, int64_t *value);
 
 /* ---- per-reactor PI dosing programs on the device (closed loop without a host round trip) ----
  * The master side of the reference's loop (__main__.py:227-271) -- whatever a Modbus master computes from the input
@@ -555,6 +581,9 @@ int wt_ensemble_score_get(wt_ensemble *h, double *slot_state, double *t_prev);
 /* host [curve_capacity][WT_SCR_SLOTS][3] counts, [curve_capacity][WT_SCR_SLOTS][bins + 2] fan and n_steps = min(C, j), the
  * entries filled (any may be NULL; entries beyond n_steps are 0); WT_E_STATE while no program is set */
 int wt_ensemble_score_curve(wt_ensemble *h, int32_t *counts, int32_t *fan, int *n_steps);
+/* fan_lo and fan_hi of the set call, host [WT_SCR_SLOTS] each (either may be NULL; 0 without a fan); no device call;
+ * WT_E_STATE while no program is set */
+int wt_ensemble_score_fan_range(wt_ensemble *h, double *fan_lo, double *fan_hi);
 /* accumulators and curve back to their set-time values, j = 0, t_prev = the current ReactorState.time; the parameters
  * stay (scoring after a warm-up); WT_E_STATE while no program is set */
 int wt_ensemble_score_reset(wt_ensemble *h);
@@ -623,6 +652,8 @@ enum { WT_KR_LABEL_START = 0, WT_KR_LABEL_END = 1, WT_NKR = 2 };
 int wt_ensemble_detect_set(wt_ensemble *h, const double *params /* [WT_DET_SLOTS][WT_NK][N] */, const double *labels /* [WT_NKR][N] */);
 /* host [WT_DET_SLOTS][WT_NKS][N] slot state and [N] t_prev (either may be NULL); WT_E_STATE while no program is set */
 int wt_ensemble_detect_get(wt_ensemble *h, double *slot_state, double *t_prev);
+/* the label block of the set call, host [WT_NKR][N]; synchronises; WT_E_STATE while no program is set */
+int wt_ensemble_detect_labels(wt_ensemble *h, double *labels);
 /* slot state and t_prev back to their set-time values at the current loop time; parameters and labels stay (detection
  * after a warm-up); WT_E_STATE while no program is set */
 int wt_ensemble_detect_reset(wt_ensemble *h);
@@ -736,6 +767,10 @@ enum { WT_TRN_PH = 1, WT_TRN_CHLORINE = 2, WT_TRN_TEMPERATURE = 4 };
 int wt_ensemble_train_set(wt_ensemble *h, int length, const double *params /* [WT_NTR][N] or NULL */);
 /* the train length, the reactors per wavefront in force and the host [WT_NTRS][N] state (any may be NULL) */
 int wt_ensemble_train_get(wt_ensemble *h, int *length, int *per_wavefront, double *state);
+/* the parameter block in force, host [WT_NTR][N] (after a set with NULL: the default it stands for); a reactor that is
+ * not linked reads rows 0, whatever the set call gave there (nothing reads them).  No device call; WT_E_STATE while no
+ * program is set */
+int wt_ensemble_train_params(wt_ensemble *h, double *params);
 int wt_ensemble_train_clear(wt_ensemble *h);
 /* the checks wt_ensemble_train_set makes on its arguments, with no handle and no device: WT_OK or WT_E_ARG with that
  * call's message (also "n_reactors must be >= 1", "n_zones must be in 2..64").  Makes no HIP call. */
@@ -796,6 +831,10 @@ int wt_pipe_check(int64_t n_reactors, const double *train_params, const double *
 enum { WT_PROG_CONTROL = 0, WT_PROG_INJECT = 1, WT_PROG_ALARM = 2, WT_PROG_ACTUATOR = 3, WT_PROG_DISTURB = 4, WT_PROG_SCORE = 5,
        WT_PROG_DETECT = 6, WT_PROG_TREND = 7 };
 int wt_program_check(int program, const double *params, int64_t n_reactors);
+/* the parameter block of a set program as its set (enable, retune) call took it, bit for bit: host, the shape
+ * wt_program_check names for `program`; synchronises.  WT_E_STATE with the program's "not set" message while it is off,
+ * WT_E_ARG for an unknown program. */
+int wt_ensemble_program_params(wt_ensemble *h, int program, double *params);
 
 /* ---- reactor diagnostics (SURVEY.md section 8(f) NEXT-4): reductions over the zones of every reactor ----
  * out: host [WT_N_DIAG][N] doubles, rows

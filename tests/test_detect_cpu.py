@@ -326,7 +326,8 @@ def test_rates(native, wt):
     assert np.isnan(wt.DetectorState.from_block(st, np.zeros(3)).rates()[2]).all()         # no label known: no delay
 
 
-ENTRIES = ("wt_ensemble_detect_set", "wt_ensemble_detect_get", "wt_ensemble_detect_reset", "wt_ensemble_detect_clear", "wt_program_check")
+ENTRIES = ("wt_ensemble_detect_set", "wt_ensemble_detect_get", "wt_ensemble_detect_labels", "wt_ensemble_detect_reset",
+           "wt_ensemble_detect_clear", "wt_program_check")
 
 
 def test_detect_symbols_declared_and_exported(native, wt):

@@ -94,6 +94,26 @@ def test_library_exports_every_declared_symbol(native):
     assert lib.wt_abi_version() == 1
 
 
+def test_binding_table_is_the_header(native):
+    """``_native.SIGNATURES`` binds exactly the functions include/wtphys.h declares, each once: the table is a dict
+    display, so a name written twice would silently keep its last entry -- the source is read for that."""
+    hdr = open(os.path.join(ROOT, "include", "wtphys.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    declared = set(re.findall(r"\b(wt_[a-z_0-9]+)\s*\(", hdr))
+    assert set(native.SIGNATURES) == declared
+    src = open(native.__file__).read()
+    table = src[src.index("SIGNATURES = {"):src.index("\n}\n", src.index("SIGNATURES = {"))]
+    keys = re.findall(r'^\s*"(wt_[a-z_0-9]+)":', table, flags=re.M)
+    assert sorted(keys) == sorted(declared), "a name bound twice, or an entry the regex does not see"
+    # nothing binds a function outside the table
+    assert not re.findall(r"\.(?:argtypes|restype)\s*=", src.replace("fn.argtypes, fn.restype = ", ""))
+    L = native.lib()
+    for name, sig in native.SIGNATURES.items():
+        argtypes, restype = sig if isinstance(sig, tuple) else (sig, C.c_int)
+        fn = getattr(L, name)
+        assert list(fn.argtypes) == list(argtypes) and fn.restype is restype, name
+
+
 def test_program_check_without_a_device(native, wt):
     """wt_program_check runs the checks of each scan program's set call on the host: the off blocks pass, a bad block
     gets the set call's message (the builder raises it as a ValueError), a malformed call is refused."""

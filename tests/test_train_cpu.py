@@ -105,7 +105,7 @@ def test_builder_raises_the_library_text(wt):
 
 def test_symbols_constants_and_exports(native, wt, trn):
     header = open(os.path.join(ROOT, "include", "wtphys.h")).read()
-    entries = ("wt_ensemble_train_set", "wt_ensemble_train_get", "wt_ensemble_train_clear", "wt_train_check")
+    entries = ("wt_ensemble_train_set", "wt_ensemble_train_get", "wt_ensemble_train_params", "wt_ensemble_train_clear", "wt_train_check")
     plain = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
     assert sorted(n for n in set(re.findall(r"\b(wt_[a-z_0-9]+)\s*\(", plain)) if "train" in n) == sorted(entries)
     for name in entries:
