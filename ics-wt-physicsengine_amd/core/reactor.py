@@ -18,7 +18,7 @@ from typing import Dict, Iterable, List, Optional, Sequence, Union
 
 import numpy as np
 
-from . import _native, _program, actuator, alarm, control, detect, disturb, inject, params, score, train, trend
+from . import _native, _program, actuator, alarm, control, detect, disturb, inject, params, score, train, trend, wire
 
 logger = logging.getLogger(__name__)
 
@@ -781,6 +781,39 @@ class ReactorEnsemble:
     def clear_pipes(self) -> None:
         """Stop the pipe program: the linked rows stay as they are, the next feed is undelayed."""
         self._program_call(_native.lib().wt_ensemble_pipe_clear)
+
+    # -- the wire program: a stage's PLC inputs from another stage's instruments, on the device (wt_wir.hpp)
+    def set_wires(self, *wires: "wire.Wire") -> None:
+        """Wire input slots of stages to instruments of other stages of the same train (:class:`Wire`): at every PLC
+        scan, before everything else in the scan, a wired slot of a reactor's controller-side copy of the readings gets
+        the source instrument's reading and fault code of this outer step, so the injection program, the input image,
+        the PI loops, the IMAGE slots of alarms and detectors and the trend recorder's image tags see the remote value
+        -- the bits of a host master that routes ``sensor_readings()`` between calls of one scan interval.  FIELD
+        slots, ``sensor_readings()`` and the sensor history stay the reactor's own instrument; a source that did not
+        take the step reads NaN with fault 1.  Needs a train program and plant I/O; replaces any wire program;
+        :meth:`clear_wires`.  ``set_trains`` and ``clear_trains`` clear the wires."""
+        if not self.info(_native.WT_INFO_TRAIN):
+            self._program_call(_native.lib().wt_ensemble_wire_set, None)    # the library's refusal
+        blk = wire.wire_block(self.n_reactors, self.info(_native.WT_INFO_TRAIN_LENGTH), *wires)
+        self._program_call(_native.lib().wt_ensemble_wire_set, _native.dptr(blk))
+
+    def wire_state(self) -> "wire.WireState":
+        """Per reactor and input slot: the scans that delivered a source's reading and those that found the source
+        stopped (one synchronisation)."""
+        st = np.empty((wire.NSENS, wire.NWS, self.n_reactors), dtype=np.float64)
+        self._program_call(_native.lib().wt_ensemble_wire_get, None, _native.dptr(st))
+        return wire.WireState.from_block(st)
+
+    def wire_params(self) -> np.ndarray:
+        """The (7, 2, N) block of the wire program in force: per slot the source stage (-1: own instrument) and the
+        source sensor."""
+        blk = np.empty((wire.NSENS, wire.NW, self.n_reactors), dtype=np.float64)
+        self._program_call(_native.lib().wt_ensemble_wire_get, _native.dptr(blk), None)
+        return blk
+
+    def clear_wires(self) -> None:
+        """Stop the wire program: every slot is the reactor's own instrument again."""
+        self._program_call(_native.lib().wt_ensemble_wire_clear)
 
     def set_detectors(self, *detectors: "detect.Detector", attack=None) -> None:
         """Run a detector program of up to four :class:`Detector` slots at every PLC scan, inside the step call, last in

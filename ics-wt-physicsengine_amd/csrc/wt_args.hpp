@@ -1,5 +1,5 @@
 // wt_args.hpp -- the step kernel's argument block: StepArgs (filled by the host, wtphys.hip: make_args) with the
-// argument structs of the sensor suite, the plant I/O, the eight per-reactor programs and the train program inside it, the words of the
+// argument structs of the sensor suite, the plant I/O, the eight per-reactor programs, the train and the wire program inside it, the words of the
 // work queue's control block, which kernel instantiations carry which sections, and fresh(): how a section of a work
 // item re-reads what it needs from the kernel-argument segment.
 #pragma once
@@ -16,6 +16,7 @@
 #include "wt_dst.hpp"
 #include "wt_scr.hpp"
 #include "wt_trn.hpp"
+#include "wt_wir.hpp"
 
 namespace wt {
 
@@ -76,6 +77,7 @@ struct StepArgs {
     wtk::DetArgs det;    // per-reactor anomaly detector programs run at PLC scans (wt_ensemble_detect_*; det.on == 0: none)
     wtt::TrdArgs trd;    // per-reactor trend recorder programs run at PLC scans (wt_ensemble_trend_*; trd.on == 0: none)
     wtr::TrnArgs trn;    // the train program: stages feed their downstream after every outer step (wt_ensemble_train_*; trn.on == 0: none)
+    wtw::WirArgs wir;    // the wire program: a train's signal cables, routed at the head of a PLC scan (wt_ensemble_wire_*; wir.on == 0: none)
 };
 static_assert(sizeof(StepArgs) <= 4096, "the kernel-argument segment holds at most 4 KiB");
 constexpr int NB = 10;     // rows of a boundary block (WT_NB)
@@ -85,7 +87,8 @@ __host__ __device__ constexpr bool x_in_item(int LV) { return LV <= 5; }
 // wt_alm.hpp, wt_act.hpp, wt_dst.hpp, wt_scr.hpp, wt_det.hpp, wt_trd.hpp).  The n > 32 kernel has no register for them: every variant tried cost it 8 B of
 // scratch and 4 VGPR spills, with or without a program, so it compiles the sections out and wt_ensemble_inject_set,
 // _alarm_set, _actuator_set, _disturb_set, _score_set, _detect_set and _trend_set refuse ensembles of more than 32 zones.
-// The train program's feed (wt_trn.hpp) shares the disturbance section; a train of two stages needs n <= 32 anyway.
+// The train program's feed (wt_trn.hpp) shares the disturbance section; a train of two stages needs n <= 32 anyway,
+// and so does the wire program on top of it (wt_wir.hpp).
 __host__ __device__ constexpr bool prog_in_item(int LV) { return LV <= 5; }
 enum { Q_AVAIL = 0, Q_HEAD = 1, Q_TAIL = 2, Q_ERROR = 3, Q_TRACE = 4, Q_DONE = 5, Q_WORDS = 16 };
 

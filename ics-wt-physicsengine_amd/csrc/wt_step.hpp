@@ -680,6 +680,15 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
                 const int gs = b->first_step + step0 + k;
                 const bool scan = ((gs + 1) % b->sens.scan_every == 0) || (gs + 1 == b->call_steps);
                 __syncthreads();
+                // the wire program (wave-uniform flags), before everything else in the scan: wired slots of a scan lane's
+                // column get the readings of another stage's instruments.  One barrier inside, between gather and
+                // scatter; none after it -- what follows reads the lane's own column only (wt_wir.hpp).
+                if constexpr (prog_in_item(LV)) {
+                  if (scan && WT_RARE(fresh(pa)->wir.on)) {
+                    ArgPtr wp = fresh(pa);
+                    wtw::route(wp->wir, wp->trn.length, lane < R && io.stepped[lane], lane, rix, io);
+                  }
+                }
                 if (lane < R && io.stepped[lane]) {                       // one lane per reactor
                     const int64_t rr = rix[lane];
                     const double lt = b->sens.pack.loop_time[rr];

@@ -114,6 +114,8 @@ struct wt_ensemble {
     wtr::TrnArgs trn = {};
     std::vector<int32_t> trn_lk;
     int R0 = 0;
+    // The wire program on top of it (wt_wir.hpp): no switch of its own beyond wir.on, no host copy.
+    wtw::WirArgs wir = {};
     // optional per-launch HIP-event timing (bench.py roofline accounting)
     bool time_launches = false;
     std::vector<hipEvent_t> lt_pool;   // start/stop pairs
@@ -150,7 +152,7 @@ wt::StepArgs make_args(const wt_ensemble *h, double dt, int n_steps, int first_s
     a.trace = h->trace; a.trace_cap = h->trace_cap;
     a.kt = wt::default_ktab(); a.rt = wt::default_rtab();
     a.kt.dense_bias = h->knob_dense ? 1.0 : 0.0;
-    a.sens = h->sens; a.ctl = h->ctl; a.inj = h->inj; a.alm = h->alm; a.act = h->act; a.dst = h->dst; a.scr = h->scr; a.det = h->det; a.trd = h->trd; a.trn = h->trn;
+    a.sens = h->sens; a.ctl = h->ctl; a.inj = h->inj; a.alm = h->alm; a.act = h->act; a.dst = h->dst; a.scr = h->scr; a.det = h->det; a.trd = h->trd; a.trn = h->trn; a.wir = h->wir;
     // a full curve takes no more entries: the launches then carry no curve pointer at all
     const bool curve = h->scr.counts && h->scr_steps < h->scr.curve_cap;
     if (!curve) a.scr.counts = nullptr;
@@ -343,6 +345,14 @@ ArrayGroup pipe_arrays(wt_ensemble *h)
             [h] { h->trn.pipe.slots = 0; }};
 }
 
+// the wire program's arrays (wt_wir.hpp)
+ArrayGroup wire_arrays(wt_ensemble *h)
+{
+    const size_t N = (size_t)h->N;
+    return {"wire", &h->wir.on, {{(void **)&h->wir.src, sizeof(uint64_t) * N},
+                                 {(void **)&h->wir.st, sizeof(double) * wtw::ST_DOUBLES * N}}};
+}
+
 ArrayGroup trend_arrays(wt_ensemble *h)
 {
     const size_t N = (size_t)h->N;
@@ -521,6 +531,14 @@ int disturb_op(wt_ensemble *h, int op)
     return WT_OK;
 }
 
+// The wire program's restart (wt_wir.hpp): n_routed = n_lost = 0 in every slot (set, and set_state with a program
+// set); queued on the handle's stream.
+int wire_restart(wt_ensemble *h)
+{
+    HIP_TRY(hipMemsetAsync(h->wir.st, 0, sizeof(double) * wtw::ST_DOUBLES * (size_t)h->N, h->stream));
+    return WT_OK;
+}
+
 // The train program's host operations (wtr::host_op_kernel) on the handle's stream, not synchronised.
 int train_op(wt_ensemble *h, int op)
 {
@@ -666,6 +684,7 @@ int wt_ensemble_set_state(wt_ensemble *h, const double *pH, const double *Cl, co
     // a pipe program: a new state is a new plant -- every line full of it, the pipe state from the start
     if (h->trn.pipe.on) if (int rc = train_op(h, wtr::OP_PIPE_FILL)) return rc;
     if (h->trn.on) if (int rc = train_op(h, wtr::OP_FEED)) return rc;   // a train program: every link from the new state
+    if (h->wir.on) if (int rc = wire_restart(h)) return rc;             // a wire program: its counters from the start
     HIP_TRY(hipStreamSynchronize(h->stream));   // the caller's buffers are free on return
     h->have_state = true;
     return WT_OK;
@@ -1643,6 +1662,33 @@ template <class Linked> const char *pipe_error(int64_t N, const double *delay, L
 // the stream is idle: the lines go, the linked rows stay as they are
 void pipe_release(wt_ensemble *h) { release(pipe_arrays(h)); }
 
+// -- the wire program (wt_wir.hpp) on top of a train program
+static_assert(WT_NSENS == wts::NSENS && WT_NW == wtw::NW && WT_NWS == wtw::NWS && WT_W_STAGE == wtw::W_STAGE &&
+              WT_W_SENSOR == wtw::W_SENSOR && WT_WS_N_ROUTED == wtw::WS_N_ROUTED && WT_WS_N_LOST == wtw::WS_N_LOST,
+              "wire blocks of the C ABI");
+const char *k_wire_not_set = "no wire program is set (wt_ensemble_wire_set)";
+
+// The first refusal of a [WT_NSENS][WT_NW][N] block for trains of `length` stages: reactor by reactor, and at one
+// reactor rule by rule over its seven slots -- finite, stage, sensor -- so that which slot holds which fault does not
+// decide the message.
+const char *wire_error(int length, int64_t N, const double *p)
+{
+    const auto at = [&](int i, int k, int64_t r) { return p[((int64_t)i * WT_NW + k) * N + r]; };
+    for (int64_t r = 0; r < N; ++r) {
+        for (int i = 0; i < WT_NSENS; ++i)
+            if (!std::isfinite(at(i, WT_W_STAGE, r)) || !std::isfinite(at(i, WT_W_SENSOR, r))) return "wire parameters must be finite";
+        for (int i = 0; i < WT_NSENS; ++i)
+            if (!whole_in(at(i, WT_W_STAGE, r), -1, length - 1))
+                return "stage must be -1 (the reactor's own instrument) or a whole number in 0..length - 1 (a stage of the same train)";
+        for (int i = 0; i < WT_NSENS; ++i)
+            if (!whole_in(at(i, WT_W_SENSOR, r), 0, WT_NSENS - 1)) return "a wire's sensor must be a whole number in 0..6";
+    }
+    return nullptr;
+}
+
+// the stream is idle: the cables go, every slot is the reactor's own instrument again
+void wire_release(wt_ensemble *h) { release(wire_arrays(h)); }
+
 // before a disturbance program's arrays go (clear, a set over a program): the targeted rows back to the base
 int disturb_restore(wt_ensemble *h)
 {
@@ -1661,7 +1707,7 @@ int wt_ensemble_destroy(wt_ensemble *h)
     if (!h) return WT_OK;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (const auto arrays : {core_arrays, queue_arrays, sensor_arrays, plant_io_arrays, record_arrays, pipe_arrays, train_arrays}) release(arrays(h));
+    for (const auto arrays : {core_arrays, queue_arrays, sensor_arrays, plant_io_arrays, record_arrays, wire_arrays, pipe_arrays, train_arrays}) release(arrays(h));
     for (const Program &p : k_programs) release(p.arrays(h));
     free_and_null(h->trace); free_and_null(h->wave_diag); free_and_null(h->snap_dev); free_and_null(h->sched);
     free_and_null(h->diag_out);
@@ -1880,7 +1926,8 @@ int wt_ensemble_train_set(wt_ensemble *h, int length, const double *params)
     if (h->trn.on) {                            // set replaces a program: its rows go back to its base first
         if (int rc = train_op(h, wtr::OP_RESTORE)) return rc;
         if (int rc = sync_checked(h)) return rc;
-        pipe_release(h);                        // and its pipes go with it
+        pipe_release(h);                        // and its pipes and wires go with it
+        wire_release(h);
     }
     // whole trains per wavefront: the small-ensemble rule of wt_ensemble_create, counted in trains
     const int k = units_per_wavefront(h->device, N / length, 64 / h->n / length);
@@ -1928,6 +1975,7 @@ int wt_ensemble_train_clear(wt_ensemble *h)
     if (int rc = train_op(h, wtr::OP_RESTORE)) return rc;
     if (int rc = sync_checked(h)) return rc;
     pipe_release(h);
+    wire_release(h);
     release(train_arrays(h));
     return reshape(h, h->R0);
 }
@@ -2001,6 +2049,72 @@ int wt_ensemble_pipe_clear(wt_ensemble *h)
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still use the lines
     pipe_release(h);
+    return WT_OK;
+}
+
+int wt_wire_check(int length, int64_t n_reactors, const double *params)
+{
+    if (n_reactors < 1) return fail(WT_E_ARG, "n_reactors must be >= 1");
+    if (length < 2 || length > 32) return fail(WT_E_ARG, "length must be in 2..32 (the length of the train program)");
+    if (!params) return fail(WT_E_ARG, "NULL argument");
+    const char *msg = wire_error(length, n_reactors, params);
+    return msg ? fail(WT_E_ARG, msg) : WT_OK;
+}
+
+int wt_ensemble_wire_set(wt_ensemble *h, const double *params)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    if (!h->trn.on) return fail(WT_E_STATE, k_train_not_set);
+    if (!h->sens.plc_on) return fail(WT_E_STATE, "wires carry readings into the plant I/O scan: enable plant I/O first");
+    if (!params) return fail(WT_E_ARG, "params is NULL");
+    const int64_t N = h->N;
+    if (const char *msg = wire_error(h->trn.length, N, params)) return fail(WT_E_ARG, msg);
+    std::vector<uint64_t> src((size_t)N, 0);
+    for (int64_t r = 0; r < N; ++r)
+        for (int i = 0; i < WT_NSENS; ++i) {
+            const double g = params[((int64_t)i * WT_NW + WT_W_STAGE) * N + r];
+            if (g >= 0.0) src[(size_t)r] |= wtw::slot_word(i, (int)g, (int)params[((int64_t)i * WT_NW + WT_W_SENSOR) * N + r]);
+        }
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still use the old records
+    int rc = allocate(wire_arrays(h));          // (those of a running program are used again: set replaces it)
+    if (rc == WT_OK) {
+        hipError_t e = hipMemcpyAsync((void *)h->wir.src, src.data(), sizeof(uint64_t) * (size_t)N, hipMemcpyHostToDevice, h->stream);
+        if (e != hipSuccess) rc = fail(WT_E_HIP, hipGetErrorString(e));
+        if (rc == WT_OK) rc = wire_restart(h);
+        if (rc == WT_OK) rc = sync_checked(h);  // the host vector is freed on return
+    }
+    if (rc != WT_OK) { (void)hipStreamSynchronize(h->stream); wire_release(h); return rc; }
+    h->wir.on = 1;
+    return WT_OK;
+}
+
+int wt_ensemble_wire_get(wt_ensemble *h, double *params, double *state)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    if (!h->wir.on) return fail(WT_E_STATE, k_wire_not_set);
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t N = (size_t)h->N;
+    std::vector<uint64_t> src(params ? N : 0);
+    if (int rc = download(h, {{params ? src.data() : nullptr, h->wir.src, sizeof(uint64_t) * N}})) return rc;
+    if (params)
+        for (size_t r = 0; r < N; ++r)
+            for (int i = 0; i < WT_NSENS; ++i) {
+                const uint32_t c = (uint32_t)(src[r] >> (wtw::SLOT_BITS * i));
+                const bool wired = (c & wtw::WIRED) != 0;
+                params[((size_t)i * WT_NW + WT_W_STAGE) * N + r] = wired ? (double)((c >> 3) & 31u) : -1.0;
+                params[((size_t)i * WT_NW + WT_W_SENSOR) * N + r] = wired ? (double)(c & 7u) : (double)i;
+            }
+    return download_records(h, {{state, h->wir.st, wtw::ST_DOUBLES, WT_NSENS, WT_NWS}});
+}
+
+int wt_ensemble_wire_clear(wt_ensemble *h)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    if (!h->wir.on) return WT_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still use the records
+    wire_release(h);
     return WT_OK;
 }
 
@@ -2159,6 +2273,7 @@ int wt_ensemble_info(wt_ensemble *h, int what, int64_t *value)
     case WT_INFO_PLANT_IO: *value = h->sens.plc_on != 0; break;
     case WT_INFO_TRAIN: *value = h->trn.on != 0; break;
     case WT_INFO_PIPE: *value = h->trn.pipe.on != 0; break;
+    case WT_INFO_WIRE: *value = h->wir.on != 0; break;
     case WT_INFO_SENSOR_HISTORY: *value = h->sens.hist_cap; break;
     case WT_INFO_DISTURB_HISTORY: *value = h->dst.hist_cap; break;
     case WT_INFO_SCORE_CURVE: *value = h->scr.curve_cap; break;

@@ -282,7 +282,8 @@ enum {
     WT_INFO_TREND_CAPACITY = 15,          /* capacity of wt_ensemble_trend_set */
     WT_INFO_TRAIN_LENGTH = 16,            /* length of wt_ensemble_train_set */
     WT_INFO_WAVE_DIAG = 17,
-    WT_INFO_BOUNDARY_UPLOADS = 18
+    WT_INFO_BOUNDARY_UPLOADS = 18,
+    WT_INFO_WIRE = 19                     /* a wire program is set */
 };
 int wt_ensemble_info(wt_ensemble *h, int what, int64_t *value);
 
@@ -819,6 +820,59 @@ int wt_ensemble_pipe_clear(wt_ensemble *h);
  * [WT_NTR][N] parameter block of wt_ensemble_train_set: WT_OK or WT_E_ARG with that call's message (also
  * "n_reactors must be >= 1", "NULL argument").  Makes no HIP call. */
 int wt_pipe_check(int64_t n_reactors, const double *train_params, const double *delay);
+
+/* ---- the wire program: a stage's PLC inputs wired to another stage's instruments of the same train ----
+ * On top of a set train program, with plant I/O on: a wiring diagram of each train's signal cables.  Per reactor and
+ * input slot i (the seven sensors, WT_N_SENSORS order) the program says where the slot's reading comes from: the
+ * reactor's own instrument i (stage -1, the default), or sensor s of stage g of the same train (g in 0..length - 1;
+ * g may be the reactor's own stage with another s).
+ * Parameters [WT_NSENS][WT_NW][N]: stage (-1, or a whole number 0..length - 1), sensor (a whole number 0..6; not read
+ * where stage is -1, but checked).
+ * Where it acts.  At a PLC scan, before everything else in the scan: for every reactor that took the outer step, each
+ * wired slot of the reactor's controller-side copy of the readings is replaced by the source instrument's reading and
+ * fault code of this outer step.  The source is always the instrument's own output, what the sensor suite left before
+ * any wire or tamper: wires do not chain (a source slot that is itself wired still gives its own instrument), and a
+ * spoof in the source stage's own image does not travel down the wire.
+ * What sees the wired value: everything downstream in the scan, in the existing order -- the receiving reactor's
+ * injection program (a spoof of the remote analyser is an injection at the receiver's slot), update_modbus_inputs
+ * (the receiver's input registers show the remote value), the PI loops, the IMAGE slots of alarms and detectors, the
+ * trend recorder's image tags.
+ * What does not change: FIELD slots of alarms, detectors and trends, wt_ensemble_sensors_get and the sensor history
+ * stay the reactor's own instrument.
+ * A source that did not step.  If the source reactor did not take the outer step (frozen, or ended T_RANGE_POST), the
+ * slot reads NaN with fault code 1 (open circuit), a dead current loop: PI loops on it hold, its image word reads 0.0
+ * and the system status reads faulted.
+ * State [WT_NSENS][WT_NWS][N]: n_routed (scans that delivered the source's reading), n_lost (scans that found the
+ * source stopped); both 0 at set, and again after wt_ensemble_set_state; 0 in slots that are not wired.
+ * Definition (the fused call gives its bits): on a handle without the program, calls of one scan interval; after each
+ * the host routes wt_ensemble_sensors_get as above and runs the scan programs on the result as a host master.
+ * wt_ensemble_wire_set replaces any wire program.  Refused with WT_E_STATE:
+ *   "no train program is set (wt_ensemble_train_set)"
+ *   "wires carry readings into the plant I/O scan: enable plant I/O first"
+ * and with WT_E_ARG:
+ *   "wire parameters must be finite"
+ *   "stage must be -1 (the reactor's own instrument) or a whole number in 0..length - 1 (a stage of the same train)"
+ *   "a wire's sensor must be a whole number in 0..6"
+ * in this order: reactor by reactor, and at one reactor rule by rule over its seven slots, so the message of a block
+ * with several faults does not depend on the slots they sit in.  wt_ensemble_wire_clear turns the program off: every
+ * slot is the reactor's own instrument again; no effect while none is set.  wt_ensemble_train_clear, and a
+ * wt_ensemble_train_set over a program, clear the wires first.  wt_ensemble_wire_get gives WT_E_STATE, "no wire program
+ * is set (wt_ensemble_wire_set)", while none is.  The program takes no code of wt_program_check: wt_wire_check is its
+ * check.  Not modelled: wires between trains or without a train program, signal lag or dead time on the wire (the
+ * sensors' own sample lines exist already), FIELD slots that follow a wire, and the n > 32 kernel, where no train
+ * fits.  All calls synchronise. */
+#define WT_NSENS WT_N_SENSORS
+enum { WT_W_STAGE = 0, WT_W_SENSOR = 1, WT_NW = 2 };
+enum { WT_WS_N_ROUTED = 0, WT_WS_N_LOST = 1, WT_NWS = 2 };
+int wt_ensemble_wire_set(wt_ensemble *h, const double *params /* [WT_NSENS][WT_NW][N] */);
+/* the program in force, host [WT_NSENS][WT_NW][N] (sensor reads i where stage is -1), and the host
+ * [WT_NSENS][WT_NWS][N] state (either may be NULL) */
+int wt_ensemble_wire_get(wt_ensemble *h, double *params, double *state);
+int wt_ensemble_wire_clear(wt_ensemble *h);
+/* the checks wt_ensemble_wire_set makes on params for trains of `length` stages, with no handle and no device: WT_OK
+ * or WT_E_ARG with that call's message (also "n_reactors must be >= 1", "length must be in 2..32 (the length of the
+ * train program)", "NULL argument").  Makes no HIP call. */
+int wt_wire_check(int length, int64_t n_reactors, const double *params);
 
 /* ---- the parameter checks of the scan programs, the disturbance and the score program, without a handle or a device ----
  * params: host, the block the program's set or enable call takes, for n_reactors reactors (WT_PROG_CONTROL:
