@@ -937,6 +937,78 @@ class ReactorEnsemble:
         self._program_call(_native.lib().wt_ensemble_score_clear)
 
     # -- diagnostics (NEXT-4)
+    # -- checkpoint, copy and rewind of everything the handle holds
+    def checkpoint(self) -> bytes:
+        """Everything that decides the next bits of the run -- state, sensors, register images, records, every
+        program with its state and stores, trains, pipes, wires, placement and schedule -- as one blob
+        (include/wtphys.h describes it).  Developer instrumentation is not part of it."""
+        n = C.c_int64(0)
+        _native.check(_native.lib().wt_ensemble_checkpoint_size(self._h, C.byref(n)))
+        buf = np.empty(n.value, dtype=np.uint8)
+        self._program_call(_native.lib().wt_ensemble_checkpoint_save, buf.ctypes.data_as(C.c_void_p), n.value)
+        return buf.tobytes()
+
+    def restore(self, blob) -> None:
+        """Back to a :meth:`checkpoint` of an ensemble with the same reactors: the blob's programs and capacities
+        replace whatever is set here.  A refused blob (``ValueError``) changes nothing."""
+        buf = np.frombuffer(bytes(blob), dtype=np.uint8)
+        self._program_call(_native.lib().wt_ensemble_checkpoint_load, buf.ctypes.data_as(C.c_void_p), buf.size)
+
+    def clone(self) -> "ReactorEnsemble":
+        """A second ensemble on the same device that continues exactly as this one would; the two share nothing."""
+        other = ReactorEnsemble(self.columns, n_zones=self.n_zones, device=self.device, validate=False)
+        try:
+            other._program_call(_native.lib().wt_ensemble_copy, self._h)
+        except Exception:
+            other.close()
+            raise
+        return other
+
+    def mark(self) -> None:
+        """Keep a checkpoint in device memory inside the ensemble (replaces an earlier mark)."""
+        self._program_call(_native.lib().wt_ensemble_mark)
+
+    def rewind(self) -> None:
+        """Back to the :meth:`mark`, any number of times: programs and capacities set since go, the marked ones return."""
+        self._program_call(_native.lib().wt_ensemble_rewind)
+
+    def unmark(self) -> None:
+        self._program_call(_native.lib().wt_ensemble_unmark)
+
+    _FILE_COLUMN = "column_"
+
+    def save(self, path) -> None:
+        """One ``.npz`` file (no pickle): the reactor columns, ``n_zones`` and the :meth:`checkpoint` blob."""
+        entries = {self._FILE_COLUMN + k: np.asarray(v) for k, v in self.columns.items()}
+        np.savez(path, n_zones=np.int64(self.n_zones), checkpoint=np.frombuffer(self.checkpoint(), dtype=np.uint8), **entries)
+
+    @classmethod
+    def load(cls, path, device: int = 0) -> "ReactorEnsemble":
+        """The ensemble a :meth:`save` file describes, on ``device``.  A file without the expected entries is a
+        ``ValueError`` that names the entry."""
+        with np.load(path, allow_pickle=False) as f:
+            for name in ("n_zones", "checkpoint"):
+                if name not in f.files:
+                    raise ValueError(f"{path}: no '{name}' entry: not a ReactorEnsemble.save file")
+            n_zones, blob = f["n_zones"], f["checkpoint"]
+            cols = {k[len(cls._FILE_COLUMN):]: f[k] for k in f.files if k.startswith(cls._FILE_COLUMN)}
+        if n_zones.shape != () or n_zones.dtype.kind != "i":
+            raise ValueError(f"{path}: 'n_zones' must be one integer")
+        if blob.ndim != 1 or blob.dtype != np.uint8:
+            raise ValueError(f"{path}: 'checkpoint' must be a one-dimensional uint8 array")
+        missing = [name for name in _CFG_FIELDS if name != "n_zones" and name not in cols]
+        if missing:
+            raise ValueError(f"{path}: no '{cls._FILE_COLUMN}{missing[0]}' entry: not a ReactorEnsemble.save file")
+        if len({v.shape for v in cols.values()}) != 1 or next(iter(cols.values())).ndim != 1:
+            raise ValueError(f"{path}: the '{cls._FILE_COLUMN}*' entries must be one-dimensional and of one length")
+        ens = cls(cols, n_zones=int(n_zones), device=device, validate=False)
+        try:
+            ens.restore(blob.tobytes())
+        except Exception:
+            ens.close()
+            raise
+        return ens
+
     DIAGNOSTIC_FIELDS = ("total_chlorine_mg", "total_H_mol", "total_OH_mol", "charge_balance_mol", "thermal_energy_kJ",
                          "pH_CV", "pH_segregation", "chlorine_CV", "chlorine_segregation", "thermocline_depth_m") + tuple(
         f"{p}_{k}" for p in ("pH", "chlorine", "temperature")

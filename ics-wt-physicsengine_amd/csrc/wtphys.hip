@@ -4,6 +4,7 @@
 #include "wt_device.hpp"
 #include "wt_diag.hpp"
 #include "wt_place.hpp"
+#include "wt_ckp.hpp"
 #include "../../include/wtphys.h"
 
 #include <cmath>
@@ -42,12 +43,15 @@ int levels_for(int n)
 
 } // namespace
 
+struct wt_mark;
+
 struct wt_ensemble {
     int64_t N = 0;
     int n = 0, R = 0, device = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
     double *par = nullptr, *bc = nullptr;
+    std::vector<double> par_sent;   // the constants as create uploaded them: what a checkpoint load or a copy compares
     double *pH = nullptr, *Cl = nullptr, *T = nullptr, *time = nullptr, *flow = nullptr;
     double *dH = nullptr, *dRho = nullptr, *dK = nullptr;
     uint32_t *status = nullptr;
@@ -80,7 +84,8 @@ struct wt_ensemble {
     // developer knobs (tools/), read from the environment once at creation: WT_Q_ITEM (outer steps per work item),
     // WT_PLACE_MIN (history before a re-deal), WT_Q_TICKETS (forces the launch split), WT_FULL_WAVES,
     // WT_DENSE_COUPLING (every solve takes the general path: the test that the fast paths give the same bits)
-    int knob_item = 0; int64_t knob_place_min = 0, knob_tickets = 0; int knob_dense = 0;
+    // WT_CKP_MEMCPY (a checkpoint's device-to-device copies as one hipMemcpyAsync per array, not the table kernel)
+    int knob_item = 0; int64_t knob_place_min = 0, knob_tickets = 0; int knob_dense = 0; int knob_memcpy = 0;
     // sticky record of a launch that did not advance every group (device word + pinned host mirror)
     int32_t *q_sticky = nullptr;   // device view of err_host (host-coherent pinned memory: the check kernel writes it in place)
     // one contiguous snapshot of a small ensemble: packed on the device, one copy into pinned memory
@@ -131,6 +136,7 @@ struct wt_ensemble {
         int every = 1, cap = 0;
         int64_t steps = 0;                                   // outer steps since wt_ensemble_record
     } rec;
+    wt_mark *mark = nullptr;      // the device-resident checkpoint of wt_ensemble_mark
 };
 
 namespace {
@@ -628,6 +634,8 @@ int wt_ensemble_create(int64_t n_reactors, int n_zones, int device, const double
     if (const char *e = getenv("WT_PLACE_MIN")) h->knob_place_min = atoll(e);
     if (const char *e = getenv("WT_Q_TICKETS")) h->knob_tickets = atoll(e);
     if (const char *e = getenv("WT_DENSE_COUPLING")) h->knob_dense = atoi(e) != 0;
+    if (const char *e = getenv("WT_CKP_MEMCPY")) h->knob_memcpy = atoi(e) != 0;
+    h->par_sent.assign(par, par + (size_t)WT_NP * N);
     h->sens.N = h->sens.cmd.N = h->N;
     h->sens.cmd.bc = h->bc;
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { cleanup(); return fail(WT_E_HIP, "hipStreamCreate failed"); }
@@ -1698,6 +1706,420 @@ int disturb_restore(wt_ensemble *h)
     return sync_checked(h);
 }
 
+// ---- checkpoint, copy and rewind: one table of the handle's parts, which save, load, copy, mark,
+// rewind and destroy all walk.  A part is its ArrayGroup function, how many of the group's trailing arrays are scratch,
+// and its host scalars, field by field.  No pointer is a scalar: after a load the pointers are the destination's own
+// allocations, and the aliases (sens.cmd.hr) are derived again by restore().
+
+enum ScalarKind { S_I32, S_U32, S_I64, S_BOOL, S_F64 };
+
+// a host field of a part; shape: a switch or a capacity that sizes arrays (two handles with equal shape scalars have
+// arrays of equal sizes, which is what the rewind's fast path needs)
+struct Scalar { ScalarKind kind; void *p; bool shape; };
+
+int64_t scalar_get(const Scalar &s)
+{
+    switch (s.kind) {
+    case S_I32: return *(const int32_t *)s.p;
+    case S_U32: return *(const uint32_t *)s.p;
+    case S_BOOL: return *(const bool *)s.p ? 1 : 0;
+    default: { int64_t v; std::memcpy(&v, s.p, sizeof v); return v; }      // S_I64; S_F64: the double's bits
+    }
+}
+
+void scalar_put(const Scalar &s, int64_t v)
+{
+    switch (s.kind) {
+    case S_I32: *(int32_t *)s.p = (int32_t)v; break;
+    case S_U32: *(uint32_t *)s.p = (uint32_t)v; break;
+    case S_BOOL: *(bool *)s.p = v != 0; break;
+    default: std::memcpy(s.p, &v, sizeof v); break;
+    }
+}
+
+using Scalars = std::vector<Scalar>;
+
+struct Part {
+    const char *tag;                                    // four characters, the part's mark in a blob
+    ArrayGroup (*arrays)(wt_ensemble *);
+    int scratch;                                        // trailing arrays of the group that no checkpoint holds
+    void (*scalars)(wt_ensemble *, Scalars &);          // nullptr: none
+    bool (*present)(const wt_ensemble *);               // nullptr: the group's switch, or always without one
+};
+
+void switch_only(int *on, Scalars &s) { s.push_back({S_I32, on, true}); }
+
+const Part k_parts[] = {
+    // place_hist and q_ctrl are scratch; perm, cost and cost_steps travel, so a restored run re-deals when the original would
+    {"CORE", core_arrays, 2, [](wt_ensemble *h, Scalars &s) {
+         s.insert(s.end(), {{S_BOOL, &h->have_state, false}, {S_BOOL, &h->have_bc, false}, {S_I32, &h->placement, false},
+                            {S_I64, &h->cost_steps, false}, {S_I32, &h->sched_mode, false}, {S_I32, &h->n_sub, false},
+                            {S_I32, &h->chunk_steps, false}, {S_I32, &h->step_limit, false}}); }, nullptr},
+    {"QUEU", queue_arrays, 2, nullptr, nullptr},
+    {"SENS", sensor_arrays, 0, [](wt_ensemble *h, Scalars &s) {
+         s.insert(s.end(), {{S_I32, &h->sens.on, true}, {S_I32, &h->sens.hist_cap, true}, {S_U32, &h->sens.seed_lo, false},
+                            {S_U32, &h->sens.seed_hi, false}, {S_I64, &h->sens.reactor_base, false}}); }, nullptr},
+    {"PLIO", plant_io_arrays, 0, [](wt_ensemble *h, Scalars &s) { switch_only(&h->sens.plc_on, s); }, nullptr},
+    {"RECD", record_arrays, 0, [](wt_ensemble *h, Scalars &s) {
+         s.insert(s.end(), {{S_I32, &h->rec.every, false}, {S_I32, &h->rec.cap, true}, {S_I64, &h->rec.steps, false}}); },
+     [](const wt_ensemble *h) { return h->rec.cap > 0; }},
+    {"CTRL", control_arrays, 0, [](wt_ensemble *h, Scalars &s) { switch_only(&h->ctl.on, s); }, nullptr},
+    {"INJC", inject_arrays, 0, [](wt_ensemble *h, Scalars &s) { switch_only(&h->inj.on, s); }, nullptr},
+    {"ALRM", alarm_arrays, 0, [](wt_ensemble *h, Scalars &s) { switch_only(&h->alm.on, s); }, nullptr},
+    {"ACTU", actuator_arrays, 0, [](wt_ensemble *h, Scalars &s) { switch_only(&h->act.on, s); }, nullptr},
+    {"DSTB", disturb_arrays, 0, [](wt_ensemble *h, Scalars &s) {
+         s.insert(s.end(), {{S_I32, &h->dst.on, true}, {S_I32, &h->dst.hist_cap, true}, {S_U32, &h->dst.seed_lo, false},
+                            {S_U32, &h->dst.seed_hi, false}, {S_I64, &h->dst.reactor_base, false}}); }, nullptr},
+    {"SCOR", score_arrays, 0, [](wt_ensemble *h, Scalars &s) {
+         s.insert(s.end(), {{S_I32, &h->scr.on, true}, {S_I32, &h->scr.curve_cap, true}, {S_I32, &h->scr.bins, true},
+                            {S_I64, &h->scr_steps, false}});
+         for (int k = 0; k < wtsc::SLOTS; ++k)
+             s.insert(s.end(), {{S_F64, &h->scr.fan_lo[k], false}, {S_F64, &h->scr.fan_hi[k], false}, {S_F64, &h->scr.fan_scale[k], false}}); },
+     nullptr},
+    {"DETC", detect_arrays, 0, [](wt_ensemble *h, Scalars &s) { switch_only(&h->det.on, s); }, nullptr},
+    {"TRAN", train_arrays, 0, [](wt_ensemble *h, Scalars &s) {
+         s.insert(s.end(), {{S_I32, &h->trn.on, true}, {S_I32, &h->trn.length, true}}); }, nullptr},
+    {"PIPE", pipe_arrays, 0, [](wt_ensemble *h, Scalars &s) {
+         s.insert(s.end(), {{S_I32, &h->trn.pipe.on, true}, {S_I32, &h->trn.pipe.slots, true}}); }, nullptr},
+    {"WIRE", wire_arrays, 0, [](wt_ensemble *h, Scalars &s) { switch_only(&h->wir.on, s); }, nullptr},
+    {"TRND", trend_arrays, 0, [](wt_ensemble *h, Scalars &s) {
+         s.insert(s.end(), {{S_I32, &h->trd.on, true}, {S_I64, &h->trd.cap, true}, {S_I32, &h->trd.wrap, false}}); }, nullptr},
+};
+constexpr int N_PARTS = (int)(sizeof k_parts / sizeof *k_parts);
+constexpr int PART_CORE = 0, PART_QUEUE = 1, PART_TRAIN = 12;   // core's first array is par, the train's first array lk
+static_assert(N_PARTS == 16, "every *_arrays function of this file has one entry in k_parts (tests/test_checkpoint_cpu.py counts them)");
+
+// a part of a handle as a checkpoint sees it: its scalars, whether it is on, and then its payload arrays
+struct PartView { Scalars scalars; bool on; std::vector<std::pair<void **, size_t>> payload; };
+
+PartView view(const Part &p, wt_ensemble *h)
+{
+    PartView v;
+    if (p.scalars) p.scalars(h, v.scalars);
+    const ArrayGroup g = p.arrays(h);
+    v.on = p.present ? p.present(h) : (g.on ? *g.on != 0 : true);
+    if (v.on) v.payload.assign(g.arrays.begin(), g.arrays.end() - p.scratch);
+    return v;
+}
+
+uint32_t tag_word(const char *t) { uint32_t w; std::memcpy(&w, t, 4); return w; }
+size_t pad8(size_t b) { return (b + 7) & ~(size_t)7; }
+
+// The layout fingerprint: the table as a blob shows it -- tags, scalar kinds, array counts -- and the byte count of every
+// payload array of a handle of one reactor with two zones and every capacity 1, which is the element size times the
+// record constant (*_DOUBLES, SLOTS, NSENS, RING, ...) that sizes the array.
+uint64_t layout_fingerprint()
+{
+    static const uint64_t value = [] {
+        wt_ensemble u;
+        u.N = 1; u.n = 2;
+        uint64_t f = wtck::fnv1a_u64(WT_CKP_FORMAT, wtck::FNV_BASIS);
+        for (const Part &p : k_parts) {
+            Scalars sc;
+            if (p.scalars) p.scalars(&u, sc);
+            for (const Scalar &s : sc) if (s.shape) scalar_put(s, 1);
+        }
+        for (const Part &p : k_parts) {
+            const PartView v = view(p, &u);
+            f = wtck::fnv1a_u64(tag_word(p.tag), f);
+            f = wtck::fnv1a_u64(v.scalars.size(), f);
+            for (const Scalar &s : v.scalars) f = wtck::fnv1a_u64((uint64_t)s.kind * 2 + s.shape, f);
+            f = wtck::fnv1a_u64(v.payload.size(), f);
+            for (const auto &a : v.payload) f = wtck::fnv1a_u64(a.second, f);
+        }
+        return f;
+    }();
+    return value;
+}
+
+std::vector<int64_t> scalars_of(wt_ensemble *h)
+{
+    std::vector<int64_t> out;
+    for (const Part &p : k_parts) {
+        Scalars sc;
+        if (p.scalars) p.scalars(h, sc);
+        for (const Scalar &s : sc) out.push_back(scalar_get(s));
+    }
+    return out;
+}
+
+void apply_scalars(wt_ensemble *h, const std::vector<int64_t> &values)
+{
+    size_t i = 0;
+    for (const Part &p : k_parts) {
+        Scalars sc;
+        if (p.scalars) p.scalars(h, sc);
+        for (const Scalar &s : sc) scalar_put(s, values[i++]);
+    }
+}
+
+// the switches and capacities of `values` are the handle's
+bool same_shape(wt_ensemble *h, const std::vector<int64_t> &values)
+{
+    size_t i = 0;
+    for (const Part &p : k_parts) {
+        Scalars sc;
+        if (p.scalars) p.scalars(h, sc);
+        for (const Scalar &s : sc) { if (s.shape && scalar_get(s) != values[i]) return false; ++i; }
+    }
+    return true;
+}
+
+int64_t checkpoint_bytes(wt_ensemble *h)
+{
+    size_t total = WT_CKP_HEADER_BYTES;
+    for (const Part &p : k_parts) {
+        const PartView v = view(p, h);
+        total += 16 + 8 * v.scalars.size();
+        for (const auto &a : v.payload) total += 8 + pad8(a.second);
+    }
+    return (int64_t)total;
+}
+
+// Where a checkpoint's payload comes from: a blob on the host, another handle's arrays, or a mark's device memory.
+struct Source {
+    std::vector<int64_t> scalars;                                       // every part's, in table order
+    std::vector<std::vector<std::pair<const void *, size_t>>> arrays;   // per part its payload arrays (none: the part is off)
+    std::vector<int32_t> trn_lk;
+    bool device = false;                                                // the arrays are device memory of the handle's device
+};
+
+Source source_of(wt_ensemble *h)
+{
+    Source s;
+    s.scalars = scalars_of(h);
+    for (const Part &p : k_parts) {
+        const PartView v = view(p, h);
+        s.arrays.emplace_back();
+        for (const auto &a : v.payload) s.arrays.back().push_back({*a.first, a.second});
+    }
+    s.trn_lk = h->trn_lk;
+    s.device = true;
+    return s;
+}
+
+// A refusal of the configuration a blob declares: the rules the set calls enforce, on a host-only handle.
+const char *config_error(wt_ensemble *u)
+{
+    for (const Part &p : k_parts) {
+        Scalars sc;
+        if (p.scalars) p.scalars(u, sc);
+        for (const Scalar &s : sc) {
+            const int64_t v = scalar_get(s);
+            if (s.shape && (v < 0 || v > 0x7fffffff)) return "range";
+            if (s.kind == S_BOOL && v != 0 && v != 1) return "range";
+        }
+    }
+    const bool programs = u->ctl.on | u->inj.on | u->alm.on | u->act.on | u->det.on | u->trd.on;
+    const bool zoned = u->inj.on | u->alm.on | u->act.on | u->dst.on | u->scr.on | u->det.on | u->trd.on;
+    const auto flag = [](int v) { return v == 0 || v == 1; };
+    if (!flag(u->sens.on) || !flag(u->sens.plc_on) || !flag(u->ctl.on) || !flag(u->inj.on) || !flag(u->alm.on) || !flag(u->act.on) ||
+        !flag(u->dst.on) || !flag(u->scr.on) || !flag(u->det.on) || !flag(u->trn.on) || !flag(u->trn.pipe.on) || !flag(u->wir.on) ||
+        !flag(u->trd.on) || !flag(u->trd.wrap))
+        return "range";
+    if (u->placement != WT_PLACE_IDENTITY && u->placement != WT_PLACE_ADAPTIVE) return "range";
+    if (u->sched_mode != WT_SCHED_STREAMS && u->sched_mode != WT_SCHED_QUEUE) return "range";
+    if (u->n_sub < 1 || u->n_sub > WT_MAX_STREAMS || u->chunk_steps < 0 || u->step_limit < 0 || u->cost_steps < 0) return "range";
+    if (u->rec.every < 1 || u->rec.steps < 0 || u->scr_steps < 0) return "range";
+    if ((u->sens.plc_on && !u->sens.on) || (programs && !u->sens.plc_on) || (zoned && !wt::prog_in_item(levels_for(u->n)))) return "range";
+    if (!u->sens.on && u->sens.hist_cap) return "range";
+    if (!u->dst.on && u->dst.hist_cap) return "range";
+    if ((!u->scr.on && (u->scr.curve_cap | u->scr.bins)) || u->scr.bins > wtsc::MAX_BINS || (!u->scr.curve_cap && u->scr.bins)) return "range";
+    if (u->trd.on ? u->trd.cap < 1 : u->trd.cap != 0) return "range";
+    if (u->trn.on ? (u->trn.length < 2 || u->trn.length > 64 / u->n || u->N % u->trn.length != 0) : u->trn.length != 0) return "range";
+    if (u->trn.pipe.on ? (!u->trn.on || u->trn.pipe.slots < 1 || u->trn.pipe.slots > WT_PIPE_MAX_DELAY + 1) : u->trn.pipe.slots != 0) return "range";
+    if (u->wir.on && (!u->trn.on || !u->sens.plc_on)) return "range";
+    return nullptr;
+}
+
+// Validates a blob on the host, every check of wt_checkpoint_check in its order, and describes it as a Source.  `into`:
+// the handle a load is for, whose N and n the blob's must be (checked where N and n are, before the arrays).
+int parse_blob(const void *blob, int64_t bytes, int64_t *N_out, int *n_out, Source *out, const wt_ensemble *into = nullptr)
+{
+    static_assert(sizeof(wt_checkpoint_header) == WT_CKP_HEADER_BYTES, "the header is 64 bytes without padding");
+    if (!blob) return fail(WT_E_ARG, "checkpoint: NULL argument");
+    if (bytes < WT_CKP_HEADER_BYTES) return fail(WT_E_ARG, "checkpoint: shorter than its header");
+    wt_checkpoint_header hd;
+    std::memcpy(&hd, blob, sizeof hd);
+    if (std::memcmp(hd.magic, WT_CKP_MAGIC, 4) != 0) return fail(WT_E_ARG, "checkpoint: bad magic");
+    if (hd.format != WT_CKP_FORMAT) return fail(WT_E_ARG, "checkpoint: unknown format version");
+    if (hd.bytes != bytes) return fail(WT_E_ARG, "checkpoint: the header's byte count is not the blob's length");
+    if (hd.layout != layout_fingerprint() || hd.abi != WT_ABI_VERSION || hd.n_parts != N_PARTS)
+        return fail(WT_E_ARG, "checkpoint: the layout fingerprint is not this library's");
+    const unsigned char *b = (const unsigned char *)blob;
+    if (hd.checksum != wtck::fnv1a(b + WT_CKP_HEADER_BYTES, (size_t)bytes - WT_CKP_HEADER_BYTES))
+        return fail(WT_E_ARG, "checkpoint: checksum mismatch");
+    if (hd.n_reactors <= 0) return fail(WT_E_ARG, "checkpoint: n_reactors must be positive");
+    if (hd.n_zones < 2 || hd.n_zones > WT_MAX_ZONES) return fail(WT_E_ARG, "checkpoint: n_zones must be in 2..64");
+    if (into && (hd.n_reactors != into->N || (int)hd.n_zones != into->n))
+        return fail(WT_E_ARG, "checkpoint_load: the checkpoint's n_reactors or n_zones differ from the handle's");
+    const char *k_arrays = "checkpoint: a part's arrays do not match the capacities it declares";
+    wt_ensemble u;                          // host only: holds the blob's scalars, sizes its arrays
+    u.N = hd.n_reactors; u.n = (int)hd.n_zones;
+    Source src;
+    size_t at = WT_CKP_HEADER_BYTES;
+    const size_t end = (size_t)bytes;
+    const auto word = [&](size_t o) { uint32_t w; std::memcpy(&w, b + o, 4); return w; };
+    for (const Part &p : k_parts) {         // the structure first: tags, counts, lengths that stay inside the blob
+        Scalars sc;
+        if (p.scalars) p.scalars(&u, sc);
+        if (end - at < 8 || word(at) != tag_word(p.tag) || word(at + 4) != sc.size()) return fail(WT_E_ARG, k_arrays);
+        at += 8;
+        if (end - at < 8 * sc.size() + 8) return fail(WT_E_ARG, k_arrays);
+        for (const Scalar &s : sc) {
+            int64_t v; std::memcpy(&v, b + at, 8); at += 8;
+            src.scalars.push_back(v);
+            scalar_put(s, v);
+        }
+        const uint32_t count = word(at);
+        if (word(at + 4) != 0) return fail(WT_E_ARG, k_arrays);
+        at += 8;
+        src.arrays.emplace_back();
+        for (uint32_t i = 0; i < count; ++i) {
+            int64_t len;
+            if (end - at < 8) return fail(WT_E_ARG, k_arrays);
+            std::memcpy(&len, b + at, 8); at += 8;
+            if (len < 0 || (uint64_t)len > end - at || pad8((size_t)len) > end - at) return fail(WT_E_ARG, k_arrays);
+            src.arrays.back().push_back({b + at, (size_t)len});
+            at += pad8((size_t)len);
+        }
+    }
+    if (at != end) return fail(WT_E_ARG, k_arrays);
+    if (config_error(&u)) return fail(WT_E_ARG, "checkpoint: a part's switches or capacities are out of range");
+    for (int i = 0; i < N_PARTS; ++i) {     // then every array's byte count against the capacities now in `u`
+        const PartView v = view(k_parts[i], &u);
+        if (v.payload.size() != src.arrays[(size_t)i].size()) return fail(WT_E_ARG, k_arrays);
+        for (size_t k = 0; k < v.payload.size(); ++k)
+            if (v.payload[k].second != src.arrays[(size_t)i][k].second) return fail(WT_E_ARG, k_arrays);
+    }
+    if (u.trn.on) {
+        const int32_t *lk = (const int32_t *)src.arrays[PART_TRAIN][0].first;
+        src.trn_lk.assign(lk, lk + u.N);
+    }
+    if (N_out) *N_out = hd.n_reactors;
+    if (n_out) *n_out = (int)hd.n_zones;
+    if (out) *out = std::move(src);
+    return WT_OK;
+}
+
+// Device-to-device copies on `stream`: the table kernel, as many launches as 128-entry tables are needed, or (memcpy)
+// one hipMemcpyAsync per array.  Zero-byte copies are skipped here.
+int device_copies(const std::vector<Copy> &copies, hipStream_t stream, bool memcpy_each)
+{
+    if (memcpy_each) {
+        for (const Copy &c : copies)
+            if (c.bytes) HIP_TRY(hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyDeviceToDevice, stream));
+        return WT_OK;
+    }
+    wtck::CopyTable t;
+    t.count = 0; t.chunks = 0;
+    const auto flush = [&]() {
+        if (t.count == 0) return;
+        t.first[t.count] = t.chunks;
+        const int grid = t.chunks < 4096 ? t.chunks : 4096;
+        hipLaunchKernelGGL(wtck::copy_table_kernel, dim3((unsigned)grid), dim3(wtck::THREADS), 0, stream, t);
+        t.count = 0; t.chunks = 0;
+    };
+    for (const Copy &c : copies) {
+        if (!c.bytes) continue;
+        const size_t chunks = (c.bytes + wtck::CHUNK - 1) / wtck::CHUNK;
+        if (chunks > 0x3fffffffu) return fail(WT_E_ARG, "checkpoint: an array is too large for one copy");
+        if (t.count == wtck::MAX_ENTRIES || (size_t)t.chunks + chunks > 0x3fffffffu) flush();
+        t.src[t.count] = c.src; t.dst[t.count] = c.dst; t.bytes[t.count] = (int64_t)c.bytes; t.first[t.count] = t.chunks;
+        t.chunks += (int)chunks; ++t.count;
+    }
+    flush();
+    HIP_TRY(hipGetLastError());
+    return WT_OK;
+}
+
+// wave diagnostics, item trace and launch timing off: what a checkpoint does not hold
+void instrumentation_off(wt_ensemble *h)
+{
+    free_and_null(h->wave_diag); free_and_null(h->trace); h->trace_cap = 0;
+    h->time_launches = false; h->lt_used = 0;
+}
+
+// every optional part off, as a fresh handle has them (the stream is idle)
+void release_optional(wt_ensemble *h)
+{
+    for (int i = 0; i < N_PARTS; ++i)
+        if (i != PART_CORE && i != PART_QUEUE) release(k_parts[i].arrays(h));
+}
+
+// The handle takes the source's configuration and payload.  Where its switches and capacities already are the
+// source's, nothing is released or allocated and the copies are queued on its stream with no synchronisation (the
+// rewind's fast path).  Otherwise the stream is synchronised, every optional part is released, the source's scalars are
+// stored, the shape is rebuilt by reshape() under the handle's own packing rule, and the groups are allocated anew.  A
+// HIP failure on that path leaves a handle without programs that needs set_state and set_boundary again.
+int restore(wt_ensemble *h, const Source &src)
+{
+    HIP_TRY(hipSetDevice(h->device));
+    if (!same_shape(h, src.scalars)) {
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        release_optional(h);
+        apply_scalars(h, src.scalars);
+        const int length = h->trn.on ? h->trn.length : 0;
+        int rc = reshape(h, length ? length * units_per_wavefront(h->device, h->N / length, 64 / h->n / length) : h->R0);
+        for (int i = 0; i < N_PARTS && rc == WT_OK; ++i)
+            if (view(k_parts[i], h).on) rc = allocate(k_parts[i].arrays(h));
+        if (rc != WT_OK) {
+            const std::string msg = g_err;
+            release_optional(h);
+            (void)reshape(h, h->R0);
+            h->have_state = h->have_bc = false;
+            return fail(rc, msg);
+        }
+    } else {
+        apply_scalars(h, src.scalars);
+    }
+    std::vector<Copy> copies;
+    for (int i = 0; i < N_PARTS; ++i) {
+        const PartView v = view(k_parts[i], h);
+        if (v.payload.size() != src.arrays[(size_t)i].size()) return fail(WT_E_ARG, "checkpoint: internal error: part count");
+        for (size_t k = 0; k < v.payload.size(); ++k) {
+            if (v.payload[k].second != src.arrays[(size_t)i][k].second) return fail(WT_E_ARG, "checkpoint: internal error: array size");
+            copies.push_back({*v.payload[k].first, src.arrays[(size_t)i][k].first, v.payload[k].second});
+        }
+    }
+    if (src.device) {
+        if (int rc = device_copies(copies, h->stream, h->knob_memcpy != 0)) return rc;
+    } else {
+        for (const Copy &c : copies)
+            if (c.bytes) HIP_TRY(hipMemcpyAsync(c.dst, c.src, c.bytes, hipMemcpyHostToDevice, h->stream));
+    }
+    // what is derived from the arrays and the shape, by the rules of the calls that set them
+    h->sens.cmd.hr = h->ctl.hr;
+    h->trn_lk = src.trn_lk;
+    if (h->sched_mode == WT_SCHED_QUEUE) h->n_sub = default_streams(h->N, h->R);
+    h->bc_known = false;                    // one extra upload, never a wrong skip
+    return WT_OK;
+}
+
+} // namespace
+
+// the device-resident checkpoint of wt_ensemble_mark: one allocation, the payload arrays at 256-byte offsets
+struct wt_mark {
+    void *buf = nullptr;
+    Source src;
+};
+
+namespace {
+
+void drop_mark(wt_ensemble *h)
+{
+    if (!h->mark) return;
+    if (h->mark->buf) (void)hipFree(h->mark->buf);
+    delete h->mark;
+    h->mark = nullptr;
+}
+
+// the two handles hold the same reactor constants
+bool same_constants(const wt_ensemble *a, const void *par, size_t bytes)
+{
+    return bytes == sizeof(double) * a->par_sent.size() && std::memcmp(a->par_sent.data(), par, bytes) == 0;
+}
+
 } // namespace
 
 extern "C" {
@@ -1707,8 +2129,8 @@ int wt_ensemble_destroy(wt_ensemble *h)
     if (!h) return WT_OK;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (const auto arrays : {core_arrays, queue_arrays, sensor_arrays, plant_io_arrays, record_arrays, wire_arrays, pipe_arrays, train_arrays}) release(arrays(h));
-    for (const Program &p : k_programs) release(p.arrays(h));
+    drop_mark(h);
+    for (const Part &p : k_parts) release(p.arrays(h));
     free_and_null(h->trace); free_and_null(h->wave_diag); free_and_null(h->snap_dev); free_and_null(h->sched);
     free_and_null(h->diag_out);
     for (int s = 0; s < WT_MAX_STREAMS; ++s) {
@@ -2282,6 +2704,7 @@ int wt_ensemble_info(wt_ensemble *h, int what, int64_t *value)
     case WT_INFO_TRAIN_LENGTH: *value = h->trn.length; break;
     case WT_INFO_WAVE_DIAG: *value = h->wave_diag != nullptr; break;
     case WT_INFO_BOUNDARY_UPLOADS: *value = h->bc_uploads; break;
+    case WT_INFO_MARK: *value = h->mark != nullptr; break;
     default: return fail(WT_E_ARG, "unknown info code");
     }
     return WT_OK;
@@ -2565,6 +2988,179 @@ int wt_ensemble_timer_stop(wt_ensemble *h, float *elapsed_ms)
     HIP_TRY(hipEventRecord(h->ev1, h->stream));
     HIP_TRY(hipEventSynchronize(h->ev1));
     HIP_TRY(hipEventElapsedTime(elapsed_ms, h->ev0, h->ev1));
+    return WT_OK;
+}
+
+int wt_ensemble_checkpoint_size(wt_ensemble *h, int64_t *bytes)
+{
+    if (!h || !bytes) return fail(WT_E_ARG, "NULL argument");
+    *bytes = checkpoint_bytes(h);
+    return WT_OK;
+}
+
+int wt_ensemble_checkpoint_save(wt_ensemble *h, void *blob, int64_t bytes)
+{
+    if (!h || !blob) return fail(WT_E_ARG, "NULL argument");
+    const int64_t total = checkpoint_bytes(h);
+    if (bytes < total) return fail(WT_E_ARG, "checkpoint_save: the buffer is smaller than wt_ensemble_checkpoint_size");
+    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = sync_checked(h)) return rc;        // an incomplete state is not saved, as it is not downloaded
+    unsigned char *b = (unsigned char *)blob;
+    std::memset(b, 0, (size_t)total);               // the padding is zero: two saves of one state give the same bytes
+    size_t at = WT_CKP_HEADER_BYTES;
+    const auto word = [&](uint32_t w) { std::memcpy(b + at, &w, 4); at += 4; };
+    std::vector<Copy> copies;
+    for (const Part &p : k_parts) {
+        const PartView v = view(p, h);
+        word(tag_word(p.tag)); word((uint32_t)v.scalars.size());
+        for (const Scalar &s : v.scalars) { const int64_t x = scalar_get(s); std::memcpy(b + at, &x, 8); at += 8; }
+        word((uint32_t)v.payload.size()); word(0);
+        for (const auto &a : v.payload) {
+            const int64_t len = (int64_t)a.second;
+            std::memcpy(b + at, &len, 8); at += 8;
+            copies.push_back({b + at, *a.first, a.second});
+            at += pad8(a.second);
+        }
+    }
+    if (int rc = download(h, copies)) return rc;
+    wt_checkpoint_header hd;
+    std::memset(&hd, 0, sizeof hd);
+    std::memcpy(hd.magic, WT_CKP_MAGIC, 4);
+    hd.format = WT_CKP_FORMAT; hd.abi = WT_ABI_VERSION; hd.n_zones = (uint32_t)h->n; hd.n_reactors = h->N; hd.bytes = total;
+    hd.layout = layout_fingerprint(); hd.n_parts = N_PARTS;
+    hd.checksum = wtck::fnv1a(b + WT_CKP_HEADER_BYTES, (size_t)total - WT_CKP_HEADER_BYTES);
+    std::memcpy(b, &hd, sizeof hd);
+    return WT_OK;
+}
+
+int wt_checkpoint_check(const void *blob, int64_t bytes, int64_t *n_reactors, int *n_zones)
+{
+    return parse_blob(blob, bytes, n_reactors, n_zones, nullptr);
+}
+
+int wt_ensemble_checkpoint_load(wt_ensemble *h, const void *blob, int64_t bytes)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    Source src;
+    int64_t N = 0; int n = 0;
+    if (int rc = parse_blob(blob, bytes, &N, &n, &src, h)) return rc;
+    if (!same_constants(h, src.arrays[PART_CORE][0].first, src.arrays[PART_CORE][0].second))
+        return fail(WT_E_ARG, "checkpoint_load: the reactor constants differ from the handle's");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    instrumentation_off(h);
+    if (int rc = restore(h, src)) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));       // the caller's blob is free on return
+    return WT_OK;
+}
+
+int wt_ensemble_copy(wt_ensemble *dst, wt_ensemble *src)
+{
+    if (!dst || !src) return fail(WT_E_ARG, "NULL handle");
+    if (dst == src) return fail(WT_E_ARG, "copy: dst and src are the same handle");
+    if (dst->N != src->N || dst->n != src->n) return fail(WT_E_ARG, "copy: the handles differ in n_reactors or n_zones");
+    if (dst->device != src->device) return fail(WT_E_ARG, "copy: the handles are on different devices");
+    if (!same_constants(dst, src->par_sent.data(), sizeof(double) * src->par_sent.size()))
+        return fail(WT_E_ARG, "copy: the reactor constants differ");
+    HIP_TRY(hipSetDevice(src->device));
+    if (int rc = sync_checked(src)) return rc;
+    HIP_TRY(hipStreamSynchronize(dst->stream));
+    instrumentation_off(dst);
+    if (int rc = restore(dst, source_of(src))) return rc;
+    HIP_TRY(hipStreamSynchronize(dst->stream));     // src may go on at once
+    return WT_OK;
+}
+
+int wt_ensemble_mark(wt_ensemble *h)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = sync_checked(h)) return rc;
+    Source live = source_of(h);
+    size_t total = 0;
+    for (const auto &part : live.arrays)
+        for (const auto &a : part) total += (a.second + 255) & ~(size_t)255;
+    void *buf = nullptr;
+    if (total) {
+        const hipError_t e = hipMalloc(&buf, total);
+        if (e != hipSuccess) return fail(WT_E_HIP, std::string("mark: ") + hipGetErrorString(e));
+    }
+    std::vector<Copy> copies;
+    size_t at = 0;
+    for (auto &part : live.arrays)
+        for (auto &a : part) {
+            void *to = (char *)buf + at;
+            copies.push_back({to, a.first, a.second});
+            a.first = to;
+            at += (a.second + 255) & ~(size_t)255;
+        }
+    if (int rc = device_copies(copies, h->stream, h->knob_memcpy != 0)) { (void)hipStreamSynchronize(h->stream); (void)hipFree(buf); return rc; }
+    drop_mark(h);                                   // (the stream was idle: nothing reads the old mark)
+    h->mark = new wt_mark();
+    h->mark->buf = buf;
+    h->mark->src = std::move(live);
+    return WT_OK;
+}
+
+int wt_ensemble_rewind(wt_ensemble *h)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    if (!h->mark) return fail(WT_E_STATE, "rewind: no mark is set (wt_ensemble_mark)");
+    return restore(h, h->mark->src);
+}
+
+int wt_ensemble_unmark(wt_ensemble *h)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    if (!h->mark) return WT_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));       // a queued rewind may still read it
+    drop_mark(h);
+    return WT_OK;
+}
+
+int wt_selftest_copy_table(int device, const int64_t *bytes, int count, int *mismatches)
+{
+    if (!mismatches || count < 0 || (count > 0 && !bytes)) return fail(WT_E_ARG, "bad argument");
+    *mismatches = 0;
+    if (count == 0) return WT_OK;
+    constexpr size_t GUARD = 64;
+    std::vector<size_t> off((size_t)count + 1, 0);
+    for (int i = 0; i < count; ++i) {
+        if (bytes[i] < 0) return fail(WT_E_ARG, "bad argument");
+        off[(size_t)i + 1] = off[(size_t)i] + (((size_t)bytes[i] + GUARD + 255) & ~(size_t)255);
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return fail(WT_E_NOGPU, "no HIP device available: libwtphys has no CPU path");
+    if (device < 0 || device >= ndev) return fail(WT_E_ARG, "bad device index");
+    HIP_TRY(hipSetDevice(device));
+    const size_t total = off[(size_t)count];
+    std::vector<unsigned char> from(total), to(total, 0xA5), got(total);
+    for (size_t i = 0; i < total; ++i) from[i] = (unsigned char)((i * 2654435761u) >> 13);
+    unsigned char *d_from = nullptr, *d_to = nullptr;
+    HIP_TRY(hipMalloc((void **)&d_from, total));
+    if (hipMalloc((void **)&d_to, total) != hipSuccess) { (void)hipFree(d_from); return fail(WT_E_HIP, "hipMalloc failed"); }
+    hipError_t e = hipMemcpy(d_from, from.data(), total, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_to, to.data(), total, hipMemcpyHostToDevice);
+    int rc = WT_OK;
+    if (e == hipSuccess) {
+        std::vector<Copy> copies;
+        for (int i = 0; i < count; ++i) copies.push_back({d_to + off[(size_t)i], d_from + off[(size_t)i], (size_t)bytes[i]});
+        rc = device_copies(copies, nullptr, false);
+        if (rc == WT_OK) e = hipDeviceSynchronize();
+    }
+    if (rc == WT_OK && e == hipSuccess) e = hipMemcpy(got.data(), d_to, total, hipMemcpyDeviceToHost);
+    (void)hipFree(d_from); (void)hipFree(d_to);
+    if (rc != WT_OK) return rc;
+    if (e != hipSuccess) return fail(WT_E_HIP, hipGetErrorString(e));
+    int bad = 0;
+    for (int i = 0; i < count; ++i)
+        for (size_t k = off[(size_t)i]; k < off[(size_t)i + 1]; ++k) {
+            const bool inside = k - off[(size_t)i] < (size_t)bytes[i];
+            if (got[k] != (inside ? from[k] : (unsigned char)0xA5) && bad < 0x7fffffff) ++bad;
+        }
+    *mismatches = bad;
     return WT_OK;
 }
 

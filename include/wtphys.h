@@ -271,7 +271,7 @@ int wt_ensemble_get_boundary(wt_ensemble *h, double *bc);
  * download of that name fills (0 while its part is off).  WT_INFO_PROGRAM + WT_PROG_*: that program is set.
  * WT_INFO_SCORE_BINS is 0 without a curve, as the fan is.  WT_INFO_WAVE_DIAG: the wave diagnostics are allocated (the
  * next wt_ensemble_wave_diag call copies instead of switching on).  WT_INFO_BOUNDARY_UPLOADS: wt_ensemble_set_boundary
- * calls that uploaded since creation.  An unknown code gives WT_E_ARG. */
+ * calls that uploaded since creation.  WT_INFO_MARK: a mark is set.  An unknown code gives WT_E_ARG. */
 enum {
     WT_INFO_PLANT_IO = 0,
     WT_INFO_PROGRAM = 1,                  /* + WT_PROG_CONTROL .. WT_PROG_TREND: codes 1..8 */
@@ -283,7 +283,8 @@ enum {
     WT_INFO_TRAIN_LENGTH = 16,            /* length of wt_ensemble_train_set */
     WT_INFO_WAVE_DIAG = 17,
     WT_INFO_BOUNDARY_UPLOADS = 18,
-    WT_INFO_WIRE = 19                     /* a wire program is set */
+    WT_INFO_WIRE = 19,                    /* a wire program is set */
+    WT_INFO_MARK = 20                     /* a mark is set (wt_ensemble_mark) */
 };
 int wt_ensemble_info(wt_ensemble *h, int what, int64_t *value);
 
@@ -889,6 +890,76 @@ int wt_program_check(int program, const double *params, int64_t n_reactors);
  * wt_program_check names for `program`; synchronises.  WT_E_STATE with the program's "not set" message while it is off,
  * WT_E_ARG for an unknown program. */
 int wt_ensemble_program_params(wt_ensemble *h, int program, double *params);
+
+/* ---- checkpoint, copy and rewind of a whole ensemble ----
+ * A checkpoint holds everything that decides the next bits of a run: the state, the boundary block, status and solver
+ * counters, the placement with its cost history, the schedule, the step limit, the sensor suite with its draw counters
+ * and rings, the register images, the trajectory records, every program's parameters, state and stores, the train
+ * shape with its pipes and wires, and the host counters that go with them.  It holds no developer instrumentation
+ * (wave diagnostics, item trace, launch timing, the environment knobs read at creation) and no scratch; after a load
+ * the instrumentation is off, and WT_INFO_BOUNDARY_UPLOADS and the re-deal count stay the destination's own.
+ *
+ * The blob is little-endian: the 64-byte wt_checkpoint_header below, then the handle's parts in a fixed order.  A part
+ * is {uint32 tag, uint32 n_scalars, n_scalars x 8 bytes (integers as int64, doubles as they are), uint32 n_arrays,
+ * uint32 0, then per array int64 bytes and the data, zero-padded to a multiple of 8}; a part that is off has
+ * n_arrays = 0.  No address is ever written.  `layout` is a hash over the parts' tags, scalar kinds and the byte
+ * counts of every array at the unit shape, so a library whose records differ refuses the blob.  `checksum` is the
+ * 64-bit FNV-1a of every byte after the header.  Two saves of one state give the same bytes.
+ *
+ * size:  bytes a save of the handle as it is now needs; no synchronisation.
+ * save:  synchronises; WT_E_ARG "checkpoint_save: the buffer is smaller than wt_ensemble_checkpoint_size" when
+ *        bytes is too small (more is fine), WT_E_HIP when a launch has left the state incomplete.
+ * check: host only, no device call.  Refusals in this order, all WT_E_ARG: "checkpoint: NULL argument",
+ *        "checkpoint: shorter than its header", "checkpoint: bad magic", "checkpoint: unknown format version",
+ *        "checkpoint: the header's byte count is not the blob's length", "checkpoint: the layout fingerprint is
+ *        not this library's", "checkpoint: checksum mismatch", "checkpoint: n_reactors must be positive",
+ *        "checkpoint: n_zones must be in 2..64", "checkpoint: a part's switches or capacities are out of range",
+ *        "checkpoint: a part's arrays do not match the capacities it declares".  n_reactors / n_zones may be NULL.
+ * load:  into a handle of equal N, n and reactor constants (WT_E_ARG "checkpoint_load: the checkpoint's n_reactors or
+ *        n_zones differ from the handle's", "checkpoint_load: the reactor constants differ from the handle's"), on
+ *        any device.  The whole blob is validated as `check` does before the first device call; a refusal changes
+ *        nothing.  Then the load replaces the configuration: the destination's optional parts are released, the
+ *        blob's switches and capacities take their place, the train shape is rebuilt under the destination's own
+ *        packing rule, and the payload is uploaded.
+ * copy:  dst becomes what load(save(src)) would make it, device to device.  Two distinct handles on one device with
+ *        equal N, n and constants; otherwise WT_E_ARG ("copy: dst and src are the same handle", "copy: the handles
+ *        differ in n_reactors or n_zones", "copy: the handles are on different devices", "copy: the reactor
+ *        constants differ").  The mark of src is not copied.
+ * mark:  a checkpoint kept in device memory inside the handle; replaces an earlier mark; freed by unmark and destroy.
+ *        WT_E_HIP when the second copy cannot be allocated (the handle is untouched).
+ * rewind: back to the mark, any number of times; WT_E_STATE "rewind: no mark is set (wt_ensemble_mark)".  Where the
+ *        switches and capacities are those of the mark, one kernel launch and no allocation; otherwise the load path
+ *        from the device-resident payload.
+ * unmark: no effect without a mark. */
+#define WT_CKP_MAGIC "WTCK"
+#define WT_CKP_FORMAT 1
+#define WT_CKP_HEADER_BYTES 64
+typedef struct {
+    char magic[4];                        /*  0  "WTCK" */
+    uint32_t format;                      /*  4  WT_CKP_FORMAT */
+    uint32_t abi;                         /*  8  WT_ABI_VERSION */
+    uint32_t n_zones;                     /* 12 */
+    int64_t n_reactors;                   /* 16 */
+    int64_t bytes;                        /* 24  of the whole blob, header included */
+    uint64_t layout;                      /* 32  layout fingerprint */
+    uint64_t checksum;                    /* 40  FNV-1a 64 of bytes 64 .. bytes - 1 */
+    uint32_t n_parts;                     /* 48 */
+    uint32_t reserved0;                   /* 52  0 */
+    uint64_t reserved1;                   /* 56  0 */
+} wt_checkpoint_header;
+int wt_ensemble_checkpoint_size(wt_ensemble *h, int64_t *bytes);
+int wt_ensemble_checkpoint_save(wt_ensemble *h, void *blob, int64_t bytes);
+int wt_ensemble_checkpoint_load(wt_ensemble *h, const void *blob, int64_t bytes);
+int wt_checkpoint_check(const void *blob, int64_t bytes, int64_t *n_reactors, int *n_zones);
+int wt_ensemble_copy(wt_ensemble *dst, wt_ensemble *src);
+int wt_ensemble_mark(wt_ensemble *h);
+int wt_ensemble_rewind(wt_ensemble *h);
+int wt_ensemble_unmark(wt_ensemble *h);
+/* Self-test of the kernel that performs a checkpoint's device-to-device copies (wtck::copy_table_kernel): `count`
+ * arrays of bytes[i] >= 0 bytes, sources filled with a position-dependent pattern, destinations with another byte and
+ * 64 guard bytes behind each; everything is compared on the host, guards included.  *mismatches must come back 0.
+ * count = 0 launches nothing. */
+int wt_selftest_copy_table(int device, const int64_t *bytes, int count, int *mismatches);
 
 /* ---- reactor diagnostics (SURVEY.md section 8(f) NEXT-4): reductions over the zones of every reactor ----
  * out: host [WT_N_DIAG][N] doubles, rows
