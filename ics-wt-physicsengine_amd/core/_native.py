@@ -22,7 +22,7 @@ WT_OK, WT_E_ARG, WT_E_HIP, WT_E_NOGPU, WT_E_STATE = 0, 1, 2, 3, 4
  WT_PROG_TREND) = range(8)   # wt_program_check
 (WT_INFO_PLANT_IO, WT_INFO_PROGRAM, WT_INFO_TRAIN, WT_INFO_PIPE, WT_INFO_SENSOR_HISTORY, WT_INFO_DISTURB_HISTORY,
  WT_INFO_SCORE_CURVE, WT_INFO_SCORE_BINS, WT_INFO_TREND_CAPACITY, WT_INFO_TRAIN_LENGTH, WT_INFO_WAVE_DIAG,
- WT_INFO_BOUNDARY_UPLOADS, WT_INFO_WIRE, WT_INFO_MARK) = (0, 1) + tuple(range(9, 21))   # wt_ensemble_info; WT_INFO_PROGRAM + WT_PROG_*: 1..8
+ WT_INFO_BOUNDARY_UPLOADS, WT_INFO_WIRE, WT_INFO_MARK, WT_INFO_JUNCTION) = (0, 1) + tuple(range(9, 22))   # wt_ensemble_info; WT_INFO_PROGRAM + WT_PROG_*: 1..8
 
 
 class WtError(RuntimeError):
@@ -159,6 +159,11 @@ SIGNATURES = {
     "wt_ensemble_wire_get": [_vp, _dp, _dp],
     "wt_ensemble_wire_clear": [_vp],
     "wt_wire_check": [C.c_int, C.c_int64, _dp],
+    "wt_ensemble_junction_set": [_vp, _dp, _dp],
+    "wt_ensemble_junction_get": [_vp, _dp],
+    "wt_ensemble_junction_params": [_vp, _dp, _dp],
+    "wt_ensemble_junction_clear": [_vp],
+    "wt_junction_check": [C.c_int, C.c_int64, _dp, _dp, _dp],
     "wt_program_check": [C.c_int, _dp, C.c_int64],
     "wt_ensemble_program_params": [_vp, C.c_int, _dp],
     "wt_ensemble_checkpoint_size": [_vp, _i64p],

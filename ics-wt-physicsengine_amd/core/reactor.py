@@ -18,7 +18,7 @@ from typing import Dict, Iterable, List, Optional, Sequence, Union
 
 import numpy as np
 
-from . import _native, _program, actuator, alarm, control, detect, disturb, inject, params, score, train, trend, wire
+from . import _native, _program, actuator, alarm, control, detect, disturb, inject, junction, params, score, train, trend, wire
 
 logger = logging.getLogger(__name__)
 
@@ -814,6 +814,42 @@ class ReactorEnsemble:
     def clear_wires(self) -> None:
         """Stop the wire program: every slot is the reactor's own instrument again."""
         self._program_call(_native.lib().wt_ensemble_wire_clear)
+
+    # -- the junction program: flow-weighted merges and splits in a train, on the device (wt_trn.hpp)
+    def set_junctions(self, *junctions: "junction.Junction") -> None:
+        """Feed stages of the train program from up to four other stages of their train (:class:`Junction`): after
+        every outer step all its sources took, a junction's inlet rows get the blend of the sources' outlet zones
+        weighted by ``share * the source's inlet flow`` -- chlorine and temperature as flow-weighted means, pH through
+        H+ -- and with ``carry`` its inlet flow becomes the summed flow: the bits (a blended pH: within 2e-14) of the
+        train program's host loop with that blend between the calls.  Needs a train program; set it before the pipes;
+        replaces any junction program; :meth:`clear_junctions`.  ``set_trains`` and ``clear_trains`` clear the
+        junctions.  A carried flow excludes plant I/O."""
+        if not self.info(_native.WT_INFO_TRAIN):
+            self._program_call(_native.lib().wt_ensemble_junction_set, None, None)    # the library's refusal
+        par = np.empty((train.NTR, self.n_reactors), dtype=np.float64)
+        self._program_call(_native.lib().wt_ensemble_train_params, _native.dptr(par))
+        blk, carry = junction.junction_block(self.n_reactors, self.info(_native.WT_INFO_TRAIN_LENGTH), par[0], *junctions)
+        self._program_call(_native.lib().wt_ensemble_junction_set, _native.dptr(blk), _native.dptr(carry))
+
+    def junction_state(self) -> "junction.JunctionState":
+        """Per reactor: the feeds a junction got inside step calls, the outer steps it was held, the summed flow of the
+        last feed (one synchronisation)."""
+        st = np.empty((junction.NJS, self.n_reactors), dtype=np.float64)
+        self._program_call(_native.lib().wt_ensemble_junction_get, _native.dptr(st))
+        return junction.JunctionState.from_block(st)
+
+    def junction_params(self):
+        """The (4, 2, N) block of the junction program in force -- per slot the source stage (-1: unused) and its share
+        -- and the (N,) carry flags."""
+        blk = np.empty((junction.JCT_SLOTS, junction.NJ, self.n_reactors), dtype=np.float64)
+        carry = np.empty(self.n_reactors, dtype=np.float64)
+        self._program_call(_native.lib().wt_ensemble_junction_params, _native.dptr(blk), _native.dptr(carry))
+        return blk, carry
+
+    def clear_junctions(self) -> None:
+        """Stop the junction program: the bases go back into the linked rows and the carriers' inlet flows, then every
+        link is fed by its upstream as the train program does."""
+        self._program_call(_native.lib().wt_ensemble_junction_clear)
 
     def set_detectors(self, *detectors: "detect.Detector", attack=None) -> None:
         """Run a detector program of up to four :class:`Detector` slots at every PLC scan, inside the step call, last in

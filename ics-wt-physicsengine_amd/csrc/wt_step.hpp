@@ -645,12 +645,16 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
             ArgPtr d = fresh(pa);            // ---- section: disturbance program, train program
             const bool live = present && stepped && !(st & ST_T_RANGE_POST);   // the sensor section's test
             bool reload = false;
+            // a junction program reads the row 0 that was in force during this step, before this section stores anything
+            double q0 = 0.0;
+            if (trn_on && d->trn.jct.on && present && !L.has_hi) q0 = d->bc[r];
             if (dst_on) {
                 if (live && L.z == 0) wtd::evaluate(d->dst, r, t_out, d->bc, d->N, ExpK());
                 reload = live;
             }
             // a stage's outlet lane stores its state into the next stage's rows 1..3; fed: this lane's reactor got rows
-            if (trn_on) reload = wtr::feed(d->trn, live, !L.has_hi, seg, n_zones, r, t_out, y0, d->bc, d->N) || reload;
+            static_assert(M::TAIL_DOUBLES >= wtr::PARK_Q * wtr::PARK_SEGS, "a junction program parks the outlets in the factor store");
+            if (trn_on) reload = wtr::feed(d->trn, present, live, !L.has_hi, seg, n_zones, r, t_out, y0, q0, d->bc, d->N, lds_factors, JctK()) || reload;
             __syncthreads();                 // the rows are in memory for every lane of the reactor
             if (reload) {
                 RK k1; load_reactor(d->par, d->bc, d->N, r, n_zones, k1); mask_reactor_for_lane(L, k1);

@@ -176,6 +176,24 @@ __device__ __forceinline__ double exp10_k(const KP &k, double x)
 // e^y by exp10_k with literal constants: the disturbance programs' exp (wt_dst.hpp)
 struct ExpK { __device__ __forceinline__ double operator()(double y) const { return exp10_k(kp_of(default_ktab()), y * wtd::LOG10_E); } };
 
+// The junction program's pH arithmetic (wt_trn.hpp): H+ = 10^-pH as load_reactor takes the inlet's, and pH of a blended
+// H+.  The device library's log10, inlined into the step kernel, keeps 10 to 18 more registers alive across the solver
+// loop (its fp64 literals are hoisted out of the outer-step loop) and costs the n = 9..32 kernels 12 and 44 B of
+// scratch; so -log10(H) is the root p of 10^-p = H by Newton's method on exp10_k, whose literals the kernel holds
+// already: p <- p + (1 - H / 10^-p) / ln 10 from the hardware's fp32 log2.  The error squares per step (1e-6, 1e-12,
+// then the floor); the floor is exp10_k's relative error over ln 10 plus the last sum's rounding, under 1 ulp(14).
+struct JctK {
+    __device__ __forceinline__ double exp10(double x) const { return exp10_k(kp_of(default_ktab()), x); }
+    __device__ __forceinline__ double pH_of(double H) const
+    {
+        const KP k = kp_of(default_ktab());
+        double p = -(double)(__builtin_amdgcn_logf((float)H) * 0.30103f);
+#pragma unroll 1
+        for (int i = 0; i < 4; ++i) p = p + (1.0 - H / exp10_k(k, -p)) / k.ln10_hi;
+        return p;
+    }
+};
+
 // The Radau constants of the solver sections, fetched the same way (radau.py:11-40 values, see rc::)
 struct alignas(64) RTab {
     double T00, T01, T02, T10, T11, T12, rtol, atol;                 // section Z: Z = T W, norm scales

@@ -334,10 +334,14 @@ ArrayGroup detect_arrays(wt_ensemble *h)
 ArrayGroup train_arrays(wt_ensemble *h)
 {
     const size_t N = (size_t)h->N;
+    wtr::JctArgs &j = h->trn.jct;   // the junction program's arrays come and go with the train's; tmp (last) is scratch
     return {"train", &h->trn.on, {{(void **)&h->trn.lk, sizeof(int32_t) * N},
                                   {(void **)&h->trn.st, sizeof(double) * wtr::NTRS * N},
-                                  {(void **)&h->trn.base, sizeof(double) * wtr::FED_ROWS * N}},
-            [h] { h->trn.length = 0; h->trn_lk.clear(); }};
+                                  {(void **)&h->trn.base, sizeof(double) * wtr::FED_ROWS * N},
+                                  {(void **)&j.src, sizeof(uint32_t) * N}, {(void **)&j.share, sizeof(double) * wtr::JCT_SLOTS * N},
+                                  {(void **)&j.st, sizeof(double) * wtr::NJS * N}, {(void **)&j.base0, sizeof(double) * N},
+                                  {(void **)&j.tmp, sizeof(double) * wtr::JCT_TMP * N}},
+            [h] { h->trn.length = 0; h->trn.jct.on = 0; h->trn_lk.clear(); }};
 }
 
 // the pipe program's arrays (wt_trn.hpp); the ring is sized by pipe.slots, which the set call stores first
@@ -549,10 +553,30 @@ int wire_restart(wt_ensemble *h)
 int train_op(wt_ensemble *h, int op)
 {
     h->bc_known = false;   // a feed, a restore or a delivery writes the linked rows
-    const wtr::HostOpArgs a{h->trn, h->bc, h->pH, h->Cl, h->T, h->N, h->n, op};
-    hipLaunchKernelGGL(wtr::host_op_kernel, dim3((unsigned)((h->N + 255) / 256)), dim3(256), 0, h->stream, a);
+    wtr::HostOpArgs a{h->trn, h->bc, h->pH, h->Cl, h->T, h->time, h->N, h->n, op};
+    const dim3 grid((unsigned)((h->N + 255) / 256));
+    if (h->trn.jct.on && (op == wtr::OP_FEED || op == wtr::OP_PIPE_FILL)) {   // every blend before any store
+        a.op = wtr::OP_JCT_BLEND;
+        hipLaunchKernelGGL(wtr::host_op_kernel<wt::JctK>, grid, dim3(256), 0, h->stream, a);
+        HIP_TRY(hipGetLastError());
+        a.op = op;
+    }
+    hipLaunchKernelGGL(wtr::host_op_kernel<wt::JctK>, grid, dim3(256), 0, h->stream, a);
     HIP_TRY(hipGetLastError());
     return WT_OK;
+}
+
+// -- the junction program (wt_trn.hpp) on top of a train program: what plant I/O asks of it (a disturbance slot never
+// targets row 0 -- wt_program_check refuses it -- so a carried flow and the disturbance program cannot meet)
+const char *k_junction_plant_io = "a carried flow cannot be combined with plant I/O (the scan's command path writes row 0 in the same outer step)";
+
+// the junction words of a set program (empty: none is set)
+int junction_words(wt_ensemble *h, std::vector<uint32_t> &w)
+{
+    w.clear();
+    if (!h->trn.jct.on) return WT_OK;
+    w.resize((size_t)h->N);
+    return download(h, {{w.data(), h->trn.jct.src, sizeof(uint32_t) * w.size()}});
 }
 
 // The device work of wt_ensemble_set_boundary.  The block is "known" once its copy is queued and before the programs'
@@ -573,6 +597,8 @@ int upload_boundary(wt_ensemble *h, const double *bc)
     // a pipe: the sample its line last delivered)
     if (h->trn.on) {
         HIP_TRY(hipMemcpyAsync(h->trn.base, bc + h->N, sizeof(double) * wtr::FED_ROWS * h->N, hipMemcpyHostToDevice, h->stream));
+        // a junction program: row 0 is the base of its carriers
+        if (h->trn.jct.on) HIP_TRY(hipMemcpyAsync(h->trn.jct.base0, bc, sizeof(double) * h->N, hipMemcpyHostToDevice, h->stream));
         if (int rc = train_op(h, wtr::OP_FEED)) return rc;
     }
     HIP_TRY(hipStreamSynchronize(h->stream));   // the caller's block is free on return
@@ -1025,6 +1051,11 @@ int wt_ensemble_plc_enable(wt_ensemble *h)
     if (h->sens.plc_on) return fail(WT_E_STATE, "plant I/O already enabled");
     HIP_TRY(hipSetDevice(h->device));
     const size_t N = (size_t)h->N;
+    {
+        std::vector<uint32_t> jw;
+        if (int rc = junction_words(h, jw)) return rc;
+        for (const uint32_t w : jw) if (w & wtr::JCT_CARRY) return fail(WT_E_STATE, k_junction_plant_io);
+    }
     const ArrayGroup arrays = plant_io_arrays(h);
     if (int rc = allocate(arrays)) return rc;
     wtp::PackArgs &p = h->sens.pack;
@@ -1650,6 +1681,11 @@ int train_restart(wt_ensemble *h)
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemsetAsync(h->cost, 0, sizeof(int32_t) * N, h->stream));
     h->cost_steps = 0;
+    // the junction program's arrays, off: no slot used, no state (a checkpoint holds them whether or not one is set)
+    HIP_TRY(hipMemsetAsync((void *)h->trn.jct.src, 0, sizeof(uint32_t) * N, h->stream));
+    HIP_TRY(hipMemsetAsync((void *)h->trn.jct.share, 0, sizeof(double) * wtr::JCT_SLOTS * N, h->stream));
+    HIP_TRY(hipMemsetAsync(h->trn.jct.st, 0, sizeof(double) * wtr::NJS * N, h->stream));
+    HIP_TRY(hipMemsetAsync(h->trn.jct.base0, 0, sizeof(double) * N, h->stream));
     if (int rc = train_op(h, wtr::OP_FEED)) return rc;
     return sync_checked(h);                     // the host vector is freed on return
 }
@@ -1669,6 +1705,41 @@ template <class Linked> const char *pipe_error(int64_t N, const double *delay, L
 
 // the stream is idle: the lines go, the linked rows stay as they are
 void pipe_release(wt_ensemble *h) { release(pipe_arrays(h)); }
+
+// -- the junction program (wt_trn.hpp) on top of a train program
+static_assert(WT_JCT_SLOTS == wtr::JCT_SLOTS && WT_NJ == wtr::NJ && WT_NJS == wtr::NJS && WT_J_STAGE == wtr::J_STAGE &&
+              WT_J_SHARE == wtr::J_SHARE && WT_JS_N_BLEND == wtr::JS_N_BLEND && WT_JS_N_HELD == wtr::JS_N_HELD &&
+              WT_JS_Q_LAST == wtr::JS_Q_LAST, "junction blocks of the C ABI");
+const char *k_junction_not_set = "no junction program is set (wt_ensemble_junction_set)";
+const char *k_junction_pipes = "junctions must be set before the pipes (a line holds what its junction delivered)";
+
+// The first refusal of a [WT_JCT_SLOTS][WT_NJ][N] block and its carry[N] for trains of `length` stages: reactor by
+// reactor, and at one reactor rule by rule in the header's order.  linked(r): the train program links reactor r.
+template <class Linked> const char *junction_error(int length, int64_t N, const double *p, const double *carry, Linked linked)
+{
+    const auto at = [&](int k, int f, int64_t r) { return p[((int64_t)k * WT_NJ + f) * N + r]; };
+    for (int64_t r = 0; r < N; ++r) {
+        bool used = false;
+        for (int k = 0; k < WT_JCT_SLOTS; ++k)
+            if (!whole_in(at(k, WT_J_STAGE, r), -1, length - 1))
+                return "a source's stage must be -1 (the slot is unused) or a whole number in 0..length - 1 (a stage of the same train)";
+        for (int k = 0; k < WT_JCT_SLOTS; ++k) {
+            used = used || at(k, WT_J_STAGE, r) >= 0.0;
+            if (at(k, WT_J_STAGE, r) == (double)(r % length)) return "a junction cannot be its own source";
+        }
+        for (int k = 0; k < WT_JCT_SLOTS; ++k)
+            for (int i = 0; i < k; ++i)
+                if (at(k, WT_J_STAGE, r) >= 0.0 && at(k, WT_J_STAGE, r) == at(i, WT_J_STAGE, r))
+                    return "a stage can be a source of a junction once only";
+        for (int k = 0; k < WT_JCT_SLOTS; ++k)
+            if (at(k, WT_J_STAGE, r) >= 0.0 && !(std::isfinite(at(k, WT_J_SHARE, r)) && at(k, WT_J_SHARE, r) > 0.0 && at(k, WT_J_SHARE, r) <= 1.0))
+                return "a source's share must be finite and in (0, 1]";
+        if (used && !linked(r)) return "a junction needs a linked reactor (the train program's link; a first stage has none)";
+        if (!(carry[r] == 0.0 || carry[r] == 1.0)) return "carry must be 0 or 1";
+        if (carry[r] == 1.0 && !used) return "carry needs a junction: a reactor without a used slot carries no flow";
+    }
+    return nullptr;
+}
 
 // -- the wire program (wt_wir.hpp) on top of a train program
 static_assert(WT_NSENS == wts::NSENS && WT_NW == wtw::NW && WT_NWS == wtw::NWS && WT_W_STAGE == wtw::W_STAGE &&
@@ -1777,8 +1848,8 @@ const Part k_parts[] = {
              s.insert(s.end(), {{S_F64, &h->scr.fan_lo[k], false}, {S_F64, &h->scr.fan_hi[k], false}, {S_F64, &h->scr.fan_scale[k], false}}); },
      nullptr},
     {"DETC", detect_arrays, 0, [](wt_ensemble *h, Scalars &s) { switch_only(&h->det.on, s); }, nullptr},
-    {"TRAN", train_arrays, 0, [](wt_ensemble *h, Scalars &s) {
-         s.insert(s.end(), {{S_I32, &h->trn.on, true}, {S_I32, &h->trn.length, true}}); }, nullptr},
+    {"TRAN", train_arrays, 1, [](wt_ensemble *h, Scalars &s) {   // (the junction program's arrays are the train's)
+         s.insert(s.end(), {{S_I32, &h->trn.on, true}, {S_I32, &h->trn.length, true}, {S_I32, &h->trn.jct.on, false}}); }, nullptr},
     {"PIPE", pipe_arrays, 0, [](wt_ensemble *h, Scalars &s) {
          s.insert(s.end(), {{S_I32, &h->trn.pipe.on, true}, {S_I32, &h->trn.pipe.slots, true}}); }, nullptr},
     {"WIRE", wire_arrays, 0, [](wt_ensemble *h, Scalars &s) { switch_only(&h->wir.on, s); }, nullptr},
@@ -1914,7 +1985,7 @@ const char *config_error(wt_ensemble *u)
     const bool zoned = u->inj.on | u->alm.on | u->act.on | u->dst.on | u->scr.on | u->det.on | u->trd.on;
     const auto flag = [](int v) { return v == 0 || v == 1; };
     if (!flag(u->sens.on) || !flag(u->sens.plc_on) || !flag(u->ctl.on) || !flag(u->inj.on) || !flag(u->alm.on) || !flag(u->act.on) ||
-        !flag(u->dst.on) || !flag(u->scr.on) || !flag(u->det.on) || !flag(u->trn.on) || !flag(u->trn.pipe.on) || !flag(u->wir.on) ||
+        !flag(u->dst.on) || !flag(u->scr.on) || !flag(u->det.on) || !flag(u->trn.on) || !flag(u->trn.pipe.on) || !flag(u->trn.jct.on) || !flag(u->wir.on) ||
         !flag(u->trd.on) || !flag(u->trd.wrap))
         return "range";
     if (u->placement != WT_PLACE_IDENTITY && u->placement != WT_PLACE_ADAPTIVE) return "range";
@@ -1929,6 +2000,7 @@ const char *config_error(wt_ensemble *u)
     if (u->trn.on ? (u->trn.length < 2 || u->trn.length > 64 / u->n || u->N % u->trn.length != 0) : u->trn.length != 0) return "range";
     if (u->trn.pipe.on ? (!u->trn.on || u->trn.pipe.slots < 1 || u->trn.pipe.slots > WT_PIPE_MAX_DELAY + 1) : u->trn.pipe.slots != 0) return "range";
     if (u->wir.on && (!u->trn.on || !u->sens.plc_on)) return "range";
+    if (u->trn.jct.on && !u->trn.on) return "range";
     return nullptr;
 }
 
@@ -2348,8 +2420,9 @@ int wt_ensemble_train_set(wt_ensemble *h, int length, const double *params)
     if (h->trn.on) {                            // set replaces a program: its rows go back to its base first
         if (int rc = train_op(h, wtr::OP_RESTORE)) return rc;
         if (int rc = sync_checked(h)) return rc;
-        pipe_release(h);                        // and its pipes and wires go with it
+        pipe_release(h);                        // and its pipes, wires and junctions go with it
         wire_release(h);
+        h->trn.jct.on = 0;
     }
     // whole trains per wavefront: the small-ensemble rule of wt_ensemble_create, counted in trains
     const int k = units_per_wavefront(h->device, N / length, 64 / h->n / length);
@@ -2472,6 +2545,104 @@ int wt_ensemble_pipe_clear(wt_ensemble *h)
     HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still use the lines
     pipe_release(h);
     return WT_OK;
+}
+
+int wt_junction_check(int length, int64_t n_reactors, const double *train_params, const double *params, const double *carry)
+{
+    if (n_reactors < 1) return fail(WT_E_ARG, "n_reactors must be >= 1");
+    if (length < 2 || length > 32) return fail(WT_E_ARG, "length must be in 2..32 (the length of the train program)");
+    if (!train_params || !params || !carry) return fail(WT_E_ARG, "NULL argument");
+    const char *msg = junction_error(length, n_reactors, params, carry,
+                                     [&](int64_t r) { return train_params[WT_TR_LINK * n_reactors + r] == 1.0; });
+    return msg ? fail(WT_E_ARG, msg) : WT_OK;
+}
+
+int wt_ensemble_junction_set(wt_ensemble *h, const double *params, const double *carry)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    if (!h->trn.on) return fail(WT_E_STATE, k_train_not_set);
+    if (h->trn.pipe.on) return fail(WT_E_STATE, k_junction_pipes);
+    if (!params || !carry) return fail(WT_E_ARG, "NULL argument");
+    const int64_t N = h->N;
+    const int length = h->trn.length;
+    if (const char *msg = junction_error(length, N, params, carry, [&](int64_t r) { return h->trn_lk[(size_t)r] != 0; }))
+        return fail(WT_E_ARG, msg);
+    std::vector<uint32_t> src((size_t)N, 0);
+    std::vector<double> share((size_t)N * wtr::JCT_SLOTS, 0.0), st((size_t)N * wtr::NJS, 0.0);
+    bool carries = false;
+    for (int64_t r = 0; r < N; ++r) {
+        for (int k = 0; k < WT_JCT_SLOTS; ++k) {
+            const double g = params[((int64_t)k * WT_NJ + WT_J_STAGE) * N + r];
+            if (g >= 0.0) {
+                src[(size_t)r] |= wtr::jct_slot_word(k, (int)g);
+                share[(size_t)(k * N + r)] = params[((int64_t)k * WT_NJ + WT_J_SHARE) * N + r];
+            }
+        }
+        if (carry[r] == 1.0) { src[(size_t)r] |= wtr::JCT_CARRY; carries = true; }
+        st[(size_t)r * wtr::NJS + wtr::JS_Q_LAST] = NAN;
+    }
+    if (carries && h->sens.plc_on) return fail(WT_E_STATE, k_junction_plant_io);
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still use the old records
+    if (h->trn.jct.on) {                        // set replaces a program: its rows and carried flows go back to the bases first
+        if (int rc = train_op(h, wtr::OP_RESTORE)) return rc;
+        if (int rc = sync_checked(h)) return rc;
+        h->trn.jct.on = 0;
+    }
+    const size_t n = (size_t)N;
+    HIP_TRY(hipMemcpyAsync((void *)h->trn.jct.src, src.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync((void *)h->trn.jct.share, share.data(), sizeof(double) * share.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->trn.jct.st, st.data(), sizeof(double) * st.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->trn.jct.base0, h->bc, sizeof(double) * n, hipMemcpyDeviceToDevice, h->stream));
+    h->trn.jct.on = 1;
+    int rc = train_op(h, wtr::OP_RESTORE);      // the rows a plain link fed go back too: a junction with Qs = 0 keeps its base
+    if (rc == WT_OK) rc = train_op(h, wtr::OP_FEED);
+    if (rc == WT_OK) rc = sync_checked(h);      // the host vectors are freed on return
+    if (rc != WT_OK) { (void)hipStreamSynchronize(h->stream); h->trn.jct.on = 0; return rc; }
+    return WT_OK;
+}
+
+int wt_ensemble_junction_get(wt_ensemble *h, double *state)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    if (!h->trn.jct.on) return fail(WT_E_STATE, k_junction_not_set);
+    HIP_TRY(hipSetDevice(h->device));
+    return download_records(h, {{state, h->trn.jct.st, wtr::NJS, 1, wtr::NJS}});
+}
+
+int wt_ensemble_junction_params(wt_ensemble *h, double *params, double *carry)
+{
+    if (!h || !params || !carry) return fail(WT_E_ARG, "NULL argument");
+    if (!h->trn.jct.on) return fail(WT_E_STATE, k_junction_not_set);
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t N = (size_t)h->N;
+    std::vector<uint32_t> src;
+    std::vector<double> share(N * wtr::JCT_SLOTS);
+    if (int rc = junction_words(h, src)) return rc;
+    if (int rc = download(h, {{share.data(), h->trn.jct.share, sizeof(double) * share.size()}})) return rc;
+    for (size_t r = 0; r < N; ++r) {
+        for (int k = 0; k < WT_JCT_SLOTS; ++k) {
+            const uint32_t c = src[r] >> (wtr::JCT_BITS * k);
+            const bool used = (c & wtr::JCT_USED) != 0;
+            params[((size_t)k * WT_NJ + WT_J_STAGE) * N + r] = used ? (double)(c & 31u) : -1.0;
+            params[((size_t)k * WT_NJ + WT_J_SHARE) * N + r] = used ? share[(size_t)k * N + r] : 0.0;
+        }
+        carry[r] = (src[r] & wtr::JCT_CARRY) ? 1.0 : 0.0;
+    }
+    return WT_OK;
+}
+
+int wt_ensemble_junction_clear(wt_ensemble *h)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    if (!h->trn.jct.on) return WT_OK;
+    if (h->trn.pipe.on) return fail(WT_E_STATE, k_junction_pipes);
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still use the records
+    if (int rc = train_op(h, wtr::OP_RESTORE)) return rc;    // the bases back, carried flows included
+    h->trn.jct.on = 0;
+    if (int rc = train_op(h, wtr::OP_FEED)) return rc;       // then every link as the train program feeds it
+    return sync_checked(h);
 }
 
 int wt_wire_check(int length, int64_t n_reactors, const double *params)
@@ -2705,6 +2876,7 @@ int wt_ensemble_info(wt_ensemble *h, int what, int64_t *value)
     case WT_INFO_WAVE_DIAG: *value = h->wave_diag != nullptr; break;
     case WT_INFO_BOUNDARY_UPLOADS: *value = h->bc_uploads; break;
     case WT_INFO_MARK: *value = h->mark != nullptr; break;
+    case WT_INFO_JUNCTION: *value = h->trn.jct.on != 0; break;
     default: return fail(WT_E_ARG, "unknown info code");
     }
     return WT_OK;

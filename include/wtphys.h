@@ -284,7 +284,8 @@ enum {
     WT_INFO_WAVE_DIAG = 17,
     WT_INFO_BOUNDARY_UPLOADS = 18,
     WT_INFO_WIRE = 19,                    /* a wire program is set */
-    WT_INFO_MARK = 20                     /* a mark is set (wt_ensemble_mark) */
+    WT_INFO_MARK = 20,                    /* a mark is set (wt_ensemble_mark) */
+    WT_INFO_JUNCTION = 21                 /* a junction program is set */
 };
 int wt_ensemble_info(wt_ensemble *h, int what, int64_t *value);
 
@@ -734,7 +735,8 @@ int wt_ensemble_trend_clear(wt_ensemble *h);
  * reactor's next outer step (zero-order hold); with plant I/O that step integrates under both this step's commands and
  * these rows.  The state is already clamped to the ranges the rows allow, so no clamp is applied.  An upstream that
  * did not step (a frozen reactor) feeds nothing: its downstream keeps the rows it holds and goes on stepping.
- * Flows are not carried: row 0 belongs to the command path or the master, and every tank keeps its own inlet flow.
+ * Flows are not carried by the train program itself: row 0 belongs to the command path or the master, and every tank
+ * keeps its own inlet flow (a junction program on top may carry them, below).
  * Definition (the fused call gives its bits): on a handle without a program, feed every link from the current state,
  * then repeat { one outer step; wt_ensemble_get_state; for every linked reactor whose upstream stepped, rows 1..3 of
  * wt_ensemble_get_boundary <- the upstream's zone n - 1; wt_ensemble_set_boundary }.
@@ -809,7 +811,7 @@ int wt_train_check(int length, int n_zones, int64_t n_reactors, const double *pa
  * rows stay as they are and the next feed is undelayed; no effect while none is set.  wt_ensemble_train_clear, and a
  * wt_ensemble_train_set over a program, clear the pipes first.  wt_ensemble_pipe_get gives WT_E_STATE, "no pipe
  * program is set (wt_ensemble_pipe_set)", while none is.  Not modelled: a dead time that follows the flow (V / Q),
- * dispersion or lag along the pipe, carried flows, merges and splits.  All calls synchronise. */
+ * dispersion or lag along the pipe.  All calls synchronise. */
 #define WT_PIPE_MAX_DELAY 4095
 enum { WT_PS_N_SENT = 0, WT_PS_T_SENT = 1, WT_NPS = 2 };
 int wt_ensemble_pipe_set(wt_ensemble *h, const double *delay /* [N] */);
@@ -874,6 +876,83 @@ int wt_ensemble_wire_clear(wt_ensemble *h);
  * or WT_E_ARG with that call's message (also "n_reactors must be >= 1", "length must be in 2..32 (the length of the
  * train program)", "NULL argument").  Makes no HIP call. */
 int wt_wire_check(int length, int64_t n_reactors, const double *params);
+
+/* ---- the junction program: flow-weighted merges and splits in a treatment train ----
+ * On top of a set train program, a linked reactor may be fed by up to WT_JCT_SLOTS other stages of its own train
+ * instead of stage - 1: parallel tanks merging into a clearwell, a bypass, a recycle.  A split needs nothing of its
+ * own: several junctions name the same source, each with the share of its flow they take.
+ * Parameters [WT_JCT_SLOTS][WT_NJ][N]: per source slot the stage g (-1: the slot is unused; else a whole number in
+ * 0..length - 1, not the reactor's own stage, each stage in one slot at most) and the share f in (0, 1] of that
+ * stage's inlet flow; and carry [N], 0 or 1.  A reactor with at least one used slot is a junction: its slots replace
+ * the default upstream r - 1 (which may be one of them).  It must be a reactor the train program links, and it uses
+ * that program's rows mask.  g may be a later stage (a recycle): a feed reads the states after the outer step and the
+ * fed rows are a zero-order hold, so the order of the stages does not matter.  A linked reactor without a used slot
+ * is fed by r - 1 as without the program, with the same stores and the same bits.
+ * Blend of the sources k = 0..m-1, in slot order, in fp64 with every product and sum rounded (no fused multiply-add)
+ * and IEEE division:
+ *   Q_k = f_k * row 0 of source k (its own inlet flow, as in force during the outer step just taken),
+ *   Qs = ((Q_0 + Q_1) + Q_2) + Q_3 (sums start from 0.0);
+ *   m = 1: the sample is the source's outlet zone (pH, Cl, T), unchanged -- a chain written as junctions gives the
+ *          train program's bits;
+ *   m >= 2: Cl = (sum Q_k Cl_k) / Qs, T = (sum Q_k T_k) / Qs, pH = -log10((sum Q_k 10^(-pH_k)) / Qs), 10^x the
+ *          library's own (the one that turns the inlet pH into H+), log10 the device library's; then pH is clamped to
+ *          [0, 14], T to [0, 100], Cl to >= 0 (the clamps of the disturbance program's rows 1..3).
+ * Every inlet term of the reference's right-hand side is Q / V (x_inlet - x_0) with H+ = 10^-pH (reactor.py:361-420),
+ * so this is exact where the tank's inlet flow is the sum of the streams, which `carry` provides.  The sample's time
+ * stamp is the first used slot's source time.
+ * Feed inside a step.  After an outer step a junction is fed if and only if every source is live (it stepped and did
+ * not end T_RANGE_POST, the train program's test) and Qs > 0; otherwise it keeps its rows.  The sample goes through
+ * the reactor's pipe line if it has one (the line carries blended samples), then into rows 1 / 2 / 3 as the rows mask
+ * says.  With carry = 1, row 0 of the junction becomes Qs.  All reads of row 0 and of source states of one outer step
+ * precede every store of that step (a source may itself be a carrying junction).  n_fed and t_last of the train program keep their meaning (t_last: the
+ * sample's time stamp).
+ * State [WT_NJS][N]: n_blend (feeds a junction got inside step calls), n_held (outer steps in which at least one
+ * source was live but nothing was fed), q_last (Qs of the last feed, NaN before the first); 0, 0, NaN elsewhere.
+ * Definition (the fused call gives its bits in chlorine, temperature, flows, counters and stamps; a blended pH within
+ * 2e-14 of a host that uses its own exp10 and log10): the train program's host loop, with the row 0 read before the
+ * step and every junction's rows (and carried row 0) computed from the state after it before any is written.
+ * Outside a step.  wt_ensemble_junction_set writes the base back into every linked row and then feeds; the feeds of
+ * wt_ensemble_train_set, wt_ensemble_set_state, wt_ensemble_set_boundary and this one blend every junction from the
+ * state and the row 0 in memory, whether or not the sources are live; Qs = 0 (or less) leaves the junction's rows as
+ * they are; these feeds are not counted.  wt_ensemble_set_boundary stores row 0 as the base of the carriers, as it
+ * stores rows 1..3.  wt_ensemble_junction_clear, and a set over a program, write the bases back first (rows 1..3 of
+ * the rows mask, row 0 of the carriers); clear then feeds every link as the train program does.
+ * With other programs.  wt_ensemble_junction_set needs a train program (WT_E_STATE, "no train program is set
+ * (wt_ensemble_train_set)") and replaces any junction program.  set and clear give WT_E_STATE while a pipe program is
+ * set: "junctions must be set before the pipes (a line holds what its junction delivered)".  wt_ensemble_pipe_set
+ * over junctions fills a junction's line with D copies of the blend from memory (Qs = 0: of the first used slot's
+ * outlet).  wt_ensemble_train_clear, and a wt_ensemble_train_set over a program, clear the junctions first.  A carried
+ * flow and plant I/O exclude each other, whichever comes second (WT_E_STATE): "a carried flow cannot be combined with
+ * plant I/O (the scan's command path writes row 0 in the same outer step)".  The disturbance program never targets
+ * row 0 (wt_program_check refuses the row), so it and a carried flow cannot meet; its slots on rows 1..3 of a junction
+ * fall under the train program's refusal.  Wires, placement and the queue are untouched.  Checkpoints, copies and
+ * marks carry the program.
+ * Refused with WT_E_ARG, reactor by reactor, at one reactor in this order:
+ *   "a source's stage must be -1 (the slot is unused) or a whole number in 0..length - 1 (a stage of the same train)"
+ *   "a junction cannot be its own source"
+ *   "a stage can be a source of a junction once only"
+ *   "a source's share must be finite and in (0, 1]"
+ *   "a junction needs a linked reactor (the train program's link; a first stage has none)"
+ *   "carry must be 0 or 1"
+ *   "carry needs a junction: a reactor without a used slot carries no flow"
+ * get and params give WT_E_STATE, "no junction program is set (wt_ensemble_junction_set)", while none is.  The program
+ * takes no code of wt_program_check: wt_junction_check is its check.  Not modelled: raw water as a blend partner at a
+ * first stage, junctions across trains, more than four sources, buffered (alkalinity-aware) pH mixing, a dead time
+ * that follows the flow.  All calls synchronise. */
+#define WT_JCT_SLOTS 4
+enum { WT_J_STAGE = 0, WT_J_SHARE = 1, WT_NJ = 2 };
+enum { WT_JS_N_BLEND = 0, WT_JS_N_HELD = 1, WT_JS_Q_LAST = 2, WT_NJS = 3 };
+int wt_ensemble_junction_set(wt_ensemble *h, const double *params /* [WT_JCT_SLOTS][WT_NJ][N] */, const double *carry /* [N] */);
+/* the host [WT_NJS][N] state */
+int wt_ensemble_junction_get(wt_ensemble *h, double *state);
+/* the program in force: host [WT_JCT_SLOTS][WT_NJ][N] (an unused slot reads stage -1, share 0) and carry [N] */
+int wt_ensemble_junction_params(wt_ensemble *h, double *params, double *carry);
+int wt_ensemble_junction_clear(wt_ensemble *h);
+/* the checks wt_ensemble_junction_set makes on params and carry for trains of `length` stages, with no handle and no
+ * device, against the link row of a [WT_NTR][N] parameter block of wt_ensemble_train_set: WT_OK or WT_E_ARG with that
+ * call's message (also "n_reactors must be >= 1", "length must be in 2..32 (the length of the train program)", "NULL
+ * argument").  Makes no HIP call. */
+int wt_junction_check(int length, int64_t n_reactors, const double *train_params, const double *params, const double *carry);
 
 /* ---- the parameter checks of the scan programs, the disturbance and the score program, without a handle or a device ----
  * params: host, the block the program's set or enable call takes, for n_reactors reactors (WT_PROG_CONTROL:

@@ -5,12 +5,16 @@
   (d) the host-fed loop (c) replaces -- one-step calls with the outlets copied into set_boundary between them
       (tests/train_ref.py): its bits must equal (c)'s;
   (e) (c) with a pipe program whose every delay is 0: its bits must equal (c)'s;
-  (f) (c) with every linked stage behind a pipe of PIPE_DELAY outer steps.
-The six alternate over five repeats, the order rotating; the medians are reported.  (c) and (d) also integrate the
+  (f) (c) with every linked stage behind a pipe of PIPE_DELAY outer steps;
+  (g) (c) with a junction program that makes every train a diamond 0 -> {1, 2} -> 3: stages 1 and 2 each take half of
+      stage 0's flow, stage 3 merges them (trains of 4 only);
+  (h) (g) with the merged flow carried into stage 3's inlet flow.
+The cases alternate over five repeats, the order rotating; the medians are reported.  (c) and (d) also integrate the
 plant under moving inlets, so (c) / (a) is not the feed's cost alone.  After the rotation the host loop with a FIFO per
 link (tests/pipe_ref.py) runs once, untimed: its bits must equal (f)'s.  Prints one JSON line.
    python tools/train_probe.py [N] [n] [steps] [length]"""
 import json, sys, time
+import importlib
 from probe_common import arguments, ensemble, outputs, rotate, same, timed_step
 from pipe_ref import host_piped_loop
 from train_ref import host_fed_loop
@@ -18,6 +22,8 @@ from train_ref import host_fed_loop
 N, n, K, cols, bc = arguments(500)
 L = int(sys.argv[4]) if len(sys.argv) > 4 else 4
 DT, PIPE_DELAY = 10.0, 5
+CASES = "abcdefgh" if L == 4 else "abcdef"
+Junction = importlib.import_module("ics-wt-physicsengine_amd").Junction
 
 
 def run(name, rep=0):
@@ -29,8 +35,10 @@ def run(name, rep=0):
         ens.synchronize()
         dt = time.perf_counter() - t0
     else:
-        if name in "bcef":
+        if name in "bcefgh":
             ens.set_trains(L, linked=(name != "b"))
+        if name in "gh":
+            ens.set_junctions(Junction(1, (0,), 0.5), Junction(2, (0,), 0.5), Junction(3, (1, 2), 1.0, carry=(name == "h")))
         if name in "ef":
             ens.set_pipes(PIPE_DELAY if name == "f" else 0)
         _, dt = timed_step(ens, DT, K)
@@ -41,7 +49,7 @@ def run(name, rep=0):
 
 run("c")                                         # module load, first launches
 REPEATS = 5
-times, med, last = rotate("abcdef", REPEATS, run)
+times, med, last = rotate(CASES, REPEATS, run)
 off_same, loop_same = same(last["a"][1], last["b"][1]), same(last["c"][1], last["d"][1])
 zero_same = same(last["c"][1], last["e"][1])
 ens = ensemble(cols, bc, n)
@@ -54,6 +62,9 @@ print(json.dumps({"N": N, "n": n, "steps": K, "length": L, "none_s": round(med["
                   "host_loop_over_linked": round(med["d"] / med["c"], 2),
                   "pipes_zero_s": round(med["e"], 4), "pipes_s": round(med["f"], 4), "pipe_delay": PIPE_DELAY,
                   "pipes_zero_over_linked": round(med["e"] / med["c"], 3), "pipes_over_linked": round(med["f"] / med["c"], 3),
+                  **({"diamond_s": round(med["g"], 4), "diamond_carry_s": round(med["h"], 4),
+                      "diamond_over_linked": round(med["g"] / med["c"], 3),
+                      "diamond_carry_over_linked": round(med["h"] / med["c"], 3)} if "g" in med else {}),
                   "repeats": REPEATS,
                   "all_s": {k: [round(t, 4) for t in v] for k, v in times.items()},
                   "unlinked_bitwise_equal": bool(off_same), "linked_equals_host_loop_bitwise": bool(loop_same),
