@@ -18,7 +18,8 @@ from typing import Dict, Iterable, List, Optional, Sequence, Union
 
 import numpy as np
 
-from . import _native, _program, actuator, alarm, control, detect, disturb, inject, junction, params, score, train, trend, wire
+from . import (_native, _program, actuator, alarm, control, detect, disturb, inject, junction, params, score, service, train,
+               trend, wire)
 
 logger = logging.getLogger(__name__)
 
@@ -487,6 +488,62 @@ class ReactorEnsemble:
         _native.check(_native.lib().wt_ensemble_sensors_history(self._h, v.ctypes.data_as(C.POINTER(C.c_float)), s.ctypes.data_as(u8),
                                                                 f.ctypes.data_as(u8), n.ctypes.data_as(C.POINTER(C.c_int32))))
         return v, s, f, n
+
+    # -- the service program: calibrate, clean and replace the instruments, on the device (wt_svc.hpp)
+    def set_services(self, *services: "service.Service") -> None:
+        """Run a service program of up to four :class:`Service` slots after every read, inside the step call: a slot
+        calibrates, cleans or replaces one sensor at a suite time (once or periodically) or some time after a read
+        returned a status; the action changes the next read, never the one just taken -- the bits of a host that
+        makes one-step calls and calls :meth:`service_sensors` in between.  Replaces any program and resets the slot
+        state.  Needs :meth:`enable_sensors` (not plant I/O) and at most 32 zones per reactor."""
+        blk = service.service_block(self.n_reactors, *services)
+        self._program_call(_native.lib().wt_ensemble_service_set, _native.dptr(blk))
+
+    def service_state(self) -> "service.ServiceState":
+        """Services done, the time of the last, the next due time and the open work order of every slot by reactor
+        (one synchronisation)."""
+        blk = np.empty((service.SLOTS, service.NSVS, self.n_reactors), dtype=np.float64)
+        self._program_call(_native.lib().wt_ensemble_service_get, _native.dptr(blk))
+        return service.ServiceState.from_block(blk)
+
+    def service_params(self) -> np.ndarray:
+        """The (4, 12, N) block of the service program in force, as :func:`service_block` built it."""
+        blk = np.empty((service.SLOTS, service.NSV, self.n_reactors), dtype=np.float64)
+        self._program_call(_native.lib().wt_ensemble_service_params, _native.dptr(blk))
+        return blk
+
+    def reset_services(self) -> None:
+        """Slot state back to its set-time values: counts 0, every timed slot due at its first time again, no work
+        order open.  The sensors keep what the services did to them."""
+        self._program_call(_native.lib().wt_ensemble_service_reset)
+
+    def clear_services(self) -> None:
+        """Stop the service program; the sensors keep what the services did to them."""
+        self._program_call(_native.lib().wt_ensemble_service_clear)
+
+    def service_sensors(self, sensor, action, ref=0.0, ref2=0.0, ref_mode="constant", mask=None) -> None:
+        """One maintenance action now, on one sensor of every reactor ``mask`` selects ((N,) bool; None: all): what a
+        :class:`Service` slot does when it falls due, at the time and with the taps of the stored state.  ``ref`` and
+        ``ref2``: scalars or (N,) arrays.  Works at any zone count."""
+        N = self.n_reactors
+        code = lambda v, names, what: int(_program.codes(v, names, what)) if isinstance(v, str) else int(v)
+        col = lambda v: np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (N,)))
+        m = None
+        if mask is not None:
+            m = np.ascontiguousarray(np.broadcast_to(np.asarray(mask), (N,)).astype(bool).astype(np.uint8))
+        self._program_call(_native.lib().wt_ensemble_sensors_service, code(sensor, _program.SENSOR_NAMES, "sensor"),
+                           code(action, service.ACTIONS, "action"), code(ref_mode, service.REF_MODES, "ref_mode"),
+                           _native.dptr(col(ref)), _native.dptr(col(ref2)),
+                           None if m is None else m.ctypes.data_as(C.POINTER(C.c_uint8)))
+
+    def sensor_health(self) -> Dict[str, np.ndarray]:
+        """What the maintenance decisions look at, by name of :data:`service.HEALTH_ROWS`, (7, N) float64 each: the
+        calibration offset and time, the power-on (warm-up) time, the three slow ageing fields of the sensor's kind
+        (pH: fouling, days since cleaning, reference contamination; amperometric: fouling, membrane age; DPD: potency,
+        light hours, reagent age; flow: electrode fouling), and the instrument's status and fault."""
+        out = np.empty((7, service.NSH, self.n_reactors), dtype=np.float64)
+        self._program_call(_native.lib().wt_ensemble_sensors_health, _native.dptr(out))
+        return {k: np.array(out[:, i]) for i, k in enumerate(service.HEALTH_ROWS)}
 
     # -- plant I/O: one virtual Modbus slave per reactor (NEXT-2 / NEXT-3)
     INPUT_REGISTERS = {"pH_inlet": 0, "pH_middle": 2, "pH_outlet": 4, "chlorine_inlet": 6, "chlorine_outlet": 8, "flow_rate": 10,

@@ -7,6 +7,7 @@
 #include <stdint.h>
 #include "wt_tables.hpp"
 #include "wt_sensors.hpp"
+#include "wt_svc.hpp"
 #include "wt_ctl.hpp"
 #include "wt_inj.hpp"
 #include "wt_alm.hpp"

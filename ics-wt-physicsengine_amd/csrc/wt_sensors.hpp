@@ -73,6 +73,10 @@ struct SuiteArgs {
     int32_t *hist_pos;     // [N] reads taken so far (next history slot)
     wtp::PackArgs pack;
     wtp::CommandArgs cmd;
+    // the service program (wt_svc.hpp): its arrays are the suite's, allocated with it; svc_on == 0: none is set
+    int svc_on;
+    const double *svc_par;    // [N][wtsv::PAR_DOUBLES]
+    double *svc_st;           // [N][wtsv::ST_DOUBLES]
 };
 
 // One wavefront's per-step hand-off between the lanes that integrate (one per zone), the lanes that run the
@@ -402,7 +406,14 @@ template <class A> __device__ __forceinline__ void emit(const A &a, int i, int64
 // state on through LDS, then the lanes of the RTDs take theirs.
 // rix[s]: ensemble index of the reactor in segment s; hist0[s]: reads reactor s had taken before this work
 // item; k: outer steps of the item completed before this one.  Leaves the readings in io.val / io.fault.
-template <class A> __device__ __forceinline__ void suite_step(const A &a, StepIO &io, const int *rix, int R, const int *hist0, int k)
+// sv: what happens to a sensor between this read and the next (wt_svc.hpp's service program; NoService: nothing),
+// called for every active lane after the read, also one that ended early, and before the state is stored.
+struct NoService {
+    template <class A> __device__ __forceinline__ void operator()(const A &, const SensorSpec &, SState &, int, const float *, int64_t, double, int) const {}
+};
+
+template <class A, class SV = NoService>
+__device__ __forceinline__ void suite_step(const A &a, StepIO &io, const int *rix, int R, const int *hist0, int k, SV sv = SV())
 {
     const int lane = threadIdx.x & 63;
     for (int base = 0; base < NSENS * R; base += 64) {
@@ -445,6 +456,7 @@ template <class A> __device__ __forceinline__ void suite_step(const A &a, StepIO
         }
         if (active) {
             if (go) read_finish(sp, st, c, t, fs, value, rstatus, rfault);
+            sv(a, sp, st, i, &io.tap[0][sl], r, t, rstatus);
             store_state(a, i, r, st);
             emit(a, i, r, pos, value, rstatus, rfault);
             io.val[i][sl] = value; io.fault[i][sl] = rfault;

@@ -226,7 +226,7 @@ ArrayGroup queue_arrays(wt_ensemble *h)
                                {(void **)&h->q_next, sizeof(int32_t) * (size_t)h->n_groups}}};
 }
 
-// the history arrays only for hist_cap > 0
+// the history arrays only for hist_cap > 0; the service program's records (wt_svc.hpp) come and go with the suite
 ArrayGroup sensor_arrays(wt_ensemble *h)
 {
     wts::SuiteArgs &s = h->sens;
@@ -241,9 +241,11 @@ ArrayGroup sensor_arrays(wt_ensemble *h)
                                {(void **)&s.out_value, sizeof(float) * wts::NSENS * N},
                                {(void **)&s.out_status, wts::NSENS * N}, {(void **)&s.out_fault, wts::NSENS * N},
                                {(void **)&s.t_enable, sizeof(double) * N},
+                               {(void **)&s.svc_par, sizeof(double) * wtsv::PAR_DOUBLES * N},
+                               {(void **)&s.svc_st, sizeof(double) * wtsv::ST_DOUBLES * N},
                                {(void **)&s.hist_value, sizeof(float) * hist}, {(void **)&s.hist_status, hist},
                                {(void **)&s.hist_fault, hist}, {(void **)&s.hist_pos, s.hist_cap > 0 ? sizeof(int32_t) * N : 0}},
-            [h] { h->sens.hist_cap = 0; }};
+            [h] { h->sens.hist_cap = 0; h->sens.svc_on = 0; }};
 }
 
 ArrayGroup plant_io_arrays(wt_ensemble *h)
@@ -1007,6 +1009,9 @@ int wt_ensemble_sensors_enable(wt_ensemble *h, uint64_t seed, int64_t reactor_ba
     if (e == hipSuccess) e = hipMemcpyAsync((double *)s.t_enable, h->time, sizeof(double) * N, hipMemcpyDeviceToDevice, h->stream);
     if (e == hipSuccess) e = hipMemsetAsync(s.ring_t, 0, sizeof(float) * 2 * wts::RING * N, h->stream);
     if (e == hipSuccess) e = hipMemsetAsync(s.ring_v, 0, sizeof(float) * 2 * wts::RING * N, h->stream);
+    // the service program's records, off: no slot enabled, no state (a checkpoint holds them whether or not one is set)
+    if (e == hipSuccess) e = hipMemsetAsync((void *)s.svc_par, 0, sizeof(double) * wtsv::PAR_DOUBLES * N, h->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(s.svc_st, 0, sizeof(double) * wtsv::ST_DOUBLES * N, h->stream);
     if (e == hipSuccess) {
         wts::SensorInitArgs a;
         a.N = h->N; a.cfg_flow = cfg; a.cfg_cl = cfg + N; a.cfg_temp = cfg + 2 * N;
@@ -1020,6 +1025,7 @@ int wt_ensemble_sensors_enable(wt_ensemble *h, uint64_t seed, int64_t reactor_ba
     (void)hipFree(cfg);
     if (e != hipSuccess) { release(arrays); return fail(WT_E_HIP, std::string("sensors_enable: ") + hipGetErrorString(e)); }
     s.seed_lo = (uint32_t)(seed & 0xffffffffu); s.seed_hi = (uint32_t)(seed >> 32); s.reactor_base = reactor_base;
+    s.svc_on = 0;                                // a freshly enabled suite has no service program
     s.on = 1;
     return WT_OK;
 }
@@ -1777,6 +1783,68 @@ int disturb_restore(wt_ensemble *h)
     return sync_checked(h);
 }
 
+// -- the sensor service program (wt_svc.hpp): its records are the suite's (sensor_arrays), its switch is sens.svc_on
+static_assert(WT_SVC_SLOTS == wtsv::SLOTS && WT_NSV == wtsv::NSV && WT_NSVS == wtsv::NSVS && WT_NSH == wtsv::NSH &&
+              WT_SV_ENABLE == wtsv::V_ENABLE && WT_SV_REF2 == wtsv::V_REF2 && WT_SVS_N_DONE == wtsv::VS_N_DONE &&
+              WT_SVS_T_SEEN == wtsv::VS_T_SEEN && WT_SVC_CALIBRATE == wtsv::A_CALIBRATE &&
+              WT_SVC_REPLACE_REAGENT == wtsv::A_REPLACE_REAGENT && WT_SVC_ON_STATUS == wtsv::TR_ON_STATUS &&
+              WT_SVC_REF_TRIM == wtsv::REF_TRIM && WT_SH_FAULT == wtsv::H_FAULT && WT_N_SENSORS == wts::NSENS,
+              "service blocks of the C ABI");
+const char *k_service_not_set = "no service program is set (wt_ensemble_service_set)";
+const char *k_service_no_suite = "the sensor suite is not enabled (wt_ensemble_sensors_enable)";
+
+// what the reference would raise for, and the codes: an action on a sensor with a reference mode
+const char *service_action_error(double sensor, double action, double ref_mode)
+{
+    if (!whole_in(sensor, 0, WT_N_SENSORS - 1)) return "sensor must be an integer in 0..6";
+    if (!whole_in(action, 0, wtsv::N_ACTIONS - 1)) return "action must be an integer in 0..6";
+    if (!whole_in(ref_mode, 0, wtsv::N_REF_MODES - 1)) return "ref_mode must be 0 (constant), 1 (sample) or 2 (trim)";
+    const int a = (int)action;
+    if (a >= wtsv::A_TWO_POINT && a <= wtsv::A_PEPSIN_CLEAN && sensor > 1.0)
+        return "two-point calibration and cleaning are for the pH sensors (0, 1)";
+    if (a == wtsv::A_REPLACE_MEMBRANE && sensor != 2.0) return "only the amperometric chlorine sensor (2) has a membrane to replace";
+    if (a == wtsv::A_REPLACE_REAGENT && sensor != 3.0) return "only the DPD chlorine sensor (3) has a reagent to replace";
+    if (a == wtsv::A_TWO_POINT && ref_mode != (double)wtsv::REF_CONSTANT)
+        return "a two-point calibration takes its buffers as constants (ref_mode 0)";
+    return nullptr;
+}
+
+// The first refusal of a [WT_SVC_SLOTS][WT_NSV][N] block: slot by slot over the reactors, rule by rule in the header's order.
+const char *service_error(int64_t N, const double *p)
+{
+    for (int k = 0; k < WT_SVC_SLOTS; ++k)
+        for (int64_t r = 0; r < N; ++r) {
+            const auto at = [&](int f) { return p[((int64_t)k * WT_NSV + f) * N + r]; };
+            if (!whole_in(at(WT_SV_ENABLE), 0, 1)) return "enable must be 0 or 1";
+            if (at(WT_SV_ENABLE) == 0.0) continue;
+            if (!whole_in(at(WT_SV_SENSOR), 0, WT_N_SENSORS - 1)) return "sensor must be an integer in 0..6";
+            if (!whole_in(at(WT_SV_ACTION), 0, wtsv::N_ACTIONS - 1)) return "action must be an integer in 0..6";
+            if (!whole_in(at(WT_SV_TRIGGER), 0, wtsv::N_TRIGGERS - 1)) return "trigger must be 0 (at_time) or 1 (on_status)";
+            if (const char *msg = service_action_error(at(WT_SV_SENSOR), at(WT_SV_ACTION), at(WT_SV_REF_MODE))) return msg;
+            for (const int f : {WT_SV_T_FIRST, WT_SV_PERIOD, WT_SV_DELAY})
+                if (!(std::isfinite(at(f)) && at(f) >= 0.0)) return "t_first, period and delay must be finite and >= 0";
+            if (at(WT_SV_PERIOD) != 0.0 && at(WT_SV_PERIOD) < wtsv::MIN_PERIOD) return "period must be 0 (once) or at least 0.001 s";
+            if (!whole_in(at(WT_SV_COUNT), 0, 9007199254740991.0)) return "count must be a whole number >= 0 (0: no cap)";
+            if (!whole_in(at(WT_SV_STATUS), 0, 11)) return "status must be an integer in 0..11 (a SensorStatus code)";
+            if (!(std::isfinite(at(WT_SV_REF)) && std::isfinite(at(WT_SV_REF2)))) return "ref and ref2 must be finite";
+        }
+    return nullptr;
+}
+
+// the slot state at its set-time values, from the program's records on the host: 0, NaN, t_first, NaN
+int service_restart(wt_ensemble *h, const std::vector<double> &par)
+{
+    std::vector<double> st((size_t)h->N * wtsv::ST_DOUBLES);
+    for (size_t r = 0; r < (size_t)h->N; ++r)
+        for (int k = 0; k < wtsv::SLOTS; ++k) {
+            double *q = st.data() + r * wtsv::ST_DOUBLES + k * wtsv::NSVS;
+            q[wtsv::VS_N_DONE] = 0.0; q[wtsv::VS_T_LAST] = NAN; q[wtsv::VS_T_SEEN] = NAN;
+            q[wtsv::VS_T_DUE] = par[r * wtsv::PAR_DOUBLES + k * wtsv::NSV + wtsv::V_T_FIRST];
+        }
+    if (int rc = upload(h, h->sens.svc_st, st)) return rc;
+    return sync_checked(h);                     // the host vector is freed on return
+}
+
 // ---- checkpoint, copy and rewind: one table of the handle's parts, which save, load, copy, mark,
 // rewind and destroy all walk.  A part is its ArrayGroup function, how many of the group's trailing arrays are scratch,
 // and its host scalars, field by field.  No pointer is a scalar: after a load the pointers are the destination's own
@@ -1829,7 +1897,8 @@ const Part k_parts[] = {
     {"QUEU", queue_arrays, 2, nullptr, nullptr},
     {"SENS", sensor_arrays, 0, [](wt_ensemble *h, Scalars &s) {
          s.insert(s.end(), {{S_I32, &h->sens.on, true}, {S_I32, &h->sens.hist_cap, true}, {S_U32, &h->sens.seed_lo, false},
-                            {S_U32, &h->sens.seed_hi, false}, {S_I64, &h->sens.reactor_base, false}}); }, nullptr},
+                            {S_U32, &h->sens.seed_hi, false}, {S_I64, &h->sens.reactor_base, false},
+                            {S_I32, &h->sens.svc_on, false}}); }, nullptr},   // (the service program's arrays are the suite's)
     {"PLIO", plant_io_arrays, 0, [](wt_ensemble *h, Scalars &s) { switch_only(&h->sens.plc_on, s); }, nullptr},
     {"RECD", record_arrays, 0, [](wt_ensemble *h, Scalars &s) {
          s.insert(s.end(), {{S_I32, &h->rec.every, false}, {S_I32, &h->rec.cap, true}, {S_I64, &h->rec.steps, false}}); },
@@ -1986,7 +2055,7 @@ const char *config_error(wt_ensemble *u)
     const auto flag = [](int v) { return v == 0 || v == 1; };
     if (!flag(u->sens.on) || !flag(u->sens.plc_on) || !flag(u->ctl.on) || !flag(u->inj.on) || !flag(u->alm.on) || !flag(u->act.on) ||
         !flag(u->dst.on) || !flag(u->scr.on) || !flag(u->det.on) || !flag(u->trn.on) || !flag(u->trn.pipe.on) || !flag(u->trn.jct.on) || !flag(u->wir.on) ||
-        !flag(u->trd.on) || !flag(u->trd.wrap))
+        !flag(u->sens.svc_on) || !flag(u->trd.on) || !flag(u->trd.wrap))
         return "range";
     if (u->placement != WT_PLACE_IDENTITY && u->placement != WT_PLACE_ADAPTIVE) return "range";
     if (u->sched_mode != WT_SCHED_STREAMS && u->sched_mode != WT_SCHED_QUEUE) return "range";
@@ -2001,6 +2070,7 @@ const char *config_error(wt_ensemble *u)
     if (u->trn.pipe.on ? (!u->trn.on || u->trn.pipe.slots < 1 || u->trn.pipe.slots > WT_PIPE_MAX_DELAY + 1) : u->trn.pipe.slots != 0) return "range";
     if (u->wir.on && (!u->trn.on || !u->sens.plc_on)) return "range";
     if (u->trn.jct.on && !u->trn.on) return "range";
+    if (u->sens.svc_on && (!u->sens.on || !wt::prog_in_item(levels_for(u->n)))) return "range";
     return nullptr;
 }
 
@@ -2645,6 +2715,122 @@ int wt_ensemble_junction_clear(wt_ensemble *h)
     return sync_checked(h);
 }
 
+int wt_service_check(int64_t n_reactors, const double *params)
+{
+    if (n_reactors < 1) return fail(WT_E_ARG, "n_reactors must be >= 1");
+    if (!params) return fail(WT_E_ARG, "NULL argument");
+    const char *msg = service_error(n_reactors, params);
+    return msg ? fail(WT_E_ARG, msg) : WT_OK;
+}
+
+int wt_ensemble_service_set(wt_ensemble *h, const double *params)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    if (!h->sens.on) return fail(WT_E_STATE, k_service_no_suite);
+    if (!wt::prog_in_item(levels_for(h->n))) return fail(WT_E_STATE, "service programs run in the kernels for up to 32 zones");
+    if (int rc = wt_service_check(h->N, params)) return rc;
+    std::vector<double> par((size_t)h->N * wtsv::PAR_DOUBLES);
+    blocks_to_records(params, wtsv::SLOTS, wtsv::NSV, h->N, par.data(), wtsv::PAR_DOUBLES);
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still use the old records
+    h->sens.svc_on = 0;
+    if (int rc = upload(h, (double *)h->sens.svc_par, par)) return rc;
+    if (int rc = service_restart(h, par)) return rc;
+    h->sens.svc_on = 1;
+    return WT_OK;
+}
+
+int wt_ensemble_service_get(wt_ensemble *h, double *state)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    if (!h->sens.svc_on) return fail(WT_E_STATE, k_service_not_set);
+    HIP_TRY(hipSetDevice(h->device));
+    return download_records(h, {{state, h->sens.svc_st, wtsv::ST_DOUBLES, wtsv::SLOTS, wtsv::NSVS}});
+}
+
+int wt_ensemble_service_params(wt_ensemble *h, double *params)
+{
+    if (!h || !params) return fail(WT_E_ARG, "NULL argument");
+    if (!h->sens.svc_on) return fail(WT_E_STATE, k_service_not_set);
+    HIP_TRY(hipSetDevice(h->device));
+    return download_records(h, {{params, h->sens.svc_par, wtsv::PAR_DOUBLES, wtsv::SLOTS, wtsv::NSV}});
+}
+
+int wt_ensemble_service_reset(wt_ensemble *h)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    if (!h->sens.svc_on) return fail(WT_E_STATE, k_service_not_set);
+    HIP_TRY(hipSetDevice(h->device));
+    std::vector<double> par((size_t)h->N * wtsv::PAR_DOUBLES);
+    if (int rc = download(h, {{par.data(), h->sens.svc_par, sizeof(double) * par.size()}})) return rc;
+    return service_restart(h, par);
+}
+
+int wt_ensemble_service_clear(wt_ensemble *h)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    if (!h->sens.svc_on) return WT_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still use the records
+    h->sens.svc_on = 0;
+    return WT_OK;
+}
+
+int wt_ensemble_sensors_service(wt_ensemble *h, int sensor, int action, int ref_mode, const double *ref, const double *ref2,
+                                const uint8_t *mask)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    if (!h->sens.on) return fail(WT_E_STATE, k_service_no_suite);
+    if (const char *msg = service_action_error((double)sensor, (double)action, (double)ref_mode)) return fail(WT_E_ARG, msg);
+    const size_t N = (size_t)h->N;
+    for (const double *v : {ref, ref2})
+        for (size_t r = 0; v && r < N; ++r)
+            if (!std::isfinite(v[r])) return fail(WT_E_ARG, "ref and ref2 must be finite");
+    HIP_TRY(hipSetDevice(h->device));
+    // one device block for what the call brings: ref, ref2, then the mask
+    double *in = nullptr;
+    HIP_TRY(hipMalloc((void **)&in, sizeof(double) * 2 * N + N));
+    uint8_t *m = (uint8_t *)(in + 2 * N);
+    hipError_t e = hipSuccess;
+    if (ref) e = hipMemcpyAsync(in, ref, sizeof(double) * N, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess && ref2) e = hipMemcpyAsync(in + N, ref2, sizeof(double) * N, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess && mask) e = hipMemcpyAsync(m, mask, N, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) {
+        const wtsv::ServiceArgs a{h->sens, h->pH, h->Cl, h->T, h->time, h->flow, h->n, sensor, action, ref_mode,
+                                  ref ? in : nullptr, ref2 ? in + N : nullptr, mask ? m : nullptr};
+        hipLaunchKernelGGL(wtsv::service_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, h->stream, a);
+        e = hipGetLastError();
+    }
+    const int rc = e == hipSuccess ? sync_checked(h) : ((void)hipStreamSynchronize(h->stream), fail(WT_E_HIP, std::string("sensors_service: ") + hipGetErrorString(e)));
+    (void)hipFree(in);
+    return rc;
+}
+
+int wt_ensemble_sensors_health(wt_ensemble *h, double *out)
+{
+    if (!h || !out) return fail(WT_E_ARG, "NULL argument");
+    if (!h->sens.on) return fail(WT_E_STATE, k_service_no_suite);
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t N = (size_t)h->N;
+    std::vector<float> fs(wts::NSENS * wts::NF * N);
+    std::vector<double> ds(wts::NSENS * wts::ND * N);
+    std::vector<int32_t> is(wts::NSENS * wts::NI * N);
+    if (int rc = download(h, {{fs.data(), h->sens.fs, sizeof(float) * fs.size()}, {ds.data(), h->sens.ds, sizeof(double) * ds.size()},
+                              {is.data(), h->sens.is, sizeof(int32_t) * is.size()}}))
+        return rc;
+    for (size_t i = 0; i < (size_t)wts::NSENS; ++i)
+        for (size_t r = 0; r < N; ++r) {
+            double *o = out + i * WT_NSH * N + r;
+            const double *D = ds.data() + i * wts::ND * N + r;
+            o[WT_SH_CAL_OFFSET * N] = (double)fs[(i * wts::NF + wts::F_CAL_OFFSET) * N + r];
+            o[WT_SH_CAL_TIME * N] = D[wts::D_CAL_TIME * N]; o[WT_SH_POWER_ON * N] = D[wts::D_POWER_ON * N];
+            o[WT_SH_SLOW0 * N] = D[wts::D_SLOW0 * N]; o[WT_SH_SLOW1 * N] = D[wts::D_SLOW1 * N]; o[WT_SH_SLOW2 * N] = D[wts::D_SLOW2 * N];
+            o[WT_SH_STATUS * N] = (double)is[(i * wts::NI + wts::I_STATUS) * N + r];
+            o[WT_SH_FAULT * N] = (double)is[(i * wts::NI + wts::I_FAULT) * N + r];
+        }
+    return WT_OK;
+}
+
 int wt_wire_check(int length, int64_t n_reactors, const double *params)
 {
     if (n_reactors < 1) return fail(WT_E_ARG, "n_reactors must be >= 1");
@@ -2877,6 +3063,7 @@ int wt_ensemble_info(wt_ensemble *h, int what, int64_t *value)
     case WT_INFO_BOUNDARY_UPLOADS: *value = h->bc_uploads; break;
     case WT_INFO_MARK: *value = h->mark != nullptr; break;
     case WT_INFO_JUNCTION: *value = h->trn.jct.on != 0; break;
+    case WT_INFO_SERVICE: *value = h->sens.svc_on != 0; break;
     default: return fail(WT_E_ARG, "unknown info code");
     }
     return WT_OK;

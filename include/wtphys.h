@@ -285,7 +285,8 @@ enum {
     WT_INFO_BOUNDARY_UPLOADS = 18,
     WT_INFO_WIRE = 19,                    /* a wire program is set */
     WT_INFO_MARK = 20,                    /* a mark is set (wt_ensemble_mark) */
-    WT_INFO_JUNCTION = 21                 /* a junction program is set */
+    WT_INFO_JUNCTION = 21,                /* a junction program is set */
+    WT_INFO_SERVICE = 22                  /* a sensor service program is set */
 };
 int wt_ensemble_info(wt_ensemble *h, int what, int64_t *value);
 
@@ -953,6 +954,95 @@ int wt_ensemble_junction_clear(wt_ensemble *h);
  * call's message (also "n_reactors must be >= 1", "length must be in 2..32 (the length of the train program)", "NULL
  * argument").  Makes no HIP call. */
 int wt_junction_check(int length, int64_t n_reactors, const double *train_params, const double *params, const double *carry);
+
+/* ---- the sensor service program: calibrate, clean and replace the instruments inside fused runs ----
+ * The maintenance half of the reference's sensor interface, which its loop would call between two iterations:
+ * BaseSensor.calibrate (base_sensor.py:701-755), pHSensor.calibrate_two_point and clean_electrode (ph_sensor.py:338-434),
+ * ChlorineSensor.replace_membrane and replace_reagent (chlorine_sensor.py:486-537).  All are deterministic and draw
+ * nothing.  With t the suite time (ReactorState.time minus its value at wt_ensemble_sensors_enable) and x the float32
+ * reference value, an action does to its sensor what the reference call does to the fields a reading depends on:
+ *   WT_SVC_CALIBRATE         cal_offset = x - current; cal_time = power_on = t; status NORMAL; fault NONE
+ *   WT_SVC_TWO_POINT         reference_contamination = 0, then CALIBRATE with x = (ref + ref2) / 2
+ *   WT_SVC_RINSE / _ACID_CLEAN / _PEPSIN_CLEAN   membrane_fouling *= 0.5 / 0.1 / 0.2; days_since_cleaning = 0; power_on = t
+ *   WT_SVC_REPLACE_MEMBRANE  membrane_fouling = membrane_age = 0, then CALIBRATE with x = 0
+ *   WT_SVC_REPLACE_REAGENT   reagent_potency = 1; light exposure = reagent age = 0, then CALIBRATE with x = 0
+ * calibrate replaces the offset as the reference does (it does not accumulate): a trim is WT_SVC_REF_TRIM.
+ * Reference value: WT_SVC_REF_CONSTANT x = ref; _SAMPLE x = tap + ref; _TRIM x = (tap + cal_offset) + ref, in fp64 and
+ * rounded once to float32, tap being the float32 true value at the sensor's own tap (zone 0 or the last zone, or the
+ * flow) and cal_offset the offset in force.
+ * Program.  Up to WT_SVC_SLOTS slots per reactor, parameters [WT_SVC_SLOTS][WT_NSV][N]: enable (0 or 1), sensor (0..6,
+ * WT_N_SENSORS order), action, trigger, t_first, period, count, status, delay, ref_mode, ref, ref2.  Slot state
+ * [WT_SVC_SLOTS][WT_NSVS][N]: n_done, t_last, t_due, t_seen; at set and reset 0, NaN, t_first, NaN.  After every read
+ * of a reactor that stepped (a read that ended in WARMING_UP or POWER_FAULT included), at the read's suite time t and
+ * with s the status that read returned, the enabled slots are walked in ascending order, in fp64 without fused
+ * multiply-adds:
+ *   if count > 0 and n_done >= count: nothing;
+ *   AT_TIME:   due = t >= t_due
+ *   ON_STATUS: if t_seen is NaN and s == status: t_seen = t;   due = t - t_seen >= delay   (NaN: not due; the order
+ *              stands even if the status clears)
+ *   if due: the action is applied (a later slot of the same sensor sees its result), n_done += 1, t_last = t, and
+ *     AT_TIME:   t_due = period > 0 ? t_due + (floor((t - t_due) / period) + 1) * period, plus period once more if
+ *                that is not > t : +inf          ON_STATUS: t_seen = NaN
+ * A service acts on the next read, never on the one just taken: the bits of a host that makes one-step calls and calls
+ * wt_ensemble_sensors_service in between.  Needs the sensor suite and n <= 32 zones (WT_E_STATE: "the sensor suite is
+ * not enabled (wt_ensemble_sensors_enable)", "service programs run in the kernels for up to 32 zones"), not plant I/O.
+ * set replaces any program; reset puts the slot state back to its set-time values; get, params and reset give
+ * WT_E_STATE, "no service program is set (wt_ensemble_service_set)", while none is.  wt_ensemble_sensors_enable starts
+ * without a program.  Checkpoints, copies and marks carry the program.  The program takes no code of wt_program_check:
+ * wt_service_check is its check, with no handle and no device.  Refused with WT_E_ARG, slot by slot over the reactors, at
+ * one slot and reactor in this order ("n_reactors must be >= 1" and "NULL argument" before them):
+ *   "enable must be 0 or 1"                                     (a slot with enable 0 is not looked at further)
+ *   "sensor must be an integer in 0..6"
+ *   "action must be an integer in 0..6"
+ *   "trigger must be 0 (at_time) or 1 (on_status)"
+ *   "ref_mode must be 0 (constant), 1 (sample) or 2 (trim)"
+ *   "two-point calibration and cleaning are for the pH sensors (0, 1)"
+ *   "only the amperometric chlorine sensor (2) has a membrane to replace"
+ *   "only the DPD chlorine sensor (3) has a reagent to replace"
+ *   "a two-point calibration takes its buffers as constants (ref_mode 0)"
+ *   "t_first, period and delay must be finite and >= 0"
+ *   "period must be 0 (once) or at least 0.001 s"
+ *   "count must be a whole number >= 0 (0: no cap)"
+ *   "status must be an integer in 0..11 (a SensorStatus code)"
+ *   "ref and ref2 must be finite"
+ * Immediate service.  wt_ensemble_sensors_service applies one action now to one sensor of every reactor with
+ * mask[r] != 0 (NULL: all), at t = ReactorState.time - the enable time and with the taps of the stored state: for a
+ * reactor that has just stepped, what the fused read used.  ref / ref2: host [N] or NULL for 0.  Any zone count; the
+ * action, sensor and ref_mode rules above apply (WT_E_ARG).  wt_ensemble_sensors_health downloads what the reference's
+ * maintenance decisions look at, [WT_N_SENSORS][WT_NSH][N]: cal_offset, cal_time, power_on, the three slow ageing
+ * fields of the sensor's kind (pH: fouling, days since cleaning, reference contamination; amperometric: fouling,
+ * membrane age; DPD: potency, light hours, reagent age; flow: electrode fouling), status and fault of the instrument.
+ * All calls synchronise. */
+#define WT_SVC_SLOTS 4
+enum {
+    WT_SVC_CALIBRATE = 0, WT_SVC_TWO_POINT = 1, WT_SVC_RINSE = 2, WT_SVC_ACID_CLEAN = 3, WT_SVC_PEPSIN_CLEAN = 4,
+    WT_SVC_REPLACE_MEMBRANE = 5, WT_SVC_REPLACE_REAGENT = 6
+};
+enum { WT_SVC_AT_TIME = 0, WT_SVC_ON_STATUS = 1 };
+enum { WT_SVC_REF_CONSTANT = 0, WT_SVC_REF_SAMPLE = 1, WT_SVC_REF_TRIM = 2 };
+enum {
+    WT_SV_ENABLE = 0, WT_SV_SENSOR = 1, WT_SV_ACTION = 2, WT_SV_TRIGGER = 3, WT_SV_T_FIRST = 4, WT_SV_PERIOD = 5,
+    WT_SV_COUNT = 6, WT_SV_STATUS = 7, WT_SV_DELAY = 8, WT_SV_REF_MODE = 9, WT_SV_REF = 10, WT_SV_REF2 = 11,
+    WT_NSV = 12
+};
+enum { WT_SVS_N_DONE = 0, WT_SVS_T_LAST = 1, WT_SVS_T_DUE = 2, WT_SVS_T_SEEN = 3, WT_NSVS = 4 };
+enum {
+    WT_SH_CAL_OFFSET = 0, WT_SH_CAL_TIME = 1, WT_SH_POWER_ON = 2, WT_SH_SLOW0 = 3, WT_SH_SLOW1 = 4, WT_SH_SLOW2 = 5,
+    WT_SH_STATUS = 6, WT_SH_FAULT = 7,
+    WT_NSH = 8
+};
+int wt_ensemble_service_set(wt_ensemble *h, const double *params /* [WT_SVC_SLOTS][WT_NSV][N] */);
+/* host [WT_SVC_SLOTS][WT_NSVS][N] slot state */
+int wt_ensemble_service_get(wt_ensemble *h, double *state);
+/* the program in force as set took it: host [WT_SVC_SLOTS][WT_NSV][N] */
+int wt_ensemble_service_params(wt_ensemble *h, double *params);
+int wt_ensemble_service_reset(wt_ensemble *h);
+/* program off (no effect while none is set); what the services did to the sensors stays */
+int wt_ensemble_service_clear(wt_ensemble *h);
+int wt_service_check(int64_t n_reactors, const double *params);
+int wt_ensemble_sensors_service(wt_ensemble *h, int sensor, int action, int ref_mode, const double *ref /* [N] or NULL */,
+                                const double *ref2 /* [N] or NULL */, const uint8_t *mask /* [N] or NULL */);
+int wt_ensemble_sensors_health(wt_ensemble *h, double *out /* [WT_N_SENSORS][WT_NSH][N] */);
 
 /* ---- the parameter checks of the scan programs, the disturbance and the score program, without a handle or a device ----
  * params: host, the block the program's set or enable call takes, for n_reactors reactors (WT_PROG_CONTROL:
