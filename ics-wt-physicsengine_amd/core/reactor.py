@@ -19,7 +19,7 @@ from typing import Dict, Iterable, List, Optional, Sequence, Union
 import numpy as np
 
 from . import (_native, _program, actuator, alarm, control, detect, disturb, inject, junction, params, score, service, train,
-               trend, wire)
+               trend, tune, wire)
 
 logger = logging.getLogger(__name__)
 
@@ -651,6 +651,38 @@ class ReactorEnsemble:
         blk = np.empty((len(control.LOOPS), control.NCS, self.n_reactors), dtype=np.float64)
         self._program_call(_native.lib().wt_ensemble_control_get, _native.dptr(blk))
         return control.ControlState.from_block(blk)
+
+    # -- relay autotune programs at every PLC scan, before the PI programs, on the device (wt_tun.hpp)
+    def set_tuners(self, chlorine: Optional["tune.RelayTune"] = None, acid: Optional["tune.RelayTune"] = None) -> None:
+        """Run up to two relay experiments per reactor at the PLC scans, inside the step call: ``chlorine`` owns the
+        chlorine_flow_rate holding register while it runs, ``acid`` the acid_flow_rate one, and the PI loop of that
+        register is skipped meanwhile.  An experiment starts at the first scan whose loop time reaches its ``start``;
+        with ``commission`` it writes the gains it found into the PI loop (:meth:`enable_control` first).  Replaces any
+        program and resets the state.  Needs :meth:`enable_plant_io` and at most 32 zones per reactor."""
+        blk = tune.tune_block(self.n_reactors, chlorine, acid)
+        self._program_call(_native.lib().wt_ensemble_tune_set, _native.dptr(blk))
+
+    def tuner_state(self) -> "tune.TunerState":
+        """Phase, relay, cycle sums, period, amplitude, Ku and the gains of both tuners by reactor (one
+        synchronisation)."""
+        blk = np.empty((len(control.LOOPS), tune.NUS, self.n_reactors), dtype=np.float64)
+        self._program_call(_native.lib().wt_ensemble_tune_get, _native.dptr(blk))
+        return tune.TunerState.from_block(blk)
+
+    def tuner_params(self) -> np.ndarray:
+        """The (2, 14, N) block of the tune program in force, as :func:`tune_block` built it."""
+        blk = np.empty((len(control.LOOPS), tune.NU, self.n_reactors), dtype=np.float64)
+        self._program_call(_native.lib().wt_ensemble_tune_params, _native.dptr(blk))
+        return blk
+
+    def reset_tuners(self) -> None:
+        """Every tuner waiting again, its state zeroed: an experiment whose ``start`` has passed begins again at the
+        next scan.  Gains already commissioned stay in the PI loops."""
+        self._program_call(_native.lib().wt_ensemble_tune_reset)
+
+    def clear_tuners(self) -> None:
+        """Stop the tune program; the holding registers and commissioned gains stay as they are."""
+        self._program_call(_native.lib().wt_ensemble_tune_clear)
 
     # -- injection programs at every PLC scan, on the device (wt_inj.hpp)
     def set_injections(self, *injections: "inject.Injection") -> None:

@@ -1,5 +1,5 @@
 // wt_args.hpp -- the step kernel's argument block: StepArgs (filled by the host, wtphys.hip: make_args) with the
-// argument structs of the sensor suite, the plant I/O, the eight per-reactor programs, the train and the wire program inside it, the words of the
+// argument structs of the sensor suite, the plant I/O, the eight per-reactor programs, the train, the wire and the tune program inside it, the words of the
 // work queue's control block, which kernel instantiations carry which sections, and fresh(): how a section of a work
 // item re-reads what it needs from the kernel-argument segment.
 #pragma once
@@ -9,6 +9,7 @@
 #include "wt_sensors.hpp"
 #include "wt_svc.hpp"
 #include "wt_ctl.hpp"
+#include "wt_tun.hpp"
 #include "wt_inj.hpp"
 #include "wt_alm.hpp"
 #include "wt_det.hpp"
@@ -79,6 +80,7 @@ struct StepArgs {
     wtt::TrdArgs trd;    // per-reactor trend recorder programs run at PLC scans (wt_ensemble_trend_*; trd.on == 0: none)
     wtr::TrnArgs trn;    // the train program: stages feed their downstream after every outer step (wt_ensemble_train_*; trn.on == 0: none)
     wtw::WirArgs wir;    // the wire program: a train's signal cables, routed at the head of a PLC scan (wt_ensemble_wire_*; wir.on == 0: none)
+    wtu::TunArgs tun;    // per-reactor relay autotune programs run at PLC scans before the PI programs (wt_ensemble_tune_*; tun.on == 0: none)
 };
 static_assert(sizeof(StepArgs) <= 4096, "the kernel-argument segment holds at most 4 KiB");
 constexpr int NB = 10;     // rows of a boundary block (WT_NB)
@@ -89,7 +91,8 @@ __host__ __device__ constexpr bool x_in_item(int LV) { return LV <= 5; }
 // scratch and 4 VGPR spills, with or without a program, so it compiles the sections out and wt_ensemble_inject_set,
 // _alarm_set, _actuator_set, _disturb_set, _score_set, _detect_set and _trend_set refuse ensembles of more than 32 zones.
 // The train program's feed (wt_trn.hpp) shares the disturbance section; a train of two stages needs n <= 32 anyway,
-// and so does the wire program on top of it (wt_wir.hpp).
+// and so does the wire program on top of it (wt_wir.hpp).  The tune program (wt_tun.hpp) is in the same kernels only, and
+// wt_ensemble_tune_set refuses more than 32 zones with the others' wording.
 __host__ __device__ constexpr bool prog_in_item(int LV) { return LV <= 5; }
 enum { Q_AVAIL = 0, Q_HEAD = 1, Q_TAIL = 2, Q_ERROR = 3, Q_TRACE = 4, Q_DONE = 5, Q_WORDS = 16 };
 

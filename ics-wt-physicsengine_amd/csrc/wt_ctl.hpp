@@ -6,6 +6,8 @@
 //   pi_execute   runs at a PLC scan, in the lane of a reactor that stepped, AFTER pack_inputs and apply_commands of
 //                that scan (wt_plc.hpp): its output acts from the next scan on, exactly like a host master's
 //                write_commands between two calls.  Loop 0 doses chlorine (holding words 2-3), loop 1 acid (words 0-1).
+//                skip: bit l set -- the tune program (wt_tun.hpp) owned loop l in this scan: the loop changes no state
+//                and writes no word; the shared t_prev still advances.  0: every enabled loop runs.
 //
 // Device layout (array of structures: the scan lane reads one reactor's record with wide loads):
 //   par [N][LOOPS][NC] fp64   enable, sensor, direction, setpoint, kp, ki, bias, out_min, out_max
@@ -37,7 +39,7 @@ struct CtlArgs {
 // a: CtlArgs (read in place from the kernel arguments); value / fault: this scan's seven raw readings of reactor r
 // (element i at [i * stride], LDS); t_now: the loop time the scan stores.  Every operation below is spelled out in the
 // order of tests/control_ref.py and nothing is contracted into an fma, so the host restatement gives the same bits.
-template <class A> __device__ __forceinline__ void pi_execute(const A &a, int64_t r, const float *value, const int *fault, int stride, double t_now)
+template <class A> __device__ __forceinline__ void pi_execute(const A &a, int64_t r, const float *value, const int *fault, int stride, double t_now, int skip = 0)
 {
 #pragma clang fp contract(off)
     double *s = a.st + r * ST_DOUBLES;
@@ -50,7 +52,7 @@ template <class A> __device__ __forceinline__ void pi_execute(const A &a, int64_
 #pragma unroll
         for (int i = 0; i < (NC + 1) / 2; ++i) { const double2 q = p2[i]; p[2 * i] = q.x; p[2 * i + 1] = q.y; }
         const double *c = p + l;   // loop 1's record starts one double into its first pair
-        if (c[C_ENABLE] == 0.0) continue;
+        if (c[C_ENABLE] == 0.0 || ((skip >> l) & 1)) continue;
         double *q = s + l * NCS;
         const int si = (int)c[C_SENSOR];
         const float v = value[si * stride];

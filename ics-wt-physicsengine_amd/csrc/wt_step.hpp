@@ -719,12 +719,22 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
                     }
                     b->sens.pack.loop_time[rr] = lt + dt;                 // sim_time += dt (__main__.py:446)
                 }
+                // the tune program (wave-uniform flag), immediately before the PLC program and with its inputs: a relay
+                // experiment owns its loop's holding words; owned: the loops the PLC program skips in this scan
+                int owned = 0;
+                if constexpr (prog_in_item(LV)) {
+                  if (scan && WT_RARE(fresh(pa)->tun.on) && lane < R && io.stepped[lane]) {
+                    ArgPtr up = fresh(pa);
+                    const int64_t rr = rix[lane];
+                    owned = wtu::tune_execute(up->tun, up->ctl, rr, &io.val[0][lane], &io.fault[0][lane], wts::RMAX, up->sens.pack.loop_time[rr]);
+                  }
+                }
                 // the PLC program, after the scan's command path: its commands act from the next scan on, like a host
                 // master's between two calls; t_now is the loop time just stored
                 if (scan && WT_RARE(fresh(pa)->ctl.on) && lane < R && io.stepped[lane]) {
                     ArgPtr cp = fresh(pa);
                     const int64_t rr = rix[lane];
-                    wtc::pi_execute(cp->ctl, rr, &io.val[0][lane], &io.fault[0][lane], wts::RMAX, cp->sens.pack.loop_time[rr]);
+                    wtc::pi_execute(cp->ctl, rr, &io.val[0][lane], &io.fault[0][lane], wts::RMAX, cp->sens.pack.loop_time[rr], owned);
                 }
                 // the alarm program, after the PLC program: IMAGE slots read this lane's (possibly tampered) copy,
                 // FIELD slots what the sensor lanes stored before the barrier above; its trips act from the next scan on

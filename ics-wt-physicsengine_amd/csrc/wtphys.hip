@@ -121,6 +121,8 @@ struct wt_ensemble {
     int R0 = 0;
     // The wire program on top of it (wt_wir.hpp): no switch of its own beyond wir.on, no host copy.
     wtw::WirArgs wir = {};
+    // The tune program (wt_tun.hpp; beside k_programs): its records are plant I/O's arrays, its switch a PLIO scalar.
+    wtu::TunArgs tun = {};
     // optional per-launch HIP-event timing (bench.py roofline accounting)
     bool time_launches = false;
     std::vector<hipEvent_t> lt_pool;   // start/stop pairs
@@ -158,7 +160,7 @@ wt::StepArgs make_args(const wt_ensemble *h, double dt, int n_steps, int first_s
     a.trace = h->trace; a.trace_cap = h->trace_cap;
     a.kt = wt::default_ktab(); a.rt = wt::default_rtab();
     a.kt.dense_bias = h->knob_dense ? 1.0 : 0.0;
-    a.sens = h->sens; a.ctl = h->ctl; a.inj = h->inj; a.alm = h->alm; a.act = h->act; a.dst = h->dst; a.scr = h->scr; a.det = h->det; a.trd = h->trd; a.trn = h->trn; a.wir = h->wir;
+    a.sens = h->sens; a.ctl = h->ctl; a.inj = h->inj; a.alm = h->alm; a.act = h->act; a.dst = h->dst; a.scr = h->scr; a.det = h->det; a.trd = h->trd; a.trn = h->trn; a.wir = h->wir; a.tun = h->tun;
     // a full curve takes no more entries: the launches then carry no curve pointer at all
     const bool curve = h->scr.counts && h->scr_steps < h->scr.curve_cap;
     if (!curve) a.scr.counts = nullptr;
@@ -248,13 +250,17 @@ ArrayGroup sensor_arrays(wt_ensemble *h)
             [h] { h->sens.hist_cap = 0; h->sens.svc_on = 0; }};
 }
 
+// the tune program's records (wt_tun.hpp) come and go with plant I/O
 ArrayGroup plant_io_arrays(wt_ensemble *h)
 {
     const size_t N = (size_t)h->N;
     return {"plc_enable", &h->sens.plc_on, {{(void **)&h->sens.pack.ir, sizeof(uint16_t) * wtp::IR_WORDS * N},
                                             {(void **)&h->ctl.hr, sizeof(uint16_t) * wtp::HR_WORDS * N},
                                             {(void **)&h->sens.pack.loop_time, sizeof(double) * N},
-                                            {(void **)&h->sens.pack.update_ok, N}}};
+                                            {(void **)&h->sens.pack.update_ok, N},
+                                            {(void **)&h->tun.par, sizeof(double) * wtu::PAR_DOUBLES * N},
+                                            {(void **)&h->tun.st, sizeof(double) * wtu::ST_DOUBLES * N}},
+            [h] { h->tun.on = 0; }};
 }
 
 ArrayGroup record_arrays(wt_ensemble *h)
@@ -1070,9 +1076,13 @@ int wt_ensemble_plc_enable(wt_ensemble *h)
     if (e == hipSuccess) e = hipMemsetAsync(h->ctl.hr, 0, sizeof(uint16_t) * wtp::HR_WORDS * N, h->stream);
     if (e == hipSuccess) e = hipMemsetAsync(p.loop_time, 0, sizeof(double) * N, h->stream);
     if (e == hipSuccess) e = hipMemsetAsync(p.update_ok, 1, N, h->stream);
+    // the tune program's records, off: no loop enabled, no state (a checkpoint holds them whether or not one is set)
+    if (e == hipSuccess) e = hipMemsetAsync((void *)h->tun.par, 0, sizeof(double) * wtu::PAR_DOUBLES * N, h->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(h->tun.st, 0, sizeof(double) * wtu::ST_DOUBLES * N, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) { release(arrays); return fail(WT_E_HIP, std::string("plc_enable: ") + hipGetErrorString(e)); }
     h->sens.cmd.hr = h->ctl.hr;
+    h->tun.on = 0;                               // freshly enabled plant I/O has no tune program
     h->sens.plc_on = 1;
     return WT_OK;
 }
@@ -1845,6 +1855,50 @@ int service_restart(wt_ensemble *h, const std::vector<double> &par)
     return sync_checked(h);                     // the host vector is freed on return
 }
 
+// -- the tune program (wt_tun.hpp): its records are plant I/O's (plant_io_arrays), its switch is tun.on
+static_assert(WT_TUN_LOOPS == wtu::LOOPS && WT_TUN_LOOPS == WT_CTL_LOOPS && WT_NU == wtu::NU && WT_NUS == wtu::NUS &&
+              WT_TUN_ENABLE == wtu::U_ENABLE && WT_TUN_AMPLITUDE == wtu::U_AMPLITUDE && WT_TUN_COMMISSION == wtu::U_COMMISSION &&
+              WT_TUNS_PHASE == wtu::US_PHASE && WT_TUNS_N_CYCLES == wtu::US_N_CYCLES && WT_TUNS_KU == wtu::US_KU &&
+              WT_TUNS_COMMISSIONED == wtu::US_COMMISSIONED && WT_TUN_DONE == wtu::PH_DONE && WT_TUN_FAILED == wtu::PH_FAILED &&
+              WT_TUN_MAX_CYCLES == wtu::MAX_CYCLES, "tune blocks of the C ABI");
+const char *k_tune_not_set = "no tune program is set (wt_ensemble_tune_set)";
+// validate_flow_rate's maxima (__main__.py:57-63, :236-242) by loop: chlorine, acid
+constexpr double k_command_limit[WT_TUN_LOOPS] = {1.0, 2.0};
+
+// The first refusal of a [WT_TUN_LOOPS][WT_NU][N] block: loop by loop over the reactors, rule by rule in the header's order.
+const char *tune_error(int64_t N, const double *p)
+{
+    for (int l = 0; l < WT_TUN_LOOPS; ++l)
+        for (int64_t r = 0; r < N; ++r) {
+            const auto at = [&](int f) { return p[((int64_t)l * WT_NU + f) * N + r]; };
+            if (!whole_in(at(WT_TUN_ENABLE), 0, 1)) return "enable must be 0 or 1";
+            if (at(WT_TUN_ENABLE) == 0.0) continue;
+            if (!whole_in(at(WT_TUN_SENSOR), 0, WT_N_SENSORS - 1)) return "sensor must be an integer in 0..6";
+            if (at(WT_TUN_DIRECTION) != 1.0 && at(WT_TUN_DIRECTION) != -1.0) return "direction must be +1 or -1";
+            if (!(std::isfinite(at(WT_TUN_SETPOINT)) && std::isfinite(at(WT_TUN_BIAS)))) return "setpoint and bias must be finite";
+            const double d = at(WT_TUN_AMPLITUDE), b = at(WT_TUN_BIAS);
+            if (!(std::isfinite(d) && d > 0.0)) return "amplitude must be finite and > 0";
+            if (!(b - d >= 0.0 && b + d <= k_command_limit[l]))
+                return "bias - amplitude must be >= 0 and bias + amplitude at most the loop's command limit (1.0 chlorine, 2.0 acid)";
+            if (!(std::isfinite(at(WT_TUN_HYSTERESIS)) && at(WT_TUN_HYSTERESIS) >= 0.0)) return "hysteresis must be finite and >= 0";
+            if (!std::isfinite(at(WT_TUN_T_START))) return "t_start must be finite";
+            if (!(at(WT_TUN_T_MAX) > 0.0)) return "t_max must be > 0 (+inf: no time-out)";
+            if (!whole_in(at(WT_TUN_SETTLE), 0, 9007199254740991.0)) return "settle must be a whole number >= 0";
+            if (!whole_in(at(WT_TUN_CYCLES), 1, WT_TUN_MAX_CYCLES)) return "cycles must be an integer in 1..4096";
+            for (const int f : {WT_TUN_KP_FACTOR, WT_TUN_TI_FACTOR})
+                if (!(std::isfinite(at(f)) && at(f) >= 0.0)) return "kp_factor and ti_factor must be finite and >= 0";
+            if (!whole_in(at(WT_TUN_COMMISSION), 0, 1)) return "commission must be 0 or 1";
+        }
+    return nullptr;
+}
+
+// every loop waiting: the state all 0 (set and reset); queued on the handle's stream
+int tune_restart(wt_ensemble *h)
+{
+    HIP_TRY(hipMemsetAsync(h->tun.st, 0, sizeof(double) * wtu::ST_DOUBLES * (size_t)h->N, h->stream));
+    return WT_OK;
+}
+
 // ---- checkpoint, copy and rewind: one table of the handle's parts, which save, load, copy, mark,
 // rewind and destroy all walk.  A part is its ArrayGroup function, how many of the group's trailing arrays are scratch,
 // and its host scalars, field by field.  No pointer is a scalar: after a load the pointers are the destination's own
@@ -1899,7 +1953,8 @@ const Part k_parts[] = {
          s.insert(s.end(), {{S_I32, &h->sens.on, true}, {S_I32, &h->sens.hist_cap, true}, {S_U32, &h->sens.seed_lo, false},
                             {S_U32, &h->sens.seed_hi, false}, {S_I64, &h->sens.reactor_base, false},
                             {S_I32, &h->sens.svc_on, false}}); }, nullptr},   // (the service program's arrays are the suite's)
-    {"PLIO", plant_io_arrays, 0, [](wt_ensemble *h, Scalars &s) { switch_only(&h->sens.plc_on, s); }, nullptr},
+    {"PLIO", plant_io_arrays, 0, [](wt_ensemble *h, Scalars &s) {
+         s.insert(s.end(), {{S_I32, &h->sens.plc_on, true}, {S_I32, &h->tun.on, false}}); }, nullptr},   // (the tune program's arrays are plant I/O's)
     {"RECD", record_arrays, 0, [](wt_ensemble *h, Scalars &s) {
          s.insert(s.end(), {{S_I32, &h->rec.every, false}, {S_I32, &h->rec.cap, true}, {S_I64, &h->rec.steps, false}}); },
      [](const wt_ensemble *h) { return h->rec.cap > 0; }},
@@ -2055,7 +2110,7 @@ const char *config_error(wt_ensemble *u)
     const auto flag = [](int v) { return v == 0 || v == 1; };
     if (!flag(u->sens.on) || !flag(u->sens.plc_on) || !flag(u->ctl.on) || !flag(u->inj.on) || !flag(u->alm.on) || !flag(u->act.on) ||
         !flag(u->dst.on) || !flag(u->scr.on) || !flag(u->det.on) || !flag(u->trn.on) || !flag(u->trn.pipe.on) || !flag(u->trn.jct.on) || !flag(u->wir.on) ||
-        !flag(u->sens.svc_on) || !flag(u->trd.on) || !flag(u->trd.wrap))
+        !flag(u->sens.svc_on) || !flag(u->tun.on) || !flag(u->trd.on) || !flag(u->trd.wrap))
         return "range";
     if (u->placement != WT_PLACE_IDENTITY && u->placement != WT_PLACE_ADAPTIVE) return "range";
     if (u->sched_mode != WT_SCHED_STREAMS && u->sched_mode != WT_SCHED_QUEUE) return "range";
@@ -2071,6 +2126,7 @@ const char *config_error(wt_ensemble *u)
     if (u->wir.on && (!u->trn.on || !u->sens.plc_on)) return "range";
     if (u->trn.jct.on && !u->trn.on) return "range";
     if (u->sens.svc_on && (!u->sens.on || !wt::prog_in_item(levels_for(u->n)))) return "range";
+    if (u->tun.on && (!u->sens.plc_on || !wt::prog_in_item(levels_for(u->n)))) return "range";
     return nullptr;
 }
 
@@ -2776,6 +2832,68 @@ int wt_ensemble_service_clear(wt_ensemble *h)
     return WT_OK;
 }
 
+int wt_tune_check(int64_t n_reactors, const double *params)
+{
+    if (n_reactors < 1) return fail(WT_E_ARG, "n_reactors must be >= 1");
+    if (!params) return fail(WT_E_ARG, "NULL argument");
+    const char *msg = tune_error(n_reactors, params);
+    return msg ? fail(WT_E_ARG, msg) : WT_OK;
+}
+
+int wt_ensemble_tune_set(wt_ensemble *h, const double *params)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    if (!h->sens.plc_on) return fail(WT_E_STATE, "tuners act on the plant I/O scan: enable plant I/O first");
+    if (!wt::prog_in_item(levels_for(h->n))) return fail(WT_E_STATE, "tune programs run in the kernels for up to 32 zones");
+    if (int rc = wt_tune_check(h->N, params)) return rc;
+    std::vector<double> par((size_t)h->N * wtu::PAR_DOUBLES);
+    blocks_to_records(params, wtu::LOOPS, wtu::NU, h->N, par.data(), wtu::PAR_DOUBLES);
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still use the old records
+    h->tun.on = 0;
+    if (int rc = upload(h, (double *)h->tun.par, par)) return rc;
+    if (int rc = tune_restart(h)) return rc;
+    if (int rc = sync_checked(h)) return rc;    // the host vector is freed on return
+    h->tun.on = 1;
+    return WT_OK;
+}
+
+int wt_ensemble_tune_get(wt_ensemble *h, double *state)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    if (!h->tun.on) return fail(WT_E_STATE, k_tune_not_set);
+    HIP_TRY(hipSetDevice(h->device));
+    return download_records(h, {{state, h->tun.st, wtu::ST_DOUBLES, wtu::LOOPS, wtu::NUS}});
+}
+
+int wt_ensemble_tune_params(wt_ensemble *h, double *params)
+{
+    if (!h || !params) return fail(WT_E_ARG, "NULL argument");
+    if (!h->tun.on) return fail(WT_E_STATE, k_tune_not_set);
+    HIP_TRY(hipSetDevice(h->device));
+    return download_records(h, {{params, h->tun.par, wtu::PAR_DOUBLES, wtu::LOOPS, wtu::NU}});
+}
+
+int wt_ensemble_tune_reset(wt_ensemble *h)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    if (!h->tun.on) return fail(WT_E_STATE, k_tune_not_set);
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still write the records
+    if (int rc = tune_restart(h)) return rc;
+    return sync_checked(h);
+}
+
+int wt_ensemble_tune_clear(wt_ensemble *h)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    if (!h->tun.on) return WT_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still use the records
+    h->tun.on = 0;
+    return WT_OK;
+}
+
 int wt_ensemble_sensors_service(wt_ensemble *h, int sensor, int action, int ref_mode, const double *ref, const double *ref2,
                                 const uint8_t *mask)
 {
@@ -3064,6 +3182,7 @@ int wt_ensemble_info(wt_ensemble *h, int what, int64_t *value)
     case WT_INFO_MARK: *value = h->mark != nullptr; break;
     case WT_INFO_JUNCTION: *value = h->trn.jct.on != 0; break;
     case WT_INFO_SERVICE: *value = h->sens.svc_on != 0; break;
+    case WT_INFO_TUNE: *value = h->tun.on != 0; break;
     default: return fail(WT_E_ARG, "unknown info code");
     }
     return WT_OK;

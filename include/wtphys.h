@@ -286,7 +286,8 @@ enum {
     WT_INFO_WIRE = 19,                    /* a wire program is set */
     WT_INFO_MARK = 20,                    /* a mark is set (wt_ensemble_mark) */
     WT_INFO_JUNCTION = 21,                /* a junction program is set */
-    WT_INFO_SERVICE = 22                  /* a sensor service program is set */
+    WT_INFO_SERVICE = 22,                 /* a sensor service program is set */
+    WT_INFO_TUNE = 23                     /* a tune program is set */
 };
 int wt_ensemble_info(wt_ensemble *h, int what, int64_t *value);
 
@@ -309,7 +310,10 @@ int wt_ensemble_info(wt_ensemble *h, int what, int64_t *value);
  * direction +1 (direct) or -1 (reverse), kp, ki >= 0 (ki per second), out_min <= out_max; otherwise WT_E_ARG.
  * Needs plant I/O (WT_E_STATE).  enable: every enabled loop starts with integral 0, output and holding words the
  * float32 of fmin(fmax(bias, out_min), out_max), metrics 0.  A disabled loop never touches its words.  retune: new
- * parameters; state, metrics and t_prev stay, a loop it switches on starts as at enable.  All synchronise. */
+ * parameters; state, metrics and t_prev stay, a loop it switches on starts as at enable.  retune reads the records in
+ * force from the device, so it sees the gains and the integral a tune program commissioned (wt_ensemble_tune_set): a
+ * loop it keeps on keeps its commissioned state, and wt_ensemble_program_params returns the commissioned kp and ki.
+ * All synchronise. */
 #define WT_CTL_LOOPS 2
 enum {
     WT_C_ENABLE = 0, WT_C_SENSOR = 1, WT_C_DIRECTION = 2, WT_C_SETPOINT = 3, WT_C_KP = 4, WT_C_KI = 5, WT_C_BIAS = 6,
@@ -1043,6 +1047,78 @@ int wt_service_check(int64_t n_reactors, const double *params);
 int wt_ensemble_sensors_service(wt_ensemble *h, int sensor, int action, int ref_mode, const double *ref /* [N] or NULL */,
                                 const double *ref2 /* [N] or NULL */, const uint8_t *mask /* [N] or NULL */);
 int wt_ensemble_sensors_health(wt_ensemble *h, double *out /* [WT_N_SENSORS][WT_NSH][N] */);
+
+/* ---- the tune program: a relay (Astrom-Hagglund) autotuner per PI loop inside fused runs ----
+ * The reference's roadmap lists "Control tuning utilities (Ziegler-Nichols, Lambda)"; it has none.  Two tuners per
+ * reactor, one per PI loop, with the loop indices and holding words of the PI programs: loop 0 chlorine (words 2-3),
+ * loop 1 acid (words 0-1).  A tuner replaces the controller by a relay with hysteresis around the setpoint, lets the
+ * loop settle into its limit cycle, reads the ultimate period Pu and the amplitude a, takes Ku = 4 d / (pi sqrt(a^2 -
+ * eps^2)) and applies a tuning rule given as two factors: kp = kp_factor * Ku, ki = kp / (ti_factor * Pu).
+ * Parameters [WT_TUN_LOOPS][WT_NU][N]: enable (0 or 1), sensor (0..6, WT_N_SENSORS order), direction (+1 or -1),
+ * setpoint, bias (the relay's centre), amplitude d, hysteresis eps, t_start (loop time at which the experiment begins),
+ * t_max (time allowed from the first running scan), settle (whole cycles discarded), cycles (whole cycles measured),
+ * kp_factor, ti_factor (0: ki = 0), commission (0 or 1).  State [WT_TUN_LOOPS][WT_NUS][N]: phase (WT_TUN_WAITING,
+ * _RUNNING, _DONE, _FAILED), relay (-1, 0, +1), output, n_up, t_up, e_max, e_min, sum_period, sum_amp, n_cycles, period,
+ * amplitude, ku, kp, ki, t_begin, t_done, n_exec, n_held, commissioned; all 0 at set and reset.
+ * One scan, for a reactor that stepped and an enabled loop, immediately before the PI programs and with their inputs
+ * (v = the scan's possibly tampered reading of the sensor, f = its fault code, t = the loop time the scan stores),
+ * without fused multiply-adds, the divisions and the square root correctly rounded:
+ *   phase >= 2: nothing.  phase 0 and t < t_start: nothing.  phase 0 and t >= t_start: phase = 1, t_begin = t,
+ *   relay = 0, output = bias, e_max = -inf, e_min = +inf, words written; then as a running scan:
+ *   the tuner owns the loop: the PI program skips it in this scan (no state change, no word; its t_prev advances);
+ *   hold when v is not finite or f != 0: n_held += 1, relay and output stay, nothing more is written; otherwise
+ *   e = direction * (setpoint - (double)v);  n_exec += 1;  if (relay == 0) relay = e >= 0 ? +1 : -1;
+ *   e_max = fmax(e_max, e);  e_min = fmin(e_min, e);
+ *   if (relay < 0 && e > eps) { relay = +1; up-switch } else if (relay > 0 && e < -eps) relay = -1;
+ *   up-switch: n_up += 1; if (n_up >= 2 && n_up - 1 > settle) { sum_period += t - t_up; sum_amp += (e_max - e_min) * 0.5;
+ *              n_cycles += 1; }  t_up = t; e_max = -inf; e_min = +inf;
+ *   if (n_cycles == cycles) finish; else { output = bias + relay * d; words written }
+ *   finish: period = sum_period / n_cycles; amplitude = sum_amp / n_cycles; arg = amplitude * amplitude - eps * eps;
+ *           !(arg > 0): phase = 3; otherwise ku = (4.0 * d) / (3.141592653589793 * sqrt(arg)); kp = kp_factor * ku;
+ *           ki = ti_factor > 0 ? kp / (ti_factor * period) : 0; phase = 2.  Both: t_done = t, output = bias, words written.
+ *   time-out, after a held or an executed scan that left phase 1: t - t_begin >= t_max: phase = 3, t_done = t,
+ *           output = bias, words written.
+ * The words are float32(output) (high, low), as the PI's.  Commissioning, at the finish with phase 2, commission 1,
+ * the control program on and this reactor's PI loop enabled: kp and ki go into the PI loop's parameter record on the
+ * device, the PI's integral becomes bias - pi_bias, commissioned = 1; the PI resumes at the next scan from the relay's
+ * centre output with the gains found.  Without it the PI resumes as it was.  Needs plant I/O (WT_E_STATE, "tuners act
+ * on the plant I/O scan: enable plant I/O first") and n <= 32 zones ("tune programs run in the kernels for up to 32
+ * zones"); runs with or without the control program.  set replaces any program and zeroes the state; reset zeroes the
+ * state, so an experiment whose t_start has passed begins again at the next scan, and commissioned PI gains stay;
+ * clear switches the program off and leaves the holding words as they are.  get, params and reset give WT_E_STATE,
+ * "no tune program is set (wt_ensemble_tune_set)", while none is.  wt_ensemble_plc_enable starts without a program;
+ * checkpoints carry it with plant I/O.  All synchronise.
+ * wt_tune_check is its check, with no handle and no device.  Refused with WT_E_ARG, loop by loop over the reactors, at
+ * the first of: "enable must be 0 or 1"; then for an enabled loop "sensor must be an integer in 0..6"; "direction must
+ * be +1 or -1"; "setpoint and bias must be finite"; "amplitude must be finite and > 0"; "bias - amplitude must be >= 0
+ * and bias + amplitude at most the loop's command limit (1.0 chlorine, 2.0 acid)"; "hysteresis must be finite and >= 0";
+ * "t_start must be finite"; "t_max must be > 0 (+inf: no time-out)"; "settle must be a whole number >= 0"; "cycles must
+ * be an integer in 1..4096"; "kp_factor and ti_factor must be finite and >= 0"; "commission must be 0 or 1". */
+#define WT_TUN_LOOPS 2
+#define WT_TUN_MAX_CYCLES 4096
+enum {
+    WT_TUN_ENABLE = 0, WT_TUN_SENSOR = 1, WT_TUN_DIRECTION = 2, WT_TUN_SETPOINT = 3, WT_TUN_BIAS = 4, WT_TUN_AMPLITUDE = 5,
+    WT_TUN_HYSTERESIS = 6, WT_TUN_T_START = 7, WT_TUN_T_MAX = 8, WT_TUN_SETTLE = 9, WT_TUN_CYCLES = 10, WT_TUN_KP_FACTOR = 11,
+    WT_TUN_TI_FACTOR = 12, WT_TUN_COMMISSION = 13,
+    WT_NU = 14
+};
+enum {
+    WT_TUNS_PHASE = 0, WT_TUNS_RELAY = 1, WT_TUNS_OUTPUT = 2, WT_TUNS_N_UP = 3, WT_TUNS_T_UP = 4, WT_TUNS_E_MAX = 5,
+    WT_TUNS_E_MIN = 6, WT_TUNS_SUM_PERIOD = 7, WT_TUNS_SUM_AMP = 8, WT_TUNS_N_CYCLES = 9, WT_TUNS_PERIOD = 10,
+    WT_TUNS_AMPLITUDE = 11, WT_TUNS_KU = 12, WT_TUNS_KP = 13, WT_TUNS_KI = 14, WT_TUNS_T_BEGIN = 15, WT_TUNS_T_DONE = 16,
+    WT_TUNS_N_EXEC = 17, WT_TUNS_N_HELD = 18, WT_TUNS_COMMISSIONED = 19,
+    WT_NUS = 20
+};
+enum { WT_TUN_WAITING = 0, WT_TUN_RUNNING = 1, WT_TUN_DONE = 2, WT_TUN_FAILED = 3 };
+int wt_ensemble_tune_set(wt_ensemble *h, const double *params /* [WT_TUN_LOOPS][WT_NU][N] */);
+/* host [WT_TUN_LOOPS][WT_NUS][N] loop state */
+int wt_ensemble_tune_get(wt_ensemble *h, double *state);
+/* the program in force as set took it: host [WT_TUN_LOOPS][WT_NU][N] */
+int wt_ensemble_tune_params(wt_ensemble *h, double *params);
+int wt_ensemble_tune_reset(wt_ensemble *h);
+/* program off (no effect while none is set); holding words and commissioned gains stay */
+int wt_ensemble_tune_clear(wt_ensemble *h);
+int wt_tune_check(int64_t n_reactors, const double *params);
 
 /* ---- the parameter checks of the scan programs, the disturbance and the score program, without a handle or a device ----
  * params: host, the block the program's set or enable call takes, for n_reactors reactors (WT_PROG_CONTROL:
