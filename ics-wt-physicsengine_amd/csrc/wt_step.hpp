@@ -58,8 +58,8 @@ struct Flag {
 enum Phase : int {
     PH_OUTER_BEGIN = 0, // start an outer step: next trip evaluates f0 = f(y0)            radau.py:303
     PH_INIT_STEP,       // f0 known: first half of select_initial_step (no evaluation needed)  common.py:111-119
-    PH_F1,              // next evaluates f(y0 + h0 f0)                                     common.py:120-122
-    PH_STEP_BEGIN,      // _step_impl prologue (no evaluation needed)                       radau.py:399-424
+    PH_F1,              // next evaluates f(y0 + h0 f0); its epilogue starts the first attempt  common.py:120-122
+    PH_STEP_BEGIN,      // _step_impl prologue of every later step (no evaluation needed)   radau.py:399-424
     PH_ATTEMPT,         // (re)start an attempt with the current h_abs                      radau.py:426-448
     PH_NEWTON,          // one simplified-Newton iteration per trip (three evaluations)     radau.py:84-134
     PH_ERR_REFINE,      // second error estimate after a rejection (one evaluation)         radau.py:485-487
@@ -120,6 +120,12 @@ __device__ __forceinline__ void rhs_points(const Lane &L, const RKStore &ks, Arg
             rhs_rows<ROW>(L, k, pp[s].H, pp[s].iw, pp[s].bpos, pt[s].kT * pp[s].phi, pt[s].rho, y[s][SCL], y[s][STT], F[s]);
     }
 }
+
+// Whether the probe's epilogue (PH_F1) also starts the first attempt, so that the trip that probed the step size goes on
+// to the Jacobian, the factorisation and Newton iteration 1 with f(y0) as the three stage values.  The one switch for an
+// instantiation whose register allocation or timing would take the join badly: without it the lane goes through
+// PH_STEP_BEGIN / PH_ATTEMPT and a stage evaluation in the next trip, same results.  No instantiation needs it.
+__host__ __device__ constexpr bool first_attempt_in_probe_trip(int /*LV*/, bool /*ROW*/) { return true; }
 
 // One work item: the reactors of wavefront-group `group` advanced by `cnt` outer steps, starting with step `step0`
 // of this launch.  Reactors of a wavefront start every outer step together (they wait for the slowest of them), so
@@ -223,7 +229,7 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
             double d0 = 0, d1 = 0, h0 = 0;            // select_initial_step
             SolverCounters cnt_s = {0, 0, 0, 0, 0};
             int attempts = 0;   // guard against unbounded solves (sliding along a discontinuity): see limit_hit
-            int badstage = 0;   // which evaluation of the trip raised: 0 deferred f(y_new), 1..3 stage / single point
+            int badstage = 0;   // which evaluation of the trip raised: 0 deferred f(y_new) / num_jac, 1..3 stage / single point
             // pend_f: f(yc) of the last accepted step has not been evaluated yet
             // jac_after_fnew: that step also asked for a fresh Jacobian (radau.py:500,512)
             int phase = PH_OUTER_BEGIN;
@@ -355,17 +361,9 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
                     }
                 }
                 WT_STAMP(1);   // step / attempt prologues
-#ifdef WT_STAMPS
-                if (__ballot(phase == PH_NEWTON && !have_lu) != 0ull) WT_COUNT(diag_fact);
-#endif
-                if (phase == PH_NEWTON && !have_lu) {
-                    { Jac Jb; ja.bands(Jb); factorize<ROW, LV>(L, Jb, h, F); } have_lu = true; cnt_s.nlu += 2;      // radau.py:454-456
-                }
-
-                WT_STAMP(2);   // factorisation
                 // ================= this trip's evaluation points
                 const bool newton = (phase == PH_NEWTON);
-                diag_trips++; if (__ballot(newton) != 0ull) diag_newton++;
+                diag_trips++;
                 const bool eval0 = (phase == PH_OUTER_BEGIN || phase == PH_F1 || phase == PH_ERR_REFINE || phase == PH_FNEW || newton);
                 // f(y) of a just-accepted step rides along with the next attempt's first Newton trip
                 const bool eval3 = newton && pend_f;
@@ -429,8 +427,8 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
                     if (seg_any(L, bad)) { raised = true; phase = PH_DONE; }
                 }
 
-                WT_STAMP(3);   // RHS evaluations
-                // ================= per-phase epilogues
+                // ================= the epilogues of the phases that are not Newton's: they may ask for a Jacobian, and the probe's
+                // starts the first attempt, so they come before num_jac, the factorisation and the Newton epilogue of this same trip
                 if (WT_RARE(phase == PH_OUTER_BEGIN)) {   // (rare: f(y0) is usually carried over from the previous outer step)
 #pragma unroll
                     for (int q = 0; q < 3; ++q) f[q] = Fe[0][q];
@@ -445,8 +443,75 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
                     else h1 = root4(0.01 * rcp(fmax(d1, d2)));
                     h_abs = fmin(fmin(100 * h0, h1), fmin(fabs(t_bound - t), max_step));
                     need_jac = true;                                          // radau.py:359-365
-                    phase = PH_STEP_BEGIN;
-                } else if (phase == PH_NEWTON) {
+                    if constexpr (!first_attempt_in_probe_trip(LV, ROW)) phase = PH_STEP_BEGIN;
+                    else {
+                        // ---- the first attempt of this fresh solver, here and not in a trip of its own: what PH_STEP_BEGIN and
+                        // PH_ATTEMPT do when nothing has been attempted yet.  have_old_l, rejected, keep_h, have_norm_old and
+                        // have_rate are still false, kk, rate and W still the zeros the outer step declared them with.  Neither
+                        // guard of PH_ATTEMPT can fire: attempts == 0, and h_abs <= max_step from the line above, so h_abs_l
+                        // is h_abs or min_step.
+                        min_step = 10 * fabs(ulp_above(t));                  // radau.py:408
+                        h_abs_l = (h_abs < min_step) ? min_step : h_abs;
+                        attempts++;
+                        h = h_abs_l;
+                        t_new = t + h;
+                        if (t_new - t_bound > 0) t_new = t_bound;
+                        h = t_new - t;
+                        h_abs_l = fabs(h);
+                        // Z0 = 0 without a dense output, and the RHS has no time argument: the three stage points are yc, their
+                        // values the f this lane holds, bit for bit (one rounding behaviour per expression); counted as scipy does
+#pragma unroll
+                        for (int s = 0; s < 3; ++s)
+#pragma unroll
+                            for (int q = 0; q < 3; ++q) Fe[s][q] = f[q];
+                        cnt_s.nfev += 3;
+                        phase = PH_NEWTON;
+                    }
+                } else if (phase == PH_FNEW) {
+                    // f(y_new) of an accepted step that needs it before anything else can happen:
+                    // Jacobian refresh (radau.py:512-514) or the end of the outer step
+#pragma unroll
+                    for (int q = 0; q < 3; ++q) f[q] = Fe[0][q];
+                    pend_f = false;
+                    fv = true;
+                    if (jac_after_fnew) { need_jac = true; jac_after_fnew = false; }
+                    phase = ((t - t_bound) < 0) ? PH_STEP_BEGIN : PH_DONE;
+                }
+
+                WT_STAMP(3);   // RHS evaluations, epilogues of the phases that are not Newton's
+                // ================= finite-difference Jacobian at (yc, f) when a phase asked for it: the probe and PH_FNEW just now,
+                // a Newton iteration that diverged on an old Jacobian in the trip before (its retry's stage points are evaluated
+                // above, the reference's after its jac call: a bad column here takes precedence over a bad stage point)
+#ifdef WT_STAMPS
+                if (__ballot(need_jac) != 0ull) WT_COUNT(diag_jac);
+#endif
+                if (need_jac) {
+                    bool jbad = false, hf = have_fac, jd = false; double jval = 0;
+                    asm volatile("" ::: "memory");               // a fresh fetch: do not keep the constants live across the epilogue
+                    double fac[3] = {fac_a[0].get(), fac_a[1].get(), fac_a[2].get()};
+                    num_jac<ROW>(L, ks, [&]() { return &fresh(pa)->kt; }, yc, f, fac, hf, J, jbad, jval, jd); cnt_s.njev++;
+                    fac_a[0].set(fac[0]); fac_a[1].set(fac[1]); fac_a[2].set(fac[2]);
+                    have_fac = hf;
+                    j_dense = jd;
+                    ja.put(J);
+                    need_jac = false;
+                    if (WT_RARE(seg_any(L, jbad))) {
+                        if (jbad) { badstage = 0; badval = jval; }
+                        bad |= jbad; raised = true; phase = PH_DONE;
+                    }
+                }
+                WT_STAMP(5);   // num_jac
+#ifdef WT_STAMPS
+                if (__ballot(phase == PH_NEWTON && !have_lu) != 0ull) WT_COUNT(diag_fact);
+#endif
+                if (phase == PH_NEWTON && !have_lu) {
+                    { Jac Jb; ja.bands(Jb); factorize<ROW, LV>(L, Jb, h, F); } have_lu = true; cnt_s.nlu += 2;      // radau.py:454-456
+                }
+
+                WT_STAMP(2);   // factorisation
+                // ================= the Newton iteration and the second error estimate
+                if (__ballot(phase == PH_NEWTON) != 0ull) diag_newton++;
+                if (phase == PH_NEWTON) {
                     // ---- one iteration of solve_collocation_system radau.py:84-134
                     Jac Jc; ja.coupling(Jc);
                     bool finite = true;
@@ -538,38 +603,8 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
                     solve_real<ROW, LV>(L, Jc, F, err, __ballot(j_dense) == 0ull);
                     error_norm = rms3<ROW, LV>(L, err, esc);
                     if (error_norm > 1) reject_step(); else accept_step();
-                } else if (phase == PH_FNEW) {
-                    // f(y_new) of an accepted step that needs it before anything else can happen:
-                    // Jacobian refresh (radau.py:512-514) or the end of the outer step
-#pragma unroll
-                    for (int q = 0; q < 3; ++q) f[q] = Fe[0][q];
-                    pend_f = false;
-                    fv = true;
-                    if (jac_after_fnew) { need_jac = true; jac_after_fnew = false; }
-                    phase = ((t - t_bound) < 0) ? PH_STEP_BEGIN : PH_DONE;
                 }
-
-                WT_STAMP(4);   // epilogues (Newton solve, error estimate, accept / reject)
-                // ================= finite-difference Jacobian at (yc, f) when a phase asked for it
-#ifdef WT_STAMPS
-                if (__ballot(need_jac) != 0ull) WT_COUNT(diag_jac);
-#endif
-                if (need_jac) {
-                    bool jbad = false, hf = have_fac, jd = false; double jval = 0;
-                    asm volatile("" ::: "memory");               // a fresh fetch: do not keep the constants live across the epilogue
-                    double fac[3] = {fac_a[0].get(), fac_a[1].get(), fac_a[2].get()};
-                    num_jac<ROW>(L, ks, [&]() { return &fresh(pa)->kt; }, yc, f, fac, hf, J, jbad, jval, jd); cnt_s.njev++;
-                    fac_a[0].set(fac[0]); fac_a[1].set(fac[1]); fac_a[2].set(fac[2]);
-                    have_fac = hf;
-                    j_dense = jd;
-                    ja.put(J);
-                    need_jac = false;
-                    if (WT_RARE(seg_any(L, jbad))) {
-                        if (jbad && !bad) { badstage = 4; badval = jval; }
-                        bad |= jbad; raised = true; phase = PH_DONE;
-                    }
-                }
-                WT_STAMP(5);   // num_jac
+                WT_STAMP(4);   // Newton solve, error estimates, accept / reject
             }
             last_cnt = cnt_s;
             cost_acc += cnt_s.nfev;

@@ -24,7 +24,8 @@ for label, k, fused in (("queue 20 steps", 20, True), ("queue 100 steps", 100, T
           f" | fact {d[:,4].mean()/k:.2f} jac {d[:,5].mean()/k:.2f} f3 {d[:,6].mean()/k:.2f}"
           f" | clk/wall GHz {np.mean(clk/wall)/1e3:.2f} | reactor nfev mean {st[:,0].mean():.1f} max {st[:,0].max()}")
     if d.shape[1] > 8:
-        names = ["setup", "prologue", "factorize", "rhs", "epilogue", "num_jac", "post-step", "sensors/io"]
+        # WT_STAMP(0...7); in a trip the blocks run in the order prologue, rhs+light, num_jac, factorize, newton
+        names = ["setup", "prologue", "factorize", "rhs+light epilogues", "newton/refine epilogue", "num_jac", "post-step", "sensors/io"]
         tot = d[:, 8:16].sum()
         print("   section shares: " + "  ".join(f"{nm} {d[:, 8 + i].sum() / tot * 100:.1f}%" for i, nm in enumerate(names) if nm != "-")
               + f" | stamped clocks/step {d[:, 8:16].sum(1).mean() / k:.0f}")
