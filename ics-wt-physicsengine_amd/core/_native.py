@@ -19,7 +19,7 @@ LIB_PATH = os.environ.get("WTPHYS_LIB", os.path.join(CSRC, "libwtphys.so"))  # o
 
 WT_OK, WT_E_ARG, WT_E_HIP, WT_E_NOGPU, WT_E_STATE = 0, 1, 2, 3, 4
 (WT_PROG_CONTROL, WT_PROG_INJECT, WT_PROG_ALARM, WT_PROG_ACTUATOR, WT_PROG_DISTURB, WT_PROG_SCORE, WT_PROG_DETECT,
- WT_PROG_TREND) = range(8)   # wt_program_check
+ WT_PROG_TREND, WT_PROG_SERVICE, WT_PROG_TUNE) = range(10)   # wt_program_check
 (WT_INFO_PLANT_IO, WT_INFO_PROGRAM, WT_INFO_TRAIN, WT_INFO_PIPE, WT_INFO_SENSOR_HISTORY, WT_INFO_DISTURB_HISTORY,
  WT_INFO_SCORE_CURVE, WT_INFO_SCORE_BINS, WT_INFO_TREND_CAPACITY, WT_INFO_TRAIN_LENGTH, WT_INFO_WAVE_DIAG,
  WT_INFO_BOUNDARY_UPLOADS, WT_INFO_WIRE, WT_INFO_MARK, WT_INFO_JUNCTION, WT_INFO_SERVICE, WT_INFO_TUNE) = (0, 1) + tuple(range(9, 24))   # wt_ensemble_info; WT_INFO_PROGRAM + WT_PROG_*: 1..8

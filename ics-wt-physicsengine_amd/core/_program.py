@@ -1,7 +1,8 @@
-"""What the per-reactor scan programs (:mod:`.control`, :mod:`.inject`, :mod:`.alarm`, :mod:`.actuator`) share on
-the host: the sensor names, names -> codes, the rows of one loop or slot, the packing of a slot program into its
-block, and the check of a block.  Each module keeps its own fields, defaults and off rows; the rules a block must
-satisfy live only in the library (``wt_program_check``)."""
+"""What the ten per-reactor programs (:mod:`.control`, :mod:`.inject`, :mod:`.alarm`, :mod:`.actuator`,
+:mod:`.disturb`, :mod:`.score`, :mod:`.detect`, :mod:`.trend`, :mod:`.service`, :mod:`.tune`) share on the host: the
+sensor names, names -> codes, the rows of one loop or slot, the packing of a slot program into its block, and the check
+of a block.  Each module keeps its own fields, defaults and off rows; the rules a block must satisfy live only in the
+library (``wt_program_check``)."""
 from __future__ import annotations
 
 import numpy as np

@@ -509,7 +509,7 @@ class ReactorEnsemble:
     def service_params(self) -> np.ndarray:
         """The (4, 12, N) block of the service program in force, as :func:`service_block` built it."""
         blk = np.empty((service.SLOTS, service.NSV, self.n_reactors), dtype=np.float64)
-        self._program_call(_native.lib().wt_ensemble_service_params, _native.dptr(blk))
+        self._program_call(_native.lib().wt_ensemble_program_params, _native.WT_PROG_SERVICE, _native.dptr(blk))
         return blk
 
     def reset_services(self) -> None:
@@ -613,7 +613,7 @@ class ReactorEnsemble:
         return out
 
     def _program_call(self, fn, *args) -> None:
-        """A call of one of the eight per-reactor programs: a refusal is the caller's ValueError."""
+        """A call of one of the ten per-reactor programs: a refusal is the caller's ValueError."""
         try:
             _native.check(fn(self._h, *args))
         except _native.WtError as e:
@@ -672,7 +672,7 @@ class ReactorEnsemble:
     def tuner_params(self) -> np.ndarray:
         """The (2, 14, N) block of the tune program in force, as :func:`tune_block` built it."""
         blk = np.empty((len(control.LOOPS), tune.NU, self.n_reactors), dtype=np.float64)
-        self._program_call(_native.lib().wt_ensemble_tune_params, _native.dptr(blk))
+        self._program_call(_native.lib().wt_ensemble_program_params, _native.WT_PROG_TUNE, _native.dptr(blk))
         return blk
 
     def reset_tuners(self) -> None:

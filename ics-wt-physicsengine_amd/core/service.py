@@ -6,7 +6,7 @@ The reference's sensors have a maintenance interface next to ``read`` -- ``calib
 A program has up to four slots per reactor.  A slot names one sensor and one action and falls due either at a suite
 time (once, or every ``every`` seconds) or some time after a read of its sensor returned a given status; the action
 then acts on the next read.  This module builds the parameter block and unpacks the state; the library checks the
-block (``wt_service_check``), and the actions themselves run in ``csrc/wt_svc.hpp``.
+block (``wt_program_check``), and the actions themselves run in ``csrc/wt_svc.hpp``.
 """
 from __future__ import annotations
 
@@ -16,7 +16,7 @@ from typing import Optional, Union
 import numpy as np
 
 from . import _native
-from ._program import SENSOR_NAMES, codes, field_rows
+from ._program import SENSOR_NAMES, codes, field_rows, slot_block
 
 SLOTS, NSV, NSVS, NSH = 4, 12, 4, 8       # WT_SVC_SLOTS, WT_NSV, WT_NSVS, WT_NSH
 PARAM_ROWS = ("enable", "sensor", "action", "trigger", "t_first", "period", "count", "status", "delay", "ref_mode", "ref", "ref2")
@@ -75,15 +75,6 @@ class ServiceState:
         return np.stack([getattr(self, k) for k in STATE_ROWS], axis=1)
 
 
-def check(block: np.ndarray) -> None:
-    """The checks ``wt_ensemble_service_set`` makes on a [WT_SVC_SLOTS][WT_NSV][N] block; ``ValueError`` names the
-    first one that fails."""
-    try:
-        _native.check(_native.lib().wt_service_check(block.shape[-1], _native.dptr(block)))
-    except _native.WtError as e:   # WT_E_ARG is the only error it returns
-        raise ValueError(e.message) from None
-
-
 def slot_rows(service: Service, n: int, name: str = "service") -> np.ndarray:
     """(NSV, N) rows of one slot."""
     if not isinstance(service, Service):
@@ -102,10 +93,4 @@ def service_block(n_reactors: int, *services: Service) -> np.ndarray:
     """The [WT_SVC_SLOTS][WT_NSV][N] float64 block of ``wt_ensemble_service_set``, checked by the library: slot k is
     the k-th service, the slots after the last are off."""
     n = int(n_reactors)
-    if len(services) > SLOTS:
-        raise ValueError(f"at most {SLOTS} services per program, got {len(services)}")
-    rows = [slot_rows(s, n, f"service {k}") for k, s in enumerate(services)]
-    rows += [np.zeros((NSV, n))] * (SLOTS - len(services))
-    block = np.ascontiguousarray(np.stack(rows))
-    check(block)
-    return block
+    return slot_block(services, n, SLOTS, "service", slot_rows, np.zeros((NSV, n)), _native.WT_PROG_SERVICE)

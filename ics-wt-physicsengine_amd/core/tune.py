@@ -5,7 +5,7 @@ The standard commissioning experiment (Astrom-Hagglund): a relay with hysteresis
 controller, the loop settles into its limit cycle, and the cycle's period Pu and amplitude a give the ultimate gain
 ``Ku = 4 d / (pi sqrt(a^2 - eps^2))``, to which a tuning rule is applied.  One tuner per PI loop, with the loop indices
 of :mod:`.control`: loop 0 doses chlorine (holding words 2-3), loop 1 acid (words 0-1).  This module only builds the
-parameter block and unpacks the state; the library checks the block (``wt_tune_check``), and the experiment itself runs
+parameter block and unpacks the state; the library checks the block (``wt_program_check``), and the experiment itself runs
 in ``csrc/wt_tun.hpp``.
 """
 from __future__ import annotations
@@ -16,7 +16,7 @@ from typing import Optional, Tuple, Union
 import numpy as np
 
 from . import _native
-from ._program import SENSOR_NAMES, codes, field_rows
+from ._program import SENSOR_NAMES, check, codes, field_rows
 from .control import COMMAND_LIMIT, LOOPS
 
 NU, NUS = 14, 20                        # WT_NU, WT_NUS
@@ -100,15 +100,6 @@ class TunerState:
         return np.stack([np.stack([getattr(getattr(self, loop), k) for k in STATE_ROWS]) for loop in LOOPS])
 
 
-def check(block: np.ndarray) -> None:
-    """The checks ``wt_ensemble_tune_set`` makes on a [WT_TUN_LOOPS][WT_NU][N] block; ``ValueError`` names the first
-    one that fails."""
-    try:
-        _native.check(_native.lib().wt_tune_check(block.shape[-1], _native.dptr(block)))
-    except _native.WtError as e:   # WT_E_ARG is the only error it returns
-        raise ValueError(e.message) from None
-
-
 def _rule_factors(rule, name: str):
     if isinstance(rule, str):
         if rule not in TUNE_RULES:
@@ -136,5 +127,5 @@ def tune_block(n_reactors: int, chlorine: Optional[RelayTune] = None, acid: Opti
     """The [WT_TUN_LOOPS][WT_NU][N] float64 parameter block of ``wt_ensemble_tune_set``, checked by the library."""
     n = int(n_reactors)
     block = np.ascontiguousarray(np.stack([loop_rows(chlorine, "chlorine", n), loop_rows(acid, "acid", n)]))
-    check(block)
+    check(_native.WT_PROG_TUNE, block)
     return block

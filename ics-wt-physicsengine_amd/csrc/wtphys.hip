@@ -101,9 +101,10 @@ struct wt_ensemble {
     // The kernel's argument structs of the optional parts, as every launch passes them (make_args adds what is per
     // call).  sens: fused sensor suite (wt_sensors.hpp, sens.on), plant I/O with its Modbus register images per reactor
     // (wt_plc.hpp, sens.plc_on: one PLC scan every chunk_steps outer steps), the command path into the boundary block.
-    // The holding image lives in ctl.hr, which sens.cmd.hr repeats.  Then the eight per-reactor programs, [N] records
-    // each, in WT_PROG_* order: k_programs below describes the host side of each.  scr_steps: outer
-    // steps the step calls have taken since score_set / score_reset (the index of the ensemble curve's next entry).
+    // The holding image lives in ctl.hr, which sens.cmd.hr repeats.  Then the per-reactor programs, [N] records each,
+    // in WT_PROG_* order: k_programs below describes the host side of each; the service program's
+    // records and switch are in sens, the tune program's in tun.  scr_steps: outer steps the step calls have taken
+    // since score_set / score_reset (the index of the ensemble curve's next entry).
     wts::SuiteArgs sens = {};
     wtc::CtlArgs ctl = {};
     wti::InjArgs inj = {};
@@ -121,7 +122,7 @@ struct wt_ensemble {
     int R0 = 0;
     // The wire program on top of it (wt_wir.hpp): no switch of its own beyond wir.on, no host copy.
     wtw::WirArgs wir = {};
-    // The tune program (wt_tun.hpp; beside k_programs): its records are plant I/O's arrays, its switch a PLIO scalar.
+    // The tune program (wt_tun.hpp; WT_PROG_TUNE of k_programs): its records are plant I/O's arrays, its switch a PLIO scalar.
     wtu::TunArgs tun = {};
     // optional per-launch HIP-event timing (bench.py roofline accounting)
     bool time_launches = false;
@@ -1180,6 +1181,19 @@ static_assert(wtt::index_range(wtt::G_IMAGE_VALUE) == WT_N_SENSORS && wtt::index
 // COMMAND channels in WT_INJ_CMD_* order
 static_assert(WT_INJ_CMD_ACID + 1 == WT_INJ_CMD_CHLORINE && WT_INJ_CMD_CHLORINE + 1 == WT_INJ_CMD_INLET, "acid, chlorine, inlet");
 
+static_assert(WT_SVC_SLOTS == wtsv::SLOTS && WT_NSV == wtsv::NSV && WT_NSVS == wtsv::NSVS && WT_NSH == wtsv::NSH &&
+              WT_SV_ENABLE == wtsv::V_ENABLE && WT_SV_REF2 == wtsv::V_REF2 && WT_SVS_N_DONE == wtsv::VS_N_DONE &&
+              WT_SVS_T_SEEN == wtsv::VS_T_SEEN && WT_SVC_CALIBRATE == wtsv::A_CALIBRATE &&
+              WT_SVC_REPLACE_REAGENT == wtsv::A_REPLACE_REAGENT && WT_SVC_ON_STATUS == wtsv::TR_ON_STATUS &&
+              WT_SVC_REF_TRIM == wtsv::REF_TRIM && WT_SH_FAULT == wtsv::H_FAULT && WT_N_SENSORS == wts::NSENS,
+              "service blocks of the C ABI");
+
+static_assert(WT_TUN_LOOPS == wtu::LOOPS && WT_TUN_LOOPS == WT_CTL_LOOPS && WT_NU == wtu::NU && WT_NUS == wtu::NUS &&
+              WT_TUN_ENABLE == wtu::U_ENABLE && WT_TUN_AMPLITUDE == wtu::U_AMPLITUDE && WT_TUN_COMMISSION == wtu::U_COMMISSION &&
+              WT_TUNS_PHASE == wtu::US_PHASE && WT_TUNS_N_CYCLES == wtu::US_N_CYCLES && WT_TUNS_KU == wtu::US_KU &&
+              WT_TUNS_COMMISSIONED == wtu::US_COMMISSIONED && WT_TUN_DONE == wtu::PH_DONE && WT_TUN_FAILED == wtu::PH_FAILED &&
+              WT_TUN_MAX_CYCLES == wtu::MAX_CYCLES, "tune blocks of the C ABI");
+
 // -- parameter rules: the checks of one slot's row vector c[fields] (slot: its index in the block); nullptr when it passes
 
 using Rule = const char *(*)(int slot, const double *c);
@@ -1331,6 +1345,67 @@ const char *trend_rule(int, const double *c)
     return nullptr;
 }
 
+const char *k_service_no_suite = "the sensor suite is not enabled (wt_ensemble_sensors_enable)";
+
+// what the reference would raise for, and the codes: an action on a sensor with a reference mode
+// (wt_ensemble_sensors_service checks its arguments with it too)
+const char *service_action_error(double sensor, double action, double ref_mode)
+{
+    if (!whole_in(sensor, 0, WT_N_SENSORS - 1)) return "sensor must be an integer in 0..6";
+    if (!whole_in(action, 0, wtsv::N_ACTIONS - 1)) return "action must be an integer in 0..6";
+    if (!whole_in(ref_mode, 0, wtsv::N_REF_MODES - 1)) return "ref_mode must be 0 (constant), 1 (sample) or 2 (trim)";
+    const int a = (int)action;
+    if (a >= wtsv::A_TWO_POINT && a <= wtsv::A_PEPSIN_CLEAN && sensor > 1.0)
+        return "two-point calibration and cleaning are for the pH sensors (0, 1)";
+    if (a == wtsv::A_REPLACE_MEMBRANE && sensor != 2.0) return "only the amperometric chlorine sensor (2) has a membrane to replace";
+    if (a == wtsv::A_REPLACE_REAGENT && sensor != 3.0) return "only the DPD chlorine sensor (3) has a reagent to replace";
+    if (a == wtsv::A_TWO_POINT && ref_mode != (double)wtsv::REF_CONSTANT)
+        return "a two-point calibration takes its buffers as constants (ref_mode 0)";
+    return nullptr;
+}
+
+const char *service_rule(int, const double *c)
+{
+    if (!whole_in(c[WT_SV_ENABLE], 0, 1)) return "enable must be 0 or 1";
+    if (c[WT_SV_ENABLE] == 0.0) return nullptr;            // the other rows of a slot that is off are not read
+    if (!whole_in(c[WT_SV_SENSOR], 0, WT_N_SENSORS - 1)) return "sensor must be an integer in 0..6";
+    if (!whole_in(c[WT_SV_ACTION], 0, wtsv::N_ACTIONS - 1)) return "action must be an integer in 0..6";
+    if (!whole_in(c[WT_SV_TRIGGER], 0, wtsv::N_TRIGGERS - 1)) return "trigger must be 0 (at_time) or 1 (on_status)";
+    if (const char *msg = service_action_error(c[WT_SV_SENSOR], c[WT_SV_ACTION], c[WT_SV_REF_MODE])) return msg;
+    for (const int f : {WT_SV_T_FIRST, WT_SV_PERIOD, WT_SV_DELAY})
+        if (!(std::isfinite(c[f]) && c[f] >= 0.0)) return "t_first, period and delay must be finite and >= 0";
+    if (c[WT_SV_PERIOD] != 0.0 && c[WT_SV_PERIOD] < wtsv::MIN_PERIOD) return "period must be 0 (once) or at least 0.001 s";
+    if (!whole_in(c[WT_SV_COUNT], 0, 9007199254740991.0)) return "count must be a whole number >= 0 (0: no cap)";
+    if (!whole_in(c[WT_SV_STATUS], 0, 11)) return "status must be an integer in 0..11 (a SensorStatus code)";
+    if (!(std::isfinite(c[WT_SV_REF]) && std::isfinite(c[WT_SV_REF2]))) return "ref and ref2 must be finite";
+    return nullptr;
+}
+
+// validate_flow_rate's maxima (__main__.py:57-63, :236-242) by loop: chlorine, acid
+constexpr double k_command_limit[WT_TUN_LOOPS] = {1.0, 2.0};
+
+const char *tune_rule(int loop, const double *c)
+{
+    if (!whole_in(c[WT_TUN_ENABLE], 0, 1)) return "enable must be 0 or 1";
+    if (c[WT_TUN_ENABLE] == 0.0) return nullptr;           // the other rows of a loop that is off are not read
+    if (!whole_in(c[WT_TUN_SENSOR], 0, WT_N_SENSORS - 1)) return "sensor must be an integer in 0..6";
+    if (c[WT_TUN_DIRECTION] != 1.0 && c[WT_TUN_DIRECTION] != -1.0) return "direction must be +1 or -1";
+    if (!(std::isfinite(c[WT_TUN_SETPOINT]) && std::isfinite(c[WT_TUN_BIAS]))) return "setpoint and bias must be finite";
+    const double d = c[WT_TUN_AMPLITUDE], b = c[WT_TUN_BIAS];
+    if (!(std::isfinite(d) && d > 0.0)) return "amplitude must be finite and > 0";
+    if (!(b - d >= 0.0 && b + d <= k_command_limit[loop]))
+        return "bias - amplitude must be >= 0 and bias + amplitude at most the loop's command limit (1.0 chlorine, 2.0 acid)";
+    if (!(std::isfinite(c[WT_TUN_HYSTERESIS]) && c[WT_TUN_HYSTERESIS] >= 0.0)) return "hysteresis must be finite and >= 0";
+    if (!std::isfinite(c[WT_TUN_T_START])) return "t_start must be finite";
+    if (!(c[WT_TUN_T_MAX] > 0.0)) return "t_max must be > 0 (+inf: no time-out)";
+    if (!whole_in(c[WT_TUN_SETTLE], 0, 9007199254740991.0)) return "settle must be a whole number >= 0";
+    if (!whole_in(c[WT_TUN_CYCLES], 1, WT_TUN_MAX_CYCLES)) return "cycles must be an integer in 1..4096";
+    for (const int f : {WT_TUN_KP_FACTOR, WT_TUN_TI_FACTOR})
+        if (!(std::isfinite(c[f]) && c[f] >= 0.0)) return "kp_factor and ti_factor must be finite and >= 0";
+    if (!whole_in(c[WT_TUN_COMMISSION], 0, 1)) return "commission must be 0 or 1";
+    return nullptr;
+}
+
 // Walks a [slots][fields][N] block slot by slot, reactor by reactor, and hands each row vector to `rule`: the first
 // message, so the first failing rule of the first bad reactor of the first bad slot is the one named.
 const char *block_error(const double *p, int slots, int fields, int64_t N, Rule rule)
@@ -1467,9 +1542,47 @@ int trend_restart(wt_ensemble *h)
     return WT_OK;
 }
 
+// the slot state at its set-time values: 0, NaN, t_first from the parameter records in force, NaN
+int service_restart(wt_ensemble *h)
+{
+    std::vector<double> par((size_t)h->N * wtsv::PAR_DOUBLES), st((size_t)h->N * wtsv::ST_DOUBLES);
+    // (the download also waits for queued launches, which may still write the old state)
+    if (int rc = download(h, {{par.data(), h->sens.svc_par, sizeof(double) * par.size()}})) return rc;
+    for (size_t r = 0; r < (size_t)h->N; ++r)
+        for (int k = 0; k < wtsv::SLOTS; ++k) {
+            double *q = st.data() + r * wtsv::ST_DOUBLES + k * wtsv::NSVS;
+            q[wtsv::VS_N_DONE] = 0.0; q[wtsv::VS_T_LAST] = NAN; q[wtsv::VS_T_SEEN] = NAN;
+            q[wtsv::VS_T_DUE] = par[r * wtsv::PAR_DOUBLES + k * wtsv::NSV + wtsv::V_T_FIRST];
+        }
+    if (int rc = upload(h, h->sens.svc_st, st)) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));   // the host vector is freed on return
+    return WT_OK;
+}
+
+// every loop waiting: the state all 0
+int tune_restart(wt_ensemble *h)
+{
+    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still write the records
+    HIP_TRY(hipMemsetAsync(h->tun.st, 0, sizeof(double) * wtu::ST_DOUBLES * (size_t)h->N, h->stream));
+    return WT_OK;
+}
+
+// The service and the tune program own no arrays: their records are the sensor suite's and plant I/O's, which
+// allocate, release and checkpoint them (sensor_arrays, plant_io_arrays).  For k_programs these two only name the
+// switch and the records, parameters first; the descriptor says `borrowed`, and nothing allocates or releases them.
+ArrayGroup service_records(wt_ensemble *h)
+{
+    return {"service", &h->sens.svc_on, {{(void **)&h->sens.svc_par, 0}, {(void **)&h->sens.svc_st, 0}}};
+}
+
+ArrayGroup tune_records(wt_ensemble *h)
+{
+    return {"tune", &h->tun.on, {{(void **)&h->tun.par, 0}, {(void **)&h->tun.st, 0}}};
+}
+
 // -- the descriptors, indexed by WT_PROG_*
 
-enum Needs { NEEDS_PLANT_IO, NEEDS_STATE, NEEDS_STATE_AND_BOUNDARY };
+enum Needs { NEEDS_PLANT_IO, NEEDS_SENSORS, NEEDS_STATE, NEEDS_STATE_AND_BOUNDARY };
 
 struct Program {
     const char *not_set;                  // refusal of get, reset and the other read calls while no program is set
@@ -1479,6 +1592,7 @@ struct Program {
     Rule first_pass, rule;                // first_pass (nullptr: none) runs over the whole block before rule does
     ArrayGroup (*arrays)(wt_ensemble *);  // switch and arrays; the parameter records are the group's first array
     int (*restart)(wt_ensemble *);        // nullptr: control_load builds the state, loop by loop
+    bool borrowed;                        // the arrays are another part's: set does not allocate, stop only clears the switch
 };
 
 const Program k_programs[] = {
@@ -1498,11 +1612,17 @@ const Program k_programs[] = {
      "detector programs run in the kernels for up to 32 zones", wtk::SLOTS, wtk::NK, nullptr, detect_rule, detect_arrays, detect_restart},
     {"no trend program is set (wt_ensemble_trend_set)", NEEDS_PLANT_IO, "trends read the plant I/O scan: enable plant I/O first",
      "trend programs run in the kernels for up to 32 zones", wtt::SLOTS, wtt::NT, nullptr, trend_rule, trend_arrays, trend_restart},
+    {"no service program is set (wt_ensemble_service_set)", NEEDS_SENSORS, k_service_no_suite,
+     "service programs run in the kernels for up to 32 zones", WT_SVC_SLOTS, WT_NSV, nullptr, service_rule, service_records, service_restart, true},
+    {"no tune program is set (wt_ensemble_tune_set)", NEEDS_PLANT_IO, "tuners act on the plant I/O scan: enable plant I/O first",
+     "tune programs run in the kernels for up to 32 zones", WT_TUN_LOOPS, WT_NU, nullptr, tune_rule, tune_records, tune_restart, true},
 };
 constexpr int N_PROGRAMS = (int)(sizeof k_programs / sizeof *k_programs);
 static_assert(WT_PROG_CONTROL == 0 && WT_PROG_INJECT == 1 && WT_PROG_ALARM == 2 && WT_PROG_ACTUATOR == 3 && WT_PROG_DISTURB == 4 &&
-              WT_PROG_SCORE == 5 && WT_PROG_DETECT == 6 && WT_PROG_TREND == 7 && N_PROGRAMS == 8, "k_programs is indexed by WT_PROG_*");
-static_assert(WT_INFO_PROGRAM + N_PROGRAMS == WT_INFO_TRAIN, "wt_ensemble_info: one code per program, then the rest");
+              WT_PROG_SCORE == 5 && WT_PROG_DETECT == 6 && WT_PROG_TREND == 7 && WT_PROG_SERVICE == 8 && WT_PROG_TUNE == 9 &&
+              N_PROGRAMS == 10, "k_programs is indexed by WT_PROG_*");
+// wt_ensemble_info: one code per program up to the trend program, then the rest; service and tune have codes among the rest
+static_assert(WT_INFO_PROGRAM + WT_PROG_SERVICE == WT_INFO_TRAIN && WT_INFO_SERVICE == 22 && WT_INFO_TUNE == 23, "wt_ensemble_info codes");
 
 // -- the lifecycle
 
@@ -1512,10 +1632,17 @@ int check_program_set(const wt_ensemble *h, int program, const double *params)
 {
     const Program &p = k_programs[program];
     if (!h || !params) return fail(WT_E_ARG, "NULL argument");
-    const bool met = p.needs == NEEDS_PLANT_IO ? h->sens.plc_on != 0 : h->have_state && (p.needs == NEEDS_STATE || h->have_bc);
+    const bool met = p.needs == NEEDS_PLANT_IO ? h->sens.plc_on != 0 : p.needs == NEEDS_SENSORS ? h->sens.on != 0
+                   : h->have_state && (p.needs == NEEDS_STATE || h->have_bc);
     if (!met) return fail(WT_E_STATE, p.needs_text);
     if (p.zones && !wt::prog_in_item(levels_for(h->n))) return fail(WT_E_STATE, p.zones);
     return WT_OK;
+}
+
+// program off: its arrays released and its capacities 0, or, where the arrays are another part's, the switch alone
+void switch_off(const Program &p, const ArrayGroup &g)
+{
+    if (p.borrowed) *g.on = 0; else release(g);
 }
 
 // The rest of a set call once the call is accepted and its sizes and settings are in the handle: the arrays (those of
@@ -1527,13 +1654,13 @@ int load_program(wt_ensemble *h, int program, const double *params)
     const ArrayGroup g = p.arrays(h);
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still read or write the old records
-    if (int rc = allocate(g)) return rc;
+    if (int rc = p.borrowed ? WT_OK : allocate(g)) return rc;
     std::vector<double> par((size_t)h->N * p.slots * p.fields);
     blocks_to_records(params, p.slots, p.fields, h->N, par.data(), p.slots * p.fields);
     int rc = upload(h, (double *)*g.arrays[0].first, par);
     if (rc == WT_OK) rc = p.restart(h);
     if (rc == WT_OK) rc = sync_checked(h);      // the host vector is freed on return
-    if (rc != WT_OK) { release(g); return rc; }
+    if (rc != WT_OK) { switch_off(p, g); return rc; }
     *g.on = 1;
     return WT_OK;
 }
@@ -1560,13 +1687,13 @@ int reset_program(wt_ensemble *h, int program)
     return sync_checked(h);
 }
 
-// clear, and a set that replaces a program whose capacities may change: program off, arrays released, capacities 0
+// clear, and a set that replaces a program whose capacities may change
 int stop_program(wt_ensemble *h, int program)
 {
     if (!h) return fail(WT_E_ARG, "NULL handle");
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still use the records
-    release(k_programs[program].arrays(h));
+    switch_off(k_programs[program], k_programs[program].arrays(h));
     return WT_OK;
 }
 
@@ -1791,112 +1918,6 @@ int disturb_restore(wt_ensemble *h)
     if (!h->dst.on) return WT_OK;
     if (int rc = disturb_op(h, wtd::OP_RESTORE)) return rc;
     return sync_checked(h);
-}
-
-// -- the sensor service program (wt_svc.hpp): its records are the suite's (sensor_arrays), its switch is sens.svc_on
-static_assert(WT_SVC_SLOTS == wtsv::SLOTS && WT_NSV == wtsv::NSV && WT_NSVS == wtsv::NSVS && WT_NSH == wtsv::NSH &&
-              WT_SV_ENABLE == wtsv::V_ENABLE && WT_SV_REF2 == wtsv::V_REF2 && WT_SVS_N_DONE == wtsv::VS_N_DONE &&
-              WT_SVS_T_SEEN == wtsv::VS_T_SEEN && WT_SVC_CALIBRATE == wtsv::A_CALIBRATE &&
-              WT_SVC_REPLACE_REAGENT == wtsv::A_REPLACE_REAGENT && WT_SVC_ON_STATUS == wtsv::TR_ON_STATUS &&
-              WT_SVC_REF_TRIM == wtsv::REF_TRIM && WT_SH_FAULT == wtsv::H_FAULT && WT_N_SENSORS == wts::NSENS,
-              "service blocks of the C ABI");
-const char *k_service_not_set = "no service program is set (wt_ensemble_service_set)";
-const char *k_service_no_suite = "the sensor suite is not enabled (wt_ensemble_sensors_enable)";
-
-// what the reference would raise for, and the codes: an action on a sensor with a reference mode
-const char *service_action_error(double sensor, double action, double ref_mode)
-{
-    if (!whole_in(sensor, 0, WT_N_SENSORS - 1)) return "sensor must be an integer in 0..6";
-    if (!whole_in(action, 0, wtsv::N_ACTIONS - 1)) return "action must be an integer in 0..6";
-    if (!whole_in(ref_mode, 0, wtsv::N_REF_MODES - 1)) return "ref_mode must be 0 (constant), 1 (sample) or 2 (trim)";
-    const int a = (int)action;
-    if (a >= wtsv::A_TWO_POINT && a <= wtsv::A_PEPSIN_CLEAN && sensor > 1.0)
-        return "two-point calibration and cleaning are for the pH sensors (0, 1)";
-    if (a == wtsv::A_REPLACE_MEMBRANE && sensor != 2.0) return "only the amperometric chlorine sensor (2) has a membrane to replace";
-    if (a == wtsv::A_REPLACE_REAGENT && sensor != 3.0) return "only the DPD chlorine sensor (3) has a reagent to replace";
-    if (a == wtsv::A_TWO_POINT && ref_mode != (double)wtsv::REF_CONSTANT)
-        return "a two-point calibration takes its buffers as constants (ref_mode 0)";
-    return nullptr;
-}
-
-// The first refusal of a [WT_SVC_SLOTS][WT_NSV][N] block: slot by slot over the reactors, rule by rule in the header's order.
-const char *service_error(int64_t N, const double *p)
-{
-    for (int k = 0; k < WT_SVC_SLOTS; ++k)
-        for (int64_t r = 0; r < N; ++r) {
-            const auto at = [&](int f) { return p[((int64_t)k * WT_NSV + f) * N + r]; };
-            if (!whole_in(at(WT_SV_ENABLE), 0, 1)) return "enable must be 0 or 1";
-            if (at(WT_SV_ENABLE) == 0.0) continue;
-            if (!whole_in(at(WT_SV_SENSOR), 0, WT_N_SENSORS - 1)) return "sensor must be an integer in 0..6";
-            if (!whole_in(at(WT_SV_ACTION), 0, wtsv::N_ACTIONS - 1)) return "action must be an integer in 0..6";
-            if (!whole_in(at(WT_SV_TRIGGER), 0, wtsv::N_TRIGGERS - 1)) return "trigger must be 0 (at_time) or 1 (on_status)";
-            if (const char *msg = service_action_error(at(WT_SV_SENSOR), at(WT_SV_ACTION), at(WT_SV_REF_MODE))) return msg;
-            for (const int f : {WT_SV_T_FIRST, WT_SV_PERIOD, WT_SV_DELAY})
-                if (!(std::isfinite(at(f)) && at(f) >= 0.0)) return "t_first, period and delay must be finite and >= 0";
-            if (at(WT_SV_PERIOD) != 0.0 && at(WT_SV_PERIOD) < wtsv::MIN_PERIOD) return "period must be 0 (once) or at least 0.001 s";
-            if (!whole_in(at(WT_SV_COUNT), 0, 9007199254740991.0)) return "count must be a whole number >= 0 (0: no cap)";
-            if (!whole_in(at(WT_SV_STATUS), 0, 11)) return "status must be an integer in 0..11 (a SensorStatus code)";
-            if (!(std::isfinite(at(WT_SV_REF)) && std::isfinite(at(WT_SV_REF2)))) return "ref and ref2 must be finite";
-        }
-    return nullptr;
-}
-
-// the slot state at its set-time values, from the program's records on the host: 0, NaN, t_first, NaN
-int service_restart(wt_ensemble *h, const std::vector<double> &par)
-{
-    std::vector<double> st((size_t)h->N * wtsv::ST_DOUBLES);
-    for (size_t r = 0; r < (size_t)h->N; ++r)
-        for (int k = 0; k < wtsv::SLOTS; ++k) {
-            double *q = st.data() + r * wtsv::ST_DOUBLES + k * wtsv::NSVS;
-            q[wtsv::VS_N_DONE] = 0.0; q[wtsv::VS_T_LAST] = NAN; q[wtsv::VS_T_SEEN] = NAN;
-            q[wtsv::VS_T_DUE] = par[r * wtsv::PAR_DOUBLES + k * wtsv::NSV + wtsv::V_T_FIRST];
-        }
-    if (int rc = upload(h, h->sens.svc_st, st)) return rc;
-    return sync_checked(h);                     // the host vector is freed on return
-}
-
-// -- the tune program (wt_tun.hpp): its records are plant I/O's (plant_io_arrays), its switch is tun.on
-static_assert(WT_TUN_LOOPS == wtu::LOOPS && WT_TUN_LOOPS == WT_CTL_LOOPS && WT_NU == wtu::NU && WT_NUS == wtu::NUS &&
-              WT_TUN_ENABLE == wtu::U_ENABLE && WT_TUN_AMPLITUDE == wtu::U_AMPLITUDE && WT_TUN_COMMISSION == wtu::U_COMMISSION &&
-              WT_TUNS_PHASE == wtu::US_PHASE && WT_TUNS_N_CYCLES == wtu::US_N_CYCLES && WT_TUNS_KU == wtu::US_KU &&
-              WT_TUNS_COMMISSIONED == wtu::US_COMMISSIONED && WT_TUN_DONE == wtu::PH_DONE && WT_TUN_FAILED == wtu::PH_FAILED &&
-              WT_TUN_MAX_CYCLES == wtu::MAX_CYCLES, "tune blocks of the C ABI");
-const char *k_tune_not_set = "no tune program is set (wt_ensemble_tune_set)";
-// validate_flow_rate's maxima (__main__.py:57-63, :236-242) by loop: chlorine, acid
-constexpr double k_command_limit[WT_TUN_LOOPS] = {1.0, 2.0};
-
-// The first refusal of a [WT_TUN_LOOPS][WT_NU][N] block: loop by loop over the reactors, rule by rule in the header's order.
-const char *tune_error(int64_t N, const double *p)
-{
-    for (int l = 0; l < WT_TUN_LOOPS; ++l)
-        for (int64_t r = 0; r < N; ++r) {
-            const auto at = [&](int f) { return p[((int64_t)l * WT_NU + f) * N + r]; };
-            if (!whole_in(at(WT_TUN_ENABLE), 0, 1)) return "enable must be 0 or 1";
-            if (at(WT_TUN_ENABLE) == 0.0) continue;
-            if (!whole_in(at(WT_TUN_SENSOR), 0, WT_N_SENSORS - 1)) return "sensor must be an integer in 0..6";
-            if (at(WT_TUN_DIRECTION) != 1.0 && at(WT_TUN_DIRECTION) != -1.0) return "direction must be +1 or -1";
-            if (!(std::isfinite(at(WT_TUN_SETPOINT)) && std::isfinite(at(WT_TUN_BIAS)))) return "setpoint and bias must be finite";
-            const double d = at(WT_TUN_AMPLITUDE), b = at(WT_TUN_BIAS);
-            if (!(std::isfinite(d) && d > 0.0)) return "amplitude must be finite and > 0";
-            if (!(b - d >= 0.0 && b + d <= k_command_limit[l]))
-                return "bias - amplitude must be >= 0 and bias + amplitude at most the loop's command limit (1.0 chlorine, 2.0 acid)";
-            if (!(std::isfinite(at(WT_TUN_HYSTERESIS)) && at(WT_TUN_HYSTERESIS) >= 0.0)) return "hysteresis must be finite and >= 0";
-            if (!std::isfinite(at(WT_TUN_T_START))) return "t_start must be finite";
-            if (!(at(WT_TUN_T_MAX) > 0.0)) return "t_max must be > 0 (+inf: no time-out)";
-            if (!whole_in(at(WT_TUN_SETTLE), 0, 9007199254740991.0)) return "settle must be a whole number >= 0";
-            if (!whole_in(at(WT_TUN_CYCLES), 1, WT_TUN_MAX_CYCLES)) return "cycles must be an integer in 1..4096";
-            for (const int f : {WT_TUN_KP_FACTOR, WT_TUN_TI_FACTOR})
-                if (!(std::isfinite(at(f)) && at(f) >= 0.0)) return "kp_factor and ti_factor must be finite and >= 0";
-            if (!whole_in(at(WT_TUN_COMMISSION), 0, 1)) return "commission must be 0 or 1";
-        }
-    return nullptr;
-}
-
-// every loop waiting: the state all 0 (set and reset); queued on the handle's stream
-int tune_restart(wt_ensemble *h)
-{
-    HIP_TRY(hipMemsetAsync(h->tun.st, 0, sizeof(double) * wtu::ST_DOUBLES * (size_t)h->N, h->stream));
-    return WT_OK;
 }
 
 // ---- checkpoint, copy and rewind: one table of the handle's parts, which save, load, copy, mark,
@@ -2771,128 +2792,51 @@ int wt_ensemble_junction_clear(wt_ensemble *h)
     return sync_checked(h);
 }
 
-int wt_service_check(int64_t n_reactors, const double *params)
+// wt_service_check and wt_tune_check: wt_program_check under the names and in the words the two programs came with
+static int named_check(int program, int64_t n_reactors, const double *params)
 {
     if (n_reactors < 1) return fail(WT_E_ARG, "n_reactors must be >= 1");
     if (!params) return fail(WT_E_ARG, "NULL argument");
-    const char *msg = service_error(n_reactors, params);
-    return msg ? fail(WT_E_ARG, msg) : WT_OK;
+    return wt_program_check(program, params, n_reactors);
 }
+
+int wt_service_check(int64_t n_reactors, const double *params) { return named_check(WT_PROG_SERVICE, n_reactors, params); }
 
 int wt_ensemble_service_set(wt_ensemble *h, const double *params)
 {
-    if (!h) return fail(WT_E_ARG, "NULL handle");
-    if (!h->sens.on) return fail(WT_E_STATE, k_service_no_suite);
-    if (!wt::prog_in_item(levels_for(h->n))) return fail(WT_E_STATE, "service programs run in the kernels for up to 32 zones");
-    if (int rc = wt_service_check(h->N, params)) return rc;
-    std::vector<double> par((size_t)h->N * wtsv::PAR_DOUBLES);
-    blocks_to_records(params, wtsv::SLOTS, wtsv::NSV, h->N, par.data(), wtsv::PAR_DOUBLES);
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still use the old records
-    h->sens.svc_on = 0;
-    if (int rc = upload(h, (double *)h->sens.svc_par, par)) return rc;
-    if (int rc = service_restart(h, par)) return rc;
-    h->sens.svc_on = 1;
-    return WT_OK;
+    if (int rc = check_program_set(h, WT_PROG_SERVICE, params)) return rc;
+    if (int rc = wt_program_check(WT_PROG_SERVICE, params, h->N)) return rc;
+    return load_program(h, WT_PROG_SERVICE, params);
 }
 
 int wt_ensemble_service_get(wt_ensemble *h, double *state)
 {
     if (!h) return fail(WT_E_ARG, "NULL handle");
-    if (!h->sens.svc_on) return fail(WT_E_STATE, k_service_not_set);
-    HIP_TRY(hipSetDevice(h->device));
-    return download_records(h, {{state, h->sens.svc_st, wtsv::ST_DOUBLES, wtsv::SLOTS, wtsv::NSVS}});
+    return get_program(h, WT_PROG_SERVICE, {{state, h->sens.svc_st, wtsv::ST_DOUBLES, wtsv::SLOTS, wtsv::NSVS}});
 }
 
-int wt_ensemble_service_params(wt_ensemble *h, double *params)
-{
-    if (!h || !params) return fail(WT_E_ARG, "NULL argument");
-    if (!h->sens.svc_on) return fail(WT_E_STATE, k_service_not_set);
-    HIP_TRY(hipSetDevice(h->device));
-    return download_records(h, {{params, h->sens.svc_par, wtsv::PAR_DOUBLES, wtsv::SLOTS, wtsv::NSV}});
-}
+int wt_ensemble_service_params(wt_ensemble *h, double *params) { return wt_ensemble_program_params(h, WT_PROG_SERVICE, params); }
+int wt_ensemble_service_reset(wt_ensemble *h) { return reset_program(h, WT_PROG_SERVICE); }
+int wt_ensemble_service_clear(wt_ensemble *h) { return stop_program(h, WT_PROG_SERVICE); }
 
-int wt_ensemble_service_reset(wt_ensemble *h)
-{
-    if (!h) return fail(WT_E_ARG, "NULL handle");
-    if (!h->sens.svc_on) return fail(WT_E_STATE, k_service_not_set);
-    HIP_TRY(hipSetDevice(h->device));
-    std::vector<double> par((size_t)h->N * wtsv::PAR_DOUBLES);
-    if (int rc = download(h, {{par.data(), h->sens.svc_par, sizeof(double) * par.size()}})) return rc;
-    return service_restart(h, par);
-}
-
-int wt_ensemble_service_clear(wt_ensemble *h)
-{
-    if (!h) return fail(WT_E_ARG, "NULL handle");
-    if (!h->sens.svc_on) return WT_OK;
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still use the records
-    h->sens.svc_on = 0;
-    return WT_OK;
-}
-
-int wt_tune_check(int64_t n_reactors, const double *params)
-{
-    if (n_reactors < 1) return fail(WT_E_ARG, "n_reactors must be >= 1");
-    if (!params) return fail(WT_E_ARG, "NULL argument");
-    const char *msg = tune_error(n_reactors, params);
-    return msg ? fail(WT_E_ARG, msg) : WT_OK;
-}
+int wt_tune_check(int64_t n_reactors, const double *params) { return named_check(WT_PROG_TUNE, n_reactors, params); }
 
 int wt_ensemble_tune_set(wt_ensemble *h, const double *params)
 {
-    if (!h) return fail(WT_E_ARG, "NULL handle");
-    if (!h->sens.plc_on) return fail(WT_E_STATE, "tuners act on the plant I/O scan: enable plant I/O first");
-    if (!wt::prog_in_item(levels_for(h->n))) return fail(WT_E_STATE, "tune programs run in the kernels for up to 32 zones");
-    if (int rc = wt_tune_check(h->N, params)) return rc;
-    std::vector<double> par((size_t)h->N * wtu::PAR_DOUBLES);
-    blocks_to_records(params, wtu::LOOPS, wtu::NU, h->N, par.data(), wtu::PAR_DOUBLES);
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still use the old records
-    h->tun.on = 0;
-    if (int rc = upload(h, (double *)h->tun.par, par)) return rc;
-    if (int rc = tune_restart(h)) return rc;
-    if (int rc = sync_checked(h)) return rc;    // the host vector is freed on return
-    h->tun.on = 1;
-    return WT_OK;
+    if (int rc = check_program_set(h, WT_PROG_TUNE, params)) return rc;
+    if (int rc = wt_program_check(WT_PROG_TUNE, params, h->N)) return rc;
+    return load_program(h, WT_PROG_TUNE, params);
 }
 
 int wt_ensemble_tune_get(wt_ensemble *h, double *state)
 {
     if (!h) return fail(WT_E_ARG, "NULL handle");
-    if (!h->tun.on) return fail(WT_E_STATE, k_tune_not_set);
-    HIP_TRY(hipSetDevice(h->device));
-    return download_records(h, {{state, h->tun.st, wtu::ST_DOUBLES, wtu::LOOPS, wtu::NUS}});
+    return get_program(h, WT_PROG_TUNE, {{state, h->tun.st, wtu::ST_DOUBLES, wtu::LOOPS, wtu::NUS}});
 }
 
-int wt_ensemble_tune_params(wt_ensemble *h, double *params)
-{
-    if (!h || !params) return fail(WT_E_ARG, "NULL argument");
-    if (!h->tun.on) return fail(WT_E_STATE, k_tune_not_set);
-    HIP_TRY(hipSetDevice(h->device));
-    return download_records(h, {{params, h->tun.par, wtu::PAR_DOUBLES, wtu::LOOPS, wtu::NU}});
-}
-
-int wt_ensemble_tune_reset(wt_ensemble *h)
-{
-    if (!h) return fail(WT_E_ARG, "NULL handle");
-    if (!h->tun.on) return fail(WT_E_STATE, k_tune_not_set);
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still write the records
-    if (int rc = tune_restart(h)) return rc;
-    return sync_checked(h);
-}
-
-int wt_ensemble_tune_clear(wt_ensemble *h)
-{
-    if (!h) return fail(WT_E_ARG, "NULL handle");
-    if (!h->tun.on) return WT_OK;
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still use the records
-    h->tun.on = 0;
-    return WT_OK;
-}
+int wt_ensemble_tune_params(wt_ensemble *h, double *params) { return wt_ensemble_program_params(h, WT_PROG_TUNE, params); }
+int wt_ensemble_tune_reset(wt_ensemble *h) { return reset_program(h, WT_PROG_TUNE); }
+int wt_ensemble_tune_clear(wt_ensemble *h) { return stop_program(h, WT_PROG_TUNE); }
 
 int wt_ensemble_sensors_service(wt_ensemble *h, int sensor, int action, int ref_mode, const double *ref, const double *ref2,
                                 const uint8_t *mask)
@@ -3162,8 +3106,11 @@ int wt_ensemble_get_boundary(wt_ensemble *h, double *bc)
 int wt_ensemble_info(wt_ensemble *h, int what, int64_t *value)
 {
     if (!h || !value) return fail(WT_E_ARG, "NULL argument");
-    if (what >= WT_INFO_PROGRAM && what < WT_INFO_PROGRAM + N_PROGRAMS) {
-        *value = *k_programs[what - WT_INFO_PROGRAM].arrays(h).on != 0;
+    // the program codes: WT_INFO_PROGRAM + p up to the trend program, then the two that came after WT_INFO_TRAIN was taken
+    const int program = what == WT_INFO_SERVICE ? WT_PROG_SERVICE : what == WT_INFO_TUNE ? WT_PROG_TUNE
+                      : what >= WT_INFO_PROGRAM && what < WT_INFO_TRAIN ? what - WT_INFO_PROGRAM : -1;
+    if (program >= 0) {
+        *value = *k_programs[program].arrays(h).on != 0;
         return WT_OK;
     }
     switch (what) {
@@ -3181,8 +3128,6 @@ int wt_ensemble_info(wt_ensemble *h, int what, int64_t *value)
     case WT_INFO_BOUNDARY_UPLOADS: *value = h->bc_uploads; break;
     case WT_INFO_MARK: *value = h->mark != nullptr; break;
     case WT_INFO_JUNCTION: *value = h->trn.jct.on != 0; break;
-    case WT_INFO_SERVICE: *value = h->sens.svc_on != 0; break;
-    case WT_INFO_TUNE: *value = h->tun.on != 0; break;
     default: return fail(WT_E_ARG, "unknown info code");
     }
     return WT_OK;

@@ -1125,11 +1125,13 @@ int wt_tune_check(int64_t n_reactors, const double *params);
  * wt_ensemble_control_enable / retune, WT_PROG_INJECT: wt_ensemble_inject_set, WT_PROG_ALARM: wt_ensemble_alarm_set,
  * WT_PROG_ACTUATOR: wt_ensemble_actuator_set, WT_PROG_DISTURB: wt_ensemble_disturb_set, WT_PROG_SCORE:
  * wt_ensemble_score_set, WT_PROG_DETECT: the slot block of wt_ensemble_detect_set, whose label block that call checks
- * itself, WT_PROG_TREND: wt_ensemble_trend_set).  WT_OK when the block passes that call's checks; otherwise WT_E_ARG
- * and wt_last_error() is the message the call gives for it.  A NULL params, n_reactors < 1 or an unknown program
- * also give WT_E_ARG.  Makes no HIP call. */
+ * itself, WT_PROG_TREND: wt_ensemble_trend_set, WT_PROG_SERVICE: wt_ensemble_service_set, WT_PROG_TUNE:
+ * wt_ensemble_tune_set).  WT_OK when the block passes that call's checks; otherwise WT_E_ARG and wt_last_error() is the
+ * message the call gives for it.  A NULL params, n_reactors < 1 or an unknown program also give WT_E_ARG.  Makes no HIP
+ * call.  wt_service_check and wt_tune_check are this check under the two programs' own names: the same codes and
+ * texts, but n_reactors is looked at first and a NULL params is "NULL argument". */
 enum { WT_PROG_CONTROL = 0, WT_PROG_INJECT = 1, WT_PROG_ALARM = 2, WT_PROG_ACTUATOR = 3, WT_PROG_DISTURB = 4, WT_PROG_SCORE = 5,
-       WT_PROG_DETECT = 6, WT_PROG_TREND = 7 };
+       WT_PROG_DETECT = 6, WT_PROG_TREND = 7, WT_PROG_SERVICE = 8, WT_PROG_TUNE = 9 };
 int wt_program_check(int program, const double *params, int64_t n_reactors);
 /* the parameter block of a set program as its set (enable, retune) call took it, bit for bit: host, the shape
  * wt_program_check names for `program`; synchronises.  WT_E_STATE with the program's "not set" message while it is off,

@@ -43,9 +43,11 @@ class ControlRef:
         self.p = new
         self._start(switched_on)
 
-    def scan(self, values, faults, t_now, stepped=None):
+    def scan(self, values, faults, t_now, stepped=None, skip=None):
         """One PLC scan: ``values`` float32 (7, N) raw readings, ``faults`` (7, N), ``t_now`` (N,) the loop time the
-        scan stores, ``stepped`` (N,) reactors that took the step (default: all)."""
+        scan stores, ``stepped`` (N,) reactors that took the step (default: all).  ``skip`` (2, N) bool: loops a tune
+        program owns in this scan (``pi_execute``'s ``owned``): no state change and no holding word for them;
+        ``t_prev`` advances all the same."""
         N = self.p.shape[2]
         stepped = np.ones(N, dtype=bool) if stepped is None else np.asarray(stepped, dtype=bool)
         t_now = np.asarray(t_now, dtype=np.float64)
@@ -55,6 +57,8 @@ class ControlRef:
         for l in range(2):
             p, q = self.p[l], self.st[l]
             on = stepped & (p[C_ENABLE] == 1)
+            if skip is not None:
+                on &= ~np.asarray(skip, dtype=bool)[l]
             s = p[C_SENSOR].astype(np.int64)
             v = np.asarray(values, dtype=np.float32)[s, idx]
             f = np.asarray(faults)[s, idx]

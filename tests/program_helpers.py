@@ -193,17 +193,18 @@ def calls(n_steps, interval, lt=0.0, dt=DT):
 
 class HostScan:
     """The host side of the PLC scan of N reactors, the one host-side statement of the device's scan order: inject ->
-    pack -> apply commands -> alarm override -> actuator -> loop time -> PI -> alarm -> detector -> trend.  It holds the
-    restatements of the programs that are on (``ctl`` ControlRef, ``inj`` InjectRef, ``alm`` AlarmRef, ``act``
-    ActuatorRef, ``det`` DetectRef, ``trd`` TrendRef; None for a program that is off) and the loop time ``lt`` (N,) of
-    the next scan.  The disturbance and score programs run after every outer step, not in the scan, and stay outside.
+    pack -> apply commands -> alarm override -> actuator -> loop time -> tune -> PI -> alarm -> detector -> trend.  It
+    holds the restatements of the programs that are on (``ctl`` ControlRef, ``tun`` TuneRef, ``inj`` InjectRef, ``alm``
+    AlarmRef, ``act`` ActuatorRef, ``det`` DetectRef, ``trd`` TrendRef; None for a program that is off) and the loop
+    time ``lt`` (N,) of the next scan.  The disturbance and score programs run after every outer step and the service
+    program after every read, not in the scan, and stay outside.
 
     ``emulated``: the device runs plant I/O without these programs, and the host master emulates the command path in
     the words it writes before a call (``holding``).  Otherwise the device runs them, and ``scan`` follows its command
     path from the decoded commands it is given."""
 
-    def __init__(self, N, ctl=None, inj=None, alm=None, act=None, det=None, trd=None, emulated=False, dt=DT):
-        self.ctl, self.inj, self.alm, self.act, self.det, self.trd = ctl, inj, alm, act, det, trd
+    def __init__(self, N, ctl=None, inj=None, alm=None, act=None, det=None, trd=None, tun=None, emulated=False, dt=DT):
+        self.ctl, self.tun, self.inj, self.alm, self.act, self.det, self.trd = ctl, tun, inj, alm, act, det, trd
         self.emulated, self.dt = emulated, dt
         self.lt = np.zeros(N)
         self.values = None         # the tag -> rows dict the trend recorder saw at the last scan
@@ -224,12 +225,14 @@ class HostScan:
         return cmd
 
     def holding(self, cmd=None):
-        """The words a host master writes before a call: those of ``cmd`` (3, N), by default the PI's holding words.
+        """The words a host master writes before a call: those of ``cmd`` (3, N), by default the PI's holding words
+        (which a tuner beside it shares; the tuner's own without a PI).
         When ``emulated``, the injection's command slots and the alarm trips in force act on them here, at the loop time
         of the scan that closes the call; the alarm program then counts its overrides here and not in ``scan``."""
+        own = None if cmd is not None else self.tun.holding if self.ctl is None else self.ctl.holding
         if self.emulated and (self.tampers or self.alm is not None):
-            return words(self._command_path(commands(self.ctl.holding) if cmd is None else cmd))
-        return self.ctl.holding if cmd is None else words(cmd)
+            return words(self._command_path(commands(own) if cmd is None else cmd))
+        return own if cmd is None else words(cmd)
 
     def tag_values(self, v, f, vt, ft):
         """Tag -> rows of what a trend slot can read at the end of a scan, for every tag whose source is held here:
@@ -256,7 +259,8 @@ class HostScan:
           alarm override  the alarm trips in force
           actuator        and the actuators (no command path with ``cmd`` None);
           loop time       the scan stores ``lt``;
-          PI              runs on the tampered readings;
+          tune            the tuners run on the tampered readings and own the loops whose experiment is live;
+          PI              runs on the tampered readings and skips the loops the tuners owned in this scan;
           alarm           FIELD slots on the raw readings, IMAGE slots on the tampered ones;
           detector        likewise;
           trend           last: a sample is an entry of ``tag_values`` as it stands at the end of this scan, with the
@@ -269,8 +273,10 @@ class HostScan:
             cmd = self._command_path(cmd, stepped)
             if self.act is not None:
                 self.act.scan(cmd, t, stepped)
+        if self.tun is not None:
+            self.tun.scan(vt, ft, t, stepped)
         if self.ctl is not None:
-            self.ctl.scan(vt, ft, t, stepped)
+            self.ctl.scan(vt, ft, t, stepped, skip=None if self.tun is None else self.tun.owned)
         if self.alm is not None:
             self.alm.scan(v, f, t, stepped, image=(vt, ft))
         if self.det is not None:

@@ -1,5 +1,5 @@
 """The ensemble handle's lifecycle (include/wtphys.h): the refusals of calls made out of order, with their exact messages,
-for every one of the eight per-reactor programs; a handle whose sensor history, plant I/O, recording and eight programs
+for every one of the ten per-reactor programs; a handle whose sensor history, plant I/O, recording and ten programs
 are released and set again mid-run giving the bits of one that was set up once; and a cleared program leaving nothing
 behind."""
 import ctypes as C
@@ -66,6 +66,14 @@ def _table(wt, native, cols):
         Program("trend", L.wt_ensemble_trend_set, wt.trend_block(nr, wt.Trend("image_value", "chlorine_outlet")), (4, 0), null, null,
                 "trends read the plant I/O scan: enable plant I/O first", "trend programs run in the kernels for up to 32 zones",
                 "no trend program is set (wt_ensemble_trend_set)", ("trend_state", "reset_trends", "trend_data"), "clear_trends"),
+        Program("service", L.wt_ensemble_service_set, wt.service_block(nr, wt.Service("chlorine_outlet", "calibrate", at=60.0)), (),
+                null, null, "the sensor suite is not enabled (wt_ensemble_sensors_enable)",
+                "service programs run in the kernels for up to 32 zones",
+                "no service program is set (wt_ensemble_service_set)", ("service_state", "service_params", "reset_services"),
+                "clear_services"),
+        Program("tune", L.wt_ensemble_tune_set, wt.tune_block(nr, wt.RelayTune("chlorine_outlet", 1.5, 0.25, 0.5)), (), null, null,
+                "tuners act on the plant I/O scan: enable plant I/O first", "tune programs run in the kernels for up to 32 zones",
+                "no tune program is set (wt_ensemble_tune_set)", ("tuner_state", "tuner_params", "reset_tuners"), "clear_tuners"),
     )
 
 
@@ -161,11 +169,13 @@ def _programs(wt, cols):
             (wt.Detector("chlorine_outlet", "cusum", 5.0, sigma=0.05, ref="track", tau=100.0),
              wt.Detector("pH_outlet", "ewma", 3.0, sigma=0.1, ref_value=7.0, source="field")),
             (wt.Trend("image_value", "chlorine_outlet"), wt.Trend("command", "acid", every=2),
-             wt.Trend("control", ("chlorine", "output"), deadband=0.01), wt.Trend("alarm_word")))
+             wt.Trend("control", ("chlorine", "output"), deadband=0.01), wt.Trend("alarm_word")),
+            (wt.Service("chlorine_outlet", "calibrate", at=60.0, every=50.0, ref_mode="trim"), wt.Service("pH_outlet", "rinse", at=30.0)),
+            (wt.RelayTune("chlorine_outlet", np.asarray(cols["initial_chlorine"]), 0.2, 0.3, start=40.0, settle=0, cycles=1), None))
 
 
 def _set_all(ens, progs, history, curve, bins, capacity):
-    ctl, inj, alm, act, dst, scr, det, trd = progs
+    ctl, inj, alm, act, dst, scr, det, trd, svc, tun = progs
     ens.enable_control(*ctl)
     ens.set_injections(*inj)
     ens.set_alarms(*alm)
@@ -174,6 +184,8 @@ def _set_all(ens, progs, history, curve, bins, capacity):
     ens.set_scores(*scr, curve=curve, bins=bins, fan_range=(0.0, 30.0))
     ens.set_detectors(*det, attack=(60.0, 150.0))
     ens.set_trends(*trd, capacity=capacity, wrap=True)
+    ens.set_services(*svc)
+    ens.set_tuners(*tun)
 
 
 def _fields(obj):
@@ -185,7 +197,8 @@ def _observe(ens):
             + (ens.injection_state().block(),) + ens.alarm_state().block() + (ens.alarm_words(),)
             + ens.actuator_state().block() + tuple(vars(ens.trajectory()).values())
             + _fields(ens.disturbance_state()) + ens.disturbance_history() + _fields(ens.score_state()) + _fields(ens.score_curve())
-            + _fields(ens.detector_state()) + _fields(ens.trend_state()) + _fields(ens.trend_data()))
+            + _fields(ens.detector_state()) + _fields(ens.trend_state()) + _fields(ens.trend_data())
+            + _fields(ens.service_state()) + (ens.tuner_state().block(),))
 
 
 def test_released_and_reset_groups_give_the_bits_of_a_handle_set_up_once(gpu, wt):
@@ -202,6 +215,7 @@ def test_released_and_reset_groups_give_the_bits_of_a_handle_set_up_once(gpu, wt
         if cycle:   # every group released and allocated again
             ens.disable_control(); ens.clear_injections(); ens.clear_alarms(); ens.clear_actuators()
             ens.clear_disturbances(); ens.clear_scores(); ens.clear_detectors(); ens.clear_trends()
+            ens.clear_services(); ens.clear_tuners()
             ens.record(capacity=0)
         # otherwise: set calls that replace the programs in place, at the new capacities
         _set_all(ens, progs, history=16, curve=12, bins=8, capacity=16)
@@ -228,7 +242,7 @@ def test_a_cleared_program_is_refused_again_and_leaves_no_capacity_behind(gpu, w
         for read in p.reads:
             _raises(native, p.not_set, getattr(ens, read))
     # the smallest capacities after the larger ones: nothing of the released arrays' sizes is left in the handle
-    _, _, _, _, dst, scr, _, trd = progs
+    dst, scr, trd = progs[4], progs[5], progs[7]
     ens.set_disturbances(*dst, history=0)
     ens.set_scores(*scr)
     ens.set_trends(*trd, capacity=1)

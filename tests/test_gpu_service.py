@@ -262,16 +262,12 @@ def test_refusals_on_a_device(gpu, wt):
     ens = wt.ReactorEnsemble(cols, n_zones=8); ens.set_boundary(bc)
     blk = wt.service_block(4, wt.Service("chlorine_outlet", "calibrate", at=60.0))
     assert L.wt_ensemble_service_set(ens._h, gpu.dptr(blk)) == gpu.WT_E_STATE
-    assert L.wt_last_error().decode() == "the sensor suite is not enabled (wt_ensemble_sensors_enable)"
     for call in (lambda: ens.service_sensors("pH_inlet", "rinse"), ens.sensor_health):
         with pytest.raises(ValueError, match="sensor suite is not enabled"):
             call()
     bare = ens.checkpoint()
     ens.enable_sensors(seed=5)
     assert ens.info(gpu.WT_INFO_SERVICE) == 0
-    for call in (ens.service_state, ens.service_params, ens.reset_services):
-        with pytest.raises(ValueError, match="no service program is set"):
-            call()
     ens.clear_services()                                   # no effect while none is set
     ens.set_services(wt.Service("chlorine_outlet", "calibrate", at=60.0))
     assert ens.info(gpu.WT_INFO_SERVICE) == 1
@@ -291,7 +287,6 @@ def test_refusals_on_a_device(gpu, wt):
     big.enable_sensors(seed=seed, history=8)
     blk = wt.service_block(2, wt.Service("chlorine_outlet", "calibrate", at=60.0))
     assert L.wt_ensemble_service_set(big._h, gpu.dptr(blk)) == gpu.WT_E_STATE
-    assert L.wt_last_error().decode() == "service programs run in the kernels for up to 32 zones"
     suite = SR.ServicedSuite(cfg.flow_rate, cfg.initial_chlorine, cfg.temperature, 0.0, seed, 1)
     f32 = lambda x: float(np.float32(x))
     ov = np.empty((8, 7))

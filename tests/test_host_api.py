@@ -156,6 +156,24 @@ def test_program_check_without_a_device(native, wt):
     bad[0, 4, 0], bad[0, 1, 1] = 9.0, -1.0
     assert L.wt_program_check(native.WT_PROG_ACTUATOR, native.dptr(bad), N) == native.WT_E_ARG
     assert L.wt_last_error() == b"delay must be an integer in 0..8"
+    # the service and tune programs: wt_service_check and wt_tune_check are the same check under their own names
+    for program, named, good, (slot, row), msg in (
+            (native.WT_PROG_SERVICE, L.wt_service_check, wt.service_block(N, wt.Service("chlorine_outlet", "calibrate", at=60.0)),
+             (0, 5), "period must be 0 (once) or at least 0.001 s"),
+            (native.WT_PROG_TUNE, L.wt_tune_check, wt.tune_block(N, acid=wt.RelayTune("pH_outlet", 7.2, 0.5, 1.5)),
+             (1, 5), "bias - amplitude must be >= 0 and bias + amplitude at most the loop's command limit (1.0 chlorine, 2.0 acid)")):
+        bad = good.copy()
+        bad[slot, row, N - 1] = 1e-4 if program == native.WT_PROG_SERVICE else 0.75
+        for blk, code, text in ((good, native.WT_OK, None), (np.zeros_like(good), native.WT_OK, None), (bad, native.WT_E_ARG, msg)):
+            for check in (lambda: L.wt_program_check(program, native.dptr(blk), N), lambda: named(N, native.dptr(blk))):
+                assert check() == code, (program, text)
+                assert text is None or L.wt_last_error().decode() == text
+        assert L.wt_program_check(program, native.dptr(good), 0) == named(0, native.dptr(good)) == native.WT_E_ARG
+        assert L.wt_last_error() == b"n_reactors must be >= 1"
+        assert named(0, None) == native.WT_E_ARG and L.wt_last_error() == b"n_reactors must be >= 1"   # their own order
+        assert named(N, None) == native.WT_E_ARG and L.wt_last_error() == b"NULL argument"             # and their own text
+    assert L.wt_program_check(native.WT_PROG_TUNE + 1, native.dptr(off[native.WT_PROG_CONTROL]), N) == native.WT_E_ARG
+    assert L.wt_last_error() == b"unknown program"
 
 
 def test_no_silent_cpu_fallback(native, wt):
@@ -348,6 +366,18 @@ PROGRAMS = {
                r"WT_NTS = 4\b", r"WT_PROG_TREND = 7\b"),
               "wt_trd.hpp", ("Trend", "TrendState", "TrendData", "trend_block"),
               ("set_trends", "trend_state", "trend_data", "reset_trends", "clear_trends")),
+    "service": (("wt_ensemble_service_set", "wt_ensemble_service_get", "wt_ensemble_service_params", "wt_ensemble_service_reset",
+                 "wt_ensemble_service_clear", "wt_service_check"),
+                (r"#define WT_SVC_SLOTS 4\b", r"WT_SVC_REPLACE_REAGENT = 6\b", r"WT_SV_REF2 = 11\b", r"WT_NSV = 12\b",
+                 r"WT_NSVS = 4\b", r"WT_INFO_SERVICE = 22\b", r"WT_PROG_SERVICE = 8\b"),
+                "wt_svc.hpp", ("Service", "ServiceState", "service_block"),
+                ("set_services", "service_state", "service_params", "reset_services", "clear_services")),
+    "tune": (("wt_ensemble_tune_set", "wt_ensemble_tune_get", "wt_ensemble_tune_params", "wt_ensemble_tune_reset",
+              "wt_ensemble_tune_clear", "wt_tune_check"),
+             (r"#define WT_TUN_LOOPS 2\b", r"WT_TUN_COMMISSION = 13\b", r"WT_NU = 14\b", r"WT_TUNS_COMMISSIONED = 19\b",
+              r"WT_NUS = 20\b", r"WT_INFO_TUNE = 23\b", r"WT_PROG_TUNE = 9\b"),
+             "wt_tun.hpp", ("RelayTune", "LoopTune", "TunerState", "tune_block"),
+             ("set_tuners", "tuner_state", "tuner_params", "reset_tuners", "clear_tuners")),
 }
 
 

@@ -7,6 +7,7 @@ import pytest
 
 import detect_ref as KR
 import trend_ref as TR
+import tune_ref as UR
 from actuator_ref import ActuatorRef
 from alarm_ref import AlarmRef
 from control_ref import ControlRef
@@ -182,3 +183,60 @@ def test_image_slots_see_the_spoof_and_field_slots_the_instrument(case, all_six)
         took = np.nonzero(stepped[:, r])[0]
         assert np.all(_series(new["trd"], 3, r) == float(np.float32(SPOOF))) and len(_series(new["trd"], 3, r)) == len(took)
         assert np.array_equal(_series(new["trd"], 4, r), v[took[::2], CL, r].astype(np.float64)), r
+
+
+def test_tuner_before_the_pi_which_skips_the_loops_it_owns(wt):
+    """``HostScan(N, ctl=, tun=)`` against the hand-written pair it stands for: ``TuneRef.scan``, then ``ControlRef.scan``
+    with the loops the tuner owned as its skip mask.  Twelve reactors, forty scans; the chlorine_outlet reading is a square
+    wave around the tuners' setpoint, so the relays cycle; reactor 3 reads a fault code and reactor 4 NaN for a few scans,
+    reactors 5 and 0 each miss one; the experiments start at three different times, every second one commissions its PI
+    loop, reactor 10 has no chlorine PI loop and reactor 11 no tuner."""
+    n_r, scans = 12, 40
+    rng = np.random.default_rng(23)
+    r = np.arange(n_r)
+    v = rng.uniform([[6.5], [6.5], [0.5], [0.5], [4.0], [10.0], [10.0]], [[8.0], [8.0], [3.0], [3.0], [8.0], [25.0], [25.0]],
+                    (scans, 7, n_r)).astype(np.float32)
+    v[:, CL] = (np.where((np.arange(scans) // 4) % 2 == 0, 1.25, 1.75)[:, None] + 0.05 * rng.random((scans, n_r))).astype(np.float32)
+    f = np.zeros((scans, 7, n_r), dtype=np.int64)
+    f[9:12, CL, 3] = 2
+    v[14:17, CL, 4] = np.nan
+    stepped = np.ones((scans, n_r), dtype=bool)
+    stepped[13, 5] = stepped[21, 0] = False
+    cblock = wt.control_block(n_r, wt.PILoop("chlorine_outlet", setpoint=1.5, kp=0.3, ki=1e-3, bias=0.2, enable=np.where(r == 10, 0, 1)),
+                              wt.PILoop("pH_outlet", setpoint=7.0, kp=0.3, ki=1e-3, direction=-1, bias=0.1))
+    tblock = wt.tune_block(n_r, wt.RelayTune("chlorine_outlet", 1.5, 0.25, 0.5, start=50.0 + 120.0 * (r % 3), settle=0, cycles=2,
+                                             commission=r % 2, enable=np.where(r == 11, 0, 1)))
+    pairs = []
+    for _ in range(2):
+        ctl = ControlRef(cblock, np.zeros(n_r))
+        pairs.append((ctl, UR.TuneRef(tblock, ctl=ctl)))
+    (ctl, tun), (hs_ctl, hs_tun) = pairs
+    hs = HostScan(n_r, ctl=hs_ctl, tun=hs_tun)
+    kept = np.zeros((2, n_r), dtype=bool)
+    for k, _ in zip(range(scans), hs.calls(scans * INTERVAL, INTERVAL)):
+        before = ctl.st.copy()
+        tun.scan(v[k], f[k], hs.lt, stepped[k])
+        ctl.scan(v[k], f[k], hs.lt, stepped[k], skip=tun.owned)
+        hs.scan(v[k], f[k], stepped=stepped[k])
+        # a loop whose experiment is still running after the scan was owned and not commissioned: its PI state stands
+        running = tun.owned & (tun.st[:, UR.US_PHASE] == UR.RUNNING)
+        for l in range(2):
+            assert np.array_equal(ctl.st[l][:, running[l]], before[l][:, running[l]]), (k, l)
+        kept |= running
+        assert np.array_equal(ctl.t_prev[stepped[k]], hs.lt[stepped[k]])               # t_prev advances, owned or not
+    state = lambda c, t: (c.st, c.t_prev, c.holding, c.p, t.st, t.owned, t.holding)
+    assert_all_equal(state(ctl, tun), state(hs_ctl, hs_tun), "tuner + PI")
+    assert hs.holding() is hs_ctl.holding and hs_tun.holding is hs_ctl.holding
+    # the run was worth comparing
+    phase, com = tun.st[0, UR.US_PHASE], tun.st[0, UR.US_COMMISSIONED] == 1
+    assert kept[0, :10].all() and not kept[0, 11] and not kept[1].any()
+    assert (phase[:11] == UR.DONE).all() and phase[11] == UR.WAITING and len(np.unique(tun.st[0, UR.US_T_BEGIN, :11])) == 3
+    assert np.array_equal(com, (r % 2 == 1) & (r < 10)) and np.array_equal(ctl.p[0, 4, com], tun.st[0, UR.US_KP, com])
+    assert tun.st[0, UR.US_N_HELD, 3] > 0 and tun.st[0, UR.US_N_HELD, 4] > 0
+    scans_taken = stepped.sum(axis=0)
+    assert np.array_equal(ctl.st[1, 5] + ctl.st[1, 6], scans_taken)                      # the acid PI ran at every scan taken
+    assert np.all((ctl.st[0, 5] + ctl.st[0, 6])[:10] < scans_taken[:10]) and np.all((ctl.st[0, 5] + ctl.st[0, 6])[:10] > 0)
+    assert ctl.st[0, 5, 11] + ctl.st[0, 6, 11] == scans_taken[11]                        # no tuner: the chlorine PI never skipped
+    # a tuner without a PI: the words HostScan hands the master are the tuner's
+    alone = UR.TuneRef(tblock)
+    assert HostScan(n_r, tun=alone, emulated=True).holding() is alone.holding

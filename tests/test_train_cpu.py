@@ -130,7 +130,7 @@ def test_symbols_constants_and_exports(native, wt, trn):
 
 def test_the_train_program_takes_no_program_code(native, wt):
     blk = wt.train_block(4, 8, 2)
-    assert native.lib().wt_program_check(8, native.dptr(blk), 4) == native.WT_E_ARG
+    assert native.lib().wt_program_check(native.WT_PROG_TUNE + 1, native.dptr(blk), 4) == native.WT_E_ARG
     assert native.lib().wt_last_error() == b"unknown program"
     assert native.lib().wt_abi_version() == 1
 

@@ -126,7 +126,7 @@ def test_every_refusal_has_the_builders_message(native, wt):
     ok[1, 4] = ok[1, 5] = 5.0
     ok[2, 1:] = np.nan
     assert L.wt_program_check(native.WT_PROG_TREND, native.dptr(ok), N) == native.WT_OK
-    assert L.wt_program_check(8, native.dptr(good), N) == native.WT_E_ARG                                   # the next code is unknown
+    assert L.wt_program_check(native.WT_PROG_TUNE + 1, native.dptr(good), N) == native.WT_E_ARG             # the code after the last is unknown
 
 
 def _feed(ref, series, times, tag=TR.IMAGE_VALUE, stepped=None):

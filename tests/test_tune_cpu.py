@@ -162,10 +162,11 @@ def test_tune_symbols_declared_and_exported(native, wt):
     assert re.search(r"constexpr int LOOPS = wtc::LOOPS, NU = 14, NUS = 20;", src)
     assert "#pragma clang fp contract(off)" in src
     assert (UR.U_COMMISSION, UR.US_COMMISSIONED, UR.US_KU, UR.US_T_DONE) == (13, 19, 12, 16)
-    # the tune program stands beside the program table, in the plant I/O part
+    # the tune program is an entry of the program table that borrows its records: they stay in the plant I/O part
     lib_src = open(os.path.join(native.CSRC, "wtphys.hip")).read()
     table = lib_src[lib_src.index("const Program k_programs[] = {"):lib_src.index("constexpr int N_PROGRAMS")]
-    assert "tune" not in table
+    assert "tune_rule, tune_records, tune_restart, true}" in table and native.WT_PROG_TUNE == 9
+    assert re.search(r"WT_PROG_SERVICE = 8, WT_PROG_TUNE = 9\b", header)
     assert re.search(r"\{S_I32, &h->sens\.plc_on, true\}, \{S_I32, &h->tun\.on, false\}", lib_src)
 
 
@@ -303,6 +304,7 @@ def test_skip_mask_and_commissioning_on_a_control_ref():
         t = np.full(N, (k + 1) * 10.0)
         pi_before = ctl.st.copy()
         ref.scan(v, f, t)
+        ctl.scan(v, f, t, skip=ref.owned)                                                # as HostScan.scan runs the two
         history.append(ref.owned.copy())
         assert np.array_equal(ctl.t_prev, t)                                             # the shared t_prev advances
         own = ref.owned[0]
@@ -326,6 +328,7 @@ def test_skip_mask_and_commissioning_on_a_control_ref():
     v[SENSOR] = 1.5
     integral1 = ctl.st[0, CS_INTEGRAL, 1]
     ref.scan(v, f, np.full(N, 260.0))
+    ctl.scan(v, f, np.full(N, 260.0), skip=ref.owned)
     assert not ref.owned.any()
     assert ctl.st[0, CS_OUTPUT, 0] == (0.2 + kp * 0.0) + (0.3 + (ki * 0.0) * 10.0) == 0.5
     assert ctl.st[0, CS_OUTPUT, 1] == (0.2 + 0.8 * 0.0) + integral1

@@ -147,9 +147,9 @@ def test_symbols_constants_and_exports(native, wt, wir):
     for name in ("set_wires", "wire_state", "wire_params", "clear_wires"):
         assert callable(getattr(wt.ReactorEnsemble, name)), name
     assert "wt_wir.hpp" in native.BUILD_SOURCES and native.lib().wt_abi_version() == 1
-    # the program takes no code of wt_program_check: code 8 stays unknown
+    # the program takes no code of wt_program_check: the code after the last program's stays unknown
     blk = _own(6)
-    assert native.lib().wt_program_check(8, native.dptr(blk), 6) == native.WT_E_ARG
+    assert native.lib().wt_program_check(native.WT_PROG_TUNE + 1, native.dptr(blk), 6) == native.WT_E_ARG
     assert "unknown" in native.lib().wt_last_error().decode()
 
 

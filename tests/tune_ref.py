@@ -3,8 +3,8 @@ reactors.
 
 numpy fp64 never contracts a product and a sum into an fma, its division and square root are correctly rounded, and
 every expression below has the association the device code has, so the results are bit-comparable with
-``ReactorEnsemble.tuner_state()``.  ``TuneRef`` has the interface ``HostScan`` asks of its ``ctl`` (``scan``,
-``holding``, ``st``): with a ``ControlRef`` inside it runs the tuners, then the PI loops the tuners did not own.
+``ReactorEnsemble.tuner_state()``.  ``TuneRef`` is ``HostScan``'s ``tun``: it runs before the PI programs, and the
+loops it ``owned`` in a scan are the ones ``ControlRef.scan`` then skips.
 """
 import numpy as np
 
@@ -19,8 +19,9 @@ WAITING, RUNNING, DONE, FAILED = range(4)
 
 class TuneRef:
     """State of both tuners of N reactors.  ``params``: (2, 14, N) block.  ``ctl``: the ``ControlRef`` of the PI
-    programs that run beside the tuners (its holding words are then the tuners'), or None: then ``holding`` (N, 6)
-    are the words the tuners write into (default: all 0, as plant I/O starts)."""
+    programs that run beside the tuners, kept for two things only: a tuner commissions its gains into it, and its
+    holding words are then the tuners'.  None: then ``holding`` (N, 6) are the words the tuners write into (default:
+    all 0, as plant I/O starts).  ``owned`` (2, N): the loops the tuners owned in the last scan."""
 
     def __init__(self, params, ctl=None, holding=None):
         self.p = np.array(params, dtype=np.float64)
@@ -111,11 +112,3 @@ class TuneRef:
             w = HOLDING_WORD[l]
             self.holding[write, w:w + 2] = float32_words(q[US_OUTPUT, write])
             self.owned[l] = live
-        if self.ctl is not None:
-            # the PI program skips the loops the tuners owned: no state change, no word; its t_prev advances
-            st, words = self.ctl.st.copy(), self.holding.copy()
-            self.ctl.scan(values, faults, t_now, stepped)
-            for l in range(2):
-                m, w = self.owned[l], HOLDING_WORD[l]
-                self.ctl.st[l][:, m] = st[l][:, m]
-                self.holding[m, w:w + 2] = words[m, w:w + 2]

@@ -46,7 +46,7 @@ def host_loop():
     ref = TuneRef(block)
     ens.synchronize()
     t0 = time.perf_counter()
-    HostScan(N, ctl=ref, emulated=True, dt=DT).run(ens, K, 1, fused=False, image=True)
+    HostScan(N, tun=ref, emulated=True, dt=DT).run(ens, K, 1, fused=False, image=True)
     dt = time.perf_counter() - t0
     out = outputs(ens, *OUT)
     ens.close()
