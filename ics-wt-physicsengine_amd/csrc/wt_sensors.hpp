@@ -20,7 +20,7 @@
 // interact (two of them hold the two sensors that share a delay line, read one after the other as
 // read_all_sensors does); lane l of a pass runs group l / R of reactor l % R of the wavefront's R reactors.
 // Sensor state is structure-of-arrays in HBM (L2-resident), read and written back by the same lane every step.
-// Signal path in fp32 (config 5); time and the slow ageing accumulators in fp64.
+// Signal path in fp32 (config 5); time, the sample lines' timestamps and the slow ageing accumulators in fp64.
 //
 // Randomness: the reference seeds numpy from `secrets`; here every rng.normal / rng.random /
 // rng.choice of the reference is one draw of Philox4x32-10 with key = suite seed and
@@ -63,7 +63,8 @@ struct SuiteArgs {
     double *ds;            // [NSENS][ND][N]
     int32_t *is;           // [NSENS][NI][N]
     float *full_scale;     // [N] flow sensor range
-    float *ring_t, *ring_v; // [2][RING][N]
+    double *ring_t;        // [2][RING][N] timestamps of the two sample lines (fp64: the closest-sample decision is the reference's)
+    float *ring_v;         // [2][RING][N] the samples
     int32_t *ring_push, *ring_cursor; // [2][N] appends so far; push index of the last sample returned
     float *out_value;      // [NSENS][N] last reading
     uint8_t *out_status, *out_fault; // [NSENS][N]
@@ -90,9 +91,10 @@ struct StepIO {
     int fault[NSENS][RMAX];
     double cmd[3][RMAX];        // boundary rows in force after the command path: inlet, acid, chlorine flow
     // sample-line hand-off from the line's first sensor (pH) to its second (RTD): appends / winner after the first,
-    // and the entry the first has just appended (push index, -1: none)
+    // and the entry the first has just appended (push index, -1: none; its timestamp in fp64 like the ring's)
+    double lt[2][RMAX];
     int lpush[2][RMAX], lcur[2][RMAX], lfresh[2][RMAX];
-    float lt[2][RMAX], lv[2][RMAX];
+    float lv[2][RMAX];
 };
 
 // ---------------------------------------------------------------- Philox4x32-10
@@ -188,27 +190,31 @@ template <class A> __device__ __forceinline__ void store_state(const A &a, int i
 // return the value whose timestamp is closest to t - 30 s (min() keeps the first of equal distances).
 // Timestamps never decrease and neither does the target, so the winner never moves backwards: the
 // search resumes from the previous winner (`cursor`, an absolute push index) and walks forward while a
-// later, different timestamp is strictly closer -- the same element a scan of all 100 entries finds
-// (the fp32 differences are exact, so equal distances only occur for equal or mirror-image timestamps).
+// later, different timestamp is strictly closer -- the same element a scan of all 100 entries finds.
+// Timestamps, target and distances are fp64 like the reference's.  Off the integer grid two entries often lie at
+// nearly the same distance from the target (30 / dt a half-integer: dt = 0.8 s, 2.4 s, ...), and which of them is
+// closer is then a matter of the last bits of t - 30 and of the stored timestamps: in fp32 (as this search was first
+// written) about every second read at such a step took the sample one step away from the reference's
+// (tests/test_gpu_sensor_edges.py).  The samples themselves stay fp32.
 struct Line {
-    float *rt, *rv; int64_t N; int pushes, cursor;
+    double *rt; float *rv; int64_t N; int pushes, cursor;
     // an entry another lane of this wavefront appended during this read (taken from the hand-off, not from memory)
-    int fresh_j; float fresh_t, fresh_v;
-    __device__ __forceinline__ float mem_t(int j) const { return (j == fresh_j) ? fresh_t : rt[(int64_t)(j % RING) * N]; }
+    int fresh_j; double fresh_t; float fresh_v;
+    __device__ __forceinline__ double mem_t(int j) const { return (j == fresh_j) ? fresh_t : rt[(int64_t)(j % RING) * N]; }
     __device__ __forceinline__ float mem_v(int j) const { return (j == fresh_j) ? fresh_v : rv[(int64_t)(j % RING) * N]; }
-    __device__ __forceinline__ float transport(float t, float tv)
+    __device__ __forceinline__ float transport(double t, float tv)
     {
         const int slot = pushes % RING;
         rt[(int64_t)slot * N] = t; rv[(int64_t)slot * N] = tv;
         ++pushes;
         const int oldest = max(0, pushes - RING);
         int c = max(cursor, oldest);
-        const float target = t - 30.0f;
+        const double target = t - 30.0;
         // The winner moves on by about one entry per read, so the entries c .. c+3 are fetched in one go (eight
         // independent loads, one memory round trip) instead of one dependent load per comparison; the walk below
         // falls back to memory only beyond them.  The entry just pushed comes from registers.
         constexpr int WIN = 4;
-        float wt[WIN], wv[WIN];
+        double wt[WIN]; float wv[WIN];
 #pragma unroll
         for (int i = 0; i < WIN; ++i) {
             const int j = c + i;
@@ -217,17 +223,17 @@ struct Line {
             wv[i] = mem ? mem_v(j) : tv;
         }
         const int c0 = c;
-        auto ts = [&](int j) -> float {
+        auto ts = [&](int j) -> double {
             const int i = j - c0;
             if (i < WIN) return i == 0 ? wt[0] : (i == 1 ? wt[1] : (i == 2 ? wt[2] : wt[3]));
             return (j == pushes - 1) ? t : mem_t(j);
         };
-        float tc = wt[0];
-        float dc = fabsf(tc - target);
+        double tc = wt[0];
+        double dc = fabs(tc - target);
         for (int j = c + 1; j < pushes; ++j) {
-            const float tj = ts(j);
+            const double tj = ts(j);
             if (tj == tc) continue;                     // same timestamp: the earlier entry wins
-            const float dj = fabsf(tj - target);
+            const double dj = fabs(tj - target);
             if (!(dj < dc)) break;
             c = j; tc = tj; dc = dj;
         }
@@ -379,10 +385,12 @@ __device__ __forceinline__ void read_finish(const SensorSpec &sp, SState &s, con
         fin = cur * fmaxf(0.9f, 1.0f - 0.005f * (float)s.slow0) + z1;
         if (fin < 0.01f * fs) fin = 0.0f;
     } else {
-        const float R_meas = 100.0f * (1.0f + 0.00385f * cur) + 2.0f * 0.5f;
-        const float power_mW = (1.0e-3f * 1.0e-3f) * R_meas * 1000.0f;
-        const float T_meas = (R_meas / 100.0f - 1.0f) / 0.00385f;
-        fin = T_meas + 0.001f * power_mW + z1;
+        // The reference goes through the resistance and back: R = 100 (1 + 0.00385 T) + 1 (lead wires),
+        // T_meas = (R / 100 - 1) / 0.00385, plus 0.001 x the self-heating power 1e-3 R [mW].  Evaluated as written, fp32
+        // returns the roundings of 1 + 0.00385 T and of R 260 times as large (R / 100 - 1 cancels): 3e-5 degC, beyond
+        // what the signal path is held to once the reading is near 0 degC.  The same function without the
+        // cancellation: T_meas = T + 0.01 / 0.00385, 0.001 x power = 1.01e-4 + 3.85e-7 T.
+        fin = cur + (float)(0.01 / 0.00385) + (1.01e-4f + 3.85e-7f * cur) + z1;
         fin += 0.01f * (cur - AMBIENT_T);
     }
     fin = fminf(fmaxf(fin, sp.lo), sp.hi);
@@ -427,7 +435,7 @@ __device__ __forceinline__ void suite_step(const A &a, StepIO &io, const int *ri
         float value = 0; int rstatus = 0, rfault = 0;
         SState st; ReadCtx c = {false, 0.0f, 0.0f, 0.0}; bool go = false;
         SensorSpec sp = spec_of(0, 0.0f);
-        Line ln = {nullptr, nullptr, N, 0, 0, -1, 0.0f, 0.0f};
+        Line ln = {nullptr, nullptr, N, 0, 0, -1, 0.0, 0.0f};
         if (active) {
             fs = a.full_scale[r];
             t = io.t_after[sl] - a.t_enable[r];
@@ -440,9 +448,9 @@ __device__ __forceinline__ void suite_step(const A &a, StepIO &io, const int *ri
         if (first) {                                         // SampleLine.transport_sample of the pH sensors  :598-609
             ln.pushes = a.ring_push[(int64_t)line * N + r]; ln.cursor = a.ring_cursor[(int64_t)line * N + r];
             const float pushed = c.tv;
-            if (go) c.tv = ln.transport((float)t, c.tv);
+            if (go) c.tv = ln.transport(t, c.tv);
             io.lpush[line][sl] = ln.pushes; io.lcur[line][sl] = ln.cursor;
-            io.lfresh[line][sl] = go ? ln.pushes - 1 : -1; io.lt[line][sl] = (float)t; io.lv[line][sl] = pushed;
+            io.lfresh[line][sl] = go ? ln.pushes - 1 : -1; io.lt[line][sl] = t; io.lv[line][sl] = pushed;
         }
         // (one wavefront: its LDS operations complete in order; the fence only stops the compiler from moving them)
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -451,7 +459,7 @@ __device__ __forceinline__ void suite_step(const A &a, StepIO &io, const int *ri
         if (second) {                                        // ... then of the RTDs on the same lines
             ln.pushes = io.lpush[line][sl]; ln.cursor = io.lcur[line][sl];
             ln.fresh_j = io.lfresh[line][sl]; ln.fresh_t = io.lt[line][sl]; ln.fresh_v = io.lv[line][sl];
-            if (go) c.tv = ln.transport((float)t, c.tv);
+            if (go) c.tv = ln.transport(t, c.tv);
             a.ring_push[(int64_t)line * N + r] = ln.pushes; a.ring_cursor[(int64_t)line * N + r] = ln.cursor;
         }
         if (active) {

@@ -238,7 +238,7 @@ ArrayGroup sensor_arrays(wt_ensemble *h)
                                {(void **)&s.ds, sizeof(double) * wts::NSENS * wts::ND * N},
                                {(void **)&s.is, sizeof(int32_t) * wts::NSENS * wts::NI * N},
                                {(void **)&s.full_scale, sizeof(float) * N},
-                               {(void **)&s.ring_t, sizeof(float) * 2 * wts::RING * N},
+                               {(void **)&s.ring_t, sizeof(double) * 2 * wts::RING * N},
                                {(void **)&s.ring_v, sizeof(float) * 2 * wts::RING * N},
                                {(void **)&s.ring_push, sizeof(int32_t) * 2 * N}, {(void **)&s.ring_cursor, sizeof(int32_t) * 2 * N},
                                {(void **)&s.out_value, sizeof(float) * wts::NSENS * N},
@@ -1014,7 +1014,7 @@ int wt_ensemble_sensors_enable(wt_ensemble *h, uint64_t seed, int64_t reactor_ba
     if (e == hipSuccess) e = hipMemcpy(cfg + N, cfg_chlorine, sizeof(double) * N, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(cfg + 2 * N, cfg_temperature, sizeof(double) * N, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpyAsync((double *)s.t_enable, h->time, sizeof(double) * N, hipMemcpyDeviceToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(s.ring_t, 0, sizeof(float) * 2 * wts::RING * N, h->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(s.ring_t, 0, sizeof(double) * 2 * wts::RING * N, h->stream);
     if (e == hipSuccess) e = hipMemsetAsync(s.ring_v, 0, sizeof(float) * 2 * wts::RING * N, h->stream);
     // the service program's records, off: no slot enabled, no state (a checkpoint holds them whether or not one is set)
     if (e == hipSuccess) e = hipMemsetAsync((void *)s.svc_par, 0, sizeof(double) * wtsv::PAR_DOUBLES * N, h->stream);
