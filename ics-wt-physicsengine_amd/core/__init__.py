@@ -16,6 +16,7 @@ from .train import PipeState, TrainState, pipe_block, pipe_delay, train_block
 from .wire import Wire, WireState, wire_block
 from .junction import Junction, JunctionState, junction_block
 from .service import Service, ServiceState, service_block
+from .install import Installation, installation_block
 from .tune import TUNE_RULES, LoopTune, RelayTune, TunerState, tune_block
 from .chemistry import AqueousChemistry, BufferSystem, solve_pH
 from .physics import (ArrheniusParameters, FlowParameters, GeometryParameters, SpatialModel, StratificationParameters,
@@ -33,7 +34,7 @@ __all__ = ["BoundaryConditions", "EnsembleState", "IntegratedCSTR", "PhysicsEngi
            "Detector", "DetectorState", "detector_block", "attack_window",
            "Trend", "TrendData", "TrendState", "trend_block", "TrainState", "train_block", "PipeState", "pipe_block", "pipe_delay",
            "Wire", "WireState", "wire_block", "Junction", "JunctionState", "junction_block",
-           "Service", "ServiceState", "service_block",
+           "Service", "ServiceState", "service_block", "Installation", "installation_block",
            "RelayTune", "LoopTune", "TunerState", "TUNE_RULES", "tune_block",
            "AqueousChemistry", "BufferSystem", "solve_pH", "make_ensemble", "make_boundary_schedule", "params", "sharding", "gather_state", "shard_bounds",
            # the rest of wt_simulator.core's export list (core/__init__.py:238-263)

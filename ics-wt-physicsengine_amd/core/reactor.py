@@ -18,8 +18,8 @@ from typing import Dict, Iterable, List, Optional, Sequence, Union
 
 import numpy as np
 
-from . import (_native, _program, actuator, alarm, control, detect, disturb, inject, junction, params, score, service, train,
-               trend, tune, wire)
+from . import (_native, _program, actuator, alarm, control, detect, disturb, inject, install, junction, params, score, service,
+               train, trend, tune, wire)
 
 logger = logging.getLogger(__name__)
 
@@ -544,6 +544,26 @@ class ReactorEnsemble:
         out = np.empty((7, service.NSH, self.n_reactors), dtype=np.float64)
         self._program_call(_native.lib().wt_ensemble_sensors_health, _native.dptr(out))
         return {k: np.array(out[:, i]) for i, k in enumerate(service.HEALTH_ROWS)}
+
+    # -- the installation: every reactor's own sample lines and InstallationQuality (wt_ins.hpp)
+    def set_installation(self, inst: "install.Installation") -> None:
+        """Give every reactor its own sample lines and instrument installation (:class:`Installation`) from the next
+        read on; needs the sensor suite.  Replaces the installation in force.  Mid-run the lines keep their samples
+        and only the delay changes."""
+        blk = install.installation_block(self.n_reactors, inst)
+        self._program_call(_native.lib().wt_ensemble_install_set, _native.dptr(blk))
+
+    def installation(self) -> np.ndarray:
+        """The (9, N) block of the installation in force, rows in :data:`install.PARAM_ROWS` order; the suite's own
+        build while none is set."""
+        blk = np.empty((install.NINS, self.n_reactors), dtype=np.float64)
+        self._program_call(_native.lib().wt_ensemble_install_get, _native.dptr(blk))
+        return blk
+
+    def clear_installation(self) -> None:
+        """Back to the suite's own build for every reactor (250 mL at 500 mL/min, 0.5 m/s, no bubbles, grounding 0.9,
+        vibration 0.1 g, ambient 30 degC)."""
+        self._program_call(_native.lib().wt_ensemble_install_clear)
 
     # -- plant I/O: one virtual Modbus slave per reactor (NEXT-2 / NEXT-3)
     INPUT_REGISTERS = {"pH_inlet": 0, "pH_middle": 2, "pH_outlet": 4, "chlorine_inlet": 6, "chlorine_outlet": 8, "flow_rate": 10,

@@ -81,6 +81,7 @@ struct StepArgs {
     wtr::TrnArgs trn;    // the train program: stages feed their downstream after every outer step (wt_ensemble_train_*; trn.on == 0: none)
     wtw::WirArgs wir;    // the wire program: a train's signal cables, routed at the head of a PLC scan (wt_ensemble_wire_*; wir.on == 0: none)
     wtu::TunArgs tun;    // per-reactor relay autotune programs run at PLC scans before the PI programs (wt_ensemble_tune_*; tun.on == 0: none)
+    wtin::InsArgs ins;   // the installation records of the sensor suite (wt_ensemble_install_*; ins.on == 0: the suite's own build)
 };
 static_assert(sizeof(StepArgs) <= 4096, "the kernel-argument segment holds at most 4 KiB");
 constexpr int NB = 10;     // rows of a boundary block (WT_NB)

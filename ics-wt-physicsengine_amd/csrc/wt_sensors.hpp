@@ -30,6 +30,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "wt_plc.hpp"
+#include "wt_ins.hpp"
 
 namespace wts {
 
@@ -150,8 +151,9 @@ __device__ __forceinline__ SensorSpec spec_of(int i, float fs)
 
 // InstallationQuality of the suite (sensors/__init__.py:53-59): none of the installation-effect
 // branches of base_sensor.py:464-507 fires (flow 0.5 >= 0.1, no bubbles, grounding 0.9 >= 0.8,
-// vibration 0.1 <= 0.2), so they draw nothing; ambient temperature 30 degC enters the RTD stem error.
-constexpr float AMBIENT_T = 30.0f;
+// vibration 0.1 <= 0.2), so they draw nothing; ambient temperature 30 degC enters the RTD stem error.  These and the
+// 30 s of the two sample lines are the defaults of wtin::Lane; an installation record (wt_ins.hpp) replaces them
+// reactor by reactor.
 
 // Sensors only interact through the two sample lines ({pH_inlet, temp_inlet} share the inlet line, {pH_outlet,
 // temp_outlet} the outlet line): one lane runs one sensor of one reactor, and the two sensors of a line take their
@@ -187,8 +189,9 @@ template <class A> __device__ __forceinline__ void store_state(const A &a, int i
 }
 
 // SampleLine.transport_sample base_sensor.py:177-216: append (t, value) to a deque(maxlen = 100), then
-// return the value whose timestamp is closest to t - 30 s (min() keeps the first of equal distances).
-// Timestamps never decrease and neither does the target, so the winner never moves backwards: the
+// return the value whose timestamp is closest to t - delay (min() keeps the first of equal distances).
+// Timestamps never decrease and neither does the target (a set call that changes the delay puts the cursor back to 0,
+// and a walk from the oldest entry is always right), so the winner never moves backwards: the
 // search resumes from the previous winner (`cursor`, an absolute push index) and walks forward while a
 // later, different timestamp is strictly closer -- the same element a scan of all 100 entries finds.
 // Timestamps, target and distances are fp64 like the reference's.  Off the integer grid two entries often lie at
@@ -202,14 +205,14 @@ struct Line {
     int fresh_j; double fresh_t; float fresh_v;
     __device__ __forceinline__ double mem_t(int j) const { return (j == fresh_j) ? fresh_t : rt[(int64_t)(j % RING) * N]; }
     __device__ __forceinline__ float mem_v(int j) const { return (j == fresh_j) ? fresh_v : rv[(int64_t)(j % RING) * N]; }
-    __device__ __forceinline__ float transport(double t, float tv)
+    __device__ __forceinline__ float transport(double t, float tv, double delay)
     {
         const int slot = pushes % RING;
         rt[(int64_t)slot * N] = t; rv[(int64_t)slot * N] = tv;
         ++pushes;
         const int oldest = max(0, pushes - RING);
         int c = max(cursor, oldest);
-        const double target = t - 30.0;
+        const double target = t - delay;
         // The winner moves on by about one entry per read, so the entries c .. c+3 are fetched in one go (eight
         // independent loads, one memory round trip) instead of one dependent load per comparison; the walk below
         // falls back to memory only beyond them.  The entry just pushed comes from registers.
@@ -283,14 +286,33 @@ __device__ __forceinline__ bool read_begin(const SensorSpec &sp, SState &s, cons
 }
 
 // from the sample line's output (c.tv) on                                                           :598-699
+// ins: the reactor's installation (the suite's build unless a record is set; then the draw count of a read depends on it)
 __device__ __forceinline__ void read_finish(const SensorSpec &sp, SState &s, const ReadCtx &c, double t, float fs,
-                                            float &value, int &rstatus, int &rfault)
+                                            const wtin::Lane &ins, float &value, int &rstatus, int &rfault)
 {
     const bool cal_expired = c.cal_expired;
     const float temp = c.temp, tv = c.tv;
     const float drift = sp.drift_rate * (float)c.cal_hours + s.cal_offset;       // :612-616
     const float noise = s.rng.normal(sp.precision);                              // :619
     float cur = 0.5f * (tv + noise + drift) + 0.5f * s.current;                  // :622-626 (hysteresis :630 is a no-op)
+    if (__builtin_expect(ins.flags != 0, 0)) {                                   // _apply_installation_effects :464-507
+        // One draw per branch taken, in the reference's order, which is the flags' bit order: stagnant scatter, the
+        // bubble draw, grounding noise, vibration noise.  A bubble returns NaN: no draw after it.  One loop for the four,
+        // not unrolled, so that this cold block is one Philox call long inside a kernel larger than the instruction cache.
+        bool live = true;
+#pragma unroll 1
+        for (int e = 0; e < 4; ++e) {
+            if (!(live && ((ins.flags >> e) & 1))) continue;
+            uint32_t x[4]; s.rng.next(x);
+            if (e == 1) {
+                // the 24-bit uniform is exact in fp32 and in fp64; the comparison is the reference's, in fp64
+                if ((double)((float)(x[0] >> 8) * (1.0f / 16777216.0f)) < ins.bubble_p) { cur = __builtin_nanf(""); live = false; }
+            } else {
+                const float scale = (e == 0) ? sp.precision * 2.0f : ((e == 2) ? sp.precision * ins.ground_scale : ins.vibration * sp.precision);
+                cur += scale * box_muller(x);
+            }
+        }
+    }
     float rate = 0.0f;                                                           // :638-648
     if (s.hist_n > 0) {
         const float dtl = (float)(t - s.last_t);
@@ -336,7 +358,8 @@ __device__ __forceinline__ void read_finish(const SensorSpec &sp, SState &s, con
         // slow0 = membrane_fouling, slow1 = days_since_cleaning, slow2 = reference_contamination
         if (have_dt) {
             const double bio = (s.slow0 > 0.05) ? 0.1 * exp(0.05 * ((double)temp - 25.0)) : 0.001;
-            s.slow0 = fmin(1.0, s.slow0 + (bio + 100.0 * 0.00001) * dday);
+            const double scaling = 100.0 * ((ins.flags & wtin::F_STAGNANT) ? 0.0001 : 0.00001);   // ph_sensor.py:203-206
+            s.slow0 = fmin(1.0, s.slow0 + (bio + scaling) * dday);
             s.slow1 += dday;
         }
         days = (t - s.cal_time) / 86400.0;
@@ -346,7 +369,7 @@ __device__ __forceinline__ void read_finish(const SensorSpec &sp, SState &s, con
         ndraw = 3;
     } else if (sp.kind == K_CL_AMP) {                                            // chlorine_sensor.py:310-331,405-449
         // slow0 = membrane fouling, slow1 = membrane age [d]
-        if (have_dt) { s.slow0 = fmin(1.0, s.slow0 + 0.01 * dday); s.slow1 += dday; }
+        if (have_dt) { s.slow0 = fmin(1.0, s.slow0 + ((ins.flags & wtin::F_STAGNANT) ? 0.05 : 0.01) * dday); s.slow1 += dday; }   // :335-338
         sc1 = 0.005f * (1.0f + (float)s.slow1 / 365.0f);                         // polarisation
         sc2 = 0.003f;                                                            // diffusion
         ndraw = 2;
@@ -369,6 +392,8 @@ __device__ __forceinline__ void read_finish(const SensorSpec &sp, SState &s, con
     float z2 = 0.0f, z3 = 0.0f;
     if (ndraw >= 2) z2 = s.rng.normal(sc2);
     if (ndraw >= 3) z3 = s.rng.normal(sc3);
+    // flow_sensor.py:150-154: the magnetic flowmeter's one draw is behind it, so the dropout's counter is the next
+    const bool dropout = __builtin_expect((ins.flags & wtin::F_BUBBLES) != 0, 0) && sp.kind == K_FLOW_MAG && (double)s.rng.uniform() < ins.bubble_p;
     float fin;
     if (sp.kind == K_PH) {
         const float slope_pct = fmaxf(90.0f, 100.0f - 0.001f * (float)days);     // ph_sensor.py:262-266
@@ -383,6 +408,7 @@ __device__ __forceinline__ void read_finish(const SensorSpec &sp, SState &s, con
         fin = cur * (float)s.slow0 * 0.95f + z1;
     } else if (sp.kind == K_FLOW_MAG) {
         fin = cur * fmaxf(0.9f, 1.0f - 0.005f * (float)s.slow0) + z1;
+        if (dropout) fin = 0.0f;
         if (fin < 0.01f * fs) fin = 0.0f;
     } else {
         // The reference goes through the resistance and back: R = 100 (1 + 0.00385 T) + 1 (lead wires),
@@ -391,7 +417,7 @@ __device__ __forceinline__ void read_finish(const SensorSpec &sp, SState &s, con
         // what the signal path is held to once the reading is near 0 degC.  The same function without the
         // cancellation: T_meas = T + 0.01 / 0.00385, 0.001 x power = 1.01e-4 + 3.85e-7 T.
         fin = cur + (float)(0.01 / 0.00385) + (1.01e-4f + 3.85e-7f * cur) + z1;
-        fin += 0.01f * (cur - AMBIENT_T);
+        fin += 0.01f * (cur - ins.ambient);
     }
     fin = fminf(fmaxf(fin, sp.lo), sp.hi);
     s.current = fin; s.last_value = fin; value = fin;
@@ -420,8 +446,9 @@ struct NoService {
     template <class A> __device__ __forceinline__ void operator()(const A &, const SensorSpec &, SState &, int, const float *, int64_t, double, int) const {}
 };
 
-template <class A, class SV = NoService>
-__device__ __forceinline__ void suite_step(const A &a, StepIO &io, const int *rix, int R, const int *hist0, int k, SV sv = SV())
+// ia: the installation records (wtin::InsArgs, read in place like a; ia.on == 0: the suite's own build for every reactor)
+template <class A, class I, class SV = NoService>
+__device__ __forceinline__ void suite_step(const A &a, const I &ia, StepIO &io, const int *rix, int R, const int *hist0, int k, SV sv = SV())
 {
     const int lane = threadIdx.x & 63;
     for (int base = 0; base < NSENS * R; base += 64) {
@@ -436,6 +463,9 @@ __device__ __forceinline__ void suite_step(const A &a, StepIO &io, const int *ri
         SState st; ReadCtx c = {false, 0.0f, 0.0f, 0.0}; bool go = false;
         SensorSpec sp = spec_of(0, 0.0f);
         Line ln = {nullptr, nullptr, N, 0, 0, -1, 0.0, 0.0f};
+        wtin::Lane ins;
+        if (active && __builtin_expect(ia.on != 0, 0)) ins = wtin::load_lane(ia.par, r);   // (wave-uniform flag)
+        const double delay = (line == 1) ? ins.delay_outlet : ins.delay_inlet;
         if (active) {
             fs = a.full_scale[r];
             t = io.t_after[sl] - a.t_enable[r];
@@ -448,7 +478,7 @@ __device__ __forceinline__ void suite_step(const A &a, StepIO &io, const int *ri
         if (first) {                                         // SampleLine.transport_sample of the pH sensors  :598-609
             ln.pushes = a.ring_push[(int64_t)line * N + r]; ln.cursor = a.ring_cursor[(int64_t)line * N + r];
             const float pushed = c.tv;
-            if (go) c.tv = ln.transport(t, c.tv);
+            if (go) c.tv = ln.transport(t, c.tv, delay);
             io.lpush[line][sl] = ln.pushes; io.lcur[line][sl] = ln.cursor;
             io.lfresh[line][sl] = go ? ln.pushes - 1 : -1; io.lt[line][sl] = t; io.lv[line][sl] = pushed;
         }
@@ -459,11 +489,11 @@ __device__ __forceinline__ void suite_step(const A &a, StepIO &io, const int *ri
         if (second) {                                        // ... then of the RTDs on the same lines
             ln.pushes = io.lpush[line][sl]; ln.cursor = io.lcur[line][sl];
             ln.fresh_j = io.lfresh[line][sl]; ln.fresh_t = io.lt[line][sl]; ln.fresh_v = io.lv[line][sl];
-            if (go) c.tv = ln.transport(t, c.tv);
+            if (go) c.tv = ln.transport(t, c.tv, delay);
             a.ring_push[(int64_t)line * N + r] = ln.pushes; a.ring_cursor[(int64_t)line * N + r] = ln.cursor;
         }
         if (active) {
-            if (go) read_finish(sp, st, c, t, fs, value, rstatus, rfault);
+            if (go) read_finish(sp, st, c, t, fs, ins, value, rstatus, rfault);
             sv(a, sp, st, i, &io.tap[0][sl], r, t, rstatus);
             store_state(a, i, r, st);
             emit(a, i, r, pos, value, rstatus, rfault);

@@ -715,8 +715,8 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
             }
             __syncthreads();
             // read_all_sensors; then the service program (wave-uniform flag), which the n > 32 kernel leaves out
-            if constexpr (prog_in_item(LV)) wts::suite_step(b->sens, io, rix, R, hist0, k, wtsv::Program());
-            else wts::suite_step(b->sens, io, rix, R, hist0, k);
+            if constexpr (prog_in_item(LV)) wts::suite_step(b->sens, b->ins, io, rix, R, hist0, k, wtsv::Program());
+            else wts::suite_step(b->sens, b->ins, io, rix, R, hist0, k);
             if (plc_on) {
                 const int gs = b->first_step + step0 + k;
                 const bool scan = ((gs + 1) % b->sens.scan_every == 0) || (gs + 1 == b->call_steps);

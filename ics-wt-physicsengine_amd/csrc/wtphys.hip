@@ -124,6 +124,8 @@ struct wt_ensemble {
     wtw::WirArgs wir = {};
     // The tune program (wt_tun.hpp; WT_PROG_TUNE of k_programs): its records are plant I/O's arrays, its switch a PLIO scalar.
     wtu::TunArgs tun = {};
+    // The installation records of the sensor suite (wt_ins.hpp; not one of k_programs): the suite's arrays and a SENS scalar.
+    wtin::InsArgs ins = {};
     // optional per-launch HIP-event timing (bench.py roofline accounting)
     bool time_launches = false;
     std::vector<hipEvent_t> lt_pool;   // start/stop pairs
@@ -161,7 +163,7 @@ wt::StepArgs make_args(const wt_ensemble *h, double dt, int n_steps, int first_s
     a.trace = h->trace; a.trace_cap = h->trace_cap;
     a.kt = wt::default_ktab(); a.rt = wt::default_rtab();
     a.kt.dense_bias = h->knob_dense ? 1.0 : 0.0;
-    a.sens = h->sens; a.ctl = h->ctl; a.inj = h->inj; a.alm = h->alm; a.act = h->act; a.dst = h->dst; a.scr = h->scr; a.det = h->det; a.trd = h->trd; a.trn = h->trn; a.wir = h->wir; a.tun = h->tun;
+    a.sens = h->sens; a.ctl = h->ctl; a.inj = h->inj; a.alm = h->alm; a.act = h->act; a.dst = h->dst; a.scr = h->scr; a.det = h->det; a.trd = h->trd; a.trn = h->trn; a.wir = h->wir; a.tun = h->tun; a.ins = h->ins;
     // a full curve takes no more entries: the launches then carry no curve pointer at all
     const bool curve = h->scr.counts && h->scr_steps < h->scr.curve_cap;
     if (!curve) a.scr.counts = nullptr;
@@ -229,7 +231,8 @@ ArrayGroup queue_arrays(wt_ensemble *h)
                                {(void **)&h->q_next, sizeof(int32_t) * (size_t)h->n_groups}}};
 }
 
-// the history arrays only for hist_cap > 0; the service program's records (wt_svc.hpp) come and go with the suite
+// the history arrays only for hist_cap > 0; the service program's records (wt_svc.hpp) and the installation records
+// (wt_ins.hpp) come and go with the suite
 ArrayGroup sensor_arrays(wt_ensemble *h)
 {
     wts::SuiteArgs &s = h->sens;
@@ -246,9 +249,10 @@ ArrayGroup sensor_arrays(wt_ensemble *h)
                                {(void **)&s.t_enable, sizeof(double) * N},
                                {(void **)&s.svc_par, sizeof(double) * wtsv::PAR_DOUBLES * N},
                                {(void **)&s.svc_st, sizeof(double) * wtsv::ST_DOUBLES * N},
+                               {(void **)&h->ins.par, sizeof(double) * wtin::REC_DOUBLES * N},
                                {(void **)&s.hist_value, sizeof(float) * hist}, {(void **)&s.hist_status, hist},
                                {(void **)&s.hist_fault, hist}, {(void **)&s.hist_pos, s.hist_cap > 0 ? sizeof(int32_t) * N : 0}},
-            [h] { h->sens.hist_cap = 0; h->sens.svc_on = 0; }};
+            [h] { h->sens.hist_cap = 0; h->sens.svc_on = 0; h->ins.on = 0; }};
 }
 
 // the tune program's records (wt_tun.hpp) come and go with plant I/O
@@ -871,6 +875,92 @@ int run_steps(wt_ensemble *h, double dt, int n_steps, int fused)
     return rc;
 }
 
+// ---- the installation records of the sensor suite (wt_ins.hpp)
+
+static_assert(WT_NINS == wtin::NINS && WT_INS_LINE_VOLUME_INLET == wtin::P_LINE_VOLUME_INLET &&
+              WT_INS_LINE_FLOW_OUTLET == wtin::P_LINE_FLOW_OUTLET && WT_INS_FLOW_VELOCITY == wtin::P_FLOW_VELOCITY &&
+              WT_INS_AIR_BUBBLE_FREQUENCY == wtin::P_AIR_BUBBLE_FREQUENCY && WT_INS_GROUNDING_QUALITY == wtin::P_GROUNDING_QUALITY &&
+              WT_INS_PIPE_VIBRATION_G == wtin::P_PIPE_VIBRATION_G && WT_INS_AMBIENT_TEMPERATURE == wtin::P_AMBIENT_TEMPERATURE,
+              "installation blocks of the C ABI");
+static_assert(wts::RING == 100, "the ring bound of install_error is the reference's 100-entry buffer");
+
+const char *const k_install_fields[wtin::NINS] = {"inlet_line_volume_mL", "inlet_line_flow_mL_min", "outlet_line_volume_mL",
+                                                  "outlet_line_flow_mL_min", "flow_velocity", "air_bubble_frequency",
+                                                  "grounding_quality", "pipe_vibration_g", "ambient_temperature"};
+// create_realistic_sensor_suite's build (sensors/__init__.py:53-67)
+constexpr double k_install_defaults[wtin::NINS] = {250.0, 500.0, 250.0, 500.0, 0.5, 0.0, 0.9, 0.1, 30.0};
+
+// SampleLine.__post_init__ (base_sensor.py:167-171), in its order of operations
+double line_delay(double volume_mL, double flow_mL_min)
+{
+    const double volume_L = volume_mL / 1000.0;
+    const double flow_L_s = flow_mL_min / 1000.0 / 60.0;
+    return flow_L_s > 0 ? volume_L / flow_L_s : 0.0;
+}
+
+// The first refusal of a [WT_NINS][N] block, reactor by reactor and at one reactor in the order of the header's list;
+// empty when the block passes.
+std::string install_error(int64_t N, const double *p)
+{
+    const auto at = [&](int k, int64_t r) { return p[(int64_t)k * N + r]; };
+    const auto bad = [&](int k, int64_t r, const char *rule) {
+        return std::string(k_install_fields[k]) + " " + rule + " (reactor " + std::to_string(r) + ")";
+    };
+    for (int64_t r = 0; r < N; ++r) {
+        for (int k = 0; k < wtin::NINS; ++k)
+            if (!std::isfinite(at(k, r))) return bad(k, r, "must be finite");
+        for (int k = wtin::P_LINE_VOLUME_INLET; k <= wtin::P_LINE_FLOW_OUTLET; ++k)
+            if (at(k, r) < 0.0) return bad(k, r, "must be >= 0");
+        for (int line = 0; line < 2; ++line) {
+            // SampleLine sizes its buffer max(100, int(delay) + 10) (base_sensor.py:174); the device's ring holds 100
+            const double delay = line_delay(at(2 * line, r), at(2 * line + 1, r));
+            if (!(delay < 91.0))
+                return bad(2 * line, r, "and flow give a delay of 91 s or more: the reference's buffer grows beyond 100 entries "
+                                        "(int(delay) + 10 > 100), the device's ring does not");
+        }
+        if (!(at(wtin::P_FLOW_VELOCITY, r) >= 0.0 && at(wtin::P_FLOW_VELOCITY, r) <= 5.0)) return bad(wtin::P_FLOW_VELOCITY, r, "must be in 0..5 m/s");
+        if (at(wtin::P_AIR_BUBBLE_FREQUENCY, r) < 0.0) return bad(wtin::P_AIR_BUBBLE_FREQUENCY, r, "must be >= 0");
+        if (!(at(wtin::P_GROUNDING_QUALITY, r) >= 0.0 && at(wtin::P_GROUNDING_QUALITY, r) <= 1.0))
+            return bad(wtin::P_GROUNDING_QUALITY, r, "must be in 0..1");
+        if (at(wtin::P_PIPE_VIBRATION_G, r) < 0.0) return bad(wtin::P_PIPE_VIBRATION_G, r, "must be >= 0");
+    }
+    return std::string();
+}
+
+// The device records of a checked [WT_NINS][N] block (nullptr: the defaults for every reactor).  Delays, the bubble
+// probability and the threshold decisions are taken here, in fp64 on the doubles as given.
+std::vector<double> install_records(int64_t N, const double *p)
+{
+    std::vector<double> rec((size_t)N * wtin::REC_DOUBLES, 0.0);
+    for (int64_t r = 0; r < N; ++r) {
+        double *q = rec.data() + r * wtin::REC_DOUBLES;
+        double *c = q + wtin::R_PARAMS;
+        for (int k = 0; k < wtin::NINS; ++k) c[k] = p ? p[(int64_t)k * N + r] : k_install_defaults[k];
+        q[wtin::R_DELAY_INLET] = line_delay(c[wtin::P_LINE_VOLUME_INLET], c[wtin::P_LINE_FLOW_INLET]);
+        q[wtin::R_DELAY_OUTLET] = line_delay(c[wtin::P_LINE_VOLUME_OUTLET], c[wtin::P_LINE_FLOW_OUTLET]);
+        q[wtin::R_BUBBLE_P] = c[wtin::P_AIR_BUBBLE_FREQUENCY] / 60.0;                       // base_sensor.py:490
+        const int flags = (c[wtin::P_FLOW_VELOCITY] < 0.1 ? wtin::F_STAGNANT : 0) | (c[wtin::P_AIR_BUBBLE_FREQUENCY] > 0 ? wtin::F_BUBBLES : 0) |
+                          (c[wtin::P_GROUNDING_QUALITY] < 0.8 ? wtin::F_GROUND : 0) | (c[wtin::P_PIPE_VIBRATION_G] > 0.2 ? wtin::F_VIBRATION : 0);
+        q[wtin::R_FLAGS] = (double)flags;
+        q[wtin::R_GROUND_SCALE] = 2.0 - c[wtin::P_GROUNDING_QUALITY];                        // :496
+        q[wtin::R_VIBRATION] = c[wtin::P_PIPE_VIBRATION_G];
+        q[wtin::R_AMBIENT] = c[wtin::P_AMBIENT_TEMPERATURE];
+    }
+    return rec;
+}
+
+// The records on the device and both lines' cursors back to 0: a changed delay may move a line's target backwards, and
+// a walk from the oldest entry is always right (Line::transport).  The stream is idle; synchronises.
+int install_load(wt_ensemble *h, const double *params, int on)
+{
+    const std::vector<double> rec = install_records(h->N, params);
+    HIP_TRY(hipMemcpyAsync((double *)h->ins.par, rec.data(), sizeof(double) * rec.size(), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemsetAsync(h->sens.ring_cursor, 0, sizeof(int32_t) * 2 * (size_t)h->N, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // the host vector is freed on return
+    h->ins.on = on;
+    return WT_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -1019,6 +1109,10 @@ int wt_ensemble_sensors_enable(wt_ensemble *h, uint64_t seed, int64_t reactor_ba
     // the service program's records, off: no slot enabled, no state (a checkpoint holds them whether or not one is set)
     if (e == hipSuccess) e = hipMemsetAsync((void *)s.svc_par, 0, sizeof(double) * wtsv::PAR_DOUBLES * N, h->stream);
     if (e == hipSuccess) e = hipMemsetAsync(s.svc_st, 0, sizeof(double) * wtsv::ST_DOUBLES * N, h->stream);
+    // the installation records: the suite's own build for every reactor, off (the copy is from pageable memory: the
+    // vector is free once the call returns)
+    const std::vector<double> inst = install_records(h->N, nullptr);
+    if (e == hipSuccess) e = hipMemcpy((double *)h->ins.par, inst.data(), sizeof(double) * inst.size(), hipMemcpyHostToDevice);
     if (e == hipSuccess) {
         wts::SensorInitArgs a;
         a.N = h->N; a.cfg_flow = cfg; a.cfg_cl = cfg + N; a.cfg_temp = cfg + 2 * N;
@@ -1033,6 +1127,7 @@ int wt_ensemble_sensors_enable(wt_ensemble *h, uint64_t seed, int64_t reactor_ba
     if (e != hipSuccess) { release(arrays); return fail(WT_E_HIP, std::string("sensors_enable: ") + hipGetErrorString(e)); }
     s.seed_lo = (uint32_t)(seed & 0xffffffffu); s.seed_hi = (uint32_t)(seed >> 32); s.reactor_base = reactor_base;
     s.svc_on = 0;                                // a freshly enabled suite has no service program
+    h->ins.on = 0;                               // and no installation
     s.on = 1;
     return WT_OK;
 }
@@ -1973,7 +2068,7 @@ const Part k_parts[] = {
     {"SENS", sensor_arrays, 0, [](wt_ensemble *h, Scalars &s) {
          s.insert(s.end(), {{S_I32, &h->sens.on, true}, {S_I32, &h->sens.hist_cap, true}, {S_U32, &h->sens.seed_lo, false},
                             {S_U32, &h->sens.seed_hi, false}, {S_I64, &h->sens.reactor_base, false},
-                            {S_I32, &h->sens.svc_on, false}}); }, nullptr},   // (the service program's arrays are the suite's)
+                            {S_I32, &h->sens.svc_on, false}, {S_I32, &h->ins.on, false}}); }, nullptr},   // (the service program's arrays and the installation records are the suite's)
     {"PLIO", plant_io_arrays, 0, [](wt_ensemble *h, Scalars &s) {
          s.insert(s.end(), {{S_I32, &h->sens.plc_on, true}, {S_I32, &h->tun.on, false}}); }, nullptr},   // (the tune program's arrays are plant I/O's)
     {"RECD", record_arrays, 0, [](wt_ensemble *h, Scalars &s) {
@@ -2131,7 +2226,7 @@ const char *config_error(wt_ensemble *u)
     const auto flag = [](int v) { return v == 0 || v == 1; };
     if (!flag(u->sens.on) || !flag(u->sens.plc_on) || !flag(u->ctl.on) || !flag(u->inj.on) || !flag(u->alm.on) || !flag(u->act.on) ||
         !flag(u->dst.on) || !flag(u->scr.on) || !flag(u->det.on) || !flag(u->trn.on) || !flag(u->trn.pipe.on) || !flag(u->trn.jct.on) || !flag(u->wir.on) ||
-        !flag(u->sens.svc_on) || !flag(u->tun.on) || !flag(u->trd.on) || !flag(u->trd.wrap))
+        !flag(u->sens.svc_on) || !flag(u->ins.on) || !flag(u->tun.on) || !flag(u->trd.on) || !flag(u->trd.wrap))
         return "range";
     if (u->placement != WT_PLACE_IDENTITY && u->placement != WT_PLACE_ADAPTIVE) return "range";
     if (u->sched_mode != WT_SCHED_STREAMS && u->sched_mode != WT_SCHED_QUEUE) return "range";
@@ -2147,6 +2242,7 @@ const char *config_error(wt_ensemble *u)
     if (u->wir.on && (!u->trn.on || !u->sens.plc_on)) return "range";
     if (u->trn.jct.on && !u->trn.on) return "range";
     if (u->sens.svc_on && (!u->sens.on || !wt::prog_in_item(levels_for(u->n)))) return "range";
+    if (u->ins.on && !u->sens.on) return "range";
     if (u->tun.on && (!u->sens.plc_on || !wt::prog_in_item(levels_for(u->n)))) return "range";
     return nullptr;
 }
@@ -2819,6 +2915,46 @@ int wt_ensemble_service_params(wt_ensemble *h, double *params) { return wt_ensem
 int wt_ensemble_service_reset(wt_ensemble *h) { return reset_program(h, WT_PROG_SERVICE); }
 int wt_ensemble_service_clear(wt_ensemble *h) { return stop_program(h, WT_PROG_SERVICE); }
 
+// ---- the installation of the sensor suite: not a program of k_programs (no slots, no state, no zone limit)
+
+int wt_install_check(int64_t n_reactors, const double *params)
+{
+    if (n_reactors < 1) return fail(WT_E_ARG, "n_reactors must be >= 1");
+    if (!params) return fail(WT_E_ARG, "NULL argument");
+    const std::string msg = install_error(n_reactors, params);
+    return msg.empty() ? WT_OK : fail(WT_E_ARG, msg);
+}
+
+int wt_ensemble_install_set(wt_ensemble *h, const double *params)
+{
+    if (!h || !params) return fail(WT_E_ARG, "NULL argument");
+    if (!h->sens.on) return fail(WT_E_STATE, k_service_no_suite);
+    if (int rc = wt_install_check(h->N, params)) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still read the old records
+    return install_load(h, params, 1);
+}
+
+int wt_ensemble_install_get(wt_ensemble *h, double *params)
+{
+    if (!h || !params) return fail(WT_E_ARG, "NULL argument");
+    if (!h->sens.on) return fail(WT_E_STATE, k_service_no_suite);
+    HIP_TRY(hipSetDevice(h->device));
+    std::vector<double> rec((size_t)h->N * wtin::REC_DOUBLES);
+    if (int rc = download(h, {{rec.data(), h->ins.par, sizeof(double) * rec.size()}})) return rc;
+    records_to_blocks(rec.data() + wtin::R_PARAMS, wtin::REC_DOUBLES, 1, wtin::NINS, h->N, params);
+    return WT_OK;
+}
+
+int wt_ensemble_install_clear(wt_ensemble *h)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    if (!h->sens.on) return WT_OK;              // no suite: nothing is set
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still read the records
+    return install_load(h, nullptr, 0);
+}
+
 int wt_tune_check(int64_t n_reactors, const double *params) { return named_check(WT_PROG_TUNE, n_reactors, params); }
 
 int wt_ensemble_tune_set(wt_ensemble *h, const double *params)
@@ -3128,6 +3264,7 @@ int wt_ensemble_info(wt_ensemble *h, int what, int64_t *value)
     case WT_INFO_BOUNDARY_UPLOADS: *value = h->bc_uploads; break;
     case WT_INFO_MARK: *value = h->mark != nullptr; break;
     case WT_INFO_JUNCTION: *value = h->trn.jct.on != 0; break;
+    case WT_INFO_INSTALL: *value = h->ins.on != 0; break;
     default: return fail(WT_E_ARG, "unknown info code");
     }
     return WT_OK;

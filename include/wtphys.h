@@ -287,7 +287,8 @@ enum {
     WT_INFO_MARK = 20,                    /* a mark is set (wt_ensemble_mark) */
     WT_INFO_JUNCTION = 21,                /* a junction program is set */
     WT_INFO_SERVICE = 22,                 /* a sensor service program is set */
-    WT_INFO_TUNE = 23                     /* a tune program is set */
+    WT_INFO_TUNE = 23,                    /* a tune program is set */
+    WT_INFO_INSTALL = 24                  /* an installation is set (wt_ensemble_install_set) */
 };
 int wt_ensemble_info(wt_ensemble *h, int what, int64_t *value);
 
@@ -1047,6 +1048,53 @@ int wt_service_check(int64_t n_reactors, const double *params);
 int wt_ensemble_sensors_service(wt_ensemble *h, int sensor, int action, int ref_mode, const double *ref /* [N] or NULL */,
                                 const double *ref2 /* [N] or NULL */, const uint8_t *mask /* [N] or NULL */);
 int wt_ensemble_sensors_health(wt_ensemble *h, double *out /* [WT_N_SENSORS][WT_NSH][N] */);
+
+/* ---- the installation of the sensor suite: sample lines and instrument installation per reactor ----
+ * create_realistic_sensor_suite (sensors/__init__.py:41-120) builds one fixed installation: two 250 mL sample lines at
+ * 500 mL/min (30 s of dead time; the pH electrode and the RTD of the inlet share one, those of the outlet the other)
+ * and one InstallationQuality for all seven sensors: 0.5 m/s, no bubbles, grounding 0.9, vibration 0.1 g, ambient
+ * 30 degC.  That is what a handle computes while no installation is set.  An installation gives every reactor its
+ * own, [WT_NINS][N]: the two lines' volume [mL] and flow [mL/min], flow_velocity [m/s], air_bubble_frequency
+ * [1/min], grounding_quality, pipe_vibration_g, ambient_temperature [degC].  From the next read on:
+ *   line delay     (volume / 1000) / (flow / 1000 / 60) in fp64, 0 for a flow of 0 (base_sensor.py:167-171); both
+ *                  sensors of the line look for the sample closest to t - delay in the line's 100 entries
+ *   effects        between lag and rate of change (base_sensor.py:464-507), one draw each in this order:
+ *                  flow_velocity < 0.1: normal(2 precision); air_bubble_frequency > 0: uniform() < frequency / 60
+ *                  makes the value NaN and ends the effects; grounding_quality < 0.8: normal(precision (2 -
+ *                  grounding)); pipe_vibration_g > 0.2: normal(vibration precision).  The NaN stays in the sensor's
+ *                  lag, as in the reference: such a sensor reads NaN from then on (and goes on drawing).
+ *   ageing         flow_velocity < 0.1: pH mineral scaling 100 * 0.0001 per day in place of 100 * 0.00001
+ *                  (ph_sensor.py:203-206), amperometric fouling 0.05 per day in place of 0.01 (chlorine_sensor.py:335-338)
+ *   flowmeter      air_bubble_frequency > 0: after its noise draw one more uniform(); below frequency / 60 the reading
+ *                  is 0.0 for this read (flow_sensor.py:150-159)
+ *   RTD            stem error 0.01 (T - ambient_temperature) (temperature_sensor.py:126)
+ * The three thresholds are decided on the doubles as given.  SampleLine.ambient_temp reaches no reading in the
+ * reference (base_sensor.py:611-614 drops the cooled temperature) and has no field.  Needs the sensor suite (WT_E_STATE,
+ * "the sensor suite is not enabled (wt_ensemble_sensors_enable)"), any zone count, not plant I/O.  set replaces the
+ * installation in force, mid-run too: the lines keep their samples and only the delay changes.  get returns the block in
+ * force, the defaults while none is set.  clear goes back to the suite's build (no effect without a suite).  A block
+ * of defaults and no installation give the same bits.  wt_ensemble_sensors_enable starts without one; checkpoints,
+ * copies and marks carry it.  wt_install_check is the check of a block, with no handle and no device.  Refused with
+ * WT_E_ARG, reactor by reactor, the message naming the field and the reactor ("grounding_quality must be in 0..1
+ * (reactor 3)"), at one reactor in this order ("n_reactors must be >= 1" and "NULL argument" before them):
+ *   "<field> must be finite"                           every field
+ *   "<field> must be >= 0"                             the lines' volumes and flows
+ *   "<line>_line_volume_mL and flow give a delay of 91 s or more: the reference's buffer grows beyond 100 entries
+ *    (int(delay) + 10 > 100), the device's ring does not"      (base_sensor.py:174)
+ *   "flow_velocity must be in 0..5 m/s", "air_bubble_frequency must be >= 0", "grounding_quality must be in 0..1",
+ *   "pipe_vibration_g must be >= 0"                    (InstallationQuality.validate, base_sensor.py:138-145)
+ * All calls synchronise. */
+enum {
+    WT_INS_LINE_VOLUME_INLET = 0, WT_INS_LINE_FLOW_INLET = 1, WT_INS_LINE_VOLUME_OUTLET = 2, WT_INS_LINE_FLOW_OUTLET = 3,
+    WT_INS_FLOW_VELOCITY = 4, WT_INS_AIR_BUBBLE_FREQUENCY = 5, WT_INS_GROUNDING_QUALITY = 6, WT_INS_PIPE_VIBRATION_G = 7,
+    WT_INS_AMBIENT_TEMPERATURE = 8,
+    WT_NINS = 9
+};
+int wt_ensemble_install_set(wt_ensemble *h, const double *params /* [WT_NINS][N] */);
+/* the installation in force: host [WT_NINS][N] */
+int wt_ensemble_install_get(wt_ensemble *h, double *params);
+int wt_ensemble_install_clear(wt_ensemble *h);
+int wt_install_check(int64_t n_reactors, const double *params);
 
 /* ---- the tune program: a relay (Astrom-Hagglund) autotuner per PI loop inside fused runs ----
  * The reference's roadmap lists "Control tuning utilities (Ziegler-Nichols, Lambda)"; it has none.  Two tuners per
