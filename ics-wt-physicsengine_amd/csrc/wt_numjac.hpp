@@ -187,13 +187,18 @@ __device__ __forceinline__ void num_jac_species(const Lane &L, const KC &kc, con
 // KTP: pointer to the constant table (kernel-argument segment in the step kernel).
 template <bool ROW, class KTP>
 __device__ __forceinline__ void num_jac(const Lane &L, const RKStore &ks, KTP ktab, const double y[3], const double f[3],
-                                        double fac[3], bool &have_fac, Jac &J, bool &bad, double &badval, bool &t_dense)
+                                        double fac[3], bool &have_fac, Jac &J, bool &bad, double &badval, bool &t_dense,
+                                        const ZoneProps *held = nullptr, bool have_held = false)
 {
     if (!have_fac) { fac[0] = fac[1] = fac[2] = rc::NJ_F0; have_fac = true; }
     FdCols cols;
     ZoneProps b;
     FdBase nb;
-    {
+    // The zone-local properties at y.  A caller that evaluated the RHS at this same y holds them (held, have_held per
+    // lane): the same functions of the same argument, the same bits.  Where every lane that is here holds them, none is
+    // formed; otherwise they are formed for all and the holders keep theirs.
+    const bool all_held = held != nullptr && __ballot(!have_held) == 0ull;
+    if (!all_held) {
         const KT ct = load_kt(ktab());
         const PropT bpt = prop_T(ct, y[STT]);
         b.kT = bpt.kT; b.rho = bpt.rho;
@@ -201,8 +206,11 @@ __device__ __forceinline__ void num_jac(const Lane &L, const RKStore &ks, KTP kt
     {
         const KP cp = load_kp(ktab());
         const RK k = fetch_reactor(ks);
-        const PropPH bpp = prop_pH(cp, k, y[SPH]);
-        b.H = bpp.H; b.iw = bpp.iw; b.phi = bpp.phi; b.bpos = bpp.bpos;
+        if (!all_held) {
+            const PropPH bpp = prop_pH(cp, k, y[SPH]);
+            b.H = bpp.H; b.iw = bpp.iw; b.phi = bpp.phi; b.bpos = bpp.bpos;
+        }
+        if (held != nullptr && (all_held || have_held)) b = *held;
         nb = fd_base<ROW>(L, k, y, b);
         num_jac_species<ROW, SPH>(L, cp, k, y, f, b, nb, fac[SPH], cols, bad, badval);
 #pragma unroll

@@ -56,14 +56,14 @@ struct Flag {
 };
 
 enum Phase : int {
-    PH_OUTER_BEGIN = 0, // start an outer step: next trip evaluates f0 = f(y0)            radau.py:303
+    PH_OUTER_BEGIN = 0, // start an outer step: f0 = f(y0) is evaluated ahead of the first trip  radau.py:303
     PH_INIT_STEP,       // f0 known: first half of select_initial_step (no evaluation needed)  common.py:111-119
     PH_F1,              // next evaluates f(y0 + h0 f0); its epilogue starts the first attempt  common.py:120-122
     PH_STEP_BEGIN,      // _step_impl prologue of every later step (no evaluation needed)   radau.py:399-424
     PH_ATTEMPT,         // (re)start an attempt with the current h_abs                      radau.py:426-448
     PH_NEWTON,          // one simplified-Newton iteration per trip (three evaluations)     radau.py:84-134
     PH_ERR_REFINE,      // second error estimate after a rejection (one evaluation)         radau.py:485-487
-    PH_FNEW,            // step accepted: evaluate f(y_new), bookkeeping                     radau.py:500-539
+    PH_FNEW,            // step accepted and a fresh Jacobian asked for: evaluate f(y_new)   radau.py:500-539
     PH_DONE             // solve finished, failed or raised: wait for the wavefront's other reactors
 };
 
@@ -90,7 +90,8 @@ template <int LV> struct LdsMap {
 // and its own share of the reactor constants (LDS), so neither is live outside it, and inside a section the NS
 // evaluations are independent chains for the scheduler to interleave.
 template <bool ROW, int NS>
-__device__ __forceinline__ void rhs_points(const Lane &L, const RKStore &ks, ArgPtr pa, const double (*y)[3], double (*F)[3], bool *bad)
+__device__ __forceinline__ void rhs_points(const Lane &L, const RKStore &ks, ArgPtr pa, const double (*y)[3], double (*F)[3], bool *bad,
+                                           ZoneProps *keep = nullptr)   // keep: the zone-local properties of point 0, for num_jac
 {
     PropPH pp[NS]; PropT pt[NS];
     {
@@ -119,6 +120,7 @@ __device__ __forceinline__ void rhs_points(const Lane &L, const RKStore &ks, Arg
         for (int s = 0; s < NS; ++s)
             rhs_rows<ROW>(L, k, pp[s].H, pp[s].iw, pp[s].bpos, pt[s].kT * pp[s].phi, pt[s].rho, y[s][SCL], y[s][STT], F[s]);
     }
+    if (keep) { keep->H = pp[0].H; keep->iw = pp[0].iw; keep->phi = pp[0].phi; keep->bpos = pp[0].bpos; keep->kT = pt[0].kT; keep->rho = pt[0].rho; }
 }
 
 // Whether the probe's epilogue (PH_F1) also starts the first attempt, so that the trip that probed the step size goes on
@@ -126,6 +128,30 @@ __device__ __forceinline__ void rhs_points(const Lane &L, const RKStore &ks, Arg
 // instantiation whose register allocation or timing would take the join badly: without it the lane goes through
 // PH_STEP_BEGIN / PH_ATTEMPT and a stage evaluation in the next trip, same results.  No instantiation needs it.
 __host__ __device__ constexpr bool first_attempt_in_probe_trip(int /*LV*/, bool /*ROW*/) { return true; }
+
+// Where a pending f is evaluated, one switch per piece; with a switch off that piece's path is the
+// one the lane took before, same results.
+// A: an outer step ends in the trip that accepts its last internal step.  f(y_new) of that step is not evaluated there:
+// its first user is the next outer step, which evaluates it as its own f(y0) -- if it still needs it (the item may end,
+// the state may be clamped, the boundary reloaded).  Off: the lane spends one more trip in PH_FNEW and carries f over.
+__host__ __device__ constexpr bool outer_step_ends_at_accept(int /*LV*/, bool /*ROW*/) { return true; }
+// B: f(y0) of an outer step that has none carried over is evaluated ahead of its first trip, so that the trip goes on
+// to the probe, the Jacobian, the factorisation and Newton iteration 1.  Off: PH_OUTER_BEGIN takes a trip of its own.
+__host__ __device__ constexpr bool outer_begin_ahead_of_first_trip(int /*LV*/, bool /*ROW*/) { return true; }
+// C: the pending f(y_new) of a non-final accepted step is the fourth point of the stage block of the next Newton trip.
+// Off: it is a single-point evaluation of its own right behind the block.
+__host__ __device__ constexpr bool pending_f_in_stage_block(int /*LV*/, bool /*ROW*/) { return true; }
+// D: the derived state (H+ concentration, density, decay rate) is formed when the item stores its results, from the
+// pre-clamp state of the reactor's last live step; a step that clamps or leaves the temperature range forms it at once.
+// Off: it is formed after every outer step.
+__host__ __device__ constexpr bool derived_once_per_item(int /*LV*/, bool /*ROW*/) { return true; }
+// E (needs B): the zone-local properties that B's evaluation forms at y0 are the base point's of the outer step's first
+// Jacobian, in the same trip: num_jac takes them over.  Ten registers held from the evaluation to the Jacobian, which
+// the n > 32 kernel does not have.  Off: num_jac forms them itself.
+__host__ __device__ constexpr bool base_properties_handed_to_num_jac(int LV, bool /*ROW*/) { return LV <= 5; }
+// F: the accept of an outer step's last internal step leaves the step-size controller and the dense output alone: they
+// would serve a next internal step, and the next outer step is a fresh solver.  Off: every accept updates them.
+__host__ __device__ constexpr bool lean_last_accept(int /*LV*/, bool /*ROW*/) { return true; }
 
 // One work item: the reactors of wavefront-group `group` advanced by `cnt` outer steps, starting with step `step0`
 // of this launch.  Reactors of a wavefront start every outer step together (they wait for the slowest of them), so
@@ -160,6 +186,10 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
     double flow_used = 0;                             // ReactorState.flow_rate: the flows of the last step taken
     uint32_t st = 0;
     bool frozen = !present, f_valid = false, wrote_k = false, raised = false;
+    bool derive_due = false;                          // y0 is the pre-clamp state of a live step whose derived state is not formed yet
+    constexpr bool END_AT_ACCEPT = outer_step_ends_at_accept(LV, ROW), BEGIN_AHEAD = outer_begin_ahead_of_first_trip(LV, ROW),
+                   PEND_IN_BLOCK = pending_f_in_stage_block(LV, ROW), DERIVE_ONCE = derived_once_per_item(LV, ROW),
+                   HAND_BASE = BEGIN_AHEAD && base_properties_handed_to_num_jac(LV, ROW), LEAN_LAST_ACCEPT = lean_last_accept(LV, ROW);
     int steps_done = 0, reads_done = 0, cost_acc = 0;
     SolverCounters last_cnt = {0, 0, 0, 0, 0};
     int diag_trips = 0, diag_newton = 0;              // per item: 32 bits are plenty
@@ -216,9 +246,13 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
                  have_lu{fl, 1u << 5}, rejected{fl, 1u << 6}, keep_h{fl, 1u << 7}, have_norm_old{fl, 1u << 8}, have_rate{fl, 1u << 9},
                  bad{fl, 1u << 10}, failed{fl, 1u << 11}, fv{fl, 1u << 12}, need_jac{fl, 1u << 13},
                  limit_hit{fl, 1u << 16}, pend_f{fl, 1u << 17}, jac_after_fnew{fl, 1u << 18},
-                 j_dense{fl, 1u << 19};               // this lane's Jacobian couples a row to a neighbour's temperature
+                 j_dense{fl, 1u << 19},               // this lane's Jacobian couples a row to a neighbour's temperature
+                 base_held{fl, 1u << 20}, base_bpos{fl, 1u << 21};   // zb_a holds the properties at yc; their beta > 0
             fv = f_valid;
             AReg64 fac_a[3]; fac_a[0].init(); fac_a[1].init(); fac_a[2].init();   // num_jac's factors: touched once per Jacobian
+            // H, iw, phi, kT, rho at y0 from the evaluation ahead of the first trip, for the Jacobian of that trip (HAND_BASE)
+            AReg64 zb_a[5];
+            if constexpr (HAND_BASE) { zb_a[0].init(); zb_a[1].init(); zb_a[2].init(); zb_a[3].init(); zb_a[4].init(); }
             double t = t_out, t_bound = t_out + dt, max_step = fmin(dt, 10.0);
             double h = 0, t_new = 0, h_abs = 0, h_abs_l = 0, min_step = 0;
             // the step-size controller's memory: written when a step is accepted / begun, read when the next one is judged
@@ -255,34 +289,54 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
                 phase = PH_ATTEMPT;
             };
             // step accepted: radau.py:500-539.  scipy evaluates f(y_new) right here; the value is first
-            // needed by the next error estimate, so unless a Jacobian refresh or the end of the outer
-            // step needs it at once, it is evaluated together with the next Newton trip (pend_f).
+            // needed by the next error estimate, so unless a Jacobian refresh needs it at once, it is
+            // evaluated together with the next Newton trip (pend_f) -- or, where the accept ends the outer
+            // step, by the next outer step as its f(y0) (END_AT_ACCEPT).
             auto accept_step = [&]() {
                 const bool recompute_jac = (n_iter > 2) && have_rate && (rate > 1e-3);
-                double fct = predict_factor(h_abs_l, have_old_l, h_abs_old_l_a.get(), error_norm, err_old_l_a.get());
-                fct = fmin(MAX_FACTOR, safety * fct);
-                if (!recompute_jac && fct < 1.2) fct = 1.0; else have_lu = false;
-                h_abs_old_a.set(h_abs);       // sic radau.py:520: the solver-level value
-                err_old_a.set(error_norm);
-                have_old = true;
-                h_abs = h_abs_l * fct;
-                const KZ kz = lit_kz(); const KA ka = lit_ka();
+                const bool more = (t_new - t_bound) < 0;
+                // The accept that ends the outer step prepares no further internal step: the next step size and the dense output
+                // belong to a solver object that the reference discards with the outer step (reactor.py:476).
+                if (!LEAN_LAST_ACCEPT || more) {
+                    double fct = predict_factor(h_abs_l, have_old_l, h_abs_old_l_a.get(), error_norm, err_old_l_a.get());
+                    fct = fmin(MAX_FACTOR, safety * fct);
+                    if (!recompute_jac && fct < 1.2) fct = 1.0; else have_lu = false;
+                    h_abs_old_a.set(h_abs);       // sic radau.py:520: the solver-level value
+                    err_old_a.set(error_norm);
+                    have_old = true;
+                    h_abs = h_abs_l * fct;
+                    const KZ kz = lit_kz(); const KA ka = lit_ka();
 #pragma unroll
-                for (int q = 0; q < 3; ++q) {
-                    const ZRow z = z_of_w(kz, W, q);
-                    y_old_a[q].set(yc[q]);
-                    Qa[q][0].set(z.z0 * ka.P[0] + z.z1 * ka.P[3] + z.z2 * ka.P[6]);  // Q = Z^T P  radau.py:541-543
-                    Qa[q][1].set(z.z0 * ka.P[1] + z.z1 * ka.P[4] + z.z2 * ka.P[7]);
-                    Qa[q][2].set(z.z0 * ka.P[2] + z.z1 * ka.P[5] + z.z2 * ka.P[8]);
-                    yc[q] = yc[q] + z.z2;
+                    for (int q = 0; q < 3; ++q) {
+                        const ZRow z = z_of_w(kz, W, q);
+                        y_old_a[q].set(yc[q]);
+                        Qa[q][0].set(z.z0 * ka.P[0] + z.z1 * ka.P[3] + z.z2 * ka.P[6]);  // Q = Z^T P  radau.py:541-543
+                        Qa[q][1].set(z.z0 * ka.P[1] + z.z1 * ka.P[4] + z.z2 * ka.P[7]);
+                        Qa[q][2].set(z.z0 * ka.P[2] + z.z1 * ka.P[5] + z.z2 * ka.P[8]);
+                    }
+                    sol_t_old_a.set(t); sol_h_a.set(t_new - t); have_sol = true;
                 }
-                sol_t_old_a.set(t); sol_h_a.set(t_new - t); have_sol = true;
+                {
+                    const KZ kz = lit_kz();
+#pragma unroll
+                    for (int q = 0; q < 3; ++q) yc[q] = yc[q] + z_of_w(kz, W, q).z2;   // y_new = y + Z[2]
+                }
                 t = t_new;
                 cnt_s.nsteps++; cnt_s.nfev++;     // f(y_new) counted where scipy calls it
                 pend_f = true; fv = false;
                 current_jac = recompute_jac;
-                const bool more = (t - t_bound) < 0;
-                if (recompute_jac || !more) { jac_after_fnew = recompute_jac; phase = PH_FNEW; }
+                if (recompute_jac || (!END_AT_ACCEPT && !more)) { jac_after_fnew = recompute_jac; phase = PH_FNEW; }
+                else if (!more) {
+                    // the outer step ends here, f(y_new) pending (fv stays false: the next outer step begins with its own
+                    // evaluation).  The reference raises out of f(y_new) when a zone of y_new is outside the temperature
+                    // range, state untouched: prop_T's own test, NaN passing as it does there.
+                    const bool out = (yc[STT] < 0.0) || (yc[STT] > 100.0);
+                    if (WT_RARE(seg_any(L, out))) {
+                        if (out) { badstage = 0; badval = yc[STT]; }
+                        bad |= out; raised = true;
+                    }
+                    phase = PH_DONE;
+                }
                 else phase = PH_STEP_BEGIN;
             };
 
@@ -291,6 +345,32 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
                 // boundary): count it as scipy does and go straight to the initial-step probe
                 cnt_s.nfev++;
                 phase = PH_INIT_STEP;
+            }
+            if constexpr (BEGIN_AHEAD) {
+                // A lane is in PH_OUTER_BEGIN in the first trip of its outer step and in no other, so the evaluation at the top
+                // of that trip stands here, ahead of the loop: f0 = f(y0), and the first trip goes through PH_INIT_STEP to the
+                // probe and on.  A temperature outside the range raises as in a trip of its own (first evaluation, stage 1).
+                if (__ballot(phase == PH_OUTER_BEGIN) != 0ull) {
+                    double fy[1][3]; bool bb[1];
+                    ZoneProps zb;
+                    rhs_points<ROW, 1>(L, ks, pa, &yc, fy, bb, HAND_BASE ? &zb : nullptr);
+                    const bool mine = bb[0] && phase == PH_OUTER_BEGIN;
+                    if (phase == PH_OUTER_BEGIN) {
+                        if constexpr (HAND_BASE) {
+                            zb_a[0].set(zb.H); zb_a[1].set(zb.iw); zb_a[2].set(zb.phi); zb_a[3].set(zb.kT); zb_a[4].set(zb.rho);
+                            base_bpos = zb.bpos; base_held = true;
+                        }
+                        cnt_s.nfev++;
+#pragma unroll
+                        for (int q = 0; q < 3; ++q) f[q] = fy[0][q];
+                        phase = PH_INIT_STEP;
+                    }
+                    if (WT_RARE(__ballot(mine) != 0ull)) {
+                        if (mine) { badstage = 1; badval = yc[STT]; }
+                        bad |= mine;
+                        if (seg_any(L, bad)) { raised = true; phase = PH_DONE; }
+                    }
+                }
             }
 
             WT_STAMP(0);   // item / outer-step set-up
@@ -364,10 +444,11 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
                 // ================= this trip's evaluation points
                 const bool newton = (phase == PH_NEWTON);
                 diag_trips++;
-                const bool eval0 = (phase == PH_OUTER_BEGIN || phase == PH_F1 || phase == PH_ERR_REFINE || phase == PH_FNEW || newton);
+                const bool eval0 = ((!BEGIN_AHEAD && phase == PH_OUTER_BEGIN) || phase == PH_F1 || phase == PH_ERR_REFINE || phase == PH_FNEW || newton);
                 // f(y) of a just-accepted step rides along with the next attempt's first Newton trip
                 const bool eval3 = newton && pend_f;
-                double ye[3][3], Fe[3][3];
+                constexpr int NPT = PEND_IN_BLOCK ? 4 : 3;   // the stage block's points: the three stages, then the pending point
+                double ye[NPT][3], Fe[NPT][3];
 #pragma unroll
                 for (int q = 0; q < 3; ++q) {
                     double p0 = yc[q];                                        // PH_OUTER_BEGIN, PH_FNEW
@@ -393,8 +474,26 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
                     if constexpr (LV < 5) stage_points();
                     // some reactor of the wavefront is in its Newton phase: all three stage points (three independent
                     // chains for the scheduler to interleave); the other lanes' slot-1/2 results are simply not used
-                    bool bb[3];
-                    rhs_points<ROW, 3>(L, ks, pa, ye, Fe, bb);
+                    bool bb[NPT];
+                    bool four = false;
+                    if constexpr (PEND_IN_BLOCK) four = __ballot(eval3) != 0ull;
+                    if (four) {
+                        // some Newton lane has a pending f(y_new): a fourth chain in the same sections, with their constants
+                        if constexpr (PEND_IN_BLOCK) {
+                            WT_COUNT(diag_f3);
+#pragma unroll
+                            for (int q = 0; q < 3; ++q) ye[NPT - 1][q] = yc[q];
+                            rhs_points<ROW, NPT>(L, ks, pa, ye, Fe, bb);
+                            b3 = bb[NPT - 1] && eval3;
+                            if (eval3) {
+                                pend_f = false;   // (counted in nfev when the step was accepted)
+#pragma unroll
+                                for (int q = 0; q < 3; ++q) f[q] = Fe[NPT - 1][q];
+                            }
+                        }
+                    } else {
+                        rhs_points<ROW, 3>(L, ks, pa, ye, Fe, bb);
+                    }
                     b0 = bb[0] && eval0; b1 = bb[1] && newton; b2 = bb[2] && newton;
                     if (eval0 && phase != PH_FNEW) cnt_s.nfev++;
                     if (newton) cnt_s.nfev += 2;
@@ -404,7 +503,7 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
                     b0 = bb[0] && eval0;
                     if (eval0 && phase != PH_FNEW) cnt_s.nfev++;
                 }
-                if (__ballot(eval3) != 0ull) {
+                if (!PEND_IN_BLOCK && __ballot(eval3) != 0ull) {
                     WT_COUNT(diag_f3);
                     double fy[1][3]; bool bb[1];
                     rhs_points<ROW, 1>(L, ks, pa, &yc, fy, bb);
@@ -429,7 +528,7 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
 
                 // ================= the epilogues of the phases that are not Newton's: they may ask for a Jacobian, and the probe's
                 // starts the first attempt, so they come before num_jac, the factorisation and the Newton epilogue of this same trip
-                if (WT_RARE(phase == PH_OUTER_BEGIN)) {   // (rare: f(y0) is usually carried over from the previous outer step)
+                if (!BEGIN_AHEAD && WT_RARE(phase == PH_OUTER_BEGIN)) {   // (with BEGIN_AHEAD no lane is in this phase inside the loop)
 #pragma unroll
                     for (int q = 0; q < 3; ++q) f[q] = Fe[0][q];
                     phase = PH_INIT_STEP;
@@ -489,7 +588,16 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
                     bool jbad = false, hf = have_fac, jd = false; double jval = 0;
                     asm volatile("" ::: "memory");               // a fresh fetch: do not keep the constants live across the epilogue
                     double fac[3] = {fac_a[0].get(), fac_a[1].get(), fac_a[2].get()};
-                    num_jac<ROW>(L, ks, [&]() { return &fresh(pa)->kt; }, yc, f, fac, hf, J, jbad, jval, jd); cnt_s.njev++;
+                    if constexpr (HAND_BASE) {
+                        // the first Jacobian of an outer step that began with its own evaluation is taken at that point, yc = y0
+                        // untouched since: its base properties are the held ones.  Any later Jacobian forms its own.
+                        const ZoneProps zb = {zb_a[0].get(), zb_a[1].get(), zb_a[2].get(), zb_a[3].get(), zb_a[4].get(), (bool)base_bpos};
+                        num_jac<ROW>(L, ks, [&]() { return &fresh(pa)->kt; }, yc, f, fac, hf, J, jbad, jval, jd, &zb, (bool)base_held);
+                        base_held = false;
+                    } else {
+                        num_jac<ROW>(L, ks, [&]() { return &fresh(pa)->kt; }, yc, f, fac, hf, J, jbad, jval, jd);
+                    }
+                    cnt_s.njev++;
                     fac_a[0].set(fac[0]); fac_a[1].set(fac[1]); fac_a[2].set(fac[2]);
                     have_fac = hf;
                     j_dense = jd;
@@ -625,33 +733,53 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
             } else {
                 if (failed) st |= ST_SOLVER_FAILED;    // reactor.py:486-487; state <- last accepted y
                 if (limit_hit) st |= ST_STEP_LIMIT;
+                const double T_before = y0[STT];       // (read on one rare path below)
 #pragma unroll
                 for (int q = 0; q < 3; ++q) y0[q] = yc[q];
                 stepped = true; steps_done++;
                 t_out = t_out + dt;                    // reactor.py:496
                 flow_used = ks.uni[15 * ks.stride];    // reactor.py:497-501
-                // _update_derived_state reactor.py:511-524 (before the clamp)
-                double dHv; PropT pt;
-                {
-                    ArgPtr a2 = fresh(pa);
-                    const KP cp = load_kp(&a2->kt); const KT ct = load_kt(&a2->kt);
-                    dHv = exp10_k(cp, -y0[SPH]); pt = prop_T(ct, y0[STT]);
+                // The derived state is stored when the item ends and read by nothing before, so an ordinary step only notes
+                // that it is due: the item's end forms it from y0, the pre-clamp state of the last live step.  A step that
+                // leaves the temperature range or clamps takes the path below, which forms it at once.
+                bool ordinary = false;
+                if constexpr (DERIVE_ONCE) {
+                    const bool odd = (y0[STT] < 0.0) || (y0[STT] > 100.0)        // prop_T's own test (T_RANGE_POST, CLAMP_T)
+                                  || (y0[SPH] < 0) || (y0[SPH] > 14) || (y0[SCL] < 0);
+                    ordinary = !WT_RARE(seg_any(L, odd));
                 }
-                dH = dHv;
-                dR = pt.rho;
-                bool clamped = false;
-                if (WT_RARE(seg_any(L, pt.bad))) {
-                    st |= ST_T_RANGE_POST; frozen = true;
-                    const unsigned long long m = __ballot(pt.bad) & L.segmask;
-                    badval = __shfl(y0[STT], (int)__builtin_ctzll(m), 64);
+                if (ordinary) {
+                    derive_due = true;
+                    f_valid = fv && !failed;
                 } else {
-                    dK = pt.kT; wrote_k = true;
-                    // _enforce_physical_bounds reactor.py:526-541
-                    if (WT_RARE(seg_any(L, y0[SPH] < 0 || y0[SPH] > 14))) { st |= ST_CLAMP_PH; y0[SPH] = fmin(fmax(y0[SPH], 0.0), 14.0); clamped = true; }
-                    if (WT_RARE(seg_any(L, y0[SCL] < 0))) { st |= ST_CLAMP_CL; y0[SCL] = fmax(y0[SCL], 0.0); clamped = true; }
-                    if (WT_RARE(seg_any(L, y0[STT] < 0 || y0[STT] > 100))) { st |= ST_CLAMP_T; y0[STT] = fmin(fmax(y0[STT], 0.0), 100.0); clamped = true; }
-                    // f(y) of the last accepted point is f0 of the next outer step when nothing touched y
-                    f_valid = fv && !clamped && !failed;
+                    // _update_derived_state reactor.py:511-524 (before the clamp)
+                    double dHv; PropT pt;
+                    if (DERIVE_ONCE && derive_due) {
+                        // the step before this one was ordinary: should this one leave the range, its decay rate is the one that stays
+                        dK = prop_T(load_kt(&fresh(pa)->kt), T_before).kT; wrote_k = true;
+                        derive_due = false;
+                    }
+                    {
+                        ArgPtr a2 = fresh(pa);
+                        const KP cp = load_kp(&a2->kt); const KT ct = load_kt(&a2->kt);
+                        dHv = exp10_k(cp, -y0[SPH]); pt = prop_T(ct, y0[STT]);
+                    }
+                    dH = dHv;
+                    dR = pt.rho;
+                    bool clamped = false;
+                    if (WT_RARE(seg_any(L, pt.bad))) {
+                        st |= ST_T_RANGE_POST; frozen = true;
+                        const unsigned long long m = __ballot(pt.bad) & L.segmask;
+                        badval = __shfl(y0[STT], (int)__builtin_ctzll(m), 64);
+                    } else {
+                        dK = pt.kT; wrote_k = true;
+                        // _enforce_physical_bounds reactor.py:526-541
+                        if (WT_RARE(seg_any(L, y0[SPH] < 0 || y0[SPH] > 14))) { st |= ST_CLAMP_PH; y0[SPH] = fmin(fmax(y0[SPH], 0.0), 14.0); clamped = true; }
+                        if (WT_RARE(seg_any(L, y0[SCL] < 0))) { st |= ST_CLAMP_CL; y0[SCL] = fmax(y0[SCL], 0.0); clamped = true; }
+                        if (WT_RARE(seg_any(L, y0[STT] < 0 || y0[STT] > 100))) { st |= ST_CLAMP_T; y0[STT] = fmin(fmax(y0[STT], 0.0), 100.0); clamped = true; }
+                        // f(y) of the last accepted point is f0 of the next outer step when nothing touched y
+                        f_valid = fv && !clamped && !failed;
+                    }
                 }
             }
           }
@@ -844,6 +972,16 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
     }
 
     // ================= the item's results
+    if constexpr (DERIVE_ONCE) {
+        // _update_derived_state reactor.py:511-524 of the last live step, whose pre-clamp state y0 still is (a reactor that
+        // froze afterwards left y0 alone, a step that clamped formed its own)
+        if (derive_due) {
+            ArgPtr a2 = fresh(pa);
+            const KP cp = load_kp(&a2->kt); const KT ct = load_kt(&a2->kt);
+            const PropT pt = prop_T(ct, y0[STT]);
+            dH = exp10_k(cp, -y0[SPH]); dR = pt.rho; dK = pt.kT; wrote_k = true;
+        }
+    }
     ArgPtr c = fresh(pa);
     if (present) {
         if (steps_done > 0) {
