@@ -47,7 +47,7 @@ __device__ __forceinline__ FdBase fd_base(const Lane &L, const RK &k, const doub
 // restricted to the rows that can change; rows that cannot depend on a column are structural zeros there too.
 // out.D[q][r] is the change of this lane's row q when the zone at offset r-1 was perturbed.
 // colmask (retry pass, common.py:343-361): only the flagged columns are perturbed.
-template <bool ROW, int SP, class KC>
+template <bool ROW, int SP, bool BAR, class KC>
 __device__ __forceinline__ void fd_species_pass(const Lane &L, const KC &kc, const RK &k, const double y[3], const double f[3],
                                                 const ZoneProps &b, const FdBase &n, double hcol, bool colmask, bool all_cols,
                                                 FdCols &out, bool &bad, double &badval)
@@ -60,7 +60,7 @@ __device__ __forceinline__ void fd_species_pass(const Lane &L, const KC &kc, con
     auto put = [&](int q, int r, double fn) { out.D[q][r] = fn - f[q]; out.S[q][r] = fmax(fabs(f[q]), fabs(fn)); };
     const double kphi = b.kT * b.phi;
     if constexpr (SP == SPH) {
-        PropPH p = prop_pH(kc, k, ypert);
+        PropPH p = prop_pH<BAR>(kc, k, ypert);
         if (!all_cols && !colmask) { p.H = b.H; p.iw = b.iw; p.phi = b.phi; }        // this column is not part of the retry
         const double Hx_lo = keep_m(L.m_lo[0], from_lo<ROW, 1>(L, p.H)), Hx_hi = keep_m(L.m_hi[0], from_hi<ROW, 1>(L, p.H));
         put(SPH, 1, row_pH(k, mix3(n.k_lo, n.k_hi, n.kd, n.H_lo, n.H_hi, p.H), p.H, p.iw));
@@ -76,7 +76,7 @@ __device__ __forceinline__ void fd_species_pass(const Lane &L, const KC &kc, con
         put(SCL, 2, row_Cl(k, mix3(n.k_lo, n.k_hi, n.kd, n.C_lo, Cx_hi, y[SCL]), y[SCL], kphi));
     }
     if constexpr (SP == STT) {
-        PropT p = prop_T(kc, ypert);
+        PropT p = prop_T<BAR>(kc, ypert);
         if (colmask && p.bad && !bad) { bad = true; badval = ypert; }   // the reference raises on this perturbed column
         double tx = ypert;
         if (!all_cols && !colmask) { p.kT = b.kT; p.rho = b.rho; tx = y[STT]; }
@@ -140,7 +140,7 @@ __device__ __forceinline__ double fd_step(double y, double fac, double ysc)
 // One species' columns: perturb, reduce, optional retry, factor update.  Leaves
 // the finished difference quotients of this species' columns in `cols.D`
 // (already divided by the column's h).
-template <bool ROW, int SP, class KC>
+template <bool ROW, int SP, bool BAR, class KC>
 __device__ __forceinline__ void num_jac_species(const Lane &L, const KC &kc, const RK &k, const double y[3], const double f[3],
                                                 const ZoneProps &b, const FdBase &nb, double &fac, FdCols &cols, bool &bad, double &badval)
 {
@@ -148,7 +148,7 @@ __device__ __forceinline__ void num_jac_species(const Lane &L, const KC &kc, con
     const double ysc = fs * fmax(ATOL, fabs(y[SP]));
     double h = fd_step(y[SP], fac, ysc);
     while (WT_RARE(h == 0)) { fac *= 10; h = fd_step(y[SP], fac, ysc); }    // common.py:327-330
-    fd_species_pass<ROW, SP>(L, kc, k, y, f, b, nb, h, true, true, cols, bad, badval);
+    fd_species_pass<ROW, SP, BAR>(L, kc, k, y, f, b, nb, h, true, true, cols, bad, badval);
     double maxd, scl;
     fd_col_reduce<ROW, SP>(L, cols, maxd, scl);
     const bool small = maxd < rc::NJ_REJECT * scl;                  // common.py:341
@@ -156,7 +156,7 @@ __device__ __forceinline__ void num_jac_species(const Lane &L, const KC &kc, con
         const double nf = 10 * fac;
         const double hn = fd_step(y[SP], nf, ysc);
         FdCols c2;
-        fd_species_pass<ROW, SP>(L, kc, k, y, f, b, nb, hn, small, false, c2, bad, badval);
+        fd_species_pass<ROW, SP, BAR>(L, kc, k, y, f, b, nb, hn, small, false, c2, bad, badval);
         double md2, sc2;
         fd_col_reduce<ROW, SP>(L, c2, md2, sc2);
         const bool upd = small && (maxd * sc2 < md2 * scl);         // common.py:354
@@ -185,7 +185,7 @@ __device__ __forceinline__ void num_jac_species(const Lane &L, const KC &kc, con
 
 // The three species' passes are sections like those of rhs_points: each fetches the constants it works with.
 // KTP: pointer to the constant table (kernel-argument segment in the step kernel).
-template <bool ROW, class KTP>
+template <bool ROW, bool BAR = false, class KTP>   // BAR: see row_fence (wt_rhs.hpp)
 __device__ __forceinline__ void num_jac(const Lane &L, const RKStore &ks, KTP ktab, const double y[3], const double f[3],
                                         double fac[3], bool &have_fac, Jac &J, bool &bad, double &badval, bool &t_dense,
                                         const ZoneProps *held = nullptr, bool have_held = false)
@@ -200,33 +200,33 @@ __device__ __forceinline__ void num_jac(const Lane &L, const RKStore &ks, KTP kt
     const bool all_held = held != nullptr && __ballot(!have_held) == 0ull;
     if (!all_held) {
         const KT ct = load_kt(ktab());
-        const PropT bpt = prop_T(ct, y[STT]);
+        const PropT bpt = prop_T<BAR>(ct, y[STT]);
         b.kT = bpt.kT; b.rho = bpt.rho;
     }
     {
         const KP cp = load_kp(ktab());
         const RK k = fetch_reactor(ks);
         if (!all_held) {
-            const PropPH bpp = prop_pH(cp, k, y[SPH]);
+            const PropPH bpp = prop_pH<BAR>(cp, k, y[SPH]);
             b.H = bpp.H; b.iw = bpp.iw; b.phi = bpp.phi; b.bpos = bpp.bpos;
         }
         if (held != nullptr && (all_held || have_held)) b = *held;
         nb = fd_base<ROW>(L, k, y, b);
-        num_jac_species<ROW, SPH>(L, cp, k, y, f, b, nb, fac[SPH], cols, bad, badval);
+        num_jac_species<ROW, SPH, BAR>(L, cp, k, y, f, b, nb, fac[SPH], cols, bad, badval);
 #pragma unroll
         for (int r = 0; r < 3; ++r) J.pp[r] = cols.D[SPH][r];
         J.cp = cols.D[SCL][1];
     }
     {
         const RK k = fetch_reactor(ks);
-        num_jac_species<ROW, SCL>(L, 0, k, y, f, b, nb, fac[SCL], cols, bad, badval);
+        num_jac_species<ROW, SCL, BAR>(L, 0, k, y, f, b, nb, fac[SCL], cols, bad, badval);
 #pragma unroll
         for (int r = 0; r < 3; ++r) J.cc[r] = cols.D[SCL][r];
     }
     {
         const KT ct = load_kt(ktab());
         const RK k = fetch_reactor(ks);
-        num_jac_species<ROW, STT>(L, ct, k, y, f, b, nb, fac[STT], cols, bad, badval);
+        num_jac_species<ROW, STT, BAR>(L, ct, k, y, f, b, nb, fac[STT], cols, bad, badval);
 #pragma unroll
         for (int r = 0; r < 3; ++r) { J.tt[r] = cols.D[STT][r]; J.pt[r] = cols.D[SPH][r]; J.ct[r] = cols.D[SCL][r]; }
         t_dense = jac_t_dense(J) || (ct.dense_bias != 0.0);

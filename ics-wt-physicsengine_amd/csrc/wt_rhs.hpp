@@ -150,51 +150,58 @@ struct PropT { double kT, rho; bool bad; };
 #define WT_EACH _Pragma("unroll") for (int s = 0; s < NS; ++s)
 // The compiler, short of registers, pulls each point's chain together again; an empty asm that "uses and redefines"
 // the step's results makes every step complete for all points before the next one starts (NS = 1: nothing to do).
-template <int NS> __device__ __forceinline__ void row_fence(double (&v)[NS])
+// BAR: the fence of a single-point evaluation is a scheduling barrier without operands.  The asm form takes the step's
+// results as operands, and the hazard recognizer then puts an `s_nop 0` in front of it whenever the instruction before
+// defines one of them: in a single-point evaluation that is after every step of the exponential's Horner chain.  One
+// point has nothing to interleave and needs the fence only to keep its sections apart, which the barrier does too.
+// (For two and more points the barrier lets the compiler pull the chains together again and spills SGPRs inside the
+// trip loop: they always keep the asm form.)  The caller chooses: single_point_fence_is_barrier in wt_step.hpp.
+template <bool BAR, int NS> __device__ __forceinline__ void row_fence(double (&v)[NS])
 {
     // (one point: nothing to interleave, but the fence keeps the compiler from merging this section with the next)
-    if constexpr (NS == 1) asm volatile("" : "+v"(v[0]));
+    if constexpr (BAR && NS == 1) __builtin_amdgcn_sched_barrier(0);
+    else if constexpr (NS == 1) asm volatile("" : "+v"(v[0]));
     if constexpr (NS == 2) asm volatile("" : "+v"(v[0]), "+v"(v[1]));
     if constexpr (NS == 3) asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]));
     if constexpr (NS == 4) asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]));
 }
-template <int NS> __device__ __forceinline__ void rcp_n(const double (&x)[NS], double (&r)[NS])
+template <int NS, bool BAR = false> __device__ __forceinline__ void rcp_n(const double (&x)[NS], double (&r)[NS])
 {
     double e[NS];
-    WT_EACH r[s] = __builtin_amdgcn_rcp(x[s]); row_fence(r);
-    WT_EACH e[s] = __builtin_fma(-x[s], r[s], 1.0); row_fence(e);
-    WT_EACH r[s] = __builtin_fma(r[s], e[s], r[s]); row_fence(r);
-    WT_EACH e[s] = __builtin_fma(-x[s], r[s], 1.0); row_fence(e);
-    WT_EACH r[s] = __builtin_fma(r[s], e[s], r[s]); row_fence(r);
+    WT_EACH r[s] = __builtin_amdgcn_rcp(x[s]); row_fence<BAR>(r);
+    WT_EACH e[s] = __builtin_fma(-x[s], r[s], 1.0); row_fence<BAR>(e);
+    WT_EACH r[s] = __builtin_fma(r[s], e[s], r[s]); row_fence<BAR>(r);
+    WT_EACH e[s] = __builtin_fma(-x[s], r[s], 1.0); row_fence<BAR>(e);
+    WT_EACH r[s] = __builtin_fma(r[s], e[s], r[s]); row_fence<BAR>(r);
 }
-template <int NS> __device__ __forceinline__ void exp_tail_n(const double c[10], const double (&t)[NS], const double (&dn)[NS], double (&z)[NS])
+template <int NS, bool BAR = false> __device__ __forceinline__ void exp_tail_n(const double c[10], const double (&t)[NS], const double (&dn)[NS], double (&z)[NS])
 {
     double p[NS];
     WT_EACH p[s] = c[0];
 #pragma unroll
-    for (int i = 1; i < 10; ++i) { WT_EACH p[s] = __builtin_fma(t[s], p[s], c[i]); row_fence(p); }
-    WT_EACH p[s] = __builtin_fma(t[s], p[s], 1.0); row_fence(p);
-    WT_EACH p[s] = __builtin_fma(t[s], p[s], 1.0); row_fence(p);
-    WT_EACH z[s] = __builtin_amdgcn_ldexp(p[s], (int)dn[s]); row_fence(z);
+    for (int i = 1; i < 10; ++i) { WT_EACH p[s] = __builtin_fma(t[s], p[s], c[i]); row_fence<BAR>(p); }
+    WT_EACH p[s] = __builtin_fma(t[s], p[s], 1.0); row_fence<BAR>(p);
+    WT_EACH p[s] = __builtin_fma(t[s], p[s], 1.0); row_fence<BAR>(p);
+    WT_EACH z[s] = __builtin_amdgcn_ldexp(p[s], (int)dn[s]); row_fence<BAR>(z);
 }
-template <int NS> __device__ __forceinline__ void prop_pH_n(const KP &c, const RK &k, const double (&pH)[NS], PropPH (&p)[NS])
+template <int NS, bool BAR = false> __device__ __forceinline__ void prop_pH_n(const KP &c, const RK &k, const double (&pH)[NS], PropPH (&p)[NS])
 {
 #pragma clang fp contract(off)
     double x[NS], dn[NS], u[NS], t[NS], H[NS];
     WT_EACH x[s] = -pH[s];
-    WT_EACH dn[s] = __builtin_rint(x[s] * c.log2_10); row_fence(dn);
-    WT_EACH u[s] = __builtin_fma(-dn[s], c.lg2_hi, x[s]); row_fence(u);
-    WT_EACH u[s] = __builtin_fma(-dn[s], c.lg2_lo, u[s]); row_fence(u);
-    WT_EACH t[s] = u[s] * c.ln10_lo; row_fence(t);
-    WT_EACH t[s] = __builtin_fma(u[s], c.ln10_hi, t[s]); row_fence(t);
-    exp_tail_n<NS>(c.c, t, dn, H);
+    WT_EACH dn[s] = __builtin_rint(x[s] * c.log2_10); row_fence<BAR>(dn);
+    WT_EACH u[s] = __builtin_fma(-dn[s], c.lg2_hi, x[s]); row_fence<BAR>(u);
+    WT_EACH u[s] = __builtin_fma(-dn[s], c.lg2_lo, u[s]); row_fence<BAR>(u);
+    WT_EACH t[s] = u[s] * c.ln10_lo; row_fence<BAR>(t);
+    WT_EACH t[s] = __builtin_fma(u[s], c.ln10_hi, t[s]); row_fence<BAR>(t);
+    exp_tail_n<NS, BAR>(c.c, t, dn, H);
     WT_EACH H[s] = (x[s] > c.t_hi) ? __builtin_inf() : H[s];
     WT_EACH H[s] = (x[s] < c.t_lo) ? 0.0 : H[s];
     double iH[NS], H2[NS], D[NS], iD[NS], HK[NS], iHK[NS];
     WT_EACH H2[s] = H[s] * H[s];
     WT_EACH D[s] = __builtin_fma(k.Ka1, H[s], H2[s]) + k.Ka1Ka2;
     WT_EACH HK[s] = H[s] + k.KaH;
-    rcp_n<NS>(H, iH); rcp_n<NS>(D, iD); rcp_n<NS>(HK, iHK);
+    rcp_n<NS, BAR>(H, iH); rcp_n<NS, BAR>(D, iD); rcp_n<NS, BAR>(HK, iHK);
     double bw[NS], a0[NS], a1[NS], a2[NS], mix[NS], beta[NS], bl[NS], ib[NS];
     WT_EACH bw[s] = c.c2303 * __builtin_fma(k.Kw, iH[s], H[s]);
     WT_EACH a0[s] = H2[s] * iD[s];
@@ -203,7 +210,7 @@ template <int NS> __device__ __forceinline__ void prop_pH_n(const KP &c, const R
     WT_EACH mix[s] = __builtin_fma(a0[s], a2[s], __builtin_fma(4 * a1[s], a2[s], a0[s] * a1[s]));
     WT_EACH beta[s] = __builtin_fma(k.cbeta, mix[s], bw[s]);
     WT_EACH bl[s] = beta[s] * c.ln10;
-    rcp_n<NS>(bl, ib);
+    rcp_n<NS, BAR>(bl, ib);
     WT_EACH {
         p[s].bpos = beta[s] > 0;                    // reactor.py:358,367,375 guards: no pH change unless beta > 0
         p[s].iw = p[s].bpos ? ib[s] : 0.0;
@@ -211,17 +218,17 @@ template <int NS> __device__ __forceinline__ void prop_pH_n(const KP &c, const R
         p[s].H = H[s];
     }
 }
-template <int NS> __device__ __forceinline__ void prop_T_n(const KT &c, const double (&T)[NS], PropT (&p)[NS])
+template <int NS, bool BAR = false> __device__ __forceinline__ void prop_T_n(const KT &c, const double (&T)[NS], PropT (&p)[NS])
 {
 #pragma clang fp contract(off)
     double tk[NS], itk[NS], ex[NS], dn[NS], t[NS], z[NS];
     WT_EACH tk[s] = T[s] + c.c27315;
-    rcp_n<NS>(tk, itk);
+    rcp_n<NS, BAR>(tk, itk);
     WT_EACH ex[s] = c.k_arr * (itk[s] - c.inv_tref);
-    WT_EACH dn[s] = __builtin_rint(ex[s] * c.log2e); row_fence(dn);
-    WT_EACH t[s] = __builtin_fma(-dn[s], c.ln2_hi, ex[s]); row_fence(t);
-    WT_EACH t[s] = __builtin_fma(-dn[s], c.ln2_lo, t[s]); row_fence(t);
-    exp_tail_n<NS>(c.c, t, dn, z);
+    WT_EACH dn[s] = __builtin_rint(ex[s] * c.log2e); row_fence<BAR>(dn);
+    WT_EACH t[s] = __builtin_fma(-dn[s], c.ln2_hi, ex[s]); row_fence<BAR>(t);
+    WT_EACH t[s] = __builtin_fma(-dn[s], c.ln2_lo, t[s]); row_fence<BAR>(t);
+    exp_tail_n<NS, BAR>(c.c, t, dn, z);
     WT_EACH z[s] = (ex[s] > c.e_hi) ? __builtin_inf() : z[s];
     WT_EACH z[s] = (ex[s] < c.e_lo) ? 0.0 : z[s];
     WT_EACH {
@@ -235,20 +242,20 @@ template <int NS> __device__ __forceinline__ void prop_T_n(const KT &c, const do
 }
 
 // H = 10^-pH, buffering capacity beta (chemistry.py:400-437), HOCl/OCl- decay factor (chemistry.py:483-523).
-__device__ __forceinline__ PropPH prop_pH(const KP &c, const RK &k, double pH)
+template <bool BAR = false> __device__ __forceinline__ PropPH prop_pH(const KP &c, const RK &k, double pH)
 {
     const double x[1] = {pH}; PropPH p[1];
-    prop_pH_n<1>(c, k, x, p);
+    prop_pH_n<1, BAR>(c, k, x, p);
     return p[0];
 }
 
 // Arrhenius decay rate (thermodynamics.py:160-193) with its [0,100] C check
 // (:146-157) and water density (spatial.py:177-189).  The density feeds the stratification switch, so it
 // is formed with the reference's roundings: products and sums separately, never fused.
-__device__ __forceinline__ PropT prop_T(const KT &c, double T)
+template <bool BAR = false> __device__ __forceinline__ PropT prop_T(const KT &c, double T)
 {
     const double x[1] = {T}; PropT p[1];
-    prop_T_n<1>(c, x, p);
+    prop_T_n<1, BAR>(c, x, p);
     return p[0];
 }
 

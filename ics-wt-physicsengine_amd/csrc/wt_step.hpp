@@ -17,13 +17,17 @@
 namespace wt {
 
 // ---------------------------------------------------------------- helpers
-template <bool ROW, int LV = 6>
+template <bool ROW, int LV = 6, int PLAIN = 1>
 __device__ __forceinline__ double rms3(const Lane &L, const double x[3], const double sc[3])
 {
     // common.py:63-65 norm(x / scale) over the 3n components of one reactor
-    double s = 0.0;
+    // Which squares fuse into the sum is spelled out: left to the compiler it differs from one inlined copy to the next,
+    // and moves when the code around a copy does.  v[PLAIN]^2 is the plain product; the probe's d2 has always had PLAIN = 0.
+#pragma clang fp contract(off)
+    double v[3];
 #pragma unroll
-    for (int q = 0; q < 3; ++q) { const double v = x[q] * rcp(sc[q]); s += v * v; }
+    for (int q = 0; q < 3; ++q) v[q] = x[q] * rcp(sc[q]);
+    const double s = __builtin_fma(v[2], v[2], __builtin_fma(v[1 - PLAIN], v[1 - PLAIN], v[PLAIN] * v[PLAIN]));
     return sqrt_k(div_by(seg_sum<ROW, LV>(L, s), L.d3n));
 }
 
@@ -43,6 +47,31 @@ __device__ __forceinline__ double predict_factor(double h_abs, bool have_old, do
     return fmin(1.0, mult) * root4(ie);
 }
 
+// The error estimate and the dense output of an accept with their roundings spelled out, as the listing of the literal
+// forms has them (loaded_constants_in_estimate_and_accept): which product of a sum stays plain, which are fused, and
+// that the first row of Q = Z^T P adds three rounded products.
+__device__ __forceinline__ ZRow z_of_w_spelled(const KZ &kz, const double (&W)[3][3], int q)
+{
+#pragma clang fp contract(off)
+    return {__builtin_fma(kz.T02, W[2][q], __builtin_fma(kz.T00, W[0][q], kz.T01 * W[1][q])),
+            __builtin_fma(kz.T12, W[2][q], __builtin_fma(kz.T10, W[0][q], kz.T11 * W[1][q])),
+            W[0][q] + W[1][q]};
+}
+__device__ __forceinline__ void estimate_spelled(const KZ &kz, const KE &ke, const ZRow &z, double ih, double fq, double ycq, double &err, double &esc)
+{
+#pragma clang fp contract(off)
+    const double ZE = __builtin_fma(ke.E2, z.z2, __builtin_fma(ke.E1, z.z1, ke.E0 * z.z0));
+    err = __builtin_fma(ZE, ih, fq);
+    esc = __builtin_fma(fmax(fabs(ycq), fabs(ycq + z.z2)), kz.rtol, kz.atol);
+}
+__device__ __forceinline__ void dense_row_spelled(const KA &ka, const ZRow &z, double (&Q)[3])
+{
+#pragma clang fp contract(off)
+    Q[0] = (z.z0 * ka.P[0] + z.z1 * ka.P[3]) + z.z2 * ka.P[6];
+    Q[1] = __builtin_fma(ka.P[7], z.z2, __builtin_fma(ka.P[4], z.z1, ka.P[1] * z.z0));
+    Q[2] = __builtin_fma(ka.P[8], z.z2, __builtin_fma(ka.P[2], z.z0, ka.P[5] * z.z1));
+}
+
 // ---------------------------------------------------------------- the solver state machine
 // The per-reactor yes/no state of the solver lives in the bits of ONE VGPR (`fl` in step_kernel).  As separate
 // `bool`s every one of them is a 64-bit lane mask in an SGPR pair for the whole loop -- two dozen of them exhaust
@@ -55,6 +84,10 @@ struct Flag {
     __device__ __forceinline__ Flag &operator|=(bool v) { w = v ? (w | m) : w; return *this; }
 };
 
+// The first three phases are the fresh solver's preamble.  With solver_preamble_ahead_of_loop a lane passes through them
+// ahead of the trip loop, once per outer step, and enters the loop in PH_NEWTON with its stage values preset (flag
+// `preset`): inside the loop a lane is then in one of the phases from PH_STEP_BEGIN on, and only PH_NEWTON, PH_ERR_REFINE
+// and PH_FNEW evaluate anything -- the first in the stage block, the other two at the loop's single-point site.
 enum Phase : int {
     PH_OUTER_BEGIN = 0, // start an outer step: f0 = f(y0) is evaluated ahead of the first trip  radau.py:303
     PH_INIT_STEP,       // f0 known: first half of select_initial_step (no evaluation needed)  common.py:111-119
@@ -89,7 +122,7 @@ template <int LV> struct LdsMap {
 // of all points, then the rows.  Each section fetches its own fp64 constants (scalar loads from the argument block)
 // and its own share of the reactor constants (LDS), so neither is live outside it, and inside a section the NS
 // evaluations are independent chains for the scheduler to interleave.
-template <bool ROW, int NS>
+template <bool ROW, int NS, bool BAR = false>   // BAR: see row_fence
 __device__ __forceinline__ void rhs_points(const Lane &L, const RKStore &ks, ArgPtr pa, const double (*y)[3], double (*F)[3], bool *bad,
                                            ZoneProps *keep = nullptr)   // keep: the zone-local properties of point 0, for num_jac
 {
@@ -101,7 +134,7 @@ __device__ __forceinline__ void rhs_points(const Lane &L, const RKStore &ks, Arg
         double x[NS];
 #pragma unroll
         for (int s = 0; s < NS; ++s) x[s] = y[s][SPH];
-        prop_pH_n<NS>(c, k, x, pp);
+        prop_pH_n<NS, BAR>(c, k, x, pp);
     }
     __builtin_amdgcn_sched_barrier(0);   // the next section's constants are fetched when this one is through (SGPR budget)
     {
@@ -110,7 +143,7 @@ __device__ __forceinline__ void rhs_points(const Lane &L, const RKStore &ks, Arg
         double x[NS];
 #pragma unroll
         for (int s = 0; s < NS; ++s) x[s] = y[s][STT];
-        prop_T_n<NS>(c, x, pt);
+        prop_T_n<NS, BAR>(c, x, pt);
 #pragma unroll
         for (int s = 0; s < NS; ++s) bad[s] = pt[s].bad;
     }
@@ -128,6 +161,14 @@ __device__ __forceinline__ void rhs_points(const Lane &L, const RKStore &ks, Arg
 // instantiation whose register allocation or timing would take the join badly: without it the lane goes through
 // PH_STEP_BEGIN / PH_ATTEMPT and a stage evaluation in the next trip, same results.  No instantiation needs it.
 __host__ __device__ constexpr bool first_attempt_in_probe_trip(int /*LV*/, bool /*ROW*/) { return true; }
+// Whether the fresh solver's preamble -- the first half of select_initial_step, the probe evaluation f(y0 + h0 f0) and
+// the probe's epilogue with its first-attempt set-up -- runs once per outer step ahead of the trip loop, right behind
+// f(y0) (needs outer_begin_ahead_of_first_trip and first_attempt_in_probe_trip).  The lanes then enter the loop in
+// PH_NEWTON with their stage values preset, every trip of the loop is a Newton trip or one of the two rare single-point
+// phases, and the loop carries neither the preamble's phase tests nor the per-phase selects of its first evaluation
+// point.  Off: the first trip goes through PH_INIT_STEP and PH_F1 inside the loop, same results.  (The n > 32 kernel
+// has its 60 B of scratch with it, and 68 B without it or without the single-point fence of wt_rhs.hpp.)
+__host__ __device__ constexpr bool solver_preamble_ahead_of_loop(int /*LV*/, bool /*ROW*/) { return true; }
 
 // Where a pending f is evaluated, one switch per piece; with a switch off that piece's path is the
 // one the lane took before, same results.
@@ -152,6 +193,17 @@ __host__ __device__ constexpr bool base_properties_handed_to_num_jac(int LV, boo
 // F: the accept of an outer step's last internal step leaves the step-size controller and the dense output alone: they
 // would serve a next internal step, and the next outer step is a fresh solver.  Off: every accept updates them.
 __host__ __device__ constexpr bool lean_last_accept(int /*LV*/, bool /*ROW*/) { return true; }
+
+// Whether the fences of the item's single-point evaluations (f(y0), the probe, the rare phases' points, num_jac, the
+// post-step properties) are scheduling barriers without operands (row_fence in wt_rhs.hpp), which spares the hazard
+// `s_nop` after every step of their chains.  At n = 8 it measures 0.8 % slower on top of the preamble piece, so the
+// kernels for n <= 16 keep the asm form.  The n > 32 kernel has its 60 B of scratch with the barrier in the two n > 16
+// kernels, and 64 to 68 B with it in that kernel alone or in none.
+__host__ __device__ constexpr bool single_point_fence_is_barrier(int LV, bool /*ROW*/) { return LV >= 5; }
+
+// Whether the error estimate and the accept take their Radau constants from the argument block (one scalar load per
+// section, as the other sections do) with their roundings spelled out, and not as fp64 literals.
+__host__ __device__ constexpr bool loaded_constants_in_estimate_and_accept(int LV, bool /*ROW*/) { return LV <= 5; }
 
 // One work item: the reactors of wavefront-group `group` advanced by `cnt` outer steps, starting with step `step0`
 // of this launch.  Reactors of a wavefront start every outer step together (they wait for the slowest of them), so
@@ -189,7 +241,9 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
     bool derive_due = false;                          // y0 is the pre-clamp state of a live step whose derived state is not formed yet
     constexpr bool END_AT_ACCEPT = outer_step_ends_at_accept(LV, ROW), BEGIN_AHEAD = outer_begin_ahead_of_first_trip(LV, ROW),
                    PEND_IN_BLOCK = pending_f_in_stage_block(LV, ROW), DERIVE_ONCE = derived_once_per_item(LV, ROW),
-                   HAND_BASE = BEGIN_AHEAD && base_properties_handed_to_num_jac(LV, ROW), LEAN_LAST_ACCEPT = lean_last_accept(LV, ROW);
+                   HAND_BASE = BEGIN_AHEAD && base_properties_handed_to_num_jac(LV, ROW), LEAN_LAST_ACCEPT = lean_last_accept(LV, ROW),
+                   LOADED_EA = loaded_constants_in_estimate_and_accept(LV, ROW), FIRST_IN_PROBE = first_attempt_in_probe_trip(LV, ROW), BAR1 = single_point_fence_is_barrier(LV, ROW),
+                   PRE_AHEAD = BEGIN_AHEAD && FIRST_IN_PROBE && solver_preamble_ahead_of_loop(LV, ROW);
     int steps_done = 0, reads_done = 0, cost_acc = 0;
     SolverCounters last_cnt = {0, 0, 0, 0, 0};
     int diag_trips = 0, diag_newton = 0;              // per item: 32 bits are plenty
@@ -247,7 +301,8 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
                  bad{fl, 1u << 10}, failed{fl, 1u << 11}, fv{fl, 1u << 12}, need_jac{fl, 1u << 13},
                  limit_hit{fl, 1u << 16}, pend_f{fl, 1u << 17}, jac_after_fnew{fl, 1u << 18},
                  j_dense{fl, 1u << 19},               // this lane's Jacobian couples a row to a neighbour's temperature
-                 base_held{fl, 1u << 20}, base_bpos{fl, 1u << 21};   // zb_a holds the properties at yc; their beta > 0
+                 base_held{fl, 1u << 20}, base_bpos{fl, 1u << 21},   // zb_a holds the properties at yc; their beta > 0
+                 preset{fl, 1u << 22};                // the stage values of this lane's next Newton iteration are f (PRE_AHEAD)
             fv = f_valid;
             AReg64 fac_a[3]; fac_a[0].init(); fac_a[1].init(); fac_a[2].init();   // num_jac's factors: touched once per Jacobian
             // H, iw, phi, kT, rho at y0 from the evaluation ahead of the first trip, for the Jacobian of that trip (HAND_BASE)
@@ -281,6 +336,39 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
 #pragma unroll
                 for (int q = 0; q < 3; ++q) aux[q] = yc[q] + h0 * f[q];
             };
+            // the probe's epilogue: fp = f(y0 + h0 f0) gives the second half of select_initial_step (common.py:120-134)
+            auto probe_epilogue = [&](const double *fp) {
+                double sc[3], df[3];
+#pragma unroll
+                for (int q = 0; q < 3; ++q) { sc[q] = ATOL + fabs(yc[q]) * RTOL; df[q] = fp[q] - f[q]; }
+                const double d2 = rms3<ROW, LV, 0>(L, df, sc) * rcp(h0);
+                double h1;
+                if (d1 <= 1e-15 && d2 <= 1e-15) h1 = fmax(1e-6, h0 * 1e-3);
+                else h1 = root4(0.01 * rcp(fmax(d1, d2)));
+                h_abs = fmin(fmin(100 * h0, h1), fmin(fabs(t_bound - t), max_step));
+                need_jac = true;                                          // radau.py:359-365
+                if constexpr (!FIRST_IN_PROBE) phase = PH_STEP_BEGIN;
+                else {
+                    // ---- the first attempt of this fresh solver, here and not in a trip of its own: what PH_STEP_BEGIN and
+                    // PH_ATTEMPT do when nothing has been attempted yet.  have_old_l, rejected, keep_h, have_norm_old and
+                    // have_rate are still false, kk, rate and W still the zeros the outer step declared them with.  Neither
+                    // guard of PH_ATTEMPT can fire: attempts == 0, and h_abs <= max_step from the line above, so h_abs_l
+                    // is h_abs or min_step.
+                    min_step = 10 * fabs(ulp_above(t));                  // radau.py:408
+                    h_abs_l = (h_abs < min_step) ? min_step : h_abs;
+                    attempts++;
+                    h = h_abs_l;
+                    t_new = t + h;
+                    if (t_new - t_bound > 0) t_new = t_bound;
+                    h = t_new - t;
+                    h_abs_l = fabs(h);
+                    // Z0 = 0 without a dense output, and the RHS has no time argument: the three stage points are yc, their
+                    // values the f this lane holds, bit for bit (one rounding behaviour per expression); counted as scipy
+                    // does.  The caller hands f to the Newton iteration as its three stage values.
+                    cnt_s.nfev += 3;
+                    phase = PH_NEWTON;
+                }
+            };
             // error_norm > 1: radau.py:489-496
             auto reject_step = [&]() {
                 const double fct = predict_factor(h_abs_l, have_old_l, h_abs_old_l_a.get(), error_norm, err_old_l_a.get());
@@ -305,6 +393,17 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
                     err_old_a.set(error_norm);
                     have_old = true;
                     h_abs = h_abs_l * fct;
+                    if constexpr (LOADED_EA) {
+                        const RTabPtr rt = &fresh(pa)->rt;
+                        const KZ kz = load_kz(rt); const KA ka = load_ka(rt);
+#pragma unroll
+                        for (int q = 0; q < 3; ++q) {
+                            double Qr[3];
+                            dense_row_spelled(ka, z_of_w_spelled(kz, W, q), Qr);
+                            y_old_a[q].set(yc[q]);
+                            Qa[q][0].set(Qr[0]); Qa[q][1].set(Qr[1]); Qa[q][2].set(Qr[2]);
+                        }
+                    } else {
                     const KZ kz = lit_kz(); const KA ka = lit_ka();
 #pragma unroll
                     for (int q = 0; q < 3; ++q) {
@@ -313,6 +412,7 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
                         Qa[q][0].set(z.z0 * ka.P[0] + z.z1 * ka.P[3] + z.z2 * ka.P[6]);  // Q = Z^T P  radau.py:541-543
                         Qa[q][1].set(z.z0 * ka.P[1] + z.z1 * ka.P[4] + z.z2 * ka.P[7]);
                         Qa[q][2].set(z.z0 * ka.P[2] + z.z1 * ka.P[5] + z.z2 * ka.P[8]);
+                    }
                     }
                     sol_t_old_a.set(t); sol_h_a.set(t_new - t); have_sol = true;
                 }
@@ -340,6 +440,7 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
                 else phase = PH_STEP_BEGIN;
             };
 
+            WT_STAMP(1);   // outer-step set-up (slot 1 also takes the step / attempt prologues inside the loop)
             if (fv) {
                 // f(y0) is already in f (last evaluation of the previous outer step, same y, same
                 // boundary): count it as scipy does and go straight to the initial-step probe
@@ -353,7 +454,7 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
                 if (__ballot(phase == PH_OUTER_BEGIN) != 0ull) {
                     double fy[1][3]; bool bb[1];
                     ZoneProps zb;
-                    rhs_points<ROW, 1>(L, ks, pa, &yc, fy, bb, HAND_BASE ? &zb : nullptr);
+                    rhs_points<ROW, 1, BAR1>(L, ks, pa, &yc, fy, bb, HAND_BASE ? &zb : nullptr);
                     const bool mine = bb[0] && phase == PH_OUTER_BEGIN;
                     if (phase == PH_OUTER_BEGIN) {
                         if constexpr (HAND_BASE) {
@@ -372,15 +473,39 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
                     }
                 }
             }
-
-            WT_STAMP(0);   // item / outer-step set-up
+            if constexpr (PRE_AHEAD) {
+                // Every lane that starts a solve holds f(y0) now, evaluated just above or carried over: the rest of the fresh
+                // solver's preamble, once per outer step.  The lanes leave it in PH_NEWTON with `preset` (or in PH_DONE: a
+                // probe point outside the temperature range ends the lane before any attempt), so inside the loop no lane is
+                // ever in PH_OUTER_BEGIN, PH_INIT_STEP or PH_F1.  The probe keeps no properties: those handed to num_jac are
+                // the ones at y0.
+                if (__ballot(phase == PH_INIT_STEP) != 0ull) {
+                    if (phase == PH_INIT_STEP) {      // the one copy of this arithmetic, whether f0 was evaluated or carried over
+                        initial_step_first_half();
+                        phase = PH_F1;
+                    }
+                    double fy[1][3]; bool bb[1];
+                    rhs_points<ROW, 1, BAR1>(L, ks, pa, &aux, fy, bb);
+                    const bool mine = bb[0] && phase == PH_F1;
+                    if (phase == PH_F1) cnt_s.nfev++;
+                    if (WT_RARE(__ballot(mine) != 0ull)) {
+                        if (mine && !bad) { badstage = 1; badval = aux[STT]; }
+                        bad |= mine;
+                        if (seg_any(L, bad)) { raised = true; phase = PH_DONE; }
+                    }
+                    if (phase == PH_F1) { probe_epilogue(fy[0]); preset = true; }
+                }
+            }
+            WT_STAMP(0);   // the solver's preamble alone: f(y0), the initial step's first half, the probe and its epilogue
             while (true) {
                 // reactors that finished their outer step wait here until every reactor of the wavefront has
                 if (__ballot(phase != PH_DONE) == 0ull) break;
                 // ================= trips that need no RHS evaluation (run first so the lane can join this trip's evaluation)
-                if (phase == PH_INIT_STEP) {      // the one copy of this arithmetic, whether f0 was evaluated or carried over
-                    initial_step_first_half();
-                    phase = PH_F1;
+                if constexpr (!PRE_AHEAD) {
+                    if (phase == PH_INIT_STEP) {  // the one copy of this arithmetic, whether f0 was evaluated or carried over
+                        initial_step_first_half();
+                        phase = PH_F1;
+                    }
                 }
                 if (phase == PH_STEP_BEGIN) {
                     min_step = 10 * fabs(ulp_above(t));                      // radau.py:408
@@ -444,17 +569,23 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
                 // ================= this trip's evaluation points
                 const bool newton = (phase == PH_NEWTON);
                 diag_trips++;
-                const bool eval0 = ((!BEGIN_AHEAD && phase == PH_OUTER_BEGIN) || phase == PH_F1 || phase == PH_ERR_REFINE || phase == PH_FNEW || newton);
+                // the lanes whose point is slot 0 of this trip's evaluation; with PRE_AHEAD the stage block is the Newton lanes'
+                // alone, and the two rare phases that evaluate one point of their own have the single-point site to themselves
+                const bool single = PRE_AHEAD && (phase == PH_ERR_REFINE || phase == PH_FNEW);
+                const bool eval0 = PRE_AHEAD ? newton
+                                             : ((!BEGIN_AHEAD && phase == PH_OUTER_BEGIN) || phase == PH_F1 || phase == PH_ERR_REFINE || phase == PH_FNEW || newton);
                 // f(y) of a just-accepted step rides along with the next attempt's first Newton trip
                 const bool eval3 = newton && pend_f;
                 constexpr int NPT = PEND_IN_BLOCK ? 4 : 3;   // the stage block's points: the three stages, then the pending point
                 double ye[NPT][3], Fe[NPT][3];
+                if constexpr (!PRE_AHEAD) {
 #pragma unroll
-                for (int q = 0; q < 3; ++q) {
-                    double p0 = yc[q];                                        // PH_OUTER_BEGIN, PH_FNEW
-                    if (phase == PH_F1) p0 = aux[q];
-                    if (phase == PH_ERR_REFINE) p0 = yc[q] + aux[q];
-                    ye[0][q] = p0;
+                    for (int q = 0; q < 3; ++q) {
+                        double p0 = yc[q];                                    // PH_OUTER_BEGIN, PH_FNEW
+                        if (phase == PH_F1) p0 = aux[q];
+                        if (phase == PH_ERR_REFINE) p0 = yc[q] + aux[q];
+                        ye[0][q] = p0;
+                    }
                 }
                 // Z = T W (radau.py:124): Z[2] = W0 + W1 -- the stage points
                 auto stage_points = [&]() {
@@ -462,7 +593,7 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
 #pragma unroll
                     for (int q = 0; q < 3; ++q) {
                         const ZRow z = z_of_w(kzp, W, q);
-                        if (newton) ye[0][q] = yc[q] + z.z0;
+                        if (PRE_AHEAD || newton) ye[0][q] = yc[q] + z.z0;
                         ye[1][q] = yc[q] + z.z1; ye[2][q] = yc[q] + z.z2;
                     }
                 };
@@ -470,7 +601,9 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
                 // extra block measures 0.6 % slower (and, before its solver state was restructured, cost a private segment)
                 if constexpr (LV >= 5) stage_points();
                 bool b0 = false, b1 = false, b2 = false, b3 = false;
-                if (__ballot(newton) != 0ull) {
+                // (with PRE_AHEAD a lane comes out of the preamble with its stage values preset: all lanes of the wavefront do so
+                // in the same trip, the first of the outer step, and that trip has no stage block)
+                if (__ballot(newton && !(PRE_AHEAD && preset)) != 0ull) {
                     if constexpr (LV < 5) stage_points();
                     // some reactor of the wavefront is in its Newton phase: all three stage points (three independent
                     // chains for the scheduler to interleave); the other lanes' slot-1/2 results are simply not used
@@ -497,16 +630,35 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
                     b0 = bb[0] && eval0; b1 = bb[1] && newton; b2 = bb[2] && newton;
                     if (eval0 && phase != PH_FNEW) cnt_s.nfev++;
                     if (newton) cnt_s.nfev += 2;
-                } else if (__ballot(eval0) != 0ull) {
+                } else if (PRE_AHEAD && __ballot(newton && preset) != 0ull) {
+                    // Z0 = 0 and the RHS has no time argument: the three stage values are f(y0), which the lane holds
+#pragma unroll
+                    for (int s = 0; s < 3; ++s)
+#pragma unroll
+                        for (int q = 0; q < 3; ++q) Fe[s][q] = f[q];
+                } else if (!PRE_AHEAD && __ballot(eval0) != 0ull) {
                     bool bb[1];
-                    rhs_points<ROW, 1>(L, ks, pa, ye, Fe, bb);
+                    rhs_points<ROW, 1, BAR1>(L, ks, pa, ye, Fe, bb);
                     b0 = bb[0] && eval0;
                     if (eval0 && phase != PH_FNEW) cnt_s.nfev++;
+                }
+                if (PRE_AHEAD && WT_RARE(__ballot(single) != 0ull)) {
+                    // the second error estimate's point and f(y_new) ahead of a Jacobian refresh: the loop's single-point site
+                    double yp[1][3], fy[1][3]; bool bb[1];
+#pragma unroll
+                    for (int q = 0; q < 3; ++q) yp[0][q] = (phase == PH_ERR_REFINE) ? yc[q] + aux[q] : yc[q];
+                    rhs_points<ROW, 1, BAR1>(L, ks, pa, yp, fy, bb);
+                    if (single) {
+#pragma unroll
+                        for (int q = 0; q < 3; ++q) { ye[0][q] = yp[0][q]; Fe[0][q] = fy[0][q]; }
+                        b0 = bb[0];
+                        if (phase == PH_ERR_REFINE) cnt_s.nfev++;
+                    }
                 }
                 if (!PEND_IN_BLOCK && __ballot(eval3) != 0ull) {
                     WT_COUNT(diag_f3);
                     double fy[1][3]; bool bb[1];
-                    rhs_points<ROW, 1>(L, ks, pa, &yc, fy, bb);
+                    rhs_points<ROW, 1, BAR1>(L, ks, pa, &yc, fy, bb);
                     b3 = bb[0] && eval3;
                     if (eval3) {
                         pend_f = false;       // (counted in nfev when the step was accepted)
@@ -532,39 +684,13 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
 #pragma unroll
                     for (int q = 0; q < 3; ++q) f[q] = Fe[0][q];
                     phase = PH_INIT_STEP;
-                } else if (phase == PH_F1) {
-                    double sc[3], df[3];
-#pragma unroll
-                    for (int q = 0; q < 3; ++q) { sc[q] = ATOL + fabs(yc[q]) * RTOL; df[q] = Fe[0][q] - f[q]; }
-                    const double d2 = rms3<ROW, LV>(L, df, sc) * rcp(h0);
-                    double h1;
-                    if (d1 <= 1e-15 && d2 <= 1e-15) h1 = fmax(1e-6, h0 * 1e-3);
-                    else h1 = root4(0.01 * rcp(fmax(d1, d2)));
-                    h_abs = fmin(fmin(100 * h0, h1), fmin(fabs(t_bound - t), max_step));
-                    need_jac = true;                                          // radau.py:359-365
-                    if constexpr (!first_attempt_in_probe_trip(LV, ROW)) phase = PH_STEP_BEGIN;
-                    else {
-                        // ---- the first attempt of this fresh solver, here and not in a trip of its own: what PH_STEP_BEGIN and
-                        // PH_ATTEMPT do when nothing has been attempted yet.  have_old_l, rejected, keep_h, have_norm_old and
-                        // have_rate are still false, kk, rate and W still the zeros the outer step declared them with.  Neither
-                        // guard of PH_ATTEMPT can fire: attempts == 0, and h_abs <= max_step from the line above, so h_abs_l
-                        // is h_abs or min_step.
-                        min_step = 10 * fabs(ulp_above(t));                  // radau.py:408
-                        h_abs_l = (h_abs < min_step) ? min_step : h_abs;
-                        attempts++;
-                        h = h_abs_l;
-                        t_new = t + h;
-                        if (t_new - t_bound > 0) t_new = t_bound;
-                        h = t_new - t;
-                        h_abs_l = fabs(h);
-                        // Z0 = 0 without a dense output, and the RHS has no time argument: the three stage points are yc, their
-                        // values the f this lane holds, bit for bit (one rounding behaviour per expression); counted as scipy does
+                } else if (!PRE_AHEAD && phase == PH_F1) {     // (with PRE_AHEAD the probe and its epilogue stand ahead of the loop)
+                    probe_epilogue(Fe[0]);
+                    if constexpr (FIRST_IN_PROBE) {
 #pragma unroll
                         for (int s = 0; s < 3; ++s)
 #pragma unroll
                             for (int q = 0; q < 3; ++q) Fe[s][q] = f[q];
-                        cnt_s.nfev += 3;
-                        phase = PH_NEWTON;
                     }
                 } else if (phase == PH_FNEW) {
                     // f(y_new) of an accepted step that needs it before anything else can happen:
@@ -592,10 +718,10 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
                         // the first Jacobian of an outer step that began with its own evaluation is taken at that point, yc = y0
                         // untouched since: its base properties are the held ones.  Any later Jacobian forms its own.
                         const ZoneProps zb = {zb_a[0].get(), zb_a[1].get(), zb_a[2].get(), zb_a[3].get(), zb_a[4].get(), (bool)base_bpos};
-                        num_jac<ROW>(L, ks, [&]() { return &fresh(pa)->kt; }, yc, f, fac, hf, J, jbad, jval, jd, &zb, (bool)base_held);
+                        num_jac<ROW, BAR1>(L, ks, [&]() { return &fresh(pa)->kt; }, yc, f, fac, hf, J, jbad, jval, jd, &zb, (bool)base_held);
                         base_held = false;
                     } else {
-                        num_jac<ROW>(L, ks, [&]() { return &fresh(pa)->kt; }, yc, f, fac, hf, J, jbad, jval, jd);
+                        num_jac<ROW, BAR1>(L, ks, [&]() { return &fresh(pa)->kt; }, yc, f, fac, hf, J, jbad, jval, jd);
                     }
                     cnt_s.njev++;
                     fac_a[0].set(fac[0]); fac_a[1].set(fac[1]); fac_a[2].set(fac[2]);
@@ -622,6 +748,7 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
                 if (phase == PH_NEWTON) {
                     // ---- one iteration of solve_collocation_system radau.py:84-134
                     Jac Jc; ja.coupling(Jc);
+                    if constexpr (PRE_AHEAD) preset = false;
                     bool finite = true;
 #pragma unroll
                     for (int s = 0; s < 3; ++s)
@@ -675,6 +802,12 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
                         // ---- error estimate radau.py:477-487
                         double err[3], esc[3];
                         const double ih_e = rcp(h);
+                        if constexpr (LOADED_EA) {
+                            const RTabPtr rte = &fresh(pa)->rt;
+                            const KZ kze = load_kz(rte); const KE ke = load_ke(rte);
+#pragma unroll
+                            for (int q = 0; q < 3; ++q) estimate_spelled(kze, ke, z_of_w_spelled(kze, W, q), ih_e, f[q], yc[q], err[q], esc[q]);
+                        } else {
                         const KZ kze = lit_kz(); const KE ke = lit_ke();
 #pragma unroll
                         for (int q = 0; q < 3; ++q) {
@@ -682,6 +815,7 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
                             const double ZE = (z.z0 * ke.E0 + z.z1 * ke.E1 + z.z2 * ke.E2) * ih_e;
                             err[q] = f[q] + ZE;
                             esc[q] = kze.atol + fmax(fabs(yc[q]), fabs(yc[q] + z.z2)) * kze.rtol;
+                        }
                         }
                         solve_real<ROW, LV>(L, Jc, F, err, __ballot(j_dense) == 0ull);
                         error_norm = rms3<ROW, LV>(L, err, esc);
@@ -700,6 +834,12 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
                     Jac Jc; ja.coupling(Jc);
                     double err[3], esc[3];
                     const double ih_e = rcp(h);
+                    if constexpr (LOADED_EA) {
+                        const RTabPtr rte = &fresh(pa)->rt;
+                        const KZ kze = load_kz(rte); const KE ke = load_ke(rte);
+#pragma unroll
+                        for (int q = 0; q < 3; ++q) estimate_spelled(kze, ke, z_of_w_spelled(kze, W, q), ih_e, Fe[0][q], yc[q], err[q], esc[q]);
+                    } else {
                     const KZ kze = lit_kz(); const KE ke = lit_ke();
 #pragma unroll
                     for (int q = 0; q < 3; ++q) {
@@ -707,6 +847,7 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
                         const double ZE = (z.z0 * ke.E0 + z.z1 * ke.E1 + z.z2 * ke.E2) * ih_e;
                         err[q] = Fe[0][q] + ZE;
                         esc[q] = kze.atol + fmax(fabs(yc[q]), fabs(yc[q] + z.z2)) * kze.rtol;
+                    }
                     }
                     solve_real<ROW, LV>(L, Jc, F, err, __ballot(j_dense) == 0ull);
                     error_norm = rms3<ROW, LV>(L, err, esc);
@@ -756,13 +897,13 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
                     double dHv; PropT pt;
                     if (DERIVE_ONCE && derive_due) {
                         // the step before this one was ordinary: should this one leave the range, its decay rate is the one that stays
-                        dK = prop_T(load_kt(&fresh(pa)->kt), T_before).kT; wrote_k = true;
+                        dK = prop_T<BAR1>(load_kt(&fresh(pa)->kt), T_before).kT; wrote_k = true;
                         derive_due = false;
                     }
                     {
                         ArgPtr a2 = fresh(pa);
                         const KP cp = load_kp(&a2->kt); const KT ct = load_kt(&a2->kt);
-                        dHv = exp10_k(cp, -y0[SPH]); pt = prop_T(ct, y0[STT]);
+                        dHv = exp10_k(cp, -y0[SPH]); pt = prop_T<BAR1>(ct, y0[STT]);
                     }
                     dH = dHv;
                     dR = pt.rho;
@@ -978,7 +1119,7 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
         if (derive_due) {
             ArgPtr a2 = fresh(pa);
             const KP cp = load_kp(&a2->kt); const KT ct = load_kt(&a2->kt);
-            const PropT pt = prop_T(ct, y0[STT]);
+            const PropT pt = prop_T<BAR1>(ct, y0[STT]);
             dH = exp10_k(cp, -y0[SPH]); dR = pt.rho; dK = pt.kT; wrote_k = true;
         }
     }

@@ -234,8 +234,10 @@ __device__ __forceinline__ KA load_ka(RTabPtr t)
     return {{a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], b[0]}};
 }
 __device__ __forceinline__ KG load_kg(RTabPtr t) { const d8 a = ((KVec)t)[6]; return {a[0], a[1]}; }
-// The error estimate and the accept block keep literal constants: with loaded ones the compiler stops sharing their
-// common subexpressions and fuses the remaining ones differently (last-bit changes; measured, tools/bits_check.py).
+// Literal constants for the error estimate and the accept block where loaded_constants_in_estimate_and_accept
+// (wt_step.hpp) is off: with loaded ones and the expressions as written the compiler stops sharing their common
+// subexpressions and fuses the remaining ones differently (last-bit changes; measured, tools/bits_check.py).  Where the
+// switch is on the roundings are spelled out (z_of_w_spelled ... in wt_step.hpp) and the constants are loaded.
 constexpr RTab RT0 = default_rtab();
 __device__ __forceinline__ KZ lit_kz() { return {RT0.T00, RT0.T01, RT0.T02, RT0.T10, RT0.T11, RT0.T12, RT0.rtol, RT0.atol}; }
 __device__ __forceinline__ KE lit_ke() { return {RT0.E0, RT0.E1, RT0.E2}; }

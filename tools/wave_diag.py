@@ -25,7 +25,8 @@ for label, k, fused in (("queue 20 steps", 20, True), ("queue 100 steps", 100, T
           f" | clk/wall GHz {np.mean(clk/wall)/1e3:.2f} | reactor nfev mean {st[:,0].mean():.1f} max {st[:,0].max()}")
     if d.shape[1] > 8:
         # WT_STAMP(0...7); in a trip the blocks run in the order prologue, rhs+light, num_jac, factorize, newton
-        names = ["setup", "prologue", "factorize", "rhs+light epilogues", "newton/refine epilogue", "num_jac", "post-step", "sensors/io"]
+        # (slot 0 is the solver's preamble ahead of the trip loop; the outer step's set-up goes with the prologues)
+        names = ["preamble", "setup+prologues", "factorize", "rhs+light epilogues", "newton/refine epilogue", "num_jac", "post-step", "sensors/io"]
         tot = d[:, 8:16].sum()
         print("   section shares: " + "  ".join(f"{nm} {d[:, 8 + i].sum() / tot * 100:.1f}%" for i, nm in enumerate(names) if nm != "-")
               + f" | stamped clocks/step {d[:, 8:16].sum(1).mean() / k:.0f}")
