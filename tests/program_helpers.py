@@ -51,6 +51,86 @@ def wavefront_groups(ens):
     return int(nw.value)
 
 
+PACKINGS = ("spread", "packed")
+
+
+def set_packing(monkeypatch, packing):
+    """How the ensembles created from now on are dealt into wavefronts: "packed" sets WT_FULL_WAVES (64 // n reactors in
+    every wavefront), "spread" removes it (the library's own choice, which depends on the card's CU count)."""
+    assert packing in PACKINGS, packing
+    if packing == "packed":
+        monkeypatch.setenv("WT_FULL_WAVES", "1")
+    else:
+        monkeypatch.delenv("WT_FULL_WAVES", raising=False)
+
+
+def assert_packing(ens, packing):
+    """The run really had the packing it was meant to have, by the library's own count of wavefront-groups: packed,
+    ceil(N / (64 // n)) of them; spread, more than that wherever a wavefront has room for a second reactor and there is
+    one (how many more is the library's business: it depends on the card).  Ask after the last step."""
+    assert packing in PACKINGS, packing
+    n, N = ens.n_zones, ens.n_reactors
+    R = 64 // n
+    full, got = -(-N // R), wavefront_groups(ens)
+    if packing == "packed":
+        assert got == full, (packing, n, N, got, full)
+    elif R > 1 and N > 1:
+        assert got > full, (packing, n, N, got, full)
+    else:
+        assert got == N, (packing, n, N, got)
+
+
+class Packing:
+    """What the ``packing`` fixture hands a test: ``name`` ("spread" or "packed"), ``place`` for an ensemble just created
+    (packed runs take the identity placement, so that reactor r sits in slot r % R of group r // R; spread runs keep what
+    they had) and ``check`` for an ensemble after its last step (``assert_packing``).  The fixture fails a test that
+    never called ``check``."""
+
+    def __init__(self, name):
+        self.name, self.packed, self.checked = name, name == "packed", 0
+
+    def __repr__(self):
+        return self.name
+
+    def place(self, ens):
+        if self.packed:
+            ens.set_placement(False)
+        return ens
+
+    def check(self, ens):
+        assert_packing(ens, self.name)
+        self.checked += 1
+
+
+@pytest.fixture(params=PACKINGS)
+def packing(request, monkeypatch):
+    """Runs a test once with the library's own spreading of a small ensemble and once with full wavefronts.  Test modules
+    import the fixture by name; a test that takes only some zone counts packed parametrises it indirectly."""
+    p = Packing(request.param)
+    set_packing(monkeypatch, p.name)
+    yield p
+    assert p.checked, f"a {p.name} test ended without asserting its wavefront-groups (Packing.check)"
+
+
+def both_packings(argnames, argvalues, packed=None):
+    """``pytest.mark.parametrize`` over ``argvalues`` and the ``packing`` fixture, for a test that was parametrised over
+    ``argvalues`` before it ran packed as well: the spread cases keep the ids they always had (pytest's own for numbers
+    and strings, name and index for anything else), the packed ones put ``packed`` in front.  ``packed``: the values
+    that run packed, where not all do."""
+    names = [a.strip() for a in argnames.split(",")]
+
+    def ident(name, i, x):
+        return x if isinstance(x, str) else str(x) if isinstance(x, (bool, int, float)) else f"{name}{i}"
+
+    params = []
+    for pk, values in (("spread", list(argvalues)), ("packed", list(argvalues if packed is None else packed))):
+        for i, v in enumerate(values):
+            vals = tuple(v) if len(names) > 1 else (v,)
+            base = "-".join(ident(nm, i, x) for nm, x in zip(names, vals))
+            params.append(pytest.param(*vals, pk, id=base if pk == "spread" else f"packed-{base}"))
+    return pytest.mark.parametrize(",".join(names + ["packing"]), params, indirect=["packing"])
+
+
 def assert_equal_by_reactor(ref, got, what, R):
     """``assert_all_equal`` for arrays whose last axis is the reactor: a mismatch names the reactors and, for the identity
     placement, their (wavefront-group, slot)."""

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from conftest import cfg_columns, golden_json, golden_npz
+from program_helpers import both_packings, packing  # noqa: F401  (a fixture: every multi-reactor test runs spread and packed)
 
 pytestmark = pytest.mark.gpu
 
@@ -53,9 +54,10 @@ def _mixed_group(wt, n, R):
 
 
 @pytest.mark.parametrize("limit", [0, 2])
-@pytest.mark.parametrize("n,R", [(8, 8), (5, 12)])
-def test_mixed_starts_in_one_wavefront(gpu, wt, n, R, limit):
-    """One wavefront-group whose reactors start their outer steps a trip apart: a reactor that was clamped (the g11
+@both_packings("n,R", [(8, 8), (5, 12)])
+def test_mixed_starts_in_one_wavefront(gpu, wt, packing, n, R, limit):
+    """Packed, one wavefront-group (spread, R wavefronts of one reactor each: the same comparison without neighbours,
+    kept as it was) whose reactors start their outer steps a trip apart: a reactor that was clamped (the g11
     clamp cases clamp on the first step they take, status asserted) has no carried f(y0) on the step after and passes
     through PH_OUTER_BEGIN, so its probe -- and with it the joined first Newton iteration -- comes one trip after its
     neighbours'.  With an attempt limit of 2 the same happens after every outer step a reactor fails, which for the
@@ -68,7 +70,9 @@ def test_mixed_starts_in_one_wavefront(gpu, wt, n, R, limit):
     ens.set_boundary(bc)
     ens.set_state(pH, Cl, T, np.zeros(R))
     ens.set_step_limit(limit)
+    packing.place(ens)
     got = _result(ens, ens.step(1.0, n_steps=steps))
+    packing.check(ens)
     ens.close()
     clamp_bits = {1: 8, 3: 4, R - 2: 4}               # ST_CLAMP_CL, ST_CLAMP_PH
     for slot, bit in clamp_bits.items():
@@ -88,22 +92,39 @@ def test_mixed_starts_in_one_wavefront(gpu, wt, n, R, limit):
             assert np.array_equal(a[r:r + 1], b, equal_nan=True), (r, a[r], b[0])
 
 
-@pytest.mark.parametrize("n", [2, 4, 5, 8, 12, 16, 20, 40])
-def test_every_instantiation_vs_oracle_with_counters(gpu, wt, oracle, n):
-    """Two full wavefronts and a partial one at every instantiation of the step kernel, 6 steps: state against the
+_ORACLE = {}                # zone count -> the oracle's state after 6 steps and its counters of every step
+
+
+@both_packings("n", [2, 4, 5, 8, 12, 16, 20, 40])
+def test_every_instantiation_vs_oracle_with_counters(gpu, wt, oracle, packing, n):
+    """Two wavefront-groups' worth of reactors and one more at every instantiation of the step kernel -- packed, two
+    full wavefronts and a partial one; spread, a wavefront per reactor -- 6 steps: state against the
     oracle's ensemble_step within the bounds of test_full_size_ensemble_vs_oracle (1e-6 on all but 1e-5 of the samples,
     1e-5 on every one), solver counters of every outer step exactly (nfev and the attempt count of the joined trip).
-    The counters come from the oracle's single-reactor step chained over the same states; the GPU's per step from a
-    second ensemble stepped one call at a time, which must leave the bits of the one-call run."""
+    The counters come from the oracle's single-reactor step chained over the same states (computed once per zone
+    count, for both packings); the GPU's per step from a second ensemble stepped one call at a time, which must leave
+    the bits of the one-call run."""
     N, steps = 2 * (64 // n) + 1, 6
     cols, bc = wt.make_ensemble(N)
-    ens = wt.ReactorEnsemble(cols, n_zones=n)
+    ens = packing.place(wt.ReactorEnsemble(cols, n_zones=n))
     ens.set_boundary(bc)
     s0 = ens.state
     es = ens.step(1.0, n_steps=steps)
     last = ens.solver_stats()
-    pH, Cl, T, t, ost = oracle.ensemble_step(n, ens.constants, bc, 1.0, steps, s0.pH, s0.chlorine, s0.temperature,
-                                             s0.time, nthreads=4)
+    if n not in _ORACLE:
+        out = tuple(oracle.ensemble_step(n, ens.constants, bc, 1.0, steps, s0.pH, s0.chlorine, s0.temperature, s0.time,
+                                         nthreads=4))
+        # the oracle's counters, step by step
+        ref = np.zeros((steps, N, 5), dtype=np.int32)
+        for r in range(N):
+            y, tt = np.concatenate([s0.pH[r], s0.chlorine[r], s0.temperature[r]]), float(s0.time[r])
+            for k in range(steps):
+                y, tt, status, ref[k, r] = _oracle_stats(oracle, n, ens.constants[:, r], bc[:, r], 1.0, y, tt)
+                assert status == 0
+        for a in out + (ref,):
+            a.setflags(write=False)
+        _ORACLE[n] = out + (ref,)
+    pH, Cl, T, t, ost, ref = _ORACLE[n]
     assert not es.status.any() and not ost.any()
     err = np.stack([np.abs(es.pH - pH) / np.abs(pH), np.abs(es.chlorine - Cl) / np.abs(Cl),
                     np.abs(es.temperature - T) / np.abs(T)])
@@ -111,13 +132,6 @@ def test_every_instantiation_vs_oracle_with_counters(gpu, wt, oracle, n):
     assert np.mean(err < 1e-6) > 1 - 1e-5
     assert err.max() < 1e-5
     assert np.array_equal(es.time, t)
-    # the oracle's counters, step by step
-    ref = np.zeros((steps, N, 5), dtype=np.int32)
-    for r in range(N):
-        y, tt = np.concatenate([s0.pH[r], s0.chlorine[r], s0.temperature[r]]), float(s0.time[r])
-        for k in range(steps):
-            y, tt, status, ref[k, r] = _oracle_stats(oracle, n, ens.constants[:, r], bc[:, r], 1.0, y, tt)
-            assert status == 0
     ens.set_state(s0.pH, s0.chlorine, s0.temperature, s0.time)
     for k in range(steps):
         es1 = ens.step(1.0, n_steps=1)
@@ -125,6 +139,7 @@ def test_every_instantiation_vs_oracle_with_counters(gpu, wt, oracle, n):
     assert np.array_equal(last, ref[steps - 1])
     for a, b in ((es.pH, es1.pH), (es.chlorine, es1.chlorine), (es.temperature, es1.temperature), (es.time, es1.time)):
         assert np.array_equal(a, b)
+    packing.check(ens)
     ens.close()
 
 
@@ -163,16 +178,17 @@ def test_first_attempt_failures_keep_the_fixture_counters(gpu, wt, oracle, name)
     ens.close()
 
 
-@pytest.mark.parametrize("limit", [1, 2])
-def test_step_limit_counts_the_joined_first_attempt(gpu, wt, oracle, limit):
-    """16 reactors of 4 zones, 3 outer steps, one call each so that every step's counters and flags can be read.  A
+@both_packings("limit", [1, 2])
+def test_step_limit_counts_the_joined_first_attempt(gpu, wt, oracle, packing, limit):
+    """16 reactors of 4 zones (packed, one full wavefront, where a flagged reactor waits beside neighbours still at
+    work; spread, sixteen wavefronts), 3 outer steps, one call each so that every step's counters and flags can be read.  A
     reactor whose outer step needs more attempts than the limit (the oracle's nsteps + nrej of that step, unlimited,
     from the state the GPU step starts from) ends it flagged STEP_LIMIT with exactly `limit` attempts made; the others
     are not flagged and keep the oracle's counters.  The first attempt is started by the probe's epilogue and never
     sees the guard at the loop top, so this is where a miscount would show."""
     n, N = 4, 16
     cols, bc = wt.make_ensemble(N)
-    ens = wt.ReactorEnsemble(cols, n_zones=n)
+    ens = packing.place(wt.ReactorEnsemble(cols, n_zones=n))
     ens.set_boundary(bc)
     ens.set_step_limit(limit)
     flagged_total = 0
@@ -194,4 +210,5 @@ def test_step_limit_counts_the_joined_first_attempt(gpu, wt, oracle, limit):
         assert np.all(es.status[~flagged] == 0)
         flagged_total += int(flagged.sum())
     assert flagged_total > 0
+    packing.check(ens)
     ens.close()

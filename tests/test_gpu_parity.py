@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import SCENARIOS, cfg_columns, golden_json, golden_npz, relerr
+from program_helpers import both_packings, packing  # noqa: F401  (a fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -230,23 +231,49 @@ def test_placement_changes_no_bit(gpu, wt, n):
         assert np.array_equal(a_, b_, equal_nan=True)
 
 
-@pytest.mark.parametrize("n", [5, 8, 12, 20, 40])
-def test_solve_fast_paths_change_no_bit(gpu, wt, monkeypatch, n):
+def _mixed_columns(wt, mask, a, b):
+    """Configuration columns that are `a`'s where `mask` is set and `b`'s elsewhere; a column one side does not name
+    has ReactorConfiguration's default there."""
+    defaults = wt.ReactorConfiguration()
+    side = lambda cols, k: np.broadcast_to(np.asarray(cols.get(k, getattr(defaults, k))), mask.shape)
+    return {k: np.where(mask, side(a, k), side(b, k)) for k in sorted(set(a) | set(b))}
+
+
+@both_packings("n", [5, 8, 12, 20, 40], packed=[5, 8, 12, 20])
+def test_solve_fast_paths_change_no_bit(gpu, wt, monkeypatch, packing, n):
     """A wavefront none of whose Jacobians couples a row to a neighbour's temperature skips those terms in every solve,
     and at the row-straddling zone counts solves the T and the pH system in lock step (wt_pcr.hpp: jac_t_dense,
     pcr_rc_pair).  Which path a reactor takes depends on the other reactors of its wavefront, so the paths must agree
     bit for bit: WT_DENSE_COUPLING sends every solve down the general path, and state, status and solver counters are
-    those of the default run."""
-    N = 1500 if n <= 20 else 300
-    cols, bc = wt.make_ensemble(N, seed=77)
+    those of the default run.
+
+    Spread: 1500 benign reactors (300 at n = 40), which the library deals two to a wavefront on an MI355X where twelve
+    fit at n = 5.  Packed: five full wavefronts under the identity placement, the even slots of each from
+    _random_edge_ensemble -- reactors at stratification switches, where jac_t_dense fires -- and the odd slots from
+    make_ensemble, an attempt limit of 300 on both runs as in test_edge_configurations_vs_oracle.  Nothing the host can
+    read records which solves took the general path in the default run (and the kernel gets no counter for it): that the
+    packed wavefronts mix the paths rests on the population, not on an assertion."""
+    if packing.packed:
+        R = 64 // n
+        N = 5 * R
+        edge = (np.arange(N) % R) % 2 == 0
+        ecols, ebc = _random_edge_ensemble(wt, N, seed=7700 + n)
+        bcols, bbc = wt.make_ensemble(N, seed=77)
+        cols, bc = _mixed_columns(wt, edge, ecols, bcols), np.ascontiguousarray(np.where(edge, ebc, bbc))
+    else:
+        N = 1500 if n <= 20 else 300
+        cols, bc = wt.make_ensemble(N, seed=77)
     def run(dense):
         if dense:
             monkeypatch.setenv("WT_DENSE_COUPLING", "1")
         else:
             monkeypatch.delenv("WT_DENSE_COUPLING", raising=False)
-        ens = wt.ReactorEnsemble(cols, n_zones=n); ens.set_boundary(bc)       # (the knob is read at creation)
+        ens = packing.place(wt.ReactorEnsemble(cols, n_zones=n)); ens.set_boundary(bc)       # (the knob is read at creation)
+        if packing.packed:
+            ens.set_step_limit(300)
         es = ens.step(1.0, n_steps=25)
         out = (es.pH, es.chlorine, es.temperature, es.time, es.status, ens.solver_stats())
+        packing.check(ens)
         ens.close()
         return out
     fast, general = run(False), run(True)
@@ -315,18 +342,27 @@ def test_plain_c_client_equals_the_python_host(gpu, wt, tmp_path):
     ens.close()
 
 
-@pytest.mark.parametrize("n,N", [(2, 5), (3, 33), (5, 1), (7, 100), (16, 9), (31, 4), (64, 3)])
-def test_ragged_shapes_vs_oracle(gpu, wt, oracle, n, N):
-    """Zone counts that do not divide 64, a single reactor, the 64-zone maximum."""
+_RAGGED = [(2, 5), (3, 33), (5, 1), (7, 100), (16, 9), (31, 4), (64, 3)]
+_RAGGED_ORACLE = {}
+
+
+@both_packings("n,N", _RAGGED, packed=[(n, N) for n, N in _RAGGED if n <= 32])
+def test_ragged_shapes_vs_oracle(gpu, wt, oracle, packing, n, N):
+    """Zone counts that do not divide 64, a single reactor, the 64-zone maximum.  Spread, these ensembles run one
+    reactor per wavefront; packed (n <= 32), wavefronts that are part full, with idle lanes behind the last segment
+    where n does not divide 64.  The oracle's result is computed once per shape."""
     cols, bc = wt.make_ensemble(N, seed=99)
-    ens = wt.ReactorEnsemble(cols, n_zones=n)
+    ens = packing.place(wt.ReactorEnsemble(cols, n_zones=n))
     ens.set_boundary(bc)
     st0 = ens.state
     es = ens.step(1.0, n_steps=5)
-    pH, Cl, T, t, ost = oracle.ensemble_step(n, ens.constants, bc, 1.0, 5, st0.pH, st0.chlorine, st0.temperature,
-                                             st0.time, nthreads=4)
+    if (n, N) not in _RAGGED_ORACLE:
+        _RAGGED_ORACLE[n, N] = oracle.ensemble_step(n, ens.constants, bc, 1.0, 5, st0.pH, st0.chlorine, st0.temperature,
+                                                    st0.time, nthreads=4)
+    pH, Cl, T, t, ost = _RAGGED_ORACLE[n, N]
     assert np.array_equal(es.status, ost.astype(np.uint32))
     assert relerr(es.pH, pH) < 1e-7 and relerr(es.chlorine, Cl) < 1e-7 and relerr(es.temperature, T) < 1e-7
+    packing.check(ens)
     ens.close()
 
 
@@ -497,23 +533,33 @@ def _random_edge_ensemble(wt, N, seed):
     return cols, np.ascontiguousarray(bc)
 
 
-@pytest.mark.parametrize("n,dt,steps", [(4, 1.0, 6), (8, 0.1, 6), (5, 10.0, 4), (8, 30.0, 3), (20, 100.0, 2)])
-def test_edge_configurations_vs_oracle(gpu, wt, oracle, n, dt, steps):
+_EDGE_ORACLE = {}
+
+
+@both_packings("n,dt,steps", [(4, 1.0, 6), (8, 0.1, 6), (5, 10.0, 4), (8, 30.0, 3), (20, 100.0, 2)])
+def test_edge_configurations_vs_oracle(gpu, wt, oracle, packing, n, dt, steps):
+    """1500 reactors on the branches of the RHS against the oracle.  Spread, the library deals them two to a wavefront
+    on an MI355X; packed, 64 // n under the identity placement, so a reactor that freezes, clamps or runs into the
+    attempt limit does so beside up to fifteen that go on.  Same population, same bounds; the oracle's result is computed
+    once per case."""
     N = 1500
     cols, bc = _random_edge_ensemble(wt, N, seed=1000 * n + int(dt * 10))
-    ens = wt.ReactorEnsemble(cols, n_zones=n)
+    ens = packing.place(wt.ReactorEnsemble(cols, n_zones=n))
     ens.set_boundary(bc)
     # some of these reactors slide along the 8 degC density jump: scipy's Radau then needs millions of
     # internal steps per outer step (hours in the reference); both sides stop after 300 attempts
     ens.set_step_limit(300)
-    oracle.set_step_limit(300)
     s0 = ens.state
     es = ens.step(dt, n_steps=steps)
-    try:
-        pH, Cl, T, t, ost = oracle.ensemble_step(n, ens.constants, bc, dt, steps, s0.pH, s0.chlorine,
-                                                 s0.temperature, s0.time, nthreads=16)
-    finally:
-        oracle.set_step_limit(0)
+    packing.check(ens)
+    if (n, dt, steps) not in _EDGE_ORACLE:
+        oracle.set_step_limit(300)
+        try:
+            _EDGE_ORACLE[n, dt, steps] = oracle.ensemble_step(n, ens.constants, bc, dt, steps, s0.pH, s0.chlorine,
+                                                              s0.temperature, s0.time, nthreads=16)
+        finally:
+            oracle.set_step_limit(0)
+    pH, Cl, T, t, ost = _EDGE_ORACLE[n, dt, steps]
     # same reactors freeze / clamp (temperature range, negative chlorine, ...); a reactor that hits the
     # attempt limit on one side is chaotic by construction and may just make it on the other
     lim = ((es.status | ost.astype(np.uint32)) & 128) != 0
@@ -536,33 +582,49 @@ def test_edge_configurations_vs_oracle(gpu, wt, oracle, n, dt, steps):
     ens.close()
 
 
-def test_nonfinite_state_is_contained(gpu, wt, oracle):
+@both_packings("n", [8], packed=[8, 5, 12, 20, 31])
+def test_nonfinite_state_is_contained(gpu, wt, oracle, packing, n):
     """A reactor whose state is NaN / inf must not disturb the reactors sharing its wavefront, and ends like the
     reference: scipy's solve_ivp refuses the state (ValueError out of step(), tests/golden/g11_branches.json), so
-    the reactor does not advance."""
-    n, N = 8, 24
+    the reactor does not advance.
+
+    Spread (n = 8, 24 reactors, a NaN in one zone of reactor 9 and an all-inf reactor 17) nobody shares a wavefront
+    with anybody on an MI355X.  Packed, identity placement, N = 3 R + 1: an all-NaN reactor in the first slot of
+    group 0, an all-inf one in the last slot of group 1 and one with a NaN in a single zone in a middle slot of group
+    2, at n = 8 and at one zone count per level whose segments do not fill DPP rows (5, 12, 20, 31), where a lane reads
+    its neighbours' values through the LDS exchange row.  The clean twin has the run's packing."""
+    if packing.packed:
+        R = 64 // n
+        N = 3 * R + 1
+        nan_all, inf_all, nan_one = 0, 2 * R - 1, 2 * R + R // 2
+    else:
+        N, nan_all, inf_all, nan_one = 24, None, 17, 9
+    bad = [r for r in (nan_all, inf_all, nan_one) if r is not None]
     cols, bc = wt.make_ensemble(N, seed=5)
-    ens = wt.ReactorEnsemble(cols, n_zones=n)
+    ens = packing.place(wt.ReactorEnsemble(cols, n_zones=n))
     ens.set_boundary(bc)
     s0 = ens.state
-    pH0 = s0.pH.copy(); pH0[9, 3] = np.nan; pH0[17, :] = np.inf
+    pH0 = s0.pH.copy(); pH0[nan_one, 3 % n] = np.nan; pH0[inf_all, :] = np.inf
+    if nan_all is not None:
+        pH0[nan_all, :] = np.nan
     ens.set_state(pH0, s0.chlorine, s0.temperature, s0.time)
     es = ens.step(1.0, n_steps=3)
     # clean twin
-    ens2 = wt.ReactorEnsemble(cols, n_zones=n)
+    ens2 = packing.place(wt.ReactorEnsemble(cols, n_zones=n))
     ens2.set_boundary(bc)
     es2 = ens2.step(1.0, n_steps=3)
-    good = np.ones(N, bool); good[[9, 17]] = False
+    good = np.ones(N, bool); good[bad] = False
     assert np.array_equal(es.pH[good], es2.pH[good]) and np.array_equal(es.chlorine[good], es2.chlorine[good])
     assert np.array_equal(es.temperature[good], es2.temperature[good])
     assert not es.status[good].any()
     pHo, Clo, To, to, ost = oracle.ensemble_step(n, ens.constants, bc, 1.0, 3, pH0, s0.chlorine, s0.temperature,
                                                  s0.time, nthreads=2)
     assert np.array_equal(es.status, ost.astype(np.uint32))
-    assert es.status[9] == 64 and es.status[17] == 64          # NONFINITE, nothing else
-    assert es.time[9] == 0.0 and es.time[17] == 0.0 and np.all(es.time[good] == 3.0)
-    assert np.array_equal(es.pH[[9, 17]], pH0[[9, 17]], equal_nan=True)      # state untouched
-    assert np.array_equal(es.chlorine[[9, 17]], s0.chlorine[[9, 17]])
+    assert np.all(es.status[bad] == 64)                        # NONFINITE, nothing else
+    assert np.all(es.time[bad] == 0.0) and np.all(es.time[good] == 3.0)
+    assert np.array_equal(es.pH[bad], pH0[bad], equal_nan=True)              # state untouched
+    assert np.array_equal(es.chlorine[bad], s0.chlorine[bad])
+    packing.check(ens); packing.check(ens2)
     ens.close(); ens2.close()
     # the drop-in raises what the reference raises, and keeps its state
     nf = golden_json("g11_branches.json")["nonfinite"]

@@ -3,11 +3,17 @@ step, the next one evaluates f(y0) ahead of its first trip, the pending f(y_new)
 of the next stage block, and the derived state is formed once per item.  None of it may move a bit or a counter, at any
 item length and at any instantiation of the step kernel.  Checked here: one call against one-step calls and a chunked
 stream schedule, the counters of every step of an item against the CPU oracle, clamps and a raise inside an item
-(g11 / g4 fixtures), a boundary reload after every step, and reactors that lag their wavefront."""
+(g11 / g4 fixtures), a boundary reload after every step, and reactors that lag their wavefront.
+
+Every test runs twice (the ``packing`` fixture).  Spread is the library's own dealing of an ensemble this small, one
+reactor per wavefront on an MI355X: nobody has a neighbour, and what the docstrings say about wavefronts with ordinary
+reactors in them holds for the packed run alone, where WT_FULL_WAVES puts 64 // n reactors into every wavefront under
+the identity placement and the group count is asserted."""
 import numpy as np
 import pytest
 
 from conftest import cfg_columns, golden_json, golden_npz
+from program_helpers import both_packings, packing  # noqa: F401  (a fixture: every test runs spread and packed)
 
 pytestmark = pytest.mark.gpu
 
@@ -32,13 +38,14 @@ def _assert_same(a, b, what):
 
 
 def _group_size(n, floor=8):
-    """Reactors of a test: two wavefront-groups, at least `floor` (a group holds 64 // n reactors), at most 64."""
+    """Reactors of a test: two wavefront-groups' worth, at least `floor` (a packed group holds 64 // n reactors), at
+    most 64."""
     return min(64, max(2 * (64 // n), floor))
 
 
 # ---------------------------------------------------------------- item length
-@pytest.mark.parametrize("n", NS)
-def test_item_length_changes_no_bit(gpu, wt, n):
+@both_packings("n", NS)
+def test_item_length_changes_no_bit(gpu, wt, packing, n):
     """The same ensemble advanced by one call of 9 steps (one item: f pending from step to step in registers, derived
     state formed once), by nine calls of one step (every step begins with f(y0) from memory, derived state stored every
     step) and by a stream schedule with launches of 2 steps: state with the derived arrays, flow and time, status and
@@ -47,7 +54,7 @@ def test_item_length_changes_no_bit(gpu, wt, n):
     cols, bc = wt.make_ensemble(N)
     got = {}
     for how in ("one call", "one-step calls", "stream, chunk 2"):
-        ens = wt.ReactorEnsemble(cols, n_zones=n)
+        ens = packing.place(wt.ReactorEnsemble(cols, n_zones=n))
         ens.set_boundary(bc)
         if how == "stream, chunk 2":
             ens.set_schedule(1, 2)
@@ -57,6 +64,7 @@ def test_item_length_changes_no_bit(gpu, wt, n):
         else:
             ens.step(1.0, n_steps=K, download=False)
         got[how] = _fields(ens)
+        packing.check(ens)
         ens.close()
     assert not got["one call"]["status"].any()
     assert np.all(got["one call"]["time"] == K)
@@ -86,8 +94,8 @@ def _oracle_counters(oracle, n, par, bc, s0, K):
 
 
 @pytest.mark.parametrize("lengths", [(1, 3, 5, 7, 9), (2, 4, 6, 8)])
-@pytest.mark.parametrize("n", NS)
-def test_counters_of_every_step_of_an_item_vs_oracle(gpu, wt, oracle, n, lengths):
+@both_packings("n", NS)
+def test_counters_of_every_step_of_an_item_vs_oracle(gpu, wt, oracle, packing, n, lengths):
     """A call stores the counters of its last outer step, so step k of an item is read from an item of k + 1 steps: the
     items of 1 ... 9 steps from the same start (two test cases, odd and even lengths), each against the oracle's
     single-reactor step chained over its own states.  nfev is where a miscount would show: f(y_new) of an outer step's
@@ -98,7 +106,7 @@ def test_counters_of_every_step_of_an_item_vs_oracle(gpu, wt, oracle, n, lengths
     cols, bc = wt.make_ensemble(N)
     ref = None
     for k in lengths:
-        ens = wt.ReactorEnsemble(cols, n_zones=n)
+        ens = packing.place(wt.ReactorEnsemble(cols, n_zones=n))
         ens.set_boundary(bc)
         if ref is None:
             ref = _oracle_counters(oracle, n, ens.constants, bc, ens.state, K)
@@ -106,15 +114,19 @@ def test_counters_of_every_step_of_an_item_vs_oracle(gpu, wt, oracle, n, lengths
         es = ens.step(1.0, n_steps=k)
         assert not es.status.any()
         got = ens.solver_stats()[:, :4]
+        packing.check(ens)
         ens.close()
         assert np.array_equal(got, ref[k - 1]), (n, k, np.argwhere(got != ref[k - 1])[:4].tolist())
 
 
 # ---------------------------------------------------------------- the rare ends of a step inside an item
-def _rare_group(wt, n, N, cold_T):
+def _rare_group(wt, n, N, cold_T, where=None):
     """N reactors of n zones: the three clamp cases of g11 in slots 1, 3 and N - 2 (their parameters, boundary and
     pre-step state: the two out-of-range inlet-side zones kept, the others at the fixture's in-range value), the cold
-    run of g4 in slot N - 4 with every zone at cold_T, ordinary reactors of make_ensemble elsewhere."""
+    run of g4 in slot N - 4 with every zone at cold_T, ordinary reactors of make_ensemble elsewhere.  `where`: other
+    reactor indices for the four, in that order."""
+    where = (1, 3, N - 2, N - 4) if where is None else tuple(where)
+    assert len(set(where)) == 4 and all(0 <= w < N for w in where), where
     g = golden_npz("g11_branches.npz")
     cold = golden_json("g4_faults.json")["cold_run"]
     cols, bc = wt.make_ensemble(N, seed=97)
@@ -126,7 +138,7 @@ def _rare_group(wt, n, N, cold_T):
     pH = np.repeat(full["initial_pH"][:, None], n, 1)
     Cl = np.repeat(full["initial_chlorine"][:, None], n, 1)
     T = np.repeat(full["temperature"][:, None], n, 1)
-    slots = dict(zip(CLAMP_CASES, (1, 3, N - 2)))
+    slots = dict(zip(CLAMP_CASES, where[:3]))
     for name, slot in slots.items():
         c = cfg_columns(g[f"{name}__cfg"], g["cfg_fields"])
         for k in full:
@@ -136,17 +148,17 @@ def _rare_group(wt, n, N, cold_T):
         for arr, row in ((pH, pre[0]), (Cl, pre[1]), (T, pre[2])):
             arr[slot, :] = row[3]
             arr[slot, :min(2, n)] = row[:min(2, n)]
-    slots["cold_run"] = N - 4
+    c = slots["cold_run"] = where[3]
     for k in full:
         if k in cold["config"]:
-            full[k][N - 4] = cold["config"][k]
-    bc[:, N - 4] = cold["bc"]
-    pH[N - 4], Cl[N - 4], T[N - 4] = cold["config"]["initial_pH"], cold["config"]["initial_chlorine"], cold_T
+            full[k][c] = cold["config"][k]
+    bc[:, c] = cold["bc"]
+    pH[c], Cl[c], T[c] = cold["config"]["initial_pH"], cold["config"]["initial_chlorine"], cold_T
     return full, np.ascontiguousarray(bc), pH, Cl, T, slots
 
 
-@pytest.mark.parametrize("n", NS)
-def test_clamps_and_a_raise_inside_an_item(gpu, wt, n):
+@both_packings("n", NS)
+def test_clamps_and_a_raise_inside_an_item(gpu, wt, packing, n):
     """Reactors that clamp on the first step of a 9-step item and one that cools below 0 degC in the middle of it, in
     wavefronts with ordinary reactors: state, status, the temperature the raise names and the derived arrays equal,
     bit for bit, those of the same ensemble advanced by one-step calls -- where the derived state is formed after every
@@ -158,7 +170,7 @@ def test_clamps_and_a_raise_inside_an_item(gpu, wt, n):
     cols, bc, pH, Cl, T, slots = _rare_group(wt, n, N, cold_T=0.05)
     runs = {}
     for how in ("one call", "one-step calls"):
-        ens = wt.ReactorEnsemble(cols, n_zones=n)
+        ens = packing.place(wt.ReactorEnsemble(cols, n_zones=n))
         ens.set_boundary(bc)
         ens.set_state(pH, Cl, T, np.zeros(N))
         if how == "one call":
@@ -177,6 +189,7 @@ def test_clamps_and_a_raise_inside_an_item(gpu, wt, n):
         runs[how] = _fields(ens)
         if how == "one-step calls":
             runs[how]["bad_T"][slots["cold_run"]] = named
+        packing.check(ens)
         ens.close()
     for name, bit in CLAMP_CASES.items():
         assert first_status[slots[name]] & bit, (name, first_status[slots[name]])
@@ -193,7 +206,7 @@ def test_clamps_and_a_raise_inside_an_item(gpu, wt, n):
     _assert_same(one, runs["one-step calls"], "one call / one-step calls")
 
 
-def test_clamp_fixtures_keep_their_counters_inside_an_item(gpu, wt):
+def test_clamp_fixtures_keep_their_counters_inside_an_item(gpu, wt, packing):
     """The g11 clamp cases from the reference's own pre-step state, in a wavefront with ordinary reactors: the items of
     1, 2 and 3 steps end on the fixture's recorded steps 0, 1 and 2.  Counters and status bits are the fixture's, the
     state within the bounds of test_branch_fixtures_vs_reference, the derived arrays within ten times those (the bound
@@ -202,11 +215,12 @@ def test_clamp_fixtures_keep_their_counters_inside_an_item(gpu, wt):
     n, N = 4, 16
     cols, bc, pH, Cl, T, slots = _rare_group(wt, n, N, cold_T=20.0)
     for k in (1, 2, 3):
-        ens = wt.ReactorEnsemble(cols, n_zones=n)
+        ens = packing.place(wt.ReactorEnsemble(cols, n_zones=n))
         ens.set_boundary(bc)
         ens.set_state(pH, Cl, T, np.zeros(N))
         es = ens.step(1.0, n_steps=k)
         stats = ens.solver_stats()
+        packing.check(ens)
         ens.close()
         for name, bit in CLAMP_CASES.items():
             c, s = branch_case(wt, name), slots[name]
@@ -223,7 +237,7 @@ def test_clamp_fixtures_keep_their_counters_inside_an_item(gpu, wt):
             assert es.time[s] == c["time"][k - 1]
 
 
-def test_cold_run_raises_inside_an_item_like_the_reference(gpu, wt):
+def test_cold_run_raises_inside_an_item_like_the_reference(gpu, wt, packing):
     """g4's cold run from its initial state in a wavefront with ordinary reactors, four items of 9 steps: the reference
     raises in step 34, the eighth step of the fourth item, out of f(y_new) of an accepted step -- the raise at the
     accept where that step ends the outer step.  Status, time, the state before the raise and the named temperature
@@ -232,12 +246,13 @@ def test_cold_run_raises_inside_an_item_like_the_reference(gpu, wt):
     n, N = 4, 16
     cols, bc, pH, Cl, T, slots = _rare_group(wt, n, N, cold_T=g["config"]["temperature"])
     s = slots["cold_run"]
-    ens = wt.ReactorEnsemble(cols, n_zones=n)
+    ens = packing.place(wt.ReactorEnsemble(cols, n_zones=n))
     ens.set_boundary(bc)
     ens.set_state(pH, Cl, T, np.zeros(N))
     for _ in range(4):
         es = ens.step(1.0, n_steps=9)
     bad_T = ens.bad_temperature()[s]
+    packing.check(ens)
     ens.close()
     assert g["raise_step_index"] == 34
     assert es.status[s] == ST_T_RANGE and es.time[s] == g["time_before_raise"]
@@ -253,8 +268,8 @@ def test_cold_run_raises_inside_an_item_like_the_reference(gpu, wt):
 
 
 # ---------------------------------------------------------------- a boundary reload after every step
-@pytest.mark.parametrize("n", NS)
-def test_boundary_reload_every_step(gpu, wt, n):
+@both_packings("n", NS)
+def test_boundary_reload_every_step(gpu, wt, packing, n):
     """Plant I/O with a PLC scan after every outer step, 24 reactors, 8 steps: every scan reloads the boundary, so no f
     is ever carried and every step begins with its own f(y0).  One call with a scan per step against one-step calls
     (a scan per launch): state with the derived arrays, status, counters, sensor readings and register image, bit for
@@ -263,7 +278,7 @@ def test_boundary_reload_every_step(gpu, wt, n):
     cols, bc = wt.make_ensemble(N)
     got = {}
     for how in ("one call", "one-step calls"):
-        ens = wt.ReactorEnsemble(cols, n_zones=n)
+        ens = packing.place(wt.ReactorEnsemble(cols, n_zones=n))
         ens.set_boundary(bc)
         ens.enable_sensors(seed=11)
         ens.enable_plant_io()
@@ -279,6 +294,7 @@ def test_boundary_reload_every_step(gpu, wt, n):
         f.update({f"image{i}": a for i, a in enumerate(ens.input_image())})
         f["boundary"] = ens.boundary()
         got[how] = f
+        packing.check(ens)
         ens.close()
     assert np.all(got["one call"]["time"] == K)
     assert np.allclose(got["one call"]["boundary"][[4, 6, 0]], np.array([[0.4], [0.2], [5.5]]))   # the command path ran
@@ -286,20 +302,22 @@ def test_boundary_reload_every_step(gpu, wt, n):
 
 
 # ---------------------------------------------------------------- reactors that lag their wavefront
-@pytest.mark.parametrize("n", NS)
-def test_lagging_reactors_in_one_wavefront(gpu, wt, n):
-    """One wavefront-group under an attempt limit of 2: a reactor that needs a third internal step fails its outer
+@both_packings("n", NS)
+def test_lagging_reactors_in_one_wavefront(gpu, wt, packing, n):
+    """Packed, one wavefront-group (spread, 64 // n wavefronts of one reactor, where nothing meets anything) under an
+    attempt limit of 2: a reactor that needs a third internal step fails its outer
     step and begins the next a trip behind its neighbours, so pending points meet other reactors' stage points, and
     evaluations ahead of the first trip meet reactors that carry their f.  9 steps in one call; every reactor equals,
     bit for bit, the same reactor stepped in an ensemble of its own."""
     R, K = 64 // n, 9
     cols, bc = wt.make_ensemble(R, seed=97)
-    ens = wt.ReactorEnsemble(cols, n_zones=n)
+    ens = packing.place(wt.ReactorEnsemble(cols, n_zones=n))
     assert ens.n_reactors == R
     ens.set_boundary(bc)
     ens.set_step_limit(2)
     ens.step(1.0, n_steps=K, download=False)
     got = _fields(ens)
+    packing.check(ens)
     ens.close()
     flagged = (got["status"] & ST_STEP_LIMIT) != 0
     if R >= 8:

@@ -2,10 +2,14 @@
 probe f(y0 + h0 f0) and the probe's epilogue run once per outer step behind f(y0), the lanes enter the loop in PH_NEWTON
 with their stage values preset, and the loop's single-point site serves PH_ERR_REFINE and PH_FNEW alone.  None of it may
 move a bit or a counter.  Every test runs at every instantiation of the step kernel, on three wavefront-groups' worth of
-synthetic reactors less a few: the last group is partly filled, so absent segments sit beside live ones."""
+synthetic reactors less a few, once spread and once packed (the ``packing`` fixture).  Packed (WT_FULL_WAVES, identity
+placement, group count asserted) these are two full wavefronts and a partly filled one, so absent segments sit beside
+live ones and lanes in different phases share a wavefront; spread, the library deals an ensemble this small one reactor
+to a wavefront on an MI355X and no reactor has a neighbour."""
 import numpy as np
 import pytest
 
+from program_helpers import both_packings, packing  # noqa: F401  (a fixture: every multi-reactor test runs spread and packed)
 from test_gpu_pending_f import ST_T_RANGE, _assert_same, _fields, _rare_group
 
 pytestmark = pytest.mark.gpu
@@ -20,8 +24,12 @@ def _population(n):
     return 3 * R - max(1, R // 3) if R > 1 else 3
 
 
-def _run(wt, n, cols, bc, how, steps=K, state=None, identity=False, dt=1.0):
+def _run(wt, n, cols, bc, how, steps=K, state=None, identity=False, dt=1.0, packing=None):
+    """`packing`: the fixture's, for a run that is to have it (asserted after the last step); None for a reactor run
+    alone."""
     ens = wt.ReactorEnsemble(cols, n_zones=n)
+    if packing is not None:
+        packing.place(ens)
     ens.set_boundary(bc)
     if state is not None:
         ens.set_state(*state)
@@ -35,19 +43,21 @@ def _run(wt, n, cols, bc, how, steps=K, state=None, identity=False, dt=1.0):
             ens.set_schedule(1, 5)
         ens.step(dt, n_steps=steps, download=False)
     f = _fields(ens)
+    if packing is not None:
+        packing.check(ens)
     ens.close()
     return f
 
 
 # ---------------------------------------------------------------- 1. the schedule moves no bit
-@pytest.mark.parametrize("n", NS)
-def test_results_do_not_depend_on_the_schedule(gpu, wt, n):
+@both_packings("n", NS)
+def test_results_do_not_depend_on_the_schedule(gpu, wt, packing, n):
     """12 one-step calls (every step begins with f(y0) from memory), one 12-step call (f carried where a step ended in
     PH_FNEW, evaluated ahead of the loop elsewhere) and the stream schedule with launches of 5 steps: state with the
     derived arrays, status and the per-reactor solver counters, bit for bit."""
     N = _population(n)
     cols, bc = wt.make_ensemble(N)
-    got = {how: _run(wt, n, cols, bc, how) for how in ("one call", "one-step calls", "stream")}
+    got = {how: _run(wt, n, cols, bc, how, packing=packing) for how in ("one call", "one-step calls", "stream")}
     assert not got["one call"]["status"].any() and np.all(got["one call"]["time"] == K)
     _assert_same(got["one call"], got["one-step calls"], "one call / one-step calls")
     _assert_same(got["one call"], got["stream"], "one call / stream schedule")
@@ -80,15 +90,15 @@ def _oracle_counters(wt, oracle, n, start=0, dt=1.0):
     return _ORACLE[n, start, dt]
 
 
-@pytest.mark.parametrize("n", NS)
-def test_counters_of_every_step_of_an_item_vs_oracle(gpu, wt, oracle, n):
+@both_packings("n", NS)
+def test_counters_of_every_step_of_an_item_vs_oracle(gpu, wt, oracle, packing, n):
     """A call stores the counters of its last outer step, so step k of a 12-step item is read from an item of k steps
     from the same start.  nfev is where a miscount of the preamble would show: f(y0) (evaluated or carried), the probe
     and the three stage values that the first Newton iteration takes from f(y0) are counted ahead of the loop."""
     N = _population(n)
     cols, bc = wt.make_ensemble(N)
     ref = _oracle_counters(wt, oracle, n)
-    ens = wt.ReactorEnsemble(cols, n_zones=n)
+    ens = packing.place(wt.ReactorEnsemble(cols, n_zones=n))
     ens.set_boundary(bc)
     s0 = ens.state
     for k in range(1, K + 1):
@@ -97,11 +107,12 @@ def test_counters_of_every_step_of_an_item_vs_oracle(gpu, wt, oracle, n):
         assert not es.status.any()
         got = ens.solver_stats()
         assert np.array_equal(got, ref[k - 1]), (n, k, np.argwhere(got != ref[k - 1])[:4].tolist())
+    packing.check(ens)
     ens.close()
 
 
-@pytest.mark.parametrize("n", NS)
-def test_lanes_that_carry_f_beside_lanes_that_do_not(gpu, wt, oracle, n):
+@both_packings("n", NS)
+def test_lanes_that_carry_f_beside_lanes_that_do_not(gpu, wt, oracle, packing, n):
     """A reactor whose outer step takes a second Jacobian (njev > 1 in the oracle's counters) went through PH_FNEW, and
     where the refresh came with the step's last accept it carries f into the next outer step while its neighbours
     evaluate theirs ahead of the loop.  Such steps are found on the CPU: the synthetic population is scanned window by
@@ -122,7 +133,7 @@ def test_lanes_that_carry_f_beside_lanes_that_do_not(gpu, wt, oracle, n):
     print(f"n={n}: dt {dt}, window at {start}: {len(carry)} outer steps with a Jacobian refresh, in {len(lanes)} of {N} reactors")
     assert len(lanes) >= 1
     cols, bc = wt.make_ensemble(N, start=start)
-    got = _run(wt, n, cols, bc, "one call", identity=True, dt=dt)
+    got = _run(wt, n, cols, bc, "one call", identity=True, dt=dt, packing=packing)
     assert not got["status"].any()
     assert np.array_equal(got["stats"], ref[K - 1])
     for r in lanes[:8]:
@@ -178,8 +189,8 @@ def _cold_T_for_a_probe_raise_in_step_3(wt, oracle, n, N):
 
 
 @pytest.mark.parametrize("where", ["f(y0)", "probe", "probe in step 3", "inside the item"])
-@pytest.mark.parametrize("n", NS)
-def test_raises_in_the_preamble(gpu, wt, oracle, n, where):
+@both_packings("n", NS)
+def test_raises_in_the_preamble(gpu, wt, oracle, packing, n, where):
     """g4's cold run (a reactor that loses heat) beside the g11 clamp cases and ordinary reactors, a 6-step item against
     one-step calls: status bits, the frozen state, the temperature the message names and the untouched neighbours, bit
     for bit.  `f(y0)`: a zone below 0 degC when the item begins, so the evaluation ahead of the loop raises (stage 1)
@@ -201,9 +212,9 @@ def test_raises_in_the_preamble(gpu, wt, oracle, n, where):
     s = slots["cold_run"]
     state = (pH, Cl, T, np.zeros(N))
     steps = 6
-    one = _run(wt, n, cols, bc, "one call", steps=steps, state=state)
+    one = _run(wt, n, cols, bc, "one call", steps=steps, state=state, packing=packing)
     # one-step calls, reading which call raised and what it named (later calls leave a frozen reactor alone)
-    ens = wt.ReactorEnsemble(cols, n_zones=n)
+    ens = packing.place(wt.ReactorEnsemble(cols, n_zones=n))
     ens.set_boundary(bc)
     ens.set_state(*state)
     raised_at, named, stats_at = None, None, None
@@ -212,6 +223,7 @@ def test_raises_in_the_preamble(gpu, wt, oracle, n, where):
         if raised_at is None and ens.status()[s] & ST_T_RANGE:
             raised_at, named, stats_at = k, ens.bad_temperature()[s], ens.solver_stats()[s].copy()
     ref = _fields(ens)
+    packing.check(ens)
     ens.close()
     assert raised_at is not None
     ref["bad_T"][s] = named
@@ -239,15 +251,15 @@ def test_raises_in_the_preamble(gpu, wt, oracle, n, where):
 
 
 # ---------------------------------------------------------------- 5. a boundary reload after every step
-@pytest.mark.parametrize("n", NS)
-def test_boundary_reload_after_every_step(gpu, wt, n):
+@both_packings("n", NS)
+def test_boundary_reload_after_every_step(gpu, wt, packing, n):
     """Plant I/O with a scan per step over 8 steps: every scan reloads the boundary, so no step carries f and every
     preamble begins with its own f(y0).  One call against one-step calls, bit for bit, readings and image included."""
     N, steps = _population(n), 8
     cols, bc = wt.make_ensemble(N)
     got = {}
     for how in ("one call", "one-step calls"):
-        ens = wt.ReactorEnsemble(cols, n_zones=n)
+        ens = packing.place(wt.ReactorEnsemble(cols, n_zones=n))
         ens.set_boundary(bc)
         ens.enable_sensors(seed=11)
         ens.enable_plant_io()
@@ -262,6 +274,7 @@ def test_boundary_reload_after_every_step(gpu, wt, n):
         f.update({f"reading{i}": a for i, a in enumerate(ens.sensor_readings())})
         f.update({f"image{i}": a for i, a in enumerate(ens.input_image())})
         got[how] = f
+        packing.check(ens)
         ens.close()
     assert np.all(got["one call"]["time"] == steps)
     _assert_same(got["one call"], got["one-step calls"], "one call / one-step calls")
