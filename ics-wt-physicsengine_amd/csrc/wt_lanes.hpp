@@ -91,18 +91,29 @@ template <int D> __device__ __forceinline__ double x_rel(const Lane &L)
 
 // At the top level of the cyclic reduction (stride S = 2^(LV-1) >= n/2) a zone has at most ONE partner: zone z - S if
 // z >= S, else zone z + S if that exists.  ROW kernels (n = 2 S): partner = z xor S, a quad permutation (n = 2, 4), a
-// row rotation (n = 16) or two bank-masked row shifts into one register (n = 8).  Otherwise through the exchange row.
+// row rotation (n = 16) or two moves (n = 8, below).  Otherwise through the exchange row.
 template <int CTRL, int BANKS> __device__ __forceinline__ double dpp_merge(double old, double x)
 {
     const int lo = __builtin_amdgcn_update_dpp(__double2loint(old), __double2loint(x), CTRL, 0xf, BANKS, false);
     const int hi = __builtin_amdgcn_update_dpp(__double2hiint(old), __double2hiint(x), CTRL, 0xf, BANKS, false);
     return __hiloint2double(hi, lo);
 }
+// n = 8 (S = 4): z xor 4 is no single DPP control.  As two bank-masked row shifts into one register every lane of a
+// 16-lane row is written by exactly one of them (banks 1 and 3 by row_shr:4, banks 0 and 2 by row_shl:4), so the first
+// shift's `old` operand never survives -- but it has to be a register, x is still live, and the compiler copies both
+// dwords of x first: six instructions per double.  As row_half_mirror (z -> 7 - z) and then quad_perm [3,2,1,0] (3 - p
+// within the quad) it is two moves per dword with no `old` at all: four.  Which of the two an instantiation takes is
+// partner_exchange_without_copy (wt_step.hpp, with the other switches).  (A zone's partner is a lane of its own reactor,
+// in the same solver phase: active whenever the zone is, as for the one-move forms.)
+__host__ __device__ constexpr bool partner_exchange_without_copy(int LV, bool ROW);
 template <bool ROW, int S> __device__ __forceinline__ double from_partner(const Lane &L, double x)
 {
     if constexpr (ROW && S == 1) return dpp_mov<0xB1>(x);            // quad_perm [1,0,3,2]
     else if constexpr (ROW && S == 2) return dpp_mov<0x4E>(x);       // quad_perm [2,3,0,1]
-    else if constexpr (ROW && S == 4) return dpp_merge<0x104, 0x5>(dpp_merge<0x114, 0xA>(x, x), x);   // row_shr:4 -> zones 4..7, row_shl:4 -> zones 0..3
+    else if constexpr (ROW && S == 4) {
+        if constexpr (partner_exchange_without_copy(3, ROW)) return dpp_mov<0x1B>(dpp_mov<0x141>(x));   // row_half_mirror, quad_perm [3,2,1,0]
+        else return dpp_merge<0x104, 0x5>(dpp_merge<0x114, 0xA>(x, x), x);   // row_shr:4 -> zones 4..7, row_shl:4 -> zones 0..3
+    }
     else if constexpr (ROW && S == 8) return dpp_mov<0x128>(x);      // row_ror:8
     else { x_put(L, x); return keep_m(L.m_pt, x_get(L, L.a_me + ((L.z >= S) ? -8 * S : 8 * S))); }   // (S: the top stride)
 }
@@ -119,6 +130,16 @@ template <bool ROW, int S> __device__ __forceinline__ void both(const Lane &L, d
 {
     if constexpr (ROW || S == 1) { lo = from_lo<ROW, S>(L, x); hi = from_hi<ROW, S>(L, x); }
     else { x_put(L, x); lo = x_rel<-S>(L); hi = x_rel<S>(L); }
+}
+
+// A double that is defined without an instruction, its value irrelevant (Held::init's idiom): for a variable that is
+// assigned on some paths only and read on those alone, so that the compiler does not carry its last contents along the
+// others (run_item's stage points and values).
+__device__ __forceinline__ double undefined_f64()
+{
+    int lo, hi;
+    asm("" : "=v"(lo)); asm("" : "=v"(hi));
+    return __hiloint2double(hi, lo);
 }
 
 __device__ __forceinline__ bool seg_any(const Lane &L, bool p) { return (__ballot(p) & L.segmask) != 0ull; }

@@ -205,6 +205,16 @@ __host__ __device__ constexpr bool single_point_fence_is_barrier(int LV, bool /*
 // section, as the other sections do) with their roundings spelled out, and not as fp64 literals.
 __host__ __device__ constexpr bool loaded_constants_in_estimate_and_accept(int LV, bool /*ROW*/) { return LV <= 5; }
 
+// Data movement that computes nothing, one switch per piece; off is the code as it stood, same results.
+// Whether the n = 8 partner exchange of the top cyclic-reduction level is the two-move form that needs no copy of its
+// operand (from_partner<true, 4>, wt_lanes.hpp).  Only <3, true> has that exchange.
+__host__ __device__ constexpr bool partner_exchange_without_copy(int /*LV*/, bool /*ROW*/) { return true; }
+// Whether a trip's stage points and stage values (ye, Fe) are defined afresh where the trip declares them.  They are
+// assigned on three paths; for a lane that takes none of them the compiler otherwise keeps the trip before's contents,
+// which no lane ever reads, and carries them round the loop's back edge through accumulation registers (in <3, true>
+// 36 + 41 v_accvgpr moves a trip and 30 registers; the n > 32 kernel has its 60 B of scratch for them).
+__host__ __device__ constexpr bool stage_values_fresh_each_trip(int /*LV*/, bool /*ROW*/) { return true; }
+
 // One work item: the reactors of wavefront-group `group` advanced by `cnt` outer steps, starting with step `step0`
 // of this launch.  Reactors of a wavefront start every outer step together (they wait for the slowest of them), so
 // their Jacobians, factorisations and Newton trips coincide, and the end of an outer step is a wave-uniform point
@@ -243,7 +253,8 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
                    PEND_IN_BLOCK = pending_f_in_stage_block(LV, ROW), DERIVE_ONCE = derived_once_per_item(LV, ROW),
                    HAND_BASE = BEGIN_AHEAD && base_properties_handed_to_num_jac(LV, ROW), LEAN_LAST_ACCEPT = lean_last_accept(LV, ROW),
                    LOADED_EA = loaded_constants_in_estimate_and_accept(LV, ROW), FIRST_IN_PROBE = first_attempt_in_probe_trip(LV, ROW), BAR1 = single_point_fence_is_barrier(LV, ROW),
-                   PRE_AHEAD = BEGIN_AHEAD && FIRST_IN_PROBE && solver_preamble_ahead_of_loop(LV, ROW);
+                   PRE_AHEAD = BEGIN_AHEAD && FIRST_IN_PROBE && solver_preamble_ahead_of_loop(LV, ROW),
+                   FRESH_STAGES = stage_values_fresh_each_trip(LV, ROW);
     int steps_done = 0, reads_done = 0, cost_acc = 0;
     SolverCounters last_cnt = {0, 0, 0, 0, 0};
     int diag_trips = 0, diag_newton = 0;              // per item: 32 bits are plenty
@@ -578,6 +589,12 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
                 const bool eval3 = newton && pend_f;
                 constexpr int NPT = PEND_IN_BLOCK ? 4 : 3;   // the stage block's points: the three stages, then the pending point
                 double ye[NPT][3], Fe[NPT][3];
+                if constexpr (FRESH_STAGES) {
+#pragma unroll
+                    for (int s = 0; s < NPT; ++s)
+#pragma unroll
+                        for (int q = 0; q < 3; ++q) { ye[s][q] = undefined_f64(); Fe[s][q] = undefined_f64(); }
+                }
                 if constexpr (!PRE_AHEAD) {
 #pragma unroll
                     for (int q = 0; q < 3; ++q) {
