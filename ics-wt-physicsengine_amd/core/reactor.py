@@ -18,8 +18,8 @@ from typing import Dict, Iterable, List, Optional, Sequence, Union
 
 import numpy as np
 
-from . import (_native, _program, actuator, alarm, control, detect, disturb, inject, install, junction, params, score, service,
-               train, trend, tune, wire)
+from . import (_native, _program, actuator, alarm, control, detect, disturb, inject, install, junction, mpc, params, score,
+               service, train, trend, tune, wire)
 
 logger = logging.getLogger(__name__)
 
@@ -703,6 +703,47 @@ class ReactorEnsemble:
     def clear_tuners(self) -> None:
         """Stop the tune program; the holding registers and commissioned gains stay as they are."""
         self._program_call(_native.lib().wt_ensemble_tune_clear)
+
+    # -- model predictive controllers at the PLC scans, between tune and PI programs, on the device (wt_mpc.hpp)
+    def set_mpc(self, chlorine: Optional["mpc.DMCLoop"] = None, acid: Optional["mpc.DMCLoop"] = None) -> None:
+        """Run up to two dynamic matrix controllers per reactor at the PLC scans, inside the step call: ``chlorine``
+        owns the chlorine_flow_rate holding register from its ``t_start`` on, ``acid`` the acid_flow_rate one, and the PI
+        loop of that register is skipped meanwhile; a relay experiment (:meth:`set_tuners`) still takes the loop while
+        it runs.  Replaces any controllers and resets state and prediction.  Needs :meth:`enable_plant_io` and at most
+        32 zones per reactor."""
+        blocks = mpc.mpc_block(self.n_reactors, chlorine, acid)
+        self._program_call(_native.lib().wt_ensemble_mpc_set, *(_native.dptr(b) for b in blocks))
+
+    def mpc_state(self) -> "mpc.MpcState":
+        """Phase, output, bias, last move, metrics and counts of both controllers by reactor (one synchronisation)."""
+        blk = np.empty((len(control.LOOPS), mpc.NMS, self.n_reactors), dtype=np.float64)
+        self._program_call(_native.lib().wt_ensemble_mpc_get, _native.dptr(blk))
+        return mpc.MpcState.from_block(blk)
+
+    def mpc_prediction(self) -> np.ndarray:
+        """The (2, 64, N) predictions: entry i is the reading a controller expects i of its periods after its last
+        execution if the output stays where it is."""
+        blk = np.empty((len(control.LOOPS), mpc.H, self.n_reactors), dtype=np.float64)
+        self._program_call(_native.lib().wt_ensemble_mpc_prediction, _native.dptr(blk))
+        return blk
+
+    def mpc_params(self):
+        """The (2, 10, N) parameter block and the (2, 64, N) step and gain blocks of the controllers in force, as
+        :func:`mpc_block` built them."""
+        n = self.n_reactors
+        blocks = (np.empty((len(control.LOOPS), mpc.NM, n)), np.empty((len(control.LOOPS), mpc.H, n)),
+                  np.empty((len(control.LOOPS), mpc.H, n)))
+        self._program_call(_native.lib().wt_ensemble_mpc_params, *(_native.dptr(b) for b in blocks))
+        return blocks
+
+    def reset_mpc(self) -> None:
+        """Every controller waiting again, state and prediction zeroed: it starts afresh from ``u0`` at the next due
+        scan with a valid reading.  The holding registers stay as they are."""
+        self._program_call(_native.lib().wt_ensemble_mpc_reset)
+
+    def clear_mpc(self) -> None:
+        """Stop the controllers; the holding registers stay as they are and the PI programs resume."""
+        self._program_call(_native.lib().wt_ensemble_mpc_clear)
 
     # -- injection programs at every PLC scan, on the device (wt_inj.hpp)
     def set_injections(self, *injections: "inject.Injection") -> None:

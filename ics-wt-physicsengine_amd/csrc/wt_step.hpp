@@ -1050,6 +1050,16 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
                     owned = wtu::tune_execute(up->tun, up->ctl, rr, &io.val[0][lane], &io.fault[0][lane], wts::RMAX, up->sens.pack.loop_time[rr]);
                   }
                 }
+                // the model predictive controllers (wave-uniform flag), between the tune program and the PLC program and
+                // with their inputs.  The whole wavefront enters: a scan lane decides, all 64 lanes carry the reactor's
+                // prediction (wt_mpc.hpp).  A controller owns its loop's holding words as a relay experiment does.
+                if constexpr (prog_in_item(LV)) {
+                  if (scan && WT_RARE(fresh(pa)->mpc.on)) {
+                    ArgPtr mp = fresh(pa);
+                    owned |= wtm::mpc_execute(mp->mpc, mp->ctl, lane < R && io.stepped[lane], lane, rix, &io.val[0][0], &io.fault[0][0],
+                                              wts::RMAX, mp->sens.pack.loop_time, owned);
+                  }
+                }
                 // the PLC program, after the scan's command path: its commands act from the next scan on, like a host
                 // master's between two calls; t_now is the loop time just stored
                 if (scan && WT_RARE(fresh(pa)->ctl.on) && lane < R && io.stepped[lane]) {

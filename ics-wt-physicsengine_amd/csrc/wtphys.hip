@@ -126,6 +126,8 @@ struct wt_ensemble {
     wtu::TunArgs tun = {};
     // The installation records of the sensor suite (wt_ins.hpp; not one of k_programs): the suite's arrays and a SENS scalar.
     wtin::InsArgs ins = {};
+    // The model predictive controllers (wt_mpc.hpp; not programs of k_programs either): plant I/O's arrays and a PLIO scalar.
+    wtm::MpcArgs mpc = {};
     // optional per-launch HIP-event timing (bench.py roofline accounting)
     bool time_launches = false;
     std::vector<hipEvent_t> lt_pool;   // start/stop pairs
@@ -163,7 +165,7 @@ wt::StepArgs make_args(const wt_ensemble *h, double dt, int n_steps, int first_s
     a.trace = h->trace; a.trace_cap = h->trace_cap;
     a.kt = wt::default_ktab(); a.rt = wt::default_rtab();
     a.kt.dense_bias = h->knob_dense ? 1.0 : 0.0;
-    a.sens = h->sens; a.ctl = h->ctl; a.inj = h->inj; a.alm = h->alm; a.act = h->act; a.dst = h->dst; a.scr = h->scr; a.det = h->det; a.trd = h->trd; a.trn = h->trn; a.wir = h->wir; a.tun = h->tun; a.ins = h->ins;
+    a.sens = h->sens; a.ctl = h->ctl; a.inj = h->inj; a.alm = h->alm; a.act = h->act; a.dst = h->dst; a.scr = h->scr; a.det = h->det; a.trd = h->trd; a.trn = h->trn; a.wir = h->wir; a.tun = h->tun; a.ins = h->ins; a.mpc = h->mpc;
     // a full curve takes no more entries: the launches then carry no curve pointer at all
     const bool curve = h->scr.counts && h->scr_steps < h->scr.curve_cap;
     if (!curve) a.scr.counts = nullptr;
@@ -255,7 +257,7 @@ ArrayGroup sensor_arrays(wt_ensemble *h)
             [h] { h->sens.hist_cap = 0; h->sens.svc_on = 0; h->ins.on = 0; }};
 }
 
-// the tune program's records (wt_tun.hpp) come and go with plant I/O
+// the tune program's records (wt_tun.hpp) and the model predictive controllers' arrays (wt_mpc.hpp) come and go with plant I/O
 ArrayGroup plant_io_arrays(wt_ensemble *h)
 {
     const size_t N = (size_t)h->N;
@@ -264,8 +266,13 @@ ArrayGroup plant_io_arrays(wt_ensemble *h)
                                             {(void **)&h->sens.pack.loop_time, sizeof(double) * N},
                                             {(void **)&h->sens.pack.update_ok, N},
                                             {(void **)&h->tun.par, sizeof(double) * wtu::PAR_DOUBLES * N},
-                                            {(void **)&h->tun.st, sizeof(double) * wtu::ST_DOUBLES * N}},
-            [h] { h->tun.on = 0; }};
+                                            {(void **)&h->tun.st, sizeof(double) * wtu::ST_DOUBLES * N},
+                                            {(void **)&h->mpc.par, sizeof(double) * wtm::PAR_DOUBLES * N},
+                                            {(void **)&h->mpc.st, sizeof(double) * wtm::ST_DOUBLES * N},
+                                            {(void **)&h->mpc.step, sizeof(double) * wtm::ROW_DOUBLES * N},
+                                            {(void **)&h->mpc.gain, sizeof(double) * wtm::ROW_DOUBLES * N},
+                                            {(void **)&h->mpc.pred, sizeof(double) * wtm::ROW_DOUBLES * N}},
+            [h] { h->tun.on = 0; h->mpc.on = 0; }};
 }
 
 ArrayGroup record_arrays(wt_ensemble *h)
@@ -1175,10 +1182,17 @@ int wt_ensemble_plc_enable(wt_ensemble *h)
     // the tune program's records, off: no loop enabled, no state (a checkpoint holds them whether or not one is set)
     if (e == hipSuccess) e = hipMemsetAsync((void *)h->tun.par, 0, sizeof(double) * wtu::PAR_DOUBLES * N, h->stream);
     if (e == hipSuccess) e = hipMemsetAsync(h->tun.st, 0, sizeof(double) * wtu::ST_DOUBLES * N, h->stream);
+    // the model predictive controllers' arrays likewise
+    if (e == hipSuccess) e = hipMemsetAsync((void *)h->mpc.par, 0, sizeof(double) * wtm::PAR_DOUBLES * N, h->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(h->mpc.st, 0, sizeof(double) * wtm::ST_DOUBLES * N, h->stream);
+    if (e == hipSuccess) e = hipMemsetAsync((void *)h->mpc.step, 0, sizeof(double) * wtm::ROW_DOUBLES * N, h->stream);
+    if (e == hipSuccess) e = hipMemsetAsync((void *)h->mpc.gain, 0, sizeof(double) * wtm::ROW_DOUBLES * N, h->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(h->mpc.pred, 0, sizeof(double) * wtm::ROW_DOUBLES * N, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) { release(arrays); return fail(WT_E_HIP, std::string("plc_enable: ") + hipGetErrorString(e)); }
     h->sens.cmd.hr = h->ctl.hr;
     h->tun.on = 0;                               // freshly enabled plant I/O has no tune program
+    h->mpc.on = 0;                               // and no model predictive controller
     h->sens.plc_on = 1;
     return WT_OK;
 }
@@ -2070,7 +2084,7 @@ const Part k_parts[] = {
                             {S_U32, &h->sens.seed_hi, false}, {S_I64, &h->sens.reactor_base, false},
                             {S_I32, &h->sens.svc_on, false}, {S_I32, &h->ins.on, false}}); }, nullptr},   // (the service program's arrays and the installation records are the suite's)
     {"PLIO", plant_io_arrays, 0, [](wt_ensemble *h, Scalars &s) {
-         s.insert(s.end(), {{S_I32, &h->sens.plc_on, true}, {S_I32, &h->tun.on, false}}); }, nullptr},   // (the tune program's arrays are plant I/O's)
+         s.insert(s.end(), {{S_I32, &h->sens.plc_on, true}, {S_I32, &h->tun.on, false}, {S_I32, &h->mpc.on, false}}); }, nullptr},   // (the tune program's and the model predictive controllers' arrays are plant I/O's)
     {"RECD", record_arrays, 0, [](wt_ensemble *h, Scalars &s) {
          s.insert(s.end(), {{S_I32, &h->rec.every, false}, {S_I32, &h->rec.cap, true}, {S_I64, &h->rec.steps, false}}); },
      [](const wt_ensemble *h) { return h->rec.cap > 0; }},
@@ -2226,7 +2240,7 @@ const char *config_error(wt_ensemble *u)
     const auto flag = [](int v) { return v == 0 || v == 1; };
     if (!flag(u->sens.on) || !flag(u->sens.plc_on) || !flag(u->ctl.on) || !flag(u->inj.on) || !flag(u->alm.on) || !flag(u->act.on) ||
         !flag(u->dst.on) || !flag(u->scr.on) || !flag(u->det.on) || !flag(u->trn.on) || !flag(u->trn.pipe.on) || !flag(u->trn.jct.on) || !flag(u->wir.on) ||
-        !flag(u->sens.svc_on) || !flag(u->ins.on) || !flag(u->tun.on) || !flag(u->trd.on) || !flag(u->trd.wrap))
+        !flag(u->sens.svc_on) || !flag(u->ins.on) || !flag(u->tun.on) || !flag(u->mpc.on) || !flag(u->trd.on) || !flag(u->trd.wrap))
         return "range";
     if (u->placement != WT_PLACE_IDENTITY && u->placement != WT_PLACE_ADAPTIVE) return "range";
     if (u->sched_mode != WT_SCHED_STREAMS && u->sched_mode != WT_SCHED_QUEUE) return "range";
@@ -2244,6 +2258,7 @@ const char *config_error(wt_ensemble *u)
     if (u->sens.svc_on && (!u->sens.on || !wt::prog_in_item(levels_for(u->n)))) return "range";
     if (u->ins.on && !u->sens.on) return "range";
     if (u->tun.on && (!u->sens.plc_on || !wt::prog_in_item(levels_for(u->n)))) return "range";
+    if (u->mpc.on && (!u->sens.plc_on || !wt::prog_in_item(levels_for(u->n)))) return "range";
     return nullptr;
 }
 
@@ -2974,6 +2989,135 @@ int wt_ensemble_tune_params(wt_ensemble *h, double *params) { return wt_ensemble
 int wt_ensemble_tune_reset(wt_ensemble *h) { return reset_program(h, WT_PROG_TUNE); }
 int wt_ensemble_tune_clear(wt_ensemble *h) { return stop_program(h, WT_PROG_TUNE); }
 
+// ---- model predictive control (wt_mpc.hpp): not a program of k_programs (three blocks, a prediction of
+// its own); its arrays are plant I/O's, as the tune program's are
+
+static_assert(WT_MPC_LOOPS == wtm::LOOPS && WT_NM == wtm::NM && WT_NMS == wtm::NMS && WT_MPC_H == wtm::H &&
+              WT_MPC_ENABLE == wtm::M_ENABLE && WT_MPC_SENSOR == wtm::M_SENSOR && WT_MPC_SETPOINT == wtm::M_SETPOINT &&
+              WT_MPC_EVERY == wtm::M_EVERY && WT_MPC_HORIZON == wtm::M_HORIZON && WT_MPC_U0 == wtm::M_U0 &&
+              WT_MPC_OUT_MIN == wtm::M_OUT_MIN && WT_MPC_OUT_MAX == wtm::M_OUT_MAX && WT_MPC_DU_MAX == wtm::M_DU_MAX &&
+              WT_MPC_T_START == wtm::M_T_START && WT_MPCS_PHASE == wtm::MS_PHASE && WT_MPCS_OUTPUT == wtm::MS_OUTPUT &&
+              WT_MPCS_COUNT == wtm::MS_COUNT && WT_MPCS_BIAS == wtm::MS_BIAS && WT_MPCS_MOVE == wtm::MS_MOVE &&
+              WT_MPCS_T_EXEC == wtm::MS_T_EXEC && WT_MPCS_ISE == wtm::MS_ISE && WT_MPCS_IAE == wtm::MS_IAE &&
+              WT_MPCS_DOSE == wtm::MS_DOSE && WT_MPCS_N_EXEC == wtm::MS_N_EXEC && WT_MPCS_N_HELD == wtm::MS_N_HELD &&
+              WT_MPCS_N_SAT == wtm::MS_N_SAT && WT_MPCS_N_RATE == wtm::MS_N_RATE && WT_MPCS_N_SKIPPED == wtm::MS_N_SKIPPED &&
+              WT_MPC_WAITING == wtm::PH_WAITING && WT_MPC_RUNNING == wtm::PH_RUNNING && WT_INFO_MPC == 25, "model predictive control blocks of the C ABI");
+
+static const char *const k_mpc_not_set = "no model predictive controller is set (wt_ensemble_mpc_set)";
+
+// The first refusal of the three blocks, loop by loop over the reactors and at one loop of one reactor rule by rule in the
+// header's order; empty: none.
+static std::string mpc_error(int64_t N, const double *p, const double *step, const double *gain)
+{
+    for (int l = 0; l < WT_MPC_LOOPS; ++l)
+        for (int64_t r = 0; r < N; ++r) {
+            const auto at = [&](int k) { return p[((int64_t)l * WT_NM + k) * N + r]; };
+            const auto row = [&](const double *b, int i) { return b[((int64_t)l * WT_MPC_H + i) * N + r]; };
+            const auto rule = [&]() -> const char * {
+                if (!whole_in(at(WT_MPC_ENABLE), 0, 1)) return "enable must be 0 or 1";
+                if (!whole_in(at(WT_MPC_SENSOR), 0, WT_N_SENSORS - 1)) return "sensor must be an integer in 0..6";
+                if (!whole_in(at(WT_MPC_EVERY), 1, 9007199254740991.0)) return "every must be a whole number >= 1";
+                if (!whole_in(at(WT_MPC_HORIZON), 1, WT_MPC_H)) return "horizon must be an integer in 1..64";
+                if (!(std::isfinite(at(WT_MPC_SETPOINT)) && std::isfinite(at(WT_MPC_U0)))) return "setpoint and u0 must be finite";
+                if (!(std::isfinite(at(WT_MPC_OUT_MIN)) && std::isfinite(at(WT_MPC_OUT_MAX)) && at(WT_MPC_OUT_MIN) <= at(WT_MPC_OUT_MAX)))
+                    return "out_min and out_max must be finite and out_min <= out_max";
+                if (!(at(WT_MPC_DU_MAX) > 0.0)) return "du_max must be > 0 (+inf: no limit)";
+                if (std::isnan(at(WT_MPC_T_START))) return "t_start must not be NaN";
+                if (at(WT_MPC_ENABLE) == 0.0) return nullptr;      // the model of a loop that is off is not read
+                for (int i = 0; i < WT_MPC_H; ++i)
+                    if (!(std::isfinite(row(step, i)) && std::isfinite(row(gain, i)))) return "step and gain must be finite";
+                bool any = false;
+                for (int i = 0; i < (int)at(WT_MPC_HORIZON); ++i) any = any || row(gain, i) != 0.0;
+                return any ? nullptr : "gain must not be all zero over the horizon";
+            };
+            if (const char *msg = rule()) return std::string(msg) + " (loop " + std::to_string(l) + ", reactor " + std::to_string(r) + ")";
+        }
+    return std::string();
+}
+
+int wt_mpc_check(int64_t n_reactors, const double *params, const double *step, const double *gain)
+{
+    if (n_reactors < 1) return fail(WT_E_ARG, "n_reactors must be >= 1");
+    if (!params || !step || !gain) return fail(WT_E_ARG, "NULL argument");
+    const std::string msg = mpc_error(n_reactors, params, step, gain);
+    return msg.empty() ? WT_OK : fail(WT_E_ARG, msg);
+}
+
+// every controller waiting: state and prediction all 0 (the stream is idle)
+static int mpc_restart(wt_ensemble *h)
+{
+    HIP_TRY(hipMemsetAsync(h->mpc.st, 0, sizeof(double) * wtm::ST_DOUBLES * (size_t)h->N, h->stream));
+    HIP_TRY(hipMemsetAsync(h->mpc.pred, 0, sizeof(double) * wtm::ROW_DOUBLES * (size_t)h->N, h->stream));
+    return WT_OK;
+}
+
+int wt_ensemble_mpc_set(wt_ensemble *h, const double *params, const double *step, const double *gain)
+{
+    if (!h || !params || !step || !gain) return fail(WT_E_ARG, "NULL argument");
+    if (!h->sens.plc_on) return fail(WT_E_STATE, "model predictive controllers act on the plant I/O scan: enable plant I/O first");
+    if (!wt::prog_in_item(levels_for(h->n))) return fail(WT_E_STATE, "model predictive controllers run in the kernels for up to 32 zones");
+    if (int rc = wt_mpc_check(h->N, params, step, gain)) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still read or write the old records
+    const int64_t N = h->N;
+    std::vector<double> par((size_t)N * wtm::PAR_DOUBLES), sr((size_t)N * wtm::ROW_DOUBLES), gr((size_t)N * wtm::ROW_DOUBLES);
+    blocks_to_records(params, wtm::LOOPS, wtm::NM, N, par.data(), wtm::PAR_DOUBLES);
+    blocks_to_records(step, wtm::LOOPS, wtm::H, N, sr.data(), wtm::ROW_DOUBLES);
+    blocks_to_records(gain, wtm::LOOPS, wtm::H, N, gr.data(), wtm::ROW_DOUBLES);
+    int rc = upload(h, (double *)h->mpc.par, par);
+    if (rc == WT_OK) rc = upload(h, (double *)h->mpc.step, sr);
+    if (rc == WT_OK) rc = upload(h, (double *)h->mpc.gain, gr);
+    if (rc == WT_OK) rc = mpc_restart(h);
+    if (rc == WT_OK) rc = sync_checked(h);      // the host vectors are freed on return
+    h->mpc.on = rc == WT_OK ? 1 : 0;
+    return rc;
+}
+
+static int mpc_ready(wt_ensemble *h)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    if (!h->mpc.on) return fail(WT_E_STATE, k_mpc_not_set);
+    HIP_TRY(hipSetDevice(h->device));
+    return WT_OK;
+}
+
+int wt_ensemble_mpc_get(wt_ensemble *h, double *state)
+{
+    if (int rc = mpc_ready(h)) return rc;
+    return download_records(h, {{state, h->mpc.st, wtm::ST_DOUBLES, wtm::LOOPS, wtm::NMS}});
+}
+
+int wt_ensemble_mpc_prediction(wt_ensemble *h, double *pred)
+{
+    if (int rc = mpc_ready(h)) return rc;
+    return download_records(h, {{pred, h->mpc.pred, wtm::ROW_DOUBLES, wtm::LOOPS, wtm::H}});
+}
+
+int wt_ensemble_mpc_params(wt_ensemble *h, double *params, double *step, double *gain)
+{
+    if (int rc = mpc_ready(h)) return rc;
+    return download_records(h, {{params, h->mpc.par, wtm::PAR_DOUBLES, wtm::LOOPS, wtm::NM},
+                                {step, h->mpc.step, wtm::ROW_DOUBLES, wtm::LOOPS, wtm::H},
+                                {gain, h->mpc.gain, wtm::ROW_DOUBLES, wtm::LOOPS, wtm::H}});
+}
+
+int wt_ensemble_mpc_reset(wt_ensemble *h)
+{
+    if (int rc = mpc_ready(h)) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still write the records
+    if (int rc = mpc_restart(h)) return rc;
+    return sync_checked(h);
+}
+
+int wt_ensemble_mpc_clear(wt_ensemble *h)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still use the records
+    h->mpc.on = 0;
+    return WT_OK;
+}
+
 int wt_ensemble_sensors_service(wt_ensemble *h, int sensor, int action, int ref_mode, const double *ref, const double *ref2,
                                 const uint8_t *mask)
 {
@@ -3265,6 +3409,7 @@ int wt_ensemble_info(wt_ensemble *h, int what, int64_t *value)
     case WT_INFO_MARK: *value = h->mark != nullptr; break;
     case WT_INFO_JUNCTION: *value = h->trn.jct.on != 0; break;
     case WT_INFO_INSTALL: *value = h->ins.on != 0; break;
+    case WT_INFO_MPC: *value = h->mpc.on != 0; break;
     default: return fail(WT_E_ARG, "unknown info code");
     }
     return WT_OK;

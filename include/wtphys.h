@@ -288,7 +288,8 @@ enum {
     WT_INFO_JUNCTION = 21,                /* a junction program is set */
     WT_INFO_SERVICE = 22,                 /* a sensor service program is set */
     WT_INFO_TUNE = 23,                    /* a tune program is set */
-    WT_INFO_INSTALL = 24                  /* an installation is set (wt_ensemble_install_set) */
+    WT_INFO_INSTALL = 24,                 /* an installation is set (wt_ensemble_install_set) */
+    WT_INFO_MPC = 25                      /* model predictive controllers are set (wt_ensemble_mpc_set) */
 };
 int wt_ensemble_info(wt_ensemble *h, int what, int64_t *value);
 
@@ -1167,6 +1168,84 @@ int wt_ensemble_tune_reset(wt_ensemble *h);
 /* program off (no effect while none is set); holding words and commissioned gains stay */
 int wt_ensemble_tune_clear(wt_ensemble *h);
 int wt_tune_check(int64_t n_reactors, const double *params);
+
+/* ---- model predictive control: a dynamic matrix controller (DMC) per dosing loop inside fused runs ----
+ * The reference's roadmap lists an "MPC controller module"; it has none.  Two controllers per reactor, one per dosing
+ * loop, with the loop indices and holding words of the PI programs: loop 0 chlorine (words 2-3), loop 1 acid (words
+ * 0-1).  A controller carries a per-reactor step-response model and a prediction of the reading over the next WT_MPC_H
+ * = 64 controller periods, so the dead time of sample lines, pipes and wires is inside its model.  It is not a program
+ * of wt_program_check: it has calls of its own, as the installation has.
+ * Parameters [WT_MPC_LOOPS][WT_NM][N]: enable (0 or 1), sensor (0..6, WT_N_SENSORS order), setpoint, every (controller
+ * period in scans, a whole number >= 1), horizon p (a whole number in 1..64), u0 (output before the first move),
+ * out_min, out_max, du_max (largest move, > 0, +inf: none), t_start (loop time from which the controller has the loop).
+ * Model: step [WT_MPC_LOOPS][WT_MPC_H][N], entry i the change of the reading i + 1 controller periods after a unit move
+ * of the output (the sign carries the direction: an acid step response is negative), and gain
+ * [WT_MPC_LOOPS][WT_MPC_H][N], the row the predicted errors are weighted with; entries at and after p are ignored.
+ * State [WT_MPC_LOOPS][WT_NMS][N]: phase (WT_MPC_WAITING, _RUNNING), output, count, bias, move, t_exec, ise, iae, dose,
+ * n_exec, n_held, n_sat, n_rate, n_skipped; and the prediction pred [WT_MPC_LOOPS][WT_MPC_H][N]; all 0 at set and reset.
+ * One scan, for a reactor that stepped and an enabled loop with t >= t_start, after the tune program and before the PI
+ * programs and with their inputs (v = the scan's possibly tampered reading of the sensor, a float32 widened to fp64,
+ * f = its fault code, t = the loop time the scan stores), in fp64 without fused multiply-adds:
+ *   the tune program owned the loop in this scan: n_skipped += 1, nothing else.  Otherwise
+ *   the controller owns the loop: the PI program skips it in this scan (no state change, no word; its t_prev advances),
+ *   on scans that are not due as well.  The scan is due when count == 0.
+ *   due, and v not finite or f != 0: n_held += 1; if (phase == 1) pred[i] = pred[min(i + 1, 63)] for all i; no move, no
+ *   word.  due otherwise:
+ *     1. if (phase == 0) { pred[i] = v for all i; output = fmin(fmax(u0, out_min), out_max); phase = 1; }
+ *     2. d = v - pred[0];
+ *     3. s[i] = pred[min(i + 1, 63)];
+ *     4. term[i] = i < p ? gain[i] * ((setpoint - s[i]) - d) : +0.0;
+ *     5. du = the balanced-tree sum of the 64 terms: for half = 32, 16, 8, 4, 2, 1: x[i] = x[i] + x[i + half], i < half;
+ *     6. dc = fmin(fmax(du, -du_max), du_max);  if (dc != du) n_rate += 1;
+ *     7. u = output + dc;  y = fmin(fmax(u, out_min), out_max);  if (y != u) n_sat += 1;
+ *     8. move = y - output;                        (the move as applied: the anti-windup)
+ *     9. pred[i] = s[i] + step[i] * move for all 64 entries;
+ *    10. output = y;  bias = d;
+ *    11. the loop's words = float32(y) (high, low), as the PI's;
+ *    12. e = setpoint - v;  h = t - t_exec, 0 at the first execution;  ise += (e * e) * h;  iae += fabs(e) * h;
+ *        dose += y * h;  t_exec = t;  n_exec += 1.
+ *   Then, in every scan the controller owned and leaves with phase 1: count = count + 1 >= every ? 0 : count + 1.
+ *   A waiting loop (phase 0) keeps count 0: it is due at every scan until its first valid reading.
+ * Commands written act from the next scan on, like the PI's and the tuner's.  Needs plant I/O (WT_E_STATE, "model
+ * predictive controllers act on the plant I/O scan: enable plant I/O first") and n <= 32 zones ("model predictive
+ * controllers run in the kernels for up to 32 zones"); runs with or without the control and tune programs.  set
+ * replaces any controllers and zeroes state and prediction; reset zeroes them, so every controller is waiting again,
+ * and keeps the holding words; clear switches the controllers off and leaves the holding words as they are, and the PI
+ * resumes.  get, prediction, params and reset give WT_E_STATE, "no model predictive controller is set
+ * (wt_ensemble_mpc_set)", while none is.  wt_ensemble_plc_enable starts without one; checkpoints carry parameters,
+ * model, state and prediction with plant I/O.  All synchronise.
+ * wt_mpc_check is the one check of the three blocks, with no handle and no device.  Refused with WT_E_ARG, loop by loop
+ * over the reactors, at the first of the following, each followed by " (loop L, reactor R)": "enable must be 0 or 1";
+ * "sensor must be an integer in 0..6"; "every must be a whole number >= 1"; "horizon must be an integer in 1..64";
+ * "setpoint and u0 must be finite"; "out_min and out_max must be finite and out_min <= out_max"; "du_max must be > 0
+ * (+inf: no limit)"; "t_start must not be NaN"; then for an enabled loop "step and gain must be finite"; "gain must not
+ * be all zero over the horizon". */
+#define WT_MPC_LOOPS 2
+#define WT_MPC_H 64
+enum {
+    WT_MPC_ENABLE = 0, WT_MPC_SENSOR = 1, WT_MPC_SETPOINT = 2, WT_MPC_EVERY = 3, WT_MPC_HORIZON = 4, WT_MPC_U0 = 5,
+    WT_MPC_OUT_MIN = 6, WT_MPC_OUT_MAX = 7, WT_MPC_DU_MAX = 8, WT_MPC_T_START = 9,
+    WT_NM = 10
+};
+enum {
+    WT_MPCS_PHASE = 0, WT_MPCS_OUTPUT = 1, WT_MPCS_COUNT = 2, WT_MPCS_BIAS = 3, WT_MPCS_MOVE = 4, WT_MPCS_T_EXEC = 5,
+    WT_MPCS_ISE = 6, WT_MPCS_IAE = 7, WT_MPCS_DOSE = 8, WT_MPCS_N_EXEC = 9, WT_MPCS_N_HELD = 10, WT_MPCS_N_SAT = 11,
+    WT_MPCS_N_RATE = 12, WT_MPCS_N_SKIPPED = 13,
+    WT_NMS = 14
+};
+enum { WT_MPC_WAITING = 0, WT_MPC_RUNNING = 1 };
+int wt_mpc_check(int64_t n_reactors, const double *params /* [WT_MPC_LOOPS][WT_NM][N] */,
+                 const double *step /* [WT_MPC_LOOPS][WT_MPC_H][N] */, const double *gain /* [WT_MPC_LOOPS][WT_MPC_H][N] */);
+int wt_ensemble_mpc_set(wt_ensemble *h, const double *params, const double *step, const double *gain);
+/* host [WT_MPC_LOOPS][WT_NMS][N] loop state */
+int wt_ensemble_mpc_get(wt_ensemble *h, double *state);
+/* host [WT_MPC_LOOPS][WT_MPC_H][N]: entry i the reading predicted i controller periods after the last execution */
+int wt_ensemble_mpc_prediction(wt_ensemble *h, double *pred);
+/* the controllers in force as set took them; each pointer may be NULL (not wanted) */
+int wt_ensemble_mpc_params(wt_ensemble *h, double *params, double *step, double *gain);
+int wt_ensemble_mpc_reset(wt_ensemble *h);
+/* controllers off (no effect while none is set); the holding words stay */
+int wt_ensemble_mpc_clear(wt_ensemble *h);
 
 /* ---- the parameter checks of the scan programs, the disturbance and the score program, without a handle or a device ----
  * params: host, the block the program's set or enable call takes, for n_reactors reactors (WT_PROG_CONTROL:
