@@ -2,7 +2,8 @@
 test_gpu_program_shapes.py, tools/*_probe.py): a plant with sensors and plant I/O, a pair of PI loops, the plant's
 observable state and every program's, the message of a refused parameter block, and the host side of the PLC scan --
 the calls of one scan interval, the device's whole scan order (``HostScan.scan``) and the holding words of a host
-master; the zone count -> kernel instantiation rule and the wavefront packing."""
+master; the zone count -> kernel instantiation rule, the wavefront packing and the sensor suite's pass structure in a
+packed wavefront."""
 import importlib
 
 import numpy as np
@@ -112,6 +113,13 @@ def packing(request, monkeypatch):
     assert p.checked, f"a {p.name} test ended without asserting its wavefront-groups (Packing.check)"
 
 
+def spread_only(monkeypatch):
+    """The ``Packing`` of a test that keeps the id it had before a packed twin was written beside it: the library's own
+    spreading, stated (WT_FULL_WAVES removed) and to be asserted through ``check`` like any other."""
+    set_packing(monkeypatch, "spread")
+    return Packing("spread")
+
+
 def both_packings(argnames, argvalues, packed=None):
     """``pytest.mark.parametrize`` over ``argvalues`` and the ``packing`` fixture, for a test that was parametrised over
     ``argvalues`` before it ran packed as well: the spread cases keep the ids they always had (pytest's own for numbers
@@ -131,6 +139,43 @@ def both_packings(argnames, argvalues, packed=None):
     return pytest.mark.parametrize(",".join(names + ["packing"]), params, indirect=["packing"])
 
 
+# Zone counts of the packed sensor, service and plant I/O cases: every program-carrying instantiation, the aligned
+# multi-pass shapes (2, 4), the ones where a pass boundary cuts a sensor's run (3, 5, 6) and single-pass shapes at 8, 5,
+# 4, 3 and 2 reactors per wavefront (tests/test_sensor_passes.py asserts it)
+SENSOR_NS = (2, 3, 4, 5, 6, 8, 12, 16, 20, 32)
+SENSOR_LINES = ((0, 5), (1, 6))    # (pH electrode, RTD) of the inlet and of the outlet sample line
+
+
+class SensorPasses:
+    """The lane rule of ``wts::suite_step`` (csrc/wt_sensors.hpp) in a wavefront that holds R = 64 // n reactors: lane l
+    of pass p reads sensor idx // R of slot idx % R, idx = 64 p + l, over 7 R sensor lanes.
+    ``cuts``: sensor -> first slot of its run that falls in the later pass, for the sensors a pass boundary cuts;
+    ``split``: line -> the slots whose RTD lane runs in a later pass than the pH lane it takes the line from."""
+
+    def __init__(self, n):
+        self.n, self.R = n, 64 // n
+        self.lanes = 7 * self.R
+        self.passes = -(-self.lanes // 64)
+        self.cuts, self.split = {}, {}
+        for i in range(7):
+            first, last = self.pass_of(i, 0), self.pass_of(i, self.R - 1)
+            assert last - first <= 1
+            if last != first:
+                self.cuts[i] = 64 * last - i * self.R
+        for line, (ph, rtd) in enumerate(SENSOR_LINES):
+            assert all(self.pass_of(ph, sl) <= self.pass_of(rtd, sl) for sl in range(self.R))
+            later = tuple(sl for sl in range(self.R) if self.pass_of(rtd, sl) > self.pass_of(ph, sl))
+            if later:
+                self.split[line] = later
+
+    def pass_of(self, sensor, slot):
+        return (sensor * self.R + slot) // 64
+
+
+def sensor_passes(n):
+    return SensorPasses(n)
+
+
 def assert_equal_by_reactor(ref, got, what, R):
     """``assert_all_equal`` for arrays whose last axis is the reactor: a mismatch names the reactors and, for the identity
     placement, their (wavefront-group, slot)."""
@@ -141,6 +186,26 @@ def assert_equal_by_reactor(ref, got, what, R):
         if bad.any():
             rs = np.unique(np.nonzero(bad)[-1])
             raise AssertionError((what, i, "reactors", rs[:8].tolist(), "(group, slot)", [(int(r) // R, int(r) % R) for r in rs[:8]]))
+
+
+_SPREAD = {}
+
+
+def equals_spread(monkeypatch, packing, key, n, got, run):
+    """``got``: the arrays (reactor on the last axis) a test's run left under ``packing``.  A spread case files them
+    under ``key``; a packed case requires its own to equal them bit for bit and names mismatches as (group, slot).  A
+    packed case that runs before its spread twin, or has none, makes the spread run itself: ``run(Packing("spread"))``,
+    which must end in the twin's ``check``."""
+    if not packing.packed:
+        _SPREAD[key] = got
+        return
+    if key not in _SPREAD:
+        set_packing(monkeypatch, "spread")
+        twin = Packing("spread")
+        _SPREAD[key] = run(twin)
+        assert twin.checked, key
+    assert len(_SPREAD[key]) == len(got), key
+    assert_equal_by_reactor(_SPREAD[key], got, ("packed against spread", key), 64 // n)
 
 
 def plant(wt, cols, bc, n, seed=11, history=0):

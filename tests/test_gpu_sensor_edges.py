@@ -9,6 +9,13 @@ where it is cheap a second handle makes one-step calls and must show the same bi
 run through: after ``enable_sensors`` the clock is moved on by 1 800 s (the suite's enable time is copied once, at
 enable), so every sensor is warm at the first read and both sensors of a sample line push from then on.
 
+Packing.  The library spreads ensembles as small as these over one wavefront per reactor, so
+every multi-reactor test runs twice: spread, under the id it always had, and packed (WT_FULL_WAVES: 64 // n reactors
+per wavefront, identity placement, so reactor r is slot r % R of wavefront-group r // R).  "Reactors per wavefront", a
+slot's position and the number of sensor passes are properties of the packed case; each case asserts through
+``Packing.check`` which of the two it was, and the packed history must equal the spread one bit for bit (mismatches
+named as (group, slot)).  The packed case shares the spread case's oracle run when the trajectories have the same bits.
+
 Observed maxima of |dv| / (1 + |v|) on an MI355X are listed in each test's docstring and in DESIGN.md's sensor section
 (7.1).  Before the sample lines carried fp64 timestamps the 0.8 s and 2.4 s cases stood at 0.08 and 1.06, and before
 the RTD's resistance round trip lost its cancellation the 7.5 s ... 100 s and irregular cases at 2.0e-5 ... 3.3e-5.
@@ -17,6 +24,8 @@ import numpy as np
 import pytest
 
 import sensor_oracle as SO
+from program_helpers import (SENSOR_LINES, SENSOR_NS, both_packings, equals_spread, packing, ragged_size,  # noqa: F401
+                             sensor_passes, spread_only)                                                   # (packing: a fixture)
 
 pytestmark = pytest.mark.gpu
 SEED = 0xC0FFEE
@@ -133,10 +142,12 @@ def quiet_plant(wt, n, N):
     return cols, bc, (rep("initial_pH"), rep("initial_chlorine"), rep("temperature"))
 
 
-def open_warm(wt, n, plant, base, history, seed=SEED):
+def open_warm(wt, n, plant, base, history, seed=SEED, packing=None):
     """An ensemble with the suite enabled at t = 0 and the clock then moved on by WARM, recording every step."""
     cols, bc, (pH, Cl, T) = plant
     ens = wt.ReactorEnsemble(cols, n_zones=n)
+    if packing is not None:
+        packing.place(ens)
     ens.set_boundary(bc)
     ens.enable_sensors(seed=seed, reactor_base=base, history=history)
     ens.set_state(pH, Cl, T, np.array(ens.state.time) + WARM)
@@ -156,11 +167,11 @@ def history_of(ens, steps):
     return hv[:steps].astype(np.float64), hs[:steps], hf[:steps]
 
 
-def run_calls(wt, n, plant, base, calls, one_step=False):
+def run_calls(wt, n, plant, base, calls, one_step=False, packing=None):
     """``calls``: (steps, dt) pairs, one fused call each (one_step: one call per step).  Returns the open handle, the
-    trajectory and the history."""
+    trajectory and the history.  ``packing``: places the ensemble and asserts its wavefront-groups after the last step."""
     steps = sum(k for k, _ in calls)
-    ens = open_warm(wt, n, plant, base, steps)
+    ens = open_warm(wt, n, plant, base, steps, packing=packing)
     for k, dt in calls:
         if one_step:
             for _ in range(k):
@@ -169,11 +180,39 @@ def run_calls(wt, n, plant, base, calls, one_step=False):
             ens.step(dt, n_steps=k, download=False)
     traj = ens.trajectory()
     assert len(traj) == steps and not traj.status.any()
+    if packing is not None:
+        packing.check(ens)
     return ens, traj, history_of(ens, steps)
 
 
 def same_bits(a, b):
     return all(np.array_equal(x, y, equal_nan=True) for x, y in zip(a, b))
+
+
+def health_arrays(ens):
+    """sensor_health() as a tuple of (7, N) arrays, in the order of its keys."""
+    health = ens.sensor_health()
+    return tuple(np.asarray(health[k]) for k in sorted(health))
+
+
+TRAJ_FIELDS = ("time", "pH", "chlorine", "temperature", "flow_rate", "status")
+_ORACLE = {}
+
+
+def oracle_of(key, plant, base, traj):
+    """(suites after the run, oracle_reads) of ``traj``, computed once per ``key`` and trajectory: the packed case of a
+    test records the bits of the spread case's trajectory and then shares its oracle run.  A trajectory with other bits
+    gets an oracle run of its own (and the packed case then fails where it compares itself with the spread one)."""
+    bits = tuple(np.asarray(getattr(traj, f)).tobytes() for f in TRAJ_FIELDS)
+    if key not in _ORACLE or _ORACLE[key][0] != bits:
+        suites = suites_of(plant, base)
+        ref = oracle_reads(suites, traj)
+        for a in ref:
+            a.setflags(write=False)
+        _ORACLE[key] = (bits, suites, ref)
+    return _ORACLE[key][1:]
+
+
 
 
 def line_report(suites):
@@ -200,10 +239,12 @@ SHAPES = [(2, 33), (8, 9), (20, 4)]
 OFF_GRID = [(0.1, 250), (0.8, 150), (2.4, 150), (7.5, 40), (45.0, 24), (100.0, 16)]
 
 
-@pytest.mark.parametrize("n,N", SHAPES)
-@pytest.mark.parametrize("dt,steps", OFF_GRID)
-def test_sample_line_off_the_grid(gpu, wt, n, N, dt, steps):
-    """32, 8 and 3 reactors per wavefront with a partial last one, one to four sensor passes, every reactor compared.
+@both_packings("dt,steps,n,N", [g + s for g in OFF_GRID for s in SHAPES])
+def test_sample_line_off_the_grid(gpu, wt, monkeypatch, dt, steps, n, N, packing):
+    """Packed: 32, 8 and 3 reactors per wavefront with a partial last one that holds one reactor, four sensor passes at
+    n = 2 and one at n = 8 and 20.  Spread (the library's own choice for ensembles this small): a wavefront per reactor
+    on a card with more wavefront slots than reactors, one sensor pass each.  Every reactor compared; the packed history
+    equals the spread one bit for bit.
     0.1 s: the 100-entry ring is shorter than the 30 s delay, the winner is the oldest entry held and the ring wraps;
     0.8 s and 2.4 s: 30 / dt is a half-integer, two timestamps lie at (nearly) the same distance from t - 30 and the
     reference's fp64 rounding settles which wins; 7.5 s: an exact hit four timestamps back; 45 s: the previous
@@ -214,26 +255,39 @@ def test_sample_line_off_the_grid(gpu, wt, n, N, dt, steps):
     Observed on an MI355X (max |dv| / (1 + |v|), the largest of the three shapes): 0.1 s 4.1e-7, 0.8 s 4.9e-7, 2.4 s 3.7e-7,
     7.5 s 3.0e-7, 45 s 3.7e-7, 100 s 2.7e-7; pushes moving by more than ten times the bound: pH >= 0.98, RTD >= 0.62."""
     plant = moving_plant(wt, n, N)
-    ens, traj, dev = run_calls(wt, n, plant, 0, [(steps, dt)])
-    ens.close()
-    ens1, traj1, dev1 = run_calls(wt, n, plant, 0, [(steps, dt)], one_step=True)
+
+    def fused(packing):
+        ens, traj, dev = run_calls(wt, n, plant, 0, [(steps, dt)], packing=packing)
+        ens.close()
+        return traj, dev
+    traj, dev = fused(packing)
+    ens1, traj1, dev1 = run_calls(wt, n, plant, 0, [(steps, dt)], one_step=True, packing=packing)
     ens1.close()
-    suites = suites_of(plant, 0)
-    ref = oracle_reads(suites, traj)
+    suites, ref = oracle_of(("off-grid", n, N, dt), plant, 0, traj)
     share, jump = line_report(suites)
     print(f"n = {n}, N = {N}, dt = {dt}: pushes moving by > 10 x bound: pH {share['pH']:.2f}, RTD {share['T']:.2f}; largest advance of a winner {jump}")
     assert share["pH"] >= 0.5 and share["T"] >= 0.5
     compare(f"off-grid n = {n} N = {N} dt = {dt}", dev, ref)
     assert same_bits(dev, dev1) and np.array_equal(traj.pH, traj1.pH) and np.array_equal(traj.time, traj1.time)
+    equals_spread(monkeypatch, packing, ("off-grid", n, N, dt), n, dev, lambda p: fused(p)[1])
 
 
 IRREGULAR = [(3, 45.0), (60, 0.1), (1, 20.0), (10, 1.0), (40, 0.8), (2, 100.0), (30, 0.3)]
 PH_OUTLET_DIES_EARLY = 1831        # tools/sensor_event_scan.py --t0 1800 --dt 45 --reads 3 --count 6000: power_low on pH_outlet at read 1
 
 
-@pytest.mark.parametrize("n,N,slot", [(8, 9, 3), (2, 33, 32)])
-def test_sample_line_irregular_calls(gpu, wt, n, N, slot):
-    """Calls of different step sizes on one handle: 3 x 45 s, 60 x 0.1 s, one of 20 s, 10 x 1 s, 40 x 0.8 s, 2 x 100 s,
+IRREGULAR_SHAPES = [(8, 9, 3), (2, 33, 32)]
+# packed only: a middle slot of a full wavefront at n = 2 (four passes), and at n = 6 a slot whose outlet RTD lane runs in
+# the pass after its pH partner's, beside slots (0 ... 3) whose RTD shares the partner's pass
+IRREGULAR_PACKED = IRREGULAR_SHAPES + [(2, 33, 17), (6, 21, 5)]
+
+
+@both_packings("n,N,slot", IRREGULAR_SHAPES, packed=IRREGULAR_PACKED)
+def test_sample_line_irregular_calls(gpu, wt, monkeypatch, n, N, slot, packing):
+    """Reactor ``slot`` is the one whose pH_outlet dies.  Packed it sits in a middle slot of a full wavefront with live
+    neighbours on both sides (8-9-3, 2-33-17, 6-21-5) or alone in the partial second wavefront (2-33-32); spread, on a
+    card with more wavefront slots than reactors, every reactor has a wavefront to itself and the slot says nothing.
+    Calls of different step sizes on one handle: 3 x 45 s, 60 x 0.1 s, one of 20 s, 10 x 1 s, 40 x 0.8 s, 2 x 100 s,
     30 x 0.3 s.  (The long steps first: the reads after a change of step size are RATE_FAULTs -- the delivered sample
     jumps by 45 s of signal within 0.1 s -- and such a read skips the circuit draw, so only an event before the first
     change is met for certain.)  After the stretch of 0.1 s steps the target sweeps over many entries per read, so the device's walk
@@ -243,15 +297,23 @@ def test_sample_line_irregular_calls(gpu, wt, n, N, slot):
     Observed: 3.5e-7 (n = 8), 6.6e-7 (n = 2)."""
     plant = moving_plant(wt, n, N)
     base = PH_OUTLET_DIES_EARLY - slot
-    ens, traj, dev = run_calls(wt, n, plant, base, IRREGULAR)
-    ens.close()
-    suites = suites_of(plant, base)
-    ref = oracle_reads(suites, traj)
+    R = 64 // n
+    if packing.packed:                                  # where the dying electrode really sits
+        assert (0 < slot % R < R - 1 and slot < R) or (slot == R and N == R + 1), (n, N, slot)
+        assert n != 6 or (slot in sensor_passes(6).split[1] and 0 not in sensor_passes(6).split[1])
+
+    def run(packing):
+        ens, traj, dev = run_calls(wt, n, plant, base, IRREGULAR, packing=packing)
+        ens.close()
+        return traj, dev
+    traj, dev = run(packing)
+    suites, ref = oracle_of(("irregular", n, N, slot), plant, base, traj)
     share, jump = line_report(suites)
     print(f"irregular n = {n}, N = {N}: pushes moving {share}, largest advance of a winner {jump}")
     assert ref[2][1, SO.S_PH_OUT, slot] == SO.FL_POWER_LOW and np.isfinite(ref[0][-1, SO.S_T_OUT, slot])
     assert jump["pH"] > 4 and jump["T"] > 4
     compare(f"irregular n = {n} N = {N}", dev, ref)
+    equals_spread(monkeypatch, packing, ("irregular", n, N, slot), n, dev, lambda p: run(p)[1])
 
 
 # ---------------------------------------------------------------- B. rare faults from the random stream
@@ -265,27 +327,47 @@ EVENTS = [(141, SO.S_PH_IN, "power_high", 5, "pH"), (581, SO.S_PH_OUT, "power_lo
 # the pH electrode alive; "single" -- on a sensor without a line.  Every fault in every position:
 POSITIONS = {"pH": (SO.S_PH_IN, SO.S_PH_OUT), "rtd": (SO.S_T_IN, SO.S_T_OUT), "single": (SO.S_CL_IN, SO.S_CL_OUT, SO.S_FLOW)}
 assert {(e[4], e[2]) for e in EVENTS} == {(p, f) for p in POSITIONS for f in CIRCUIT.values()} and all(e[1] in POSITIONS[e[4]] for e in EVENTS)
-# (reactor, n, N, slot, steps): first and last slot of a wavefront (n = 8: 8 reactors, n = 2: 32, n = 20: 3), the first
-# slot of a partial second wavefront; at n = 2 the sensors of a reactor spread over four passes of the wavefront
+# (reactor, n, N, slot, steps).  In the packed cases: first and last slot of a wavefront (n = 8: 8 reactors, n = 2: 32,
+# n = 20: 3), the first slot of a partial second wavefront; at n = 2 the sensors of a reactor spread over four passes of
+# the wavefront (``fault_position`` asserts it from R and the slot).  Spread, a reactor has a wavefront to itself.
 FAULT_RUNS = [(141, 2, 33, 31, 20), (581, 8, 9, 0, 28), (340, 20, 4, 2, 20), (208, 8, 9, 8, 44), (168, 2, 33, 32, 40),
               (506, 8, 9, 7, 14), (540, 2, 33, 0, 38), (68, 8, 9, 0, 100), (348, 20, 4, 0, 18), (552, 8, 9, 8, 18),
               (251, 8, 9, 7, 26)]
 PARTNER = {SO.S_PH_IN: SO.S_T_IN, SO.S_PH_OUT: SO.S_T_OUT, SO.S_T_IN: SO.S_PH_IN, SO.S_T_OUT: SO.S_PH_OUT}
 
 
-@pytest.mark.parametrize("reactor,n,N,slot,steps", FAULT_RUNS)
-def test_rare_faults_vs_oracle(gpu, wt, reactor, n, N, slot, steps):
+def fault_position(n, N, slot):
+    """Where ``slot`` lies once the N reactors are packed 64 // n to a wavefront."""
+    R = 64 // n
+    assert N == R + 1 and 0 <= slot < N, (n, N, slot)
+    return "lone" if slot == R else "first" if slot == 0 else "last" if slot == R - 1 else "middle"
+
+
+assert [fault_position(n, N, slot) for _, n, N, slot, _ in FAULT_RUNS] == ["last", "first", "last", "lone", "lone", "last", "first", "first",
+                                                                            "first", "lone", "last"]
+
+
+@both_packings("reactor,n,N,slot,steps", FAULT_RUNS)
+def test_rare_faults_vs_oracle(gpu, wt, monkeypatch, reactor, n, N, slot, steps, packing):
     """A reactor whose stream draws a power fault or an open / short circuit within the run (EVENTS), in a small ensemble
-    with ``reactor_base = reactor - slot``; steps of 30 s, the whole ensemble compared, sensor_health() included.  The
+    with ``reactor_base = reactor - slot``; steps of 30 s, the whole ensemble compared, sensor_health() included.
+    Packed, the reactor is the first or the last of a full wavefront beside live neighbours, or the lone one of the
+    second wavefront (``fault_position``); spread, every reactor of these ensembles has its own wavefront.  The packed
+    history and sensor_health() equal the spread run's bit for bit.  The
     reads after the event run the sticky POWER_FAULT return of read_begin, the NaN that feeds back through the lag, and
     a sample line with one sensor of the pair dead and the other pushing on.  The oracle's run contains the reactor's
     events of the list at their reads, the other sensor of the line alive; the list holds every fault in every position.
     Observed: at most 3.8e-7 over the eleven runs; the ageing accumulators equal to the digits compared."""
     plant = quiet_plant(wt, n, N)
     base = reactor - slot
-    ens, traj, dev = run_calls(wt, n, plant, base, [(steps, 30.0)])
-    suites = suites_of(plant, base)
-    ref = oracle_reads(suites, traj)
+    assert fault_position(n, N, slot) in ("first", "last", "lone")
+
+    def run(packing):
+        ens, traj, dev = run_calls(wt, n, plant, base, [(steps, 30.0)], packing=packing)
+        return ens, traj, dev + health_arrays(ens)
+    ens, traj, got = run(packing)
+    dev = got[:3]
+    suites, ref = oracle_of(("faults", reactor), plant, base, traj)
     mine = [e for e in EVENTS if e[0] == reactor]
     assert mine
     for _, i, name, k, _ in mine:                                       # (a condition on the oracle's run, not on the device)
@@ -294,6 +376,12 @@ def test_rare_faults_vs_oracle(gpu, wt, reactor, n, N, slot, steps):
     compare(f"faults reactor {reactor} n = {n} N = {N} slot {slot}", dev, ref)
     compare_health(f"faults reactor {reactor}", ens, suites)
     ens.close()
+
+    def twin(p):
+        e, _, g = run(p)
+        e.close()
+        return g
+    equals_spread(monkeypatch, packing, ("faults", reactor), n, got, twin)
 
 
 # ---------------------------------------------------------------- C. deterministic statuses by host edits
@@ -304,7 +392,20 @@ def chlorine_for(reading, pH0, offset):
     return (reading - offset) / (0.5 + 0.5 * ratio / (1.0 + ratio))
 
 
-def test_statuses_by_host_edits(gpu, wt):
+def test_statuses_by_host_edits(gpu, wt, monkeypatch):
+    """The spread case of ``statuses_by_host_edits``: the library's own dealing of nine reactors (a wavefront each on a
+    card with more wavefront slots than that)."""
+    statuses_by_host_edits(wt, monkeypatch, spread_only(monkeypatch))
+
+
+@pytest.mark.parametrize("packing", ["packed"], indirect=True)
+def test_statuses_by_host_edits_packed(gpu, wt, monkeypatch, packing):
+    """One full wavefront of eight reactors and a lone ninth: the edited reactors are slots 1 and 4 of the first, beside
+    reactors that keep their state, and the lone one.  The histories equal the spread run's bit for bit."""
+    statuses_by_host_edits(wt, monkeypatch, packing)
+
+
+def statuses_by_host_edits(wt, monkeypatch, packing):
     """dt = 1 s, 9 reactors of 8 zones, three of them edited with set_state between calls and set back a few steps
     later: pH up by 2 (the electrodes answer 30 s later, through the sample line, with RATE_FAULT on the rise and on the
     fall), chlorine to where the amperometric analyser settles at 10.5 mg/L of its 0 .. 10 range (SATURATED), chlorine
@@ -322,39 +423,43 @@ def test_statuses_by_host_edits(gpu, wt):
     # (steps before the edit, the edit, steps it is held, steps after it is set back)
     script = [(3, "pH", 3, 40), (2, "saturate", 6, 10), (2, "out_of_range", 6, 12)]
     total = sum(a + b + c for a, _, b, c in script)
-    runs = {}
-    for name in ("edited", "twin"):
-        ens = open_warm(wt, n, plant, 0, total)
-        for before, what, held, after in script:
-            ens.step(1.0, n_steps=before, download=False)
-            s = ens.state
-            pH, Cl = s.pH.copy(), s.chlorine.copy()
-            if name == "edited":
-                if what == "pH":
-                    pH[edited] += 2.0
+
+    def run(packing):
+        runs = {}
+        for name in ("edited", "twin"):
+            ens = open_warm(wt, n, plant, 0, total, packing=packing)
+            for before, what, held, after in script:
+                ens.step(1.0, n_steps=before, download=False)
+                s = ens.state
+                pH, Cl = s.pH.copy(), s.chlorine.copy()
+                if name == "edited":
+                    if what == "pH":
+                        pH[edited] += 2.0
+                    else:
+                        offset = cols["initial_chlorine"][edited]                    # calibrated against it from a zero reading
+                        Cl[edited] = chlorine_for(10.5 if what == "saturate" else 14.0, s.pH[edited, 0], offset)[:, None]
+                ens.set_state(pH, Cl, s.temperature)
+                ens.step(1.0, n_steps=held, download=False)
+                h = ens.state
+                if name == "edited":                                                 # back: the edited field as it was, the rest as it is
+                    pH, Cl = h.pH.copy(), h.chlorine.copy()
+                    if what == "pH":
+                        pH[edited] = s.pH[edited]
+                    else:
+                        Cl[edited] = s.chlorine[edited]
+                    ens.set_state(pH, Cl, h.temperature)
                 else:
-                    offset = cols["initial_chlorine"][edited]                    # calibrated against it from a zero reading
-                    Cl[edited] = chlorine_for(10.5 if what == "saturate" else 14.0, s.pH[edited, 0], offset)[:, None]
-            ens.set_state(pH, Cl, s.temperature)
-            ens.step(1.0, n_steps=held, download=False)
-            h = ens.state
-            if name == "edited":                                                 # back: the edited field as it was, the rest as it is
-                pH, Cl = h.pH.copy(), h.chlorine.copy()
-                if what == "pH":
-                    pH[edited] = s.pH[edited]
-                else:
-                    Cl[edited] = s.chlorine[edited]
-                ens.set_state(pH, Cl, h.temperature)
-            else:
-                ens.set_state(h.pH, h.chlorine, h.temperature)
-            ens.step(1.0, n_steps=after, download=False)
-        traj = ens.trajectory()
-        assert len(traj) == total and not traj.status.any()
-        runs[name] = (traj, history_of(ens, total))
-        ens.close()
+                    ens.set_state(h.pH, h.chlorine, h.temperature)
+                ens.step(1.0, n_steps=after, download=False)
+            traj = ens.trajectory()
+            assert len(traj) == total and not traj.status.any()
+            runs[name] = (traj, history_of(ens, total))
+            packing.check(ens)
+            ens.close()
+        return runs
+    runs = run(packing)
     traj, dev = runs["edited"]
-    suites = suites_of(plant, 0)
-    ref = oracle_reads(suites, traj)
+    suites, ref = oracle_of("host edits", plant, 0, traj)
     ov, os_, of = ref
     marks = np.cumsum([0] + [a + b + c for a, _, b, c in script])
     for r in edited:
@@ -373,6 +478,58 @@ def test_statuses_by_host_edits(gpu, wt):
     twin = runs["twin"][1]
     assert all(np.array_equal(a[:, :, kept], b[:, :, kept], equal_nan=True) for a, b in zip(dev, twin))
     assert not same_bits(dev, twin)
+    both = lambda runs: runs["edited"][1] + runs["twin"][1]
+    equals_spread(monkeypatch, packing, "host edits", n, both(runs), lambda p: both(run(p)))
+
+
+# ---------------------------------------------------------------- E. every pass structure of a packed wavefront
+PASS_STEPS, PASS_DT = 40, 0.8
+
+
+@pytest.mark.parametrize("n", SENSOR_NS)
+def test_every_pass_structure_vs_oracle(gpu, wt, monkeypatch, n, packing):
+    """``moving_plant``, three full wavefronts of R = 64 // n reactors and a lone one, one fused call of 40 steps of 0.8 s
+    (30 / dt is a half-integer: the line's winner hangs on the last bits), every reactor against the oracle.  Packed,
+    the suite runs in the pass structure of ``sensor_passes(n)``: four aligned passes at n = 2 and two at n = 4, a pass
+    boundary inside the DPD analyser's and the outlet RTD's runs at n = 3, inside the inlet RTD's at n = 5 (slots 4 ... 11
+    take their line a pass after the pH lane left it) and inside the outlet RTD's at n = 6, one pass of 56 ... 14 lanes
+    from n = 8 on; spread, one pass of seven lanes per reactor.  The oracle's trace shows that the pH electrode and the
+    RTD of both lines transported in every slot (those behind a pass boundary among them), that winners advanced and
+    that more than half of the pushes moved by more than ten times the bound.  Packed equals spread bit for bit,
+    sensor_health() included."""
+    R, N = ragged_size(n, 3)
+    plant = moving_plant(wt, n, N)
+
+    def run(packing):
+        ens, traj, dev = run_calls(wt, n, plant, 0, [(PASS_STEPS, PASS_DT)], packing=packing)
+        return ens, traj, dev + health_arrays(ens)
+    ens, traj, got = run(packing)
+    suites, ref = oracle_of(("passes", n), plant, 0, traj)
+    share, jump = line_report(suites)
+    print(f"passes n = {n}, N = {N}: pushes moving by > 10 x bound: pH {share['pH']:.2f}, RTD {share['T']:.2f}; largest advance of a winner {jump}")
+    assert share["pH"] >= 0.5 and share["T"] >= 0.5
+    assert jump["pH"] >= 1                                   # (an RTD reads just after its pH partner moved the winner on)
+    p = sensor_passes(n)
+    assert (p.R, N) == (R, 3 * R + 1)
+    # transports per (sensor of a line, reactor): a sensor pushes at every read unless its stream draws a fault (a few
+    # in ten thousand reads), so nine in ten pushed at all forty, on the whole and behind a pass boundary
+    pushes = {i: np.array([sum(1 for reader, _, _ in s.lines[line].trace if reader == i) for s in suites])
+              for line, pair in enumerate(SENSOR_LINES) for i in pair}
+    for i, cnt in pushes.items():
+        assert np.mean(cnt == PASS_STEPS) >= 0.9, (n, i, cnt.tolist())
+    far = {i: [r for r in range(N) if r % R >= slot] for i, slot in p.cuts.items() if i >= 5}
+    assert {i: len(rs) for i, rs in far.items()} == {3: {6: 3 * 19}, 5: {5: 3 * 8}, 6: {6: 3 * 6}}.get(n, {})
+    for i, rs in far.items():
+        assert np.mean(pushes[i][rs] == PASS_STEPS) >= 0.9 and np.isfinite(ref[0][-1, i, rs]).mean() >= 0.9, (n, i, pushes[i][rs].tolist())
+    compare(f"passes n = {n} N = {N}", got[:3], ref)
+    compare_health(f"passes n = {n}", ens, suites)
+    ens.close()
+
+    def twin(pk):
+        e, _, g = run(pk)
+        e.close()
+        return g
+    equals_spread(monkeypatch, packing, ("passes", n), n, got, twin)
 
 
 # ---------------------------------------------------------------- D. the long horizon

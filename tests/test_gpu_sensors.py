@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 from conftest import golden_npz
+from program_helpers import equals_spread, packing, ragged_size, sensor_passes, spread_only  # noqa: F401  (packing: a fixture)
 
 pytestmark = pytest.mark.gpu
 CASES = ("main5", "dose8", "quiet4")
@@ -93,15 +94,48 @@ def test_suite_statistics_and_independence(gpu, wt):
 def test_suite_at_config5_share_vs_oracle(gpu, wt, N, n):
     """BASELINE config 5's per-GPU share (12 500 reactors x 8 zones, sensors on): the readings of a sample of
     reactors over 45 steps against the sensor oracle fed the device's own per-step state; every wavefront position
-    (first / last reactor of a wavefront, last wavefront of the ensemble) is in the sample.  Likewise with 16, 32 and
-    12 reactors per wavefront, where the suite takes two / four passes of nine reactors (seven lanes each)."""
+    (first / last reactor of a wavefront, last wavefront of the ensemble) is in the sample.  Only this case is packed
+    (8 reactors per wavefront: one sensor pass of 56 lanes).  The library spreads the other three over all its wavefront
+    slots: on an MI355X (1 024 of them) 4 000 x 4, 4 100 x 2 and 3 000 x 5 run 4, 5 and 3 reactors per wavefront where
+    16, 32 and 12 would fit, that is 28, 35 and 21 sensor lanes in one pass.  The two- to four-pass shapes run packed in
+    test_suite_packed_vs_oracle."""
+    R = 64 // n
+    sample = sorted({0, R - 1, R, 8, 9, 10, 17, 18, 26, 27, 63, 64, N // 3, N // 3 + 9, N - R - 1, N - 5, N - 4, N - 1} & set(range(N)))
+    suite_vs_oracle(wt, N, n, sample).close()
+
+
+@pytest.mark.parametrize("n", [2, 3, 4, 5, 6])
+@pytest.mark.parametrize("packing", ["packed"], indirect=True)
+def test_suite_packed_vs_oracle(gpu, wt, monkeypatch, n, packing):
+    """The method of test_suite_at_config5_share_vs_oracle with full wavefronts, at every zone count where the suite
+    takes more than one pass: five wavefronts of 32, 21, 16, 12 and 10 reactors and a lone reactor, four, three and two
+    passes, with a pass boundary between sensors (n = 2, 4) and inside a sensor's run (3, 5, 6).  Every reactor is in the
+    sample; the history equals the spread run's bit for bit."""
+    R, N = ragged_size(n)
+    assert sensor_passes(n).passes == {2: 4, 3: 3}.get(n, 2)
+    ens = suite_vs_oracle(wt, N, n, list(range(N)), packing)
+    got = ens.sensor_history()
+    ens.close()
+
+    def twin(p):
+        e = suite_vs_oracle(wt, N, n, [], p)
+        out = e.sensor_history()
+        e.close()
+        return out
+    equals_spread(monkeypatch, packing, ("suite", n), n, got, twin)
+
+
+def suite_vs_oracle(wt, N, n, sample, packing=None):
+    """45 one-step calls; the readings of the reactors of ``sample`` against the sensor oracle fed the device's own
+    per-step state.  Returns the open ensemble (its wavefront-groups asserted through ``packing``, where given)."""
     import sensor_oracle as SO
     steps, seed = 45, 0xC0FFEE
     cols, bc = wt.make_ensemble(N)
-    ens = wt.ReactorEnsemble(cols, n_zones=n); ens.set_boundary(bc)
+    ens = wt.ReactorEnsemble(cols, n_zones=n)
+    if packing is not None:
+        packing.place(ens)
+    ens.set_boundary(bc)
     ens.enable_sensors(seed=seed, reactor_base=0, history=steps)
-    R = 64 // n
-    sample = sorted({0, R - 1, R, 8, 9, 10, 17, 18, 26, 27, 63, 64, N // 3, N // 3 + 9, N - R - 1, N - 5, N - 4, N - 1} & set(range(N)))
     suites = {r: SO.SensorSuite(float(cols["flow_rate"][r]), float(cols["initial_chlorine"][r]), float(cols["temperature"][r]),
                                 0.0, seed, r) for r in sample}
     ov = np.empty((steps, 7, len(sample))); os_ = np.empty((steps, 7, len(sample)), dtype=np.uint8); of = np.empty_like(os_)
@@ -114,17 +148,35 @@ def test_suite_at_config5_share_vs_oracle(gpu, wt, N, n):
             ov[k, :, j], os_[k, :, j], of[k, :, j] = v, s, f
     hv, hs, hf, nf = ens.sensor_history()
     assert np.all(nf == steps)
+    if packing is not None:
+        packing.check(ens)
+    if not sample:
+        return ens
     hv, hs, hf = hv[:, :, sample], hs[:, :, sample], hf[:, :, sample]
     assert np.array_equal(np.isnan(hv), np.isnan(ov))
     ok = ~np.isnan(ov)
-    assert ok.sum() > 500 and np.max(np.abs(hv[ok] - ov[ok]) / (1.0 + np.abs(ov[ok]))) < 2e-5      # fp32 signal path
+    worst = np.max(np.abs(hv[ok] - ov[ok]) / (1.0 + np.abs(ov[ok])))
+    print(f"N = {N}, n = {n}: max |dv| / (1 + |v|) = {worst:.3e} over {int(ok.sum())} finite reads of {len(sample)} reactors")
+    assert ok.sum() > 500 and worst < 2e-5                                                        # fp32 signal path
     assert np.array_equal(hs, os_) and np.array_equal(hf, of)
     v, s, f = ens.sensor_readings()
     assert np.array_equal(v[:, sample], hv[-1], equal_nan=True)
-    ens.close()
+    return ens
 
 
-def test_history_counts_only_the_reads_taken(gpu, wt):
+def test_history_counts_only_the_reads_taken(gpu, wt, monkeypatch):
+    """The spread case of ``history_counts_only_the_reads_taken``: the two reactors get a wavefront each."""
+    history_counts_only_the_reads_taken(wt, monkeypatch, spread_only(monkeypatch))
+
+
+@pytest.mark.parametrize("packing", ["packed"], indirect=True)
+def test_history_counts_only_the_reads_taken_packed(gpu, wt, monkeypatch, packing):
+    """The raising reactor and its neighbour are slots 0 and 1 of one wavefront (4 zones: 16 would fit); the history
+    equals the spread run's bit for bit."""
+    history_counts_only_the_reads_taken(wt, monkeypatch, packing)
+
+
+def history_counts_only_the_reads_taken(wt, monkeypatch, packing):
     """A reactor whose step raises takes no reading from then on (the reference's loop stops at the raise): its history
     length is the number of completed steps, what lies beyond is zero, not uninitialised memory; its neighbour in the
     same ensemble keeps reading.  (Cold-run fixture g4: the reference raises at step index 34.)"""
@@ -132,13 +184,18 @@ def test_history_counts_only_the_reads_taken(gpu, wt):
     g = golden_json("g4_faults.json")["cold_run"]
     cfg = wt.ReactorConfiguration(**g["config"])
     b = wt.BoundaryConditions(**dict(zip(wt.params.BOUNDARY_FIELDS, g["bc"])))
-    ens = wt.ReactorEnsemble([cfg, wt.ReactorConfiguration(n_zones=cfg.n_zones)])
-    ens.set_boundary([b, wt.BoundaryConditions()])
-    ens.enable_sensors(seed=3, history=64)
-    for k in (10, 30, 20):
-        ens.step(1.0, n_steps=k)
-    v, st, fl, n = ens.sensor_history()
+    def run(packing):
+        ens = packing.place(wt.ReactorEnsemble([cfg, wt.ReactorConfiguration(n_zones=cfg.n_zones)]))
+        ens.set_boundary([b, wt.BoundaryConditions()])
+        ens.enable_sensors(seed=3, history=64)
+        for k in (10, 30, 20):
+            ens.step(1.0, n_steps=k)
+        out = ens.sensor_history()
+        packing.check(ens)
+        ens.close()
+        return out
+    v, st, fl, n = run(packing)
     assert n[0] == g["raise_step_index"] and n[1] == 60
     assert not v[n[0]:, :, 0].any() and not st[n[0]:, :, 0].any() and not fl[n[0]:, :, 0].any()
     assert st[:n[1], :, 1].any()                      # the neighbour's sixty reads are there (status codes of warming-up sensors)
-    ens.close()
+    equals_spread(monkeypatch, packing, "history counts", cfg.n_zones, (v, st, fl, n), run)

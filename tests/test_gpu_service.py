@@ -1,6 +1,12 @@
 """The sensor service program on the GPU: the fused call against the host loop it replaces (bit for bit), against the
 restatement of the reference's maintenance methods (tests/service_ref.py) at the golden scenarios, next to plant I/O,
-through checkpoints, and its refusals."""
+through checkpoints, and its refusals.
+
+Packing: ensembles this small are spread by the library, a wavefront per reactor on a card
+with more wavefront slots than reactors.  The fused-against-host-loop test and the test beside plant I/O therefore run
+twice, spread under the ids they always had and packed (WT_FULL_WAVES, identity placement: reactor r is slot r % R of
+wavefront-group r // R); "reactors per wavefront" and the number of sensor passes describe the packed cases.  The
+golden-scenario test holds one reactor per ensemble and stays as it is."""
 import numpy as np
 import pytest
 
@@ -8,32 +14,42 @@ from conftest import golden_npz
 
 import sensor_oracle as SO
 import service_ref as SR
+from program_helpers import both_packings, equals_spread, packing, spread_only  # noqa: F401  (packing: a fixture)
 from test_service_cpu import block_of, deal
 
 pytestmark = pytest.mark.gpu
 DT, STEPS = 30.0, 80
 SHAPES = [(2, 70), (5, 27), (8, 19), (20, 7), (32, 5)]
+# packed only: two full wavefronts and a lone reactor at the zone counts SHAPES leaves out, so that the packed cases reach
+# every program-carrying instantiation and every pass structure of the suite (tests/test_sensor_passes.py)
+PACKED_SHAPES = [(3, 43), (4, 33), (6, 21), (12, 11), (16, 9)]
 
 
-def ensemble(wt, n, N, seed=0x5E41CE, history=STEPS):
+def ensemble(wt, n, N, seed=0x5E41CE, history=STEPS, packing=None):
     cols, bc = wt.make_ensemble(N)
     ens = wt.ReactorEnsemble(cols, n_zones=n)
+    if packing is not None:
+        packing.place(ens)
     ens.set_boundary(bc)
     ens.enable_sensors(seed=seed, history=history)
     return ens
 
 
-def mixed_program(wt, N):
-    """Four slots with per-reactor arrays: neighbouring reactors (neighbouring lanes of a sensor's run) take different
-    actions with different references in the same step; slots 0 and 1 of every fifth reactor hit the DPD sensor in the
+def mixed_program(wt, N, phase=0, together=False):
+    """Four slots with per-reactor arrays: reactors four apart take different actions with different references in the
+    same step, direct neighbours in different steps (the timed slots are staggered by ``r % 4`` and ``r % 3`` read
+    intervals); with ``together`` slot 2 falls due in every reactor at the same read, so that neighbouring reactors
+    (neighbouring lanes of a sensor's run in a packed wavefront) apply five different actions to two sensors in one
+    step.  Slots 0 and 1 of every fifth reactor hit the DPD sensor in the
     same step (replace first, then trim); slot 2 works on the pH electrodes once they are warm (1 800 s); slot 3 is a
-    work order on the flowmeter's DRIFT_WARNING with per-reactor delays."""
-    r = np.arange(N)
+    work order on the flowmeter's DRIFT_WARNING with per-reactor delays.  ``phase`` moves every per-reactor pattern on
+    by that many reactors."""
+    r = np.arange(N) + phase
     return (wt.Service("chlorine_outlet", np.where(r % 5 == 0, "replace_reagent", "calibrate"), at=300.0 + 30.0 * (r % 4), every=600.0,
                        ref=0.5 + 0.01 * r, ref_mode=np.array(["constant", "sample", "trim"])[r % 3]),
             wt.Service(np.array([3, 2, 6, 5, 4])[r % 5], "calibrate", at=300.0 + 30.0 * (r % 4), every=np.where(r % 2 == 0, 450.0, 0.0),
                        count=3, ref=0.02 * (r % 7), ref_mode=np.array(["trim", "sample"])[r % 2]),
-            wt.Service(r % 2, np.array(["rinse", "two_point", "acid_clean", "pepsin_clean", "calibrate"])[r % 5], at=1860.0 + 30.0 * (r % 3),
+            wt.Service(r % 2, np.array(["rinse", "two_point", "acid_clean", "pepsin_clean", "calibrate"])[r % 5], at=1860.0 + (0.0 if together else 30.0) * (r % 3),
                        ref=7.0, ref2=4.0),
             wt.Service("flow_main", "calibrate", on_status="drift_warning", delay=60.0 * (r % 3), ref_mode="trim", count=2))
 
@@ -42,12 +58,14 @@ def host_loop(ens, prog, steps, dt=DT):
     """What the fused call replaces: one-step calls, the restatement deciding after each read, service_sensors applying."""
     N = ens.n_reactors
     before = np.array(ens.state.time)
+    log = []                                                  # per step: what fell due in every reactor
     for _ in range(steps):
         es = ens.step(dt, n_steps=1)
         status = ens.sensor_readings()[1]
         # (a reactor whose step raised takes no reading and gets no service)
         due = [prog.after_read(r, float(es.time[r]), status[:, r]) if es.time[r] > before[r] else [] for r in range(N)]
         before = np.array(es.time)
+        log.append(due)
         for k in range(prog.slots):                           # slot order; the reactors of a slot do not interact
             groups = {}
             for r in range(N):
@@ -59,6 +77,7 @@ def host_loop(ens, prog, steps, dt=DT):
                 for r, a, b in members:
                     mask[r], ref[r], ref2[r] = True, a, b
                 ens.service_sensors(sensor, action, ref=ref, ref2=ref2, ref_mode=mode, mask=mask)
+    return log
 
 
 def snapshot(ens):
@@ -66,6 +85,12 @@ def snapshot(ens):
     health = ens.sensor_health()
     return dict(hv=hv, hs=hs, hf=hf, nf=nf, readings=ens.sensor_readings(), health=np.stack([health[k] for k in sorted(health)]),
                 state=np.stack([ens.state.pH, ens.state.chlorine, ens.state.temperature]))
+
+
+def by_reactor(snap, *more):
+    """The arrays of a ``snapshot`` and ``more`` (reactor last already), each with the reactor on its last axis."""
+    return ((snap["hv"], snap["hs"], snap["hf"], snap["nf"]) + tuple(np.asarray(v) for v in snap["readings"])
+            + (snap["health"], np.moveaxis(snap["state"], 1, -1)) + tuple(more))
 
 
 def same(a, b):
@@ -77,18 +102,29 @@ def same(a, b):
     return None
 
 
-@pytest.mark.parametrize("n,N", SHAPES)
-def test_fused_equals_host_loop(gpu, wt, n, N):
-    """32, 12, 8, 3 and 2 reactors per wavefront, a partial last wavefront, one to four sensor passes; 80 steps of 30 s,
-    so the pH electrodes warm up inside the run.  One call under set_schedule(1, 7) (slot state crosses item
-    boundaries), one under the default schedule, and the host loop of 80 one-step calls: the same bits everywhere."""
+@both_packings("n,N", SHAPES, packed=SHAPES + PACKED_SHAPES)
+def test_fused_equals_host_loop(gpu, wt, monkeypatch, n, N, packing):
+    """Packed: 32, 12, 8, 3 and 2 reactors per wavefront (SHAPES) and 21, 16, 10, 5 and 4 (PACKED_SHAPES), a partial last
+    wavefront, one to four sensor passes, at n = 3, 5 and 6 with a pass boundary inside a sensor's run.  Spread: the
+    library's own dealing, a wavefront per reactor where the card has more wavefront slots than the ensemble reactors,
+    one sensor pass.  80 steps of 30 s, so the pH electrodes warm up inside the run.  One call under set_schedule(1, 7)
+    (slot state crosses item boundaries), one under the default schedule, and the host loop of 80 one-step calls (its
+    ``service_sensors`` is a kernel of one thread per reactor, whatever the packing): the same bits everywhere, and the
+    packed snapshot and service state equal the spread run's."""
+    R = 64 // n
+    # The packed cases' program: slot 2 due in all reactors at one read (neighbours otherwise never act in the same
+    # step), and the per-reactor patterns moved on until one of the reactors that hit the DPD sensor twice in a step --
+    # every fifth -- sits in a slot other than the first (with 5, 3 or 2 to a wavefront and this few reactors none does
+    # unmoved).  The spread cases keep the program they always had; a packed case makes its own spread run.
+    phase = next(p for p in range(5) if any((r + p) % 5 == 0 and r % R for r in range(N))) if packing.packed else 0
+    program = lambda: mixed_program(wt, N, phase, together=packing.packed)
     runs = {}
     for name in ("items", "queue", "host"):
-        ens = ensemble(wt, n, N)
-        slots = mixed_program(wt, N)
+        ens = ensemble(wt, n, N, packing=packing)
+        slots = program()
         if name == "host":
             prog = SR.ServiceProgram(wt.service_block(N, *slots))
-            host_loop(ens, prog, STEPS)
+            log = host_loop(ens, prog, STEPS)
         else:
             if name == "items":
                 ens.set_schedule(1, 7)
@@ -98,6 +134,7 @@ def test_fused_equals_host_loop(gpu, wt, n, N):
             ens.step(DT, n_steps=STEPS)
             runs[name + "_state"] = ens.service_state().block()
         runs[name] = snapshot(ens)
+        packing.check(ens)
         ens.close()
     assert np.all(runs["host"]["nf"] == STEPS)
     assert same(runs["items"], runs["host"]) is None and same(runs["queue"], runs["host"]) is None
@@ -107,9 +144,25 @@ def test_fused_equals_host_loop(gpu, wt, n, N):
     assert np.all(prog.state[:, SR.VS_N_DONE].sum(axis=1) > 0)
     both = prog.params[0, SR.V_T_FIRST] == prog.params[1, SR.V_T_FIRST]
     assert np.any(both & (prog.params[1, SR.V_SENSOR] == 3))
-    base = ensemble(wt, n, N); base.step(DT, n_steps=STEPS)
+    base = ensemble(wt, n, N, packing=packing); base.step(DT, n_steps=STEPS)
     assert same(snapshot(base), runs["host"]) in ("hv", "hs")          # and it changed the readings
     base.close()
+    if packing.packed:
+        # in some step two neighbouring slots of one wavefront applied different actions, and a reactor in a slot other
+        # than the first had program slots 0 and 1 hit the DPD sensor together (on the restatement's record)
+        acts = lambda due: {d[2] for d in due}
+        assert any(due[r] and due[r + 1] and acts(due[r]) != acts(due[r + 1]) for due in log for r in range(N - 1) if r // R == (r + 1) // R)
+        assert any({(d[0], d[1]) for d in due[r]} >= {(0, 3), (1, 3)} for due in log for r in range(N) if r % R)
+
+    def twin(p):                                              # (the spread run of a packed-only shape or a moved program)
+        ens = ensemble(wt, n, N, packing=p)
+        ens.set_services(*program())
+        ens.step(DT, n_steps=STEPS)
+        got = by_reactor(snapshot(ens), ens.service_state().block())
+        p.check(ens)
+        ens.close()
+        return got
+    equals_spread(monkeypatch, packing, ("service", n, N, packing.name), n, by_reactor(runs["queue"], runs["queue_state"]), twin)
 
 
 CASE_SETUP = {"short8": (dict(n_zones=8, flow_rate=8.0, initial_chlorine=2.0),
@@ -177,14 +230,41 @@ def test_device_against_the_restatement_at_the_golden_scenarios(gpu, wt, case):
         ens.close()
 
 
-def test_a_program_changes_nothing_before_its_first_service(gpu, wt):
+def test_a_program_changes_nothing_before_its_first_service(gpu, wt, monkeypatch):
+    """The spread case of ``changes_nothing_before_its_first_service`` (19 reactors: the library deals them a wavefront
+    each on a card with more wavefront slots than that)."""
+    changes_nothing_before_its_first_service(wt, monkeypatch, spread_only(monkeypatch))
+
+
+@pytest.mark.parametrize("packing", ["packed"], indirect=True)
+def test_a_program_changes_nothing_before_its_first_service_packed(gpu, wt, monkeypatch, packing):
+    """Two full wavefronts of eight reactors and one of three: the scan lanes read the serviced instruments of their
+    neighbours' slots.  What the serviced run leaves equals the spread run's, bit for bit."""
+    changes_nothing_before_its_first_service(wt, monkeypatch, packing)
+
+
+def changes_nothing_before_its_first_service(wt, monkeypatch, packing):
     """Plant I/O with a PI loop on chlorine_outlet; the program's first service is the DPD calibration after the read at
     t = 600 s (step 20 of 30 s).  After 20 steps every image word, command, PI state and reading equals the run without
     the program, bit for bit; ten steps later the loop has seen the serviced instrument."""
     n, N = 8, 19
+    out = run_beside_plant_io(wt, n, N, packing)
+    # (the service follows the read of step 20: the instrument's calibration fields already differ, nothing read so far does)
+    health = out["serviced", "before"].pop("health"), out["plain", "before"].pop("health")
+    assert not np.array_equal(health[0], health[1], equal_nan=True)
+    assert same(out["plain", "before"], out["serviced", "before"]) is None
+    after = same(out["plain", "after"], out["serviced", "after"])
+    assert after is not None
+    assert not np.array_equal(out["plain", "after"]["ctl"], out["serviced", "after"]["ctl"], equal_nan=True)
+    left = lambda o: by_reactor(o["serviced", "after"], o["serviced", "after"]["img"].T, o["serviced", "after"]["ok"].T,
+                                o["serviced", "after"]["bc"], o["serviced", "after"]["ctl"])
+    equals_spread(monkeypatch, packing, "service beside plant I/O", n, left(out), lambda p: left(run_beside_plant_io(wt, n, N, p)))
+
+
+def run_beside_plant_io(wt, n, N, packing):
     out = {}
     for name in ("plain", "serviced"):
-        ens = ensemble(wt, n, N, history=40)
+        ens = ensemble(wt, n, N, history=40, packing=packing)
         ens.enable_plant_io()
         ens.set_schedule(0, 5)
         ens.enable_control(chlorine=wt.PILoop("chlorine_outlet", setpoint=1.5, kp=0.05, ki=0.001, bias=0.2, out_max=1.0))
@@ -195,14 +275,9 @@ def test_a_program_changes_nothing_before_its_first_service(gpu, wt):
             ens.step(DT, n_steps=steps)
             img, ok = ens.input_image()
             out[name, stage] = dict(img=img, ok=ok, bc=ens.boundary(), ctl=ens.control_state().block(), **snapshot(ens))
+        packing.check(ens)
         ens.close()
-    # (the service follows the read of step 20: the instrument's calibration fields already differ, nothing read so far does)
-    health = out["serviced", "before"].pop("health"), out["plain", "before"].pop("health")
-    assert not np.array_equal(health[0], health[1], equal_nan=True)
-    assert same(out["plain", "before"], out["serviced", "before"]) is None
-    after = same(out["plain", "after"], out["serviced", "after"])
-    assert after is not None
-    assert not np.array_equal(out["plain", "after"]["ctl"], out["serviced", "after"]["ctl"], equal_nan=True)
+    return out
 
 
 def test_checkpoints_carry_the_program(gpu, wt):
