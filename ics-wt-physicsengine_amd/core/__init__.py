@@ -19,6 +19,7 @@ from .service import Service, ServiceState, service_block
 from .install import Installation, installation_block
 from .tune import TUNE_RULES, LoopTune, RelayTune, TunerState, tune_block
 from .mpc import DMCLoop, LoopMpc, MpcState, dmc_gain, fopdt_step, mpc_block
+from .respond import Response, ResponseState, response_block
 from .chemistry import AqueousChemistry, BufferSystem, solve_pH
 from .physics import (ArrheniusParameters, FlowParameters, GeometryParameters, SpatialModel, StratificationParameters,
                       TemperatureDependentKinetics, TransportModel, run_all_validations, validate_chemistry,
@@ -38,6 +39,7 @@ __all__ = ["BoundaryConditions", "EnsembleState", "IntegratedCSTR", "PhysicsEngi
            "Service", "ServiceState", "service_block", "Installation", "installation_block",
            "RelayTune", "LoopTune", "TunerState", "TUNE_RULES", "tune_block",
            "DMCLoop", "LoopMpc", "MpcState", "dmc_gain", "fopdt_step", "mpc_block",
+           "Response", "ResponseState", "response_block",
            "AqueousChemistry", "BufferSystem", "solve_pH", "make_ensemble", "make_boundary_schedule", "params", "sharding", "gather_state", "shard_bounds",
            # the rest of wt_simulator.core's export list (core/__init__.py:238-263)
            "TemperatureDependentKinetics", "ArrheniusParameters", "TransportModel", "GeometryParameters", "FlowParameters",

@@ -18,8 +18,8 @@ from typing import Dict, Iterable, List, Optional, Sequence, Union
 
 import numpy as np
 
-from . import (_native, _program, actuator, alarm, control, detect, disturb, inject, install, junction, mpc, params, score,
-               service, train, trend, tune, wire)
+from . import (_native, _program, actuator, alarm, control, detect, disturb, inject, install, junction, mpc, params, respond,
+               score, service, train, trend, tune, wire)
 
 logger = logging.getLogger(__name__)
 
@@ -744,6 +744,40 @@ class ReactorEnsemble:
     def clear_mpc(self) -> None:
         """Stop the controllers; the holding registers stay as they are and the PI programs resume."""
         self._program_call(_native.lib().wt_ensemble_mpc_clear)
+
+    # -- response programs at every PLC scan, between the tune program and the controllers, on the device (wt_rsp.hpp)
+    def set_responses(self, *responses: "respond.Response") -> None:
+        """Run a response program of up to four :class:`Response` slots at every PLC scan, inside the step call: a slot
+        whose cause (an active alarm slot, a detector slot in alarm, a bad reading) has stood for its ``delay`` takes its
+        dosing loop from the PI and model predictive controllers, holds or drives the holding register, and hands the
+        loop back when the cause has been clear for ``clear_delay``.  The lowest engaged slot of a loop owns it; a relay
+        experiment (:meth:`set_tuners`) keeps a loop it has.  Replaces any program and restarts the state.  Needs
+        :meth:`enable_plant_io` and at most 32 zones per reactor."""
+        block = respond.response_block(self.n_reactors, *responses)
+        self._program_call(_native.lib().wt_ensemble_respond_set, _native.dptr(block))
+
+    def response_state(self) -> "respond.ResponseState":
+        """Phase, timers, forced output, times and counts of every slot, and the owner of each loop, by reactor (one
+        synchronisation)."""
+        n = self.n_reactors
+        st, rst = np.empty((respond.SLOTS, respond.NRS, n), dtype=np.float64), np.empty((respond.NRR, n), dtype=np.float64)
+        self._program_call(_native.lib().wt_ensemble_respond_state, _native.dptr(st), _native.dptr(rst))
+        return respond.ResponseState.from_block(st, rst)
+
+    def response_params(self) -> np.ndarray:
+        """The (4, 11, N) parameter block of the program in force, as :func:`response_block` built it."""
+        blk = np.empty((respond.SLOTS, respond.NR, self.n_reactors), dtype=np.float64)
+        self._program_call(_native.lib().wt_ensemble_respond_params, _native.dptr(blk))
+        return blk
+
+    def reset_responses(self) -> None:
+        """Every slot idle again, latched ones included, counts and times zeroed.  The holding registers stay as they
+        are, and the controllers resume from their own state."""
+        self._program_call(_native.lib().wt_ensemble_respond_reset)
+
+    def clear_responses(self) -> None:
+        """Stop the response program; the holding registers stay as they are and the controllers resume."""
+        self._program_call(_native.lib().wt_ensemble_respond_clear)
 
     # -- injection programs at every PLC scan, on the device (wt_inj.hpp)
     def set_injections(self, *injections: "inject.Injection") -> None:

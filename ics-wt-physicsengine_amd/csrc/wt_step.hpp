@@ -1050,6 +1050,17 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
                     owned = wtu::tune_execute(up->tun, up->ctl, rr, &io.val[0][lane], &io.fault[0][lane], wts::RMAX, up->sens.pack.loop_time[rr]);
                   }
                 }
+                // the response program (wave-uniform flag), directly after the tune program and before the controllers: a
+                // slot that is engaged holds its loop's words as a relay experiment does, except where the tuner has the
+                // loop in this scan (wt_rsp.hpp).  The controllers and the PLC program see one mask.
+                if constexpr (prog_in_item(LV)) {
+                  if (scan && WT_RARE(fresh(pa)->rsp.on) && lane < R && io.stepped[lane]) {
+                    ArgPtr rp = fresh(pa);
+                    const int64_t rr = rix[lane];
+                    owned |= wtrp::respond_execute(rp->rsp, rp->ctl, rp->alm, rp->det, rp->mpc, rr, &io.val[0][lane], &io.fault[0][lane],
+                                                   wts::RMAX, rp->sens.pack.loop_time[rr], owned);
+                  }
+                }
                 // the model predictive controllers (wave-uniform flag), between the tune program and the PLC program and
                 // with their inputs.  The whole wavefront enters: a scan lane decides, all 64 lanes carry the reactor's
                 // prediction (wt_mpc.hpp).  A controller owns its loop's holding words as a relay experiment does.

@@ -128,6 +128,8 @@ struct wt_ensemble {
     wtin::InsArgs ins = {};
     // The model predictive controllers (wt_mpc.hpp; not programs of k_programs either): plant I/O's arrays and a PLIO scalar.
     wtm::MpcArgs mpc = {};
+    // The response programs (wt_rsp.hpp; not programs of k_programs either): plant I/O's arrays and a PLIO scalar.
+    wtrp::RspArgs rsp = {};
     // optional per-launch HIP-event timing (bench.py roofline accounting)
     bool time_launches = false;
     std::vector<hipEvent_t> lt_pool;   // start/stop pairs
@@ -165,7 +167,7 @@ wt::StepArgs make_args(const wt_ensemble *h, double dt, int n_steps, int first_s
     a.trace = h->trace; a.trace_cap = h->trace_cap;
     a.kt = wt::default_ktab(); a.rt = wt::default_rtab();
     a.kt.dense_bias = h->knob_dense ? 1.0 : 0.0;
-    a.sens = h->sens; a.ctl = h->ctl; a.inj = h->inj; a.alm = h->alm; a.act = h->act; a.dst = h->dst; a.scr = h->scr; a.det = h->det; a.trd = h->trd; a.trn = h->trn; a.wir = h->wir; a.tun = h->tun; a.ins = h->ins; a.mpc = h->mpc;
+    a.sens = h->sens; a.ctl = h->ctl; a.inj = h->inj; a.alm = h->alm; a.act = h->act; a.dst = h->dst; a.scr = h->scr; a.det = h->det; a.trd = h->trd; a.trn = h->trn; a.wir = h->wir; a.tun = h->tun; a.ins = h->ins; a.mpc = h->mpc; a.rsp = h->rsp;
     // a full curve takes no more entries: the launches then carry no curve pointer at all
     const bool curve = h->scr.counts && h->scr_steps < h->scr.curve_cap;
     if (!curve) a.scr.counts = nullptr;
@@ -257,7 +259,8 @@ ArrayGroup sensor_arrays(wt_ensemble *h)
             [h] { h->sens.hist_cap = 0; h->sens.svc_on = 0; h->ins.on = 0; }};
 }
 
-// the tune program's records (wt_tun.hpp) and the model predictive controllers' arrays (wt_mpc.hpp) come and go with plant I/O
+// the tune program's records (wt_tun.hpp), the model predictive controllers' arrays (wt_mpc.hpp) and the response
+// programs' records (wt_rsp.hpp) come and go with plant I/O
 ArrayGroup plant_io_arrays(wt_ensemble *h)
 {
     const size_t N = (size_t)h->N;
@@ -271,8 +274,11 @@ ArrayGroup plant_io_arrays(wt_ensemble *h)
                                             {(void **)&h->mpc.st, sizeof(double) * wtm::ST_DOUBLES * N},
                                             {(void **)&h->mpc.step, sizeof(double) * wtm::ROW_DOUBLES * N},
                                             {(void **)&h->mpc.gain, sizeof(double) * wtm::ROW_DOUBLES * N},
-                                            {(void **)&h->mpc.pred, sizeof(double) * wtm::ROW_DOUBLES * N}},
-            [h] { h->tun.on = 0; h->mpc.on = 0; }};
+                                            {(void **)&h->mpc.pred, sizeof(double) * wtm::ROW_DOUBLES * N},
+                                            {(void **)&h->rsp.par, sizeof(double) * wtrp::PAR_DOUBLES * N},
+                                            {(void **)&h->rsp.st, sizeof(double) * wtrp::ST_DOUBLES * N},
+                                            {(void **)&h->rsp.rst, sizeof(double) * wtrp::RST_DOUBLES * N}},
+            [h] { h->tun.on = 0; h->mpc.on = 0; h->rsp.on = 0; }};
 }
 
 ArrayGroup record_arrays(wt_ensemble *h)
@@ -1188,11 +1194,16 @@ int wt_ensemble_plc_enable(wt_ensemble *h)
     if (e == hipSuccess) e = hipMemsetAsync((void *)h->mpc.step, 0, sizeof(double) * wtm::ROW_DOUBLES * N, h->stream);
     if (e == hipSuccess) e = hipMemsetAsync((void *)h->mpc.gain, 0, sizeof(double) * wtm::ROW_DOUBLES * N, h->stream);
     if (e == hipSuccess) e = hipMemsetAsync(h->mpc.pred, 0, sizeof(double) * wtm::ROW_DOUBLES * N, h->stream);
+    // and the response programs' records: every slot off
+    if (e == hipSuccess) e = hipMemsetAsync((void *)h->rsp.par, 0, sizeof(double) * wtrp::PAR_DOUBLES * N, h->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(h->rsp.st, 0, sizeof(double) * wtrp::ST_DOUBLES * N, h->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(h->rsp.rst, 0, sizeof(double) * wtrp::RST_DOUBLES * N, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) { release(arrays); return fail(WT_E_HIP, std::string("plc_enable: ") + hipGetErrorString(e)); }
     h->sens.cmd.hr = h->ctl.hr;
     h->tun.on = 0;                               // freshly enabled plant I/O has no tune program
     h->mpc.on = 0;                               // and no model predictive controller
+    h->rsp.on = 0;                               // and no response program
     h->sens.plc_on = 1;
     return WT_OK;
 }
@@ -2084,7 +2095,7 @@ const Part k_parts[] = {
                             {S_U32, &h->sens.seed_hi, false}, {S_I64, &h->sens.reactor_base, false},
                             {S_I32, &h->sens.svc_on, false}, {S_I32, &h->ins.on, false}}); }, nullptr},   // (the service program's arrays and the installation records are the suite's)
     {"PLIO", plant_io_arrays, 0, [](wt_ensemble *h, Scalars &s) {
-         s.insert(s.end(), {{S_I32, &h->sens.plc_on, true}, {S_I32, &h->tun.on, false}, {S_I32, &h->mpc.on, false}}); }, nullptr},   // (the tune program's and the model predictive controllers' arrays are plant I/O's)
+         s.insert(s.end(), {{S_I32, &h->sens.plc_on, true}, {S_I32, &h->tun.on, false}, {S_I32, &h->mpc.on, false}, {S_I32, &h->rsp.on, false}}); }, nullptr},   // (the tune program's, the model predictive controllers' and the response programs' arrays are plant I/O's)
     {"RECD", record_arrays, 0, [](wt_ensemble *h, Scalars &s) {
          s.insert(s.end(), {{S_I32, &h->rec.every, false}, {S_I32, &h->rec.cap, true}, {S_I64, &h->rec.steps, false}}); },
      [](const wt_ensemble *h) { return h->rec.cap > 0; }},
@@ -2240,7 +2251,7 @@ const char *config_error(wt_ensemble *u)
     const auto flag = [](int v) { return v == 0 || v == 1; };
     if (!flag(u->sens.on) || !flag(u->sens.plc_on) || !flag(u->ctl.on) || !flag(u->inj.on) || !flag(u->alm.on) || !flag(u->act.on) ||
         !flag(u->dst.on) || !flag(u->scr.on) || !flag(u->det.on) || !flag(u->trn.on) || !flag(u->trn.pipe.on) || !flag(u->trn.jct.on) || !flag(u->wir.on) ||
-        !flag(u->sens.svc_on) || !flag(u->ins.on) || !flag(u->tun.on) || !flag(u->mpc.on) || !flag(u->trd.on) || !flag(u->trd.wrap))
+        !flag(u->sens.svc_on) || !flag(u->ins.on) || !flag(u->tun.on) || !flag(u->mpc.on) || !flag(u->rsp.on) || !flag(u->trd.on) || !flag(u->trd.wrap))
         return "range";
     if (u->placement != WT_PLACE_IDENTITY && u->placement != WT_PLACE_ADAPTIVE) return "range";
     if (u->sched_mode != WT_SCHED_STREAMS && u->sched_mode != WT_SCHED_QUEUE) return "range";
@@ -2259,6 +2270,7 @@ const char *config_error(wt_ensemble *u)
     if (u->ins.on && !u->sens.on) return "range";
     if (u->tun.on && (!u->sens.plc_on || !wt::prog_in_item(levels_for(u->n)))) return "range";
     if (u->mpc.on && (!u->sens.plc_on || !wt::prog_in_item(levels_for(u->n)))) return "range";
+    if (u->rsp.on && (!u->sens.plc_on || !wt::prog_in_item(levels_for(u->n)))) return "range";
     return nullptr;
 }
 
@@ -3118,6 +3130,139 @@ int wt_ensemble_mpc_clear(wt_ensemble *h)
     return WT_OK;
 }
 
+// ---- response programs (wt_rsp.hpp): not programs of k_programs (they read the alarm and detector
+// programs' records and write the controllers'); their arrays are plant I/O's, as the tune program's are
+
+static_assert(WT_RSP_SLOTS == wtrp::SLOTS && WT_NR == wtrp::NR && WT_NRS == wtrp::NRS && WT_NRR == wtrp::NRR &&
+              WT_RSP_CAUSE == wtrp::R_CAUSE && WT_RSP_INDEX == wtrp::R_INDEX && WT_RSP_DELAY == wtrp::R_DELAY &&
+              WT_RSP_LOOP == wtrp::R_LOOP && WT_RSP_ACTION == wtrp::R_ACTION && WT_RSP_VALUE == wtrp::R_VALUE &&
+              WT_RSP_RATE == wtrp::R_RATE && WT_RSP_LATCH == wtrp::R_LATCH && WT_RSP_CLEAR_DELAY == wtrp::R_CLEAR_DELAY &&
+              WT_RSP_MIN_HOLD == wtrp::R_MIN_HOLD && WT_RSP_HANDBACK == wtrp::R_HANDBACK && WT_RSPS_PHASE == wtrp::RS_PHASE &&
+              WT_RSPS_PENDING == wtrp::RS_PENDING && WT_RSPS_CLEARING == wtrp::RS_CLEARING && WT_RSPS_OUTPUT == wtrp::RS_OUTPUT &&
+              WT_RSPS_T_FIRST == wtrp::RS_T_FIRST && WT_RSPS_T_ENGAGED == wtrp::RS_T_ENGAGED &&
+              WT_RSPS_T_RELEASED == wtrp::RS_T_RELEASED && WT_RSPS_N_ENGAGED == wtrp::RS_N_ENGAGED &&
+              WT_RSPS_TIME_ENGAGED == wtrp::RS_TIME_ENGAGED && WT_RSPS_N_OWNED == wtrp::RS_N_OWNED &&
+              WT_RSPS_N_BLOCKED == wtrp::RS_N_BLOCKED && WT_RSPS_N_CAUSE == wtrp::RS_N_CAUSE &&
+              WT_RSPS_N_TRACKED == wtrp::RS_N_TRACKED && WT_RSPS_N_HANDBACK == wtrp::RS_N_HANDBACK &&
+              WT_RSPR_T_PREV == wtrp::RR_T_PREV && WT_RSPR_OWNER_CHLORINE == wtrp::RR_OWNER_CHLORINE &&
+              WT_RSPR_OWNER_ACID == wtrp::RR_OWNER_ACID && WT_RSP_OFF == wtrp::C_OFF && WT_RSP_ALARM == wtrp::C_ALARM &&
+              WT_RSP_DETECTOR == wtrp::C_DETECTOR && WT_RSP_BAD == wtrp::C_BAD && WT_RSP_HOLD == wtrp::ACT_HOLD &&
+              WT_RSP_MANUAL == wtrp::ACT_MANUAL && WT_RSP_RAMP == wtrp::ACT_RAMP && WT_RSP_BUMP == wtrp::HB_BUMP &&
+              WT_RSP_BUMPLESS == wtrp::HB_BUMPLESS && WT_RSP_IDLE == wtrp::PH_IDLE && WT_RSP_ENGAGED == wtrp::PH_ENGAGED &&
+              WT_INFO_RESPOND == 26, "response program blocks of the C ABI");
+
+static const char *const k_respond_not_set = "no response program is set (wt_ensemble_respond_set)";
+
+// one slot of one reactor, rule by rule in the header's order
+static const char *respond_rule(const double *c)
+{
+    if (!whole_in(c[WT_RSP_CAUSE], 0, wtrp::N_CAUSES - 1)) return "cause must be 0 (off), 1 (alarm), 2 (detector) or 3 (bad)";
+    if (c[WT_RSP_CAUSE] == (double)WT_RSP_OFF) return nullptr;     // the other rows of a slot that is off are not read
+    if (c[WT_RSP_CAUSE] == (double)WT_RSP_ALARM && !whole_in(c[WT_RSP_INDEX], 0, wta::SLOTS - 1))
+        return "an ALARM cause's index must be an alarm slot in 0..3";
+    if (c[WT_RSP_CAUSE] == (double)WT_RSP_DETECTOR && !whole_in(c[WT_RSP_INDEX], 0, wtk::SLOTS - 1))
+        return "a DETECTOR cause's index must be a detector slot in 0..3";
+    if (c[WT_RSP_CAUSE] == (double)WT_RSP_BAD && !whole_in(c[WT_RSP_INDEX], 0, WT_N_SENSORS - 1))
+        return "a BAD cause's index must be a sensor index in 0..6";
+    if (!whole_in(c[WT_RSP_LOOP], 0, wtrp::LOOPS - 1)) return "loop must be 0 (chlorine) or 1 (acid)";
+    if (!whole_in(c[WT_RSP_ACTION], 0, wtrp::N_ACTIONS - 1)) return "action must be 0 (hold), 1 (manual) or 2 (ramp)";
+    if (!whole_in(c[WT_RSP_LATCH], 0, 1)) return "latch must be 0 or 1";
+    if (!whole_in(c[WT_RSP_HANDBACK], 0, 1)) return "handback must be 0 (bump) or 1 (bumpless)";
+    for (const int f : {WT_RSP_DELAY, WT_RSP_CLEAR_DELAY, WT_RSP_MIN_HOLD, WT_RSP_RATE})
+        if (!(c[f] >= 0.0)) return "delay, clear_delay, min_hold and rate must be >= 0 and not NaN";
+    if (!(c[WT_RSP_VALUE] >= 0.0 && c[WT_RSP_VALUE] <= k_command_limit[(int)c[WT_RSP_LOOP]]))
+        return "value must be within 0 and the loop's command limit (1.0 chlorine, 2.0 acid)";
+    return nullptr;
+}
+
+int wt_respond_check(int64_t n_reactors, const double *params)
+{
+    if (n_reactors < 1) return fail(WT_E_ARG, "n_reactors must be >= 1");
+    if (!params) return fail(WT_E_ARG, "NULL argument");
+    double c[WT_NR];
+    for (int s = 0; s < WT_RSP_SLOTS; ++s)
+        for (int64_t r = 0; r < n_reactors; ++r) {
+            for (int k = 0; k < WT_NR; ++k) c[k] = params[((int64_t)s * WT_NR + k) * n_reactors + r];
+            if (const char *msg = respond_rule(c))
+                return fail(WT_E_ARG, std::string(msg) + " (slot " + std::to_string(s) + ", reactor " + std::to_string(r) + ")");
+        }
+    return WT_OK;
+}
+
+// every slot idle: counts 0, times NaN, no owner, t_prev the loop time
+static int respond_restart(wt_ensemble *h)
+{
+    const int64_t N = h->N;
+    std::vector<double> st((size_t)N * wtrp::ST_DOUBLES, 0.0), rst((size_t)N * wtrp::RST_DOUBLES, 0.0), lt;
+    for (size_t i = 0; i < st.size(); i += wtrp::NRS) {
+        double *q = st.data() + i;
+        q[wtrp::RS_PENDING] = q[wtrp::RS_CLEARING] = q[wtrp::RS_T_FIRST] = q[wtrp::RS_T_ENGAGED] = q[wtrp::RS_T_RELEASED] = NAN;
+    }
+    if (int rc = loop_time(h, lt)) return rc;       // (the download also waits for queued launches)
+    for (int64_t r = 0; r < N; ++r) {
+        double *q = rst.data() + r * wtrp::RST_DOUBLES;
+        q[wtrp::RR_T_PREV] = lt[(size_t)r]; q[wtrp::RR_OWNER_CHLORINE] = q[wtrp::RR_OWNER_ACID] = -1.0;
+    }
+    if (int rc = upload(h, h->rsp.st, st)) return rc;
+    if (int rc = upload(h, h->rsp.rst, rst)) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));   // the host vectors are freed on return
+    return WT_OK;
+}
+
+int wt_ensemble_respond_set(wt_ensemble *h, const double *params)
+{
+    if (!h || !params) return fail(WT_E_ARG, "NULL argument");
+    if (!h->sens.plc_on) return fail(WT_E_STATE, "response programs act on the plant I/O scan: enable plant I/O first");
+    if (!wt::prog_in_item(levels_for(h->n))) return fail(WT_E_STATE, "response programs run in the kernels for up to 32 zones");
+    if (int rc = wt_respond_check(h->N, params)) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still read or write the old records
+    std::vector<double> par((size_t)h->N * wtrp::PAR_DOUBLES);
+    blocks_to_records(params, wtrp::SLOTS, wtrp::NR, h->N, par.data(), wtrp::PAR_DOUBLES);
+    int rc = upload(h, (double *)h->rsp.par, par);
+    if (rc == WT_OK) rc = respond_restart(h);
+    if (rc == WT_OK) rc = sync_checked(h);      // the host vector is freed on return
+    h->rsp.on = rc == WT_OK ? 1 : 0;
+    return rc;
+}
+
+static int respond_ready(wt_ensemble *h)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    if (!h->rsp.on) return fail(WT_E_STATE, k_respond_not_set);
+    HIP_TRY(hipSetDevice(h->device));
+    return WT_OK;
+}
+
+int wt_ensemble_respond_state(wt_ensemble *h, double *state, double *reactor_state)
+{
+    if (int rc = respond_ready(h)) return rc;
+    return download_records(h, {{state, h->rsp.st, wtrp::ST_DOUBLES, wtrp::SLOTS, wtrp::NRS},
+                                {reactor_state, h->rsp.rst, wtrp::RST_DOUBLES, 1, wtrp::NRR}});
+}
+
+int wt_ensemble_respond_params(wt_ensemble *h, double *params)
+{
+    if (int rc = respond_ready(h)) return rc;
+    return download_records(h, {{params, h->rsp.par, wtrp::PAR_DOUBLES, wtrp::SLOTS, wtrp::NR}});
+}
+
+int wt_ensemble_respond_reset(wt_ensemble *h)
+{
+    if (int rc = respond_ready(h)) return rc;
+    if (int rc = respond_restart(h)) return rc;
+    return sync_checked(h);
+}
+
+int wt_ensemble_respond_clear(wt_ensemble *h)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still use the records
+    h->rsp.on = 0;
+    return WT_OK;
+}
+
 int wt_ensemble_sensors_service(wt_ensemble *h, int sensor, int action, int ref_mode, const double *ref, const double *ref2,
                                 const uint8_t *mask)
 {
@@ -3410,6 +3555,7 @@ int wt_ensemble_info(wt_ensemble *h, int what, int64_t *value)
     case WT_INFO_JUNCTION: *value = h->trn.jct.on != 0; break;
     case WT_INFO_INSTALL: *value = h->ins.on != 0; break;
     case WT_INFO_MPC: *value = h->mpc.on != 0; break;
+    case WT_INFO_RESPOND: *value = h->rsp.on != 0; break;
     default: return fail(WT_E_ARG, "unknown info code");
     }
     return WT_OK;

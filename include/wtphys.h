@@ -289,7 +289,8 @@ enum {
     WT_INFO_SERVICE = 22,                 /* a sensor service program is set */
     WT_INFO_TUNE = 23,                    /* a tune program is set */
     WT_INFO_INSTALL = 24,                 /* an installation is set (wt_ensemble_install_set) */
-    WT_INFO_MPC = 25                      /* model predictive controllers are set (wt_ensemble_mpc_set) */
+    WT_INFO_MPC = 25,                     /* model predictive controllers are set (wt_ensemble_mpc_set) */
+    WT_INFO_RESPOND = 26                  /* a response program is set (wt_ensemble_respond_set) */
 };
 int wt_ensemble_info(wt_ensemble *h, int what, int64_t *value);
 
@@ -1246,6 +1247,91 @@ int wt_ensemble_mpc_params(wt_ensemble *h, double *params, double *step, double 
 int wt_ensemble_mpc_reset(wt_ensemble *h);
 /* controllers off (no effect while none is set); the holding words stay */
 int wt_ensemble_mpc_clear(wt_ensemble *h);
+
+/* ---- response programs: the reaction to an alarm, a detection or a bad reading inside fused runs ----
+ * What an operator or a safety PLC does about what the alarm and detector programs noticed: on a cause that has stood
+ * for a reaction time, a slot takes a dosing loop out of automatic, holds or drives its output, and hands the loop back
+ * when the cause is gone.  Up to WT_RSP_SLOTS = 4 slots per reactor, evaluated at every PLC scan of a reactor that
+ * stepped, directly after the tune program and before the model predictive controllers and the PI programs, with their
+ * inputs.  Loop 0 is chlorine (holding words 2-3), loop 1 acid (words 0-1).  It is not a program of wt_program_check:
+ * it has calls of its own, as the model predictive controllers have.
+ * Parameters [WT_RSP_SLOTS][WT_NR][N]: cause (WT_RSP_OFF, _ALARM, _DETECTOR, _BAD), index (the alarm slot, detector slot
+ * or sensor the cause refers to), delay (s the cause must have stood without interruption before the slot engages; 0
+ * engages on the scan that first sees it), loop, action (WT_RSP_HOLD, _MANUAL, _RAMP), value (target output of MANUAL
+ * and RAMP), rate (of a RAMP, per second), latch (1: engaged until reset), clear_delay, min_hold (s), handback
+ * (WT_RSP_BUMP, _BUMPLESS).
+ * State [WT_RSP_SLOTS][WT_NRS][N]: phase (WT_RSP_IDLE, _ENGAGED), pending and clearing (the loop times since which the
+ * cause has stood, or has been clear; NaN: none), output (the forced output), t_first, t_engaged (first and last
+ * engagement), t_released (last release; NaN: never), n_engaged, time_engaged (s), n_owned, n_blocked, n_cause, n_tracked,
+ * n_handback (scans and events); and per reactor [WT_NRR][N]: t_prev, owner_chlorine, owner_acid (the slot that owned the
+ * loop in the last scan, -1: none).  At set and reset: counts 0, times NaN, owners -1, t_prev the loop time.
+ * One scan, slot by slot from 0 to 3, in fp64 without fused multiply-adds (t: the loop time the scan stores;
+ * h = t - t_prev, then t_prev = t; every slot whose cause is not OFF, l its loop):
+ *   1. the cause c.  ALARM: the alarm program is on and its slot `index` is active; DETECTOR: the detector program is on
+ *      and its slot `index` has its alarm set -- both as the previous scan left them, since those programs run later in
+ *      the scan; BAD: this scan's image copy of sensor `index` (after any wire and injection program) is not finite or
+ *      carries a fault code.  A cause whose program is off is false.  if (c) n_cause += 1.
+ *   2. a slot that entered the scan engaged: time_engaged += h.  If latch == 0: if (c) clearing = NaN; else { if clearing
+ *      is NaN, clearing = t; if (t - clearing >= clear_delay && t - t_engaged >= min_hold) the slot releases: phase = 0,
+ *      t_released = t, clearing = NaN, then the hand-back. }
+ *   3. a slot that entered the scan idle: if (!c) pending = NaN; else { if pending is NaN, pending = t;
+ *      if (t - pending >= delay) the slot engages: phase = 1, pending = clearing = NaN, n_engaged += 1, t_first = t if it
+ *      is NaN, t_engaged = t, output = the float32 the loop's holding words decode to (widened to fp64). }  A slot does
+ *      not engage and release, or release and engage, in one scan.
+ *   4. a slot that is engaged now: if the tune program owned loop l in this scan: n_blocked += 1, nothing is written;
+ *      else if a lower slot owns loop l in this scan: output = that slot's output, n_tracked += 1 (a later take-over
+ *      does not bump); else the slot owns the loop: HOLD y = output; MANUAL y = value; RAMP step = rate * h,
+ *      d = value - output, y = d > step ? output + step : d < -step ? output - step : value; then output = y, the loop's
+ *      words = float32(y) (high, low), n_owned += 1.
+ *   Then owner_chlorine / owner_acid = the slot that owned the loop in this scan, -1 for none.
+ * A loop a slot owns is skipped by the model predictive controllers (they count n_skipped) and by the PI programs (no
+ * state change, no word) exactly like a loop a relay experiment has.  An alarm trip still replaces whatever command the
+ * words decode to.  Commands written act from the next scan on.
+ * The hand-back of a releasing BUMPLESS slot that owned its loop in the previous scan, where neither the tune program
+ * nor a lower slot has the loop in this scan: n_handback += 1; if the control program is on and its loop l enabled,
+ * integral = output - (bias + kp * e), e = direction * (setpoint - v) of this scan's reading v as the PI computes it, or
+ * output - bias where that reading is not finite or faulted, so that the PI's output of this same scan continues from
+ * the forced value; an enabled, running model predictive controller of loop l gets its output = output.  Every other
+ * release leaves the controllers as they are.
+ * Needs plant I/O (WT_E_STATE, "response programs act on the plant I/O scan: enable plant I/O first") and n <= 32 zones
+ * ("response programs run in the kernels for up to 32 zones").  set replaces any program and restarts the state; reset
+ * restarts it, which releases latched slots, and keeps the holding words; clear switches the program off and leaves the
+ * words.  state, params and reset give WT_E_STATE, "no response program is set (wt_ensemble_respond_set)", while none
+ * is.  wt_ensemble_plc_enable starts without one; checkpoints carry parameters and state with plant I/O.  All synchronise.
+ * wt_respond_check is the one check of the block, with no handle and no device.  Refused with WT_E_ARG, slot by slot over
+ * the reactors, at the first of the following, each followed by " (slot S, reactor R)": "cause must be 0 (off), 1
+ * (alarm), 2 (detector) or 3 (bad)"; then for a slot that is not off "an ALARM cause's index must be an alarm slot in
+ * 0..3"; "a DETECTOR cause's index must be a detector slot in 0..3"; "a BAD cause's index must be a sensor index in
+ * 0..6"; "loop must be 0 (chlorine) or 1 (acid)"; "action must be 0 (hold), 1 (manual) or 2 (ramp)"; "latch must be 0
+ * or 1"; "handback must be 0 (bump) or 1 (bumpless)"; "delay, clear_delay, min_hold and rate must be >= 0 and not NaN"
+ * (+inf is allowed: a delay never reached); "value must be within 0 and the loop's command limit (1.0 chlorine, 2.0
+ * acid)". */
+#define WT_RSP_SLOTS 4
+enum {
+    WT_RSP_CAUSE = 0, WT_RSP_INDEX = 1, WT_RSP_DELAY = 2, WT_RSP_LOOP = 3, WT_RSP_ACTION = 4, WT_RSP_VALUE = 5,
+    WT_RSP_RATE = 6, WT_RSP_LATCH = 7, WT_RSP_CLEAR_DELAY = 8, WT_RSP_MIN_HOLD = 9, WT_RSP_HANDBACK = 10,
+    WT_NR = 11
+};
+enum {
+    WT_RSPS_PHASE = 0, WT_RSPS_PENDING = 1, WT_RSPS_CLEARING = 2, WT_RSPS_OUTPUT = 3, WT_RSPS_T_FIRST = 4,
+    WT_RSPS_T_ENGAGED = 5, WT_RSPS_T_RELEASED = 6, WT_RSPS_N_ENGAGED = 7, WT_RSPS_TIME_ENGAGED = 8, WT_RSPS_N_OWNED = 9,
+    WT_RSPS_N_BLOCKED = 10, WT_RSPS_N_CAUSE = 11, WT_RSPS_N_TRACKED = 12, WT_RSPS_N_HANDBACK = 13,
+    WT_NRS = 14
+};
+enum { WT_RSPR_T_PREV = 0, WT_RSPR_OWNER_CHLORINE = 1, WT_RSPR_OWNER_ACID = 2, WT_NRR = 3 };
+enum { WT_RSP_OFF = 0, WT_RSP_ALARM = 1, WT_RSP_DETECTOR = 2, WT_RSP_BAD = 3 };
+enum { WT_RSP_HOLD = 0, WT_RSP_MANUAL = 1, WT_RSP_RAMP = 2 };
+enum { WT_RSP_BUMP = 0, WT_RSP_BUMPLESS = 1 };
+enum { WT_RSP_IDLE = 0, WT_RSP_ENGAGED = 1 };
+int wt_respond_check(int64_t n_reactors, const double *params /* [WT_RSP_SLOTS][WT_NR][N] */);
+int wt_ensemble_respond_set(wt_ensemble *h, const double *params);
+/* host [WT_RSP_SLOTS][WT_NRS][N] slot state and [WT_NRR][N] reactor state; each pointer may be NULL (not wanted) */
+int wt_ensemble_respond_state(wt_ensemble *h, double *state, double *reactor_state);
+/* host [WT_RSP_SLOTS][WT_NR][N]: the program in force as set took it */
+int wt_ensemble_respond_params(wt_ensemble *h, double *params);
+int wt_ensemble_respond_reset(wt_ensemble *h);
+/* program off (no effect while none is set); the holding words stay */
+int wt_ensemble_respond_clear(wt_ensemble *h);
 
 /* ---- the parameter checks of the scan programs, the disturbance and the score program, without a handle or a device ----
  * params: host, the block the program's set or enable call takes, for n_reactors reactors (WT_PROG_CONTROL:
