@@ -20,6 +20,8 @@ from .install import Installation, installation_block
 from .tune import TUNE_RULES, LoopTune, RelayTune, TunerState, tune_block
 from .mpc import DMCLoop, LoopMpc, MpcState, dmc_gain, fopdt_step, mpc_block
 from .respond import Response, ResponseState, response_block
+from . import link
+from .link import Link, LinkState, link_block
 from .chemistry import AqueousChemistry, BufferSystem, solve_pH
 from .physics import (ArrheniusParameters, FlowParameters, GeometryParameters, SpatialModel, StratificationParameters,
                       TemperatureDependentKinetics, TransportModel, run_all_validations, validate_chemistry,
@@ -40,6 +42,7 @@ __all__ = ["BoundaryConditions", "EnsembleState", "IntegratedCSTR", "PhysicsEngi
            "RelayTune", "LoopTune", "TunerState", "TUNE_RULES", "tune_block",
            "DMCLoop", "LoopMpc", "MpcState", "dmc_gain", "fopdt_step", "mpc_block",
            "Response", "ResponseState", "response_block",
+           "Link", "LinkState", "link_block", "link",
            "AqueousChemistry", "BufferSystem", "solve_pH", "make_ensemble", "make_boundary_schedule", "params", "sharding", "gather_state", "shard_bounds",
            # the rest of wt_simulator.core's export list (core/__init__.py:238-263)
            "TemperatureDependentKinetics", "ArrheniusParameters", "TransportModel", "GeometryParameters", "FlowParameters",

@@ -23,7 +23,7 @@ WT_OK, WT_E_ARG, WT_E_HIP, WT_E_NOGPU, WT_E_STATE = 0, 1, 2, 3, 4
 (WT_INFO_PLANT_IO, WT_INFO_PROGRAM, WT_INFO_TRAIN, WT_INFO_PIPE, WT_INFO_SENSOR_HISTORY, WT_INFO_DISTURB_HISTORY,
  WT_INFO_SCORE_CURVE, WT_INFO_SCORE_BINS, WT_INFO_TREND_CAPACITY, WT_INFO_TRAIN_LENGTH, WT_INFO_WAVE_DIAG,
  WT_INFO_BOUNDARY_UPLOADS, WT_INFO_WIRE, WT_INFO_MARK, WT_INFO_JUNCTION, WT_INFO_SERVICE, WT_INFO_TUNE, WT_INFO_INSTALL, WT_INFO_MPC,
- WT_INFO_RESPOND) = (0, 1) + tuple(range(9, 27))   # wt_ensemble_info; WT_INFO_PROGRAM + WT_PROG_*: 1..8
+ WT_INFO_RESPOND, WT_INFO_LINK) = (0, 1) + tuple(range(9, 28))   # wt_ensemble_info; WT_INFO_PROGRAM + WT_PROG_*: 1..8
 
 
 class WtError(RuntimeError):
@@ -42,7 +42,7 @@ class SolverStats(C.Structure):
 
 # what libwtphys.so is built from: wtphys.hip and exactly the headers it includes
 # (tests/test_host_api.py::test_build_staleness_list_matches_the_includes)
-BUILD_SOURCES = ("wtphys.hip", "wt_device.hpp", "wt_tables.hpp", "wt_args.hpp", "wt_lanes.hpp", "wt_rhs.hpp", "wt_pcr.hpp", "wt_numjac.hpp", "wt_queue.hpp", "wt_step.hpp", "wt_sensors.hpp", "wt_ins.hpp", "wt_svc.hpp", "wt_plc.hpp", "wt_ctl.hpp", "wt_tun.hpp", "wt_mpc.hpp", "wt_inj.hpp", "wt_alm.hpp", "wt_det.hpp", "wt_rsp.hpp", "wt_trd.hpp", "wt_act.hpp", "wt_dst.hpp", "wt_scr.hpp", "wt_trn.hpp", "wt_wir.hpp", "wt_diag.hpp", "wt_place.hpp", "wt_ckp.hpp")
+BUILD_SOURCES = ("wtphys.hip", "wt_device.hpp", "wt_tables.hpp", "wt_args.hpp", "wt_lanes.hpp", "wt_rhs.hpp", "wt_pcr.hpp", "wt_numjac.hpp", "wt_queue.hpp", "wt_step.hpp", "wt_sensors.hpp", "wt_ins.hpp", "wt_svc.hpp", "wt_plc.hpp", "wt_ctl.hpp", "wt_tun.hpp", "wt_mpc.hpp", "wt_inj.hpp", "wt_lnk.hpp", "wt_alm.hpp", "wt_det.hpp", "wt_rsp.hpp", "wt_trd.hpp", "wt_act.hpp", "wt_dst.hpp", "wt_scr.hpp", "wt_trn.hpp", "wt_wir.hpp", "wt_diag.hpp", "wt_place.hpp", "wt_ckp.hpp")
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
@@ -190,6 +190,13 @@ SIGNATURES = {
     "wt_ensemble_respond_params": [_vp, _dp],
     "wt_ensemble_respond_reset": [_vp],
     "wt_ensemble_respond_clear": [_vp],
+    "wt_link_check": [C.c_int64, _dp],
+    "wt_ensemble_link_set": [_vp, _dp, C.c_uint64],
+    "wt_ensemble_link_state": [_vp, _dp],
+    "wt_ensemble_link_params": [_vp, _dp, C.POINTER(C.c_uint64)],
+    "wt_ensemble_link_ring": [_vp, _dp, _dp, _dp],
+    "wt_ensemble_link_reset": [_vp],
+    "wt_ensemble_link_clear": [_vp],
     "wt_ensemble_install_set": [_vp, _dp],
     "wt_ensemble_install_get": [_vp, _dp],
     "wt_ensemble_install_clear": [_vp],

@@ -18,7 +18,7 @@ from typing import Dict, Iterable, List, Optional, Sequence, Union
 
 import numpy as np
 
-from . import (_native, _program, actuator, alarm, control, detect, disturb, inject, install, junction, mpc, params, respond,
+from . import (_native, _program, actuator, alarm, control, detect, disturb, inject, install, junction, link, mpc, params, respond,
                score, service, train, trend, tune, wire)
 
 logger = logging.getLogger(__name__)
@@ -778,6 +778,46 @@ class ReactorEnsemble:
     def clear_responses(self) -> None:
         """Stop the response program; the holding registers stay as they are and the controllers resume."""
         self._program_call(_native.lib().wt_ensemble_respond_clear)
+
+    # -- link programs at every PLC scan, before the injection programs on both paths, on the device (wt_lnk.hpp)
+    def set_links(self, *links: "link.Link", seed: int = 0) -> None:
+        """Run a link program of up to four :class:`Link` slots at every PLC scan, inside the step call: each slot keeps
+        a ring of the last 64 samples of one reading or command and, inside its window, delivers a delayed sample, the
+        last value that came through (with a timeout into a fail state) or a replayed tape.  Readings are linked after
+        the wire program and before the injection program; commands after the decoding and before the injection
+        program's command slots.  ``seed`` keys the draws of LOSS and jittered DELAY slots.  Replaces any program and
+        restarts state and rings.  Needs :meth:`enable_plant_io` and at most 32 zones per reactor."""
+        block = link.link_block(self.n_reactors, *links)
+        self._program_call(_native.lib().wt_ensemble_link_set, _native.dptr(block), int(seed) & 0xFFFFFFFFFFFFFFFF)
+
+    def link_state(self) -> "link.LinkState":
+        """Counts, the last fresh delivery and the tape mark of every slot, by reactor (one synchronisation)."""
+        st = np.empty((link.SLOTS, link.NLS, self.n_reactors), dtype=np.float64)
+        self._program_call(_native.lib().wt_ensemble_link_state, _native.dptr(st))
+        return link.LinkState.from_block(st)
+
+    def link_params(self) -> np.ndarray:
+        """The (4, 8, N) parameter block of the program in force, as :func:`link_block` built it."""
+        blk = np.empty((link.SLOTS, link.NL, self.n_reactors), dtype=np.float64)
+        self._program_call(_native.lib().wt_ensemble_link_params, _native.dptr(blk), None)
+        return blk
+
+    def link_ring(self):
+        """The rings in recording order: ``(values, faults, n_rec)`` with values and faults (4, 64, N) -- entry k is the
+        k-th oldest sample a ring still holds, NaN and 0 past the ``min(n_rec, 64)`` it has -- and n_rec (4, N)."""
+        n = self.n_reactors
+        v, f = np.empty((link.SLOTS, link.DEPTH, n), dtype=np.float64), np.empty((link.SLOTS, link.DEPTH, n), dtype=np.float64)
+        c = np.empty((link.SLOTS, n), dtype=np.float64)
+        self._program_call(_native.lib().wt_ensemble_link_ring, _native.dptr(v), _native.dptr(f), _native.dptr(c))
+        return v, f, c
+
+    def reset_links(self) -> None:
+        """State and rings as :meth:`set_links` left them; the parameters and the seed stay."""
+        self._program_call(_native.lib().wt_ensemble_link_reset)
+
+    def clear_links(self) -> None:
+        """Stop the link program; readings and commands pass as they are again."""
+        self._program_call(_native.lib().wt_ensemble_link_clear)
 
     # -- injection programs at every PLC scan, on the device (wt_inj.hpp)
     def set_injections(self, *injections: "inject.Injection") -> None:

@@ -12,6 +12,7 @@
 #include "wt_tun.hpp"
 #include "wt_mpc.hpp"
 #include "wt_inj.hpp"
+#include "wt_lnk.hpp"
 #include "wt_alm.hpp"
 #include "wt_det.hpp"
 #include "wt_rsp.hpp"
@@ -85,6 +86,7 @@ struct StepArgs {
     wtu::TunArgs tun;    // per-reactor relay autotune programs run at PLC scans before the PI programs (wt_ensemble_tune_*; tun.on == 0: none)
     wtin::InsArgs ins;   // the installation records of the sensor suite (wt_ensemble_install_*; ins.on == 0: the suite's own build)
     wtrp::RspArgs rsp;   // per-reactor response programs run at PLC scans between the tune program and the controllers (wt_ensemble_respond_*; rsp.on == 0: none)
+    wtl::LnkArgs lnk;    // per-reactor link programs run at PLC scans before the injection programs, on readings and commands (wt_ensemble_link_*; lnk.on == 0: none)
     wtm::MpcArgs mpc;    // per-reactor model predictive controllers run at PLC scans between tune and PI programs (wt_ensemble_mpc_*; mpc.on == 0: none)
 };
 static_assert(sizeof(StepArgs) <= 4096, "the kernel-argument segment holds at most 4 KiB");
@@ -98,7 +100,8 @@ __host__ __device__ constexpr bool x_in_item(int LV) { return LV <= 5; }
 // The train program's feed (wt_trn.hpp) shares the disturbance section; a train of two stages needs n <= 32 anyway,
 // and so does the wire program on top of it (wt_wir.hpp).  The tune program (wt_tun.hpp) is in the same kernels only, and
 // wt_ensemble_tune_set refuses more than 32 zones with the others' wording; so are the model predictive controllers
-// (wt_mpc.hpp) and wt_ensemble_mpc_set, and the response programs (wt_rsp.hpp) and wt_ensemble_respond_set.
+// (wt_mpc.hpp) and wt_ensemble_mpc_set, and the response programs (wt_rsp.hpp) and wt_ensemble_respond_set,
+// and the link programs (wt_lnk.hpp) and wt_ensemble_link_set.
 __host__ __device__ constexpr bool prog_in_item(int LV) { return LV <= 5; }
 enum { Q_AVAIL = 0, Q_HEAD = 1, Q_TAIL = 2, Q_ERROR = 3, Q_TRACE = 4, Q_DONE = 5, Q_WORDS = 16 };
 

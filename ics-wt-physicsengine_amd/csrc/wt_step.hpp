@@ -1022,7 +1022,11 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
                     if (scan) {
                         // an injection program (wave-uniform flag) tampers with this lane's copy of the readings and
                         // with the decoded commands; t is the loop time this scan stores.  Not in the n > 32 kernel.
+                        // a link program (wave-uniform flag) comes first on both paths: what the fieldbus delivers of this
+                        // lane's readings and of the decoded commands is what an injection tampers with (wt_lnk.hpp)
+                        const bool lnk = prog_in_item(LV) && WT_RARE(fresh(pa)->lnk.on);
                         const bool inj = prog_in_item(LV) && WT_RARE(fresh(pa)->inj.on);
+                        if (lnk) wtl::link_sensors(fresh(pa)->lnk, fresh(pa)->sens.reactor_base, rr, &io.val[0][lane], &io.fault[0][lane], wts::RMAX, lt + dt);
                         if (inj) wti::tamper_sensors(fresh(pa)->inj, rr, &io.val[0][lane], &io.fault[0][lane], wts::RMAX, lt + dt);
                         wtp::pack_inputs(b->sens.pack, rr, &io.val[0][lane], &io.fault[0][lane], wts::RMAX, lt);   // update_modbus_inputs
                         double c[3];
@@ -1030,7 +1034,8 @@ __device__ __forceinline__ void run_item(ArgPtr pa, const Lane &L, double *lds, 
                         const bool act = prog_in_item(LV) && WT_RARE(fresh(pa)->act.on);
                         const double row0 = act ? b->sens.cmd.bc[rr] : 0.0;
                         double inlet_v;
-                        if (inj) inlet_v = wtp::apply_commands(b->sens.cmd, rr, c, wti::command_tamper(fresh(pa)->inj, rr, lt + dt));
+                        if (lnk) inlet_v = wtp::apply_commands(b->sens.cmd, rr, c, wtl::link_then_tamper(fresh(pa)->lnk, fresh(pa)->inj, inj, fresh(pa)->sens.reactor_base, rr, lt + dt));
+                        else if (inj) inlet_v = wtp::apply_commands(b->sens.cmd, rr, c, wti::command_tamper(fresh(pa)->inj, rr, lt + dt));
                         else inlet_v = wtp::apply_commands(b->sens.cmd, rr, c);    // read_modbus_commands + apply_boundary_conditions
                         // an alarm program's trips in force (from the previous scan) replace the validated commands
                         if (prog_in_item(LV) && WT_RARE(fresh(pa)->alm.on)) wta::override_commands(fresh(pa)->alm, b->sens.cmd, rr, c);

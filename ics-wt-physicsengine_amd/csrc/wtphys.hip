@@ -130,6 +130,8 @@ struct wt_ensemble {
     wtm::MpcArgs mpc = {};
     // The response programs (wt_rsp.hpp; not programs of k_programs either): plant I/O's arrays and a PLIO scalar.
     wtrp::RspArgs rsp = {};
+    // The link programs (wt_lnk.hpp; not programs of k_programs either): plant I/O's arrays and PLIO scalars.
+    wtl::LnkArgs lnk = {};
     // optional per-launch HIP-event timing (bench.py roofline accounting)
     bool time_launches = false;
     std::vector<hipEvent_t> lt_pool;   // start/stop pairs
@@ -167,7 +169,7 @@ wt::StepArgs make_args(const wt_ensemble *h, double dt, int n_steps, int first_s
     a.trace = h->trace; a.trace_cap = h->trace_cap;
     a.kt = wt::default_ktab(); a.rt = wt::default_rtab();
     a.kt.dense_bias = h->knob_dense ? 1.0 : 0.0;
-    a.sens = h->sens; a.ctl = h->ctl; a.inj = h->inj; a.alm = h->alm; a.act = h->act; a.dst = h->dst; a.scr = h->scr; a.det = h->det; a.trd = h->trd; a.trn = h->trn; a.wir = h->wir; a.tun = h->tun; a.ins = h->ins; a.mpc = h->mpc; a.rsp = h->rsp;
+    a.sens = h->sens; a.ctl = h->ctl; a.inj = h->inj; a.alm = h->alm; a.act = h->act; a.dst = h->dst; a.scr = h->scr; a.det = h->det; a.trd = h->trd; a.trn = h->trn; a.wir = h->wir; a.tun = h->tun; a.ins = h->ins; a.mpc = h->mpc; a.rsp = h->rsp; a.lnk = h->lnk;
     // a full curve takes no more entries: the launches then carry no curve pointer at all
     const bool curve = h->scr.counts && h->scr_steps < h->scr.curve_cap;
     if (!curve) a.scr.counts = nullptr;
@@ -259,8 +261,8 @@ ArrayGroup sensor_arrays(wt_ensemble *h)
             [h] { h->sens.hist_cap = 0; h->sens.svc_on = 0; h->ins.on = 0; }};
 }
 
-// the tune program's records (wt_tun.hpp), the model predictive controllers' arrays (wt_mpc.hpp) and the response
-// programs' records (wt_rsp.hpp) come and go with plant I/O
+// the tune program's records (wt_tun.hpp), the model predictive controllers' arrays (wt_mpc.hpp), the response
+// programs' records (wt_rsp.hpp) and the link programs' records and rings (wt_lnk.hpp) come and go with plant I/O
 ArrayGroup plant_io_arrays(wt_ensemble *h)
 {
     const size_t N = (size_t)h->N;
@@ -277,8 +279,12 @@ ArrayGroup plant_io_arrays(wt_ensemble *h)
                                             {(void **)&h->mpc.pred, sizeof(double) * wtm::ROW_DOUBLES * N},
                                             {(void **)&h->rsp.par, sizeof(double) * wtrp::PAR_DOUBLES * N},
                                             {(void **)&h->rsp.st, sizeof(double) * wtrp::ST_DOUBLES * N},
-                                            {(void **)&h->rsp.rst, sizeof(double) * wtrp::RST_DOUBLES * N}},
-            [h] { h->tun.on = 0; h->mpc.on = 0; h->rsp.on = 0; }};
+                                            {(void **)&h->rsp.rst, sizeof(double) * wtrp::RST_DOUBLES * N},
+                                            {(void **)&h->lnk.par, sizeof(double) * wtl::PAR_DOUBLES * N},
+                                            {(void **)&h->lnk.st, sizeof(double) * wtl::ST_DOUBLES * N},
+                                            {(void **)&h->lnk.ring, sizeof(double) * wtl::RING_ENTRIES * N},
+                                            {(void **)&h->lnk.fring, sizeof(uint8_t) * wtl::RING_ENTRIES * N}},
+            [h] { h->tun.on = 0; h->mpc.on = 0; h->rsp.on = 0; h->lnk.on = 0; }};
 }
 
 ArrayGroup record_arrays(wt_ensemble *h)
@@ -1198,12 +1204,18 @@ int wt_ensemble_plc_enable(wt_ensemble *h)
     if (e == hipSuccess) e = hipMemsetAsync((void *)h->rsp.par, 0, sizeof(double) * wtrp::PAR_DOUBLES * N, h->stream);
     if (e == hipSuccess) e = hipMemsetAsync(h->rsp.st, 0, sizeof(double) * wtrp::ST_DOUBLES * N, h->stream);
     if (e == hipSuccess) e = hipMemsetAsync(h->rsp.rst, 0, sizeof(double) * wtrp::RST_DOUBLES * N, h->stream);
+    // and the link programs' records and rings: every slot off
+    if (e == hipSuccess) e = hipMemsetAsync((void *)h->lnk.par, 0, sizeof(double) * wtl::PAR_DOUBLES * N, h->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(h->lnk.st, 0, sizeof(double) * wtl::ST_DOUBLES * N, h->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(h->lnk.ring, 0, sizeof(double) * wtl::RING_ENTRIES * N, h->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(h->lnk.fring, 0, sizeof(uint8_t) * wtl::RING_ENTRIES * N, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) { release(arrays); return fail(WT_E_HIP, std::string("plc_enable: ") + hipGetErrorString(e)); }
     h->sens.cmd.hr = h->ctl.hr;
     h->tun.on = 0;                               // freshly enabled plant I/O has no tune program
     h->mpc.on = 0;                               // and no model predictive controller
     h->rsp.on = 0;                               // and no response program
+    h->lnk.on = 0; h->lnk.seed_lo = h->lnk.seed_hi = 0;   // and no link program
     h->sens.plc_on = 1;
     return WT_OK;
 }
@@ -2095,7 +2107,8 @@ const Part k_parts[] = {
                             {S_U32, &h->sens.seed_hi, false}, {S_I64, &h->sens.reactor_base, false},
                             {S_I32, &h->sens.svc_on, false}, {S_I32, &h->ins.on, false}}); }, nullptr},   // (the service program's arrays and the installation records are the suite's)
     {"PLIO", plant_io_arrays, 0, [](wt_ensemble *h, Scalars &s) {
-         s.insert(s.end(), {{S_I32, &h->sens.plc_on, true}, {S_I32, &h->tun.on, false}, {S_I32, &h->mpc.on, false}, {S_I32, &h->rsp.on, false}}); }, nullptr},   // (the tune program's, the model predictive controllers' and the response programs' arrays are plant I/O's)
+         s.insert(s.end(), {{S_I32, &h->sens.plc_on, true}, {S_I32, &h->tun.on, false}, {S_I32, &h->mpc.on, false}, {S_I32, &h->rsp.on, false},
+                            {S_I32, &h->lnk.on, false}, {S_U32, &h->lnk.seed_lo, false}, {S_U32, &h->lnk.seed_hi, false}}); }, nullptr},   // (the tune program's, the model predictive controllers', the response programs' and the link programs' arrays are plant I/O's)
     {"RECD", record_arrays, 0, [](wt_ensemble *h, Scalars &s) {
          s.insert(s.end(), {{S_I32, &h->rec.every, false}, {S_I32, &h->rec.cap, true}, {S_I64, &h->rec.steps, false}}); },
      [](const wt_ensemble *h) { return h->rec.cap > 0; }},
@@ -2251,7 +2264,7 @@ const char *config_error(wt_ensemble *u)
     const auto flag = [](int v) { return v == 0 || v == 1; };
     if (!flag(u->sens.on) || !flag(u->sens.plc_on) || !flag(u->ctl.on) || !flag(u->inj.on) || !flag(u->alm.on) || !flag(u->act.on) ||
         !flag(u->dst.on) || !flag(u->scr.on) || !flag(u->det.on) || !flag(u->trn.on) || !flag(u->trn.pipe.on) || !flag(u->trn.jct.on) || !flag(u->wir.on) ||
-        !flag(u->sens.svc_on) || !flag(u->ins.on) || !flag(u->tun.on) || !flag(u->mpc.on) || !flag(u->rsp.on) || !flag(u->trd.on) || !flag(u->trd.wrap))
+        !flag(u->sens.svc_on) || !flag(u->ins.on) || !flag(u->tun.on) || !flag(u->mpc.on) || !flag(u->rsp.on) || !flag(u->lnk.on) || !flag(u->trd.on) || !flag(u->trd.wrap))
         return "range";
     if (u->placement != WT_PLACE_IDENTITY && u->placement != WT_PLACE_ADAPTIVE) return "range";
     if (u->sched_mode != WT_SCHED_STREAMS && u->sched_mode != WT_SCHED_QUEUE) return "range";
@@ -2271,6 +2284,7 @@ const char *config_error(wt_ensemble *u)
     if (u->tun.on && (!u->sens.plc_on || !wt::prog_in_item(levels_for(u->n)))) return "range";
     if (u->mpc.on && (!u->sens.plc_on || !wt::prog_in_item(levels_for(u->n)))) return "range";
     if (u->rsp.on && (!u->sens.plc_on || !wt::prog_in_item(levels_for(u->n)))) return "range";
+    if (u->lnk.on && (!u->sens.plc_on || !wt::prog_in_item(levels_for(u->n)))) return "range";
     return nullptr;
 }
 
@@ -3263,6 +3277,168 @@ int wt_ensemble_respond_clear(wt_ensemble *h)
     return WT_OK;
 }
 
+// ---- link programs (wt_lnk.hpp): not programs of k_programs (a seed beside the block, rings beside the
+// state); their arrays are plant I/O's, as the response programs' are
+
+static_assert(WT_LNK_SLOTS == wtl::SLOTS && WT_LNK_DEPTH == wtl::DEPTH && WT_NL == wtl::NL && WT_NLS == wtl::NLS &&
+              WT_LNK_MODE == wtl::L_MODE && WT_LNK_TARGET == wtl::L_TARGET && WT_LNK_START == wtl::L_START &&
+              WT_LNK_END == wtl::L_END && WT_LNK_A == wtl::L_A && WT_LNK_B == wtl::L_B && WT_LNK_TIMEOUT == wtl::L_TIMEOUT &&
+              WT_LNK_FAIL == wtl::L_FAIL && WT_LNKS_N_REC == wtl::LS_N_REC && WT_LNKS_N_APPLIED == wtl::LS_N_APPLIED &&
+              WT_LNKS_N_FRESH == wtl::LS_N_FRESH && WT_LNKS_N_LOST == wtl::LS_N_LOST && WT_LNKS_N_TIMEOUT == wtl::LS_N_TIMEOUT &&
+              WT_LNKS_N_DRAW == wtl::LS_N_DRAW && WT_LNKS_T_FRESH == wtl::LS_T_FRESH && WT_LNKS_HELD_VALUE == wtl::LS_HELD_VALUE &&
+              WT_LNKS_HELD_FAULT == wtl::LS_HELD_FAULT && WT_LNKS_TAPE_END == wtl::LS_TAPE_END && WT_LNK_OFF == wtl::M_OFF &&
+              WT_LNK_DELAY == wtl::M_DELAY && WT_LNK_LOSS == wtl::M_LOSS && WT_LNK_REPLAY == wtl::M_REPLAY &&
+              WT_INFO_LINK == 27, "link program blocks of the C ABI");
+
+static const char *const k_link_not_set = "no link program is set (wt_ensemble_link_set)";
+
+// one slot of one reactor, rule by rule in the header's order
+static const char *link_rule(const double *c)
+{
+    const double mode = c[WT_LNK_MODE], a = c[WT_LNK_A], b = c[WT_LNK_B], timeout = c[WT_LNK_TIMEOUT], fl = c[WT_LNK_FAIL];
+    if (!whole_in(mode, 0, wtl::N_MODES - 1)) return "mode must be 0 (off), 1 (delay), 2 (loss) or 3 (replay)";
+    if (!whole_in(c[WT_LNK_TARGET], 0, wtl::N_TARGETS - 1)) return "target must be an integer in 0..9";
+    if (!std::isfinite(c[WT_LNK_START]) || std::isnan(c[WT_LNK_END])) return "start must be finite and end a number (end may be +inf)";
+    if (!(c[WT_LNK_START] <= c[WT_LNK_END])) return "start must not exceed end";
+    const bool no_timeout = timeout == INFINITY;
+    if (mode == (double)WT_LNK_OFF) {
+        if (a != 0.0 || b != 0.0 || !no_timeout || fl != 0.0) return "a slot that is off takes no a, b, timeout or fail";
+    } else if (mode == (double)WT_LNK_DELAY) {
+        if (!whole_in(a, 0, wtl::DEPTH - 1) || !whole_in(b, 0, wtl::DEPTH - 1) || a + b > wtl::DEPTH - 1)
+            return "a DELAY slot's delay (a) and jitter (b) must be whole numbers of scans with a + b <= 63";
+        if (!no_timeout || fl != 0.0) return "a DELAY slot takes no timeout or fail";
+    } else if (mode == (double)WT_LNK_LOSS) {
+        if (!(a >= 0.0 && a <= 1.0)) return "a LOSS slot's probability (a) must be within 0 and 1";
+        if (b != 0.0) return "a LOSS slot takes no b";
+        if (!(timeout >= 0.0)) return "a LOSS slot's timeout must be >= 0 or +inf";
+        if (no_timeout) {
+            if (fl != 0.0) return "a LOSS slot without a timeout takes no fail";
+        } else if (c[WT_LNK_TARGET] < (double)wtl::CMD_ACID) {
+            if (!whole_in(fl, 1, 6)) return "a LOSS slot on a reading fails to a fault code (fail) in 1..6";
+        } else if (!std::isfinite(fl)) {
+            return "a LOSS slot on a command fails to a finite value (fail)";
+        }
+    } else {
+        if (!whole_in(a, 1, wtl::DEPTH - 1)) return "a REPLAY slot's tape length (a) must be a whole number of scans in 1..63";
+        if (b != 0.0 || !no_timeout || fl != 0.0) return "a REPLAY slot takes no b, timeout or fail";
+    }
+    return nullptr;
+}
+
+int wt_link_check(int64_t n_reactors, const double *params)
+{
+    if (n_reactors < 1) return fail(WT_E_ARG, "n_reactors must be >= 1");
+    if (!params) return fail(WT_E_ARG, "NULL argument");
+    double c[WT_NL];
+    for (int s = 0; s < WT_LNK_SLOTS; ++s)
+        for (int64_t r = 0; r < n_reactors; ++r) {
+            for (int k = 0; k < WT_NL; ++k) c[k] = params[((int64_t)s * WT_NL + k) * n_reactors + r];
+            if (const char *msg = link_rule(c))
+                return fail(WT_E_ARG, std::string(msg) + " (slot " + std::to_string(s) + ", reactor " + std::to_string(r) + ")");
+        }
+    return WT_OK;
+}
+
+// every slot as set leaves it: counts and held_fault 0, t_fresh, held_value and tape_end NaN, the rings zeroed
+static int link_restart(wt_ensemble *h)
+{
+    const size_t N = (size_t)h->N;
+    std::vector<double> st(N * wtl::ST_DOUBLES, 0.0);
+    for (size_t i = 0; i < st.size(); i += wtl::NLS) {
+        double *q = st.data() + i;
+        q[wtl::LS_T_FRESH] = q[wtl::LS_HELD_VALUE] = q[wtl::LS_TAPE_END] = NAN;
+    }
+    if (int rc = upload(h, h->lnk.st, st)) return rc;
+    HIP_TRY(hipMemsetAsync(h->lnk.ring, 0, sizeof(double) * wtl::RING_ENTRIES * N, h->stream));
+    HIP_TRY(hipMemsetAsync(h->lnk.fring, 0, sizeof(uint8_t) * wtl::RING_ENTRIES * N, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // the host vector is freed on return
+    return WT_OK;
+}
+
+int wt_ensemble_link_set(wt_ensemble *h, const double *params, uint64_t seed)
+{
+    if (!h || !params) return fail(WT_E_ARG, "NULL argument");
+    if (!h->sens.plc_on) return fail(WT_E_STATE, "link programs act on the plant I/O scan: enable plant I/O first");
+    if (!wt::prog_in_item(levels_for(h->n))) return fail(WT_E_STATE, "link programs run in the kernels for up to 32 zones");
+    if (int rc = wt_link_check(h->N, params)) return rc;
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still read or write the old records
+    std::vector<double> par((size_t)h->N * wtl::PAR_DOUBLES);
+    blocks_to_records(params, wtl::SLOTS, wtl::NL, h->N, par.data(), wtl::PAR_DOUBLES);
+    int rc = upload(h, (double *)h->lnk.par, par);
+    if (rc == WT_OK) rc = link_restart(h);
+    if (rc == WT_OK) rc = sync_checked(h);      // the host vector is freed on return
+    h->lnk.seed_lo = (uint32_t)(seed & 0xffffffffu); h->lnk.seed_hi = (uint32_t)(seed >> 32);
+    h->lnk.on = rc == WT_OK ? 1 : 0;
+    return rc;
+}
+
+static int link_ready(wt_ensemble *h)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    if (!h->lnk.on) return fail(WT_E_STATE, k_link_not_set);
+    HIP_TRY(hipSetDevice(h->device));
+    return WT_OK;
+}
+
+int wt_ensemble_link_state(wt_ensemble *h, double *state)
+{
+    if (int rc = link_ready(h)) return rc;
+    return download_records(h, {{state, h->lnk.st, wtl::ST_DOUBLES, wtl::SLOTS, wtl::NLS}});
+}
+
+int wt_ensemble_link_params(wt_ensemble *h, double *params, uint64_t *seed)
+{
+    if (int rc = link_ready(h)) return rc;
+    if (seed) *seed = ((uint64_t)h->lnk.seed_hi << 32) | h->lnk.seed_lo;
+    return download_records(h, {{params, h->lnk.par, wtl::PAR_DOUBLES, wtl::SLOTS, wtl::NL}});
+}
+
+int wt_ensemble_link_ring(wt_ensemble *h, double *values, double *faults, double *n_rec)
+{
+    if (int rc = link_ready(h)) return rc;
+    const int64_t N = h->N;
+    const size_t E = (size_t)N * wtl::RING_ENTRIES;
+    std::vector<double> ring(E), st((size_t)N * wtl::ST_DOUBLES);
+    std::vector<uint8_t> fring(E);
+    if (int rc = download(h, {{ring.data(), h->lnk.ring, sizeof(double) * E}, {fring.data(), h->lnk.fring, sizeof(uint8_t) * E},
+                              {st.data(), h->lnk.st, sizeof(double) * st.size()}})) return rc;
+    // recording order: entry k is the k-th oldest sample the ring still holds; entries past the count are NaN and 0
+    for (int64_t r = 0; r < N; ++r)
+        for (int s = 0; s < wtl::SLOTS; ++s) {
+            const double c = st[(size_t)r * wtl::ST_DOUBLES + s * wtl::NLS + wtl::LS_N_REC];
+            const uint64_t n = (c >= 0.0 && c < 4294967296.0) ? (uint64_t)c : 0;      // wtl::whole
+            const uint64_t kept = n < (uint64_t)wtl::DEPTH ? n : (uint64_t)wtl::DEPTH;
+            const size_t at = ((size_t)r * wtl::SLOTS + s) * wtl::DEPTH;
+            for (int k = 0; k < wtl::DEPTH; ++k) {
+                const size_t o = ((size_t)s * wtl::DEPTH + k) * N + r;
+                const bool have = (uint64_t)k < kept;
+                const size_t i = at + (size_t)((n - kept + k) & (wtl::DEPTH - 1));
+                if (values) values[o] = have ? ring[i] : NAN;
+                if (faults) faults[o] = have ? (double)fring[i] : 0.0;
+            }
+            if (n_rec) n_rec[(size_t)s * N + r] = c;
+        }
+    return WT_OK;
+}
+
+int wt_ensemble_link_reset(wt_ensemble *h)
+{
+    if (int rc = link_ready(h)) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still use the records
+    if (int rc = link_restart(h)) return rc;
+    return sync_checked(h);
+}
+
+int wt_ensemble_link_clear(wt_ensemble *h)
+{
+    if (!h) return fail(WT_E_ARG, "NULL handle");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // queued launches may still use the records
+    h->lnk.on = 0;
+    return WT_OK;
+}
+
 int wt_ensemble_sensors_service(wt_ensemble *h, int sensor, int action, int ref_mode, const double *ref, const double *ref2,
                                 const uint8_t *mask)
 {
@@ -3556,6 +3732,7 @@ int wt_ensemble_info(wt_ensemble *h, int what, int64_t *value)
     case WT_INFO_INSTALL: *value = h->ins.on != 0; break;
     case WT_INFO_MPC: *value = h->mpc.on != 0; break;
     case WT_INFO_RESPOND: *value = h->rsp.on != 0; break;
+    case WT_INFO_LINK: *value = h->lnk.on != 0; break;
     default: return fail(WT_E_ARG, "unknown info code");
     }
     return WT_OK;

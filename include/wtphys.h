@@ -290,7 +290,8 @@ enum {
     WT_INFO_TUNE = 23,                    /* a tune program is set */
     WT_INFO_INSTALL = 24,                 /* an installation is set (wt_ensemble_install_set) */
     WT_INFO_MPC = 25,                     /* model predictive controllers are set (wt_ensemble_mpc_set) */
-    WT_INFO_RESPOND = 26                  /* a response program is set (wt_ensemble_respond_set) */
+    WT_INFO_RESPOND = 26,                 /* a response program is set (wt_ensemble_respond_set) */
+    WT_INFO_LINK = 27                     /* a link program is set (wt_ensemble_link_set) */
 };
 int wt_ensemble_info(wt_ensemble *h, int what, int64_t *value);
 
@@ -1332,6 +1333,89 @@ int wt_ensemble_respond_params(wt_ensemble *h, double *params);
 int wt_ensemble_respond_reset(wt_ensemble *h);
 /* program off (no effect while none is set); the holding words stay */
 int wt_ensemble_respond_clear(wt_ensemble *h);
+
+/* ---- link programs: delay, loss and replay on the plant's I/O inside fused runs ----
+ * What the fieldbus between the plant and its controller does to a signal in time.  Up to WT_LNK_SLOTS = 4 slots per
+ * reactor; a slot sits on one channel -- the injection program's targets with its codes: the seven readings 0..6,
+ * acid_flow_rate 7, chlorine_flow_rate 8, inlet_flow_rate 9 -- keeps a ring of the channel's last WT_LNK_DEPTH = 64
+ * samples and decides at every PLC scan of a reactor that stepped what the receiving end gets.  Reading slots act on
+ * the scan's copy of the readings after the wire program and directly before the injection program's sensor slots: the
+ * input image, the controllers, IMAGE slots of alarms and detectors and the trend tags see the linked value, FIELD slots
+ * and wt_ensemble_sensors_get keep the instrument's own.  Command slots act on the three float32 commands decoded from
+ * the holding words, before the injection program's command slots and the validation; the holding image is not touched.
+ * Slots run in slot order; two slots on one channel chain.  It is not a program of wt_program_check: it has calls of
+ * its own, as the response programs have.
+ * Parameters [WT_LNK_SLOTS][WT_NL][N]: mode (WT_LNK_OFF, _DELAY, _LOSS, _REPLAY), target, start, end (the window
+ * start <= t < end in loop time, t the loop time the scan stores: the injection program's), a, b, timeout, fail.
+ * Defaults: end = +inf, timeout = +inf, the others 0.
+ * State [WT_LNK_SLOTS][WT_NLS][N]: n_rec (samples recorded), n_applied (in-window scans), n_fresh, n_lost, n_timeout,
+ * n_draw, t_fresh (loop time of the last fresh delivery), held_value, held_fault (the last fresh delivery), tape_end
+ * (n_rec when the replay window opened; NaN outside one).  At set and reset: t_fresh, held_value and tape_end NaN,
+ * held_fault and the counts 0, the rings empty.
+ * One scan of one slot on the sample (x, f) of its channel, x a float32 and f its fault code (0 for a command), counts
+ * in fp64:
+ *   1. record: ring[n_rec % 64] = (x, f), n_rec += 1 -- except a REPLAY slot inside its window, whose tape must survive.
+ *      Recording runs from set on, inside and outside the window, whatever the mode.
+ *   2. outside the window (start <= t < end does not hold, or the mode is OFF): (x, f) passes; held = (x, f),
+ *      t_fresh = t, tape_end = NaN.
+ *   3. inside: j = n_applied, n_applied += 1, then
+ *      DELAY (a scans, jitter b scans, both whole, a + b <= 63): d = a where b == 0, else a + floor(u * (b + 1)); the
+ *        sample recorded d scans ago is delivered, ring[max(n_rec - 1 - d, 0) % 64] (the oldest while there are fewer);
+ *        fresh.
+ *      LOSS (probability a in [0, 1], timeout in s or +inf, fail): one draw u per in-window scan; the update is lost iff
+ *        u < a (a = 0 never loses, a = 1 always does).  Not lost: (x, f) is delivered, fresh.  Lost: n_lost += 1; if
+ *        nothing was ever delivered (t_fresh is NaN) the sample passes, fresh; else if t - t_fresh > timeout the fail
+ *        state is delivered and n_timeout += 1 -- a reading becomes NaN with fault code fail (1..6), a command the
+ *        value float32(fail); else held is delivered.
+ *      REPLAY (a = tape length in scans, 1..63): if tape_end is NaN (the window's first scan): if n_rec == 0 this
+ *        sample is recorded first; then tape_end = n_rec.  L = min(a, tape_end), at least 1; in-window scan j delivers
+ *        ring[(tape_end - L + j % L) % 64]; fresh.
+ *      A fresh delivery (y, g) sets held = (y, g), t_fresh = t and n_fresh += 1.
+ *   u is word 0 of Philox4x32-10 on the counter (reactor_base + r, slot, n_draw, 2) with the key (seed & 0xffffffff,
+ *   seed >> 32), times 2^-32 (exact in fp64); reactor_base is the sensor suite's; n_draw += 1 per draw.  DELAY without
+ *   jitter, REPLAY and OFF draw nothing.
+ * A count used as an index is taken as 0 unless it is a number in [0, 2^32), and every ring index is reduced modulo 64
+ * on the device: no restored or edited state addresses outside the ring.  A fault code is kept in a byte.
+ * Needs plant I/O (WT_E_STATE, "link programs act on the plant I/O scan: enable plant I/O first") and n <= 32 zones
+ * ("link programs run in the kernels for up to 32 zones").  set replaces any program and restarts state and rings;
+ * reset restarts them; clear switches the program off.  state, params, ring and reset give WT_E_STATE, "no link program
+ * is set (wt_ensemble_link_set)", while none is.  wt_ensemble_plc_enable starts without one; checkpoints carry
+ * parameters, seed, state and rings with plant I/O.  All synchronise.
+ * wt_link_check is the one check of the block, with no handle and no device.  Refused with WT_E_ARG, slot by slot over
+ * the reactors, at the first of the following, each followed by " (slot S, reactor R)": "mode must be 0 (off), 1
+ * (delay), 2 (loss) or 3 (replay)"; "target must be an integer in 0..9"; "start must be finite and end a number (end may
+ * be +inf)"; "start must not exceed end"; then by mode -- a field a mode does not use must be at its default --
+ * OFF: "a slot that is off takes no a, b, timeout or fail"; DELAY: "a DELAY slot's delay (a) and jitter (b) must be
+ * whole numbers of scans with a + b <= 63", "a DELAY slot takes no timeout or fail"; LOSS: "a LOSS slot's probability (a)
+ * must be within 0 and 1", "a LOSS slot takes no b", "a LOSS slot's timeout must be >= 0 or +inf", and with timeout
+ * +inf "a LOSS slot without a timeout takes no fail", else on a reading "a LOSS slot on a reading fails to a fault code
+ * (fail) in 1..6", on a command "a LOSS slot on a command fails to a finite value (fail)"; REPLAY: "a REPLAY slot's tape
+ * length (a) must be a whole number of scans in 1..63", "a REPLAY slot takes no b, timeout or fail". */
+#define WT_LNK_SLOTS 4
+#define WT_LNK_DEPTH 64
+enum {
+    WT_LNK_MODE = 0, WT_LNK_TARGET = 1, WT_LNK_START = 2, WT_LNK_END = 3, WT_LNK_A = 4, WT_LNK_B = 5, WT_LNK_TIMEOUT = 6,
+    WT_LNK_FAIL = 7,
+    WT_NL = 8
+};
+enum {
+    WT_LNKS_N_REC = 0, WT_LNKS_N_APPLIED = 1, WT_LNKS_N_FRESH = 2, WT_LNKS_N_LOST = 3, WT_LNKS_N_TIMEOUT = 4,
+    WT_LNKS_N_DRAW = 5, WT_LNKS_T_FRESH = 6, WT_LNKS_HELD_VALUE = 7, WT_LNKS_HELD_FAULT = 8, WT_LNKS_TAPE_END = 9,
+    WT_NLS = 10
+};
+enum { WT_LNK_OFF = 0, WT_LNK_DELAY = 1, WT_LNK_LOSS = 2, WT_LNK_REPLAY = 3 };
+int wt_link_check(int64_t n_reactors, const double *params /* [WT_LNK_SLOTS][WT_NL][N] */);
+int wt_ensemble_link_set(wt_ensemble *h, const double *params, uint64_t seed);
+/* host [WT_LNK_SLOTS][WT_NLS][N] */
+int wt_ensemble_link_state(wt_ensemble *h, double *state);
+/* host [WT_LNK_SLOTS][WT_NL][N]: the program in force as set took it, and its seed; each pointer may be NULL */
+int wt_ensemble_link_params(wt_ensemble *h, double *params, uint64_t *seed);
+/* the rings in recording order: values, faults host [WT_LNK_SLOTS][WT_LNK_DEPTH][N], entry k the k-th oldest sample a
+ * ring still holds (min(n_rec, 64) of them; NaN and 0 past those), n_rec host [WT_LNK_SLOTS][N]; each may be NULL */
+int wt_ensemble_link_ring(wt_ensemble *h, double *values, double *faults, double *n_rec);
+int wt_ensemble_link_reset(wt_ensemble *h);
+/* program off (no effect while none is set) */
+int wt_ensemble_link_clear(wt_ensemble *h);
 
 /* ---- the parameter checks of the scan programs, the disturbance and the score program, without a handle or a device ----
  * params: host, the block the program's set or enable call takes, for n_reactors reactors (WT_PROG_CONTROL:
